@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the beam-speculative-decoding hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Metric (BASELINE.json): recommended items/sec + mean accepted length, Llama-68M draft /
@@ -13,7 +13,13 @@ verify rounds), prompts already resident in HBM; `value` = users * K beams / wal
 Users are independent, so N GPUs shard the user list (weak scaling: --steps batches per GPU)
 and exchange only one all-gather of counters at the end.
 
-Extra objects on the JSON line (N = 1; all driver-clocked, all bounded so the default run stays within minutes):
+A plain run does only what the headline needs: it builds the models, runs the W warm-up steps, times the K steps and prints the
+result line (`metric`, `value`, `unit`, `ms_per_step` = wall milliseconds of one timed step, `higher_is_better`, `dtype`, `config`,
+`mean_accept_len`, `per_user`).  --dump-outputs DIR then also writes what the last timed step returned to its callers (see
+dump_outputs); the inputs depend only on the arguments (seeded synthetic weights and prompts), so two builds compare output for output.
+
+--full adds everything else, as extra objects on the JSON line and in bench_detail.json (N = 1 unless noted; all driver-clocked, all
+bounded so the run stays within minutes; the timed steps then also carry the GEMM launch brackets the roofline is built from):
   roofline     — the dominant kernel (the target forward's gate_up projection GEMM), hipEvent-bracketed on its
                  launch stream: algorithmic flops / launch time vs the 2.5 PF dense bf16 MFMA peak when users are
                  batched; verify_scan: the verify step's scan vs 8 TB/s.
@@ -30,6 +36,7 @@ Extra objects on the JSON line (N = 1; all driver-clocked, all bounded so the de
   single_user_stream — the reference's one-user-at-a-time loop (HBM-bound projections).
   cpu_baseline — the oracle (oracle/beamsd_ref.py, torch-CPU fp32) timed on the host cores on a
                  bounded sample of the same workload with the same weights (rank 0, N=1 only).
+  measured_peaks, verify_scan — this box's MFMA / HBM probe figures and the verify step's scan kernel alone (rank 0, any N).
 """
 from __future__ import annotations
 
@@ -58,7 +65,7 @@ MFMA_PEAK_TFLOPS = 2500.0    # same guide: ~2.5 PF dense bf16
 MFMA_FP8_PEAK_TFLOPS = 5000.0    # same guide: ~5 PF dense fp8 (block-scaled v_mfma_scale_f32_*_f8f6f4; the non-scaled fp8 forms run at the bf16 rate)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2, help="timed steps per GPU; a step = one lock-step batch of --streams users")
@@ -88,7 +95,12 @@ def parse():
     ap.add_argument("--sub-steps", type=int, default=2, help="timed batches of each sub-pass (configs 3 / 5, aligned brackets); independent of --steps so the line stays bounded")
     ap.add_argument("--no-configs", action="store_true", help="skip the config 3 / config 5 sub-passes")
     ap.add_argument("--no-latency-curve", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline (roofline, measured peaks, sub-passes, curves, CPU baseline; see the "
+                         "module docstring) and write bench_detail.json; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64; rank 0)")
+    return ap.parse_args(argv)
 
 
 # ------------------------------------------------------------------------------------------------ roofline.traffic provenance
@@ -324,6 +336,46 @@ def emit(detail: dict, out_dir: str = None):
                 break
     print(text, flush=True)
     return text
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 2025
+
+
+def dump_outputs(outs, first_user: int, out_dir: str, budget: int = DUMP_BUDGET_BYTES):
+    """What the timed path returned for the users of its last step, as float64 arrays DIR/<name>.npy (token ids are exact in float64):
+      beam_sequence       [users, K, max(P) + L]  prompt + generated tokens per beam, right-padded with -1 (prompt lengths differ)
+      beam_scores         [users, K]
+      n_run, total_accept_steps, n_target_forwards, n_draft_forwards  [users]
+      accept_steps        [users, max n_run]      accepted draft steps per verification round, padded with -1
+      user_index          [users]                 which users of the run these are
+    Wall-clock fields are left out: they are not outputs of the computation.  Over `budget` bytes in all, a fixed, seeded sample of the users
+    is written.  -> {name: shape}"""
+    n = len(outs)
+    seqs = [o["beam_sequence"].detach().cpu().numpy() for o in outs]
+    K = max(s.shape[0] for s in seqs)
+    T = max(s.shape[1] for s in seqs)
+    R = max([len(o.get("accept_steps", [])) for o in outs] + [1])
+    per_user = 8 * (K * T + K + 5 + R)
+    keep = np.arange(n)
+    if n * per_user > budget:
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, max(1, budget // per_user), replace=False))
+    seq = np.full((len(keep), K, T), -1.0)
+    acc = np.full((len(keep), R), -1.0)
+    for j, u in enumerate(keep):
+        seq[j, :seqs[u].shape[0], :seqs[u].shape[1]] = seqs[u]
+        a = outs[u].get("accept_steps", [])
+        acc[j, :len(a)] = a
+    arrays = dict(beam_sequence=seq,
+                  beam_scores=np.stack([outs[u]["beam_scores"].detach().cpu().to(torch.float64).numpy() for u in keep]),
+                  accept_steps=acc, user_index=(first_user + keep).astype(np.float64))
+    for k in ("n_run", "total_accept_steps", "n_target_forwards", "n_draft_forwards"):
+        arrays[k] = np.array([float(outs[u][k]) for u in keep])
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: v.shape for k, v in arrays.items()}
 
 
 # ------------------------------------------------------------------------------------------------ launch plumbing
@@ -599,7 +651,8 @@ def main():
     run_users(target, draft, dprompts, 0, n_warm, args.streams, fn, args)
     if args.streams > 1:                         # create every decoder / grow the batch buffers outside the timed region
         BSSD_batch(target, draft, dprompts[:args.streams], args.gamma, args.new_tokens, prefix_allowed_tokens_fn=fn)
-    target.profile(1)
+    if args.full:
+        target.profile(1)                        # hipEvent brackets around the GEMMs for the roofline (they keep the target off hipGraph replay)
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
@@ -617,15 +670,17 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    prof_big = target.profile_big()
-    prof = target.profile(0)
-    solo = world == 1                 # auxiliary passes belong to the N = 1 line only
+    if args.dump_outputs and rank == 0:
+        dump_outputs(outs[-ups:], rank * n_local + n_local - ups, args.dump_outputs)
+    prof_big = target.profile_big() if args.full else None
+    prof = target.profile(0) if args.full else None
+    solo = world == 1 and args.full   # auxiliary passes belong to the N = 1 line of a --full run only
     sub_steps = max(1, min(args.sub_steps, args.steps))
     sub_warm = 1 if (args.warmup + args.steps) > sub_steps else 0       # sub-passes reuse the main pass's users: one warm batch if there is room
 
     # ---- measured peaks of THIS box: register-only bf16 MFMA loop on random operands, read-only HBM stream over 2 GiB
     measured = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes as C
         from atspeed_amd import _lib
         lib, tf, gbs = _lib.load(), C.c_double(), C.c_double()
@@ -886,7 +941,7 @@ def main():
             scan["peak_measured"], scan["frac_of_measured"] = measured["hbm_read_gbs"], scan["achieved"] / measured["hbm_read_gbs"]
         return scan
 
-    scan = guarded("verify_scan", scan_pass) if rank == 0 else None
+    scan = guarded("verify_scan", scan_pass) if (rank == 0 and args.full) else None
 
     per_rank = all_gather_counters(Counters(n_timed, n_run, acc, int(elapsed * 1e9)), dev if backend == "nccl" else "cpu")   # the path's single collective
     if rank != 0:
@@ -897,8 +952,10 @@ def main():
     users, t_max, value, mean_accept = agg["users"], agg["elapsed_s"], agg["items_per_s"], agg["mean_accept_len"]
     total_runs = sum(c.n_run for c in per_rank)
 
-    roofline = gemm_roofline(target, prof, prof_big, args.target_fp8, measured, args.streams, True)
-    roofline["target_forward"] = dict(avg_ms_per_user=1e3 * stage[1] / max(1, n_tf), weight_bytes=tdims.n_params_streamed() * 2)
+    roofline = None
+    if args.full:
+        roofline = gemm_roofline(target, prof, prof_big, args.target_fp8, measured, args.streams, True)
+        roofline["target_forward"] = dict(avg_ms_per_user=1e3 * stage[1] / max(1, n_tf), weight_bytes=tdims.n_params_streamed() * 2)
 
     line = {
         "metric": "recommended items/sec (K=20 beams per user), mean accepted length alongside",
@@ -943,9 +1000,12 @@ def main():
             1, sum(o["n_run"] for o in outs[:len(ref_outs)]))
         return cb
 
-    line["cpu_baseline"] = guarded("cpu_baseline", cpu_pass) if (world == 1 and not args.no_cpu_baseline and not args.do_sample) else None
+    line["cpu_baseline"] = guarded("cpu_baseline", cpu_pass) if (solo and not args.no_cpu_baseline and not args.do_sample) else None
     line["sub_pass_errors"] = sub_errors or None
-    emit(line)
+    if args.full:
+        emit(line)
+    else:
+        print(json.dumps(compact_line(line), separators=(",", ":")), flush=True)
     if device_dead:
         raise SystemExit(f"bench.py: device error in sub-pass {device_dead[0]} (line printed above with sub_pass_errors); exiting non-zero")
     if world > 1:

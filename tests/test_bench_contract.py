@@ -259,3 +259,48 @@ def test_gpu_suite_duration_is_within_budget():
     assert seconds <= 600.0, f"the GPU suite took {seconds:.0f} s on the recorded run: over the 600 s budget (driver limit 900 s)"
     durs = [(float(x), name) for x, name in re.findall(r"^([\d.]+)s call\s+(\S+)", text, re.M)]
     assert durs and max(durs)[0] <= 150.0, max(durs)
+
+
+def test_plain_run_is_the_default_and_the_rest_is_behind_full():
+    """`bench.py --gpus 1 --steps N --warmup W` times the headline only; every other measurement needs --full, outputs need --dump-outputs."""
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 3, 2, False, None)
+    a = bench.parse(["--steps", "1", "--warmup", "0", "--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out" and a.steps == 1
+
+
+def _fake_outs(n, K=4, L=3, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    outs = []
+    for u in range(n):
+        P = 5 + u % 3                                                       # prompt lengths differ per user
+        outs.append(dict(beam_sequence=torch.randint(0, 30000, (K, P + L), generator=g), beam_scores=-torch.rand(K, generator=g),
+                         n_run=2 + u % 2, total_accept_steps=u % 3, accept_steps=[u % 3] + [0] * (1 + u % 2) if u % 2 else [u % 3, 0],
+                         n_target_forwards=4, n_draft_forwards=12, time_cost=0.1 * u))
+    return outs
+
+
+def test_dump_outputs_writes_what_the_callers_received(tmp_path):
+    outs = _fake_outs(6)
+    shapes = bench.dump_outputs(outs, 100, str(tmp_path))
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(got) == set(shapes) and "time_cost" not in got
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["user_index"].tolist() == list(range(100, 106))
+    seq = got["beam_sequence"]
+    assert seq.shape == (6, 4, 7 + 3)
+    for u, o in enumerate(outs):
+        w = o["beam_sequence"].shape[1]
+        assert (seq[u, :, :w] == o["beam_sequence"].numpy()).all() and (seq[u, :, w:] == -1).all()
+    np.testing.assert_array_equal(got["beam_scores"], np.stack([o["beam_scores"].double().numpy() for o in outs]))
+    assert got["n_run"].tolist() == [o["n_run"] for o in outs] and got["accept_steps"][1].tolist() == [1, 0, 0]
+
+
+def test_dump_outputs_samples_a_fixed_subset_over_the_budget(tmp_path):
+    outs = _fake_outs(50)
+    bench.dump_outputs(outs, 0, str(tmp_path / "a"), budget=10 * 8 * (4 * 10 + 4 + 5 + 3))
+    bench.dump_outputs(outs, 0, str(tmp_path / "b"), budget=10 * 8 * (4 * 10 + 4 + 5 + 3))
+    a, b = (np.load(tmp_path / d / "user_index.npy") for d in ("a", "b"))
+    assert len(a) == 10 and a.tolist() == b.tolist() == sorted(set(a.tolist()))
+    total = sum(os.path.getsize(p) for p in (tmp_path / "a").glob("*.npy"))
+    assert total < 10 * 8 * (4 * 10 + 4 + 5 + 3) + 10 * 128                # the arrays plus one .npy header each

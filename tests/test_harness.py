@@ -2,8 +2,8 @@
 ranking metrics, on CPU.  Pinned to the REFERENCE: tests/golden/harness_golden.json holds the outputs of the reference's own
 `computeTopNAccuracy` (utils.py:215-271), `SeqRecDataset(mode="test")` (data.py:112-278) and
 `BaseDataset.get_prefix_allowed_tokens_fn` (data.py:84-104), produced by tests/golden/gen_harness_golden.py importing them.
-Facts about the real Beauty / Games files are checked when the data files are present (this container); scikit-learn and
-hand-computed values stay as independent cross-checks of the formulas."""
+Facts about the real Beauty / Games files are checked on the copy of them the tests read (tests/golden/real_data.py); scikit-learn
+and hand-computed values stay as independent cross-checks of the formulas."""
 import json
 import math
 import os
@@ -15,9 +15,14 @@ from atspeed_amd import synth
 from atspeed_amd.harness import (CodeTokenEncoder, InferenceResult, ItemIndex, SeqRecTestData, computeTopNAccuracy,
                                  encode_prompt, load_interactions)
 
-REF_DATA = "/root/reference/data"
-has_ref = os.path.isdir(REF_DATA)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def ref_data(tmp_path_factory):
+    """the reference's Beauty / Games files, written back from tests/golden/real_*.json.xz"""
+    from tests.golden.real_data import materialize
+    return materialize(str(tmp_path_factory.mktemp("ref_data")))
 
 
 @pytest.fixture(scope="module")
@@ -88,11 +93,10 @@ def test_position_set_mask_equals_the_references_closure(gold):
             assert fsm.allowed(fsm.start).tolist() == want
 
 
-@pytest.mark.skipif(not has_ref, reason="reference data files are only in the build container")
 @pytest.mark.parametrize("name", ["beauty", "games"])
-def test_real_splits_equal_the_references(gold, name):
+def test_real_splits_equal_the_references(gold, name, ref_data):
     g = gold["real"][name]
-    d = SeqRecTestData.load(REF_DATA, name)
+    d = SeqRecTestData.load(ref_data, name)
     ix = d.index
     sp = g["split"]
     assert len(d) == sp["n_users"]
@@ -214,26 +218,24 @@ def test_result_metrics_compare_by_code_tuple():
     assert r.counters()["items_per_s"] == 8.0
 
 
-@pytest.mark.skipif(not has_ref, reason="reference data files are only in the build container")
-def test_real_index_files_match_the_survey():
-    b = ItemIndex.load(REF_DATA, "beauty")
+def test_real_index_files_match_the_survey(ref_data):
+    b = ItemIndex.load(ref_data, "beauty")
     assert len(b.indices) == 12035 and len(set(b.item_codes.values())) == 12023 and b.vocab_size == synth.BEAUTY.vocab_size == 32859
     al = b.allowed_tokens()
     assert [(al[i][0], al[i][-1] + 1) for i in range(4)] == [(32000, 32091), (32091, 32347), (32347, 32603), (32603, 32859)] and al[4] == [2]
     assert {i: list(v) for i, v in synth.BEAUTY.allowed_tokens().items()} == al
-    g = ItemIndex.load(REF_DATA, "games")
+    g = ItemIndex.load(ref_data, "games")
     assert len(g.indices) == 17332 and g.vocab_size == synth.GAMES.vocab_size == 33014
     assert len(b.trie()) == 12023
 
 
-@pytest.mark.skipif(not has_ref, reason="reference data files are only in the build container")
-def test_real_test_split_statistics():
-    d = SeqRecTestData.load(REF_DATA, "beauty")
+def test_real_test_split_statistics(ref_data):
+    d = SeqRecTestData.load(ref_data, "beauty")
     assert len(d) == 3553
     H = np.array([len(u.history) for u in d.users])
     assert abs(H.mean() - 7.33) < 0.01 and np.median(H) == 5 and H.max() == 20
-    tr, va, te = load_interactions(REF_DATA, "games")                   # only the sequential_*.txt form exists for Games
-    g = SeqRecTestData(ItemIndex.load(REF_DATA, "games"), tr, va, te)
+    tr, va, te = load_interactions(ref_data, "games")                   # Games through the interaction loader on its own
+    g = SeqRecTestData(ItemIndex.load(ref_data, "games"), tr, va, te)
     assert len(g) == 8696
     ids = encode_prompt(d, d.users[0])
     assert len(ids) == 4 + 5 * len(d.users[0].history) - 1 + 4 + 2 if d.users[0].history else True

@@ -168,13 +168,14 @@ def test_chained_trie_flattens_to_one_automaton_that_answers_like_get(trie_golde
         assert got == sorted(set(exp)), q
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference/data"), reason="reference data files are only in the build container")
-def test_native_trie_flatten_on_the_real_item_tries():
+def test_native_trie_flatten_on_the_real_item_tries(tmp_path):
     """The strict tries of the real Beauty / Games indices (12 023 / 17 289 distinct code tuples, keyed bos + codes + eos as
     inference.py:130 builds them): native CSR == Python flattening; node counts per depth as SURVEY.md 8a row T records."""
     from atspeed_amd.harness import ItemIndex
+    from tests.golden.real_data import materialize
+    data = materialize(str(tmp_path))
     for name, depth_nodes in (("beauty", [91, 6539, 11172, 12023]), ("games", [248, 11317, 16628, 17289])):
-        tr = ItemIndex.load("/root/reference/data", name).trie()
+        tr = ItemIndex.load(data, name).trie()
         fsm = tr.flatten([1])
         assert _same_csr(fsm, ref_flatten(tr.trie_dict, [1]))
         level, counts = [0], []
