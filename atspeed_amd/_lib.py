@@ -61,6 +61,10 @@ SIGNATURES = {
     "atspeed_probe_hbm_read": (C.c_int, [_P, C.c_size_t, _I, _P, _P, _P]),
     "atspeed_llama_enable_fp8": (C.c_int, [_P, _P]),
     "atspeed_llama_fp8_counters": (C.c_int, [_P, _P, _P, _I]),
+    "atspeed_llama_enable_fp4": (C.c_int, [_P, _P]),
+    "atspeed_llama_fp4_counters": (C.c_int, [_P, _P, _P, _I]),
+    "atspeed_quant_weights_mxfp4": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "atspeed_gemm_w4a8": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "atspeed_llama_rope_fused_launches": (C.c_int64, [_P, _I]),
     "atspeed_llama_sk_arena_bytes": (C.c_int64, [_P]),
     "atspeed_quant_rows_fp8": (C.c_int, [_P, _I, _I, _P, _P, _P]),

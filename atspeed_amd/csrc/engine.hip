@@ -254,7 +254,7 @@ struct ActCtx {
   // 20-140 tokens and launch-bound); the segment table lives at a fixed device address so that it is data, not a kernel argument
   SegTable* segtab_dev = nullptr;
   hipStream_t cap_stream = nullptr;
-  typedef std::tuple<int, int, int, int, int, int> GraphKey;      // tokens, logit rows, segments, query tiles, tile rows, fp8
+  typedef std::tuple<int, int, int, int, int, int> GraphKey;      // tokens, logit rows, segments, query tiles, tile rows, weight scheme (0 16-bit, 1 fp8, 2 fp4)
   std::map<GraphKey, hipGraphExec_t> graphs;
   std::map<GraphKey, int> graph_seen;
   // optional per-GEMM hipEvent brackets (bench.py roofline): 0 qkv, 1 o_proj, 2 gate_up, 3 down, 4 lm_head
@@ -274,6 +274,10 @@ struct atspeed_llama {
   // optional fp8 (e4m3, per-output-row scales) copies of the layer projections, library-owned (atspeed_llama_enable_fp8)
   struct Fp8Layer { void *wqkv, *wo, *wgu, *wd; float *sqkv, *so, *sgu, *sd; };
   std::vector<Fp8Layer> fp8;
+  // optional MXFP4 copies (e2m1 nibbles [rows][K / 2] + E8M0 scale bytes [rows][K / 32], gemm.hip "W4A8"), library-owned (atspeed_llama_enable_fp4);
+  // exclusive with fp8
+  struct Fp4Layer { void *wqkv, *wo, *wgu, *wd; void *sqkv, *so, *sgu, *sd; };
+  std::vector<Fp4Layer> fp4;
   KvCache kv0;                                   // cache of the plain atspeed_llama_forward API
   std::vector<KvCache> kv_pool;                  // one more cache per segment of atspeed_llama_forward_batch (grown on demand)
   ActCtx* act;                                   // grown on demand (ensure_act)
@@ -287,6 +291,7 @@ struct atspeed_llama {
   long prof_big_rows[5] = {0, 0, 0, 0, 0};
   // how often each layer projection (0 qkv, 1 o_proj, 2 gate_up, 3 down) ran as an fp8 / as a bf16 (fp32) GEMM (atspeed_llama_fp8_counters)
   long fp8_cnt[4] = {0, 0, 0, 0}, other_cnt[4] = {0, 0, 0, 0};
+  long fp4_cnt[4] = {0, 0, 0, 0};                // the same for the W4A8 projections (atspeed_llama_fp4_counters; `other` is shared)
   long rope_fused_cnt = 0;                       // qkv projections that carried RoPE + the KV scatter in their epilogue (atspeed_llama_rope_fused_launches)
   bool fwd_log_on = false;                       // (tokens, logit rows) of every forward while on (atspeed_llama_forward_log)
   std::vector<int32_t> fwd_log;
@@ -333,6 +338,11 @@ static size_t gemm_ws_for(const atspeed_llama_config& c, int max_tok, int max_ro
       best = std::max(best, ATS_KD(c.dtype, ats_gemm_fp8_workspace_bytes(m, 3 * c.hidden, c.hidden)));
       best = std::max(best, ATS_KD(c.dtype, ats_gemm_fp8_workspace_bytes(m, c.hidden, c.hidden)));
       best = std::max(best, ATS_KD(c.dtype, ats_gemm_fp8_workspace_bytes(m, c.hidden, c.ffn)));
+      // the W4A8 copies (atspeed_llama_enable_fp4): split plans of thin grids (qkv, o_proj, gate_up, down)
+      best = std::max(best, ATS_KD(c.dtype, ats_gemm_w4a8_workspace_bytes(m, 3 * c.hidden, c.hidden)));
+      best = std::max(best, ATS_KD(c.dtype, ats_gemm_w4a8_workspace_bytes(m, c.hidden, c.hidden)));
+      best = std::max(best, ATS_KD(c.dtype, ats_gemm_w4a8_workspace_bytes(m, 2 * c.ffn, c.hidden)));
+      best = std::max(best, ATS_KD(c.dtype, ats_gemm_w4a8_workspace_bytes(m, c.hidden, c.ffn)));
     }
   }
   return best + (1 << 20);
@@ -471,6 +481,7 @@ extern "C" void atspeed_llama_destroy(atspeed_llama* m) {
   for (KvCache& kv : m->kv_pool) kv_free(&kv);
   act_free(m->act);
   for (auto& f : m->fp8) { hipFree(f.wqkv); hipFree(f.wo); hipFree(f.wgu); hipFree(f.wd); hipFree(f.sqkv); hipFree(f.so); hipFree(f.sgu); hipFree(f.sd); }
+  for (auto& f : m->fp4) { hipFree(f.wqkv); hipFree(f.wo); hipFree(f.wgu); hipFree(f.wd); hipFree(f.sqkv); hipFree(f.so); hipFree(f.sgu); hipFree(f.sd); }
   hipFree(m->cos_tab); hipFree(m->sin_tab);
   delete m;
 }
@@ -532,6 +543,16 @@ extern "C" int atspeed_llama_fp8_counters(atspeed_llama* m, int64_t* fp8_out, in
   return ATSPEED_OK;
 }
 
+extern "C" int atspeed_llama_fp4_counters(atspeed_llama* m, int64_t* fp4_out, int64_t* other_out, int32_t reset) {
+  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "fp4_counters: null model");
+  for (int i = 0; i < 4; ++i) {
+    if (fp4_out) fp4_out[i] = m->fp4_cnt[i];
+    if (other_out) other_out[i] = m->other_cnt[i];
+    if (reset) { m->fp4_cnt[i] = 0; m->other_cnt[i] = 0; }
+  }
+  return ATSPEED_OK;
+}
+
 extern "C" int64_t atspeed_llama_rope_fused_launches(atspeed_llama* m, int32_t reset) {
   if (!m) return -1;
   const int64_t n = m->rope_fused_cnt;
@@ -548,6 +569,7 @@ extern "C" int atspeed_llama_enable_fp8(atspeed_llama* m, void* stream) {
   // made from the model's own 16-bit values by the quantisation kernel of its flavour, the activations between the W8A8 projections stay in that type
   ATS_REQUIRE(m->cfg.dtype == ATSPEED_BF16 || m->cfg.dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "enable_fp8: the model must hold bf16 or fp16 weights");
   ATS_REQUIRE(m->cfg.hidden % 256 == 0 && m->cfg.ffn % 256 == 0, ATSPEED_ERR_INVALID, "enable_fp8: hidden and ffn must be multiples of 256");
+  ATS_REQUIRE(m->fp4.empty(), ATSPEED_ERR_INVALID, "enable_fp8: the model already runs the 4-bit target (atspeed_llama_enable_fp4)");
   if (!m->fp8.empty()) return ATSPEED_OK;
   hipStream_t st = (hipStream_t)stream;
   const int H = m->cfg.hidden, F = m->cfg.ffn;
@@ -566,6 +588,38 @@ extern "C" int atspeed_llama_enable_fp8(atspeed_llama* m, void* stream) {
     ATS_TRY(quant(w.wd, H, F, &f.wd, &f.sd));
   }
   ATS_HIP(hipStreamSynchronize(st));
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_llama_enable_fp4(atspeed_llama* m, void* stream) {
+  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "enable_fp4: null model");
+  // the MXFP4 copies are made from the model's own 16-bit values by the quantiser of its flavour (gemm.hip quant_mxfp4_kernel)
+  ATS_REQUIRE(m->cfg.dtype == ATSPEED_BF16 || m->cfg.dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "enable_fp4: the model must hold bf16 or fp16 weights");
+  ATS_REQUIRE(m->cfg.hidden % 256 == 0 && m->cfg.ffn % 256 == 0, ATSPEED_ERR_INVALID, "enable_fp4: hidden and ffn must be multiples of 256");
+  ATS_REQUIRE(m->fp8.empty(), ATSPEED_ERR_INVALID, "enable_fp4: the model already runs the 8-bit target (atspeed_llama_enable_fp8)");
+  if (!m->fp4.empty()) return ATSPEED_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int H = m->cfg.hidden, F = m->cfg.ffn;
+  std::vector<atspeed_llama::Fp4Layer> fp4(m->cfg.n_layers, atspeed_llama::Fp4Layer{});
+  auto free_all = [&]() { for (auto& f : fp4) { hipFree(f.wqkv); hipFree(f.wo); hipFree(f.wgu); hipFree(f.wd); hipFree(f.sqkv); hipFree(f.so); hipFree(f.sgu); hipFree(f.sd); } };
+  auto quant = [&](const void* w, int rows, int cols, void** q, void** sc) -> int {     // 16-bit rows (packed or row-major) -> nibbles + scale bytes
+    if (hipMalloc(q, (size_t)rows * cols / 2) != hipSuccess || hipMalloc(sc, (size_t)rows * cols / 32) != hipSuccess) {
+      atspeed_set_error("enable_fp4: out of device memory for the MXFP4 copies");
+      return ATSPEED_ERR_HIP;
+    }
+    return ATS_KD(m->cfg.dtype, ats_quant_weights_mxfp4(w, rows, cols, *q, *sc, st, m->pk));
+  };
+  for (int l = 0; l < m->cfg.n_layers; ++l) {
+    const atspeed_llama_layer_weights& w = m->layers[l];
+    atspeed_llama::Fp4Layer& f = fp4[l];
+    int rc = quant(w.wqkv, 3 * H, H, &f.wqkv, &f.sqkv);
+    if (rc == ATSPEED_OK) rc = quant(w.wo, H, H, &f.wo, &f.so);
+    if (rc == ATSPEED_OK) rc = quant(w.wgu, 2 * F, H, &f.wgu, &f.sgu);
+    if (rc == ATSPEED_OK) rc = quant(w.wd, H, F, &f.wd, &f.sd);
+    if (rc != ATSPEED_OK) { (void)hipStreamSynchronize(st); free_all(); return rc; }
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) { free_all(); ATS_HIP(hipGetLastError()); return ATSPEED_ERR_HIP; }
+  m->fp4 = std::move(fp4);
   return ATSPEED_OK;
 }
 
@@ -601,7 +655,7 @@ static int llama_forward_segs(atspeed_llama* m, const SegTable& t, float* logits
   const int use_graphs = ats_switch(ATS_SW_GRAPHS);                // (atspeed_set_switch("graphs", 1): the tests compare both modes in one process)
   constexpr int graph_max_tok = 512;
   if (use_graphs && !m->prof_on && logits_out == nullptr && T <= graph_max_tok) {
-    const ActCtx::GraphKey key(T, t.total_logit, t.n, t.n_qtiles, t.qtile_rows, m->fp8.empty() ? 0 : 1);
+    const ActCtx::GraphKey key(T, t.total_logit, t.n, t.n_qtiles, t.qtile_rows, !m->fp4.empty() ? 2 : m->fp8.empty() ? 0 : 1);
     auto it = cx->graphs.find(key);
     if (it == cx->graphs.end() && cx->graphs.size() < 64 && ++cx->graph_seen[key] >= 2) {   // a shape seen twice recurs (K + dl*DK tokens)
       if (!cx->cap_stream) ATS_HIP(hipStreamCreateWithFlags(&cx->cap_stream, hipStreamNonBlocking));

@@ -10,6 +10,44 @@ static int proj_fp8(atspeed_llama* m, const void* x, const void* wq, const float
   return ats_gemm_fp8(cx->xq, cx->sx, wq, sw, out, M, N, K, ldc, epi, st, m->pk, cx->ws, cx->ws_bytes);
 }
 
+// One layer of the 4-bit target (atspeed_llama_enable_fp4): all four projections W4A8 at every size, the activations exactly the W8A8 ones
+// (per-token e4m3 from the fused RMSNorm / residual reduce or ats_quant_rows_fp8).  qkv: plain 16-bit store, then the RoPE / KV pass (the
+// projection rounded to 16 bits, the rotation in fp32).  On entry cx->xq / cx->sx hold the layer's normed input when xq_ready, else cx->xn does.
+static int layer_fp4(atspeed_llama* m, int l, const SegTable& t, const SegTable* dtab, size_t loff, bool& xq_ready, hipStream_t st) {
+  const atspeed_llama_config& c = m->cfg;
+  ActCtx* cx = m->act;
+  const atspeed_llama::Fp4Layer& f = m->fp4[l];
+  const int T = t.total_tok, H = c.hidden, pk = m->pk;
+  const bool q_next = H <= 8192;                           // the fused norm + e4m3 quantisation exists up to hidden 8192
+  { ProfBracket pb(m, 0, T, st);
+    m->fp4_cnt[0]++;
+    if (!xq_ready) ATS_TRY(ats_quant_rows_fp8(cx->xn, T, H, H, cx->xq, cx->sx, st, pk));
+    ATS_TRY(ats_gemm_w4a8(cx->xq, cx->sx, f.wqkv, f.sqkv, cx->qkv, T, 3 * H, H, 3 * H, EPI_STORE, st, pk, cx->ws, cx->ws_bytes)); }
+  ATS_TRY(ats_rope_kv_segs(cx->qkv, t, dtab, m->cos_tab, m->sin_tab, loff, c.n_heads, m->head_dim, c.max_slots, c.dtype, st));
+  ATS_TRY(ats_tree_attention_segs(cx->qkv, 3 * H, t, dtab, loff, m->vis_words, cx->att, H, c.n_heads, m->head_dim, c.dtype, st, 0, pk));
+  { ProfBracket pb(m, 1, T, st);     // h += att Wo^T ; then gate_up's input norm (e4m3 rows + scales, or xn)
+    m->fp4_cnt[1]++;
+    ATS_TRY(ats_quant_rows_fp8(cx->att, T, H, H, cx->xq, cx->sx, st, pk));
+    ATS_TRY(ats_gemm_w4a8_resid_norm(cx->xq, cx->sx, f.wo, f.so, cx->h, T, H, H, H, m->layers[l].post_norm, q_next ? nullptr : cx->xn,
+                                     q_next ? cx->xq : nullptr, q_next ? cx->sx : nullptr, c.rms_eps, cx->ws, cx->ws_bytes, st, pk)); }
+  { ProfBracket pb(m, 2, T, st);
+    m->fp4_cnt[2]++;
+    if (!q_next) ATS_TRY(ats_quant_rows_fp8(cx->xn, T, H, H, cx->xq, cx->sx, st, pk));
+    ATS_TRY(ats_gemm_w4a8(cx->xq, cx->sx, f.wgu, f.sgu, cx->act, T, 2 * c.ffn, H, c.ffn, EPI_SWIGLU, st, pk, cx->ws, cx->ws_bytes)); }
+  { ProfBracket pb(m, 3, T, st);     // h += act Wd^T ; then the next layer's input norm
+    m->fp4_cnt[3]++;
+    ATS_TRY(ats_quant_rows_fp8(cx->act, T, c.ffn, c.ffn, cx->xq, cx->sx, st, pk));
+    if (l + 1 < c.n_layers) {
+      ATS_TRY(ats_gemm_w4a8_resid_norm(cx->xq, cx->sx, f.wd, f.sd, cx->h, T, H, c.ffn, H, m->layers[l + 1].input_norm, q_next ? nullptr : cx->xn,
+                                       q_next ? cx->xq : nullptr, q_next ? cx->sx : nullptr, c.rms_eps, cx->ws, cx->ws_bytes, st, pk));
+      xq_ready = q_next;
+    } else {
+      ATS_TRY(ats_gemm_w4a8(cx->xq, cx->sx, f.wd, f.sd, cx->h, T, H, c.ffn, H, EPI_RESID, st, pk, cx->ws, cx->ws_bytes));
+      xq_ready = false;
+    } }
+  return ATSPEED_OK;
+}
+
 // the launches of one forward (also the body of a captured graph: no allocation, no synchronisation, no staging in here)
 static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTable* dtab, float* logits_out, hipStream_t st,
                               const unsigned char* tile_store) {
@@ -20,7 +58,8 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
   const SkArena* sk = cx->sk.ws ? &cx->sk : nullptr;       // this model's arena for the ring kernel's split-K tail (ordered by this stream alone)
   ATS_TRY(ats_embed_segs(m->embed, t, dtab, cx->h, H, c.vocab_size, dt, st));
   // fp8 projections fed by an RMSNorm take their e4m3 rows + scales straight from the norm kernel (no quantisation pass, no bf16 xn)
-  const bool f8_qkv = !m->fp8.empty() && H <= 8192 && ats_gemm_fp8_applies(T, 3 * H, H, 3 * H, EPI_STORE);
+  const bool f4 = !m->fp4.empty();                         // the 4-bit target: layer_fp4 above
+  const bool f8_qkv = f4 ? H <= 8192 : !m->fp8.empty() && H <= 8192 && ats_gemm_fp8_applies(T, 3 * H, H, 3 * H, EPI_STORE);
   const bool f8_gu = !m->fp8.empty() && H <= 8192 && ats_gemm_fp8_applies(T, 2 * c.ffn, H, c.ffn, EPI_SWIGLU);
   bool xq_ready = false;
   if (f8_qkv) { ATS_TRY(ats_rmsnorm_quant_fp8(cx->h, m->layers[0].input_norm, nullptr, cx->xq, cx->sx, T, H, c.rms_eps, st, pk)); xq_ready = true; }
@@ -28,11 +67,12 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
   // RoPE and the KV scatter ride in the qkv projection's epilogue (one pass over qkv / one launch less per layer): the ring kernels of the batched
   // 16-bit and W8A8 forwards, and since round 6 ONE user's W8A8 projection on the weight-streaming kernel (gemm_wdma_kernel<..., EPI_QKV_ROPE, F8>)
   const bool qkv_in_fp8 = !m->fp8.empty() && ats_gemm_fp8_applies(T, 3 * H, H, 3 * H, EPI_STORE);
-  const bool qkv_rope_fused = qkv_in_fp8 ? ats_gemm_fp8_qkv_rope_applies(T, H, m->head_dim) : ats_gemm_qkv_rope_applies(T, H, m->head_dim, dt);
+  const bool qkv_rope_fused = f4 ? false : qkv_in_fp8 ? ats_gemm_fp8_qkv_rope_applies(T, H, m->head_dim) : ats_gemm_qkv_rope_applies(T, H, m->head_dim, dt);
   if (qkv_rope_fused) ATS_TRY(ats_row_info(t, dtab, cx->rowinfo, c.max_slots, st));
   for (int l = 0; l < c.n_layers; ++l) {
     const atspeed_llama_layer_weights& w = m->layers[l];
     const size_t loff = (size_t)l * m->layer_kv_bytes;
+    if (f4) { ATS_TRY(layer_fp4(m, l, t, dtab, loff, xq_ready, st)); continue; }
     // cx->xn holds rmsnorm(h) * input_norm here (from the embed above or the previous layer's fused down_proj epilogue)
     const bool f8 = !m->fp8.empty();
     const bool fuse_qkv_reduce = ats_switch(ATS_SW_FUSE_QKV_REDUCE) != 0;

@@ -2661,6 +2661,299 @@ int ats_gemm_fp8_qkv_rope(const void* xq, const float* sx, const void* wq, const
 }
 
 
+// =====================================================================================
+// W4A8: OCP MXFP4 weights x the W8A8 form's e4m3 activations (atspeed_llama_enable_fp4).
+//
+// Weight format (ats_quant_weights_mxfp4; INTEGRATION.md "4-bit target"): each row of K is cut into blocks of 32 consecutive k.  A block has one
+// E8M0 scale byte 127 + X, X = clamp(floor(log2(amax)) - 2, -127, 127) (OCP MX v1.0; 2 = e2m1's emax), and 32 elements e2m1(v / 2^X) rounded to
+// nearest on {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to the even mantissa (.25 -> 0, .75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4),
+// saturating at 6; a value that rounds to 0 is +0 (code 0), an all-zero block has byte 0 and zero elements.  Codes: bit 3 sign, 0..7 = the
+// grid in order.  Storage: row-major [rows][K / 2] bytes, element k in byte k / 2, LOW nibble = even k -- every row is whole 128-byte lines,
+// 256 k per line -- and a row-major [rows][K / 32] table of scale bytes.
+//
+// MFMA operand maps (tools/probe/mx4_probe.hip, v_mfma_scale_f32_16x16x128_f8f6f4, cbsz = 4: e2m1 A, blgp = 0: e4m3 B): an e2m1 lane l holds row
+// l & 15 in 16 bytes with the hardware's own k order, and byte 0 of its scale VGPR (opsel 0) scales exactly its 32 elements.  Putting OCP block g
+// of a 128-k step (16 contiguous bytes of the weight row) in lane group g = l >> 4 therefore gives each lane one scale block, and the e4m3
+// operand of lane group g must then take the 16-byte chunks g and 4 + g of the step's 128 activation bytes -- the F8 form's chunk order
+// (gemm_wdma_kernel<..., F8>), here a requirement of the FP4 k order rather than a bank-conflict choice.  The token scale multiplies the fp32
+// accumulator (B scale unit), as in the F8 form; every e4m3 x (e2m1 2^X) product is exact in fp32.
+//
+// Kernel: C^T[n][m] = sum_k W[n][k] X[m][k].  4 waves, 2 along the weight rows (32 rows each: two 16-row A tiles) x 2 along the tokens (16 MI
+// tokens each); a workgroup owns 64 weight rows x 32 MI tokens, the grid is (N / 64, K-split parts, M / (32 MI)) -- it tiles M, so every forward
+// size runs W4A8, lock-step batches of 10^5 tokens included.  Operands go global -> VGPR (no LDS): a k-tile of 256 k is one 128-byte line per
+// weight row (two 64-byte MFMA steps) and two per token row; latency is hidden by occupancy, not by a ring.  SPLIT: part z of the grid's y takes
+// 256-k tiles z * n / parts .. (z + 1) * n / parts and stores scaled fp32 slabs [z][M][N] for the W8A8 path's reduce kernels; otherwise the
+// epilogue (store / fp32 / residual / SwiGLU) is applied in the kernel.  Vector stores only.
+typedef int i32x8_w4_t __attribute__((ext_vector_type(8)));
+template <int MI, int EPI, bool SPLIT>
+__global__ __launch_bounds__(256) void gemm_w4a8_kernel(const unsigned char* __restrict__ X, const float* __restrict__ sx, const unsigned char* __restrict__ W,
+                                                        const unsigned char* __restrict__ S, void* __restrict__ Cv, int M, int N, int K, int ldc, int pk,
+                                                        int n_split) {
+  constexpr int NI = 2;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wn = wave & 1, wm = wave >> 1, lq = lane & 15, g = lane >> 4;
+  const int nw = blockIdx.x * 64 + wn * 32;                            // this wave's first weight row
+  const int mw = blockIdx.z * (32 * MI) + wm * (16 * MI);              // this wave's first token row
+  int kt0 = 0, n_kt = K / 256;
+  if constexpr (SPLIT) {
+    const int all = n_kt, z = blockIdx.y;
+    kt0 = (int)((long long)z * all / n_split);
+    n_kt = (int)((long long)(z + 1) * all / n_split) - kt0;
+  }
+  const size_t wrow = (size_t)K / 2, srow = (size_t)K / 32;
+  const unsigned char* wp[NI];
+  const unsigned char* sp[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const size_t r = (size_t)min(nw + i * 16 + lq, N - 1);
+    wp[i] = W + r * wrow + (size_t)kt0 * 128 + g * 16;                 // OCP block g of each 128-k step
+    sp[i] = S + r * srow + (size_t)kt0 * 8 + g;
+  }
+  const unsigned char* xp[MI];
+  const size_t xstep = pk ? 256 : 128;                                 // bytes from one 128-k step of a token row to the next
+#pragma unroll
+  for (int j = 0; j < MI; ++j) {
+    const size_t r = (size_t)min(mw + j * 16 + lq, M - 1);
+    xp[j] = X + (pk ? ats_pk_byte(r, (size_t)g * 16, K) : r * K + g * 16) + (size_t)kt0 * 2 * xstep;
+  }
+  const size_t xhi = pk ? 128 : 64;                                    // chunk 4 + g, 64 bytes of k further
+
+  f32x4_t acc[NI][MI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int j = 0; j < MI; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  for (int kt = 0; kt < n_kt; ++kt) {
+    u32x4_t wv[2][NI], xlo[2][MI], xhv[2][MI];
+    int sv[2][NI];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        wv[s][i] = *reinterpret_cast<const u32x4_t*>(wp[i] + (size_t)kt * 128 + s * 64);
+        sv[s][i] = sp[i][(size_t)kt * 8 + s * 4];
+      }
+#pragma unroll
+      for (int j = 0; j < MI; ++j) {
+        const unsigned char* p = xp[j] + ((size_t)kt * 2 + s) * xstep;
+        xlo[s][j] = *reinterpret_cast<const u32x4_t*>(p);
+        xhv[s][j] = *reinterpret_cast<const u32x4_t*>(p + xhi);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        const i32x8_w4_t a = {(int)wv[s][i][0], (int)wv[s][i][1], (int)wv[s][i][2], (int)wv[s][i][3], 0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < MI; ++j) {
+          const i32x8_w4_t b = {(int)xlo[s][j][0], (int)xlo[s][j][1], (int)xlo[s][j][2], (int)xlo[s][j][3],
+                                (int)xhv[s][j][0], (int)xhv[s][j][1], (int)xhv[s][j][2], (int)xhv[s][j][3]};
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc[i][j], 4, 0, 0, sv[s][i], 0, 0x7f7f7f7f);
+        }
+      }
+  }
+
+  // epilogue: acc[i][j][r] = C[m][n], m = mw + 16 j + lq (token), n = nw + 16 i + 4 g + r (weight row); the token scale first
+#pragma unroll
+  for (int j = 0; j < MI; ++j) {
+    const int gm = mw + j * 16 + lq;
+    if (gm >= M) continue;
+    const float fx = sx[gm];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[i][j][r] *= fx;
+    if constexpr (SPLIT || EPI == EPI_F32) {
+      float* C = SPLIT ? reinterpret_cast<float*>(Cv) + (size_t)blockIdx.y * M * N + (size_t)gm * N : reinterpret_cast<float*>(Cv) + (size_t)gm * ldc;
+      const int ld = SPLIT ? N : ldc;
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        const int gn = nw + i * 16 + g * 4;
+        if (gn >= N) continue;
+        if (gn + 3 < N && (ld & 3) == 0) *reinterpret_cast<float4*>(C + gn) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+        else
+#pragma unroll
+          for (int r = 0; r < 4; ++r) if (gn + r < N) C[gn + r] = acc[i][j][r];
+      }
+    } else if constexpr (EPI == EPI_SWIGLU) {                          // gate rows 32b .. 32b+15, up rows 32b+16 .. 32b+31 (the packed gate_up order)
+      bf16_t* C = reinterpret_cast<bf16_t*>(Cv);
+      if (nw + 16 >= N) continue;                                      // N % 32 == 0: the whole (gate, up) group is inside N or not at all
+      uint32_t o[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const uint32_t gp = f2bf_pk(acc[0][j][2 * h], acc[0][j][2 * h + 1]), up = f2bf_pk(acc[1][j][2 * h], acc[1][j][2 * h + 1]);
+        o[h] = f2bf_pk(ats_silu<false>(bf_lo(gp)) * bf_lo(up), ats_silu<false>(bf_hi(gp)) * bf_hi(up));
+      }
+      *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (nw >> 1) + g * 4, ldc)) = make_uint2(o[0], o[1]);
+    } else {
+      static_assert(EPI == EPI_STORE || EPI == EPI_RESID, "store / fp32 / residual / SwiGLU");
+      bf16_t* C = reinterpret_cast<bf16_t*>(Cv) + (size_t)gm * ldc;
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        const int gn = nw + i * 16 + g * 4;
+        if (gn >= N) continue;
+        float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+        const bool vec = gn + 3 < N && (ldc & 3) == 0;
+        if constexpr (EPI == EPI_RESID) {                              // h = round(h + round(proj)): the ring kernel's residual numerics
+          if (vec) {
+            const uint2 hv = *reinterpret_cast<const uint2*>(C + gn);
+            v[0] = bf_lo(hv.x) + bf2f(f2bf(v[0])); v[1] = bf_hi(hv.x) + bf2f(f2bf(v[1]));
+            v[2] = bf_lo(hv.y) + bf2f(f2bf(v[2])); v[3] = bf_hi(hv.y) + bf2f(f2bf(v[3]));
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (gn + r < N) v[r] = bf2f(C[gn + r]) + bf2f(f2bf(v[r]));
+          }
+        }
+        if (vec) *reinterpret_cast<uint2*>(C + gn) = make_uint2(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]));
+        else
+#pragma unroll
+          for (int r = 0; r < 4; ++r) if (gn + r < N) C[gn + r] = f2bf(v[r]);
+      }
+    }
+  }
+}
+
+// 16-bit weights (packed operand layout when pk, else row-major) -> MXFP4 (format above).  One thread per (row, 128 k): four blocks, 64 bytes of
+// nibbles (four 16-byte stores) and one 32-bit word of scale bytes.
+__device__ __forceinline__ uint32_t mxfp4_code(float y) {              // y already divided by the block scale; RNE on the e2m1 grid, saturating
+  const float a = fabsf(y);
+  const uint32_t c = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) + (uint32_t)(a > 2.5f) +
+                     (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.f);
+  return c == 0 ? 0u : (c | (y < 0.f ? 8u : 0u));
+}
+__global__ __launch_bounds__(256) void quant_mxfp4_kernel(const bf16_t* __restrict__ w, unsigned char* __restrict__ q, unsigned char* __restrict__ sc,
+                                                          int rows, int K, int pk) {
+  const int per_row = K / 128;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)rows * per_row) return;
+  const int r = (int)(idx / per_row), c = (int)(idx % per_row);
+  uint32_t sw = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int k0 = c * 128 + b * 32;
+    const bf16_t* src = w + ats_opnd_idx<2>(pk, r, k0, K);            // 32 elements = 64 contiguous bytes in either layout
+    float v[32];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const u32x4_t p = *reinterpret_cast<const u32x4_t*>(src + u * 8);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { v[u * 8 + 2 * e] = bf_lo(p[e]); v[u * 8 + 2 * e + 1] = bf_hi(p[e]); }
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int e = 0; e < 32; ++e) amax = fmaxf(amax, fabsf(v[e]));
+    uint32_t byte = 0;
+    u32x4_t out = {0u, 0u, 0u, 0u};
+    if (amax > 0.f) {
+      int ex;
+      (void)frexpf(amax, &ex);                                         // amax = f 2^ex, f in [0.5, 1): floor(log2(amax)) = ex - 1
+      const int X = min(max(ex - 1 - 2, -127), 127);
+      byte = (uint32_t)(127 + X);
+#pragma unroll
+      for (int e = 0; e < 32; ++e) out[e >> 3] |= mxfp4_code(ldexpf(v[e], -X)) << ((e & 7) * 4);
+    }
+    sw |= byte << (8 * b);
+    *reinterpret_cast<u32x4_t*>(q + (size_t)r * (K / 2) + k0 / 2) = out;
+  }
+  *reinterpret_cast<uint32_t*>(sc + (size_t)r * (K / 32) + c * 4) = sw;
+}
+
+int ats_quant_weights_mxfp4(const void* w, int rows, int k, void* q, void* scales, hipStream_t st, int pk) {
+  ATS_REQUIRE(w && q && scales && rows >= 1 && k >= 256 && k % 256 == 0, ATSPEED_ERR_INVALID, "quant_weights_mxfp4: bad arguments (K=%d must be a multiple of 256)", k);
+  ATS_REQUIRE((((uintptr_t)w | (uintptr_t)q) & 15) == 0 && ((uintptr_t)scales & 3) == 0, ATSPEED_ERR_INVALID, "quant_weights_mxfp4: unaligned buffer");
+  const long long threads = (long long)rows * (k / 128);
+  hipLaunchKernelGGL(quant_mxfp4_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, (const bf16_t*)w, (unsigned char*)q,
+                     (unsigned char*)scales, rows, k, pk);
+  ATS_LAUNCH_CHECK();
+  return ATSPEED_OK;
+}
+
+// tokens per workgroup: 32 MI (MI = 1 / 2 / 4); K-split parts: until tiles x parts reach two workgroups per CU, at least 4 tiles (1024 k) a part
+static int w4a8_mi(int m) { return m <= 32 ? 1 : m <= 64 ? 2 : 4; }
+static int w4a8_split_count(int m, int n, int k) {
+  const int tiles = ((n + 63) / 64) * ((m + 32 * w4a8_mi(m) - 1) / (32 * w4a8_mi(m))), n_kt = k / 256;
+  if (tiles >= 256) return 1;
+  return std::max(1, std::min(512 / tiles, n_kt / 4));
+}
+size_t ats_gemm_w4a8_workspace_bytes(int m, int n, int k) {
+  if (m < 1 || k % 256 != 0) return 0;
+  const int s_ = w4a8_split_count(m, n, k);
+  return s_ > 1 ? (size_t)s_ * m * n * sizeof(float) : 0;
+}
+template <int MI, int EPI, bool SPLIT>
+static int launch_w4a8_mi(const unsigned char* xq, const float* sx, const unsigned char* wq, const unsigned char* wsc, void* c, int m, int n, int k,
+                          int ldc, int splits, hipStream_t st, int pk) {
+  hipLaunchKernelGGL((gemm_w4a8_kernel<MI, EPI, SPLIT>), dim3((n + 63) / 64, SPLIT ? splits : 1, (m + 32 * MI - 1) / (32 * MI)), dim3(256), 0, st,
+                     xq, sx, wq, wsc, c, m, n, k, ldc, pk, splits);
+  ATS_LAUNCH_CHECK();
+  return ATSPEED_OK;
+}
+template <int EPI, bool SPLIT>
+static int launch_w4a8(const unsigned char* xq, const float* sx, const unsigned char* wq, const unsigned char* wsc, void* c, int m, int n, int k,
+                       int ldc, int splits, hipStream_t st, int pk) {
+  switch (w4a8_mi(m)) {
+    case 1:  return launch_w4a8_mi<1, EPI, SPLIT>(xq, sx, wq, wsc, c, m, n, k, ldc, splits, st, pk);
+    case 2:  return launch_w4a8_mi<2, EPI, SPLIT>(xq, sx, wq, wsc, c, m, n, k, ldc, splits, st, pk);
+    default: return launch_w4a8_mi<4, EPI, SPLIT>(xq, sx, wq, wsc, c, m, n, k, ldc, splits, st, pk);
+  }
+}
+static int w4a8_check(const void* xq, const float* sx, const void* wq, const void* wsc, void* c, int m, int n, int k, int ldc, int epilogue) {
+  ATS_REQUIRE(xq && sx && wq && wsc && c, ATSPEED_ERR_INVALID, "gemm_w4a8: null argument");
+  ATS_REQUIRE(m >= 1 && n >= 1 && k >= 256 && k % 256 == 0, ATSPEED_ERR_INVALID, "gemm_w4a8: %d x %d x %d (K must be a multiple of 256)", m, n, k);
+  ATS_REQUIRE((((uintptr_t)xq | (uintptr_t)wq) & 15) == 0, ATSPEED_ERR_INVALID, "gemm_w4a8: operands must be 16-byte aligned");
+  ATS_REQUIRE(epilogue != EPI_SWIGLU || ((ldc & 3) == 0 && n % 32 == 0), ATSPEED_ERR_INVALID, "gemm_w4a8: SwiGLU needs N %% 32 == 0 and ldc %% 4 == 0");
+  ATS_REQUIRE(epilogue == EPI_STORE || epilogue == EPI_F32 || epilogue == EPI_RESID || epilogue == EPI_SWIGLU, ATSPEED_ERR_INVALID,
+              "gemm_w4a8: unknown epilogue %d", epilogue);
+  return ATSPEED_OK;
+}
+
+// c (epilogue) x W^T with MXFP4 weights (wq, wsc) and e4m3 activations (xq, per-token sx): split into scaled fp32 slabs + the W8A8 reduce where the
+// grid is thin and `ws` holds them, else the epilogue in the kernel
+int ats_gemm_w4a8(const void* xq, const float* sx, const void* wq, const void* wsc, void* c, int m, int n, int k, int ldc, int epilogue,
+                  hipStream_t st, int pk, void* ws, size_t ws_bytes) {
+  ATS_TRY(w4a8_check(xq, sx, wq, wsc, c, m, n, k, ldc, epilogue));
+  const unsigned char *X = (const unsigned char*)xq, *Wq = (const unsigned char*)wq, *Sc = (const unsigned char*)wsc;
+  const int s_ = w4a8_split_count(m, n, k);
+  ats_count_path(ATS_PATH_FP4);
+  if (s_ > 1 && wdma8_ws_ok(m, n, s_, ws, ws_bytes) && (n % 4) == 0) {
+    ATS_TRY((launch_w4a8<EPI_F32, true>(X, sx, Wq, Sc, ws, m, n, k, n, s_, st, pk)));
+    switch (epilogue) {
+      case EPI_STORE:  return reduce_splits<bf16_t, EPI_STORE>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
+      case EPI_F32:    return reduce_splits<bf16_t, EPI_F32>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
+      case EPI_RESID:  return reduce_splits<bf16_t, EPI_RESID>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
+      default:         return reduce_splits<bf16_t, EPI_SWIGLU>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
+    }
+  }
+  switch (epilogue) {
+    case EPI_STORE:  return launch_w4a8<EPI_STORE, false>(X, sx, Wq, Sc, c, m, n, k, ldc, 1, st, pk);
+    case EPI_F32:    return launch_w4a8<EPI_F32, false>(X, sx, Wq, Sc, c, m, n, k, ldc, 1, st, pk);
+    case EPI_RESID:  return launch_w4a8<EPI_RESID, false>(X, sx, Wq, Sc, c, m, n, k, ldc, 1, st, pk);
+    default:         return launch_w4a8<EPI_SWIGLU, false>(X, sx, Wq, Sc, c, m, n, k, ldc, 1, st, pk);
+  }
+}
+
+// h += xq W^T (W4A8), then the next op's input norm (xn and / or e4m3 rows + scales): the W8A8 form's fused reduce / residual / norm /
+// quantisation pass on the slabs where the grid is split, else the kernel's residual epilogue followed by the norm kernels
+int ats_gemm_w4a8_resid_norm(const void* xq, const float* sx, const void* wq, const void* wsc, void* h, int m, int n, int k, int ldh,
+                             const void* norm_w, void* xn, void* q_out, float* s_out, float eps, void* ws, size_t ws_bytes, hipStream_t st, int pk) {
+  ATS_REQUIRE(xn || (q_out && s_out), ATSPEED_ERR_INVALID, "gemm_w4a8_resid_norm: no output for the norm");
+  ATS_REQUIRE(norm_w, ATSPEED_ERR_INVALID, "gemm_w4a8_resid_norm: null norm weight");
+  ATS_TRY(w4a8_check(xq, sx, wq, wsc, h, m, n, k, ldh, EPI_RESID));
+  const int s_ = w4a8_split_count(m, n, k);
+  if (s_ > 1 && wdma8_ws_ok(m, n, s_, ws, ws_bytes) && n <= 8192 && (n % 4) == 0 && (ldh % 4) == 0) {
+    ats_count_path(ATS_PATH_FP4);
+    ATS_TRY((launch_w4a8<EPI_F32, true>((const unsigned char*)xq, sx, (const unsigned char*)wq, (const unsigned char*)wsc, ws, m, n, k, n, s_, st, pk)));
+    FusedNorm fn{norm_w, xn, eps, false, q_out, s_out};
+    ATS_TRY((reduce_splits<bf16_t, EPI_RESID>((const float*)ws, h, m, n, ldh, s_, st, &fn, pk)));
+    if (fn.done) return ATSPEED_OK;
+  } else {
+    ATS_TRY(ats_gemm_w4a8(xq, sx, wq, wsc, h, m, n, k, ldh, EPI_RESID, st, pk, nullptr, 0));
+  }
+  return q_out ? ats_rmsnorm_quant_fp8(h, norm_w, xn, q_out, s_out, m, n, eps, st, pk) : ats_rmsnorm(h, norm_w, xn, m, n, eps, ATS_HALF, st, pk);
+}
+
+
 
 // the same GEMMs on operands in the packed layout (what the bf16 / fp8 engine runs; atspeed_pack_rows makes them): a, w packed;
 // the SwiGLU epilogue's output packed too (it is the down projection's operand), every other output row-major
@@ -2682,6 +2975,17 @@ extern "C" int atspeed_gemm(const void* a, const void* w, void* c, int32_t m, in
 extern "C" int atspeed_gemm_packed(const void* a, const void* w, void* c, int32_t m, int32_t n, int32_t k, int32_t ldc, int32_t epilogue,
                                    void* workspace, size_t workspace_bytes, void* stream) {
   return ats_bf16::ats_gemm(a, w, c, m, n, k, k, ldc, ATSPEED_BF16, epilogue, workspace, workspace_bytes, (hipStream_t)stream, 1, nullptr);
+}
+
+extern "C" int atspeed_quant_weights_mxfp4(const void* w, int32_t rows, int32_t k, int32_t dtype, int32_t packed, void* q, void* scales, void* stream) {
+  ATS_REQUIRE(dtype == ATSPEED_BF16 || dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "quant_weights_mxfp4: dtype must be bf16 or fp16");
+  return ATS_KD(dtype, ats_quant_weights_mxfp4(w, rows, k, q, scales, (hipStream_t)stream, packed ? 1 : 0));
+}
+
+extern "C" int atspeed_gemm_w4a8(const void* xq, const float* sx, const void* wq, const void* wsc, void* c, int32_t m, int32_t n, int32_t k,
+                                 int32_t ldc, int32_t epilogue, int32_t dtype, int32_t packed, void* workspace, size_t workspace_bytes, void* stream) {
+  ATS_REQUIRE(dtype == ATSPEED_BF16 || dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "gemm_w4a8: dtype must be bf16 or fp16");
+  return ATS_KD(dtype, ats_gemm_w4a8(xq, sx, wq, wsc, c, m, n, k, ldc, epilogue, (hipStream_t)stream, packed ? 1 : 0, workspace, workspace_bytes));
 }
 
 extern "C" int atspeed_gemm_fp8_packed(const void* xq, const float* sx, const void* wq, const float* sw, void* c, int32_t m, int32_t n,

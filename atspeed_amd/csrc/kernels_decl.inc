@@ -57,6 +57,15 @@ int ats_gemm_fp8_partials(const void* xq, const float* sx, const void* wq, const
 int ats_gemm_fp8_resid_norm(const void* xq, const float* sx, const void* wq, const float* sw, void* h, int m, int n, int k, int ldh,
                             const void* norm_w, void* xn, void* q_out, float* s_out, float eps, void* ws, size_t ws_bytes, hipStream_t st, int pk = 0);
 
+// W4A8 (OCP MXFP4 weights, e4m3 activations with per-token scales; format: gemm.hip "W4A8"): weights row-major [rows][K / 2] e2m1 nibbles +
+// [rows][K / 32] E8M0 scale bytes; K % 256 == 0.  pk: the 16-bit input of the quantiser / xq and a SwiGLU output in the packed operand layout
+int ats_quant_weights_mxfp4(const void* w, int rows, int k, void* q, void* scales, hipStream_t st, int pk = 0);
+size_t ats_gemm_w4a8_workspace_bytes(int m, int n, int k);
+int ats_gemm_w4a8(const void* xq, const float* sx, const void* wq, const void* wsc, void* c, int m, int n, int k, int ldc, int epilogue,
+                  hipStream_t st, int pk = 0, void* ws = nullptr, size_t ws_bytes = 0);
+int ats_gemm_w4a8_resid_norm(const void* xq, const float* sx, const void* wq, const void* wsc, void* h, int m, int n, int k, int ldh,
+                             const void* norm_w, void* xn, void* q_out, float* s_out, float eps, void* ws, size_t ws_bytes, hipStream_t st, int pk = 0);
+
 size_t ats_lmhead_lse_part_bytes(int m, int n);
 int ats_lmhead_lse(const void* a, const void* w, float* logits, int m, int n, int k, int lda, int ldc, int dtype, const unsigned char* tile_store,
                    float* part, size_t part_bytes, float* lse, void* workspace, size_t workspace_bytes, hipStream_t st, int* fused_out = nullptr,

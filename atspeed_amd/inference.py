@@ -51,6 +51,10 @@ def parse(argv=None):
     ap.add_argument("--target_fp8", action="store_true",
                     help="W8A8 (e4m3) target projections -- the place of the reference's `load_in_8bit` target (inference.py:86-91); works on bf16 and "
                          "fp16 targets (an fp16 checkpoint under --dtype auto keeps its type), not with --dtype fp32")
+    ap.add_argument("--target_fp4", action="store_true",
+                    help="W4A8 target projections: OCP MXFP4 weights (e2m1, one E8M0 scale per 32 k) against the W8A8 e4m3 activations, on the "
+                         "block-scaled MFMA; bf16 and fp16 targets only, exclusive with --target_fp8.  Opt-in: MXFP4 without rotation or outlier "
+                         "handling costs model quality on real checkpoints")
     ap.add_argument("--dtype", choices=("auto", "fp16", "bf16", "fp32"), default="auto",
                     help="engine arithmetic.  auto: a checkpoint runs in the type it is stored in (fp16 -- what the reference loads, inference.py:75-100 -- "
                          "takes the engine's fp16 flavour and keeps every weight bit; bf16 and fp32 likewise), synthetic weights are bf16")
@@ -59,6 +63,10 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.target_fp8 and args.dtype == "fp32":
         ap.error("--target_fp8 makes its e4m3 copies from 16-bit weights: use --dtype auto, fp16 or bf16")
+    if args.target_fp4 and args.dtype == "fp32":
+        ap.error("--target_fp4 makes its MXFP4 copies from 16-bit weights: use --dtype auto, fp16 or bf16")
+    if args.target_fp4 and args.target_fp8:
+        ap.error("--target_fp4 and --target_fp8 are exclusive: choose one target precision")
     return args
 
 
@@ -85,6 +93,8 @@ def load_models(args, vocab_size: int, beam: int, dev, max_prompt: int = 0):
                                       align_to=drf if args.aligned is not None else None, **kw)
     if args.target_fp8:
         tgt.enable_fp8()
+    if args.target_fp4:
+        tgt.enable_fp4()
     return tgt, drf
 
 

@@ -276,6 +276,22 @@ class HipLlama:
         _lib.check(_lib.load().atspeed_llama_fp8_counters(self._handle, f8, other, 1 if reset else 0))
         return {k: dict(fp8=int(f8[i]), other=int(other[i])) for i, k in enumerate(self.GEMM_KINDS[:4])}
 
+    def enable_fp4(self) -> "HipLlama":
+        """4-bit target: OCP MXFP4 layer projections (e2m1 weights with one E8M0 scale per 32 k of a row) against the W8A8 activations
+        (per-token e4m3), on the block-scaled MFMA (atspeed_llama_enable_fp4).  bf16 and fp16 models; the copies are made from the model's
+        own 16-bit weight values.  Exclusive with enable_fp8.  Opt-in: MXFP4 without rotation or outlier handling costs model quality."""
+        with torch.cuda.device(self._device):
+            _lib.check(_lib.load().atspeed_llama_enable_fp4(self._handle, _lib.stream_ptr(self._device)))
+        self.fp4 = True
+        return self
+
+    def fp4_counters(self, reset: bool = False) -> Dict[str, Dict[str, int]]:
+        """Launches of each layer projection that ran as W4A8 / as 16-bit GEMMs since the last reset (atspeed_llama_fp4_counters)."""
+        f4 = (C.c_int64 * 4)()
+        other = (C.c_int64 * 4)()
+        _lib.check(_lib.load().atspeed_llama_fp4_counters(self._handle, f4, other, 1 if reset else 0))
+        return {k: dict(fp4=int(f4[i]), other=int(other[i])) for i, k in enumerate(self.GEMM_KINDS[:4])}
+
     def rope_fused_launches(self, reset: bool = False) -> int:
         """qkv projections that carried RoPE + the KV scatter in their epilogue since the last reset (atspeed_llama_rope_fused_launches)."""
         return int(_lib.load().atspeed_llama_rope_fused_launches(self._handle, 1 if reset else 0))

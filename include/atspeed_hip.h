@@ -179,6 +179,18 @@ int atspeed_llama_enable_fp8(atspeed_llama* m, void* stream);
  * (fp8_out[4]) and how many as a bf16 / fp32 GEMM (other_out[4]) since the last reset: lets a test or a bench state that config 5
  * really ran its projections in fp8 rather than fell back by shape.  Either output may be NULL.  No reference counterpart. */
 int atspeed_llama_fp8_counters(atspeed_llama* m, int64_t* fp8_out, int64_t* other_out, int32_t reset);
+/* 4-bit target (W4A8 on the block-scaled MFMA, v_mfma_scale_f32_16x16x128_f8f6f4 with an e2m1 A operand): build library-owned OCP MXFP4
+ * copies of the four layer projections from the model's own 16-bit weights -- per row, blocks of 32 consecutive k with one E8M0 scale byte
+ * 127 + X, X = clamp(floor(log2(amax)) - 2, -127, 127), elements e2m1(v / 2^X) rounded to nearest (ties to the even mantissa), saturating at
+ * 6 (INTEGRATION.md "4-bit target").  From then on EVERY forward runs qkv, o_proj, gate_up and down as W4A8 (activations exactly the W8A8
+ * ones: per-token e4m3, fp32 scale; fp32 accumulation); embedding, norms, attention, KV cache and lm_head stay 16-bit.  Refused
+ * (ATSPEED_ERR_INVALID, atspeed_last_error says why): fp32 models, hidden or ffn not a multiple of 256, a model with fp8 copies
+ * (atspeed_llama_enable_fp8 in turn refuses a model with fp4 copies).  A second call is a no-op.  Opt-in: MXFP4 without rotation or
+ * outlier handling costs model quality on real checkpoints. */
+int atspeed_llama_enable_fp4(atspeed_llama* m, void* stream);
+/* as atspeed_llama_fp8_counters for the 4-bit target: launches of each layer projection that ran as W4A8 (fp4_out[4]) and as 16-bit / fp32
+ * GEMMs (other_out[4]) since the last reset */
+int atspeed_llama_fp4_counters(atspeed_llama* m, int64_t* fp4_out, int64_t* other_out, int32_t reset);
 /* how many qkv projections (one per layer per forward) ran with the rotary embedding and the KV-cache scatter in the GEMM's epilogue
  * (batched bf16 forwards, head_dim 128, hidden % 256 == 0: the reference's apply_rotary_pos_emb + cache update, modeling_llama.py as
  * called from beamSD.py:120, without re-reading the projection) rather than as the separate pass, since the last reset; -1 on a NULL
@@ -331,7 +343,7 @@ int atspeed_gemm(const void* a_dev, const void* w_dev, void* c_dev, int32_t m, i
 /* Which kernel family the library's GEMM launches took since the last reset (dispatch is a fitted cost model: tests assert the path they
  * mean to exercise).  out[i], i < n: 0 ring kernel, 1 ring kernel with its split-K tail, 2 weight-streaming kernel, 3 the same split in K,
  * 4 ring kernel in split-K mode, 5 LDS-tiled kernel, 6 fp8 ring kernel, 7 / 8 fp8 weight-streaming kernel / split, 9 / 10 panel kernel /
- * split, 11 fp8 ring kernel cut in K.  Returns the number of counters the library keeps. */
+ * split, 11 fp8 ring kernel cut in K, 12 W4A8 kernel (any form).  Returns the number of counters the library keeps. */
 int atspeed_gemm_path_counters(int64_t* out, int32_t n, int32_t reset);
 /* Process-wide tuning / test switches.  Each is an int read ONCE from its environment variable when the library first needs one (the
  * variable is the way to set it for a whole run) and changeable afterwards only through this call (tests and sweeps that compare two
@@ -347,6 +359,18 @@ int atspeed_gemm_packed(const void* a_dev, const void* w_dev, void* c_dev, int32
                         void* workspace_dev, size_t workspace_bytes, void* stream);
 int atspeed_gemm_fp8_packed(const void* xq_dev, const float* sx_dev, const void* wq_dev, const float* sw_dev, void* c_dev, int32_t m,
                             int32_t n, int32_t k, int32_t ldc, int32_t epilogue, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* MXFP4 weight quantiser (format: atspeed_llama_enable_fp4): w [rows][k] 16-bit (dtype ATSPEED_BF16 / ATSPEED_F16; packed = 1: in the packed
+ * operand layout, rows even, else row-major) -> q [rows][k / 2] bytes (element j of a row in byte j / 2, low nibble = even j; e2m1 codes: bit 3
+ * sign, 0..7 = 0, .5, 1, 1.5, 2, 3, 4, 6) and scales [rows][k / 32] E8M0 bytes; k % 256 == 0, 16-byte aligned buffers. */
+int atspeed_quant_weights_mxfp4(const void* w_dev, int32_t rows, int32_t k, int32_t dtype, int32_t packed, void* q_dev, void* scales_dev, void* stream);
+/* W4A8 GEMM: C[m][n] = epilogue((sum_k e4m3(xq[m][k]) e2m1(wq[n][k]) 2^(wscale[n][k / 32] - 127)) * sx[m]) in fp32; xq from
+ * atspeed_quant_rows_fp8 (packed = 1: atspeed_quant_rows_fp8_packed, and a SwiGLU output comes out packed too), wq / wscale from
+ * atspeed_quant_weights_mxfp4; epilogues as atspeed_gemm (0 store, 1 fp32, 2 residual add, 3 SwiGLU) in dtype (ATSPEED_BF16 / ATSPEED_F16);
+ * any m >= 1 (tiled over m); k % 256 == 0.  Thin grids are cut in k into fp32 slabs in workspace_dev when it holds them (parts x m x n x 4
+ * bytes), else one part per tile. */
+int atspeed_gemm_w4a8(const void* xq_dev, const float* sx_dev, const void* wq_dev, const void* wscale_dev, void* c_dev, int32_t m, int32_t n,
+                      int32_t k, int32_t ldc, int32_t epilogue, int32_t dtype, int32_t packed, void* workspace_dev, size_t workspace_bytes,
+                      void* stream);
 /* per-row e4m3 quantisation q = e4m3(x / scale[r]), scale[r] = max|x[r]| / 448, and the W8A8 GEMM over such operands */
 int atspeed_quant_rows_fp8(const void* x_bf16_dev, int32_t rows, int32_t cols, void* q_dev, float* scale_dev, void* stream);
 /* the same on operands in the packed layout (x through atspeed_pack_rows with row_bytes = 2 cols, q comes out as atspeed_pack_rows with
