@@ -15,7 +15,6 @@
 //  * tree_attn_kernel (fp32 parity mode / odd head dims): one wave per (token, head), scalar.
 #include "internal.h"
 #include <type_traits>
-#include <cstdlib>
 
 namespace ATS_NS {
 
@@ -546,10 +545,9 @@ int ats_tree_attention_segs(const void* q, int ldq, const SegTable& t, const Seg
   if (dtype == ATS_HALF && (head_dim == 64 || head_dim == 128) && (ldq % 8) == 0 && (ldo % 4) == 0) {
     dim3 mgrid(t.n_qtiles * n_heads);
     ATS_REQUIRE(t.qtile_rows == 64 || t.qtile_rows == 128 || t.qtile_rows == 256, ATSPEED_ERR_INVALID, "attention: query tile of %d rows", t.qtile_rows);
-    static const int rows32 = getenv("ATSPEED_ATTN32") ? atoi(getenv("ATSPEED_ATTN32")) : 1;
     // small grids (one user: 32-64 workgroups) are latency-bound per workgroup and keep the 16-rows-per-wave kernel (twice the waves per tile)
-    constexpr int rows32_min_wgs = 512;       // (round 6: a constant -- no test or tool set ATSPEED_ATTN32_MIN_WGS; measured in round 2)
-    if (rows_per_wave == 32 || (rows_per_wave == 0 && rows32 && t.n_qtiles * n_heads >= rows32_min_wgs)) {
+    constexpr int rows32_min_wgs = 512;       // (measured in round 2)
+    if (rows_per_wave == 32 || (rows_per_wave == 0 && t.n_qtiles * n_heads >= rows32_min_wgs)) {
 #define ATS_ATTN32(DHV, NWV)                                                                                                   \
   {                                                                                                                            \
     constexpr int lds_bytes = 2 * (64 * DHV * 2 + 64 * (DHV * 2 + 32));                                                        \
@@ -569,14 +567,13 @@ int ats_tree_attention_segs(const void* q, int ldq, const SegTable& t, const Seg
       return ATSPEED_OK;
     }
     // one user's forwards (at most one workgroup per CU): the DMA-ring form, the whole K/V of a user in flight before the first product
-    static const int ring_on = getenv("ATSPEED_ATTN_RING") ? atoi(getenv("ATSPEED_ATTN_RING")) : 1;
-    constexpr int ring_max_wgs = 256;         // (round 6: a constant -- one user's forwards; ATSPEED_ATTN_RING_MAX_WGS was set by nothing)
+    constexpr int ring_max_wgs = 256;
     {
       const int nw = t.qtile_rows / 16;
       const size_t tile = (size_t)64 * head_dim * 2 + (size_t)64 * (head_dim * 2 + 32);
       const size_t ring_lds = 4 * tile + (size_t)16 * nw * vis_words * sizeof(uint64_t);
       // (not the 256-row tile: 16 waves cap a lane at 128 registers and the compiler's spill traffic would sit in the hand-counted vmcnt window)
-      if (ring_on && nw <= 8 && (int)(t.n_qtiles * n_heads) <= ring_max_wgs && ring_lds <= 160 * 1024 - 64) {
+      if (nw <= 8 && (int)(t.n_qtiles * n_heads) <= ring_max_wgs && ring_lds <= 160 * 1024 - 64) {
 #define ATS_ATTN_RING(DHV, NWV)                                                                                                \
   {                                                                                                                            \
     static thread_local AtsPerDeviceFlag attr_flag;                                                                            \

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bf16_vec_kernel(const bf16_t* __r
   // would leave the two halves of a line dirty in two different L2s; inside a group of 16 workgroups the pair goes to the SAME XCD
   // (workgroups x and x + 8 take rows 2x and 2x + 1) and its lines leave one L2 whole
   int row = blockIdx.x;
-  if (pk && (row | 15) < (int)gridDim.x && !(pk & 2)) { const int b = row & 15; row = (row & ~15) + (b & 7) * 2 + (b >> 3); }
+  if (pk && (row | 15) < (int)gridDim.x) { const int b = row & 15; row = (row & ~15) + (b & 7) * 2 + (b >> 3); }
   const uint4* xr = reinterpret_cast<const uint4*>(x + (size_t)row * hidden);
   const uint4* wr = reinterpret_cast<const uint4*>(w);
   uint4 v[NC];
@@ -143,13 +143,6 @@ __global__ __launch_bounds__(256) void rmsnorm_bf16_vec_kernel(const bf16_t* __r
   }
 }
 
-// kernel argument `pk` of rmsnorm_bf16_vec_kernel: bit 0 = packed output, bit 1 = keep the workgroup -> row map linear (A/B switch
-// ATSPEED_RMSNORM_PAIRS=0)
-static int rmsnorm_pk_arg(int pk) {
-  static const bool pairs_off = getenv("ATSPEED_RMSNORM_PAIRS") && atoi(getenv("ATSPEED_RMSNORM_PAIRS")) == 0;
-  return pk ? (pairs_off ? 3 : 1) : 0;
-}
-
 // RMSNorm whose consumer is a W8A8 projection: y (bf16, optional) and the e4m3 row + scale in one pass
 int ats_rmsnorm_quant_fp8(const void* x, const void* w, void* y, void* q, float* scale, int rows, int hidden, float eps, hipStream_t st, int pk) {
   if (rows <= 0) return ATSPEED_OK;
@@ -158,9 +151,9 @@ int ats_rmsnorm_quant_fp8(const void* x, const void* w, void* y, void* q, float*
   const bf16_t *xb = (const bf16_t*)x, *wb = (const bf16_t*)w;
   bf16_t* yb = (bf16_t*)y;
   unsigned char* qb = (unsigned char*)q;
-  if (hidden <= 2048)      rmsnorm_bf16_vec_kernel<1, true><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, qb, scale, rmsnorm_pk_arg(pk));
-  else if (hidden <= 4096) rmsnorm_bf16_vec_kernel<2, true><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, qb, scale, rmsnorm_pk_arg(pk));
-  else                     rmsnorm_bf16_vec_kernel<4, true><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, qb, scale, rmsnorm_pk_arg(pk));
+  if (hidden <= 2048)      rmsnorm_bf16_vec_kernel<1, true><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, qb, scale, pk);
+  else if (hidden <= 4096) rmsnorm_bf16_vec_kernel<2, true><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, qb, scale, pk);
+  else                     rmsnorm_bf16_vec_kernel<4, true><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, qb, scale, pk);
   ATS_LAUNCH_CHECK();
   return ATSPEED_OK;
 }
@@ -173,9 +166,9 @@ int ats_rmsnorm(const void* x, const void* w, void* y, int rows, int hidden, flo
   if (vec_ok) {
     const bf16_t *xb = (const bf16_t*)x, *wb = (const bf16_t*)w;
     bf16_t* yb = (bf16_t*)y;
-    if (hidden <= 2048)      rmsnorm_bf16_vec_kernel<1, false><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, nullptr, nullptr, rmsnorm_pk_arg(pk));
-    else if (hidden <= 4096) rmsnorm_bf16_vec_kernel<2, false><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, nullptr, nullptr, rmsnorm_pk_arg(pk));
-    else                     rmsnorm_bf16_vec_kernel<4, false><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, nullptr, nullptr, rmsnorm_pk_arg(pk));
+    if (hidden <= 2048)      rmsnorm_bf16_vec_kernel<1, false><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, nullptr, nullptr, pk);
+    else if (hidden <= 4096) rmsnorm_bf16_vec_kernel<2, false><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, nullptr, nullptr, pk);
+    else                     rmsnorm_bf16_vec_kernel<4, false><<<rows, 256, 0, st>>>(xb, wb, yb, hidden, eps, nullptr, nullptr, pk);
     ATS_LAUNCH_CHECK();
     return ATSPEED_OK;
   }
@@ -566,8 +559,7 @@ int ats_quant_rows_fp8(const void* x, int rows, int cols, int ld, void* q, float
   if (rows <= 0) return ATSPEED_OK;
   ATS_REQUIRE(cols % 8 == 0 && ld % 8 == 0, ATSPEED_ERR_INVALID, "quant_fp8: cols=%d / ld=%d must be multiples of 8", cols, ld);
   ATS_REQUIRE(!pk || (cols % 64 == 0 && ld == cols), ATSPEED_ERR_INVALID, "quant_fp8: packed operands need cols %% 64 == 0 and ld == cols");
-  static const bool pairs_off = getenv("ATSPEED_QUANT_PAIRS") && atoi(getenv("ATSPEED_QUANT_PAIRS")) == 0;
-  if (pk && !pairs_off && cols <= 12 * 1024) {                     // a pair of up to 12288 columns in registers (12 x 16 bytes per thread)
+  if (pk && cols <= 12 * 1024) {                                   // a pair of up to 12288 columns in registers (12 x 16 bytes per thread)
     const int n_pairs = (rows + 1) / 2, nc = ((cols >> 5) + 31) / 32;     // the pad row of an odd count is allocated (operands hold an even number of rows)
     if (nc <= 4)       quant_row_pairs_fp8_kernel<4><<<n_pairs, 256, 0, st>>>((const bf16_t*)x, rows, cols, (unsigned char*)q, scale);
     else if (nc <= 8)  quant_row_pairs_fp8_kernel<8><<<n_pairs, 256, 0, st>>>((const bf16_t*)x, rows, cols, (unsigned char*)q, scale);

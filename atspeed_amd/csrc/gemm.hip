@@ -9,12 +9,10 @@
 //     bf16: v_mfma_f32_16x16x32_bf16, fp32 parity mode: v_mfma_f32_16x16x4_f32 with a k permutation that lets a
 //     lane take its four k-steps from one chunk; split-K into fp32 slabs sized for >= 2-3 workgroups per CU, reduced
 //     by a second kernel that also applies the epilogue (and, for the residual projections, the next RMSNorm).
-//   * gemm_ring_kernel<EPI,MT2,FP8> — M = tokens of all users of a lock-step batch (thousands): MFMA-bound.  256 x
+//   * gemm_ring_kernel<EPI,MT2,...> — M = tokens of all users of a lock-step batch (thousands): MFMA-bound.  256 x
 //     {256,128} tile, 8 waves, both operands by LDS-DMA into a four-stage ring of 32-deep k-steps, hand-placed inner
-//     loop (see the kernel's comment); the same kernel on e4m3 operands with per-row scales (W8A8).
+//     loop (see the kernel's comment); gemm_ring_mx_kernel is the same ring on e4m3 operands with per-row scales (W8A8).
 // Epilogues: store (dtype), fp32 store (logits), residual add, SwiGLU over interleaved gate/up 16-row groups.
-#include <stdlib.h>
-
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -26,7 +24,6 @@ namespace ATS_NS {
 
 namespace {
 
-static int env_int(const char* name, int dflt);
 // share of the last wave of 256 CUs a grid of `tiles` workgroups keeps busy, in percent
 static int big_fill_pct(int tiles) { return tiles * 100 / (((tiles + 255) / 256) * 256); }
 // Tile height of the 256-wide kernels from a cost model fitted to tools/gemm_ab.py sweeps (MI355X, ring kernel): time ~
@@ -429,7 +426,7 @@ __device__ __forceinline__ void big_epilogue(f32x4_t (&acc)[NA][MT2], void* __re
         // read-modify-write of h: the loads of a row group must not wait behind the previous group's stores (same pointer: the compiler
         // keeps them in order, one memory round trip per store), so all residuals of a 64-column quarter are fetched first
 #pragma unroll
-        for (int q = 0; q < NA / 4; ++q) {                          // (NA = 8: 64 residual registers at a time, not 128)
+        for (int q = 0; q < NA / 4; ++q) {
           uint4 rs[2][MT2];
 #pragma unroll
           for (int j = 0; j < MT2; ++j) {
@@ -631,22 +628,16 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
 // Result on MI355X: MFMA pipe 74 % busy at ~1.55 GHz (the chip lowers its clock under this load), 1.15-1.25 PF on the
 // Llama-7B projections at 2-7 k tokens; hipBLASLt's stream-K 256x256x64 kernel reaches 1.05-1.39 PF on the same shapes.
 #define ATS_MFMA_BF16(c, a, b) asm volatile(ATS_MFMA_16x16x32_NAME " %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b))
-#define ATS_MFMA_BF16_A(c, a, b) asm volatile(ATS_MFMA_16x16x32_NAME " %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b))
-#define ATS_MFMA_FP8(c, a, b) asm volatile("v_mfma_f32_16x16x32_fp8_fp8 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b))
 // (m0 is written here without an "m0" clobber on purpose: m0 is a RESERVED register for LLVM's AMDGPU backend -- it never keeps a value
 // live in it across instructions, it re-materialises m0 glued to each of its own m0 readers -- and hipcc rejects the clobber with
 // -Winline-asm "clobber list contains reserved registers ... may lead to undefined behaviour".)
 #define ATS_DMA16(voff, sbase, m0v) \
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(m0v) : "memory")
 
-// FP8: the operands are e4m3 bytes with per-row scales (W8A8); a 64-byte row then holds 64 k, a lane's 16-byte fragment
-// chunk feeds two v_mfma_f32_16x16x32_fp8_fp8 (low / high 8 bytes: the k order inside a 64-k group is permuted
-// identically on both operands), so a stage carries twice the flops for the same DMA and LDS bytes.
 // SPLITK (one user's tokens, M <= 256: every launch is one pass over W and HBM-bound): the grid is tiles x n_split, part z
 // accumulates the k-steps of its share of the 128-k units and stores fp32 partials to slab z of Cv ([z][M][N]); the deep
 // LDS-DMA ring (three k-steps = 72-96 KB per CU in flight, no register staging) is what pulls the weight stream.
-// NA = 16-row weight tiles per wave: 4 -> 8 waves (4 x 2) of 64 x (MT2*16); 8 -> 4 waves (2 x 2) of 128 x 128 with the 256
-// accumulator registers in AGPRs: one wave per SIMD and a third fewer LDS fragment bytes per flop (the kernel is power-limited).
+// NA = 16-row weight tiles per wave: 4 -> 8 waves (4 x 2) of 64 x (MT2*16).
 // SK (stream-K tail, bf16 batched forwards in the 4-64-user band): the tile grid of such a forward is 0.3-3 rounds of 256 workgroups and a
 // tile lasts 50-85 us, so the last, partly filled round costs a whole tile time (gate_up at 912 tokens: 344 tiles = 1.34 rounds, paid as 2).
 // With SK the first n_dp = 256 * floor(tiles / 256) tiles run as before (one workgroup each, whole K, the epilogue of EPI), and the k-steps
@@ -671,12 +662,17 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
                                                            int tiles_n, int tiles_m, int GM, int n_split = 1,
                                                            float* __restrict__ lse_part = nullptr, const unsigned char* __restrict__ tile_store = nullptr,
                                                            int pk = 0, RopeEpi rope = RopeEpi{}, SkTail sk = SkTail{}) {
+  // FP8 (the round-1 e4m3 form, replaced by gemm_ring_mx_kernel) and NA = 8 here, NWV = 4 in gemm_ring_mx_kernel (four waves, accumulators
+  // in AGPRs, 2-5 % slower) are retired; the parameters and the sx / sw arguments stay so that the kernel symbols named by profiles/,
+  // bench.py and the rocprof filters do not change
+  static_assert(!FP8, "the e4m3 form is gemm_ring_mx_kernel");
+  static_assert(NA == 4, "eight-wave form only");
   static_assert(!(SK && (SPLITK || FP8 || NA != 4 || WN != 4 || WM != 2)), "the stream-K tail is built for the bf16 eight-wave 4 x 2 form");
   static_assert((EPI != EPI_F32_LSE && EPI != EPI_QKV_ROPE) || (WN == 4 && WM == 2), "the LSE / RoPE epilogues are written for the 4 x 2 wave grid");
   // pk: X and W (and the SwiGLU output) are in the packed operand layout -- every 1 KB DMA piece is then eight FULL 128-byte lines
   // (two rows x 64 bytes each) instead of sixteen half lines: 83 against 55 GB/s per CU from L2 (tools/probe/dma_depth.hip)
-  constexpr int BT = WN * NA * 16, RB = 64, ESZ = FP8 ? 1 : 2;   // weight rows per workgroup: 256 (4 x 2 waves) or 128 (panel form, 2 x 4)
-  constexpr int BK = RB / ESZ;                                   // k per stage: 32 (bf16) or 64 (fp8)
+  constexpr int BT = WN * NA * 16, RB = 64, ESZ = 2;             // weight rows per workgroup: 256 (4 x 2 waves) or 128 (panel form, 2 x 4)
+  constexpr int BK = RB / ESZ;                                   // k per stage: 32
   constexpr int XR = WM * MT2 * 16;                              // token rows per workgroup (256 or 128; panel: 384 or 512)
   constexpr int NWV = WN * WM;                                   // waves per workgroup: 8 or 4
   constexpr int WP = (BT / 16) / NWV;                            // W DMA pieces (16 rows each) per wave per k-step
@@ -789,10 +785,6 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
     if (r < NA) {
       switch (r) {
         ATS_RD(fa[buf][0], a, 0) ATS_RD(fa[buf][1], a, 1) ATS_RD(fa[buf][2], a, 2) ATS_RD(fa[buf][3], a, 3)
-        case 4: if constexpr (NA == 8) ATS_DS_READ_B128(fa[buf][NA - 4], a, so + 4096); break;
-        case 5: if constexpr (NA == 8) ATS_DS_READ_B128(fa[buf][NA - 3], a, so + 5120); break;
-        case 6: if constexpr (NA == 8) ATS_DS_READ_B128(fa[buf][NA - 2], a, so + 6144); break;
-        case 7: if constexpr (NA == 8) ATS_DS_READ_B128(fa[buf][NA - 1], a, so + 7168); break;
         default: break;
       }
     } else {
@@ -816,16 +808,7 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
       if (RD && idx % RG == 0 && idx / RG < NR) read_one(((Q) + 1) & 3, ((Q) + 1) & 1, idx / RG);       \
       if (DMA && idx >= NR * RG && (idx - NR * RG) % DG == 0 && (idx - NR * RG) / DG < NP)              \
         dma_piece((Q), (ks) + 4, (idx - NR * RG) / DG);                                                  \
-      if constexpr (FP8) {                                                                               \
-        ATS_MFMA_FP8(acc[i][j], __builtin_shufflevector(fa[(Q) & 1][i], fa[(Q) & 1][i], 0, 1),           \
-                     __builtin_shufflevector(fb[(Q) & 1][j], fb[(Q) & 1][j], 0, 1));                     \
-        ATS_MFMA_FP8(acc[i][j], __builtin_shufflevector(fa[(Q) & 1][i], fa[(Q) & 1][i], 2, 3),           \
-                     __builtin_shufflevector(fb[(Q) & 1][j], fb[(Q) & 1][j], 2, 3));                     \
-      } else if constexpr (NA == 8) {                                                                    \
-        ATS_MFMA_BF16_A(acc[i][j], fa[(Q) & 1][i], fb[(Q) & 1][j]);                                      \
-      } else {                                                                                           \
-        ATS_MFMA_BF16(acc[i][j], fa[(Q) & 1][i], fb[(Q) & 1][j]);                                        \
-      }                                                                                                  \
+      ATS_MFMA_BF16(acc[i][j], fa[(Q) & 1][i], fb[(Q) & 1][j]);                                          \
     }                                                                                                    \
     if (RD) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                           \
     if ((VM) >= 0) {                                                                                     \
@@ -931,18 +914,6 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
     }
   }
   if (sk_epilogue) {
-  if constexpr (FP8) {                                             // per-row scales: acc[i][j][r] *= sx[m] * sw[n]
-#pragma unroll
-    for (int j = 0; j < MT2; ++j) {
-      const float fx = sx[min(m0 + wm * (MT2 * 16) + j * 16 + lq, M - 1)];
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int gn = n0 + wn * (NA * 16) + (i >> 2) * 64 + ring_src_row<ORD>((i & 3) * 16 + g * 4);   // weight row of acc[i][j][0]; r: the next three
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][j][r] *= fx * sw[min(gn + r, N - 1)];
-      }
-    }
-  }
   if constexpr (EPI == EPI_F32_LSE) {
     // lm_head fused with the full-vocabulary normaliser (beamSD.py:58,285: log-softmax over ALL columns before masking): this tile's
     // (max, sum exp) per token row goes to lse_part[row][tile_n]; the fp32 logits themselves are stored only when some column of the
@@ -999,9 +970,9 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
 // block scales (E8M0 0x7f) issues 2x the flops per cycle of the bf16 / non-scaled fp8 forms (tools/probe/mx_probe.hip on MI355X:
 // 4.6 PF register-only against 2.4 PF for v_mfma_f32_16x16x32_fp8_fp8; lane map checked there with exact integer data: lane l
 // holds row l&31 and the 32 bytes k = 32*(l>>5) .. +31; C/D as the bf16 32x32 forms).  The per-row / per-token fp32 scales of
-// the W8A8 scheme are applied to the accumulators as before, so the numerics equal the non-scaled kernel's (exact products,
-// fp32 accumulation; only the summation order inside a 64-k group differs).
-// Same LDS image, DMA pieces and four-stage ring as gemm_ring_kernel<.., FP8 = true> (a stage = 64 k of e4m3 in 64-byte rows);
+// the W8A8 scheme are applied to the accumulators, so the numerics equal those of the non-scaled kernel this one replaced (exact
+// products, fp32 accumulation; only the summation order inside a 64-k group differs).
+// Same LDS image, DMA pieces and four-stage ring as gemm_ring_kernel (a stage = 64 k of e4m3 in 64-byte rows);
 // what changes is the consumer: a wave's 64 x (MT2*16) tile is 2 x MT2/2 tiles of 32x32, a lane's operand for one 32x32x64
 // MFMA is the two 16-byte chunks 2h, 2h+1 of its row (two ds_read_b128 into the halves of an 8-register tuple), and a k-step
 // is 8 (4) MFMAs of 64 cycles with the 12 (8) fragment reads of the next k-step and the 4 (3) DMA pieces of k-step s+4 spread
@@ -1010,19 +981,10 @@ typedef unsigned int u32x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 #define ATS_MFMA_MX(c, a, b, s) \
   asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(a), "v"(b), "v"(s))
-// accumulators in AGPRs (the one-wave-per-SIMD form: 256 accumulator registers do not fit the 256 architectural VGPRs beside the fragments)
-// (the host pass of hipcc checks asm constraints against x86, where "a" is rax: a 64-byte operand fails template substitution there and the
-// kernel's host stub silently disappears, so the statement exists in the device pass only)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define ATS_MFMA_MX_A(c, a, b, s) \
-  asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+a"(c) : "v"(a), "v"(b), "v"(s))
-#else
-#define ATS_MFMA_MX_A(c, a, b, s) ((void)0)
-#endif
 
 // accumulator tile (it, jt) of a wave: m = m0w + jt*32 + (lane&31); registers 4q..4q+3 hold n = n0w + it*32 + 8q + 4(lane>>5) + r
 // The per-row scales of the W8A8 scheme (acc *= sx[m] * sw[n]) are applied tile by tile right where a tile is consumed: scaling all
-// accumulators first kept 256 of them live in VGPRs in the one-wave-per-SIMD form (they sit in AGPRs during the loop) and spilled.
+// accumulators first kept 256 of them live in VGPRs in the retired one-wave-per-SIMD form (they sat in AGPRs during the loop) and spilled.
 template <int TA, int TB>
 __device__ __forceinline__ void mx_scale_tile(f32x16_t& t, const float* __restrict__ sx, const float* __restrict__ sw, int gm, int gn0, int h, int M, int N) {
   const float fx = sx[min(gm, M - 1)];
@@ -1207,9 +1169,7 @@ __device__ __forceinline__ void mx_qkv_rope_epilogue(f32x16_t (&acc)[TA][TB], bf
   }
 }
 
-// NWV = 8: waves 4 (n) x 2 (m), wave tile 64 x MT2*16 (2 x MT2/2 tiles of 32x32), two waves per SIMD.  NWV = 4: waves 2 x 2, wave tile
-// 128 x MT2*16 (4 x MT2/2 tiles), ONE wave per SIMD with up to 512 registers: a third fewer LDS fragment bytes per flop and no two waves
-// contending for a SIMD's matrix pipe and issue slots (measured 2-5 % slower; the launcher instantiates NWV = 8 only).
+// NWV = 8: waves 4 (n) x 2 (m), wave tile 64 x MT2*16 (2 x MT2/2 tiles of 32x32), two waves per SIMD.
 // SPLITK (round 5: the N = 4096 projections of 257-2000-token forwards in fp8, whose tile grids fill a fifth to a half of a round): the grid is
 // tiles x n_split, part z accumulates its share of the 256-k units and stores SCALED fp32 partial sums to slab z of Cv ([z][M][N]); the reduce
 // kernels of every other split form finish the job (residual + RMSNorm + the next projection's e4m3 rows).
@@ -1217,6 +1177,7 @@ template <int EPI, int MT2, int NWV = 8, bool SPLITK = false>
 __global__ __launch_bounds__(NWV * 64, 1) void gemm_ring_mx_kernel(const void* __restrict__ X, const void* __restrict__ W, const float* __restrict__ sx,
                                                               const float* __restrict__ sw, void* __restrict__ Cv, int M, int N, int K, int ldc,
                                                               int tiles_n, int tiles_m, int GM, int pk, RopeEpi rope = RopeEpi{}, int n_split = 1) {
+  static_assert(NWV == 8, "eight-wave form only (see gemm_ring_kernel)");
   static_assert(!SPLITK || EPI == EPI_F32, "split-K parts leave fp32 slabs");
   constexpr int BT = 256, RB = 64;                                // 64-byte LDS rows = 64 k of e4m3 per stage
   constexpr int XR = 2 * MT2 * 16;                               // token rows per workgroup (256 or 128)
@@ -1312,10 +1273,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void gemm_ring_mx_kernel(const void* _
           else if (DMA) dma_piece((Q), (ks) + 4, t - NR);                                                \
         }                                                                                                \
       }                                                                                                  \
-      if constexpr (NWV == 4)                                                                            \
-        ATS_MFMA_MX_A(acc[i][j], ATS_CAT8(fal[(Q) & 1][i], fah[(Q) & 1][i]), ATS_CAT8(fbl[(Q) & 1][j], fbh[(Q) & 1][j]), unit_scale); \
-      else                                                                                               \
-        ATS_MFMA_MX(acc[i][j], ATS_CAT8(fal[(Q) & 1][i], fah[(Q) & 1][i]), ATS_CAT8(fbl[(Q) & 1][j], fbh[(Q) & 1][j]), unit_scale); \
+      ATS_MFMA_MX(acc[i][j], ATS_CAT8(fal[(Q) & 1][i], fah[(Q) & 1][i]), ATS_CAT8(fbl[(Q) & 1][j], fbh[(Q) & 1][j]), unit_scale); \
     }                                                                                                    \
     if (RD) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                           \
     if ((VM) >= 0) {                                                                                     \
@@ -1580,38 +1538,20 @@ int launch_big_fp8(const unsigned char* x, const float* sx, const unsigned char*
                    int ldc, hipStream_t st, int pk, const RopeEpi& rope = RopeEpi{}) {
   constexpr int gm = 4;
   const int tiles_n = (n + 255) / 256;
-  static thread_local AtsPerDeviceFlag attr_flag;
-  bool& attr_done = attr_flag.cur();
-  if (!attr_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr_done = true;
+  static thread_local AtsPerDeviceFlag mx_flag;
+  bool& mx_done = mx_flag.cur();
+  if (!mx_done) {
+    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_mx_kernel<EPI, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_mx_kernel<EPI, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    mx_done = true;
   }
   const int t256 = tiles_n * ((m + 255) / 256), t128 = tiles_n * ((m + 127) / 128);
-  // block-scaled MFMA form (2x the flops per cycle); ATSPEED_FP8_MX=0 keeps the non-scaled v_mfma_f32_16x16x32_fp8_fp8 kernel for A/B runs
-  static const int use_mx = env_int("ATSPEED_FP8_MX", 1);
-  if (use_mx) {
-    static thread_local AtsPerDeviceFlag mx_flag;
-    bool& mx_done = mx_flag.cur();
-    if (!mx_done) {
-      ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_mx_kernel<EPI, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-      ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_mx_kernel<EPI, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      mx_done = true;
-    }
-    // (the four-wave form of this kernel, NWV = 4, was 2-5 % slower and is not instantiated any more)
-    if (big_use_256_rows(t256, t128))
-      hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI, 8>), dim3(t256), dim3(512), 128 * 1024, st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, ldc, tiles_n, (m + 255) / 256, gm, pk, rope);
-    else
-      hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI, 4>), dim3(t128), dim3(512), 96 * 1024, st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, ldc, tiles_n, (m + 127) / 128, gm, pk, rope);
-    ATS_LAUNCH_CHECK();
-    ats_count_path(ATS_PATH_FP8_RING);
-    return ATSPEED_OK;
-  }
   if (big_use_256_rows(t256, t128))
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI, 8, true>), dim3(t256), dim3(512), 128 * 1024, st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, k, ldc, tiles_n, (m + 255) / 256, gm, 1, (float*)nullptr, (const unsigned char*)nullptr, pk, rope);
+    hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI, 8>), dim3(t256), dim3(512), 128 * 1024, st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, ldc, tiles_n, (m + 255) / 256, gm, pk, rope);
   else
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI, 4, true>), dim3(t128), dim3(512), 96 * 1024, st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, k, ldc, tiles_n, (m + 127) / 128, gm, 1, (float*)nullptr, (const unsigned char*)nullptr, pk, rope);
+    hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI, 4>), dim3(t128), dim3(512), 96 * 1024, st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, ldc, tiles_n, (m + 127) / 128, gm, pk, rope);
   ATS_LAUNCH_CHECK();
+  ats_count_path(ATS_PATH_FP8_RING);
   return ATSPEED_OK;
 }
 
@@ -1866,11 +1806,6 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
 
 struct Plan { int bm; int bn; int splits; int k_per_split; };
 
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 // Occupancy first: tools/stream_bench.hip shows streamed bandwidth ~ resident streaming waves (up to ~770), and a
 // workgroup keeps only one k-tile of loads in flight, so the plan aims at >= ~2 workgroups per CU (split-K when the
 // M x N tiling alone is too coarse) before anything else.
@@ -2050,10 +1985,9 @@ int launch_cfg(const T* a, const T* w, void* c, int m, int n, int k, int lda, in
 // 35-42 us; 192 tiles of 64 give 27.7 / 32.6 against 30.9 / 35.4, but the split-K form hands its slabs to the RoPE kernel, which the
 // bf16 store + separate RoPE pass of this form gives back: 22.71 vs 22.65 ms per user) and not N = 4096 (split-K + fused reduce / norm).
 static bool wdma_applies(int m, int n, int k, int lda, int epilogue) {
-  static const int on = env_int("ATSPEED_GEMM_WDMA", 1);
   constexpr int min_m = 33;
   constexpr int max_m = 256;
-  if (!on || m < min_m || m > max_m || k % 64 != 0 || k < 512 || (lda % 8) != 0 || !dma_offsets_fit(n, k, 2) || !dma_offsets_fit(m, lda, 2)) return false;
+  if (m < min_m || m > max_m || k % 64 != 0 || k < 512 || (lda % 8) != 0 || !dma_offsets_fit(n, k, 2) || !dma_offsets_fit(m, lda, 2)) return false;
   const int t192 = (n + 191) / 192, t128 = (n + 127) / 128;
   const bool ok128 = t128 >= 150 && t128 <= 256, ok192 = t192 >= 150 && t192 <= 256;
   if (!(ok128 || (ok192 && m <= 128))) return false;                  // 129-256 rows: 128-row tiles only
@@ -2076,9 +2010,8 @@ int launch_wdma_cfg(const bf16_t* a, const bf16_t* w, void* c, int m, int n, int
 }
 // split-K form: projections whose N gives too few 128-row tiles (qkv: 96, o_proj and down: 32) take tiles x splits = 150-256 workgroups
 static int wdma_split_count(int m, int n, int k, int lda) {
-  static const int on_all = env_int("ATSPEED_GEMM_WDMA", 1);
   constexpr int min_m = 33;
-  if (!on_all || m < min_m || m > 256 || k % 64 != 0 || (lda % 8) != 0 || n < 2048 || !dma_offsets_fit(n, k, 2) || !dma_offsets_fit(m, lda, 2)) return 0;
+  if (m < min_m || m > 256 || k % 64 != 0 || (lda % 8) != 0 || n < 2048 || !dma_offsets_fit(n, k, 2) || !dma_offsets_fit(m, lda, 2)) return 0;
   const int t128 = (n + 127) / 128, n_kt = k / 64;
   if (t128 >= 150) return 0;                                           // wide enough for the no-split form (or too wide for one round)
   // k-tiles per part at least: 8 up to 128 tokens (o_proj, K = 4096: 8 parts of 8 tiles, 15.8 / 18.8 -> 13.5 / 16.0 us at 60 / 100 tokens), 16 above
@@ -2364,10 +2297,9 @@ size_t ats_lmhead_lse_part_bytes(int m, int n) { return (size_t)m * ((n + 255) /
 int ats_lmhead_lse(const void* a, const void* w, float* logits, int m, int n, int k, int lda, int ldc, int dtype, const unsigned char* tile_store,
                    float* part, size_t part_bytes, float* lse, void* workspace, size_t workspace_bytes, hipStream_t st, int* fused_out, int pk,
                    const SkArena* sk) {
-  static const int fuse = env_int("ATSPEED_FUSE_LSE", 1);
   if (fused_out) *fused_out = 0;
   if (m <= 0) return ATSPEED_OK;
-  if (fuse && dtype == ATS_HALF && part && part_bytes >= ats_lmhead_lse_part_bytes(m, n) && ((uintptr_t)part & 7) == 0 &&
+  if (dtype == ATS_HALF && part && part_bytes >= ats_lmhead_lse_part_bytes(m, n) && ((uintptr_t)part & 7) == 0 &&
       big_kernel_applies(m, n, k, lda, ldc, dtype, EPI_F32, true)) {
     ATS_REQUIRE(a && w && logits && lse, ATSPEED_ERR_INVALID, "lmhead_lse: null operand");
     ATS_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)w & 15) == 0, ATSPEED_ERR_INVALID, "lmhead_lse: operands must be 16-byte aligned");
@@ -2381,7 +2313,7 @@ int ats_lmhead_lse(const void* a, const void* w, float* logits, int m, int n, in
 // h += a * w^T, then xn = rmsnorm(h) * norm_w  (split-K path fuses the reduce, the residual and the norm)
 static bool big_kernel_applies(int m, int n, int k, int lda, int ldc, int dtype, int epilogue, bool lm_head) {
   // the 256-wide ring kernel vs the 128-wide LDS-tiled kernel (with split-K): the ring kernel wins once its tile grid keeps
-  // a fair share of the 256 CUs busy (measured, tools/gemm_ab.py with ATSPEED_GEMM_BIG_MIN_FILL)
+  // a fair share of the 256 CUs busy (measured with tools/gemm_ab.py)
   // from 257 tokens (two token tiles): measured against the split-K mode at 300-500 tokens, gate_up 115-138 -> 96-108 us, qkv 80 -> 75 us
   constexpr int big_min_m = 257;
   constexpr int min_fill = 60;   // crossover measured at ~50-60 % (o_proj, down, qkv, gate_up at 512-1920 tokens)
@@ -2463,17 +2395,13 @@ static int launch_mx_split(const unsigned char* x, const float* sx, const unsign
 // directly; the others are cut in K so that tiles x parts fill the chip (qkv 96 x 2, o_proj / down 32 x 8) and leave scaled fp32 slabs to
 // the 16-bit form's consumers (reduce + residual + RMSNorm [+ e4m3 quantisation for the next projection], RoPE + KV scatter).
 static bool wdma8_applies(int m, int n, int k) {
-  static const int on = env_int("ATSPEED_FP8_SMALL", 1);               // 0: one user's forwards stay on the 16-bit kernels (A/B)
-  return on && m >= 1 && m <= 256 && k % 128 == 0 && k >= 512 && n >= 16 && dma_offsets_fit(n, k, 1) && dma_offsets_fit(m, k, 1);
+  return m >= 1 && m <= 256 && k % 128 == 0 && k >= 512 && n >= 16 && dma_offsets_fit(n, k, 1) && dma_offsets_fit(m, k, 1);
 }
 // 64-row weight tiles for the projections of up to 256 such tiles (N <= 16384: qkv, o_proj, down): the PMC passes of the 128-row form showed the split
 // launches' traffic to be their fp32 slabs (down at 228 tokens: 29.9 MB written + 31.8 MB re-read next to 47.6 MB of operands), and 64 tiles x 4 parts
 // halve them; qkv's 192 tiles need no split at all (bf16 store + the plain RoPE pass instead of 2 slabs).  One user 16.8 -> 15.75 ms at zero
-// acceptance, 5.97 -> 5.48 ms at three accepted steps (A/B ATSPEED_FP8_SMALL_BN64 = 0 / 1 (N <= 4096 only: 16.0 / 5.6) / 2 on one box).
-static bool wdma8_bn64(int n) {
-  static const int on = env_int("ATSPEED_FP8_SMALL_BN64", 2);
-  return on && n <= (on >= 2 ? 16384 : 4096) && n % 64 == 0;
-}
+// acceptance, 5.97 -> 5.48 ms at three accepted steps (A/B on one box; 64-row tiles only up to N = 4096: 16.0 / 5.6).
+static bool wdma8_bn64(int n) { return n <= 16384 && n % 64 == 0; }
 static int wdma8_split_count(int n, int k) {                           // 1: no split
   const int t128 = wdma8_bn64(n) ? (n + 63) / 64 : (n + 127) / 128, n_kt = k / 128;
   if (t128 >= 150) return 1;

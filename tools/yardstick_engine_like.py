@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One user's wide projections as the ENGINE runs them (packed operands, SwiGLU epilogue for gate_up, fp32 logits for the lm_head), cold weights:
-us per launch and GB/s of W at 20 / 60 / 100 / 225 tokens.  A/B with ATSPEED_GEMM_WDMA=0 (tools/ab_env.sh)."""
+us per launch and GB/s of W at 20 / 60 / 100 / 225 tokens."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
