@@ -551,12 +551,7 @@ int ats_tree_attention_segs(const void* q, int ldq, const SegTable& t, const Seg
 #define ATS_ATTN32(DHV, NWV)                                                                                                   \
   {                                                                                                                            \
     constexpr int lds_bytes = 2 * (64 * DHV * 2 + 64 * (DHV * 2 + 32));                                                        \
-    static thread_local AtsPerDeviceFlag attr_flag;                                                                            \
-    bool& attr_done = attr_flag.cur();                                                                                         \
-    if (!attr_done) {                                                                                                          \
-      ATS_HIP(hipFuncSetAttribute((const void*)tree_attn32_kernel<DHV, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)); \
-      attr_done = true;                                                                                                        \
-    }                                                                                                                          \
+    ATS_TRY((ats_lds_limit<tree_attn32_kernel<DHV, NWV>>(lds_bytes)));                                                        \
     tree_attn32_kernel<DHV, NWV><<<mgrid, 64 * NWV, lds_bytes, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words,    \
                                                                      (bf16_t*)out, ldo, pk, n_heads, scale);                       \
   }
@@ -576,12 +571,7 @@ int ats_tree_attention_segs(const void* q, int ldq, const SegTable& t, const Seg
       if (nw <= 8 && (int)(t.n_qtiles * n_heads) <= ring_max_wgs && ring_lds <= 160 * 1024 - 64) {
 #define ATS_ATTN_RING(DHV, NWV)                                                                                                \
   {                                                                                                                            \
-    static thread_local AtsPerDeviceFlag attr_flag;                                                                            \
-    bool& attr_done = attr_flag.cur();                                                                                         \
-    if (!attr_done) {                                                                                                          \
-      ATS_HIP(hipFuncSetAttribute((const void*)tree_attn_mfma_kernel<DHV, NWV, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64)); \
-      attr_done = true;                                                                                                        \
-    }                                                                                                                          \
+    ATS_TRY((ats_lds_limit<tree_attn_mfma_kernel<DHV, NWV, 4>>(160 * 1024 - 64)));                                             \
     tree_attn_mfma_kernel<DHV, NWV, 4><<<mgrid, 64 * NWV, ring_lds, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words, \
                                                                           (bf16_t*)out, ldo, pk, n_heads, scale);                  \
   }

@@ -83,6 +83,17 @@ struct AtsPerDeviceFlag {
   bool never = false;                 // unknown device: "not done yet" every time (the attribute call is simply repeated)
   bool& cur() { const int d = ats_cur_device(); if (d < 0) { never = false; return never; } return done[d]; }
 };
+// raise a kernel's dynamic-LDS limit above the default, once per (host thread, device)
+template <auto KERNEL>
+inline int ats_lds_limit(int bytes) {
+  static thread_local AtsPerDeviceFlag flag;
+  bool& done = flag.cur();
+  if (!done) {
+    ATS_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done = true;
+  }
+  return ATSPEED_OK;
+}
 
 // ---------------------------------------------------------------- packed GEMM-operand layout
 // What the LDS-DMA of the ring GEMMs wants from HBM (measured, tools/probe/dma_depth.hip: 83 GB/s per CU against 55 GB/s): every

@@ -2,7 +2,7 @@
 //
 //   C[M,N] (+)= A[M,K] * W[N,K]^T      A, W row-major with K contiguous (HF nn.Linear layout)
 //
-// Two regimes, two kernels (dispatch in ats_gemm / big_kernel_applies):
+// Two regimes, two kernels (dispatch: plan_gemm, plan_fp8):
 //   * gemm_kernel<T,...>  — M = one user's tokens (tens to a few hundred): every launch is one pass over W and is
 //     bound by that HBM stream.  256 threads = 4 waves, tile BM x {64,128} x (128 bytes of K), LDS double buffered,
 //     register-staged 16-byte loads one tile ahead; 16-byte chunk c of LDS row r lives at chunk c ^ (r & 7);
@@ -1371,15 +1371,10 @@ int launch_big(const bf16_t* x, const bf16_t* w, void* c, int m, int n, int k, i
   constexpr int gm = ATS_RING_GM;
   const int tiles_n = (n + 255) / 256;
   constexpr int LDS8 = EPI == EPI_F32_LSE ? 136 * 1024 : 128 * 1024, LDS4 = EPI == EPI_F32_LSE ? 100 * 1024 : 96 * 1024;
-  static thread_local AtsPerDeviceFlag attr_flag;
-  bool& attr_done = attr_flag.cur();
-  if (!attr_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8));
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4));
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI, 8, false, false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8));
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI, 4, false, false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4));
-    attr_done = true;
-  }
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, 8, false>>(LDS8)));
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, 4, false>>(LDS4)));
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, 8, false, false, 4, true>>(LDS8)));
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, 4, false, false, 4, true>>(LDS4)));
   const int t256 = tiles_n * ((m + 255) / 256), t128 = tiles_n * ((m + 127) / 128);
   const BigChoice ch = big_choose(t256, t128, k);
   const bool use256 = ch.rows256;
@@ -1538,13 +1533,8 @@ int launch_big_fp8(const unsigned char* x, const float* sx, const unsigned char*
                    int ldc, hipStream_t st, int pk, const RopeEpi& rope = RopeEpi{}) {
   constexpr int gm = 4;
   const int tiles_n = (n + 255) / 256;
-  static thread_local AtsPerDeviceFlag mx_flag;
-  bool& mx_done = mx_flag.cur();
-  if (!mx_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_mx_kernel<EPI, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_mx_kernel<EPI, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    mx_done = true;
-  }
+  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI, 8>>(128 * 1024)));
+  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI, 4>>(96 * 1024)));
   const int t256 = tiles_n * ((m + 255) / 256), t128 = tiles_n * ((m + 127) / 128);
   if (big_use_256_rows(t256, t128))
     hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI, 8>), dim3(t256), dim3(512), 128 * 1024, st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, ldc, tiles_n, (m + 255) / 256, gm, pk, rope);
@@ -1890,16 +1880,9 @@ static int ring_split_count(int m, int n, int k) {
   if (s > max_s) s = max_s;
   return s >= 1 ? s : 0;
 }
-template <int EPI>
-int launch_ring_split(const bf16_t* a, const bf16_t* w, void* c, int m, int n, int k, int lda, int ldc, int splits, float* partial,
-                      hipStream_t st, FusedNorm* fn, int pk) {
-  static thread_local AtsPerDeviceFlag attr_flag;
-  bool& attr_done = attr_flag.cur();
-  if (!attr_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI_F32, 8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI_F32, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr_done = true;
-  }
+static int launch_ring_split(const bf16_t* a, const bf16_t* w, float* partial, int m, int n, int k, int lda, int splits, hipStream_t st, int pk) {
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 8, false, true>>(128 * 1024)));
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 4, false, true>>(96 * 1024)));
   const int tiles_n = (n + 255) / 256;
   const float* none = nullptr;
   const int tiles_m = (m + 255) / 256;
@@ -1911,8 +1894,7 @@ int launch_ring_split(const bf16_t* a, const bf16_t* w, void* c, int m, int n, i
                        none, none, (void*)partial, m, n, k, lda, n, tiles_n, 1, 1, splits, (float*)nullptr, (const unsigned char*)nullptr, pk);
   ATS_LAUNCH_CHECK();
   ats_count_path(ATS_PATH_RING_SPLIT);
-  if (c == nullptr) return ATSPEED_OK;          // partials only: the caller's next kernel sums the slabs itself (ats_gemm_partials)
-  return reduce_splits<bf16_t, EPI>(partial, c, m, n, ldc, splits, st, fn, pk);
+  return ATSPEED_OK;
 }
 
 // ---- K-cut form of the ring kernel for the bf16 / fp16 N <= 4096 projections (o_proj, down) at 257-1100 tokens (round 6; 4-16 users in lock
@@ -1935,13 +1917,8 @@ static int kcut_split_count(int m, int n, int k, int lda, bool* rows256 = nullpt
   return s_ >= 2 ? s_ : 0;
 }
 static int launch_ring_kcut(const bf16_t* a, const bf16_t* w, float* partial, int m, int n, int k, int lda, int splits, bool rows256, hipStream_t st, int pk) {
-  static thread_local AtsPerDeviceFlag attr_flag;
-  bool& attr_done = attr_flag.cur();
-  if (!attr_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI_F32, 8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI_F32, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr_done = true;
-  }
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 8, false, true>>(128 * 1024)));
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 4, false, true>>(96 * 1024)));
   const int tiles_n = (n + 255) / 256, tiles_m = rows256 ? (m + 255) / 256 : (m + 127) / 128;
   const float* none = nullptr;
   if (rows256)
@@ -1955,26 +1932,27 @@ static int launch_ring_kcut(const bf16_t* a, const bf16_t* w, float* partial, in
   return ATSPEED_OK;
 }
 
+// the LDS-tiled kernel; SPLIT (p.splits > 1) stores fp32 slabs [z][M][N] to `partial`, the caller reduces them
 template <typename T, int BM, int BN, int WM, int WN, int EPI>
-int launch_cfg(const T* a, const T* w, void* c, int m, int n, int k, int lda, int ldc, const Plan& p, float* partial,
-               hipStream_t st, FusedNorm* fn, int pk) {
+int launch_cfg(const T* a, const T* w, void* c, int m, int n, int k, int lda, int ldc, const Plan& p, float* partial, hipStream_t st, int pk) {
   using Cfg = TileCfg<T, BM, BN, WM, WN>;
   dim3 grid((n + BN - 1) / BN, (m + BM - 1) / BM, p.splits);
   size_t lds = 2 * Cfg::STAGE_BYTES;
-  if (p.splits > 1) {
-    auto kern = gemm_kernel<T, BM, BN, WM, WN, EPI, true>;
-    hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, st, a, w, c, m, n, k, lda, ldc, p.k_per_split, partial, pk);
-    ATS_LAUNCH_CHECK();
-    ats_count_path(ATS_PATH_TILED);
-    if (c == nullptr) return ATSPEED_OK;        // partials only: the caller's next kernel sums the slabs itself (ats_gemm_partials)
-    return reduce_splits<T, EPI>(partial, c, m, n, ldc, p.splits, st, fn, pk);
-  } else {
-    auto kern = gemm_kernel<T, BM, BN, WM, WN, EPI, false>;
-    hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, st, a, w, c, m, n, k, lda, ldc, p.k_per_split, partial, pk);
-    ATS_LAUNCH_CHECK();
-    ats_count_path(ATS_PATH_TILED);
-  }
+  if (p.splits > 1) hipLaunchKernelGGL((gemm_kernel<T, BM, BN, WM, WN, EPI, true>), grid, dim3(kThreads), lds, st, a, w, c, m, n, k, lda, ldc, p.k_per_split, partial, pk);
+  else              hipLaunchKernelGGL((gemm_kernel<T, BM, BN, WM, WN, EPI, false>), grid, dim3(kThreads), lds, st, a, w, c, m, n, k, lda, ldc, p.k_per_split, partial, pk);
+  ATS_LAUNCH_CHECK();
+  ats_count_path(ATS_PATH_TILED);
   return ATSPEED_OK;
+}
+template <typename T, int EPI>
+int launch_tiled(const Plan& p, const T* a, const T* w, void* c, int m, int n, int k, int lda, int ldc, float* partial, hipStream_t st, int pk) {
+  if (p.bn == 64) return launch_cfg<T, 128, 64, 2, 2, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, pk);
+  switch (p.bm) {
+    case 16:  return launch_cfg<T, 16, 128, 1, 4, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, pk);
+    case 32:  return launch_cfg<T, 32, 128, 1, 4, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, pk);
+    case 64:  return launch_cfg<T, 64, 128, 1, 4, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, pk);
+    default:  return launch_cfg<T, 128, 128, 2, 2, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, pk);
+  }
 }
 
 
@@ -1995,15 +1973,10 @@ static bool wdma_applies(int m, int n, int k, int lda, int epilogue) {
 }
 template <int BM, int BN, int NST, int EPI, int WM = 2>
 int launch_wdma_cfg(const bf16_t* a, const bf16_t* w, void* c, int m, int n, int k, int lda, int ldc, hipStream_t st, int pk) {
-  auto kern = gemm_wdma_kernel<BM, BN, NST, EPI, false, WM>;
   constexpr int lds = NST * (BM + BN) * 128;
-  static thread_local AtsPerDeviceFlag attr_flag;
-  bool& attr_done = attr_flag.cur();
-  if (!attr_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((n + BN - 1) / BN), dim3(128 * WM), lds, st, (const void*)a, (const void*)w, c, m, n, k, lda, ldc, pk, 1, (const float*)nullptr, (const float*)nullptr, RopeEpi{});
+  ATS_TRY((ats_lds_limit<gemm_wdma_kernel<BM, BN, NST, EPI, false, WM>>(lds)));
+  hipLaunchKernelGGL((gemm_wdma_kernel<BM, BN, NST, EPI, false, WM>), dim3((n + BN - 1) / BN), dim3(128 * WM), lds, st, (const void*)a, (const void*)w, c, m, n, k, lda, ldc, pk, 1,
+                     (const float*)nullptr, (const float*)nullptr, RopeEpi{});
   ATS_LAUNCH_CHECK();
   ats_count_path(ATS_PATH_WDMA);
   return ATSPEED_OK;
@@ -2022,15 +1995,10 @@ static int wdma_split_count(int m, int n, int k, int lda) {
 }
 template <int BM, int NST, int WM = 2>
 int launch_wdma_split_cfg(const bf16_t* a, const bf16_t* w, float* partial, int m, int n, int k, int lda, int splits, hipStream_t st, int pk) {
-  auto kern = gemm_wdma_kernel<BM, 128, NST, EPI_F32, true, WM>;
   constexpr int lds = NST * (BM + 128) * 128;
-  static thread_local AtsPerDeviceFlag attr_flag;
-  bool& attr_done = attr_flag.cur();
-  if (!attr_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((n + 127) / 128, splits), dim3(128 * WM), lds, st, (const void*)a, (const void*)w, (void*)partial, m, n, k, lda, n, pk, splits, (const float*)nullptr, (const float*)nullptr, RopeEpi{});
+  ATS_TRY((ats_lds_limit<gemm_wdma_kernel<BM, 128, NST, EPI_F32, true, WM>>(lds)));
+  hipLaunchKernelGGL((gemm_wdma_kernel<BM, 128, NST, EPI_F32, true, WM>), dim3((n + 127) / 128, splits), dim3(128 * WM), lds, st, (const void*)a, (const void*)w, (void*)partial,
+                     m, n, k, lda, n, pk, splits, (const float*)nullptr, (const float*)nullptr, RopeEpi{});
   ATS_LAUNCH_CHECK();
   ats_count_path(ATS_PATH_WDMA_SPLIT);
   return ATSPEED_OK;
@@ -2042,8 +2010,7 @@ static int launch_wdma_split(const bf16_t* a, const bf16_t* w, float* partial, i
 }
 template <int EPI>
 int launch_wdma(const bf16_t* a, const bf16_t* w, void* c, int m, int n, int k, int lda, int ldc, hipStream_t st, int pk) {
-  const int t192 = (n + 191) / 192, t128 = (n + 127) / 128;
-  const bool ok128 = t128 >= 150 && t128 <= 256;
+  const bool ok128 = (n + 127) / 128 >= 150 && (n + 127) / 128 <= 256;
   // tile width: 128 weight rows when that gives 150-256 workgroups, else 192 (the lm_head: 257 tiles of 128 would spill one into a second round)
   if (m <= 64) {
     if (ok128) return launch_wdma_cfg<64, 128, 6, EPI>(a, w, c, m, n, k, lda, ldc, st, pk);           // 24 KB x 6
@@ -2053,7 +2020,6 @@ int launch_wdma(const bf16_t* a, const bf16_t* w, void* c, int m, int n, int k, 
     if (ok128) return launch_wdma_cfg<128, 128, 4, EPI>(a, w, c, m, n, k, lda, ldc, st, pk);          // 32 KB x 4 (x 5 = all 160 KB: no faster)
     return launch_wdma_cfg<128, 192, 3, EPI>(a, w, c, m, n, k, lda, ldc, st, pk);                     // 40 KB x 3
   }
-  (void)t192;
   return launch_wdma_cfg<256, 128, 3, EPI, 4>(a, w, c, m, n, k, lda, ldc, st, pk);                    // 129-256 tokens: 48 KB x 3 (the X rows are two thirds of a stage), 8 waves
 }
 
@@ -2081,171 +2047,176 @@ static int panel_split_count(int n, int k) {                           // 1: no 
   if (t128 >= 150) return 1;
   return std::max(1, std::min(256 / t128, units / 4));                 // at least 4 units (512 k) per part
 }
-template <int EPI, int MT2, bool SPLIT>
-int launch_panel_cfg(const bf16_t* x, const bf16_t* w, void* c, int m, int n, int k, int ldx, int ldc, int splits, hipStream_t st, int pk) {
-  auto kern = gemm_ring_kernel<EPI, MT2, false, SPLIT, 4, false, 2, 4>;
+template <int EPI, bool SPLIT>
+int launch_panel(const bf16_t* x, const bf16_t* w, void* c, int m, int n, int k, int ldx, int ldc, int splits, hipStream_t st, int pk) {
+  constexpr int MT2 = 6;
   constexpr int lds = 4 * (128 + 4 * MT2 * 16) * 64;                   // 128 KB at 384 token rows
-  static thread_local AtsPerDeviceFlag attr_flag;
-  bool& attr_done = attr_flag.cur();
-  if (!attr_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_done = true;
-  }
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, MT2, false, SPLIT, 4, false, 2, 4>>(lds)));
   const int tiles_n = (n + 127) / 128;
   const float* none = nullptr;
-  hipLaunchKernelGGL(kern, dim3(tiles_n * (SPLIT ? splits : 1)), dim3(512), lds, st, (const void*)x, (const void*)w, none, none, c, m, n, k, ldx, ldc,
-                     tiles_n, 1, 1, SPLIT ? splits : 1, (float*)nullptr, (const unsigned char*)nullptr, pk, RopeEpi{}, SkTail{});
+  hipLaunchKernelGGL((gemm_ring_kernel<EPI, MT2, false, SPLIT, 4, false, 2, 4>), dim3(tiles_n * (SPLIT ? splits : 1)), dim3(512), lds, st, (const void*)x, (const void*)w,
+                     none, none, c, m, n, k, ldx, ldc, tiles_n, 1, 1, SPLIT ? splits : 1, (float*)nullptr, (const unsigned char*)nullptr, pk, RopeEpi{}, SkTail{});
   ATS_LAUNCH_CHECK();
   ats_count_path(SPLIT ? ATS_PATH_PANEL_SPLIT : ATS_PATH_PANEL);
   return ATSPEED_OK;
 }
-template <int EPI>
-int launch_panel(const bf16_t* x, const bf16_t* w, void* c, int m, int n, int k, int ldx, int ldc, hipStream_t st, int pk) {
-  return launch_panel_cfg<EPI, 6, false>(x, w, c, m, n, k, ldx, ldc, 1, st, pk);
+
+// the 256-wide ring kernel (launch_big) vs the 128-wide LDS-tiled kernel (with split-K): the ring kernel wins once its tile grid keeps a fair share
+// of the 256 CUs busy -- crossover measured at ~50-60 % (tools/gemm_ab.py: o_proj, down, qkv, gate_up at 512-1920 tokens)
+static bool ring_fills(int m, int n) {
+  const int tn = (n + 255) / 256;
+  return big_fill_pct(tn * ((m + 255) / 256)) >= 60 || big_fill_pct(tn * ((m + 127) / 128)) >= 60;
 }
-static int launch_panel_split(const bf16_t* x, const bf16_t* w, float* partial, int m, int n, int k, int ldx, int splits, hipStream_t st, int pk) {
-  return launch_panel_cfg<EPI_F32, 6, true>(x, w, (void*)partial, m, n, k, ldx, n, splits, st, pk);
+static bool big_kernel_applies(int m, int n, int k, int lda, int ldc, int epilogue, bool lm_head) {
+  // from 257 tokens (two token tiles): measured against the split-K mode at 300-500 tokens, gate_up 115-138 -> 96-108 us, qkv 80 -> 75 us
+  constexpr int big_min_m = 257;
+  if (m < big_min_m || k % 128 != 0 || (lda % 8) != 0 || !dma_offsets_fit(n, k, 2) || !dma_offsets_fit(m, lda, 2)) return false;
+  if (epilogue == EPI_SWIGLU && ((ldc & 3) != 0 || n % 32 != 0)) return false;
+  // 257-384 tokens on a projection of 16-256 panels: the panel form, also where its slabs do not fit the workspace.  Not the lm_head with the fused
+  // normaliser (a vocabulary of 150-256 panels, e.g. the stock 32000, at 257-352 logit rows would leave the fused-LSE / tile_store ring
+  // path for panel<EPI_F32> + a separate LSE pass, a regime the panel sweep never measured; Beauty's 32859 misses the band by one panel)
+  if (!lm_head && panel_applies(m, n, k, lda)) return false;
+  if (ring_fills(m, n)) return true;
+  // a thin grid whose k-steps the split-K tail spreads over the chip: from 48 tiles of 128 rows (four parts per tile on 192 CUs; N = 4096
+  // from 257 tokens), where it overtakes the LDS-tiled split-K kernel + reduce pass (tools/sk_sweep.py: o_proj at 320 tokens 36.7 -> 34.1 us,
+  // down 73.6 -> 70.3; at 400 tokens 33.7 -> 29.6 and 68.4 -> 59.7)
+  constexpr int sk_min_tiles = 48;
+  const int t128 = ((n + 255) / 256) * ((m + 127) / 128);
+  return t128 >= sk_min_tiles && sk_any_plan(t128, k);
 }
 
-template <typename T, int EPI>
-int launch_epi(const T* a, const T* w, void* c, int m, int n, int k, int lda, int ldc, float* partial, size_t ws_bytes,
-               hipStream_t st, FusedNorm* fn, int pk) {
-  if constexpr (sizeof(T) == 2 && (EPI == EPI_STORE || EPI == EPI_F32 || EPI == EPI_RESID)) {
-    bool r256 = false;
-    const int ks = kcut_split_count(m, n, k, lda, &r256);
-    if (ks >= 2 && (size_t)ks * m * n * sizeof(float) <= ws_bytes && ((uintptr_t)partial & 15) == 0) {
-      ATS_TRY(launch_ring_kcut(a, w, partial, m, n, k, lda, ks, r256, st, pk));
-      return reduce_splits<bf16_t, EPI>(partial, c, m, n, ldc, ks, st, fn, pk);
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (panel_applies(m, n, k, lda) && (EPI != EPI_SWIGLU || (n % 32 == 0 && (ldc & 3) == 0))) {
+// ---- the 16-bit planner: which form a projection GEMM (bf16 / fp16 / fp32) takes, the fitted dispatch model in its order.  K-cut -> panel ->
+// the ring kernel (its split-K tail is launch_big's own choice) -> weight-streaming -> weight-streaming split -> ring split -> LDS-tiled.  A split
+// form is taken only where its slabs fit the workspace; where they do not, the next form in the order runs.  lm_head: the logits projection with
+// the fused log-sum-exp (ats_lmhead_lse), which asks for the ring kernel only and never takes the K-cut or panel forms.
+enum { G16_KCUT, G16_PANEL, G16_PANEL_SPLIT, G16_RING, G16_WDMA, G16_WDMA_SPLIT, G16_RING_SPLIT, G16_TILED };
+struct GemmPlan {
+  int form = G16_TILED;
+  int splits = 1;
+  bool rows256 = false;     // K-cut: 256-row token tiles (else 128)
+  Plan tiled{};             // G16_TILED: tile shape and split of the LDS-tiled kernel
+  size_t slab_bytes = 0;    // fp32 slabs [splits][m][n] the form leaves in the workspace (0: it applies its epilogue itself)
+};
+static GemmPlan plan_gemm(int m, int n, int k, int lda, int ldc, int dtype, int epilogue, const void* ws, size_t ws_bytes, bool lm_head = false) {
+  const size_t slab = (size_t)m * n * sizeof(float);
+  const bool ws16 = ((uintptr_t)ws & 15) == 0;
+  GemmPlan p;
+  auto split = [&](int form, int s) { p.form = form; p.splits = s; p.slab_bytes = (size_t)s * slab; return p; };
+  if (dtype != ATSPEED_F32) {
+    const bool swiglu_ok = epilogue != EPI_SWIGLU || n % 32 == 0;
+    const int ks = lm_head || !(epilogue == EPI_STORE || epilogue == EPI_F32 || epilogue == EPI_RESID) ? 0 : kcut_split_count(m, n, k, lda, &p.rows256);
+    if (ks >= 2 && ws && ws16 && (size_t)ks * slab <= ws_bytes) return split(G16_KCUT, ks);
+    if (!lm_head && panel_applies(m, n, k, lda) && (epilogue != EPI_SWIGLU || (n % 32 == 0 && (ldc & 3) == 0))) {
       const int ps = panel_split_count(n, k);
-      if (ps == 1) return launch_panel<EPI>(a, w, c, m, n, k, lda, ldc, st, pk);
-      if ((size_t)ps * m * n * sizeof(float) <= ws_bytes && ((uintptr_t)partial & 15) == 0) {
-        ATS_TRY(launch_panel_split(a, w, partial, m, n, k, lda, ps, st, pk));
-        return reduce_splits<bf16_t, EPI>(partial, c, m, n, ldc, ps, st, fn, pk);
-      }
+      if (ps == 1) { p.form = G16_PANEL; return p; }
+      if ((size_t)ps * slab <= ws_bytes && ws16) return split(G16_PANEL_SPLIT, ps);
     }
-  }
-  if constexpr (sizeof(T) == 2 && (EPI == EPI_STORE || EPI == EPI_F32 || EPI == EPI_SWIGLU)) {
-    if (wdma_applies(m, n, k, lda, EPI)) return launch_wdma<EPI>(a, w, c, m, n, k, lda, ldc, st, pk);
-  }
-  if constexpr (sizeof(T) == 2) {
+    if (big_kernel_applies(m, n, k, lda, ldc, epilogue, lm_head)) { p.form = G16_RING; return p; }
+    if (wdma_applies(m, n, k, lda, epilogue)) { p.form = G16_WDMA; return p; }
     const int s = wdma_split_count(m, n, k, lda);
-    if (s >= 2 && (size_t)s * m * n * sizeof(float) <= ws_bytes && ((uintptr_t)partial & 15) == 0 && (EPI != EPI_SWIGLU || n % 32 == 0)) {
-      ATS_TRY(launch_wdma_split(a, w, partial, m, n, k, lda, s, st, pk));
-      return reduce_splits<bf16_t, EPI>(partial, c, m, n, ldc, s, st, fn, pk);
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
+    if (s >= 2 && (size_t)s * slab <= ws_bytes && ws16 && swiglu_ok) return split(G16_WDMA_SPLIT, s);
     const int rs = ring_split_count(m, n, k);
-    if (rs >= 1 && (lda % 8) == 0 && (size_t)rs * m * n * sizeof(float) <= ws_bytes && (EPI != EPI_SWIGLU || n % 32 == 0))
-      return launch_ring_split<EPI>(a, w, c, m, n, k, lda, ldc, rs, partial, st, fn, pk);
+    if (rs >= 1 && (lda % 8) == 0 && (size_t)rs * slab <= ws_bytes && swiglu_ok) return split(G16_RING_SPLIT, rs);
   }
-  Plan p = make_plan<T>(m, n, k);
-  if (p.bn == 64 && p.bm != 128) p.bn = 128;
-  if (p.splits > 1 && (size_t)p.splits * m * n * sizeof(float) > ws_bytes) {   // not enough workspace: no split
-    p.splits = 1;
-    p.k_per_split = ((k + GemmTraits<T>::BK - 1) / GemmTraits<T>::BK) * GemmTraits<T>::BK;
+  p.tiled = dtype == ATSPEED_F32 ? make_plan<float>(m, n, k) : make_plan<bf16_t>(m, n, k);
+  if (p.tiled.splits > 1 && (size_t)p.tiled.splits * slab > ws_bytes) {    // not enough workspace: no split
+    const int bk = dtype == ATSPEED_F32 ? GemmTraits<float>::BK : GemmTraits<bf16_t>::BK;
+    p.tiled.splits = 1;
+    p.tiled.k_per_split = ((k + bk - 1) / bk) * bk;
   }
-  if (p.bn == 64 && p.bm == 128) return launch_cfg<T, 128, 64, 2, 2, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, fn, pk);
-  switch (p.bm) {
-    case 16:  return launch_cfg<T, 16, 128, 1, 4, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, fn, pk);
-    case 32:  return launch_cfg<T, 32, 128, 1, 4, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, fn, pk);
-    case 64:  return launch_cfg<T, 64, 128, 1, 4, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, fn, pk);
-    default:  return launch_cfg<T, 128, 128, 2, 2, EPI>(a, w, c, m, n, k, lda, ldc, p, partial, st, fn, pk);
-  }
+  return p.tiled.splits > 1 ? split(G16_TILED, p.tiled.splits) : p;
 }
 
-template <typename T>
-int launch_typed(const void* a, const void* w, void* c, int m, int n, int k, int lda, int ldc, int epi, void* ws,
-                 size_t ws_bytes, hipStream_t st, int pk) {
-  const T* A = (const T*)a; const T* Wt = (const T*)w; float* P = (float*)ws;
-  switch (epi) {
-    case EPI_STORE:  return launch_epi<T, EPI_STORE>(A, Wt, c, m, n, k, lda, ldc, P, ws_bytes, st, nullptr, pk);
-    case EPI_F32:    return launch_epi<T, EPI_F32>(A, Wt, c, m, n, k, lda, ldc, P, ws_bytes, st, nullptr, pk);
-    case EPI_RESID:  return launch_epi<T, EPI_RESID>(A, Wt, c, m, n, k, lda, ldc, P, ws_bytes, st, nullptr, pk);
-    case EPI_SWIGLU: return launch_epi<T, EPI_SWIGLU>(A, Wt, c, m, n, k, lda, ldc, P, ws_bytes, st, nullptr, pk);
+// the slab half of a split plan: fp32 partial sums [splits][m][n] in `partial` (c, ldc: what the LDS-tiled kernel is handed)
+template <typename T, int EPI>
+int launch_slabs(const GemmPlan& p, const T* a, const T* w, void* c, int m, int n, int k, int lda, int ldc, float* partial, hipStream_t st, int pk) {
+  if constexpr (sizeof(T) == 2) {
+    switch (p.form) {
+      case G16_KCUT:        return launch_ring_kcut(a, w, partial, m, n, k, lda, p.splits, p.rows256, st, pk);
+      case G16_PANEL_SPLIT: return launch_panel<EPI_F32, true>(a, w, (void*)partial, m, n, k, lda, n, p.splits, st, pk);
+      case G16_WDMA_SPLIT:  return launch_wdma_split(a, w, partial, m, n, k, lda, p.splits, st, pk);
+      case G16_RING_SPLIT:  return launch_ring_split(a, w, partial, m, n, k, lda, p.splits, st, pk);
+    }
   }
-  atspeed_set_error("gemm: unknown epilogue %d", epi);
-  return ATSPEED_ERR_INVALID;
+  return launch_tiled<T, EPI>(p.tiled, a, w, c, m, n, k, lda, ldc, partial, st, pk);
+}
+// the launcher: runs a plan, the split forms followed by their reduce pass (fused with the next RMSNorm for the residual projections when fn is given)
+template <typename T, int EPI>
+int run_plan(const GemmPlan& p, const T* a, const T* w, void* c, int m, int n, int k, int lda, int ldc, float* partial, hipStream_t st, FusedNorm* fn,
+             int pk, const SkArena* sk) {
+  if (p.slab_bytes) {
+    ATS_TRY((launch_slabs<T, EPI>(p, a, w, c, m, n, k, lda, ldc, partial, st, pk)));
+    return reduce_splits<T, EPI>(partial, c, m, n, ldc, p.splits, st, fn, pk);
+  }
+  if constexpr (sizeof(T) == 2) {
+    if (p.form == G16_PANEL) return launch_panel<EPI, false>(a, w, c, m, n, k, lda, ldc, 1, st, pk);
+    if (p.form == G16_RING) return launch_big<EPI>(a, w, c, m, n, k, lda, ldc, st, pk, RopeEpi{}, nullptr, nullptr, sk);
+    if constexpr (EPI != EPI_RESID) { if (p.form == G16_WDMA) return launch_wdma<EPI>(a, w, c, m, n, k, lda, ldc, st, pk); }
+  }
+  return launch_tiled<T, EPI>(p.tiled, a, w, c, m, n, k, lda, ldc, partial, st, pk);
 }
 
 }  // namespace
 
-size_t ats_gemm_workspace_bytes(int m, int n, int k, int dtype) {
-  Plan p = dtype == ATS_HALF ? make_plan<bf16_t>(m, n, k) : make_plan<float>(m, n, k);
-  size_t b = p.splits > 1 ? (size_t)p.splits * m * n * sizeof(float) : 0;
-  if (dtype == ATS_HALF) b = std::max(b, (size_t)ring_split_count(m, n, k) * m * n * sizeof(float));
-  if (dtype == ATS_HALF) b = std::max(b, (size_t)wdma_split_count(m, n, k, k) * m * n * sizeof(float));
-  if (dtype == ATS_HALF && panel_applies(m, n, k, k) && panel_split_count(n, k) > 1) b = std::max(b, (size_t)panel_split_count(n, k) * m * n * sizeof(float));
-  if (dtype == ATS_HALF) b = std::max(b, (size_t)kcut_split_count(m, n, k, k) * m * n * sizeof(float));
-  return b;
+// a runtime epilogue code as the template argument of f (STORE / F32 / RESID / SWIGLU; any other code is refused)
+template <typename F>
+static int with_epi(int epilogue, const char* who, F&& f) {
+  switch (epilogue) {
+    case EPI_STORE:  return f(std::integral_constant<int, EPI_STORE>{});
+    case EPI_F32:    return f(std::integral_constant<int, EPI_F32>{});
+    case EPI_RESID:  return f(std::integral_constant<int, EPI_RESID>{});
+    case EPI_SWIGLU: return f(std::integral_constant<int, EPI_SWIGLU>{});
+  }
+  atspeed_set_error("%s: unknown epilogue %d", who, epilogue);
+  return ATSPEED_ERR_INVALID;
+}
+// the reduce pass of the W8A8 / W4A8 split forms (16-bit output, no fused norm)
+static int reduce_slabs(int epilogue, const char* who, const void* ws, void* c, int m, int n, int ldc, int splits, hipStream_t st, int pk) {
+  return with_epi(epilogue, who, [&](auto e) { return reduce_splits<bf16_t, decltype(e)::value>((const float*)ws, c, m, n, ldc, splits, st, nullptr, pk); });
+}
+// the residual projections' tail: h += the slabs' sum (slabs: null when the GEMM applied its residual epilogue itself), then the next op's
+// input norm -- xn and / or the e4m3 rows + scales (fn.q) a following W8A8 projection reads -- fused into that reduce pass where it can be,
+// else the norm kernels
+static int resid_norm_tail(FusedNorm& fn, const float* slabs, int splits, void* h, int m, int n, int ldh, int dtype, hipStream_t st, int pk) {
+  if (slabs) ATS_TRY((reduce_splits<bf16_t, EPI_RESID>(slabs, h, m, n, ldh, splits, st, &fn, pk)));
+  if (fn.done) return ATSPEED_OK;
+  return fn.q ? ats_rmsnorm_quant_fp8(h, fn.w, fn.xn, fn.q, fn.qscale, m, n, fn.eps, st, pk) : ats_rmsnorm(h, fn.w, fn.xn, m, n, fn.eps, dtype, st, pk);
+}
+// the operands of an entry point that leaves slabs only: present and 16-byte aligned
+static int slab_operands_ok(const char* who, const void* a, const void* w, const void* ws) {
+  ATS_REQUIRE(a && w && ws, ATSPEED_ERR_INVALID, "%s: null operand", who);
+  ATS_REQUIRE((((uintptr_t)a | (uintptr_t)w) & 15) == 0, ATSPEED_ERR_INVALID, "%s: operands must be 16-byte aligned", who);
+  return ATSPEED_OK;
 }
 
-static bool big_kernel_applies(int m, int n, int k, int lda, int ldc, int dtype, int epilogue, bool lm_head = false);
-// does this launch take the K-cut form (launch_epi)?  Then the ring kernel's dispatch (big_kernel_applies) does not get it.
-static bool kcut_takes(int m, int n, int k, int lda, int dtype, int epilogue, const void* ws, size_t ws_bytes) {
-  if (dtype != ATS_HALF || !(epilogue == EPI_STORE || epilogue == EPI_F32 || epilogue == EPI_RESID)) return false;
-  const int ks = kcut_split_count(m, n, k, lda);
-  return ks >= 2 && ws && ((uintptr_t)ws & 15) == 0 && (size_t)ks * m * n * sizeof(float) <= ws_bytes;
+size_t ats_gemm_workspace_bytes(int m, int n, int k, int dtype) {
+  // the largest slab set any form may take at this shape (the engine's lda == K), workspace permitting
+  Plan p = dtype == ATS_HALF ? make_plan<bf16_t>(m, n, k) : make_plan<float>(m, n, k);
+  int s = p.splits > 1 ? p.splits : 0;
+  if (dtype == ATS_HALF) {
+    s = std::max({s, ring_split_count(m, n, k), wdma_split_count(m, n, k, k), kcut_split_count(m, n, k, k)});
+    if (panel_applies(m, n, k, k) && panel_split_count(n, k) > 1) s = std::max(s, panel_split_count(n, k));
+  }
+  return (size_t)s * m * n * sizeof(float);
 }
 
 // One user's wide bf16 projection as fp32 split-K slabs [splits][m][n] in the workspace, WITHOUT the reduce pass: the consumer sums the
-// slabs while it reads them (RoPE + KV scatter after the qkv projection: one launch less per layer).  *splits_out = 0 when this shape does
-// not take the split-K ring path (the caller then runs the ordinary ats_gemm).
+// slabs while it reads them (RoPE + KV scatter after the qkv projection: one launch less per layer).  Round 6 added the LDS-tiled kernel's
+// slabs (the draft's forwards, one user's K-beam final step, beamSD.py:505-509): the RoPE kernel sums them in the same order and rounds as the
+// reduce pass stored.  *splits_out = 0 when the plan leaves no slabs (the caller then runs the ordinary ats_gemm).
 int ats_gemm_partials(const void* a, const void* w, int m, int n, int k, int lda, int dtype, void* workspace, size_t workspace_bytes,
                       hipStream_t st, int* splits_out, int pk) {
   *splits_out = 0;
-  if (dtype != ATS_HALF || m <= 0 || big_kernel_applies(m, n, k, lda, n, dtype, EPI_STORE)) return ATSPEED_OK;
-  if (panel_applies(m, n, k, lda)) {
-    const int ps = panel_split_count(n, k);
-    if (ps >= 2 && (n % 4) == 0 && ((uintptr_t)workspace & 15) == 0 && (size_t)ps * m * n * sizeof(float) <= workspace_bytes) {
-      ATS_REQUIRE(a && w && workspace, ATSPEED_ERR_INVALID, "gemm: null operand");
-      ATS_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)w & 15) == 0, ATSPEED_ERR_INVALID, "gemm: operands must be 16-byte aligned");
-      ATS_TRY(launch_panel_split((const bf16_t*)a, (const bf16_t*)w, (float*)workspace, m, n, k, lda, ps, st, pk));
-      *splits_out = ps;
-    }
-    return ATSPEED_OK;
-  }
-  if (wdma_applies(m, n, k, lda, EPI_STORE)) return ATSPEED_OK;        // the no-split kernel writes bf16 qkv itself: the caller runs ats_gemm + the plain RoPE pass
-  {
-    const int s = wdma_split_count(m, n, k, lda);
-    if (s >= 2 && (n % 4) == 0 && ((uintptr_t)workspace & 15) == 0 && (size_t)s * m * n * sizeof(float) <= workspace_bytes) {
-      ATS_REQUIRE(a && w && workspace, ATSPEED_ERR_INVALID, "gemm: null operand");
-      ATS_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)w & 15) == 0, ATSPEED_ERR_INVALID, "gemm: operands must be 16-byte aligned");
-      ATS_TRY(launch_wdma_split((const bf16_t*)a, (const bf16_t*)w, (float*)workspace, m, n, k, lda, s, st, pk));
-      *splits_out = s;
-      return ATSPEED_OK;
-    }
-  }
-  const int rs = ring_split_count(m, n, k);
-  if (rs >= 1 && (lda % 8) == 0 && (n % 4) == 0 && ((uintptr_t)workspace & 15) == 0 && (size_t)rs * m * n * sizeof(float) <= workspace_bytes) {
-    ATS_REQUIRE(a && w && workspace, ATSPEED_ERR_INVALID, "gemm: null operand");
-    ATS_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)w & 15) == 0, ATSPEED_ERR_INVALID, "gemm: operands must be 16-byte aligned");
-    ATS_TRY(launch_ring_split<EPI_STORE>((const bf16_t*)a, (const bf16_t*)w, nullptr, m, n, k, lda, n, rs, (float*)workspace, st, nullptr, pk));
-    *splits_out = rs;
-    return ATSPEED_OK;
-  }
-  // Round 6: the LDS-tiled split-K kernel's slabs too (up to 32 tokens: the K-beam final step of one user, beamSD.py:505-509; the draft's forwards).
-  // Its reduce pass was one more launch per layer; the RoPE kernel sums the same slabs in the same order and rounds as the reduce pass stored.
-  if (k % 8 == 0 && lda % 8 == 0 && (n % 4) == 0 && workspace && ((uintptr_t)workspace & 15) == 0 && a && w && (((uintptr_t)a | (uintptr_t)w) & 15) == 0) {
-    Plan p = make_plan<bf16_t>(m, n, k);
-    if (p.bn == 64 && p.bm != 128) p.bn = 128;
-    if (p.splits > 1 && p.bn == 128 && (size_t)p.splits * m * n * sizeof(float) <= workspace_bytes) {
-      const bf16_t* A = (const bf16_t*)a; const bf16_t* Wt = (const bf16_t*)w; float* P = (float*)workspace;
-      int rc;
-      switch (p.bm) {
-        case 16:  rc = launch_cfg<bf16_t, 16, 128, 1, 4, EPI_STORE>(A, Wt, nullptr, m, n, k, lda, n, p, P, st, nullptr, pk); break;
-        case 32:  rc = launch_cfg<bf16_t, 32, 128, 1, 4, EPI_STORE>(A, Wt, nullptr, m, n, k, lda, n, p, P, st, nullptr, pk); break;
-        case 64:  rc = launch_cfg<bf16_t, 64, 128, 1, 4, EPI_STORE>(A, Wt, nullptr, m, n, k, lda, n, p, P, st, nullptr, pk); break;
-        default:  rc = launch_cfg<bf16_t, 128, 128, 2, 2, EPI_STORE>(A, Wt, nullptr, m, n, k, lda, n, p, P, st, nullptr, pk); break;
-      }
-      ATS_TRY(rc);
-      *splits_out = p.splits;
-    }
-  }
+  if (dtype != ATS_HALF || m <= 0 || (n % 4) != 0 || ((uintptr_t)workspace & 15) != 0) return ATSPEED_OK;
+  const GemmPlan p = plan_gemm(m, n, k, lda, n, dtype, EPI_STORE, workspace, workspace_bytes);
+  if (!p.slab_bytes) return ATSPEED_OK;
+  // a panel shape whose slabs do not fit: the caller's ats_gemm runs what follows the panel form in the order
+  if (p.form != G16_PANEL_SPLIT && panel_applies(m, n, k, lda)) return ATSPEED_OK;
+  // the LDS-tiled kernel: K and lda in whole 16-byte chunks, and its 128-wide tiles only
+  if (p.form == G16_TILED && (k % 8 != 0 || lda % 8 != 0 || p.tiled.bn != 128)) return ATSPEED_OK;
+  ATS_TRY(slab_operands_ok("gemm", a, w, workspace));
+  ATS_TRY((launch_slabs<bf16_t, EPI_STORE>(p, (const bf16_t*)a, (const bf16_t*)w, nullptr, m, n, k, lda, n, (float*)workspace, st, pk)));
+  *splits_out = p.splits;
   return ATSPEED_OK;
 }
 
@@ -2260,31 +2231,25 @@ int ats_gemm(const void* a, const void* w, void* c, int m, int n, int k, int lda
   ATS_REQUIRE(k % epc == 0 && lda % epc == 0, ATSPEED_ERR_INVALID, "gemm: K=%d / lda=%d must be multiples of %d", k, lda, epc);
   ATS_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)w & 15) == 0, ATSPEED_ERR_INVALID, "gemm: operands must be 16-byte aligned");
   ATS_REQUIRE(epilogue != EPI_SWIGLU || n % 32 == 0, ATSPEED_ERR_INVALID, "gemm: SwiGLU needs N %% 32 == 0 (N=%d)", n);
-  if (dtype == ATSPEED_F32) return launch_typed<float>(a, w, c, m, n, k, lda, ldc, epilogue, workspace, workspace_bytes, st, 0);
-  if (dtype == ATS_HALF) {
-    if (!kcut_takes(m, n, k, lda, dtype, epilogue, workspace, workspace_bytes) && big_kernel_applies(m, n, k, lda, ldc, dtype, epilogue)) {
-      const bf16_t* X = (const bf16_t*)a; const bf16_t* Wt = (const bf16_t*)w;
-      switch (epilogue) {
-        case EPI_STORE:  return launch_big<EPI_STORE>(X, Wt, c, m, n, k, lda, ldc, st, pk, RopeEpi{}, nullptr, nullptr, sk);
-        case EPI_F32:    return launch_big<EPI_F32>(X, Wt, c, m, n, k, lda, ldc, st, pk, RopeEpi{}, nullptr, nullptr, sk);
-        case EPI_RESID:  return launch_big<EPI_RESID>(X, Wt, c, m, n, k, lda, ldc, st, pk, RopeEpi{}, nullptr, nullptr, sk);
-        case EPI_SWIGLU: return launch_big<EPI_SWIGLU>(X, Wt, c, m, n, k, lda, ldc, st, pk, RopeEpi{}, nullptr, nullptr, sk);
-      }
-    }
-    return launch_typed<bf16_t>(a, w, c, m, n, k, lda, ldc, epilogue, workspace, workspace_bytes, st, pk);
-  }
-  atspeed_set_error("gemm: unknown dtype %d", dtype);
-  return ATSPEED_ERR_INVALID;
+  ATS_REQUIRE(dtype == ATSPEED_F32 || dtype == ATS_HALF, ATSPEED_ERR_INVALID, "gemm: unknown dtype %d", dtype);
+  const GemmPlan p = plan_gemm(m, n, k, lda, ldc, dtype, epilogue, workspace, workspace_bytes);
+  return with_epi(epilogue, "gemm", [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    if (dtype == ATSPEED_F32) return run_plan<float, EPI>(p, (const float*)a, (const float*)w, c, m, n, k, lda, ldc, (float*)workspace, st, nullptr, 0, sk);
+    return run_plan<bf16_t, EPI>(p, (const bf16_t*)a, (const bf16_t*)w, c, m, n, k, lda, ldc, (float*)workspace, st, nullptr, pk, sk);
+  });
 }
 
+// the batched qkv projection with RoPE + the KV scatter in the ring kernel's epilogue: where the plan takes the ring kernel (planned without a
+// workspace; the K-cut form, which needs one, never takes the qkv shape anyway: it wants N <= 4096 and K >= 2048, and here N = 3 K)
+static bool qkv_rope_ring(int m, int hidden) { return plan_gemm(m, 3 * hidden, hidden, hidden, 3 * hidden, ATS_HALF, EPI_STORE, nullptr, 0).form == G16_RING; }
 bool ats_gemm_qkv_rope_applies(int m, int hidden, int head_dim, int dtype) {
-  return ats_switch(ATS_SW_FUSE_QKV_ROPE) != 0 && dtype == ATS_HALF && head_dim == 128 && hidden % 256 == 0 && big_kernel_applies(m, 3 * hidden, hidden, hidden, 3 * hidden, dtype, EPI_STORE);
+  return ats_switch(ATS_SW_FUSE_QKV_ROPE) != 0 && dtype == ATS_HALF && head_dim == 128 && hidden % 256 == 0 && qkv_rope_ring(m, hidden);
 }
 
 int ats_gemm_qkv_rope(const void* x, const void* wqkv, void* qkv, int m, int hidden, const RopeEpi& rope, hipStream_t st, int pk, const SkArena* sk) {
   ATS_REQUIRE(x && wqkv && qkv && rope.rows && rope.cos_tab && rope.sin_tab && rope.hidden == hidden, ATSPEED_ERR_INVALID, "gemm_qkv_rope: null / inconsistent argument");
-  ATS_REQUIRE(hidden % 256 == 0 && big_kernel_applies(m, 3 * hidden, hidden, hidden, 3 * hidden, ATS_HALF, EPI_STORE), ATSPEED_ERR_INVALID,
-              "gemm_qkv_rope: shape %d x %d is not the batched kernel's", m, hidden);
+  ATS_REQUIRE(hidden % 256 == 0 && qkv_rope_ring(m, hidden), ATSPEED_ERR_INVALID, "gemm_qkv_rope: shape %d x %d is not the batched kernel's", m, hidden);
   ATS_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)wqkv & 15) == 0 && ((uintptr_t)qkv & 15) == 0, ATSPEED_ERR_INVALID, "gemm_qkv_rope: operands must be 16-byte aligned");
   return launch_big<EPI_QKV_ROPE>((const bf16_t*)x, (const bf16_t*)wqkv, qkv, m, 3 * hidden, hidden, hidden, 3 * hidden, st, pk, rope, nullptr, nullptr, sk);
 }
@@ -2300,7 +2265,7 @@ int ats_lmhead_lse(const void* a, const void* w, float* logits, int m, int n, in
   if (fused_out) *fused_out = 0;
   if (m <= 0) return ATSPEED_OK;
   if (dtype == ATS_HALF && part && part_bytes >= ats_lmhead_lse_part_bytes(m, n) && ((uintptr_t)part & 7) == 0 &&
-      big_kernel_applies(m, n, k, lda, ldc, dtype, EPI_F32, true)) {
+      plan_gemm(m, n, k, lda, ldc, dtype, EPI_F32, workspace, workspace_bytes, true).form == G16_RING) {
     ATS_REQUIRE(a && w && logits && lse, ATSPEED_ERR_INVALID, "lmhead_lse: null operand");
     ATS_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)w & 15) == 0, ATSPEED_ERR_INVALID, "lmhead_lse: operands must be 16-byte aligned");
     if (fused_out) *fused_out = 1;
@@ -2311,45 +2276,19 @@ int ats_lmhead_lse(const void* a, const void* w, float* logits, int m, int n, in
 }
 
 // h += a * w^T, then xn = rmsnorm(h) * norm_w  (split-K path fuses the reduce, the residual and the norm)
-static bool big_kernel_applies(int m, int n, int k, int lda, int ldc, int dtype, int epilogue, bool lm_head) {
-  // the 256-wide ring kernel vs the 128-wide LDS-tiled kernel (with split-K): the ring kernel wins once its tile grid keeps
-  // a fair share of the 256 CUs busy (measured with tools/gemm_ab.py)
-  // from 257 tokens (two token tiles): measured against the split-K mode at 300-500 tokens, gate_up 115-138 -> 96-108 us, qkv 80 -> 75 us
-  constexpr int big_min_m = 257;
-  constexpr int min_fill = 60;   // crossover measured at ~50-60 % (o_proj, down, qkv, gate_up at 512-1920 tokens)
-  if (dtype != ATS_HALF || m < big_min_m || k % 128 != 0 || (lda % 8) != 0 || !dma_offsets_fit(n, k, 2) || !dma_offsets_fit(m, lda, 2)) return false;
-  if (epilogue == EPI_SWIGLU && ((ldc & 3) != 0 || n % 32 != 0)) return false;
-  // 257-384 tokens on a projection of 16-256 panels: the panel form (launch_epi).  Not the lm_head with the fused normaliser (a vocabulary of
-  // 150-256 panels, e.g. the stock 32000, at 257-352 logit rows would leave the fused-LSE / tile_store ring path for panel<EPI_F32> + a separate LSE pass,
-  // a regime the panel sweep never measured; Beauty's 32859 misses the band by one panel)
-  if (!lm_head && panel_applies(m, n, k, lda)) return false;
-  const int tn = (n + 255) / 256;
-  if (big_fill_pct(tn * ((m + 255) / 256)) >= min_fill || big_fill_pct(tn * ((m + 127) / 128)) >= min_fill) return true;
-  // a thin grid whose k-steps the split-K tail spreads over the chip: from 48 tiles of 128 rows (four parts per tile on 192 CUs; N = 4096
-  // from 257 tokens), where it overtakes the LDS-tiled split-K kernel + reduce pass (tools/sk_sweep.py: o_proj at 320 tokens 36.7 -> 34.1 us,
-  // down 73.6 -> 70.3; at 400 tokens 33.7 -> 29.6 and 68.4 -> 59.7)
-  constexpr int sk_min_tiles = 48;
-  const int t128 = tn * ((m + 127) / 128);
-  return t128 >= sk_min_tiles && sk_any_plan(t128, k);
-}
-
 int ats_gemm_resid_norm(const void* a, const void* w, void* h, int m, int n, int k, int lda, int ldh, int dtype,
                         const void* norm_w, void* xn, float eps, void* workspace, size_t workspace_bytes, hipStream_t st, int pk, const SkArena* sk) {
   if (m <= 0) return ATSPEED_OK;
   FusedNorm fn{norm_w, xn, eps, false};
-  int epc = dtype == ATSPEED_F32 ? 4 : 8;
-  if ((kcut_takes(m, n, k, lda, dtype, EPI_RESID, workspace, workspace_bytes) || !big_kernel_applies(m, n, k, lda, ldh, dtype, EPI_RESID)) && k % epc == 0 && lda % epc == 0) {
-    int rc;
-    if (dtype == ATSPEED_F32)
-      rc = launch_epi<float, EPI_RESID>((const float*)a, (const float*)w, h, m, n, k, lda, ldh, (float*)workspace, workspace_bytes, st, &fn, 0);
-    else
-      rc = launch_epi<bf16_t, EPI_RESID>((const bf16_t*)a, (const bf16_t*)w, h, m, n, k, lda, ldh, (float*)workspace, workspace_bytes, st, &fn, pk);
-    if (rc != ATSPEED_OK) return rc;
-  } else {
+  const int epc = dtype == ATSPEED_F32 ? 4 : 8;
+  const GemmPlan p = plan_gemm(m, n, k, lda, ldh, dtype, EPI_RESID, workspace, workspace_bytes);
+  if (p.form == G16_RING || k % epc != 0 || lda % epc != 0)            // (ats_gemm checks the operands)
     ATS_TRY(ats_gemm(a, w, h, m, n, k, lda, ldh, dtype, EPI_RESID, workspace, workspace_bytes, st, pk, sk));
-  }
-  if (!fn.done) return ats_rmsnorm(h, norm_w, xn, m, n, eps, dtype, st, pk);
-  return ATSPEED_OK;
+  else if (dtype == ATSPEED_F32)
+    ATS_TRY((run_plan<float, EPI_RESID>(p, (const float*)a, (const float*)w, h, m, n, k, lda, ldh, (float*)workspace, st, &fn, 0, sk)));
+  else
+    ATS_TRY((run_plan<bf16_t, EPI_RESID>(p, (const bf16_t*)a, (const bf16_t*)w, h, m, n, k, lda, ldh, (float*)workspace, st, &fn, pk, sk)));
+  return resid_norm_tail(fn, nullptr, 0, h, m, n, ldh, dtype, st, pk);
 }
 
 // ---- W8A8 projections whose 256-wide tile grid is thin (N = 4096 at 257-2000 tokens: o_proj, down): the block-scaled ring kernel cut in K
@@ -2357,8 +2296,8 @@ int ats_gemm_resid_norm(const void* a, const void* w, void* h, int m, int n, int
 // Before: 32-80 workgroups on 256 CUs (down at 300 tokens 71 us against 50 us in bf16), and from 512 tokens these projections ran bf16.
 static int mx_split_count(int m, int n, int k, bool* rows256 = nullptr) {   // 0: this shape takes the plain ring kernel (or is not an fp8 shape at all)
   if (m < 257 || k % 256 != 0 || !dma_offsets_fit(n, k, 1) || !dma_offsets_fit(m, k, 1)) return 0;
+  if (ring_fills(m, n)) return 0;
   const int tn = (n + 255) / 256, t256 = tn * ((m + 255) / 256), t128 = tn * ((m + 127) / 128);
-  if (big_fill_pct(t256) >= 60 || big_fill_pct(t128) >= 60) return 0;
   // measured (tools/gemm_fp8_ab.py with / without a workspace, us per launch incl. the reduce): down 70.9 -> 37.4 at 300 tokens, 72.1 -> 42.7 at 456,
   // 76.5 -> 54.4 at 640, 77.7 -> 66.2 at 912; o_proj (K = 4096: short parts) 30.7 -> 27.6 at 300, 36.2 -> 32.4 at 456 but 35.5 -> 39.1 at 640; qkv (96
   // tiles of 256 rows already) 32.3 -> 50.1 at 300: only really thin grids, and K = 4096 only up to 512 tokens
@@ -2370,16 +2309,9 @@ static int mx_split_count(int m, int n, int k, bool* rows256 = nullptr) {   // 0
   return s_ >= 2 ? s_ : 0;
 }
 static int launch_mx_split(const unsigned char* x, const float* sx, const unsigned char* w, const float* sw, float* partial, int m, int n, int k,
-                           int splits, hipStream_t st, int pk) {
-  static thread_local AtsPerDeviceFlag attr_flag;
-  bool& attr_done = attr_flag.cur();
-  if (!attr_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_mx_kernel<EPI_F32, 4, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    ATS_HIP(hipFuncSetAttribute((const void*)gemm_ring_mx_kernel<EPI_F32, 8, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    attr_done = true;
-  }
-  bool r256 = false;
-  (void)mx_split_count(m, n, k, &r256);
+                           int splits, bool r256, hipStream_t st, int pk) {
+  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI_F32, 4, 8, true>>(96 * 1024)));
+  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI_F32, 8, 8, true>>(128 * 1024)));
   const int tiles_n = (n + 255) / 256, tiles_m = r256 ? (m + 255) / 256 : (m + 127) / 128;
   if (r256) hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI_F32, 8, 8, true>), dim3(tiles_n * tiles_m * splits), dim3(512), 128 * 1024, st, (const void*)x, (const void*)w, sx, sw,
                                (void*)partial, m, n, k, n, tiles_n, tiles_m, 4, pk, RopeEpi{}, splits);
@@ -2410,15 +2342,10 @@ static int wdma8_split_count(int n, int k) {                           // 1: no 
 template <int BM, int NST, int EPI, bool SPLIT, int WM = 2, int BN = 128>
 int launch_wdma8_cfg(const unsigned char* xq, const float* sx, const unsigned char* wq, const float* sw, void* c, int m, int n, int k, int ldc,
                      int splits, hipStream_t st, int pk, const RopeEpi& rope = RopeEpi{}) {
-  auto kern = gemm_wdma_kernel<BM, BN, NST, EPI, SPLIT, WM, true>;
   constexpr int lds = NST * (BM + BN) * 128;
-  static thread_local AtsPerDeviceFlag attr_flag;
-  bool& attr_done = attr_flag.cur();
-  if (!attr_done) {
-    ATS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((n + BN - 1) / BN, SPLIT ? splits : 1), dim3(128 * WM), lds, st, (const void*)xq, (const void*)wq, c, m, n, k, k, ldc, pk, splits, sx, sw, rope);
+  ATS_TRY((ats_lds_limit<gemm_wdma_kernel<BM, BN, NST, EPI, SPLIT, WM, true>>(lds)));
+  hipLaunchKernelGGL((gemm_wdma_kernel<BM, BN, NST, EPI, SPLIT, WM, true>), dim3((n + BN - 1) / BN, SPLIT ? splits : 1), dim3(128 * WM), lds, st, (const void*)xq, (const void*)wq,
+                     c, m, n, k, k, ldc, pk, splits, sx, sw, rope);
   ATS_LAUNCH_CHECK();
   ats_count_path(SPLIT ? ATS_PATH_FP8_WDMA_SPLIT : ATS_PATH_FP8_WDMA);
   return ATSPEED_OK;
@@ -2426,20 +2353,18 @@ int launch_wdma8_cfg(const unsigned char* xq, const float* sx, const unsigned ch
 template <int EPI, bool SPLIT>
 int launch_wdma8(const unsigned char* xq, const float* sx, const unsigned char* wq, const float* sw, void* c, int m, int n, int k, int ldc,
                  int splits, hipStream_t st, int pk, const RopeEpi& rope = RopeEpi{}) {
-  {
-    if (EPI == EPI_QKV_ROPE || wdma8_bn64(n)) {                        // (the RoPE epilogue exists for 64-row tiles only: the caller asked ats_gemm_fp8_qkv_rope_applies)
-      if (m <= 32)  return launch_wdma8_cfg<32, 8, EPI, SPLIT, 2, 64>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk, rope);     // 12 KB x 8
-      if (m <= 64)  return launch_wdma8_cfg<64, 8, EPI, SPLIT, 2, 64>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk, rope);     // 16 KB x 8
-      if (m <= 128) return launch_wdma8_cfg<128, 6, EPI, SPLIT, 2, 64>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk, rope);    // 24 KB x 6
-      return launch_wdma8_cfg<256, 4, EPI, SPLIT, 4, 64>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk, rope);                  // 40 KB x 4, 8 waves
-    }
+  if (EPI == EPI_QKV_ROPE || wdma8_bn64(n)) {                          // (the RoPE epilogue exists for 64-row tiles only: the caller asked ats_gemm_fp8_qkv_rope_applies)
+    if (m <= 32)  return launch_wdma8_cfg<32, 8, EPI, SPLIT, 2, 64>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk, rope);     // 12 KB x 8
+    if (m <= 64)  return launch_wdma8_cfg<64, 8, EPI, SPLIT, 2, 64>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk, rope);     // 16 KB x 8
+    if (m <= 128) return launch_wdma8_cfg<128, 6, EPI, SPLIT, 2, 64>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk, rope);    // 24 KB x 6
+    return launch_wdma8_cfg<256, 4, EPI, SPLIT, 4, 64>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk, rope);                  // 40 KB x 4, 8 waves
   }
   if constexpr (EPI == EPI_QKV_ROPE) return ATSPEED_ERR_INVALID;
   else {
-  if (m <= 32)  return launch_wdma8_cfg<32, 6, EPI, SPLIT>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk);        // 20 KB x 6
-  if (m <= 64)  return launch_wdma8_cfg<64, 6, EPI, SPLIT>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk);        // 24 KB x 6
-  if (m <= 128) return launch_wdma8_cfg<128, 4, EPI, SPLIT>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk);       // 32 KB x 4
-  return launch_wdma8_cfg<256, 3, EPI, SPLIT, 4>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk);                  // 48 KB x 3, 8 waves
+    if (m <= 32)  return launch_wdma8_cfg<32, 6, EPI, SPLIT>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk);        // 20 KB x 6
+    if (m <= 64)  return launch_wdma8_cfg<64, 6, EPI, SPLIT>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk);        // 24 KB x 6
+    if (m <= 128) return launch_wdma8_cfg<128, 4, EPI, SPLIT>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk);       // 32 KB x 4
+    return launch_wdma8_cfg<256, 3, EPI, SPLIT, 4>(xq, sx, wq, sw, c, m, n, k, ldc, splits, st, pk);                  // 48 KB x 3, 8 waves
   }
 }
 // the slabs of a split launch: [splits][m][n] fp32 in `ws`
@@ -2447,76 +2372,65 @@ static bool wdma8_ws_ok(int m, int n, int splits, const void* ws, size_t ws_byte
   return ws && ((uintptr_t)ws & 15) == 0 && (size_t)splits * m * n * sizeof(float) <= ws_bytes;
 }
 
+// ---- the W8A8 planner.  1-256 tokens where the weight-streaming kernel takes the shape: unsplit, or split into scaled fp32 slabs where the grid
+// is thin -- the residual epilogue always through slabs (one part per tile if need be; where not even those fit the workspace, the ring kernel's own
+// residual epilogue, as before round 5).  Else the ring kernel, cut in K on thin grids whose slabs fit the workspace.
+enum { F8_WDMA, F8_WDMA_SPLIT, F8_RING_KCUT, F8_RING, F8_RING_RESID };
+struct Fp8Plan { int form; int splits; bool rows256; };
+static Fp8Plan plan_fp8(int m, int n, int k, int epilogue, const void* ws, size_t ws_bytes) {
+  if (wdma8_applies(m, n, k)) {
+    int s_ = wdma8_split_count(n, k);
+    if (s_ > 1 && !wdma8_ws_ok(m, n, s_, ws, ws_bytes)) s_ = 1;        // no room for the slabs: one part per tile
+    if (s_ == 1 && epilogue != EPI_RESID) return {F8_WDMA, 1, false};
+    if (!wdma8_ws_ok(m, n, s_, ws, ws_bytes) && epilogue == EPI_RESID && k % 256 == 0) return {F8_RING_RESID, 1, false};
+    return {F8_WDMA_SPLIT, s_, false};                                 // (ats_gemm_fp8 refuses it when the slabs do not fit)
+  }
+  bool r256 = false;
+  const int ms = mx_split_count(m, n, k, &r256);
+  if (ms >= 2 && wdma8_ws_ok(m, n, ms, ws, ws_bytes) && (n % 4) == 0) return {F8_RING_KCUT, ms, r256};
+  return {F8_RING, 1, false};
+}
+// the slab half of a split W8A8 plan
+static int launch_fp8_slabs(const Fp8Plan& p, const void* xq, const float* sx, const void* wq, const float* sw, void* ws, int m, int n, int k, hipStream_t st, int pk) {
+  const unsigned char *X = (const unsigned char*)xq, *Wq = (const unsigned char*)wq;
+  if (p.form == F8_RING_KCUT) return launch_mx_split(X, sx, Wq, sw, (float*)ws, m, n, k, p.splits, p.rows256, st, pk);
+  return launch_wdma8<EPI_F32, true>(X, sx, Wq, sw, ws, m, n, k, n, p.splits, st, pk);
+}
+
 bool ats_gemm_fp8_applies(int m, int n, int k, int ldc, int epilogue) {
   if (epilogue == EPI_SWIGLU && ((ldc & 3) != 0 || n % 32 != 0)) return false;
   if (m <= 256) return wdma8_applies(m, n, k);
   if (k % 256 != 0) return false;
   if (m < 512) return true;                                            // 257-511 tokens (a long prompt's first verification): the ring kernel whatever its fill
-  if (mx_split_count(m, n, k) >= 2) return true;                       // thin grids: the ring kernel cut in K
-  const int tn = (n + 255) / 256;
-  return big_fill_pct(tn * ((m + 255) / 256)) >= 60 || big_fill_pct(tn * ((m + 127) / 128)) >= 60;
+  return mx_split_count(m, n, k) >= 2 || ring_fills(m, n);             // thin grids: the ring kernel cut in K
 }
 size_t ats_gemm_fp8_workspace_bytes(int m, int n, int k) {
-  if (m <= 256) return wdma8_applies(m, n, k) ? (size_t)wdma8_split_count(n, k) * m * n * sizeof(float) : 0;
-  return (size_t)mx_split_count(m, n, k) * m * n * sizeof(float);
+  return (size_t)(wdma8_applies(m, n, k) ? wdma8_split_count(n, k) : mx_split_count(m, n, k)) * m * n * sizeof(float);
 }
 
 int ats_gemm_fp8(const void* xq, const float* sx, const void* wq, const float* sw, void* c, int m, int n, int k, int ldc,
                  int epilogue, hipStream_t st, int pk, void* ws, size_t ws_bytes) {
   ATS_REQUIRE(xq && sx && wq && sw && c, ATSPEED_ERR_INVALID, "gemm_fp8: null argument");
-  const unsigned char* X = (const unsigned char*)xq; const unsigned char* Wq = (const unsigned char*)wq;
-  if (m >= 1 && m <= 256 && wdma8_applies(m, n, k)) {
+  const Fp8Plan p = plan_fp8(m, n, k, epilogue, ws, ws_bytes);
+  if (p.form == F8_WDMA || p.form == F8_WDMA_SPLIT || p.form == F8_RING_RESID) {
     ATS_REQUIRE(epilogue != EPI_SWIGLU || ((ldc & 3) == 0 && n % 32 == 0), ATSPEED_ERR_INVALID, "gemm_fp8: SwiGLU needs N %% 32 == 0 and ldc %% 4 == 0");
     ATS_REQUIRE((((uintptr_t)xq | (uintptr_t)wq) & 15) == 0, ATSPEED_ERR_INVALID, "gemm_fp8: operands must be 16-byte aligned");
-    int s_ = wdma8_split_count(n, k);
-    if (s_ > 1 && !wdma8_ws_ok(m, n, s_, ws, ws_bytes)) s_ = 1;         // no room for the slabs: one part per tile
-    if (s_ == 1 && epilogue != EPI_RESID) {
-      switch (epilogue) {
-        case EPI_STORE:  return launch_wdma8<EPI_STORE, false>(X, sx, Wq, sw, c, m, n, k, ldc, 1, st, pk);
-        case EPI_F32:    return launch_wdma8<EPI_F32, false>(X, sx, Wq, sw, c, m, n, k, ldc, 1, st, pk);
-        case EPI_SWIGLU: return launch_wdma8<EPI_SWIGLU, false>(X, sx, Wq, sw, c, m, n, k, ldc, 1, st, pk);
-      }
-      atspeed_set_error("gemm_fp8: unknown epilogue %d", epilogue);
-      return ATSPEED_ERR_INVALID;
-    }
-    if (!wdma8_ws_ok(m, n, s_, ws, ws_bytes) && epilogue == EPI_RESID && k % 256 == 0)       // residual epilogue without room for the slabs: the ring kernel's own (as before round 5)
-      return launch_big_fp8<EPI_RESID>(X, sx, Wq, sw, c, m, n, k, ldc, st, pk);
-    ATS_REQUIRE(wdma8_ws_ok(m, n, s_, ws, ws_bytes), ATSPEED_ERR_CAPACITY, "gemm_fp8: %d x %d x %d parts of fp32 partial sums do not fit the workspace (%zu bytes)", s_, m, n, ws_bytes);
-    ATS_TRY((launch_wdma8<EPI_F32, true>(X, sx, Wq, sw, ws, m, n, k, n, s_, st, pk)));
-    switch (epilogue) {
-      case EPI_STORE:  return reduce_splits<bf16_t, EPI_STORE>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
-      case EPI_F32:    return reduce_splits<bf16_t, EPI_F32>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
-      case EPI_RESID:  return reduce_splits<bf16_t, EPI_RESID>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
-      case EPI_SWIGLU: return reduce_splits<bf16_t, EPI_SWIGLU>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
-    }
-    atspeed_set_error("gemm_fp8: unknown epilogue %d", epilogue);
-    return ATSPEED_ERR_INVALID;
+  } else {
+    ATS_REQUIRE(m >= 1 && n >= 1 && k % 256 == 0, ATSPEED_ERR_INVALID, "gemm_fp8: K=%d must be a multiple of 256", k);
+    ATS_REQUIRE(dma_offsets_fit(n, k, 1) && dma_offsets_fit(m, k, 1), ATSPEED_ERR_CAPACITY, "gemm_fp8: an operand of %d x %d or %d x %d bytes exceeds the kernel's 32-bit row offsets", n, k, m, k);
+    ATS_REQUIRE(epilogue != EPI_SWIGLU || ((ldc & 3) == 0 && n % 32 == 0), ATSPEED_ERR_INVALID, "gemm_fp8: SwiGLU needs N %% 32 == 0 and ldc %% 4 == 0");
   }
-  ATS_REQUIRE(m >= 1 && n >= 1 && k % 256 == 0, ATSPEED_ERR_INVALID, "gemm_fp8: K=%d must be a multiple of 256", k);
-  ATS_REQUIRE(dma_offsets_fit(n, k, 1) && dma_offsets_fit(m, k, 1), ATSPEED_ERR_CAPACITY, "gemm_fp8: an operand of %d x %d or %d x %d bytes exceeds the kernel's 32-bit row offsets", n, k, m, k);
-  ATS_REQUIRE(epilogue != EPI_SWIGLU || ((ldc & 3) == 0 && n % 32 == 0), ATSPEED_ERR_INVALID, "gemm_fp8: SwiGLU needs N %% 32 == 0 and ldc %% 4 == 0");
-  {
-    const int ms = mx_split_count(m, n, k);
-    if (ms >= 2 && wdma8_ws_ok(m, n, ms, ws, ws_bytes) && (n % 4) == 0) {
-      ATS_TRY(launch_mx_split(X, sx, Wq, sw, (float*)ws, m, n, k, ms, st, pk));
-      switch (epilogue) {
-        case EPI_STORE:  return reduce_splits<bf16_t, EPI_STORE>((const float*)ws, c, m, n, ldc, ms, st, nullptr, pk);
-        case EPI_F32:    return reduce_splits<bf16_t, EPI_F32>((const float*)ws, c, m, n, ldc, ms, st, nullptr, pk);
-        case EPI_RESID:  return reduce_splits<bf16_t, EPI_RESID>((const float*)ws, c, m, n, ldc, ms, st, nullptr, pk);
-        case EPI_SWIGLU: return reduce_splits<bf16_t, EPI_SWIGLU>((const float*)ws, c, m, n, ldc, ms, st, nullptr, pk);
-      }
-      atspeed_set_error("gemm_fp8: unknown epilogue %d", epilogue);
-      return ATSPEED_ERR_INVALID;
-    }
+  const unsigned char* X = (const unsigned char*)xq; const unsigned char* Wq = (const unsigned char*)wq;
+  if (p.form == F8_WDMA_SPLIT || p.form == F8_RING_KCUT) {
+    ATS_REQUIRE(wdma8_ws_ok(m, n, p.splits, ws, ws_bytes), ATSPEED_ERR_CAPACITY, "gemm_fp8: %d x %d x %d parts of fp32 partial sums do not fit the workspace (%zu bytes)", p.splits, m, n, ws_bytes);
+    ATS_TRY(launch_fp8_slabs(p, xq, sx, wq, sw, ws, m, n, k, st, pk));
+    return reduce_slabs(epilogue, "gemm_fp8", ws, c, m, n, ldc, p.splits, st, pk);
   }
-  switch (epilogue) {
-    case EPI_STORE:  return launch_big_fp8<EPI_STORE>(X, sx, Wq, sw, c, m, n, k, ldc, st, pk);
-    case EPI_F32:    return launch_big_fp8<EPI_F32>(X, sx, Wq, sw, c, m, n, k, ldc, st, pk);
-    case EPI_RESID:  return launch_big_fp8<EPI_RESID>(X, sx, Wq, sw, c, m, n, k, ldc, st, pk);
-    case EPI_SWIGLU: return launch_big_fp8<EPI_SWIGLU>(X, sx, Wq, sw, c, m, n, k, ldc, st, pk);
-  }
-  atspeed_set_error("gemm_fp8: unknown epilogue %d", epilogue);
-  return ATSPEED_ERR_INVALID;
+  return with_epi(epilogue, "gemm_fp8", [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    if constexpr (EPI != EPI_RESID) { if (p.form == F8_WDMA) return launch_wdma8<EPI, false>(X, sx, Wq, sw, c, m, n, k, ldc, 1, st, pk); }
+    return launch_big_fp8<EPI>(X, sx, Wq, sw, c, m, n, k, ldc, st, pk);
+  });
 }
 
 // One user's W8A8 qkv projection as scaled fp32 split-K slabs [splits][m][n] in the workspace, without the reduce pass (ats_gemm_partials'
@@ -2524,46 +2438,34 @@ int ats_gemm_fp8(const void* xq, const float* sx, const void* wq, const float* s
 int ats_gemm_fp8_partials(const void* xq, const float* sx, const void* wq, const float* sw, int m, int n, int k, void* ws, size_t ws_bytes,
                           hipStream_t st, int* splits_out, int pk) {
   *splits_out = 0;
-  if (m < 1 || m > 256 || !wdma8_applies(m, n, k) || (n % 4) != 0) return ATSPEED_OK;
-  const int s_ = wdma8_split_count(n, k);
-  if (s_ < 2 || !wdma8_ws_ok(m, n, s_, ws, ws_bytes)) return ATSPEED_OK;
-  ATS_REQUIRE(xq && sx && wq && sw && (((uintptr_t)xq | (uintptr_t)wq) & 15) == 0, ATSPEED_ERR_INVALID, "gemm_fp8_partials: null / unaligned operand");
-  ATS_TRY((launch_wdma8<EPI_F32, true>((const unsigned char*)xq, sx, (const unsigned char*)wq, sw, ws, m, n, k, n, s_, st, pk)));
-  *splits_out = s_;
+  const Fp8Plan p = plan_fp8(m, n, k, EPI_STORE, ws, ws_bytes);
+  if (p.form != F8_WDMA_SPLIT || (n % 4) != 0) return ATSPEED_OK;      // (the ring kernel's slabs stay with ats_gemm_fp8)
+  ATS_REQUIRE(sx && sw, ATSPEED_ERR_INVALID, "gemm_fp8_partials: null operand");
+  ATS_TRY(slab_operands_ok("gemm_fp8_partials", xq, wq, ws));
+  ATS_TRY(launch_fp8_slabs(p, xq, sx, wq, sw, ws, m, n, k, st, pk));
+  *splits_out = p.splits;
   return ATSPEED_OK;
 }
 
 // h += xq wq^T (W8A8), then the NEXT op's input norm of the updated rows: xn (16-bit operand; may be null when q_out is given) and / or the
-// e4m3 rows + per-token scales (q_out, s_out) a following W8A8 projection consumes.  One user's tokens: split-K slabs + ONE fused reduce /
-// residual / norm / quantisation pass; batched: the ring kernel's residual epilogue, then the norm kernels.
+// e4m3 rows + per-token scales (q_out, s_out) a following W8A8 projection consumes.  Split plans: the slabs + ONE fused reduce / residual / norm /
+// quantisation pass; the others: the kernel's residual epilogue, then the norm kernels.
 int ats_gemm_fp8_resid_norm(const void* xq, const float* sx, const void* wq, const float* sw, void* h, int m, int n, int k, int ldh,
                             const void* norm_w, void* xn, void* q_out, float* s_out, float eps, void* ws, size_t ws_bytes, hipStream_t st, int pk) {
   if (m <= 0) return ATSPEED_OK;
   ATS_REQUIRE(xn || (q_out && s_out), ATSPEED_ERR_INVALID, "gemm_fp8_resid_norm: no output for the norm");
-  if (m <= 256 && wdma8_applies(m, n, k) && n <= 8192 && (n % 4) == 0 && (ldh % 4) == 0) {
-    const int s_ = wdma8_split_count(n, k);
-    if (wdma8_ws_ok(m, n, s_, ws, ws_bytes)) {
-      ATS_REQUIRE(xq && sx && wq && sw && h && norm_w && (((uintptr_t)xq | (uintptr_t)wq) & 15) == 0, ATSPEED_ERR_INVALID, "gemm_fp8_resid_norm: null / unaligned operand");
-      ATS_TRY((launch_wdma8<EPI_F32, true>((const unsigned char*)xq, sx, (const unsigned char*)wq, sw, ws, m, n, k, n, s_, st, pk)));
-      FusedNorm fn{norm_w, xn, eps, false, q_out, s_out};
-      ATS_TRY((reduce_splits<bf16_t, EPI_RESID>((const float*)ws, h, m, n, ldh, s_, st, &fn, pk)));
-      if (fn.done) return ATSPEED_OK;
-      return q_out ? ats_rmsnorm_quant_fp8(h, norm_w, xn, q_out, s_out, m, n, eps, st, pk) : ats_rmsnorm(h, norm_w, xn, m, n, eps, ATS_HALF, st, pk);
-    }
-  }
-  {
-    const int ms = mx_split_count(m, n, k);                           // thin grid: K-split ring + ONE fused reduce / residual / norm / quantisation pass
-    if (ms >= 2 && wdma8_ws_ok(m, n, ms, ws, ws_bytes) && n <= 8192 && (n % 4) == 0 && (ldh % 4) == 0) {
-      ATS_REQUIRE(xq && sx && wq && sw && h && norm_w, ATSPEED_ERR_INVALID, "gemm_fp8_resid_norm: null operand");
-      ATS_TRY(launch_mx_split((const unsigned char*)xq, sx, (const unsigned char*)wq, sw, (float*)ws, m, n, k, ms, st, pk));
-      FusedNorm fn{norm_w, xn, eps, false, q_out, s_out};
-      ATS_TRY((reduce_splits<bf16_t, EPI_RESID>((const float*)ws, h, m, n, ldh, ms, st, &fn, pk)));
-      if (fn.done) return ATSPEED_OK;
-      return q_out ? ats_rmsnorm_quant_fp8(h, norm_w, xn, q_out, s_out, m, n, eps, st, pk) : ats_rmsnorm(h, norm_w, xn, m, n, eps, ATS_HALF, st, pk);
-    }
+  FusedNorm fn{norm_w, xn, eps, false, q_out, s_out};
+  const Fp8Plan p = plan_fp8(m, n, k, EPI_RESID, ws, ws_bytes);
+  // (the weight-streaming split only with its full part count: one part per tile goes through ats_gemm_fp8)
+  const bool full = p.form == F8_RING_KCUT || (p.form == F8_WDMA_SPLIT && p.splits == wdma8_split_count(n, k));
+  if (full && wdma8_ws_ok(m, n, p.splits, ws, ws_bytes) && n <= 8192 && (n % 4) == 0 && (ldh % 4) == 0) {
+    ATS_REQUIRE(xq && sx && wq && sw && h && norm_w, ATSPEED_ERR_INVALID, "gemm_fp8_resid_norm: null operand");
+    ATS_REQUIRE(p.form == F8_RING_KCUT || (((uintptr_t)xq | (uintptr_t)wq) & 15) == 0, ATSPEED_ERR_INVALID, "gemm_fp8_resid_norm: unaligned operand");
+    ATS_TRY(launch_fp8_slabs(p, xq, sx, wq, sw, ws, m, n, k, st, pk));
+    return resid_norm_tail(fn, (const float*)ws, p.splits, h, m, n, ldh, ATS_HALF, st, pk);
   }
   ATS_TRY(ats_gemm_fp8(xq, sx, wq, sw, h, m, n, k, ldh, EPI_RESID, st, pk, ws, ws_bytes));
-  return q_out ? ats_rmsnorm_quant_fp8(h, norm_w, xn, q_out, s_out, m, n, eps, st, pk) : ats_rmsnorm(h, norm_w, xn, m, n, eps, ATS_HALF, st, pk);
+  return resid_norm_tail(fn, nullptr, 0, h, m, n, ldh, ATS_HALF, st, pk);
 }
 
 // the fp8 qkv projection with RoPE + the KV scatter in its epilogue (see ats_gemm_qkv_rope); the caller checks ats_gemm_fp8_applies,
@@ -2846,19 +2748,9 @@ int ats_gemm_w4a8(const void* xq, const float* sx, const void* wq, const void* w
   ats_count_path(ATS_PATH_FP4);
   if (s_ > 1 && wdma8_ws_ok(m, n, s_, ws, ws_bytes) && (n % 4) == 0) {
     ATS_TRY((launch_w4a8<EPI_F32, true>(X, sx, Wq, Sc, ws, m, n, k, n, s_, st, pk)));
-    switch (epilogue) {
-      case EPI_STORE:  return reduce_splits<bf16_t, EPI_STORE>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
-      case EPI_F32:    return reduce_splits<bf16_t, EPI_F32>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
-      case EPI_RESID:  return reduce_splits<bf16_t, EPI_RESID>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
-      default:         return reduce_splits<bf16_t, EPI_SWIGLU>((const float*)ws, c, m, n, ldc, s_, st, nullptr, pk);
-    }
+    return reduce_slabs(epilogue, "gemm_w4a8", ws, c, m, n, ldc, s_, st, pk);
   }
-  switch (epilogue) {
-    case EPI_STORE:  return launch_w4a8<EPI_STORE, false>(X, sx, Wq, Sc, c, m, n, k, ldc, 1, st, pk);
-    case EPI_F32:    return launch_w4a8<EPI_F32, false>(X, sx, Wq, Sc, c, m, n, k, ldc, 1, st, pk);
-    case EPI_RESID:  return launch_w4a8<EPI_RESID, false>(X, sx, Wq, Sc, c, m, n, k, ldc, 1, st, pk);
-    default:         return launch_w4a8<EPI_SWIGLU, false>(X, sx, Wq, Sc, c, m, n, k, ldc, 1, st, pk);
-  }
+  return with_epi(epilogue, "gemm_w4a8", [&](auto e) { return launch_w4a8<decltype(e)::value, false>(X, sx, Wq, Sc, c, m, n, k, ldc, 1, st, pk); });
 }
 
 // h += xq W^T (W4A8), then the next op's input norm (xn and / or e4m3 rows + scales): the W8A8 form's fused reduce / residual / norm /
@@ -2868,23 +2760,16 @@ int ats_gemm_w4a8_resid_norm(const void* xq, const float* sx, const void* wq, co
   ATS_REQUIRE(xn || (q_out && s_out), ATSPEED_ERR_INVALID, "gemm_w4a8_resid_norm: no output for the norm");
   ATS_REQUIRE(norm_w, ATSPEED_ERR_INVALID, "gemm_w4a8_resid_norm: null norm weight");
   ATS_TRY(w4a8_check(xq, sx, wq, wsc, h, m, n, k, ldh, EPI_RESID));
+  FusedNorm fn{norm_w, xn, eps, false, q_out, s_out};
   const int s_ = w4a8_split_count(m, n, k);
   if (s_ > 1 && wdma8_ws_ok(m, n, s_, ws, ws_bytes) && n <= 8192 && (n % 4) == 0 && (ldh % 4) == 0) {
     ats_count_path(ATS_PATH_FP4);
     ATS_TRY((launch_w4a8<EPI_F32, true>((const unsigned char*)xq, sx, (const unsigned char*)wq, (const unsigned char*)wsc, ws, m, n, k, n, s_, st, pk)));
-    FusedNorm fn{norm_w, xn, eps, false, q_out, s_out};
-    ATS_TRY((reduce_splits<bf16_t, EPI_RESID>((const float*)ws, h, m, n, ldh, s_, st, &fn, pk)));
-    if (fn.done) return ATSPEED_OK;
-  } else {
-    ATS_TRY(ats_gemm_w4a8(xq, sx, wq, wsc, h, m, n, k, ldh, EPI_RESID, st, pk, nullptr, 0));
+    return resid_norm_tail(fn, (const float*)ws, s_, h, m, n, ldh, ATS_HALF, st, pk);
   }
-  return q_out ? ats_rmsnorm_quant_fp8(h, norm_w, xn, q_out, s_out, m, n, eps, st, pk) : ats_rmsnorm(h, norm_w, xn, m, n, eps, ATS_HALF, st, pk);
+  ATS_TRY(ats_gemm_w4a8(xq, sx, wq, wsc, h, m, n, k, ldh, EPI_RESID, st, pk, nullptr, 0));
+  return resid_norm_tail(fn, nullptr, 0, h, m, n, ldh, ATS_HALF, st, pk);
 }
-
-
-
-// the same GEMMs on operands in the packed layout (what the bf16 / fp8 engine runs; atspeed_pack_rows makes them): a, w packed;
-// the SwiGLU epilogue's output packed too (it is the down projection's operand), every other output row-major
 
 }  // namespace ATS_NS
 
