@@ -539,7 +539,7 @@ __global__ __launch_bounds__(256) void quant_row_pairs_fp8_kernel(const bf16_t* 
 #pragma unroll
   for (int i = 0; i < NC; ++i) {
     const int line = l0 + 32 * i;
-    if (line < n_lines) {
+    if (line < n_lines && row < rows) {                            // (the pad row of an odd count is read, never written)
       const bf16_t* e = reinterpret_cast<const bf16_t*>(&v[i]);
       float f[8];
 #pragma unroll

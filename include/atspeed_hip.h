@@ -208,7 +208,10 @@ int64_t atspeed_llama_sk_arena_bytes(const atspeed_llama* m);
  * logits are never re-read, and with `fsm` given only the 256-column tiles that hold a token of the automaton are written (the
  * others are never read by a step: Beauty 5 of 129 tiles) -- *fused_out = 1; otherwise the plain GEMM + atspeed_lse_rows (0).
  * workspace: at least rows * ceil(vocab / 256) * 8 bytes for the fused path (+ the split-K slabs of the small path).  This is what
- * the decoder's forwards run; standalone for tests and benches. */
+ * the decoder's forwards run; standalone for tests and benches.
+ * Memory contract (tests/test_guard_bands_gpu.py::test_lmhead_lse_guard_bands, both paths): x_dev and w_dev 16-byte aligned; of the
+ * logits only [rows][0 .. vocab) is written (columns vocab .. ld - 1 and everything outside the rows stay untouched), lse_dev gets `rows`
+ * floats, nothing from workspace_bytes on is written; weight rows >= vocab and x rows >= rows influence no result. */
 int atspeed_lmhead_lse(const void* x_dev, const void* w_dev, float* logits_dev, float* lse_dev, int32_t rows, int32_t vocab,
                        int32_t hidden, int32_t ld, const atspeed_fsm* fsm /* may be NULL */, void* workspace_dev, size_t workspace_bytes,
                        int32_t* fused_out /* may be NULL */, void* stream);
@@ -336,7 +339,17 @@ int64_t atspeed_decoder_decisions(atspeed_decoder* d, int32_t* out, int64_t cap_
 
 /* ------------------------------------------------------------------ low-level ops (tests, benches)
  * C[M,N] = A[M,K] * W[N,K]^T on MFMA; epilogue: 0 store (dtype), 1 fp32 store, 2 residual add into
- * C (dtype), 3 SwiGLU over interleaved gate/up column groups (C is [M, N/2]). */
+ * C (dtype), 3 SwiGLU over interleaved gate/up column groups (C is [M, N/2]).
+ * Memory contract (tests/test_guard_bands_gpu.py::test_gemm_guard_bands, every kernel form x epilogue x type; ::test_workspace_ladder):
+ *   - a_dev and w_dev are 16-byte aligned (no more is needed); K and lda are multiples of 8 elements (fp32: 4); lda >= K; w has row
+ *     stride K; ldc >= the output's columns (tested: multiples of 8, fp32 outputs of 4, and the dense ldc = N of any parity).
+ *   - no byte outside [M][0 .. N) (SwiGLU: [M][0 .. N/2)) of C is written -- not the columns up to ldc, not a row past M -- and none from
+ *     workspace_bytes on; the workspace need not be 16-byte aligned.
+ *   - no element outside a[M][0 .. K) and w[N][0 .. K) influences a result, whatever its bits (NaN included): not a row past M or N,
+ *     not what lies between column K and lda of a row.  No slack is required after an operand -- every kernel clamps the rows it
+ *     fetches to M - 1 and N - 1 -- and the reference call of each case runs on exactly-sized buffers.
+ *   - a form that leaves split-K slabs in the workspace runs only where parts x M x N x 4 bytes fit workspace_bytes; with less (or no)
+ *     workspace another form computes the same product. */
 int atspeed_gemm(const void* a_dev, const void* w_dev, void* c_dev, int32_t m, int32_t n, int32_t k,
                  int32_t lda, int32_t ldc, int32_t dtype, int32_t epilogue, void* workspace_dev,
                  size_t workspace_bytes, void* stream);
@@ -354,7 +367,10 @@ int atspeed_set_switch(const char* name, int32_t value);
 int atspeed_get_switch(const char* name, int32_t* value_out);
 /* atspeed_gemm / atspeed_gemm_fp8 on operands in the packed layout (a / xq and w / wq through atspeed_pack_rows; K % 32 == 0, for fp8 K % 64 == 0):
  * what the bf16 / fp8 engine runs.  The SwiGLU epilogue's output (ldc % 32 == 0) is packed as well -- it is the down projection's operand --,
- * every other output is row-major.  Same arithmetic as the row-major calls: results are bit-identical. */
+ * every other output is row-major.  Same arithmetic as the row-major calls: results are bit-identical.
+ * Packed buffers hold an even number of rows: the pad row of an odd m (or n) may hold anything (NaN included) and reaches no output row
+ * < m; of a packed SwiGLU output neither the pad row nor, with ldc > N / 2 (a multiple of 32), the columns N / 2 .. ldc - 1 are written
+ * (::test_gemm_packed_pad_rows, ::test_gemm_fp8_packed_pad_rows). */
 int atspeed_gemm_packed(const void* a_dev, const void* w_dev, void* c_dev, int32_t m, int32_t n, int32_t k, int32_t ldc, int32_t epilogue,
                         void* workspace_dev, size_t workspace_bytes, void* stream);
 int atspeed_gemm_fp8_packed(const void* xq_dev, const float* sx_dev, const void* wq_dev, const float* sw_dev, void* c_dev, int32_t m,
@@ -367,7 +383,10 @@ int atspeed_quant_weights_mxfp4(const void* w_dev, int32_t rows, int32_t k, int3
  * atspeed_quant_rows_fp8 (packed = 1: atspeed_quant_rows_fp8_packed, and a SwiGLU output comes out packed too), wq / wscale from
  * atspeed_quant_weights_mxfp4; epilogues as atspeed_gemm (0 store, 1 fp32, 2 residual add, 3 SwiGLU) in dtype (ATSPEED_BF16 / ATSPEED_F16);
  * any m >= 1 (tiled over m); k % 256 == 0.  Thin grids are cut in k into fp32 slabs in workspace_dev when it holds them (parts x m x n x 4
- * bytes), else one part per tile. */
+ * bytes), else one part per tile.
+ * Memory contract (::test_gemm_w4a8_guard_bands, ::test_workspace_ladder[w4a8_split]): xq_dev and wq_dev 16-byte aligned; only
+ * [m][0 .. n) of C (SwiGLU: n / 2) and nothing from workspace_bytes on is written; xq rows >= m, sx entries >= m, weight rows >= n and
+ * their scale bytes influence no result. */
 int atspeed_gemm_w4a8(const void* xq_dev, const float* sx_dev, const void* wq_dev, const void* wscale_dev, void* c_dev, int32_t m, int32_t n,
                       int32_t k, int32_t ldc, int32_t epilogue, int32_t dtype, int32_t packed, void* workspace_dev, size_t workspace_bytes,
                       void* stream);
@@ -375,7 +394,8 @@ int atspeed_gemm_w4a8(const void* xq_dev, const float* sx_dev, const void* wq_de
 int atspeed_quant_rows_fp8(const void* x_bf16_dev, int32_t rows, int32_t cols, void* q_dev, float* scale_dev, void* stream);
 /* the same on operands in the packed layout (x through atspeed_pack_rows with row_bytes = 2 cols, q comes out as atspeed_pack_rows with
  * row_bytes = cols would lay it out; cols % 64 == 0; both buffers hold an even number of rows): what the engine runs between a bf16
- * producer (attention, SwiGLU) and the fp8 projection that consumes it -- one workgroup per row PAIR, whole 128-byte lines in and out */
+ * producer (attention, SwiGLU) and the fp8 projection that consumes it -- one workgroup per row PAIR, whole 128-byte lines in and out.
+ * The pad row of an odd row count is read (any bits) and never written, in q as in scale (::test_quant_rows_fp8_and_packed_guard_bands). */
 int atspeed_quant_rows_fp8_packed(const void* x_bf16_packed_dev, int32_t rows, int32_t cols, void* q_packed_dev, float* scale_dev, void* stream);
 /* m >= 257: the block-scaled MFMA ring kernel (K % 256 == 0, lock-step batches).  m <= 256 (round 5: one user's forwards, the reference's
  * own regime -- code/inference.py:86-91 loads its target 8-bit for every batch-1 forward): the weight-streaming kernel on e4m3 rows
@@ -384,7 +404,11 @@ int atspeed_quant_rows_fp8_packed(const void* x_bf16_packed_dev, int32_t rows, i
  * small N; 64 MB always suffices); with too little workspace the launch runs one part per tile; the residual epilogue (2) then takes the ring
  * kernel when K % 256 == 0 and returns ATSPEED_ERR_CAPACITY otherwise.
  * SIGNATURE NOTE: (workspace_dev, workspace_bytes) were inserted before `stream` in round 5; atspeed_version() reports 0.2 since round 6 so
- * that a caller built against the 0.1 header (stream in the workspace position) can tell. */
+ * that a caller built against the 0.1 header (stream in the workspace position) can tell.
+ * Memory contract (::test_gemm_fp8_guard_bands, ::test_workspace_ladder[fp8_*], ::test_gemm_fp8_residual_without_room_for_slabs_is_refused_before_any_launch):
+ * xq_dev and wq_dev 16-byte aligned, rows K bytes apart; only [m][0 .. n) of C (SwiGLU: n / 2) and nothing from workspace_bytes on is
+ * written, and a refused call has written nothing at all; xq rows >= m, wq rows >= n, sx entries >= m and sw entries >= n influence no
+ * result. */
 int atspeed_gemm_fp8(const void* xq_dev, const float* sx_dev, const void* wq_dev, const float* sw_dev, void* c_dev, int32_t m,
                      int32_t n, int32_t k, int32_t ldc, int32_t epilogue, void* workspace_dev, size_t workspace_bytes, void* stream);
 int atspeed_rmsnorm(const void* x_dev, const void* w_dev, void* y_dev, int32_t rows, int32_t hidden,
@@ -393,7 +417,13 @@ int atspeed_rmsnorm(const void* x_dev, const void* w_dev, void* y_dev, int32_t r
  * gate_up projections); y_dev may be NULL; q / scale equal atspeed_quant_rows_fp8 of the bf16 norm output bit for bit */
 int atspeed_rmsnorm_quant_fp8(const void* x_dev, const void* w_dev, void* y_dev, void* q_dev, float* scale_dev, int32_t rows,
                               int32_t hidden, float eps, void* stream);
-/* tree attention over a slot-addressed KV cache ([max_slots][hidden] per K and V) */
+/* tree attention over a slot-addressed KV cache ([max_slots][hidden] per K and V)
+ * Memory contract (tests/test_guard_bands_gpu.py::test_tree_attention_mfma_guard_bands, ::test_tree_attention_scalar_guard_bands): q rows are ldq
+ * >= 3 * hidden elements apart (tested: a multiple of 8), 16-byte aligned; out gets [n_tokens][hidden] and nothing else; q rows >=
+ * n_tokens, the columns 3 * hidden .. ldq - 1 and cache slots >= n_slots influence no result, whatever their bits.  Slots BELOW n_slots
+ * that no row sees must hold FINITE values: with any finite content, the type's largest value included, they change no output bit
+ * (::test_tree_attention_invisible_slots_below_n_slots_are_never_seen), but p = 0 times a NaN or Inf V inside an MFMA is NaN -- callers
+ * zero-fill a cache before its first use, as the engine does. */
 int atspeed_tree_attention(const void* q_dev, int32_t ldq, const void* kcache_dev, const void* vcache_dev,
                            const uint64_t* vis_bits_dev, int32_t vis_words, void* out_dev, int32_t n_tokens,
                            int32_t n_slots, int32_t n_heads, int32_t head_dim, int32_t dtype, void* stream);
