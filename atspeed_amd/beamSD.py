@@ -277,6 +277,34 @@ def _result(prompt: torch.Tensor, toks: torch.Tensor, scores: torch.Tensor, k: i
     return {"beam_sequence": seq, "beam_scores": scores}
 
 
+def _bssd_stats(st, k: int) -> Dict:
+    """One user's BSSD statistics (beamSD.py:527-541) from the library's record of the run."""
+    n_run = int(st.n_run)
+    total = int(st.total_accept_steps)
+    return {
+        "n_run": n_run,
+        "total_accept_steps": total,
+        "total_accept_tokens": total * k,
+        "ave_accept_tokens": total * k / n_run if n_run else 0.0,
+        "draft_time_cost": st.draft_ms * 1e-3,
+        "target_time_cost": st.target_ms * 1e-3,
+        "verify_time_cost": st.verify_ms * 1e-3,
+        "device_time_cost": st.total_ms * 1e-3,
+        "accept_steps": [int(st.accept_steps[i]) for i in range(min(n_run, _lib.MAX_NEW_TOKENS))],
+        "n_valid": int(st.n_valid),
+        "n_target_forwards": int(st.n_target_forwards),
+        "n_draft_forwards": int(st.n_draft_forwards),
+    }
+
+
+def _shared_fsm(fsms, who: str):
+    """The one automaton of a lock-step batch: the users' constraints may differ in their start node only."""
+    for f in fsms[1:]:
+        if f.row_ptr is not fsms[0].row_ptr:
+            raise ValueError(f"{who} needs one shared constraint automaton (only the start node may differ per user)")
+    return fsms[0]
+
+
 @Timer()
 @torch.no_grad()
 def BSSD(target_model, draft_model, inputs: Dict, gamma: int, max_new_tokens: int,
@@ -322,22 +350,7 @@ def BSSD(target_model, draft_model, inputs: Dict, gamma: int, max_new_tokens: in
                                              int(max_new_tokens), k, dk, toks.data_ptr(), scores.data_ptr(),
                                              C.byref(stats), _lib.stream_ptr(dev)))
     out = _result(prompt, toks, scores, k)
-    n_run = int(stats.n_run)
-    total = int(stats.total_accept_steps)
-    out.update({
-        "n_run": n_run,                                              # beamSD.py:527-541
-        "total_accept_steps": total,
-        "total_accept_tokens": total * k,
-        "ave_accept_tokens": total * k / n_run if n_run else 0.0,
-        "draft_time_cost": stats.draft_ms * 1e-3,
-        "target_time_cost": stats.target_ms * 1e-3,
-        "verify_time_cost": stats.verify_ms * 1e-3,
-        "device_time_cost": stats.total_ms * 1e-3,
-        "accept_steps": [int(stats.accept_steps[i]) for i in range(min(n_run, _lib.MAX_NEW_TOKENS))],
-        "n_valid": int(stats.n_valid),
-        "n_target_forwards": int(stats.n_target_forwards),
-        "n_draft_forwards": int(stats.n_draft_forwards),
-    })
+    out.update(_bssd_stats(stats, k))
     return out
 
 
@@ -371,10 +384,7 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
     t0 = time.time()
     prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
     fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
-    dfsm = _DeviceFSM.get(fsms[0], target_model.dims.vocab_size)
-    for f in fsms[1:]:
-        if f.row_ptr is not fsms[0].row_ptr:
-            raise ValueError("BSSD_batch needs one shared constraint automaton (only the start node may differ per user)")
+    dfsm = _DeviceFSM.get(_shared_fsm(fsms, "BSSD_batch"), target_model.dims.vocab_size)
     decs = [_Decoder.get(target_model, draft_model, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
     _set_sampling(decs, mode)
     _set_trace(decs, trace_decisions)
@@ -391,16 +401,9 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
     outs = []
     results = _batch_results(_keep, toks, scores, k)
     for i in range(n):
-        st = stats[i]
         out = results[i]
-        n_run, total = int(st.n_run), int(st.total_accept_steps)
-        out.update({"n_run": n_run, "total_accept_steps": total, "total_accept_tokens": total * k,
-                    "ave_accept_tokens": total * k / n_run if n_run else 0.0,
-                    "draft_time_cost": st.draft_ms * 1e-3, "target_time_cost": st.target_ms * 1e-3,
-                    "verify_time_cost": st.verify_ms * 1e-3, "device_time_cost": st.total_ms * 1e-3,
-                    "time_cost": wall / n, "n_valid": int(st.n_valid), "status": int(st.status),
-                    "accept_steps": [int(st.accept_steps[j]) for j in range(min(n_run, _lib.MAX_NEW_TOKENS))],
-                    "n_target_forwards": int(st.n_target_forwards), "n_draft_forwards": int(st.n_draft_forwards)})
+        out.update(_bssd_stats(stats[i], k))
+        out.update({"time_cost": wall / n, "status": int(stats[i].status)})
         outs.append(out)
     return outs
 
@@ -464,10 +467,7 @@ def target_generate_batch(model, inputs_list, max_new_tokens: int, prefix_allowe
     t0 = time.time()
     prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
     fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
-    dfsm = _DeviceFSM.get(fsms[0], model.dims.vocab_size)
-    for f in fsms[1:]:
-        if f.row_ptr is not fsms[0].row_ptr:
-            raise ValueError("target_generate_batch needs one shared constraint automaton (only the start node may differ per user)")
+    dfsm = _DeviceFSM.get(_shared_fsm(fsms, "target_generate_batch"), model.dims.vocab_size)
     decs = [_Decoder.get(model, None, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
     _set_sampling(decs, mode)
     with torch.cuda.device(dev):

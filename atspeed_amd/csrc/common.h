@@ -48,6 +48,7 @@ void atspeed_set_error(const char* fmt, ...);
     hipError_t _e = (expr);                                                                        \
     if (_e != hipSuccess) {                                                                        \
       atspeed_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+      (void)hipGetLastError(); /* reported here: the next launch check must not find it again */  \
       return ATSPEED_ERR_HIP;                                                                      \
     }                                                                                              \
   } while (0)

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -91,12 +92,13 @@ thread_local StageRing g_stage_dev[ATS_MAX_DEVICES];      // one ring per device
 constexpr size_t kStageBytes = 8u << 20;
 }  // namespace
 
-int ats_stage(const void* host_obj, size_t bytes, const void** dev_out, hipStream_t st) {
+// the current device's ring with `bytes` of host_obj copied to the pinned side; *off_out is the slot's offset on both sides
+static int stage_slot(const void* host_obj, size_t bytes, hipStream_t st, StageRing** ring_out, size_t* off_out) {
   const int dev = ats_cur_device();
   ATS_REQUIRE(dev >= 0, ATSPEED_ERR_NO_DEVICE, "staging: no current HIP device, or its id is >= %d", ATS_MAX_DEVICES);
   StageRing& r = g_stage_dev[dev];
-  if (!r.host) {
-    ATS_HIP(hipHostMalloc((void**)&r.host, kStageBytes));
+  if (!r.dev) {                                          // (a pinned side whose device side did not fit is kept for the next try)
+    if (!r.host) ATS_HIP(hipHostMalloc((void**)&r.host, kStageBytes));
     ATS_HIP(hipMalloc((void**)&r.dev, kStageBytes));
     r.cap = kStageBytes; r.used = 0;
   }
@@ -104,32 +106,32 @@ int ats_stage(const void* host_obj, size_t bytes, const void** dev_out, hipStrea
   ATS_REQUIRE(need <= r.cap, ATSPEED_ERR_CAPACITY, "staging: object of %zu bytes too large", bytes);
   if (r.used + need > r.cap) { ATS_HIP(hipStreamSynchronize(st)); r.used = 0; }
   memcpy(r.host + r.used, host_obj, bytes);
-  ATS_HIP(hipMemcpyAsync(r.dev + r.used, r.host + r.used, bytes, hipMemcpyHostToDevice, st));
-  *dev_out = r.dev + r.used;
+  *ring_out = &r; *off_out = r.used;
   r.used += need;
+  return ATSPEED_OK;
+}
+int ats_stage(const void* host_obj, size_t bytes, const void** dev_out, hipStream_t st) {
+  StageRing* r = nullptr; size_t off = 0;
+  ATS_TRY(stage_slot(host_obj, bytes, st, &r, &off));
+  ATS_HIP(hipMemcpyAsync(r->dev + off, r->host + off, bytes, hipMemcpyHostToDevice, st));
+  *dev_out = r->dev + off;
   return ATSPEED_OK;
 }
 // the same through the pinned ring, but to a device address of the caller's choice
 int ats_stage_to(const void* host_obj, size_t bytes, void* dev_dst, hipStream_t st) {
-  const int dev = ats_cur_device();
-  ATS_REQUIRE(dev >= 0, ATSPEED_ERR_NO_DEVICE, "staging: no current HIP device, or its id is >= %d", ATS_MAX_DEVICES);
-  StageRing& r = g_stage_dev[dev];
-  if (!r.host) {
-    ATS_HIP(hipHostMalloc((void**)&r.host, kStageBytes));
-    ATS_HIP(hipMalloc((void**)&r.dev, kStageBytes));
-    r.cap = kStageBytes; r.used = 0;
-  }
-  size_t need = (bytes + 255) / 256 * 256;
-  ATS_REQUIRE(need <= r.cap, ATSPEED_ERR_CAPACITY, "staging: object of %zu bytes too large", bytes);
-  if (r.used + need > r.cap) { ATS_HIP(hipStreamSynchronize(st)); r.used = 0; }
-  memcpy(r.host + r.used, host_obj, bytes);
-  ATS_HIP(hipMemcpyAsync(dev_dst, r.host + r.used, bytes, hipMemcpyHostToDevice, st));
-  r.used += need;
+  StageRing* r = nullptr; size_t off = 0;
+  ATS_TRY(stage_slot(host_obj, bytes, st, &r, &off));
+  ATS_HIP(hipMemcpyAsync(dev_dst, r->host + off, bytes, hipMemcpyHostToDevice, st));
   return ATSPEED_OK;
 }
 void ats_stage_reset() { const int dev = ats_cur_device(); if (dev >= 0) g_stage_dev[dev].used = 0; }
 
 // ---------------------------------------------------------------------------- FSM
+// A create function owns its half-built object through one of these: any early return (ATS_HIP / ATS_TRY / ATS_REQUIRE) then runs
+// the handle's own destroy function, which takes a partly filled object (handles are value-initialised, hipFree(nullptr) does nothing).
+template <typename T>
+using Building = std::unique_ptr<T, void (*)(T*)>;
+
 extern "C" int atspeed_fsm_create(const int32_t* row_ptr, const int32_t* tok, const int32_t* nxt, int32_t n_nodes,
                                   int32_t n_edges, int32_t vocab_size, atspeed_fsm** out) {
   ATS_REQUIRE(row_ptr && out && n_nodes >= 1 && n_edges >= 0 && vocab_size > 0, ATSPEED_ERR_INVALID, "fsm_create: bad arguments");
@@ -143,8 +145,7 @@ extern "C" int atspeed_fsm_create(const int32_t* row_ptr, const int32_t* tok, co
     }
   }
   ATS_REQUIRE((int64_t)ATSPEED_MAX_BEAMS * vocab_size < (int64_t)0x7fffffff, ATSPEED_ERR_CAPACITY, "fsm_create: vocab too large for 32-bit flat ids");
-  atspeed_fsm* f = new atspeed_fsm();
-  memset(f, 0, sizeof(*f));
+  Building<atspeed_fsm> f(new atspeed_fsm(), atspeed_fsm_destroy);
   size_t ne = (size_t)std::max(n_edges, 1);
   ATS_HIP(hipMalloc(&f->d_row_ptr, (size_t)(n_nodes + 1) * sizeof(int32_t)));
   ATS_HIP(hipMalloc(&f->d_tok, ne * sizeof(int32_t)));
@@ -161,7 +162,7 @@ extern "C" int atspeed_fsm_create(const int32_t* row_ptr, const int32_t* tok, co
   for (int e = 0; e < n_edges; ++e) tiles[tok[e] / 256] = 1;
   ATS_HIP(hipMalloc((void**)&f->d_tile_store, tiles.size()));
   ATS_HIP(hipMemcpy(f->d_tile_store, tiles.data(), tiles.size(), hipMemcpyHostToDevice));
-  *out = f;
+  *out = f.release();
   return ATSPEED_OK;
 }
 
@@ -170,13 +171,12 @@ extern "C" int atspeed_fsm_create(const int32_t* row_ptr, const int32_t* tok, co
 extern "C" int atspeed_fsm_create_free(int32_t vocab_size, atspeed_fsm** out) {
   ATS_REQUIRE(out && vocab_size > 0, ATSPEED_ERR_INVALID, "fsm_create_free: bad arguments");
   ATS_REQUIRE((int64_t)ATSPEED_MAX_BEAMS * vocab_size < (int64_t)0x7fffffff, ATSPEED_ERR_CAPACITY, "fsm_create_free: vocab too large for 32-bit flat ids");
-  atspeed_fsm* f = new atspeed_fsm();
-  memset(f, 0, sizeof(*f));
+  Building<atspeed_fsm> f(new atspeed_fsm(), atspeed_fsm_destroy);
   f->dev = FsmDev{nullptr, nullptr, nullptr, 0, 0, vocab_size, 0, -1};
   std::vector<unsigned char> tiles((size_t)(vocab_size + 255) / 256, 1);      // every logit tile can be read
   ATS_HIP(hipMalloc((void**)&f->d_tile_store, tiles.size()));
   ATS_HIP(hipMemcpy(f->d_tile_store, tiles.data(), tiles.size(), hipMemcpyHostToDevice));
-  *out = f;
+  *out = f.release();
   return ATSPEED_OK;
 }
 
@@ -263,6 +263,15 @@ struct ActCtx {
   std::vector<int> prof_kind, prof_m;            // kind / M per bracket of the pending forward
 };
 
+// library-owned quantised copies of one layer's four projections: weights and their scales (S = float: one per output row; void: packed bytes)
+template <typename S>
+struct QuantLayer { void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr; S *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr; };
+template <typename S>
+static void quant_layers_free(std::vector<QuantLayer<S>>& v) {
+  for (auto& f : v) { hipFree(f.wqkv); hipFree(f.wo); hipFree(f.wgu); hipFree(f.wd); hipFree(f.sqkv); hipFree(f.so); hipFree(f.sgu); hipFree(f.sd); }
+  v.clear();
+}
+
 struct atspeed_llama {
   atspeed_llama_config cfg;
   const void *embed, *final_norm, *lm_head;
@@ -271,12 +280,11 @@ struct atspeed_llama {
   int pk;                                        // 1: weights and GEMM-operand activations in the packed operand layout (common.h), bf16 only
   size_t layer_kv_bytes;
   float *cos_tab, *sin_tab;                      // [max_slots][head_dim/2]
-  // optional fp8 (e4m3, per-output-row scales) copies of the layer projections, library-owned (atspeed_llama_enable_fp8)
-  struct Fp8Layer { void *wqkv, *wo, *wgu, *wd; float *sqkv, *so, *sgu, *sd; };
+  // optional fp8 (e4m3, per-output-row scales) copies of the layer projections (atspeed_llama_enable_fp8)
+  using Fp8Layer = QuantLayer<float>;
   std::vector<Fp8Layer> fp8;
-  // optional MXFP4 copies (e2m1 nibbles [rows][K / 2] + E8M0 scale bytes [rows][K / 32], gemm.hip "W4A8"), library-owned (atspeed_llama_enable_fp4);
-  // exclusive with fp8
-  struct Fp4Layer { void *wqkv, *wo, *wgu, *wd; void *sqkv, *so, *sgu, *sd; };
+  // optional MXFP4 copies (e2m1 nibbles [rows][K / 2] + E8M0 scale bytes [rows][K / 32], gemm.hip "W4A8") (atspeed_llama_enable_fp4); exclusive with fp8
+  using Fp4Layer = QuantLayer<void>;
   std::vector<Fp4Layer> fp4;
   KvCache kv0;                                   // cache of the plain atspeed_llama_forward API
   std::vector<KvCache> kv_pool;                  // one more cache per segment of atspeed_llama_forward_batch (grown on demand)
@@ -365,7 +373,7 @@ static int ensure_act(atspeed_llama* m, int tok, int rows) {
   if (m->act && m->act->cap_tok >= tok && m->act->cap_rows >= rows) return ATSPEED_OK;
   if (m->act) { prof_harvest(m); ATS_HIP(hipDeviceSynchronize()); act_free(m->act); m->act = nullptr; }
   const atspeed_llama_config& c = m->cfg;
-  ActCtx* cx = new ActCtx();
+  Building<ActCtx> cx(new ActCtx(), act_free);
   // 25 % headroom: the next batch's token count differs by a few prompt tokens, and growing costs a device synchronisation plus
   // the re-allocation of every activation buffer (seen as 30-40 ms hiccups inside timed regions)
   // even counts: the packed operand layout stores row pairs, a last row with an even index still owns a full 128-byte line pair
@@ -389,7 +397,7 @@ static int ensure_act(atspeed_llama* m, int tok, int rows) {
   cx->ws_bytes = gemm_ws_for(c, cx->cap_tok, cx->cap_rows);
   ATS_HIP(hipMalloc(&cx->ws, cx->ws_bytes));
   ATS_HIP(hipMalloc((void**)&cx->segtab_dev, sizeof(SegTable)));
-  m->act = cx;
+  m->act = cx.release();
   return ATSPEED_OK;
 }
 
@@ -415,15 +423,20 @@ static void sk_arena_lazy(atspeed_llama* m, int T, hipStream_t st) {
 }
 extern "C" int64_t atspeed_llama_sk_arena_bytes(const atspeed_llama* m) { return m && m->act && m->act->sk.ws ? (int64_t)ATS_SK_ARENA_BYTES : 0; }
 
-static int kv_create(atspeed_llama* m, KvCache* kv) {
-  size_t bytes = (size_t)m->cfg.n_layers * m->layer_kv_bytes;
-  ATS_HIP(hipMalloc(&kv->k, bytes));
-  ATS_HIP(hipMalloc(&kv->v, bytes));
-  ATS_HIP(hipMemset(kv->k, 0, bytes));
-  ATS_HIP(hipMemset(kv->v, 0, bytes));
-  return ATSPEED_OK;
-}
 static void kv_free(KvCache* kv) { hipFree(kv->k); hipFree(kv->v); kv->k = kv->v = nullptr; }
+static int kv_create(atspeed_llama* m, KvCache* kv) {           // both halves or, on failure, neither
+  size_t bytes = (size_t)m->cfg.n_layers * m->layer_kv_bytes;
+  auto make = [&]() -> int {
+    ATS_HIP(hipMalloc(&kv->k, bytes));
+    ATS_HIP(hipMalloc(&kv->v, bytes));
+    ATS_HIP(hipMemset(kv->k, 0, bytes));
+    ATS_HIP(hipMemset(kv->v, 0, bytes));
+    return ATSPEED_OK;
+  };
+  const int rc = make();
+  if (rc != ATSPEED_OK) kv_free(kv);
+  return rc;
+}
 
 extern "C" int atspeed_llama_create(const atspeed_llama_config* cfg, const void* embed, const void* final_norm,
                                     const void* lm_head, const atspeed_llama_layer_weights* layers, atspeed_llama** out) {
@@ -439,7 +452,7 @@ extern "C" int atspeed_llama_create(const atspeed_llama_config* cfg, const void*
               "llama_create: bad token limits");
   ATS_REQUIRE(cfg->weight_layout == ATSPEED_WEIGHTS_ROW_MAJOR || cfg->weight_layout == ATSPEED_WEIGHTS_PACKED, ATSPEED_ERR_INVALID,
               "llama_create: weight_layout must be ATSPEED_WEIGHTS_ROW_MAJOR (0) or ATSPEED_WEIGHTS_PACKED (1)");
-  atspeed_llama* m = new atspeed_llama();
+  Building<atspeed_llama> m(new atspeed_llama(), atspeed_llama_destroy);
   m->cfg = *cfg;
   m->embed = embed; m->final_norm = final_norm; m->lm_head = lm_head;
   m->layers.assign(layers, layers + cfg->n_layers);
@@ -449,14 +462,10 @@ extern "C" int atspeed_llama_create(const atspeed_llama_config* cfg, const void*
   m->logits_ld = (cfg->vocab_size + 63) / 64 * 64;
   m->layer_kv_bytes = (size_t)cfg->max_slots * cfg->hidden * m->esz;
   m->pk = cfg->weight_layout == ATSPEED_WEIGHTS_PACKED ? 1 : 0;
-  if (m->pk && !((cfg->dtype == ATSPEED_BF16 || cfg->dtype == ATSPEED_F16) && cfg->hidden % 32 == 0 && cfg->ffn % 32 == 0)) {
-    atspeed_set_error("llama_create: packed weights need bf16 / fp16 and hidden / ffn multiples of 32 (hidden %d, ffn %d)", cfg->hidden, cfg->ffn);
-    delete m;
-    return ATSPEED_ERR_INVALID;
-  }
-  m->act = nullptr;
-  ATS_TRY(kv_create(m, &m->kv0));
-  ATS_TRY(ensure_act(m, cfg->max_tokens, cfg->max_logit_rows));
+  ATS_REQUIRE(!m->pk || ((cfg->dtype == ATSPEED_BF16 || cfg->dtype == ATSPEED_F16) && cfg->hidden % 32 == 0 && cfg->ffn % 32 == 0), ATSPEED_ERR_INVALID,
+              "llama_create: packed weights need bf16 / fp16 and hidden / ffn multiples of 32 (hidden %d, ffn %d)", cfg->hidden, cfg->ffn);
+  ATS_TRY(kv_create(m.get(), &m->kv0));
+  ATS_TRY(ensure_act(m.get(), cfg->max_tokens, cfg->max_logit_rows));
   // RoPE tables: HF computes inv_freq and the angle in fp32; cos/sin of that angle in double, rounded once
   int half = hd / 2;
   std::vector<float> ct((size_t)cfg->max_slots * half), stv((size_t)cfg->max_slots * half);
@@ -471,7 +480,7 @@ extern "C" int atspeed_llama_create(const atspeed_llama_config* cfg, const void*
   ATS_HIP(hipMalloc((void**)&m->sin_tab, stv.size() * sizeof(float)));
   ATS_HIP(hipMemcpy(m->cos_tab, ct.data(), ct.size() * sizeof(float), hipMemcpyHostToDevice));
   ATS_HIP(hipMemcpy(m->sin_tab, stv.data(), stv.size() * sizeof(float), hipMemcpyHostToDevice));
-  *out = m;
+  *out = m.release();
   return ATSPEED_OK;
 }
 
@@ -480,8 +489,8 @@ extern "C" void atspeed_llama_destroy(atspeed_llama* m) {
   kv_free(&m->kv0);
   for (KvCache& kv : m->kv_pool) kv_free(&kv);
   act_free(m->act);
-  for (auto& f : m->fp8) { hipFree(f.wqkv); hipFree(f.wo); hipFree(f.wgu); hipFree(f.wd); hipFree(f.sqkv); hipFree(f.so); hipFree(f.sgu); hipFree(f.sd); }
-  for (auto& f : m->fp4) { hipFree(f.wqkv); hipFree(f.wo); hipFree(f.wgu); hipFree(f.wd); hipFree(f.sqkv); hipFree(f.so); hipFree(f.sgu); hipFree(f.sd); }
+  quant_layers_free(m->fp8);
+  quant_layers_free(m->fp4);
   hipFree(m->cos_tab); hipFree(m->sin_tab);
   delete m;
 }
@@ -533,24 +542,21 @@ extern "C" int atspeed_lmhead_lse(const void* x, const void* w, float* logits, f
   return rc;
 }
 
-extern "C" int atspeed_llama_fp8_counters(atspeed_llama* m, int64_t* fp8_out, int64_t* other_out, int32_t reset) {
-  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "fp8_counters: null model");
+// how often each layer projection ran in the quantised format (`cnt`: fp8_cnt or fp4_cnt) and how often as a 16-bit (fp32) GEMM
+static int quant_counters(atspeed_llama* m, const char* who, long* cnt, int64_t* quant_out, int64_t* other_out, int32_t reset) {
+  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "%s: null model", who);
   for (int i = 0; i < 4; ++i) {
-    if (fp8_out) fp8_out[i] = m->fp8_cnt[i];
+    if (quant_out) quant_out[i] = cnt[i];
     if (other_out) other_out[i] = m->other_cnt[i];
-    if (reset) { m->fp8_cnt[i] = 0; m->other_cnt[i] = 0; }
+    if (reset) { cnt[i] = 0; m->other_cnt[i] = 0; }
   }
   return ATSPEED_OK;
 }
-
+extern "C" int atspeed_llama_fp8_counters(atspeed_llama* m, int64_t* fp8_out, int64_t* other_out, int32_t reset) {
+  return quant_counters(m, "fp8_counters", m ? m->fp8_cnt : nullptr, fp8_out, other_out, reset);
+}
 extern "C" int atspeed_llama_fp4_counters(atspeed_llama* m, int64_t* fp4_out, int64_t* other_out, int32_t reset) {
-  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "fp4_counters: null model");
-  for (int i = 0; i < 4; ++i) {
-    if (fp4_out) fp4_out[i] = m->fp4_cnt[i];
-    if (other_out) other_out[i] = m->other_cnt[i];
-    if (reset) { m->fp4_cnt[i] = 0; m->other_cnt[i] = 0; }
-  }
-  return ATSPEED_OK;
+  return quant_counters(m, "fp4_counters", m ? m->fp4_cnt : nullptr, fp4_out, other_out, reset);
 }
 
 extern "C" int64_t atspeed_llama_rope_fused_launches(atspeed_llama* m, int32_t reset) {
@@ -563,6 +569,31 @@ extern "C" int64_t atspeed_llama_rope_fused_launches(atspeed_llama* m, int32_t r
 extern "C" float* atspeed_llama_logits(atspeed_llama* m) { return m && m->act ? m->act->logits : nullptr; }
 extern "C" int32_t atspeed_llama_logits_ld(const atspeed_llama* m) { return m ? m->logits_ld : 0; }
 
+// The quantised copies of every layer, made by `quant` (allocates one projection's copy and scales, launches its quantiser on st).  They are
+// built aside and reach *dst only after the last quantiser has run: on any failure the copies made so far are freed and the model is as before.
+template <typename S, typename Quant>
+static int quant_layers_build(atspeed_llama* m, std::vector<QuantLayer<S>>* dst, hipStream_t st, Quant quant) {
+  const int H = m->cfg.hidden, F = m->cfg.ffn;
+  std::vector<QuantLayer<S>> q(m->cfg.n_layers);
+  int rc = ATSPEED_OK;
+  for (int l = 0; rc == ATSPEED_OK && l < m->cfg.n_layers; ++l) {
+    const atspeed_llama_layer_weights& w = m->layers[l];
+    QuantLayer<S>& f = q[l];
+    rc = quant(w.wqkv, 3 * H, H, &f.wqkv, &f.sqkv);
+    if (rc == ATSPEED_OK) rc = quant(w.wo, H, H, &f.wo, &f.so);
+    if (rc == ATSPEED_OK) rc = quant(w.wgu, 2 * F, H, &f.wgu, &f.sgu);
+    if (rc == ATSPEED_OK) rc = quant(w.wd, H, F, &f.wd, &f.sd);
+  }
+  const hipError_t e = hipStreamSynchronize(st);      // on failure too: the quantisers already launched write the copies
+  if (rc != ATSPEED_OK || e != hipSuccess) {
+    quant_layers_free(q);
+    ATS_TRY(rc);
+    ATS_HIP(e);
+  }
+  *dst = std::move(q);
+  return ATSPEED_OK;
+}
+
 extern "C" int atspeed_llama_enable_fp8(atspeed_llama* m, void* stream) {
   ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "enable_fp8: null model");
   // bf16 or fp16 weights (round 6: the reference loads fp16 checkpoints and runs the target 8-bit, code/inference.py:75-91): the e4m3 copies are
@@ -572,23 +603,11 @@ extern "C" int atspeed_llama_enable_fp8(atspeed_llama* m, void* stream) {
   ATS_REQUIRE(m->fp4.empty(), ATSPEED_ERR_INVALID, "enable_fp8: the model already runs the 4-bit target (atspeed_llama_enable_fp4)");
   if (!m->fp8.empty()) return ATSPEED_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int H = m->cfg.hidden, F = m->cfg.ffn;
-  auto quant = [&](const void* w, int rows, int cols, void** q, float** sc) -> int {     // packed 16-bit rows -> packed e4m3 rows (or row-major both)
+  return quant_layers_build(m, &m->fp8, st, [&](const void* w, int rows, int cols, void** q, float** sc) -> int {     // packed 16-bit rows -> packed e4m3 rows (or row-major both)
     ATS_HIP(hipMalloc(q, (size_t)((rows + 1) & ~1) * cols));
     ATS_HIP(hipMalloc((void**)sc, (size_t)rows * sizeof(float)));
     return ATS_KD(m->cfg.dtype, ats_quant_rows_fp8(w, rows, cols, cols, *q, *sc, st, m->pk));
-  };
-  m->fp8.resize(m->cfg.n_layers);
-  for (int l = 0; l < m->cfg.n_layers; ++l) {
-    const atspeed_llama_layer_weights& w = m->layers[l];
-    atspeed_llama::Fp8Layer& f = m->fp8[l];
-    ATS_TRY(quant(w.wqkv, 3 * H, H, &f.wqkv, &f.sqkv));
-    ATS_TRY(quant(w.wo, H, H, &f.wo, &f.so));
-    ATS_TRY(quant(w.wgu, 2 * F, H, &f.wgu, &f.sgu));
-    ATS_TRY(quant(w.wd, H, F, &f.wd, &f.sd));
-  }
-  ATS_HIP(hipStreamSynchronize(st));
-  return ATSPEED_OK;
+  });
 }
 
 extern "C" int atspeed_llama_enable_fp4(atspeed_llama* m, void* stream) {
@@ -599,28 +618,14 @@ extern "C" int atspeed_llama_enable_fp4(atspeed_llama* m, void* stream) {
   ATS_REQUIRE(m->fp8.empty(), ATSPEED_ERR_INVALID, "enable_fp4: the model already runs the 8-bit target (atspeed_llama_enable_fp8)");
   if (!m->fp4.empty()) return ATSPEED_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int H = m->cfg.hidden, F = m->cfg.ffn;
-  std::vector<atspeed_llama::Fp4Layer> fp4(m->cfg.n_layers, atspeed_llama::Fp4Layer{});
-  auto free_all = [&]() { for (auto& f : fp4) { hipFree(f.wqkv); hipFree(f.wo); hipFree(f.wgu); hipFree(f.wd); hipFree(f.sqkv); hipFree(f.so); hipFree(f.sgu); hipFree(f.sd); } };
-  auto quant = [&](const void* w, int rows, int cols, void** q, void** sc) -> int {     // 16-bit rows (packed or row-major) -> nibbles + scale bytes
+  return quant_layers_build(m, &m->fp4, st, [&](const void* w, int rows, int cols, void** q, void** sc) -> int {     // 16-bit rows (packed or row-major) -> nibbles + scale bytes
     if (hipMalloc(q, (size_t)rows * cols / 2) != hipSuccess || hipMalloc(sc, (size_t)rows * cols / 32) != hipSuccess) {
       atspeed_set_error("enable_fp4: out of device memory for the MXFP4 copies");
+      (void)hipGetLastError();
       return ATSPEED_ERR_HIP;
     }
     return ATS_KD(m->cfg.dtype, ats_quant_weights_mxfp4(w, rows, cols, *q, *sc, st, m->pk));
-  };
-  for (int l = 0; l < m->cfg.n_layers; ++l) {
-    const atspeed_llama_layer_weights& w = m->layers[l];
-    atspeed_llama::Fp4Layer& f = fp4[l];
-    int rc = quant(w.wqkv, 3 * H, H, &f.wqkv, &f.sqkv);
-    if (rc == ATSPEED_OK) rc = quant(w.wo, H, H, &f.wo, &f.so);
-    if (rc == ATSPEED_OK) rc = quant(w.wgu, 2 * F, H, &f.wgu, &f.sgu);
-    if (rc == ATSPEED_OK) rc = quant(w.wd, H, F, &f.wd, &f.sd);
-    if (rc != ATSPEED_OK) { (void)hipStreamSynchronize(st); free_all(); return rc; }
-  }
-  if (hipStreamSynchronize(st) != hipSuccess) { free_all(); ATS_HIP(hipGetLastError()); return ATSPEED_ERR_HIP; }
-  m->fp4 = std::move(fp4);
-  return ATSPEED_OK;
+  });
 }
 
 // One forward over the tokens of every segment (user) of the table.  Logits of each segment's last n_logit rows land
@@ -808,7 +813,7 @@ extern "C" int atspeed_decoder_create(atspeed_llama* target, atspeed_llama* draf
     ATS_REQUIRE(draft->cfg.vocab_size == target->cfg.vocab_size, ATSPEED_ERR_INVALID, "decoder_create: draft/target vocab differ");
     ATS_REQUIRE(draft->cfg.max_slots == target->cfg.max_slots, ATSPEED_ERR_INVALID, "decoder_create: draft/target max_slots differ");
   }
-  atspeed_decoder* d = new atspeed_decoder();
+  Building<atspeed_decoder> d(new atspeed_decoder(), atspeed_decoder_destroy);
   d->target = target; d->draft = draft;
   ATS_TRY(kv_create(target, &d->tkv));
   if (draft) ATS_TRY(kv_create(draft, &d->dkv));
@@ -837,19 +842,19 @@ extern "C" int atspeed_decoder_create(atspeed_llama* target, atspeed_llama* draf
   ATS_HIP(hipHostGetDevicePointer((void**)&d->mail_dev, d->mail_host, 0));
   ATS_HIP(hipHostMalloc((void**)&d->trace_host, sizeof(int32_t) * ATSPEED_MAX_GAMMA * MAXB));
   d->run.done = true;
-  *out = d;
+  *out = d.release();
   return ATSPEED_OK;
 }
 
 extern "C" void atspeed_decoder_destroy(atspeed_decoder* d) {
   if (!d) return;
-  hipFree(d->tab_score); hipFree(d->tab_off); hipFree(d->tab_lse);
   hipDeviceSynchronize();
+  hipFree(d->tab_score); hipFree(d->tab_off); hipFree(d->tab_lse);
   kv_free(&d->tkv);
-  if (d->draft) kv_free(&d->dkv);
+  kv_free(&d->dkv);
   hipFree(d->arena);
-  hipHostFree(d->mail_host);
-  hipHostFree(d->trace_host);
+  if (d->mail_host) hipHostFree(d->mail_host);
+  if (d->trace_host) hipHostFree(d->trace_host);
   if (d->dump_host) hipHostFree(d->dump_host);
   delete d;
 }
@@ -989,6 +994,48 @@ static int seg_finish(SegTable& t) {
   return ATSPEED_OK;
 }
 
+// ---- one decode step: forward, then every user's beam step on its rows of the result
+// where a segment's logit rows, their normalisers and their candidate lists start in the model's buffers
+struct RowViews { const float* logits; const float* lse; const int32_t* row_cand; };
+static RowViews seg_rows(const atspeed_llama* m, const Seg& sg) {
+  const ActCtx* cx = m->act;
+  return RowViews{cx->logits + (size_t)sg.logit_row0 * m->logits_ld, cx->lse + sg.logit_row0, cx->row_cand + (size_t)sg.logit_row0 * MAXB};
+}
+
+// the forward of a decode step: only the logit tiles the automaton can read are written; a mask-free search takes its candidates from
+// the kk best tokens of every row instead
+static int decode_forward(atspeed_llama* m, const SegTable& t, const atspeed_fsm* fsm, int kk, hipStream_t st) {
+  ATS_TRY(llama_forward_segs(m, t, nullptr, st, fsm->d_tile_store));
+  if (fsm->dev.n_nodes == 0) ATS_TRY(ats_row_topk(m->act->logits, t.total_logit, m->cfg.vocab_size, m->logits_ld, kk, m->act->row_cand, st));
+  return ATSPEED_OK;
+}
+
+// what every beam step shares: user d expands the sg.n_logit beams of `src`, scored by model m's logit rows of segment sg, into the k best
+// of `dst`.  The caller adds what differs: emit with the in / out token rows, the tab_* tables and, when a.sample is set, rng_sub.
+static BeamStepArgs beam_step_args(const atspeed_decoder* d, const atspeed_llama* m, const Seg& sg, const atspeed_fsm* fsm, const BeamSet& src,
+                                   const BeamSet& dst, int gen_len, int k) {
+  const RowViews rv = seg_rows(m, sg);
+  BeamStepArgs a{};
+  a.src = src; a.n_src = sg.n_logit; a.gen_len = gen_len; a.dst = dst; a.k = k;
+  a.logits = rv.logits; a.ld = m->logits_ld; a.lse = rv.lse; a.row_cand = rv.row_cand; a.n_row_cand = k;
+  a.fsm = fsm->dev; a.filter_ids = fsm->dev.n_nodes == 0 ? 0 : 1;
+  a.mail = d->mail_dev; a.vis_words = d->W;
+  if (d->sample) { a.sample = 1; a.temperature = d->temperature; }
+  return a;
+}
+// the step also writes the next forward's inputs: the parents' rows start at in_row0 of tb, the k new rows go to out_row0 (KV slots from out_slot0)
+static void beam_step_emit(BeamStepArgs& a, const TokBuf& tb, int in_row0, int out_row0, int out_slot0) {
+  a.emit = 1; a.in = tb; a.in_row0 = in_row0; a.out = tb; a.out_row0 = out_row0; a.out_slot0 = out_slot0;
+}
+
+// out_tokens / out_scores of the users that finish: one user by value, several through one staged launch
+static int export_beams(const std::vector<ExportBeamsArgs>& ex, int k, int max_new, hipStream_t st) {
+  if (ex.size() == 1) return ats_export_beams(ex[0].b, k, max_new, ex[0].out_tokens, ex[0].out_scores, st, ex[0].sort_desc != 0);
+  const ExportBeamsArgs* de = nullptr;
+  ATS_TRY(stage_args(ex, &de, st));
+  return ats_export_beams_multi(de, (int)ex.size(), k, max_new, st);
+}
+
 // prompts of every user of a batch -> token buffers, start beams and mailboxes, one launch
 static int init_prompts_multi(atspeed_decoder** decs, int n, const int32_t* const* prompts, const int32_t* prompt_lens, const int32_t* start_nodes,
                               hipStream_t st) {
@@ -1076,24 +1123,14 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
         r.s.n_draft_forwards++;
       }
       ATS_TRY(seg_finish(t));
-      ATS_TRY(llama_forward_segs(D, t, nullptr, st, decs[0]->run.fsm->d_tile_store));
-      const bool free_fsm = decs[0]->run.fsm->dev.n_nodes == 0;
-      if (free_fsm) ATS_TRY(ats_row_topk(D->act->logits, t.total_logit, D->cfg.vocab_size, D->logits_ld, decs[0]->run.dk, D->act->row_cand, st));
+      ATS_TRY(decode_forward(D, t, decs[0]->run.fsm, decs[0]->run.dk, st));
       for (size_t j = 0; j < us.size(); ++j) {
         atspeed_decoder* d = us[j];
         atspeed_decoder::Run& r = d->run;
-        TokBuf& tin = d->tin[r.cur];
-        BeamStepArgs a{};
-        a.src = i == 0 ? d->round_beams[r.cur] : d->blk[i]; a.n_src = t.seg[j].n_logit; a.gen_len = r.gen + i;
-        a.logits = D->act->logits + (size_t)t.seg[j].logit_row0 * D->logits_ld; a.ld = D->logits_ld;
-        a.lse = D->act->lse + t.seg[j].logit_row0; a.fsm = r.fsm->dev; a.k = r.dk;
-        a.dst = d->blk[i + 1]; a.emit = 1; a.filter_ids = free_fsm ? 0 : 1;
-        a.row_cand = D->act->row_cand + (size_t)t.seg[j].logit_row0 * ATSPEED_MAX_BEAMS; a.n_row_cand = r.dk;
-        a.in = tin; a.in_row0 = i == 0 ? r.n0 - r.nb : r.n0 + (i - 1) * r.dk;
-        a.out = tin; a.out_row0 = r.n0 + i * r.dk; a.out_slot0 = r.base + r.n0 + i * r.dk; a.vis_words = W;
-        a.mail = d->mail_dev;
-        if (d->sample) {
-          a.sample = 1; a.temperature = d->temperature; a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, i, 1);
+        BeamStepArgs a = beam_step_args(d, D, t.seg[j], r.fsm, i == 0 ? d->round_beams[r.cur] : d->blk[i], d->blk[i + 1], r.gen + i, r.dk);
+        beam_step_emit(a, d->tin[r.cur], i == 0 ? r.n0 - r.nb : r.n0 + (i - 1) * r.dk, r.n0 + i * r.dk, r.base + r.n0 + i * r.dk);
+        if (a.sample) {
+          a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, i, 1);
           a.tab_score = d->tab_score + (size_t)i * ATS_MAX_CAND; a.tab_off = d->tab_off + (size_t)i * (MAXB + 1); a.tab_lse = d->tab_lse + i;
         }
         args.push_back(a);
@@ -1119,22 +1156,20 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
         r.s.n_target_forwards++;
       }
       ATS_TRY(seg_finish(t));
-      ATS_TRY(llama_forward_segs(T, t, nullptr, st, decs[0]->run.fsm->d_tile_store));
-      const bool free_fsm = decs[0]->run.fsm->dev.n_nodes == 0;
-      if (free_fsm) ATS_TRY(ats_row_topk(T->act->logits, t.total_logit, T->cfg.vocab_size, T->logits_ld, decs[0]->run.k, T->act->row_cand, st));
+      ATS_TRY(decode_forward(T, t, decs[0]->run.fsm, decs[0]->run.k, st));
       hipEventRecord(g_ev[2], st);
       // ---- 3. verify (:242-456) for the verifying users, one workgroup each
       std::vector<VerifyArgs> vargs;
       for (size_t j = 0; j < ver.size(); ++j) {
         atspeed_decoder* d = ver[j];
         atspeed_decoder::Run& r = d->run;
+        const RowViews rv = seg_rows(T, t.seg[j]);
         VerifyArgs va{};
         va.blk[0] = d->round_beams[r.cur];
         for (int i = 1; i <= r.dl; ++i) va.blk[i] = d->blk[i];
         va.nb = r.nb; va.dl = r.dl; va.k = r.k; va.dk = r.dk; va.gen_len0 = r.gen;
-        va.logits = T->act->logits + (size_t)t.seg[j].logit_row0 * T->logits_ld; va.ld = T->logits_ld;
-        va.lse = T->act->lse + t.seg[j].logit_row0; va.fsm = r.fsm->dev;
-        va.row_cand = T->act->row_cand + (size_t)t.seg[j].logit_row0 * ATSPEED_MAX_BEAMS; va.n_row_cand = r.k;
+        va.logits = rv.logits; va.ld = T->logits_ld; va.lse = rv.lse; va.fsm = r.fsm->dev;
+        va.row_cand = rv.row_cand; va.n_row_cand = r.k;
         va.cur = d->tin[r.cur]; va.n0 = r.n0; va.next = d->tin[r.cur ^ 1]; va.dnext = d->dround; va.vis_words = W;
         va.res = d->round_beams[r.cur ^ 1]; va.mail = d->mail_dev;
         va.vtrace = (d->trace_level >= 1 && !d->sample) ? d->vtrace_dev : nullptr;
@@ -1156,14 +1191,8 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
       for (size_t j = 0; j < fin.size(); ++j) {
         atspeed_decoder* d = fin[j];
         atspeed_decoder::Run& r = d->run;
-        const Seg& sg = t.seg[ver.size() + j];
-        BeamStepArgs a{};
-        a.src = d->round_beams[r.cur]; a.n_src = r.nb; a.gen_len = r.gen;
-        a.logits = T->act->logits + (size_t)sg.logit_row0 * T->logits_ld; a.ld = T->logits_ld;
-        a.lse = T->act->lse + sg.logit_row0; a.fsm = r.fsm->dev; a.k = r.k;
-        a.dst = d->round_beams[r.cur ^ 1]; a.emit = 0; a.filter_ids = free_fsm ? 0 : 1; a.mail = d->mail_dev; a.vis_words = W;
-        a.row_cand = T->act->row_cand + (size_t)sg.logit_row0 * ATSPEED_MAX_BEAMS; a.n_row_cand = r.k;
-        if (d->sample) { a.sample = 1; a.temperature = d->temperature; a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, 0, 0); }
+        BeamStepArgs a = beam_step_args(d, T, t.seg[ver.size() + j], r.fsm, d->round_beams[r.cur], d->round_beams[r.cur ^ 1], r.gen, r.k);   // emits nothing
+        if (a.sample) a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, 0, 0);
         fargs.push_back(a);
       }
       if (!fargs.empty()) {
@@ -1183,12 +1212,7 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
       atspeed_decoder::Run& r = d->run;
       if (!r.done && r.final_step) ex.push_back(ExportBeamsArgs{d->round_beams[r.cur], r.out_tokens, r.out_scores, d->sample ? 1 : 0});
     }
-    if (ex.size() == 1) ATS_TRY(ats_export_beams(ex[0].b, decs[0]->run.k, decs[0]->run.max_new, ex[0].out_tokens, ex[0].out_scores, st, ex[0].sort_desc != 0));
-    else if (!ex.empty()) {
-      const ExportBeamsArgs* de = nullptr;
-      ATS_TRY(stage_args(ex, &de, st));
-      ATS_TRY(ats_export_beams_multi(de, (int)ex.size(), decs[0]->run.k, decs[0]->run.max_new, st));
-    }
+    if (!ex.empty()) ATS_TRY(export_beams(ex, decs[0]->run.k, decs[0]->run.max_new, st));
     for (int u = 0; u < n; ++u) {
       atspeed_decoder* d = decs[u];
       atspeed_decoder::Run& r = d->run;
@@ -1285,129 +1309,76 @@ extern "C" int atspeed_bssd_generate(atspeed_decoder* d, const int32_t* prompt, 
   return bssd_group_run(&d, 1, (hipStream_t)stream);
 }
 
-extern "C" int atspeed_target_generate(atspeed_decoder* d, const int32_t* prompt, int32_t P, const atspeed_fsm* fsm,
-                                       int32_t start_node, int32_t max_new, int32_t k, int32_t* out_tokens,
-                                       float* out_scores, atspeed_gen_stats* stats, void* stream) {
+// ---- target_generate (beamSD.py:544-595) for n users in lock step: step g of every user is ONE forward + one beam-step launch
+// (the teacher-data job of generate_teacher_data.py:211-244 is exactly this loop over a whole training set)
+static int target_check(atspeed_decoder* d, const int32_t* prompt, int P, const atspeed_fsm* fsm, int start_node, int max_new, int k,
+                        const int32_t* out_tokens, const float* out_scores) {
   ATS_TRY(check_common(d, prompt, P, fsm, start_node, max_new, k, out_tokens, out_scores));
-  hipStream_t st = (hipStream_t)stream;
-  atspeed_llama* T = d->target;
-  const int W = d->W, V = T->cfg.vocab_size;
-  atspeed_gen_stats s;
-  memset(&s, 0, sizeof(s));
-  ATS_REQUIRE(P + max_new * k <= T->cfg.max_slots, ATSPEED_ERR_CAPACITY, "target_generate: KV slots exhausted");
+  ATS_REQUIRE(P + max_new * k <= d->target->cfg.max_slots, ATSPEED_ERR_CAPACITY, "target_generate: KV slots exhausted");
   ATS_REQUIRE(P + max_new * k <= d->tok_cap, ATSPEED_ERR_CAPACITY, "target_generate: token buffer too small");
-  ATS_TRY(ensure_act(T, std::max(P, k), MAXB));
-  hipEvent_t* g_ev = nullptr;
-  ATS_TRY(stage_events(&g_ev));
-  TokBuf& tin = d->tin[0];
-  ATS_TRY(ats_init_prompt(tin, prompt, P, W, d->round_beams[0], start_node, T->cfg.vocab_size, d->mail_dev, st));
-  hipEventRecord(g_ev[0], st);
-  int cur = 0, row0 = 0, n_in = P, nb = 1, base = 0;
-  for (int g = 0; g < max_new; ++g) {                                                // beamSD.py:579-588
-    SegTable t{};
-    t.n = 1;
-    t.seg[0] = make_seg(tb_offset(tin, row0, W), n_in, base + n_in, nb, d->tkv);
-    ATS_TRY(seg_finish(t));
-    ATS_TRY(llama_forward_segs(T, t, nullptr, st, fsm->d_tile_store));
-    const bool free_fsm = fsm->dev.n_nodes == 0;
-    if (free_fsm) ATS_TRY(ats_row_topk(T->act->logits, t.total_logit, V, T->logits_ld, k, T->act->row_cand, st));
-    s.n_target_forwards++;
-    BeamStepArgs a{};
-    a.src = d->round_beams[cur]; a.n_src = nb; a.gen_len = g;
-    a.logits = T->act->logits; a.ld = T->logits_ld; a.lse = T->act->lse; a.fsm = fsm->dev; a.k = k;
-    a.dst = d->round_beams[cur ^ 1]; a.emit = 1; a.filter_ids = free_fsm ? 0 : 1;
-    a.row_cand = T->act->row_cand; a.n_row_cand = k;
-    a.in = tin; a.in_row0 = row0 + n_in - nb;
-    a.out = tin; a.out_row0 = row0 + n_in; a.out_slot0 = base + n_in; a.vis_words = W;
-    a.mail = d->mail_dev;
-    if (d->sample) { a.sample = 1; a.temperature = d->temperature; a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, g, 0, 0); }
-    ATS_TRY(ats_beam_step(a, st));
-    row0 += n_in; base += n_in; n_in = k; nb = k; cur ^= 1;
-  }
-  ATS_TRY(ats_export_beams(d->round_beams[cur], k, max_new, out_tokens, out_scores, st, d->sample));
-  hipEventRecord(g_ev[1], st);
-  ATS_HIP(hipStreamSynchronize(st));
-  ATS_TRY(mailbox_status(d));
-  s.n_valid = d->mail_host->n_valid;
-  hipEventElapsedTime(&s.total_ms, g_ev[0], g_ev[1]);
-  s.target_ms = s.total_ms;
-  if (stats) *stats = s;
   return ATSPEED_OK;
 }
 
-// target_generate (beamSD.py:544-595) for n users in lock step: step g of every user is ONE forward + one beam-step launch
-// (the teacher-data job of generate_teacher_data.py:211-244 is exactly this loop over a whole training set).
-extern "C" int atspeed_target_generate_batch(atspeed_decoder** decs, int32_t n, const int32_t* const* prompts,
-                                             const int32_t* prompt_lens, const atspeed_fsm* fsm, const int32_t* start_nodes,
-                                             int32_t max_new, int32_t k, int32_t* const* out_tokens, float* const* out_scores,
-                                             atspeed_gen_stats* stats, void* stream) {
-  ATS_REQUIRE(decs && prompts && prompt_lens && start_nodes && out_tokens && out_scores, ATSPEED_ERR_INVALID, "target_generate_batch: null argument");
-  ATS_REQUIRE(n >= 1 && n <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "target_generate_batch: %d users per call (max %d)", n, ATS_MAX_SEGS);
-  hipStream_t st = (hipStream_t)stream;
+// the users have passed target_check.  One user's launches take their arguments by value (nothing but the segment table is staged: no
+// host-to-device copy in front of its beam kernels); several users' go through staged argument blocks, one workgroup per user.
+static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const* prompts, const int32_t* prompt_lens, const atspeed_fsm* fsm,
+                            const int32_t* start_nodes, int max_new, int k, int32_t* const* out_tokens, float* const* out_scores,
+                            atspeed_gen_stats* stats, hipStream_t st) {
   atspeed_llama* T = decs[0]->target;
   const int W = decs[0]->W;
   int cap_t = 0;
-  for (int u = 0; u < n; ++u) {
-    atspeed_decoder* d = decs[u];
-    ATS_REQUIRE(d && d->target == T, ATSPEED_ERR_INVALID, "target_generate_batch: decoders must share one target model");
-    for (int j = 0; j < u; ++j) ATS_REQUIRE(decs[u] != decs[j], ATSPEED_ERR_INVALID, "target_generate_batch: decoder %d used twice", u);
-    ATS_TRY(check_common(d, prompts[u], prompt_lens[u], fsm, start_nodes[u], max_new, k, out_tokens[u], out_scores[u]));
-    ATS_REQUIRE(prompt_lens[u] + max_new * k <= T->cfg.max_slots, ATSPEED_ERR_CAPACITY, "target_generate: KV slots exhausted");
-    ATS_REQUIRE(prompt_lens[u] + max_new * k <= d->tok_cap, ATSPEED_ERR_CAPACITY, "target_generate: token buffer too small");
-    cap_t += std::max(prompt_lens[u], k);
-  }
+  for (int u = 0; u < n; ++u) cap_t += std::max(prompt_lens[u], k);
   ATS_TRY(ensure_act(T, cap_t, n * MAXB));
   hipEvent_t* g_ev = nullptr;
   ATS_TRY(stage_events(&g_ev));
-  ATS_TRY(init_prompts_multi(decs, n, prompts, prompt_lens, start_nodes, st));
+  if (n == 1) {
+    atspeed_decoder* d = decs[0];
+    ATS_TRY(ats_init_prompt(d->tin[0], prompts[0], prompt_lens[0], W, d->round_beams[0], start_nodes[0], T->cfg.vocab_size, d->mail_dev, st));
+  } else {
+    ATS_TRY(init_prompts_multi(decs, n, prompts, prompt_lens, start_nodes, st));
+  }
   hipEventRecord(g_ev[0], st);
   struct St { int row0, n_in, nb, base, cur; };
   std::vector<St> s(n);
   for (int u = 0; u < n; ++u) s[u] = St{0, prompt_lens[u], 1, 0, 0};
+  std::vector<BeamStepArgs> args(n);
   for (int g = 0; g < max_new; ++g) {                                                // beamSD.py:579-588
     SegTable t{};
     for (int u = 0; u < n; ++u)
       t.seg[t.n++] = make_seg(tb_offset(decs[u]->tin[0], s[u].row0, W), s[u].n_in, s[u].base + s[u].n_in, s[u].nb, decs[u]->tkv);
     ATS_TRY(seg_finish(t));
-    ATS_TRY(llama_forward_segs(T, t, nullptr, st, fsm->d_tile_store));
-    const bool free_fsm = fsm->dev.n_nodes == 0;
-    if (free_fsm) ATS_TRY(ats_row_topk(T->act->logits, t.total_logit, T->cfg.vocab_size, T->logits_ld, k, T->act->row_cand, st));
-    std::vector<BeamStepArgs> args;
+    ATS_TRY(decode_forward(T, t, fsm, k, st));
     for (int u = 0; u < n; ++u) {
       atspeed_decoder* d = decs[u];
-      BeamStepArgs a{};
-      a.src = d->round_beams[s[u].cur]; a.n_src = s[u].nb; a.gen_len = g;
-      a.logits = T->act->logits + (size_t)t.seg[u].logit_row0 * T->logits_ld; a.ld = T->logits_ld;
-      a.lse = T->act->lse + t.seg[u].logit_row0; a.fsm = fsm->dev; a.k = k;
-      a.dst = d->round_beams[s[u].cur ^ 1]; a.emit = 1; a.filter_ids = free_fsm ? 0 : 1;
-      a.row_cand = T->act->row_cand + (size_t)t.seg[u].logit_row0 * ATSPEED_MAX_BEAMS; a.n_row_cand = k;
-      a.in = d->tin[0]; a.in_row0 = s[u].row0 + s[u].n_in - s[u].nb;
-      a.out = d->tin[0]; a.out_row0 = s[u].row0 + s[u].n_in; a.out_slot0 = s[u].base + s[u].n_in; a.vis_words = W;
-      a.mail = d->mail_dev;
-      if (d->sample) { a.sample = 1; a.temperature = d->temperature; a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, g, 0, 0); }
-      args.push_back(a);
+      BeamStepArgs& a = args[u];
+      a = beam_step_args(d, T, t.seg[u], fsm, d->round_beams[s[u].cur], d->round_beams[s[u].cur ^ 1], g, k);
+      beam_step_emit(a, d->tin[0], s[u].row0 + s[u].n_in - s[u].nb, s[u].row0 + s[u].n_in, s[u].base + s[u].n_in);
+      if (a.sample) a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, g, 0, 0);
       s[u].row0 += s[u].n_in; s[u].base += s[u].n_in; s[u].n_in = k; s[u].nb = k; s[u].cur ^= 1;
     }
-    const BeamStepArgs* dev_args = nullptr;
-    ATS_TRY(stage_args(args, &dev_args, st));
-    ATS_TRY(ats_beam_step_multi(dev_args, n, st));
+    if (n == 1) ATS_TRY(ats_beam_step(args[0], st));
+    else {
+      const BeamStepArgs* dev_args = nullptr;
+      ATS_TRY(stage_args(args, &dev_args, st));
+      ATS_TRY(ats_beam_step_multi(dev_args, n, st));
+    }
   }
-  { std::vector<ExportBeamsArgs> ex;
-    for (int u = 0; u < n; ++u) ex.push_back(ExportBeamsArgs{decs[u]->round_beams[s[u].cur], out_tokens[u], out_scores[u], decs[u]->sample ? 1 : 0});
-    const ExportBeamsArgs* de = nullptr;
-    ATS_TRY(stage_args(ex, &de, st));
-    ATS_TRY(ats_export_beams_multi(de, n, k, max_new, st)); }
+  std::vector<ExportBeamsArgs> ex;
+  for (int u = 0; u < n; ++u) ex.push_back(ExportBeamsArgs{decs[u]->round_beams[s[u].cur], out_tokens[u], out_scores[u], decs[u]->sample ? 1 : 0});
+  ATS_TRY(export_beams(ex, k, max_new, st));
   hipEventRecord(g_ev[1], st);
   ATS_HIP(hipStreamSynchronize(st));
   ats_stage_reset();
   float ms = 0.f;
   hipEventElapsedTime(&ms, g_ev[0], g_ev[1]);
+  // a lock-step batch does not die with a user that lost every beam of a step to the id filter: that user ends with a blanked result block
+  // and its status, the others go on (as in the beam-SD batch loop); the one-user call returns the error
   bool any_filtered = false;
   for (int u = 0; u < n; ++u)
     if (n > 1 && decs[u]->mail_host->status == ATSPEED_ERR_FILTERED) { ATS_TRY(blank_outputs(out_tokens[u], out_scores[u], k, max_new, st)); any_filtered = true; }
   if (any_filtered) ATS_HIP(hipStreamSynchronize(st));
   for (int u = 0; u < n; ++u) {
-    const bool filtered = n > 1 && decs[u]->mail_host->status == ATSPEED_ERR_FILTERED;    // per user, as in the beam-SD batch loop
+    const bool filtered = n > 1 && decs[u]->mail_host->status == ATSPEED_ERR_FILTERED;
     if (!filtered) ATS_TRY(mailbox_status(decs[u]));
     if (stats) {
       atspeed_gen_stats gs;
@@ -1419,6 +1390,27 @@ extern "C" int atspeed_target_generate_batch(atspeed_decoder** decs, int32_t n, 
     }
   }
   return ATSPEED_OK;
+}
+
+extern "C" int atspeed_target_generate_batch(atspeed_decoder** decs, int32_t n, const int32_t* const* prompts,
+                                             const int32_t* prompt_lens, const atspeed_fsm* fsm, const int32_t* start_nodes,
+                                             int32_t max_new, int32_t k, int32_t* const* out_tokens, float* const* out_scores,
+                                             atspeed_gen_stats* stats, void* stream) {
+  ATS_REQUIRE(decs && prompts && prompt_lens && start_nodes && out_tokens && out_scores, ATSPEED_ERR_INVALID, "target_generate_batch: null argument");
+  ATS_REQUIRE(n >= 1 && n <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "target_generate_batch: %d users per call (max %d)", n, ATS_MAX_SEGS);
+  for (int u = 0; u < n; ++u) {
+    ATS_REQUIRE(decs[u] && decs[u]->target == decs[0]->target, ATSPEED_ERR_INVALID, "target_generate_batch: decoders must share one target model");
+    for (int j = 0; j < u; ++j) ATS_REQUIRE(decs[u] != decs[j], ATSPEED_ERR_INVALID, "target_generate_batch: decoder %d used twice", u);
+    ATS_TRY(target_check(decs[u], prompts[u], prompt_lens[u], fsm, start_nodes[u], max_new, k, out_tokens[u], out_scores[u]));
+  }
+  return target_group_run(decs, n, prompts, prompt_lens, fsm, start_nodes, max_new, k, out_tokens, out_scores, stats, (hipStream_t)stream);
+}
+
+extern "C" int atspeed_target_generate(atspeed_decoder* d, const int32_t* prompt, int32_t P, const atspeed_fsm* fsm,
+                                       int32_t start_node, int32_t max_new, int32_t k, int32_t* out_tokens,
+                                       float* out_scores, atspeed_gen_stats* stats, void* stream) {
+  ATS_TRY(target_check(d, prompt, P, fsm, start_node, max_new, k, out_tokens, out_scores));
+  return target_group_run(&d, 1, &prompt, &P, fsm, &start_node, max_new, k, &out_tokens, &out_scores, stats, (hipStream_t)stream);
 }
 
 extern "C" int atspeed_decoder_trace(atspeed_decoder* d, int32_t* rounds_out, int32_t cap) {

@@ -59,14 +59,19 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
   ATS_TRY(ats_embed_segs(m->embed, t, dtab, cx->h, H, c.vocab_size, dt, st));
   // fp8 projections fed by an RMSNorm take their e4m3 rows + scales straight from the norm kernel (no quantisation pass, no bf16 xn)
   const bool f4 = !m->fp4.empty();                         // the 4-bit target: layer_fp4 above
-  const bool f8_qkv = f4 ? H <= 8192 : !m->fp8.empty() && H <= 8192 && ats_gemm_fp8_applies(T, 3 * H, H, 3 * H, EPI_STORE);
-  const bool f8_gu = !m->fp8.empty() && H <= 8192 && ats_gemm_fp8_applies(T, 2 * c.ffn, H, c.ffn, EPI_SWIGLU);
+  // which projections of the 8-bit target run as W8A8 GEMMs in this forward (the rule depends on the token count alone, not on the layer)
+  const bool f8 = !m->fp8.empty();
+  const bool qkv_in_fp8 = f8 && ats_gemm_fp8_applies(T, 3 * H, H, 3 * H, EPI_STORE);
+  const bool o_in_fp8 = f8 && ats_gemm_fp8_applies(T, H, H, H, EPI_RESID);
+  const bool gu_in_fp8 = f8 && ats_gemm_fp8_applies(T, 2 * c.ffn, H, c.ffn, EPI_SWIGLU);
+  const bool down_in_fp8 = f8 && ats_gemm_fp8_applies(T, H, c.ffn, H, EPI_RESID);
+  const bool f8_qkv = f4 ? H <= 8192 : qkv_in_fp8 && H <= 8192;
+  const bool f8_gu = gu_in_fp8 && H <= 8192;
   bool xq_ready = false;
   if (f8_qkv) { ATS_TRY(ats_rmsnorm_quant_fp8(cx->h, m->layers[0].input_norm, nullptr, cx->xq, cx->sx, T, H, c.rms_eps, st, pk)); xq_ready = true; }
   else ATS_TRY(ats_rmsnorm(cx->h, m->layers[0].input_norm, cx->xn, T, H, c.rms_eps, dt, st, pk));
   // RoPE and the KV scatter ride in the qkv projection's epilogue (one pass over qkv / one launch less per layer): the ring kernels of the batched
   // 16-bit and W8A8 forwards, and since round 6 ONE user's W8A8 projection on the weight-streaming kernel (gemm_wdma_kernel<..., EPI_QKV_ROPE, F8>)
-  const bool qkv_in_fp8 = !m->fp8.empty() && ats_gemm_fp8_applies(T, 3 * H, H, 3 * H, EPI_STORE);
   const bool qkv_rope_fused = f4 ? false : qkv_in_fp8 ? ats_gemm_fp8_qkv_rope_applies(T, H, m->head_dim) : ats_gemm_qkv_rope_applies(T, H, m->head_dim, dt);
   if (qkv_rope_fused) ATS_TRY(ats_row_info(t, dtab, cx->rowinfo, c.max_slots, st));
   for (int l = 0; l < c.n_layers; ++l) {
@@ -74,7 +79,6 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
     const size_t loff = (size_t)l * m->layer_kv_bytes;
     if (f4) { ATS_TRY(layer_fp4(m, l, t, dtab, loff, xq_ready, st)); continue; }
     // cx->xn holds rmsnorm(h) * input_norm here (from the embed above or the previous layer's fused down_proj epilogue)
-    const bool f8 = !m->fp8.empty();
     const bool fuse_qkv_reduce = ats_switch(ATS_SW_FUSE_QKV_REDUCE) != 0;
     int qkv_splits = 0;
     { ProfBracket pb(m, 0, T, st);
@@ -109,7 +113,7 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
       ATS_TRY(ats_rope_kv_segs(cx->qkv, t, dtab, m->cos_tab, m->sin_tab, loff, c.n_heads, m->head_dim, c.max_slots, dt, st));
     ATS_TRY(ats_tree_attention_segs(cx->qkv, 3 * H, t, dtab, loff, m->vis_words, cx->att, H, c.n_heads, m->head_dim, dt, st, 0, pk));
     { ProfBracket pb(m, 1, T, st);     // h += att Wo^T ; xn = rmsnorm(h) * post_norm
-      if (f8 && ats_gemm_fp8_applies(T, H, H, H, EPI_RESID)) {
+      if (o_in_fp8) {
         m->fp8_cnt[1]++;
         ATS_TRY(ats_quant_rows_fp8(cx->att, T, H, H, cx->xq, cx->sx, st, pk));
         ATS_TRY(ats_gemm_fp8_resid_norm(cx->xq, cx->sx, m->fp8[l].wo, m->fp8[l].so, cx->h, T, H, H, H, w.post_norm, f8_gu ? nullptr : cx->xn,
@@ -121,7 +125,7 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
         xq_ready = false;
       } }
     { ProfBracket pb(m, 2, T, st);
-      if (f8 && ats_gemm_fp8_applies(T, 2 * c.ffn, H, c.ffn, EPI_SWIGLU)) {
+      if (gu_in_fp8) {
         m->fp8_cnt[2]++;
         ATS_TRY(proj_fp8(m, xq_ready ? nullptr : cx->xn, m->fp8[l].wgu, m->fp8[l].sgu, cx->act, T, 2 * c.ffn, H, c.ffn, EPI_SWIGLU, st));
       } else {
@@ -129,9 +133,8 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
         ATS_TRY(ats_gemm(cx->xn, w.wgu, cx->act, T, 2 * c.ffn, H, H, c.ffn, dt, EPI_SWIGLU, cx->ws, cx->ws_bytes, st, pk, sk));
       } }
     { ProfBracket pb(m, 3, T, st);     // h += act Wd^T ; xn = rmsnorm(h) * next layer's input_norm
-      m->fp8_cnt[3] += (f8 && ats_gemm_fp8_applies(T, H, c.ffn, H, EPI_RESID)) ? 1 : 0;
-      m->other_cnt[3] += (f8 && ats_gemm_fp8_applies(T, H, c.ffn, H, EPI_RESID)) ? 0 : 1;
-      if (f8 && ats_gemm_fp8_applies(T, H, c.ffn, H, EPI_RESID)) {
+      (down_in_fp8 ? m->fp8_cnt : m->other_cnt)[3]++;
+      if (down_in_fp8) {
         if (l + 1 < c.n_layers) {
           ATS_TRY(ats_quant_rows_fp8(cx->act, T, c.ffn, c.ffn, cx->xq, cx->sx, st, pk));
           ATS_TRY(ats_gemm_fp8_resid_norm(cx->xq, cx->sx, m->fp8[l].wd, m->fp8[l].sd, cx->h, T, H, c.ffn, H, m->layers[l + 1].input_norm,

@@ -152,7 +152,6 @@ struct VerifyArgs {
   // (score bits, parent = index into blk[i], token; flat < 0 picks have token -1); NULL = off
   int32_t* vtrace;
 };
-int ats_verify_walk(const VerifyArgs& a, hipStream_t st);
 int ats_verify_walk_multi(const VerifyArgs* dev_args, int n, hipStream_t st);
 
 int ats_init_prompt(TokBuf tb, const int32_t* prompt, int prompt_len, int vis_words, BeamSet beams, int start_node,

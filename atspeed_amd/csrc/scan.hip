@@ -523,9 +523,6 @@ __device__ void beam_step_body(const BeamStepArgs& a) {
 __device__ void verify_walk_body(const VerifyArgs& a);
 
 __device__ void verify_sample_body(const VerifyArgs& a);
-__global__ __launch_bounds__(kScanThreads) void verify_walk_kernel(VerifyArgs a) {
-  if (a.sample) verify_sample_body(a); else verify_walk_body(a);
-}
 __global__ __launch_bounds__(kScanThreads) void verify_walk_multi_kernel(const VerifyArgs* __restrict__ args) {
   __shared__ VerifyArgs a;
   const int words = sizeof(VerifyArgs) / 4;
@@ -905,14 +902,6 @@ int ats_beam_step_multi(const BeamStepArgs* dev_args, int n, hipStream_t st) {
 int ats_verify_walk_multi(const VerifyArgs* dev_args, int n, hipStream_t st) {
   if (n <= 0) return ATSPEED_OK;
   verify_walk_multi_kernel<<<n, kScanThreads, 0, st>>>(dev_args);
-  ATS_LAUNCH_CHECK();
-  return ATSPEED_OK;
-}
-
-int ats_verify_walk(const VerifyArgs& a, hipStream_t st) {
-  ATS_REQUIRE(a.k >= 1 && a.k <= MAXB && a.dk >= a.k && a.dk <= MAXB && a.dl >= 1 && a.dl <= ATSPEED_MAX_GAMMA,
-              ATSPEED_ERR_CAPACITY, "verify: k=%d dk=%d dl=%d out of range", a.k, a.dk, a.dl);
-  verify_walk_kernel<<<1, kScanThreads, 0, st>>>(a);
   ATS_LAUNCH_CHECK();
   return ATSPEED_OK;
 }
