@@ -145,10 +145,44 @@ def check(status: int) -> None:
     raise AtSpeedError(status, msg)
 
 
+class Handle:
+    """Owner of one library object: its `c_void_p` (`ptr`) and the name of the function that destroys it.  `close()`, leaving a `with` block
+    and collection all destroy it, at most once between them; at interpreter shutdown, when the library may be gone already, errors are
+    swallowed."""
+
+    def __init__(self, destroy: str):
+        self.ptr, self._destroy = C.c_void_p(), destroy
+
+    @classmethod
+    def create(cls, destroy: str, create_fn, *args) -> "Handle":
+        """`create_fn(*args, &ptr)`: every create function of the library takes its out pointer last."""
+        h = cls(destroy)
+        check(create_fn(*args, C.byref(h.ptr)))
+        return h
+
+    def close(self) -> None:
+        ptr, self.ptr = self.ptr, None
+        if ptr:
+            try:
+                getattr(load(), self._destroy)(ptr)
+            except Exception:
+                pass
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class switches:
     """`with _lib.switches(gemm_sk=2, gemm_panel=0): ...` -- set process-wide library switches (atspeed_set_switch) and restore them on exit.
     The environment variables (ATSPEED_GEMM_SK, ...) only give the INITIAL values, read once by the library; tests and sweeps that compare
-    two settings in one process go through here."""
+    two settings in one process go through here.  Every name is read before any is set, so an unknown name changes nothing."""
 
     def __init__(self, **values: int):
         self.values = values
@@ -156,17 +190,23 @@ class switches:
 
     def __enter__(self):
         lib = load()
-        for name, v in self.values.items():
-            cur = _I(0)
+        cur = _I(0)
+        for name in self.values:
             check(lib.atspeed_get_switch(name.encode(), C.byref(cur)))
             self.old[name] = cur.value
-            check(lib.atspeed_set_switch(name.encode(), int(v)))
+        try:
+            for name, v in self.values.items():
+                check(lib.atspeed_set_switch(name.encode(), int(v)))
+        except Exception:
+            self.__exit__()
+            raise
         return self
 
     def __exit__(self, *exc):
         lib = load()
-        for name, v in self.old.items():
-            lib.atspeed_set_switch(name.encode(), v)
+        failed = [st for st in [lib.atspeed_set_switch(name.encode(), v) for name, v in self.old.items()] if st != 0]
+        if failed:                  # every name has been tried by now: a failure leaves no other switch unrestored
+            check(failed[0])
         return False
 
 

@@ -21,14 +21,22 @@ beam per step, all arithmetic still in HIP).  `generation_config.do_sample` sele
 No mask at all (`prefix_allowed_tokens_fn=None`, legal in the reference: beamSD.py:460-481) runs on the device too: every token is a
 candidate, the id filter of :80-86 is off as in the reference.  Extra `logits_processor` entries (the reference always passes None,
 inference.py:175-176) are torch callables and are served by the host path: each step's log-softmax rows go through them between the
-library's forward and its expand + top-K.  Sampling with a host-side mask or processors (round 4) draws on the host from the device's
+library's forward and its expand + top-K.  Sampling with a host-side mask or processors draws on the host from the device's
 counter-based streams (hostmask.py): a callable wrapping a compilable constraint samples exactly what the device path samples for that seed.
+
+The four entry points (BSSD, BSSD_batch, target_generate, target_generate_batch) share their scaffolding: `_mode` (models checked, sampling
+mode), `_setup` (prompts on the device, compiled constraints, the shared `_DeviceFSM`, one `_Decoder` per user, sampling and trace set),
+`_host_call` (dispatch to hostmask.py and result conversion), `_chunked` (lists above MAX_USERS_PER_CALL) and `_one_user_call` /
+`_batch_call` (buffers, argument marshalling and the library call: the one-user entry points keep their by-value launches, the batch ones
+take one pointer array entry per user).  `_DeviceFSM` and `_Decoder` cache device objects per constraint and per (model pair, lane) and
+hold what they were built from weakly; the objects themselves are owned by `_lib.Handle`.
 """
 from __future__ import annotations
 
 import ctypes as C
 import time
 import weakref
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import numpy as np
@@ -76,41 +84,38 @@ class Timer:
 
 # ---------------------------------------------------------------- device handles (cached)
 class _DeviceFSM:
-    """Device copy of a ConstraintFSM's CSR arrays (shared by every prompt; only the start node differs)."""
-    _cache: Dict[int, "_DeviceFSM"] = {}
+    """Device copy of a ConstraintFSM's CSR arrays (shared by every prompt; only the start node differs).  The library copies the arrays, so
+    the cache refers to them WEAKLY: an entry goes when the `row_ptr` array it was built from is collected, i.e. with the last constraint
+    object that holds the automaton.  The mask-free constraint is one object that lives as long as the process."""
+    _cache: Dict[tuple, "_DeviceFSM"] = {}
 
     def __init__(self, fsm: ConstraintFSM, vocab_size: int):
         lib = _lib.load()
-        self.arrays = (np.ascontiguousarray(fsm.row_ptr, np.int32), np.ascontiguousarray(fsm.tok, np.int32),
-                       np.ascontiguousarray(fsm.nxt, np.int32))
-        h = C.c_void_p()
         if fsm.free:
-            _lib.check(lib.atspeed_fsm_create_free(vocab_size, C.byref(h)))
+            self._owner = _lib.Handle.create("atspeed_fsm_destroy", lib.atspeed_fsm_create_free, vocab_size)
         else:
-            _lib.check(lib.atspeed_fsm_create(self.arrays[0].ctypes.data, self.arrays[1].ctypes.data, self.arrays[2].ctypes.data,
-                                              fsm.n_nodes, len(self.arrays[1]), vocab_size, C.byref(h)))
-        if fsm.id_filter is not None and not fsm.free:
-            _lib.check(lib.atspeed_fsm_set_id_filter(h, int(fsm.id_filter[0]), int(fsm.id_filter[1])))
-        self.handle = h
-        self.src = fsm.row_ptr       # keeps id() stable while cached
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
-            try:
-                _lib.load().atspeed_fsm_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
+            row_ptr, tok, nxt = (np.ascontiguousarray(a, np.int32) for a in (fsm.row_ptr, fsm.tok, fsm.nxt))
+            self._owner = _lib.Handle.create("atspeed_fsm_destroy", lib.atspeed_fsm_create, row_ptr.ctypes.data, tok.ctypes.data,
+                                             nxt.ctypes.data, fsm.n_nodes, len(tok), vocab_size)
+            if fsm.id_filter is not None:
+                _lib.check(lib.atspeed_fsm_set_id_filter(self._owner.ptr, int(fsm.id_filter[0]), int(fsm.id_filter[1])))
+        self.handle = self._owner.ptr
+        self.src = weakref.ref(fsm.row_ptr)      # an id() can be reused once its array is gone: `get` checks the identity
 
     @classmethod
     def get(cls, fsm: ConstraintFSM, vocab_size: int) -> "_DeviceFSM":
         key = (id(fsm.row_ptr), id(fsm.tok), vocab_size, fsm.id_filter)
         d = cls._cache.get(key)
-        if d is None or d.src is not fsm.row_ptr:
-            d = cls(fsm, vocab_size)
-            cls._cache[key] = d
+        if d is None or d.src() is not fsm.row_ptr:
+            d = cls._cache[key] = cls(fsm, vocab_size)
+            weakref.finalize(fsm.row_ptr, cls._evict, key, d.src)
         return d
+
+    @classmethod
+    def _evict(cls, key: tuple, src) -> None:
+        """weakref.finalize callback: the array behind `src` is gone, so is the entry built from it (not a later one under a reused id)"""
+        if key in cls._cache and cls._cache[key].src is src:
+            del cls._cache[key]
 
 
 class _Decoder:
@@ -121,38 +126,40 @@ class _Decoder:
     _watched: set = set()
 
     def __init__(self, target: HipLlama, draft: Optional[HipLlama], max_prompt: int):
-        lib = _lib.load()
-        h = C.c_void_p()
         with torch.cuda.device(target.device):
-            _lib.check(lib.atspeed_decoder_create(target._handle, draft._handle if draft is not None else None,
-                                                  max_prompt, C.byref(h)))
-        self.handle, self.max_prompt = h, max_prompt
+            self._owner = _lib.Handle.create("atspeed_decoder_destroy", _lib.load().atspeed_decoder_create, target._handle,
+                                             draft._handle if draft is not None else None, max_prompt)
+        self.handle, self.max_prompt = self._owner.ptr, max_prompt
         self.models = (weakref.ref(target), weakref.ref(draft) if draft is not None else None)
         for m in (target, draft):
             if m is not None and id(m) not in _Decoder._watched:
                 _Decoder._watched.add(id(m))
                 weakref.finalize(m, _evict_model, id(m))
 
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
-            try:
-                _lib.load().atspeed_decoder_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
-
     def serves(self, target, draft) -> bool:
         return self.models[0]() is target and (self.models[1]() if self.models[1] is not None else None) is draft
+
+    @staticmethod
+    def _key(target, draft, lane: int) -> tuple:
+        return id(target), id(draft) if draft is not None else None, lane
 
     @classmethod
     def get(cls, target: HipLlama, draft: Optional[HipLlama], prompt_len: int, lane: int = 0) -> "_Decoder":
         """One decoder (= one user stream: private KV + activations) per (model pair, lane)."""
-        key = (id(target), id(draft) if draft is not None else None, lane)
+        key = cls._key(target, draft, lane)
         d = cls._cache.get(key)
         if d is None or d.max_prompt < prompt_len or not d.serves(target, draft):
             d = cls(target, draft, max(prompt_len, min(target.max_tokens, 512)))
             cls._cache[key] = d
+        return d
+
+    @classmethod
+    def cached(cls, target: HipLlama, draft: Optional[HipLlama], lane: int = 0) -> "_Decoder":
+        """The decoder an earlier call left for this (model pair, lane): what `last_trace` / `last_decisions` read."""
+        d = cls._cache.get(cls._key(target, draft, lane))
+        if d is None or not d.serves(target, draft):
+            raise KeyError(f"no decoder of this model pair for lane {lane}: call BSSD (lane 0) or BSSD_batch with more than {lane} users "
+                           "on these models first (and not release_decoders after it)")
         return d
 
 
@@ -173,6 +180,7 @@ def release_decoders(*models) -> int:
     return len(keys)
 
 
+# ---------------------------------------------------------------- what every entry point does around its library call
 def _compile_constraint(fn, prompt):
     if fn is None:               # no mask: every token is a candidate (beamSD.py:469-478 builds an empty processor list)
         return free_constraint()
@@ -198,18 +206,15 @@ def _prompt_lists(prompts):
     return out
 
 
-def _check_models(*models):
+def _mode(seed, *models):
+    """The models checked, then (do_sample, temperature, seed) of the call.  The reference samples when
+    `target_model.generation_config.do_sample` is set (beamSD.py:479-481) with its temperature warper; draws there come from torch's global
+    generator, here from a counter-based stream whose 32-bit seed is drawn from that generator (so `torch.manual_seed` makes a call
+    repeatable) unless `seed` is given."""
     for m in models:
         if not isinstance(m, HipLlama):
             raise TypeError("models must be atspeed_amd.HipLlama (use HipLlama.from_hf(model) for an HF module)")
-
-
-def _sampling(model, seed):
-    """(do_sample, temperature, seed) of a call.  The reference samples when `target_model.generation_config.do_sample`
-    is set (beamSD.py:479-481) with its temperature warper; draws there come from torch's global generator, here from a
-    counter-based stream whose 32-bit seed is drawn from that generator (so `torch.manual_seed` makes a call repeatable)
-    unless `seed` is given."""
-    gc = model.generation_config
+    gc = models[0].generation_config
     if not getattr(gc, "do_sample", False):
         return False, 1.0, 0
     if seed is None:
@@ -218,26 +223,66 @@ def _sampling(model, seed):
     return True, 1.0 if temp is None else float(temp), int(seed) & 0xFFFFFFFF
 
 
-def _set_sampling(decs, mode, per_user: bool = True):
-    do, temp, seed = mode
-    lib = _lib.load()
-    for u, d in enumerate(decs):
-        _lib.check(lib.atspeed_decoder_set_sampling(d.handle, 1 if do else 0, temp, (seed + (u if per_user else 0)) & 0xFFFFFFFF))
-
-
-def _set_trace(decs, on: bool):
-    lib = _lib.load()
-    for d in decs:
-        if getattr(d, "trace_on", False) != bool(on):
-            _lib.check(lib.atspeed_decoder_set_trace(d.handle, 1 if on else 0))
-            d.trace_on = bool(on)
-
-
 def _prompt_row(inputs) -> torch.Tensor:
     ids = inputs["input_ids"]
     if ids.dim() == 2:
         ids = ids[0]            # the reference reads batch row 0 only (beamSD.py:57,203,224)
     return ids
+
+
+def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allowed_tokens_fn, mode, who: str, trace=None) -> SimpleNamespace:
+    """The device path's call setup, for one user or a lock-step batch: prompts on the device, each user's compiled constraint (the mask
+    functions look at the prompt -- position of "Response:", data.py:97-102 -- with one D2H copy per call, where the reference does one per beam
+    per step, generation_trie.py:94, data.py:98), the ONE automaton they share (they may differ in their start node only), one decoder per
+    user (lane), set to the call's sampling mode (user u draws from stream seed + u) and, for BSSD (`trace` not None), its decision trace."""
+    lib = _lib.load()
+    dev = target.device
+    prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
+    fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
+    for f in fsms[1:]:
+        if f.row_ptr is not fsms[0].row_ptr:
+            raise ValueError(f"{who} needs one shared constraint automaton (only the start node may differ per user)")
+    dfsm = _DeviceFSM.get(fsms[0], target.dims.vocab_size)
+    decs = [_Decoder.get(target, draft, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
+    do, temp, seed = mode
+    for u, d in enumerate(decs):
+        _lib.check(lib.atspeed_decoder_set_sampling(d.handle, 1 if do else 0, temp, (seed + u) & 0xFFFFFFFF))
+    if trace is not None:
+        for d in decs:
+            if getattr(d, "trace_on", False) != bool(trace):
+                _lib.check(lib.atspeed_decoder_set_trace(d.handle, 1 if trace else 0))
+                d.trace_on = bool(trace)
+    return SimpleNamespace(dev=dev, prompts=prompts, fsms=fsms, dfsm=dfsm, decs=decs)
+
+
+def _host_call(host_fn, models, inputs: Dict, args, logits_processor, prefix_allowed_tokens_fn, mode) -> Dict:
+    """Arbitrary Python callables (a mask closure, extra logits processors) are served like the reference does, one host call per beam per
+    step: `host_fn(*models, prompt, *args, fn, processors, sample)` of hostmask.py, its arrays back on the device.  With do_sample the draws happen
+    on the host, from the device's streams.  BSSD's statistics keys come with the result (stage times are wall clock with a device
+    synchronisation, like the reference's Timer)."""
+    if mode[0] and mode[1] <= 0.0:
+        raise ValueError("sampling needs a temperature > 0")
+    dev = models[0].device
+    prompt = _prompt_row(inputs).to(dev).cpu().numpy().astype(np.int64)
+    r = host_fn(*models, prompt, *args, prefix_allowed_tokens_fn, list(logits_processor or ()),
+                sample=mode[1:] if mode[0] else None)
+    return dict(r, beam_sequence=torch.from_numpy(r["beam_sequence"]).to(dev), beam_scores=torch.from_numpy(r["beam_scores"]).to(dev),
+                n_valid=int(len(r["beam_scores"])))
+
+
+def _one_user_call(entry, c: SimpleNamespace, k: int, max_new_tokens: int, *middle):
+    """`entry(decoder, prompt, P, automaton, start node, *middle, tokens, scores, &stats, stream)`, the by-value launches of one user
+    -> (result with `beam_sequence` [k, P + L] int64 = prompt ++ suffix per beam, stats)"""
+    prompt, dev = c.prompts[0], c.dev
+    with torch.cuda.device(dev):
+        ids32 = prompt.to(torch.int32).contiguous()
+        toks = torch.empty(k, max_new_tokens, dtype=torch.int32, device=dev)
+        scores = torch.empty(k, dtype=torch.float32, device=dev)
+        stats = _lib.GenStats()
+        _lib.check(entry(c.decs[0].handle, ids32.data_ptr(), int(prompt.numel()), c.dfsm.handle, c.fsms[0].start, *middle,
+                         toks.data_ptr(), scores.data_ptr(), C.byref(stats), _lib.stream_ptr(dev)))
+    seq = torch.cat((prompt.to(torch.int64)[None, :].repeat(k, 1), toks.to(torch.int64)), dim=1)
+    return {"beam_sequence": seq, "beam_scores": scores}, stats
 
 
 def _batch_buffers(prompts, k: int, max_new_tokens: int, dev):
@@ -272,9 +317,30 @@ def _batch_results(keep, toks: torch.Tensor, scores: torch.Tensor, k: int):
     return res
 
 
-def _result(prompt: torch.Tensor, toks: torch.Tensor, scores: torch.Tensor, k: int) -> Dict:
-    seq = torch.cat((prompt.to(torch.int64)[None, :].repeat(k, 1), toks.to(torch.int64)), dim=1)
-    return {"beam_sequence": seq, "beam_scores": scores}
+def _batch_call(entry, c: SimpleNamespace, k: int, max_new_tokens: int, *middle):
+    """`entry(decoders, n, prompts, lengths, automaton, start nodes, *middle, tokens, scores, stats, stream)` with one pointer / int32 array
+    entry per user -> (what `_batch_results` needs, stats[n]); the caller stops its clock when this returns"""
+    n = len(c.prompts)
+    ptrs, ints = C.c_void_p * n, C.c_int32 * n
+    with torch.cuda.device(c.dev):
+        ids32, toks, scores, keep = _batch_buffers(c.prompts, k, max_new_tokens, c.dev)
+        stats = (_lib.GenStats * n)()
+        _lib.check(entry(ptrs(*[d.handle for d in c.decs]), n, ptrs(*[t.data_ptr() for t in ids32]),
+                         ints(*[int(p.numel()) for p in c.prompts]), c.dfsm.handle, ints(*[f.start for f in c.fsms]), *middle,
+                         ptrs(*[t.data_ptr() for t in toks]), ptrs(*[t.data_ptr() for t in scores]), stats, _lib.stream_ptr(c.dev)))
+    return (keep, toks, scores, k), stats
+
+
+MAX_USERS_PER_CALL = 256
+
+
+def _chunked(call, inputs_list, mode):
+    """The library batches up to MAX_USERS_PER_CALL users per forward; a longer list goes chunk by chunk through `call(chunk, seed)`, user u
+    of the list still drawing from stream seed + u."""
+    outs = []
+    for i in range(0, len(inputs_list), MAX_USERS_PER_CALL):
+        outs += call(inputs_list[i:i + MAX_USERS_PER_CALL], (mode[2] + i) if mode[0] else None)
+    return outs
 
 
 def _bssd_stats(st, k: int) -> Dict:
@@ -297,65 +363,25 @@ def _bssd_stats(st, k: int) -> Dict:
     }
 
 
-def _shared_fsm(fsms, who: str):
-    """The one automaton of a lock-step batch: the users' constraints may differ in their start node only."""
-    for f in fsms[1:]:
-        if f.row_ptr is not fsms[0].row_ptr:
-            raise ValueError(f"{who} needs one shared constraint automaton (only the start node may differ per user)")
-    return fsms[0]
-
-
+# ---------------------------------------------------------------- entry points
 @Timer()
 @torch.no_grad()
 def BSSD(target_model, draft_model, inputs: Dict, gamma: int, max_new_tokens: int,
          logits_processor=None, prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False) -> Dict:
-    _check_models(target_model, draft_model)
-    mode = _sampling(target_model, seed)
-    lib = _lib.load()
-    dev = target_model.device
-    prompt = _prompt_row(inputs).to(dev)
-    P = int(prompt.numel())
+    mode = _mode(seed, target_model, draft_model)
+    if _host_path(logits_processor, prefix_allowed_tokens_fn):
+        from .hostmask import bssd_host_mask
+        return _host_call(bssd_host_mask, (target_model, draft_model), inputs, (int(gamma), int(max_new_tokens)), logits_processor,
+                          prefix_allowed_tokens_fn, mode)
     k = int(target_model.generation_config.num_beams)                 # beamSD.py:482
     dk = int(draft_model.generation_config.num_beams)                 # beamSD.py:483
-    if _host_path(logits_processor, prefix_allowed_tokens_fn):
-        # arbitrary Python callables (a mask closure, extra logits processors): served like the reference does, one host call per
-        # beam per step (hostmask.py); stage times are wall clock with a device sync, like the reference's Timer
-        from .hostmask import bssd_host_mask, bssd_host_mask_sample
-        if mode[0]:                                   # do_sample with a host-side mask / processors: the draws happen on the host, from the device's streams
-            if mode[1] <= 0.0:
-                raise ValueError("sampling needs a temperature > 0")
-            r = bssd_host_mask_sample(target_model, draft_model, prompt.cpu().numpy().astype(np.int64), int(gamma), int(max_new_tokens),
-                                      prefix_allowed_tokens_fn, list(logits_processor or ()), mode[1], mode[2])
-        else:
-            r = bssd_host_mask(target_model, draft_model, prompt.cpu().numpy().astype(np.int64), int(gamma), int(max_new_tokens),
-                               prefix_allowed_tokens_fn, list(logits_processor or ()))
-        out = {"beam_sequence": torch.from_numpy(r["beam_sequence"]).to(dev), "beam_scores": torch.from_numpy(r["beam_scores"]).to(dev)}
-        out.update({kk: r[kk] for kk in ("n_run", "total_accept_steps", "total_accept_tokens", "ave_accept_tokens", "accept_steps",
-                                         "draft_time_cost", "target_time_cost", "verify_time_cost")})
-        out["n_valid"] = int(len(r["beam_scores"]))
-        return out
-    # the mask functions look at the prompt (position of "Response:", data.py:97-102): one D2H copy per
-    # user, where the reference does one per beam per step (generation_trie.py:94, data.py:98)
-    fsm = _compile_constraint(prefix_allowed_tokens_fn, prompt.tolist())
-    dfsm = _DeviceFSM.get(fsm, target_model.dims.vocab_size)
-    dec = _Decoder.get(target_model, draft_model, P)
-    _set_sampling([dec], mode)
-    _set_trace([dec], trace_decisions)
-    with torch.cuda.device(dev):
-        ids32 = prompt.to(torch.int32).contiguous()
-        toks = torch.empty(k, max_new_tokens, dtype=torch.int32, device=dev)
-        scores = torch.empty(k, dtype=torch.float32, device=dev)
-        stats = _lib.GenStats()
-        _lib.check(lib.atspeed_bssd_generate(dec.handle, ids32.data_ptr(), P, dfsm.handle, fsm.start, int(gamma),
-                                             int(max_new_tokens), k, dk, toks.data_ptr(), scores.data_ptr(),
-                                             C.byref(stats), _lib.stream_ptr(dev)))
-    out = _result(prompt, toks, scores, k)
+    c = _setup(target_model, draft_model, [inputs], prefix_allowed_tokens_fn, mode, "BSSD", trace_decisions)
+    out, stats = _one_user_call(_lib.load().atspeed_bssd_generate, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     out.update(_bssd_stats(stats, k))
     return out
 
 
 beam_sd_generate = BSSD
-MAX_USERS_PER_CALL = 256
 
 
 @torch.no_grad()
@@ -368,43 +394,20 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
     verification of a round is ONE forward over the tokens of all users (`atspeed_bssd_generate_batch`), so the
     weights are streamed once per forward instead of once per user.  Token ids, n_matches and draft candidates
     are identical to calling BSSD() per user (scores agree to fp32 rounding: the GEMM tiling depends on the batch)."""
-    _check_models(target_model, draft_model)
-    mode = _sampling(target_model, seed)             # user u of the call draws from stream seed + u
-    if len(inputs_list) > MAX_USERS_PER_CALL:            # the library batches up to 256 users per forward
-        outs = []
-        for i in range(0, len(inputs_list), MAX_USERS_PER_CALL):
-            outs += BSSD_batch(target_model, draft_model, inputs_list[i:i + MAX_USERS_PER_CALL], gamma, max_new_tokens,
-                               prefix_allowed_tokens_fn, seed=(mode[2] + i) if mode[0] else None, trace_decisions=trace_decisions)
-        return outs
-    lib = _lib.load()
-    dev = target_model.device
-    n = len(inputs_list)
+    mode = _mode(seed, target_model, draft_model)
+    if len(inputs_list) > MAX_USERS_PER_CALL:
+        return _chunked(lambda chunk, s: BSSD_batch(target_model, draft_model, chunk, gamma, max_new_tokens, prefix_allowed_tokens_fn,
+                                                    seed=s, trace_decisions=trace_decisions), inputs_list, mode)
     k = int(target_model.generation_config.num_beams)
     dk = int(draft_model.generation_config.num_beams)
     t0 = time.time()
-    prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
-    fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
-    dfsm = _DeviceFSM.get(_shared_fsm(fsms, "BSSD_batch"), target_model.dims.vocab_size)
-    decs = [_Decoder.get(target_model, draft_model, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
-    _set_sampling(decs, mode)
-    _set_trace(decs, trace_decisions)
-    with torch.cuda.device(dev):
-        ids32, toks, scores, _keep = _batch_buffers(prompts, k, max_new_tokens, dev)
-        stats = (_lib.GenStats * n)()
-        arr_p = (C.c_void_p * n)
-        _lib.check(lib.atspeed_bssd_generate_batch(
-            arr_p(*[d.handle for d in decs]), n, arr_p(*[t.data_ptr() for t in ids32]),
-            (C.c_int32 * n)(*[int(p.numel()) for p in prompts]), dfsm.handle, (C.c_int32 * n)(*[f.start for f in fsms]),
-            int(gamma), int(max_new_tokens), k, dk, arr_p(*[t.data_ptr() for t in toks]),
-            arr_p(*[t.data_ptr() for t in scores]), stats, _lib.stream_ptr(dev)))
+    c = _setup(target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, mode, "BSSD_batch", trace_decisions)
+    raw, stats = _batch_call(_lib.load().atspeed_bssd_generate_batch, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     wall = time.time() - t0
-    outs = []
-    results = _batch_results(_keep, toks, scores, k)
-    for i in range(n):
-        out = results[i]
-        out.update(_bssd_stats(stats[i], k))
-        out.update({"time_cost": wall / n, "status": int(stats[i].status)})
-        outs.append(out)
+    outs = _batch_results(*raw)
+    for out, st in zip(outs, stats):
+        out.update(_bssd_stats(st, k))
+        out.update({"time_cost": wall / len(outs), "status": int(st.status)})
     return outs
 
 
@@ -412,38 +415,14 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
 @torch.no_grad()
 def target_generate(model, inputs: Dict, max_new_tokens: int, logits_processor=None,
                     prefix_allowed_tokens_fn=None, seed=None) -> Dict:
-    _check_models(model)
-    mode = _sampling(model, seed)
-    lib = _lib.load()
-    dev = model.device
-    prompt = _prompt_row(inputs).to(dev)
-    P = int(prompt.numel())
-    k = int(model.generation_config.num_beams)                        # beamSD.py:553
+    mode = _mode(seed, model)
     if _host_path(logits_processor, prefix_allowed_tokens_fn):
-        from .hostmask import target_generate_host_mask, target_generate_host_mask_sample
-        if mode[0]:
-            if mode[1] <= 0.0:
-                raise ValueError("sampling needs a temperature > 0")
-            r = target_generate_host_mask_sample(model, prompt.cpu().numpy().astype(np.int64), int(max_new_tokens), prefix_allowed_tokens_fn,
-                                                 list(logits_processor or ()), mode[1], mode[2])
-        else:
-            r = target_generate_host_mask(model, prompt.cpu().numpy().astype(np.int64), int(max_new_tokens), prefix_allowed_tokens_fn,
-                                          list(logits_processor or ()))
-        return {"beam_sequence": torch.from_numpy(r["beam_sequence"]).to(dev), "beam_scores": torch.from_numpy(r["beam_scores"]).to(dev),
-                "n_valid": int(len(r["beam_scores"]))}
-    fsm = _compile_constraint(prefix_allowed_tokens_fn, prompt.tolist())
-    dfsm = _DeviceFSM.get(fsm, model.dims.vocab_size)
-    dec = _Decoder.get(model, None, P)
-    _set_sampling([dec], mode)
-    with torch.cuda.device(dev):
-        ids32 = prompt.to(torch.int32).contiguous()
-        toks = torch.empty(k, max_new_tokens, dtype=torch.int32, device=dev)
-        scores = torch.empty(k, dtype=torch.float32, device=dev)
-        stats = _lib.GenStats()
-        _lib.check(lib.atspeed_target_generate(dec.handle, ids32.data_ptr(), P, dfsm.handle, fsm.start,
-                                               int(max_new_tokens), k, toks.data_ptr(), scores.data_ptr(),
-                                               C.byref(stats), _lib.stream_ptr(dev)))
-    out = _result(prompt, toks, scores, k)
+        from .hostmask import target_generate_host_mask
+        return _host_call(target_generate_host_mask, (model,), inputs, (int(max_new_tokens),), logits_processor, prefix_allowed_tokens_fn,
+                          mode)
+    k = int(model.generation_config.num_beams)                        # beamSD.py:553
+    c = _setup(model, None, [inputs], prefix_allowed_tokens_fn, mode, "target_generate")
+    out, stats = _one_user_call(_lib.load().atspeed_target_generate, c, k, max_new_tokens, int(max_new_tokens), k)
     out.update({"n_valid": int(stats.n_valid), "device_time_cost": stats.total_ms * 1e-3})
     return out
 
@@ -452,41 +431,19 @@ def target_generate_batch(model, inputs_list, max_new_tokens: int, prefix_allowe
     """`target_generate` for several independent users in lock step (one result dict per user): position g of every
     user's constrained beam search is ONE forward.  This is the loop `code/generate_teacher_data.py:211-244` runs over
     a whole training set with HF `generate`; token ids equal per-user `target_generate` calls."""
-    _check_models(model)
-    mode = _sampling(model, seed)
+    mode = _mode(seed, model)
     if len(inputs_list) > MAX_USERS_PER_CALL:
-        outs = []
-        for i in range(0, len(inputs_list), MAX_USERS_PER_CALL):
-            outs += target_generate_batch(model, inputs_list[i:i + MAX_USERS_PER_CALL], max_new_tokens, prefix_allowed_tokens_fn,
-                                          seed=(mode[2] + i) if mode[0] else None)
-        return outs
-    lib = _lib.load()
-    dev = model.device
-    n = len(inputs_list)
+        return _chunked(lambda chunk, s: target_generate_batch(model, chunk, max_new_tokens, prefix_allowed_tokens_fn, seed=s),
+                        inputs_list, mode)
     k = int(model.generation_config.num_beams)
     t0 = time.time()
-    prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
-    fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
-    dfsm = _DeviceFSM.get(_shared_fsm(fsms, "target_generate_batch"), model.dims.vocab_size)
-    decs = [_Decoder.get(model, None, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
-    _set_sampling(decs, mode)
-    with torch.cuda.device(dev):
-        ids32, toks, scores, _keep = _batch_buffers(prompts, k, max_new_tokens, dev)
-        stats = (_lib.GenStats * n)()
-        arr_p = (C.c_void_p * n)
-        _lib.check(lib.atspeed_target_generate_batch(
-            arr_p(*[d.handle for d in decs]), n, arr_p(*[t.data_ptr() for t in ids32]),
-            (C.c_int32 * n)(*[int(p.numel()) for p in prompts]), dfsm.handle, (C.c_int32 * n)(*[f.start for f in fsms]),
-            int(max_new_tokens), k, arr_p(*[t.data_ptr() for t in toks]), arr_p(*[t.data_ptr() for t in scores]), stats,
-            _lib.stream_ptr(dev)))
+    c = _setup(model, None, inputs_list, prefix_allowed_tokens_fn, mode, "target_generate_batch")
+    raw, stats = _batch_call(_lib.load().atspeed_target_generate_batch, c, k, max_new_tokens, int(max_new_tokens), k)
     wall = time.time() - t0
-    outs = []
-    results = _batch_results(_keep, toks, scores, k)
-    for i in range(n):
-        out = results[i]
-        out.update({"n_valid": int(stats[i].n_valid), "status": int(stats[i].status), "device_time_cost": stats[i].total_ms * 1e-3,
-                    "time_cost": wall / n})
-        outs.append(out)
+    outs = _batch_results(*raw)
+    for out, st in zip(outs, stats):
+        out.update({"n_valid": int(st.n_valid), "status": int(st.status), "device_time_cost": st.total_ms * 1e-3,
+                    "time_cost": wall / len(outs)})
     return outs
 
 
@@ -494,7 +451,7 @@ def last_trace(target_model, draft_model):
     """Per-round trace of the last BSSD call on this model pair (parity tests):
     list of dict(draft_len, n_matches, n_beams, draft_ids=[draft_len][dk])."""
     lib = _lib.load()
-    dec = _Decoder._cache[(id(target_model), id(draft_model) if draft_model is not None else None, 0)]
+    dec = _Decoder.cached(target_model, draft_model)
     n = lib.atspeed_decoder_trace(dec.handle, None, 0)
     buf = (C.c_int32 * max(n, 1))()
     lib.atspeed_decoder_trace(dec.handle, buf, n)
@@ -515,7 +472,7 @@ def last_decisions(target_model, draft_model, lane: int = 0):
     every verify step (the decisions of beamSD.py:297-298,323-328) and n_matches; a final single step (beamSD.py:505-509) is a round
     of kind "final".  Sequences are the generated suffixes (lists of token ids), scores fp32."""
     lib = _lib.load()
-    dec = _Decoder._cache[(id(target_model), id(draft_model) if draft_model is not None else None, lane)]
+    dec = _Decoder.cached(target_model, draft_model, lane)
     n = int(lib.atspeed_decoder_decisions(dec.handle, None, 0))
     buf = np.zeros(max(n, 1), dtype=np.int32)
     lib.atspeed_decoder_decisions(dec.handle, buf.ctypes.data, n)

@@ -99,12 +99,10 @@ class HipLlama:
         for l, lw in enumerate(packed["layers"]):
             layers[l] = _lib.LlamaLayerWeights(lw["input_norm"].data_ptr(), lw["wqkv"].data_ptr(), lw["wo"].data_ptr(),
                                                lw["post_norm"].data_ptr(), lw["wgu"].data_ptr(), lw["wd"].data_ptr())
-        h = C.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(lib.atspeed_llama_create(C.byref(cfg), packed["embed"].data_ptr(), packed["final_norm"].data_ptr(),
-                                                packed["lm_head"].data_ptr(), layers, C.byref(h)))
-        self._handle = h
-        self.logits_ld = int(lib.atspeed_llama_logits_ld(h))
+            self._owner = _lib.Handle.create("atspeed_llama_destroy", lib.atspeed_llama_create, C.byref(cfg), packed["embed"].data_ptr(),
+                                             packed["final_norm"].data_ptr(), packed["lm_head"].data_ptr(), layers)
+        self.logits_ld = int(lib.atspeed_llama_logits_ld(self._handle))
 
     @staticmethod
     def _pack_rows(t: torch.Tensor) -> torch.Tensor:
@@ -129,17 +127,13 @@ class HipLlama:
     def device(self) -> torch.device:
         return self._device
 
+    @property
+    def _handle(self) -> C.c_void_p:
+        """the library's model object; `_owner` (a `_lib.Handle`) destroys it with this object"""
+        return self._owner.ptr
+
     def eval(self):
         return self
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h:
-            try:
-                _lib.load().atspeed_llama_destroy(h)
-            except Exception:
-                pass
-            self._handle = None
 
     # ---- construction --------------------------------------------------------------
     @staticmethod
@@ -260,37 +254,37 @@ class HipLlama:
             del sd
         return cls(dims, packed, dtype, device, **kw)
 
+    def _enable_quant(self, fmt: str) -> "HipLlama":
+        with torch.cuda.device(self._device):
+            _lib.check(getattr(_lib.load(), f"atspeed_llama_enable_{fmt}")(self._handle, _lib.stream_ptr(self._device)))
+        setattr(self, fmt, True)
+        return self
+
+    def _quant_counters(self, fmt: str, reset: bool) -> Dict[str, Dict[str, int]]:
+        quant = (C.c_int64 * 4)()
+        other = (C.c_int64 * 4)()
+        _lib.check(getattr(_lib.load(), f"atspeed_llama_{fmt}_counters")(self._handle, quant, other, 1 if reset else 0))
+        return {k: {fmt: int(quant[i]), "other": int(other[i])} for i, k in enumerate(self.GEMM_KINDS[:4])}
+
     def enable_fp8(self) -> "HipLlama":
         """fp8 (e4m3, W8A8 with per-row scales) layer projections (BASELINE config 5; the place of the reference's `load_in_8bit` target,
         code/inference.py:86-91).  bf16 and fp16 models: the e4m3 copies are made from the model's own 16-bit weight values, the activations
         between the W8A8 projections stay in the model's type (an fp16 checkpoint, the reference's, keeps the fp16 flavour)."""
-        with torch.cuda.device(self._device):
-            _lib.check(_lib.load().atspeed_llama_enable_fp8(self._handle, _lib.stream_ptr(self._device)))
-        self.fp8 = True
-        return self
+        return self._enable_quant("fp8")
 
     def fp8_counters(self, reset: bool = False) -> Dict[str, Dict[str, int]]:
         """Launches of each layer projection that ran as fp8 / as bf16 GEMMs since the last reset (atspeed_llama_fp8_counters)."""
-        f8 = (C.c_int64 * 4)()
-        other = (C.c_int64 * 4)()
-        _lib.check(_lib.load().atspeed_llama_fp8_counters(self._handle, f8, other, 1 if reset else 0))
-        return {k: dict(fp8=int(f8[i]), other=int(other[i])) for i, k in enumerate(self.GEMM_KINDS[:4])}
+        return self._quant_counters("fp8", reset)
 
     def enable_fp4(self) -> "HipLlama":
         """4-bit target: OCP MXFP4 layer projections (e2m1 weights with one E8M0 scale per 32 k of a row) against the W8A8 activations
         (per-token e4m3), on the block-scaled MFMA (atspeed_llama_enable_fp4).  bf16 and fp16 models; the copies are made from the model's
         own 16-bit weight values.  Exclusive with enable_fp8.  Opt-in: MXFP4 without rotation or outlier handling costs model quality."""
-        with torch.cuda.device(self._device):
-            _lib.check(_lib.load().atspeed_llama_enable_fp4(self._handle, _lib.stream_ptr(self._device)))
-        self.fp4 = True
-        return self
+        return self._enable_quant("fp4")
 
     def fp4_counters(self, reset: bool = False) -> Dict[str, Dict[str, int]]:
         """Launches of each layer projection that ran as W4A8 / as 16-bit GEMMs since the last reset (atspeed_llama_fp4_counters)."""
-        f4 = (C.c_int64 * 4)()
-        other = (C.c_int64 * 4)()
-        _lib.check(_lib.load().atspeed_llama_fp4_counters(self._handle, f4, other, 1 if reset else 0))
-        return {k: dict(fp4=int(f4[i]), other=int(other[i])) for i, k in enumerate(self.GEMM_KINDS[:4])}
+        return self._quant_counters("fp4", reset)
 
     def rope_fused_launches(self, reset: bool = False) -> int:
         """qkv projections that carried RoPE + the KV scatter in their epilogue since the last reset (atspeed_llama_rope_fused_launches)."""
@@ -303,21 +297,20 @@ class HipLlama:
     # ---- measurement hooks --------------------------------------------------------------
     GEMM_KINDS = ("qkv", "o_proj", "gate_up", "down", "lm_head")
 
-    def profile(self, enable: int = -1) -> Dict[str, Dict[str, float]]:
-        """hipEvent brackets around the forward's GEMMs (see atspeed_llama_profile)."""
+    def _profile(self, fn, *args) -> Dict[str, Dict[str, float]]:
         ms = (C.c_double * 5)()
         cnt = (C.c_int64 * 5)()
         rows = (C.c_int64 * 5)()
-        _lib.check(_lib.load().atspeed_llama_profile(self._handle, enable, ms, cnt, rows))
+        _lib.check(fn(self._handle, *args, ms, cnt, rows))
         return {k: dict(ms=ms[i], count=int(cnt[i]), rows=int(rows[i])) for i, k in enumerate(self.GEMM_KINDS)}
+
+    def profile(self, enable: int = -1) -> Dict[str, Dict[str, float]]:
+        """hipEvent brackets around the forward's GEMMs (see atspeed_llama_profile)."""
+        return self._profile(_lib.load().atspeed_llama_profile, enable)
 
     def profile_big(self) -> Dict[str, Dict[str, float]]:
         """The brackets of launches with >= 1024 tokens only (one kernel: the 256x256 ring GEMM); read before `profile(0)` resets."""
-        ms = (C.c_double * 5)()
-        cnt = (C.c_int64 * 5)()
-        rows = (C.c_int64 * 5)()
-        _lib.check(_lib.load().atspeed_llama_profile_big(self._handle, ms, cnt, rows))
-        return {k: dict(ms=ms[i], count=int(cnt[i]), rows=int(rows[i])) for i, k in enumerate(self.GEMM_KINDS)}
+        return self._profile(_lib.load().atspeed_llama_profile_big)
 
     def forward_log(self, enable: int = -1):
         """[(tokens, logit rows)] of the forwards run since the log was switched on (atspeed_llama_forward_log); enable as there."""
@@ -359,19 +352,24 @@ class HipLlama:
         return sd
 
     # ---- forward (tests / tools; the decoder calls the C entry point directly) --------
-    def forward_raw(self, ids: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, vis_bits: torch.Tensor,
-                    n_slots: int, n_logit_rows: int) -> torch.Tensor:
-        """ids/pos/slots int32 [T]; vis_bits int64 [T, max_slots/64] (bit s of word s//64 = slot s visible).
-        Returns fp32 logits [n_logit_rows, vocab] of the last rows."""
-        lib = _lib.load()
+    def forward_padded(self, ids: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, vis_bits: torch.Tensor,
+                       n_slots: int, n_logit_rows: int) -> torch.Tensor:
+        """The forward call (device tensors as in `forward_raw`): fp32 logits [n_logit_rows, logits_ld] of the last rows, the library's
+        padded row stride kept (the row kernels of the host-mask path take `logits_ld`)."""
         T = ids.numel()
         assert vis_bits.shape == (T, self.max_slots // 64) and vis_bits.dtype == torch.int64
         with torch.cuda.device(self._device):
             raw = torch.empty(n_logit_rows * self.logits_ld, dtype=torch.float32, device=self._device)
-            _lib.check(lib.atspeed_llama_forward(self._handle, ids.data_ptr(), pos.data_ptr(), slots.data_ptr(),
-                                                 vis_bits.data_ptr(), T, n_slots, n_logit_rows, raw.data_ptr(),
-                                                 _lib.stream_ptr(self._device)))
-        return raw.view(n_logit_rows, self.logits_ld)[:, : self.dims.vocab_size]
+            _lib.check(_lib.load().atspeed_llama_forward(self._handle, ids.data_ptr(), pos.data_ptr(), slots.data_ptr(),
+                                                         vis_bits.data_ptr(), T, n_slots, n_logit_rows, raw.data_ptr(),
+                                                         _lib.stream_ptr(self._device)))
+        return raw.view(n_logit_rows, self.logits_ld)
+
+    def forward_raw(self, ids: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, vis_bits: torch.Tensor,
+                    n_slots: int, n_logit_rows: int) -> torch.Tensor:
+        """ids/pos/slots int32 [T]; vis_bits int64 [T, max_slots/64] (bit s of word s//64 = slot s visible).
+        Returns fp32 logits [n_logit_rows, vocab] of the last rows."""
+        return self.forward_padded(ids, pos, slots, vis_bits, n_slots, n_logit_rows)[:, : self.dims.vocab_size]
 
     def forward_raw_batch(self, seqs, return_all: bool = False):
         """Several independent sequences in ONE forward.  `seqs`: list of (ids, pos, slots, vis_bits, n_slots, n_logit_rows) with CPU
@@ -406,13 +404,14 @@ class HipLlama:
         return [out[int(r0[i]): int(r0[i + 1])] for i in range(n)]
 
 
+def pack_vis_bits(vis: np.ndarray, max_slots: int) -> np.ndarray:
+    """bool [T, S] -> int64 [T, max_slots/64]: bit s % 64 of word s // 64 = slot s visible (slots >= S are not); little-endian hosts."""
+    T, S = vis.shape
+    full = np.zeros((T, max_slots), bool)
+    full[:, :S] = vis
+    return np.packbits(full, axis=-1, bitorder="little").view(np.int64)
+
+
 def vis_bits_from_bool(vis: torch.Tensor, max_slots: int) -> torch.Tensor:
     """bool [T, S] -> int64 [T, max_slots/64] bitset (host helper for tests)."""
-    T, S = vis.shape
-    v = torch.zeros(T, max_slots, dtype=torch.bool)
-    v[:, :S] = vis.cpu()
-    w = v.view(T, max_slots // 64, 64).to(torch.int64)
-    shifts = torch.arange(64, dtype=torch.int64)
-    lo = (w[..., :63] << shifts[:63]).sum(-1)
-    hi = w[..., 63] << 63            # wraps to the sign bit, which is what the bit pattern needs
-    return (lo + hi).contiguous()
+    return torch.from_numpy(pack_vis_bits(vis.cpu().numpy(), max_slots))

@@ -186,6 +186,30 @@ def test_decoder_cache_does_not_keep_models_alive():
     assert free0 - torch.cuda.mem_get_info()[0] < 64 << 20, "device memory grew across the sweep"
 
 
+def test_device_automaton_cache_does_not_keep_constraints_alive():
+    """The device copy of a compiled constraint (its CSR arrays and tile table) goes when the constraint does: the cache refers to the
+    `row_ptr` array it was built from weakly and drops the entry when that array is collected -- a process that compiles many tries must
+    not keep every one of them on the device."""
+    from atspeed_amd.beamSD import _DeviceFSM
+    case = CASES[0]
+    ci = build_case_inputs(case)                                           # a constraint object of its own, held by `ci` alone
+    tgt, drf = _models(ci, case["K"], case["DK"])
+    inputs = {"input_ids": torch.from_numpy(ci["prompt"])[None].cuda()}
+    gc.collect()
+    n0 = len(_DeviceFSM._cache)
+    fn = ci.pop("fn")
+    a = BSSD(tgt, drf, inputs, case["gamma"], case["max_new_tokens"], prefix_allowed_tokens_fn=fn)
+    b = target_generate(tgt, inputs, case["max_new_tokens"], prefix_allowed_tokens_fn=fn)
+    assert torch.equal(a["beam_sequence"], b["beam_sequence"])
+    assert len(_DeviceFSM._cache) == n0 + 1                                # both calls share the one automaton
+    del fn
+    gc.collect()
+    assert len(_DeviceFSM._cache) == n0, "the automaton of a collected constraint stayed in the cache"
+    fn2 = build_case_inputs(case)["fn"]                                    # and a new one compiles and runs as before
+    c = BSSD(tgt, drf, inputs, case["gamma"], case["max_new_tokens"], prefix_allowed_tokens_fn=fn2)
+    assert torch.equal(a["beam_sequence"], c["beam_sequence"])
+
+
 def test_bf16_engine_without_packed_operands_equals_packed_one():
     """The packed operand layout is an address change only: a bf16 model whose dims do not allow it (ffn % 32 != 0) keeps HF's row-major layout
     and works; and for dims that allow both, the engine with ATSPEED_PACK=0 (row-major weights, `weight_layout = 0`) returns exactly what the

@@ -3,6 +3,7 @@ atspeed_set_switch family takes its initial values from environment variables at
 (`tests/env_switch_worker.py`): the same users through the bf16 engine (one user per call and a 24-user lock-step batch) and through the W8A8
 target, compared with the default configuration -- rounds and accepted steps equal, scores within the 16-bit noise of another summation order,
 item sets overlapping.  One process at a time on the card."""
+import ctypes as C
 import json
 import os
 import subprocess
@@ -50,3 +51,28 @@ def test_switched_configuration_decodes_like_the_default(default_run, switch):
             overlap = len({tuple(x) for x in a["items"]} & {tuple(x) for x in b["items"]}) / 20.0
             assert overlap >= 0.7, (key, overlap)
             assert abs(a["scores"][0] - b["scores"][0]) <= (0.5 if key.startswith("fp8") else 0.25), (key, a["scores"][0], b["scores"][0])
+
+
+def test_switches_with_an_unknown_name_change_no_switch():
+    """`_lib.switches` reads every name before it sets any: a misspelt later name raises on entry (there is no `__exit__` then) and must
+    leave the earlier, valid switches as they were; a valid block still sets on entry and restores on exit."""
+    from atspeed_amd import _lib
+    lib = _lib.load()
+
+    def read(name):
+        cur = C.c_int32(0)
+        _lib.check(lib.atspeed_get_switch(name.encode(), C.byref(cur)))
+        return cur.value
+
+    old = read("gemm_sk")
+    other = 2 if old != 2 else 0
+    try:
+        with pytest.raises(_lib.AtSpeedError, match="unknown switch"):
+            with _lib.switches(gemm_sk=other, no_such_switch=1):
+                pass
+        assert read("gemm_sk") == old
+        with _lib.switches(gemm_sk=other):
+            assert read("gemm_sk") == other
+        assert read("gemm_sk") == old
+    finally:
+        _lib.check(lib.atspeed_set_switch(b"gemm_sk", old))      # a failure here must not reconfigure the tests that follow
