@@ -531,6 +531,37 @@ __global__ __launch_bounds__(64 * NW, 2) void tree_attn32_kernel(const bf16_t* _
   }
 }
 
+// ---- launch layer of the MFMA kernels.  They take one argument list; a launch site varies only the instantiation <DH, NW[, NSTG]>, the block
+// (64 * NW) and the dynamic LDS.  lds_limit != 0: the kernel's dynamic-LDS cap is raised to it first (ats_lds_limit).
+struct AttnArgs {
+  const bf16_t* q; int ldq; const SegTable* dt; size_t layer_off_bytes; int vis_words; bf16_t* out; int ldo, pk, n_heads; float scale;
+};
+template <auto KERNEL>
+int launch_attn(dim3 grid, int block, size_t lds, int lds_limit, hipStream_t st, const AttnArgs& a) {
+  if (lds_limit) ATS_TRY((ats_lds_limit<KERNEL>(lds_limit)));
+  KERNEL<<<grid, block, lds, st>>>(a.q, a.ldq, a.dt, a.layer_off_bytes, a.vis_words, a.out, a.ldo, a.pk, a.n_heads, a.scale);
+  return ATSPEED_OK;
+}
+// one selection per kernel family: the caller picks DH from head_dim (64 | 128), the waves of a query tile pick NW
+template <int DH>
+int launch_attn32(int nw, dim3 grid, hipStream_t st, const AttnArgs& a) {            // nw = tile rows / 32: 2 | 4 | 8
+  constexpr int lds_bytes = 2 * (64 * DH * 2 + 64 * (DH * 2 + 32));
+  if (nw == 8) return launch_attn<tree_attn32_kernel<DH, 8>>(grid, 512, lds_bytes, lds_bytes, st, a);
+  if (nw == 4) return launch_attn<tree_attn32_kernel<DH, 4>>(grid, 256, lds_bytes, lds_bytes, st, a);
+  return launch_attn<tree_attn32_kernel<DH, 2>>(grid, 128, lds_bytes, lds_bytes, st, a);
+}
+template <int DH>
+int launch_attn_ring(int nw, dim3 grid, size_t ring_lds, hipStream_t st, const AttnArgs& a) {   // nw = tile rows / 16: 4 | 8
+  if (nw == 8) return launch_attn<tree_attn_mfma_kernel<DH, 8, 4>>(grid, 512, ring_lds, 160 * 1024 - 64, st, a);
+  return launch_attn<tree_attn_mfma_kernel<DH, 4, 4>>(grid, 256, ring_lds, 160 * 1024 - 64, st, a);
+}
+template <int DH>
+int launch_attn_mfma(int nw, dim3 grid, hipStream_t st, const AttnArgs& a) {         // nw = tile rows / 16: 4 | 8 | 16
+  if (nw == 16) return launch_attn<tree_attn_mfma_kernel<DH, 16>>(grid, 1024, 0, 0, st, a);
+  if (nw == 8) return launch_attn<tree_attn_mfma_kernel<DH, 8>>(grid, 512, 0, 0, st, a);
+  return launch_attn<tree_attn_mfma_kernel<DH, 4>>(grid, 256, 0, 0, st, a);
+}
+
 }  // namespace
 
 int ats_tree_attention_segs(const void* q, int ldq, const SegTable& t, const SegTable* dt, size_t layer_off_bytes, int vis_words,
@@ -545,59 +576,26 @@ int ats_tree_attention_segs(const void* q, int ldq, const SegTable& t, const Seg
   if (dtype == ATS_HALF && (head_dim == 64 || head_dim == 128) && (ldq % 8) == 0 && (ldo % 4) == 0) {
     dim3 mgrid(t.n_qtiles * n_heads);
     ATS_REQUIRE(t.qtile_rows == 64 || t.qtile_rows == 128 || t.qtile_rows == 256, ATSPEED_ERR_INVALID, "attention: query tile of %d rows", t.qtile_rows);
+    const AttnArgs a{(const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words, (bf16_t*)out, ldo, pk, n_heads, scale};
     // small grids (one user: 32-64 workgroups) are latency-bound per workgroup and keep the 16-rows-per-wave kernel (twice the waves per tile)
     constexpr int rows32_min_wgs = 512;       // (measured in round 2)
     if (rows_per_wave == 32 || (rows_per_wave == 0 && t.n_qtiles * n_heads >= rows32_min_wgs)) {
-#define ATS_ATTN32(DHV, NWV)                                                                                                   \
-  {                                                                                                                            \
-    constexpr int lds_bytes = 2 * (64 * DHV * 2 + 64 * (DHV * 2 + 32));                                                        \
-    ATS_TRY((ats_lds_limit<tree_attn32_kernel<DHV, NWV>>(lds_bytes)));                                                        \
-    tree_attn32_kernel<DHV, NWV><<<mgrid, 64 * NWV, lds_bytes, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words,    \
-                                                                     (bf16_t*)out, ldo, pk, n_heads, scale);                       \
-  }
-      if (head_dim == 128) { if (t.qtile_rows == 256) ATS_ATTN32(128, 8) else if (t.qtile_rows == 128) ATS_ATTN32(128, 4) else ATS_ATTN32(128, 2) }
-      else                 { if (t.qtile_rows == 256) ATS_ATTN32(64, 8)  else if (t.qtile_rows == 128) ATS_ATTN32(64, 4)  else ATS_ATTN32(64, 2) }
-#undef ATS_ATTN32
+      ATS_TRY(head_dim == 128 ? launch_attn32<128>(t.qtile_rows / 32, mgrid, st, a) : launch_attn32<64>(t.qtile_rows / 32, mgrid, st, a));
       ATS_LAUNCH_CHECK();
       return ATSPEED_OK;
     }
     // one user's forwards (at most one workgroup per CU): the DMA-ring form, the whole K/V of a user in flight before the first product
     constexpr int ring_max_wgs = 256;
-    {
-      const int nw = t.qtile_rows / 16;
-      const size_t tile = (size_t)64 * head_dim * 2 + (size_t)64 * (head_dim * 2 + 32);
-      const size_t ring_lds = 4 * tile + (size_t)16 * nw * vis_words * sizeof(uint64_t);
-      // (not the 256-row tile: 16 waves cap a lane at 128 registers and the compiler's spill traffic would sit in the hand-counted vmcnt window)
-      if (nw <= 8 && (int)(t.n_qtiles * n_heads) <= ring_max_wgs && ring_lds <= 160 * 1024 - 64) {
-#define ATS_ATTN_RING(DHV, NWV)                                                                                                \
-  {                                                                                                                            \
-    ATS_TRY((ats_lds_limit<tree_attn_mfma_kernel<DHV, NWV, 4>>(160 * 1024 - 64)));                                             \
-    tree_attn_mfma_kernel<DHV, NWV, 4><<<mgrid, 64 * NWV, ring_lds, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words, \
-                                                                          (bf16_t*)out, ldo, pk, n_heads, scale);                  \
-  }
-        if (head_dim == 128) { if (nw == 8) ATS_ATTN_RING(128, 8) else ATS_ATTN_RING(128, 4) }
-        else                 { if (nw == 8) ATS_ATTN_RING(64, 8)  else ATS_ATTN_RING(64, 4) }
-#undef ATS_ATTN_RING
-        ATS_LAUNCH_CHECK();
-        return ATSPEED_OK;
-      }
+    const int nw = t.qtile_rows / 16;
+    const size_t tile = (size_t)64 * head_dim * 2 + (size_t)64 * (head_dim * 2 + 32);
+    const size_t ring_lds = 4 * tile + (size_t)16 * nw * vis_words * sizeof(uint64_t);
+    // (not the 256-row tile: 16 waves cap a lane at 128 registers and the compiler's spill traffic would sit in the hand-counted vmcnt window)
+    if (nw <= 8 && (int)(t.n_qtiles * n_heads) <= ring_max_wgs && ring_lds <= 160 * 1024 - 64) {
+      ATS_TRY(head_dim == 128 ? launch_attn_ring<128>(nw, mgrid, ring_lds, st, a) : launch_attn_ring<64>(nw, mgrid, ring_lds, st, a));
+      ATS_LAUNCH_CHECK();
+      return ATSPEED_OK;
     }
-    if (t.qtile_rows == 256) {
-      if (head_dim == 128)
-        tree_attn_mfma_kernel<128, 16><<<mgrid, 1024, 0, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words, (bf16_t*)out, ldo, pk, n_heads, scale);
-      else
-        tree_attn_mfma_kernel<64, 16><<<mgrid, 1024, 0, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words, (bf16_t*)out, ldo, pk, n_heads, scale);
-    } else if (t.qtile_rows == 128) {
-      if (head_dim == 128)
-        tree_attn_mfma_kernel<128, 8><<<mgrid, 512, 0, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words, (bf16_t*)out, ldo, pk, n_heads, scale);
-      else
-        tree_attn_mfma_kernel<64, 8><<<mgrid, 512, 0, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words, (bf16_t*)out, ldo, pk, n_heads, scale);
-    } else {
-      if (head_dim == 128)
-        tree_attn_mfma_kernel<128, 4><<<mgrid, 256, 0, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words, (bf16_t*)out, ldo, pk, n_heads, scale);
-      else
-        tree_attn_mfma_kernel<64, 4><<<mgrid, 256, 0, st>>>((const bf16_t*)q, ldq, dt, layer_off_bytes, vis_words, (bf16_t*)out, ldo, pk, n_heads, scale);
-    }
+    ATS_TRY(head_dim == 128 ? launch_attn_mfma<128>(nw, mgrid, st, a) : launch_attn_mfma<64>(nw, mgrid, st, a));
     ATS_LAUNCH_CHECK();
     return ATSPEED_OK;
   }

@@ -22,30 +22,6 @@ __global__ void fill_hash_normal_kernel(T* dst, size_t n, uint32_t seed, float s
   }
 }
 
-
-// ---------------------------------------------------------------------------- embed
-// one 16-byte chunk per thread; a token row is hidden*sizeof(T) contiguous bytes
-__global__ void embed_kernel(const uint4* __restrict__ table, const int32_t* __restrict__ ids, uint4* __restrict__ out,
-                             int n_tokens, int chunks_per_row, int vocab) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  int total = n_tokens * chunks_per_row;
-  if (i >= total) return;
-  int t = i / chunks_per_row, c = i - t * chunks_per_row;
-  int id = ids[t];
-  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-  out[i] = table[(size_t)id * chunks_per_row + c];
-}
-
-int ats_embed(const void* table, const int32_t* ids, void* out, int n_tokens, int hidden, int vocab, int dtype,
-              hipStream_t st) {
-  int esz = dtype == ATSPEED_F32 ? 4 : 2;
-  int cpr = hidden * esz / 16;
-  int total = n_tokens * cpr;
-  embed_kernel<<<(total + 255) / 256, 256, 0, st>>>((const uint4*)table, ids, (uint4*)out, n_tokens, cpr, vocab);
-  ATS_LAUNCH_CHECK();
-  return ATSPEED_OK;
-}
-
 // ---------------------------------------------------------------------------- rmsnorm
 // one workgroup per row; fp32 statistics (HF LlamaRMSNorm upcasts); y = w * (x * rsqrt(mean(x^2)+eps))
 template <typename T>
@@ -180,56 +156,6 @@ int ats_rmsnorm(const void* x, const void* w, void* y, int rows, int hidden, flo
   return ATSPEED_OK;
 }
 
-
-
-// ---------------------------------------------------------------------------- rope + kv scatter
-// rotate-half convention of HF Llama: pairs (i, i + dh/2); cos/sin tables [max_pos][dh/2] fp32.
-// thread = (token, head, pair i): rotates q in place, writes rotated k and v to the cache slot.
-template <typename T>
-__global__ void rope_kv_kernel(T* __restrict__ qkv, const int32_t* __restrict__ pos, const int32_t* __restrict__ slots,
-                               const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
-                               T* __restrict__ kcache, T* __restrict__ vcache, int n_tokens, int n_heads, int head_dim,
-                               int max_pos) {
-  int half = head_dim >> 1;
-  int hidden = n_heads * head_dim;
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  int total = n_tokens * n_heads * half;
-  if (i >= total) return;
-  int p = i % half;
-  int h = (i / half) % n_heads;
-  int t = i / (half * n_heads);
-  int ps = pos[t];
-  ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
-  float c = cos_tab[(size_t)ps * half + p], s = sin_tab[(size_t)ps * half + p];
-  T* row = qkv + (size_t)t * 3 * hidden;
-  int d0 = h * head_dim + p, d1 = d0 + half;
-  float q0 = Elt<T>::load(row + d0), q1 = Elt<T>::load(row + d1);
-  Elt<T>::store(row + d0, q0 * c - q1 * s);
-  Elt<T>::store(row + d1, q1 * c + q0 * s);
-  float k0 = Elt<T>::load(row + hidden + d0), k1 = Elt<T>::load(row + hidden + d1);
-  size_t co = (size_t)slots[t] * hidden;
-  Elt<T>::store(kcache + co + d0, k0 * c - k1 * s);
-  Elt<T>::store(kcache + co + d1, k1 * c + k0 * s);
-  vcache[co + d0] = row[2 * hidden + d0];
-  vcache[co + d1] = row[2 * hidden + d1];
-}
-
-int ats_rope_kv(void* qkv, const int32_t* pos, const int32_t* slots, const float* cos_tab, const float* sin_tab,
-                void* kcache, void* vcache, int n_tokens, int n_heads, int head_dim, int max_pos, int dtype,
-                hipStream_t st) {
-  int total = n_tokens * n_heads * (head_dim / 2);
-  if (total <= 0) return ATSPEED_OK;
-  if (dtype == ATSPEED_F32)
-    rope_kv_kernel<float><<<(total + 255) / 256, 256, 0, st>>>((float*)qkv, pos, slots, cos_tab, sin_tab, (float*)kcache,
-                                                                (float*)vcache, n_tokens, n_heads, head_dim, max_pos);
-  else
-    rope_kv_kernel<bf16_t><<<(total + 255) / 256, 256, 0, st>>>((bf16_t*)qkv, pos, slots, cos_tab, sin_tab,
-                                                                 (bf16_t*)kcache, (bf16_t*)vcache, n_tokens, n_heads,
-                                                                 head_dim, max_pos);
-  ATS_LAUNCH_CHECK();
-  return ATSPEED_OK;
-}
-
 // ---------------------------------------------------------------------------- multi-user (segment) variants
 __device__ __forceinline__ int seg_of_row(const SegTable* t, int row) {
   int lo = 0, hi = t->n;                           // last segment with row0 <= row
@@ -257,6 +183,7 @@ int ats_row_info(const SegTable& t, const SegTable* dt, RowInfo* out, int max_po
   return ATSPEED_OK;
 }
 
+// one 16-byte chunk per thread; a token row is hidden*sizeof(T) contiguous bytes
 __global__ void embed_segs_kernel(const uint4* __restrict__ table, const SegTable* __restrict__ t, uint4* __restrict__ out,
                                   int chunks_per_row, int vocab) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -277,6 +204,8 @@ int ats_embed_segs(const void* table, const SegTable& t, const SegTable* dt, voi
   return ATSPEED_OK;
 }
 
+// rotate-half convention of HF Llama: pairs (i, i + dh/2); cos/sin tables [max_pos][dh/2] fp32.
+// thread = (token, head, pair i): rotates q in place, writes rotated k and v to the cache slot.
 template <typename T>
 __global__ void rope_kv_segs_kernel(T* __restrict__ qkv, const SegTable* __restrict__ t, const float* __restrict__ cos_tab,
                                     const float* __restrict__ sin_tab, size_t layer_off, int n_heads, int head_dim, int max_pos) {

@@ -1826,32 +1826,28 @@ Plan make_plan(int m, int n, int k) {
 
 struct FusedNorm { const void* w; void* xn; float eps; bool done; void* q = nullptr; float* qscale = nullptr; };   // q: also / instead the e4m3 row + per-token scale
 
+// the fused reduce of a residual projection (n <= 8192): 4 values per thread up to 4096 columns, else 8; V = 4 reads the slabs 16 bytes at a time;
+// QUANT: the W8A8 consumer's e4m3 row + per-token scale (and xn if asked for)
+template <typename T, int V, bool QUANT>
+int launch_resid_rmsnorm(const float* partial, void* c, int m, int n, int ldc, int splits, hipStream_t st, FusedNorm* fn, int pk) {
+  unsigned char* q = QUANT ? (unsigned char*)fn->q : nullptr;
+  float* qscale = QUANT ? fn->qscale : nullptr;
+  if (n <= 4096) splitk_resid_rmsnorm_kernel<T, 4, V, QUANT><<<m, 1024, 0, st>>>(partial, (T*)c, (const T*)fn->w, (T*)fn->xn, m, n, ldc, splits, fn->eps, pk, q, qscale);
+  else           splitk_resid_rmsnorm_kernel<T, 8, V, QUANT><<<m, 1024, 0, st>>>(partial, (T*)c, (const T*)fn->w, (T*)fn->xn, m, n, ldc, splits, fn->eps, pk, q, qscale);
+  ATS_LAUNCH_CHECK();
+  fn->done = true;
+  return ATSPEED_OK;
+}
+
 // second pass of a split-K GEMM: sum the fp32 slabs and apply the epilogue (fused with the next RMSNorm for the residual projections)
 template <typename T, int EPI>
 int reduce_splits(const float* partial, void* c, int m, int n, int ldc, int splits, hipStream_t st, FusedNorm* fn, int pk) {
   const bool v4 = (n % 4) == 0 && (ldc % 4) == 0 && ((uintptr_t)partial & 15) == 0;
   if constexpr (EPI == EPI_RESID) {
-    if constexpr (sizeof(T) == 2) {
-      if (fn && fn->q && n <= 8192 && v4) {                     // W8A8 consumer: e4m3 row + scale (and xn if asked for)
-        if (n <= 4096) splitk_resid_rmsnorm_kernel<T, 4, 4, true><<<m, 1024, 0, st>>>(partial, (T*)c, (const T*)fn->w, (T*)fn->xn, m, n, ldc, splits, fn->eps, pk, (unsigned char*)fn->q, fn->qscale);
-        else           splitk_resid_rmsnorm_kernel<T, 8, 4, true><<<m, 1024, 0, st>>>(partial, (T*)c, (const T*)fn->w, (T*)fn->xn, m, n, ldc, splits, fn->eps, pk, (unsigned char*)fn->q, fn->qscale);
-        ATS_LAUNCH_CHECK();
-        fn->done = true;
-        return ATSPEED_OK;
-      }
-    }
-    if (fn && !fn->q && n <= 8192) {
-      if (n <= 4096) {
-        if (v4) splitk_resid_rmsnorm_kernel<T, 4, 4><<<m, 1024, 0, st>>>(partial, (T*)c, (const T*)fn->w, (T*)fn->xn, m, n, ldc, splits, fn->eps, pk);
-        else    splitk_resid_rmsnorm_kernel<T, 4, 1><<<m, 1024, 0, st>>>(partial, (T*)c, (const T*)fn->w, (T*)fn->xn, m, n, ldc, splits, fn->eps, pk);
-      } else {
-        if (v4) splitk_resid_rmsnorm_kernel<T, 8, 4><<<m, 1024, 0, st>>>(partial, (T*)c, (const T*)fn->w, (T*)fn->xn, m, n, ldc, splits, fn->eps, pk);
-        else    splitk_resid_rmsnorm_kernel<T, 8, 1><<<m, 1024, 0, st>>>(partial, (T*)c, (const T*)fn->w, (T*)fn->xn, m, n, ldc, splits, fn->eps, pk);
-      }
-      ATS_LAUNCH_CHECK();
-      fn->done = true;
-      return ATSPEED_OK;
-    }
+    if constexpr (sizeof(T) == 2)
+      if (fn && fn->q && n <= 8192 && v4) return launch_resid_rmsnorm<T, 4, true>(partial, c, m, n, ldc, splits, st, fn, pk);
+    if (fn && !fn->q && n <= 8192)
+      return v4 ? launch_resid_rmsnorm<T, 4, false>(partial, c, m, n, ldc, splits, st, fn, pk) : launch_resid_rmsnorm<T, 1, false>(partial, c, m, n, ldc, splits, st, fn, pk);
   }
   size_t outs = EPI == EPI_SWIGLU ? (size_t)m * (n / 2) : (size_t)m * n;
   if (v4) splitk_reduce_kernel<T, EPI, 4><<<(unsigned)((outs / 4 + 255) / 256), 256, 0, st>>>(partial, c, m, n, ldc, splits, pk);
@@ -1880,18 +1876,19 @@ static int ring_split_count(int m, int n, int k) {
   if (s > max_s) s = max_s;
   return s >= 1 ? s : 0;
 }
-static int launch_ring_split(const bf16_t* a, const bf16_t* w, float* partial, int m, int n, int k, int lda, int splits, hipStream_t st, int pk) {
+// the slab launch of both split forms of the ring kernel (ring_split_count above: tile_rows 256 above 128 tokens, group height 1;
+// kcut_split_count below: tile_rows from its rows256, group height 4): grid = weight tiles x token tiles x parts
+static int launch_ring_split(const bf16_t* a, const bf16_t* w, float* partial, int m, int n, int k, int lda, int splits, int tile_rows, int group_m, hipStream_t st, int pk) {
   ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 8, false, true>>(128 * 1024)));
   ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 4, false, true>>(96 * 1024)));
-  const int tiles_n = (n + 255) / 256;
+  const int tiles_n = (n + 255) / 256, tiles_m = (m + tile_rows - 1) / tile_rows;
   const float* none = nullptr;
-  const int tiles_m = (m + 255) / 256;
-  if (m > 128)
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, 8, false, true>), dim3(tiles_n * tiles_m * splits), dim3(512), 128 * 1024, st, (const void*)a, (const void*)w,
-                       none, none, (void*)partial, m, n, k, lda, n, tiles_n, tiles_m, 1, splits, (float*)nullptr, (const unsigned char*)nullptr, pk);
-  else
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, 4, false, true>), dim3(tiles_n * splits), dim3(512), 96 * 1024, st, (const void*)a, (const void*)w,
-                       none, none, (void*)partial, m, n, k, lda, n, tiles_n, 1, 1, splits, (float*)nullptr, (const unsigned char*)nullptr, pk);
+  auto launch = [&](auto mt2, int lds) {
+    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, decltype(mt2)::value, false, true>), dim3(tiles_n * tiles_m * splits), dim3(512), lds, st, (const void*)a, (const void*)w,
+                       none, none, (void*)partial, m, n, k, lda, n, tiles_n, tiles_m, group_m, splits, (float*)nullptr, (const unsigned char*)nullptr, pk);
+  };
+  if (tile_rows == 256) launch(std::integral_constant<int, 8>{}, 128 * 1024);
+  else                  launch(std::integral_constant<int, 4>{}, 96 * 1024);
   ATS_LAUNCH_CHECK();
   ats_count_path(ATS_PATH_RING_SPLIT);
   return ATSPEED_OK;
@@ -1915,21 +1912,6 @@ static int kcut_split_count(int m, int n, int k, int lda, bool* rows256 = nullpt
   if (rows256) *rows256 = r256;
   const int s_ = std::min(256 / tiles, (k / 128) / 4);
   return s_ >= 2 ? s_ : 0;
-}
-static int launch_ring_kcut(const bf16_t* a, const bf16_t* w, float* partial, int m, int n, int k, int lda, int splits, bool rows256, hipStream_t st, int pk) {
-  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 8, false, true>>(128 * 1024)));
-  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 4, false, true>>(96 * 1024)));
-  const int tiles_n = (n + 255) / 256, tiles_m = rows256 ? (m + 255) / 256 : (m + 127) / 128;
-  const float* none = nullptr;
-  if (rows256)
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, 8, false, true>), dim3(tiles_n * tiles_m * splits), dim3(512), 128 * 1024, st, (const void*)a, (const void*)w,
-                       none, none, (void*)partial, m, n, k, lda, n, tiles_n, tiles_m, 4, splits, (float*)nullptr, (const unsigned char*)nullptr, pk);
-  else
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, 4, false, true>), dim3(tiles_n * tiles_m * splits), dim3(512), 96 * 1024, st, (const void*)a, (const void*)w,
-                       none, none, (void*)partial, m, n, k, lda, n, tiles_n, tiles_m, 4, splits, (float*)nullptr, (const unsigned char*)nullptr, pk);
-  ATS_LAUNCH_CHECK();
-  ats_count_path(ATS_PATH_RING_SPLIT);
-  return ATSPEED_OK;
 }
 
 // the LDS-tiled kernel; SPLIT (p.splits > 1) stores fp32 slabs [z][M][N] to `partial`, the caller reduces them
@@ -2132,10 +2114,10 @@ template <typename T, int EPI>
 int launch_slabs(const GemmPlan& p, const T* a, const T* w, void* c, int m, int n, int k, int lda, int ldc, float* partial, hipStream_t st, int pk) {
   if constexpr (sizeof(T) == 2) {
     switch (p.form) {
-      case G16_KCUT:        return launch_ring_kcut(a, w, partial, m, n, k, lda, p.splits, p.rows256, st, pk);
+      case G16_KCUT:        return launch_ring_split(a, w, partial, m, n, k, lda, p.splits, p.rows256 ? 256 : 128, 4, st, pk);
       case G16_PANEL_SPLIT: return launch_panel<EPI_F32, true>(a, w, (void*)partial, m, n, k, lda, n, p.splits, st, pk);
       case G16_WDMA_SPLIT:  return launch_wdma_split(a, w, partial, m, n, k, lda, p.splits, st, pk);
-      case G16_RING_SPLIT:  return launch_ring_split(a, w, partial, m, n, k, lda, p.splits, st, pk);
+      case G16_RING_SPLIT:  return launch_ring_split(a, w, partial, m, n, k, lda, p.splits, m > 128 ? 256 : 128, 1, st, pk);
     }
   }
   return launch_tiled<T, EPI>(p.tiled, a, w, c, m, n, k, lda, ldc, partial, st, pk);
@@ -2313,10 +2295,12 @@ static int launch_mx_split(const unsigned char* x, const float* sx, const unsign
   ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI_F32, 4, 8, true>>(96 * 1024)));
   ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI_F32, 8, 8, true>>(128 * 1024)));
   const int tiles_n = (n + 255) / 256, tiles_m = r256 ? (m + 255) / 256 : (m + 127) / 128;
-  if (r256) hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI_F32, 8, 8, true>), dim3(tiles_n * tiles_m * splits), dim3(512), 128 * 1024, st, (const void*)x, (const void*)w, sx, sw,
-                               (void*)partial, m, n, k, n, tiles_n, tiles_m, 4, pk, RopeEpi{}, splits);
-  else      hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI_F32, 4, 8, true>), dim3(tiles_n * tiles_m * splits), dim3(512), 96 * 1024, st, (const void*)x, (const void*)w, sx, sw,
-                               (void*)partial, m, n, k, n, tiles_n, tiles_m, 4, pk, RopeEpi{}, splits);
+  auto launch = [&](auto mt2, int lds) {
+    hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI_F32, decltype(mt2)::value, 8, true>), dim3(tiles_n * tiles_m * splits), dim3(512), lds, st, (const void*)x, (const void*)w,
+                       sx, sw, (void*)partial, m, n, k, n, tiles_n, tiles_m, 4, pk, RopeEpi{}, splits);
+  };
+  if (r256) launch(std::integral_constant<int, 8>{}, 128 * 1024);
+  else      launch(std::integral_constant<int, 4>{}, 96 * 1024);
   ATS_LAUNCH_CHECK();
   ats_count_path(ATS_PATH_FP8_RING_SPLIT);
   return ATSPEED_OK;

@@ -1,26 +1,21 @@
 // Host-side interfaces of the kernel translation units that exist once per 16-bit flavour (gemm.hip, attn.hip, elementwise.hip: common.h,
 // "the 16-bit flavour").  internal.h includes this file inside namespace ats_bf16 (which also holds the fp32 parity kernels) and inside
 // namespace ats_f16; callers outside those translation units choose with ATS_KD(dtype, call).  No include guard on purpose.
-// ---- fill.hip / elementwise.hip -------------------------------------------------------
+// ---- elementwise.hip --------------------------------------------------------------
 // `t` = host copy (sizes), `dt` = the staged device copy the kernels read
 int ats_fill_hash_normal(void* dst, size_t n, uint32_t seed, float scale, float add, int dtype, uint64_t offset, hipStream_t st);
 int ats_embed_segs(const void* table, const SegTable& t, const SegTable* dt, void* out, int hidden, int vocab, int dtype, hipStream_t st);
 // qkv_slabs != nullptr: the projection's fp32 split-K slabs [splits][total_tok][3 * hidden]; q is written (rotated) to qkv, k / v only to the caches
 int ats_rope_kv_segs_slabs(const float* qkv_slabs, int splits, void* qkv, const SegTable& t, const SegTable* dt, const float* cos_tab,
                            const float* sin_tab, size_t layer_off_bytes, int n_heads, int head_dim, int max_pos, hipStream_t st);
+// rotate q and k in place inside the fused qkv buffer ([T][3*hidden]) and scatter k,v to the cache slots
 int ats_rope_kv_segs(void* qkv, const SegTable& t, const SegTable* dt, const float* cos_tab, const float* sin_tab, size_t layer_off_bytes,
                      int n_heads, int head_dim, int max_pos, int dtype, hipStream_t st);
 int ats_row_info(const SegTable& t, const SegTable* dt, RowInfo* out, int max_pos, hipStream_t st);
 int ats_gather_logit_rows(const void* h, const SegTable& t, const SegTable* dt, void* out, int hidden, int dtype, hipStream_t st);
-int ats_embed(const void* table, const int32_t* ids, void* out, int n_tokens, int hidden, int vocab, int dtype,
-              hipStream_t st);
 int ats_rmsnorm(const void* x, const void* w, void* y, int rows, int hidden, float eps, int dtype, hipStream_t st, int pk = 0);   // pk: y in the packed operand layout
 // row-major [rows][row_bytes] -> packed operand layout (common.h ats_pk_byte) or back; out of place, row_bytes % 64 == 0
 int ats_pack_rows(const void* src, void* dst, int rows, int row_bytes, int to_packed, hipStream_t st);
-// rotate q and k in place inside the fused qkv buffer ([T][3*hidden]) and scatter k,v to the cache slots
-int ats_rope_kv(void* qkv, const int32_t* pos, const int32_t* slots, const float* cos_tab, const float* sin_tab,
-                void* kcache, void* vcache, int n_tokens, int n_heads, int head_dim, int max_pos, int dtype,
-                hipStream_t st);
 
 // ---- gemm.hip -------------------------------------------------------------------------
 size_t ats_gemm_workspace_bytes(int m, int n, int k, int dtype);

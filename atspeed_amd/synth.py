@@ -3,7 +3,7 @@
 There is no tokenizer, dataset or checkpoint offline, so every test, fixture and
 benchmark draws its weights / prompts / item index from one counter-based hash
 PRNG that is bit-reproducible in numpy (here) and on the device
-(`csrc/fill.hip`, same integer recipe).  Nothing here is on the product path's
+(`csrc/elementwise.hip`, same integer recipe).  Nothing here is on the product path's
 compute: it only manufactures inputs.
 
 Vocabulary shape follows the reference's data (facts, not copied data):
