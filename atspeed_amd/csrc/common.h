@@ -163,11 +163,6 @@ template <bool EXACT> __device__ __forceinline__ float ats_silu(float g) {
   if constexpr (EXACT) return g / d;
   else return g * __builtin_amdgcn_rcpf(d);
 }
-// The rotary pair (x0, x1) = (x[d], x[d + head_dim/2]) of the bf16 engine, with the contraction spelled out: the separate RoPE pass, the
-// slab-summing one and the qkv GEMM's fused epilogue must round identically (the compiler is otherwise free to pick which product it fuses).
-__device__ __forceinline__ float rope_first(float x0, float x1, float c, float s) { return __fmaf_rn(x0, c, -__fmul_rn(x1, s)); }    // x0 cos - x1 sin
-__device__ __forceinline__ float rope_second(float x0, float x1, float c, float s) { return __fmaf_rn(x1, c, __fmul_rn(x0, s)); }    // x1 cos + x0 sin
-
 template <typename T> struct Elt;
 template <> struct Elt<float> {
   static constexpr int kPerChunk = 4;   // elements per 16-byte chunk
@@ -222,5 +217,153 @@ __device__ __forceinline__ uint32_t ford(float f) {
 __device__ __forceinline__ float ford_inv(uint32_t o) {
   uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
   return __uint_as_float(u);
+}
+
+// ---------------------------------------------------------------- rounding rules several kernels share
+// Kernels that must agree bit for bit (a fused epilogue and the separate pass it replaces, the e4m3 producers, every residual add) call
+// ONE definition here; written in the flavour primitives only, so bf16 and fp16 stay the same source.  "16-bit" = the flavour's type.
+template <typename T> __device__ __forceinline__ float round_elt(float v) {          // v as the engine's T holds it
+  if constexpr (sizeof(T) == 2) return bf2f(f2bf(v));
+  else return v;
+}
+
+// The rotary pair (x0, x1) = (x[d], x[d + head_dim/2]) of the 16-bit engine, with the contraction spelled out: the separate RoPE pass, the
+// slab-summing one and the qkv GEMMs' fused epilogues must round identically (the compiler is otherwise free to pick which product it fuses).
+__device__ __forceinline__ float rope_first(float x0, float x1, float c, float s) { return __fmaf_rn(x0, c, -__fmul_rn(x1, s)); }    // x0 cos - x1 sin
+__device__ __forceinline__ float rope_second(float x0, float x1, float c, float s) { return __fmaf_rn(x1, c, __fmul_rn(x0, s)); }    // x1 cos + x0 sin
+// two pairs at once: x = 16-bit (x[d], x[d+1]), y = (x[d + half], x[d+1 + half]), i.e. the projection's rounded outputs; the rotation in fp32
+// on those, one more rounding.  Returns (rotated x, rotated y).
+__device__ __forceinline__ uint2 rope_pk(uint32_t x, uint32_t y, float c0, float s0, float c1, float s1) {
+  return make_uint2(f2bf_pk(rope_first(bf_lo(x), bf_lo(y), c0, s0), rope_first(bf_hi(x), bf_hi(y), c1, s1)),
+                    f2bf_pk(rope_second(bf_lo(x), bf_lo(y), c0, s0), rope_second(bf_hi(x), bf_hi(y), c1, s1)));
+}
+// four pairs: the form of the GEMM epilogues (a lane holds four adjacent columns and their partners)
+__device__ __forceinline__ void rope_pk(const uint2& x, const uint2& y, const float4& c, const float4& s, uint2& first, uint2& second) {
+  const uint2 a = rope_pk(x.x, y.x, c.x, s.x, c.y, s.y), b = rope_pk(x.y, y.y, c.z, s.z, c.w, s.w);
+  first = make_uint2(a.x, b.x);
+  second = make_uint2(a.y, b.y);
+}
+// rotation index of a token position: clamped to the cos / sin tables
+__device__ __forceinline__ int rope_pos(int ps, int max_pos) { return ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps); }
+// row `slot` of one layer's K or V cache (cache = the user's layer-0 base, H elements per row)
+template <typename T = bf16_t> __device__ __forceinline__ T* kv_row(void* cache, size_t layer_off, int slot, int H) {
+  return reinterpret_cast<T*>(reinterpret_cast<char*>(cache) + layer_off) + (size_t)slot * H;
+}
+
+// Residual add h = round(h + round(proj)): the projection's output is a T tensor before the add (HF: o_proj / down_proj return the dtype).
+__device__ __forceinline__ uint32_t resid_pk(uint32_t h, uint32_t p) { return f2bf_pk(bf_lo(h) + bf_lo(p), bf_hi(h) + bf_hi(p)); }
+template <typename T> __device__ __forceinline__ float resid_add(T* h, float proj) {   // in memory; returns what *h now holds
+  const float v = Elt<T>::load(h) + round_elt<T>(proj);
+  Elt<T>::store(h, v);
+  return round_elt<T>(v);
+}
+
+// SwiGLU: gate and up rounded to T first (the reference's two projections are T tensors), SiLU and the product in fp32, one rounding.  The
+// fp32 engine (parity mode) rounds nothing and takes the exact quotient.
+__device__ __forceinline__ uint32_t swiglu_pk(float g0, float g1, float u0, float u1) {
+  const uint32_t gp = f2bf_pk(g0, g1), up = f2bf_pk(u0, u1);
+  return f2bf_pk(ats_silu<false>(bf_lo(gp)) * bf_lo(up), ats_silu<false>(bf_hi(gp)) * bf_hi(up));
+}
+template <typename T> __device__ __forceinline__ float swiglu(float g, float u) {      // the caller's store rounds
+  return ats_silu<sizeof(T) == 4>(round_elt<T>(g)) * round_elt<T>(u);
+}
+
+// OCP e4m3 with a per-row scale: scale = max|x| / 448 (1 for an all-zero row), q = e4m3(clamp(x / scale, +-448)), x the 16-bit-rounded value
+// (the fused producers quantise what the separate pass would read back).  inv = 1 / scale.
+__device__ __forceinline__ float e4m3_scale(float amax) { return amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f; }
+__device__ __forceinline__ float e4m3_fit(float f, float inv) { return fminf(fmaxf(f * inv, -448.f), 448.f); }
+__device__ __forceinline__ uint32_t e4m3_cvt4(float c0, float c1, float c2, float c3) {  // four fitted values -> four bytes, the first lowest
+  int w = 0;
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c0, c1, w, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c2, c3, w, true);
+  return (uint32_t)w;
+}
+__device__ __forceinline__ uint32_t e4m3_pk4(float f0, float f1, float f2, float f3, float inv) {
+  return e4m3_cvt4(e4m3_fit(f0, inv), e4m3_fit(f1, inv), e4m3_fit(f2, inv), e4m3_fit(f3, inv));
+}
+__device__ __forceinline__ uint2 e4m3_pk8(const uint4& v, float inv) {                  // v: eight 16-bit values
+  const bf16_t* e = reinterpret_cast<const bf16_t*>(&v);
+  float f[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] = e4m3_fit(bf2f(e[j]), inv);
+  return make_uint2(e4m3_cvt4(f[0], f[1], f[2], f[3]), e4m3_cvt4(f[4], f[5], f[6], f[7]));
+}
+
+// Four adjacent columns gn .. gn + 3 of a row, p = the address of column gn: one vector store if all four are inside N and the stride allows
+// it (vec), else element by element up to N.  16-bit: packed conversions; RESID: the residual add on what p holds.
+__device__ __forceinline__ void store4(float* p, const f32x4_t& v, int gn, int N, bool vec) {
+  if (gn + 3 < N && vec) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else
+#pragma unroll
+    for (int r = 0; r < 4; ++r) if (gn + r < N) p[r] = v[r];
+}
+template <bool RESID = false>
+__device__ __forceinline__ void store4(bf16_t* p, const f32x4_t& v, int gn, int N, bool vec) {
+  if (gn + 3 < N && vec) {
+    uint2 o = make_uint2(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]));
+    if constexpr (RESID) { const uint2 h = *reinterpret_cast<const uint2*>(p); o.x = resid_pk(h.x, o.x); o.y = resid_pk(h.y, o.y); }
+    *reinterpret_cast<uint2*>(p) = o;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (gn + r < N) {
+        if constexpr (RESID) resid_add(p + r, v[r]);
+        else p[r] = f2bf(v[r]);
+      }
+  }
+}
+
+// Sum / maximum over a workgroup of NW waves through its __shared__ red[NW].  The per-wave partials are combined left to right, ((r0 + r1) + r2) + ...:
+// the RMSNorm statistics depend on that order.  block_put + barrier + red_*: for a kernel that reduces two values behind one barrier.
+template <int NW> __device__ __forceinline__ void block_put(float wave_value, float (&red)[NW]) { if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wave_value; }
+template <int NW> __device__ __forceinline__ float red_sum(const float (&red)[NW]) {
+  float t = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) t += red[w];
+  return t;
+}
+template <int NW> __device__ __forceinline__ float red_max(const float (&red)[NW]) {
+  float t = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) t = fmaxf(t, red[w]);
+  return t;
+}
+template <int NW> __device__ __forceinline__ float block_sum(float v, float (&red)[NW]) {
+  v = wave_sum_f32(v);
+  block_put(v, red);
+  __syncthreads();
+  return red_sum(red);
+}
+template <int NW> __device__ __forceinline__ float block_max(float v, float (&red)[NW]) {
+  v = wave_max_f32(v);
+  block_put(v, red);
+  __syncthreads();
+  return red_max(red);
+}
+
+// V consecutive floats of every split-K slab, summed in slab order.  The loads of four slabs are issued before their adds: with a runtime
+// slab count the plain loop waited out one memory round trip per slab (8 slabs = 8 x ~2 us; seen as 19 us reduce kernels behind
+// 15 us GEMMs in the one-user trace).
+template <int V>
+__device__ __forceinline__ void sum_slabs(const float* __restrict__ p, size_t slab_stride, int splits, float (&acc)[V]) {
+  typedef float vf __attribute__((ext_vector_type(V)));
+#pragma unroll
+  for (int i = 0; i < V; ++i) acc[i] = 0.f;
+  int z = 0;
+  for (; z + 4 <= splits; z += 4) {
+    vf q[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) q[u] = *reinterpret_cast<const vf*>(p + (size_t)(z + u) * slab_stride);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+      for (int i = 0; i < V; ++i) acc[i] += q[u][i];
+    }
+  }
+  for (; z < splits; ++z) {
+    vf q = *reinterpret_cast<const vf*>(p + (size_t)z * slab_stride);
+#pragma unroll
+    for (int i = 0; i < V; ++i) acc[i] += q[i];
+  }
 }
 #endif

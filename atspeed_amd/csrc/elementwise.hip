@@ -31,21 +31,17 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const T* __restrict__ x, c
   const T* xr = x + (size_t)blockIdx.x * hidden;
   float ss = 0.f;
   for (int i = threadIdx.x; i < hidden; i += 256) { float v = Elt<T>::load(xr + i); ss += v * v; }
-  ss = wave_sum_f32(ss);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-  __syncthreads();
-  float tot = red[0] + red[1] + red[2] + red[3];
-  float rs = rsqrtf(tot / (float)hidden + eps);
+  float rs = rsqrtf(block_sum(ss, red) / (float)hidden + eps);
   for (int i = threadIdx.x; i < hidden; i += 256) {
     float v = Elt<T>::load(xr + i) * rs;
-    if constexpr (sizeof(T) == 2) v = bf2f(f2bf(v));    // HF casts the normalised value to the input dtype first
+    v = round_elt<T>(v);                                // HF casts the normalised value to the input dtype first
     Elt<T>::store(y + ats_opnd_idx<sizeof(T)>(pk, blockIdx.x, i, hidden), Elt<T>::load(w + i) * v);   // y: a GEMM operand (packed when pk)
   }
 }
 
 // bf16 rows of up to 8192 elements: 16-byte loads, the row stays in registers between the two passes (read once, written once).
-// QUANT: also emit the row as OCP e4m3 with its scale (= what quant_rows_fp8_kernel makes of the bf16 output, bit for bit), so the
-// W8A8 projection that consumes the norm needs no quantisation pass of its own; y may then be null.
+// QUANT: also emit the row as OCP e4m3 with its scale (common.h: e4m3_scale / e4m3_pk8 on the 16-bit output), so the W8A8 projection that
+// consumes the norm needs no quantisation pass of its own; y may then be null.
 template <int NC, bool QUANT>
 __global__ __launch_bounds__(256) void rmsnorm_bf16_vec_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
                                                                bf16_t* __restrict__ y, int hidden, float eps,
@@ -69,10 +65,11 @@ __global__ __launch_bounds__(256) void rmsnorm_bf16_vec_kernel(const bf16_t* __r
 #pragma unroll
     for (int j = 0; j < 8; ++j) { float f = bf2f(e[j]); ss += f * f; }
   }
+  // block_sum (common.h) with its first half written out: through the helper, <4, true> is allocated 76 instead of 72 registers (one wave per SIMD less)
   ss = wave_sum_f32(ss);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
   __syncthreads();
-  const float rs = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)hidden + eps);
+  const float rs = rsqrtf(red_sum(red) / (float)hidden + eps);
   float amax = 0.f;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -93,28 +90,13 @@ __global__ __launch_bounds__(256) void rmsnorm_bf16_vec_kernel(const bf16_t* __r
     }
   }
   if constexpr (QUANT) {
-    amax = wave_max_f32(amax);
-    if ((threadIdx.x & 63) == 0) red2[threadIdx.x >> 6] = amax;
-    __syncthreads();
-    amax = fmaxf(fmaxf(red2[0], red2[1]), fmaxf(red2[2], red2[3]));
-    const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+    const float sc = e4m3_scale(block_max(amax, red2));
     const float inv = 1.0f / sc;
     if (threadIdx.x == 0) scale[row] = sc;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const int i = threadIdx.x + c * 256;
-      if (i < nchunk) {
-        const bf16_t* e = reinterpret_cast<const bf16_t*>(&v[c]);
-        float f[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(bf2f(e[j]) * inv, -448.f), 448.f);
-        int lo = 0, hi = 0;
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-        *reinterpret_cast<uint2*>(q + ats_opnd_idx<1>(pk & 1, row, (size_t)i * 8, hidden)) = make_uint2((unsigned)lo, (unsigned)hi);
-      }
+      if (i < nchunk) *reinterpret_cast<uint2*>(q + ats_opnd_idx<1>(pk & 1, row, (size_t)i * 8, hidden)) = e4m3_pk8(v[c], inv);
     }
   }
 }
@@ -170,8 +152,7 @@ __global__ void row_info_kernel(const SegTable* __restrict__ t, RowInfo* __restr
   if (row >= t->total_tok) return;
   const Seg& sg = t->seg[seg_of_row(t, row)];
   const int lt = row - sg.row0;
-  int ps = sg.pos[lt];
-  ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+  const int ps = rope_pos(sg.pos[lt], max_pos);
   out[row] = RowInfo{sg.kc, sg.vc, ps, sg.slot[lt]};
 }
 
@@ -218,8 +199,7 @@ __global__ void rope_kv_segs_kernel(T* __restrict__ qkv, const SegTable* __restr
   int row = i / (half * n_heads);
   const Seg& sg = t->seg[seg_of_row(t, row)];
   int lt = row - sg.row0;
-  int ps = sg.pos[lt];
-  ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+  const int ps = rope_pos(sg.pos[lt], max_pos);
   float c = cos_tab[(size_t)ps * half + p], s = sin_tab[(size_t)ps * half + p];
   T* r = qkv + (size_t)row * 3 * hidden;
   int d0 = h * head_dim + p, d1 = d0 + half;
@@ -227,8 +207,8 @@ __global__ void rope_kv_segs_kernel(T* __restrict__ qkv, const SegTable* __restr
   Elt<T>::store(r + d0, q0 * c - q1 * s);
   Elt<T>::store(r + d1, q1 * c + q0 * s);
   float k0 = Elt<T>::load(r + hidden + d0), k1 = Elt<T>::load(r + hidden + d1);
-  T* kc = reinterpret_cast<T*>(reinterpret_cast<char*>(sg.kc) + layer_off) + (size_t)sg.slot[lt] * hidden;
-  T* vc = reinterpret_cast<T*>(reinterpret_cast<char*>(sg.vc) + layer_off) + (size_t)sg.slot[lt] * hidden;
+  T* kc = kv_row<T>(sg.kc, layer_off, sg.slot[lt], hidden);
+  T* vc = kv_row<T>(sg.vc, layer_off, sg.slot[lt], hidden);
   Elt<T>::store(kc + d0, k0 * c - k1 * s);
   Elt<T>::store(kc + d1, k1 * c + k0 * s);
   vc[d0] = r[2 * hidden + d0];
@@ -247,15 +227,13 @@ __global__ void rope_kv_segs_vec_kernel(bf16_t* __restrict__ qkv, const SegTable
   const int row = i / (groups * n_heads);
   const Seg& sg = t->seg[seg_of_row(t, row)];
   const int lt = row - sg.row0;
-  int ps = sg.pos[lt];
-  ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+  const int ps = rope_pos(sg.pos[lt], max_pos);
   const float* cp = cos_tab + (size_t)ps * half + gi * 8;
   const float* sp = sin_tab + (size_t)ps * half + gi * 8;
   bf16_t* r = qkv + (size_t)row * 3 * hidden;
   const int d0 = h * head_dim + gi * 8, d1 = d0 + half;
-  const size_t co = (size_t)sg.slot[lt] * hidden;
-  bf16_t* kc = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(sg.kc) + layer_off) + co;
-  bf16_t* vc = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(sg.vc) + layer_off) + co;
+  bf16_t* kc = kv_row(sg.kc, layer_off, sg.slot[lt], hidden);
+  bf16_t* vc = kv_row(sg.vc, layer_off, sg.slot[lt], hidden);
   uint4 q0v = *reinterpret_cast<const uint4*>(r + d0), q1v = *reinterpret_cast<const uint4*>(r + d1);
   uint4 k0v = *reinterpret_cast<const uint4*>(r + hidden + d0), k1v = *reinterpret_cast<const uint4*>(r + hidden + d1);
   uint4 qo0, qo1, ko0, ko1;
@@ -264,10 +242,9 @@ __global__ void rope_kv_segs_vec_kernel(bf16_t* __restrict__ qkv, const SegTable
 #pragma unroll
   for (int e = 0; e < 4; ++e) {                                   // two elements per packed register
     const float ca = cp[2 * e], sa = sp[2 * e], cb = cp[2 * e + 1], sb = sp[2 * e + 1];
-    a0[e] = f2bf_pk(rope_first(bf_lo(q0[e]), bf_lo(q1[e]), ca, sa), rope_first(bf_hi(q0[e]), bf_hi(q1[e]), cb, sb));
-    a1[e] = f2bf_pk(rope_second(bf_lo(q0[e]), bf_lo(q1[e]), ca, sa), rope_second(bf_hi(q0[e]), bf_hi(q1[e]), cb, sb));
-    b0[e] = f2bf_pk(rope_first(bf_lo(k0[e]), bf_lo(k1[e]), ca, sa), rope_first(bf_hi(k0[e]), bf_hi(k1[e]), cb, sb));
-    b1[e] = f2bf_pk(rope_second(bf_lo(k0[e]), bf_lo(k1[e]), ca, sa), rope_second(bf_hi(k0[e]), bf_hi(k1[e]), cb, sb));
+    const uint2 qr = rope_pk(q0[e], q1[e], ca, sa, cb, sb), kr = rope_pk(k0[e], k1[e], ca, sa, cb, sb);
+    a0[e] = qr.x; a1[e] = qr.y;
+    b0[e] = kr.x; b1[e] = kr.y;
   }
   *reinterpret_cast<uint4*>(r + d0) = qo0; *reinterpret_cast<uint4*>(r + d1) = qo1;
   *reinterpret_cast<uint4*>(kc + d0) = ko0; *reinterpret_cast<uint4*>(kc + d1) = ko1;
@@ -275,12 +252,14 @@ __global__ void rope_kv_segs_vec_kernel(bf16_t* __restrict__ qkv, const SegTable
   *reinterpret_cast<uint4*>(vc + d1) = *reinterpret_cast<const uint4*>(r + 2 * hidden + d1);
 }
 
-// The same on the qkv projection's split-K slabs (one user's forward): sums the fp32 slabs in slab order, rounds to bf16 exactly as the
-// separate reduce pass stored them, rotates, writes q to the qkv buffer and k / v straight to the caches.
+// The same on the qkv projection's split-K slabs (one user's forward): sums the fp32 slabs in slab order (the reduce pass's, common.h: sum_slabs), rounds
+// to 16 bits as that pass stored them, rotates, writes q to the qkv buffer and k / v straight to the caches.
 __global__ void rope_kv_segs_slab_kernel(const float* __restrict__ slabs, int splits, bf16_t* __restrict__ qkv, const SegTable* __restrict__ t,
                                          const float* __restrict__ cos_tab, const float* __restrict__ sin_tab, size_t layer_off, int n_heads,
                                          int head_dim, int max_pos) {
-  // a thread owns 8 consecutive (i, i + dh/2) pairs of ONE of q / k / v (part): 4 float4 loads per slab, four slabs' loads in flight
+  // a thread owns 8 consecutive (i, i + dh/2) pairs of ONE of q / k / v (part): 4 float4 loads per slab, four slabs' loads in flight.  The order
+  // per element is sum_slabs' (slab-ascending).  Two sum_slabs<8> calls are not interleaved by the compiler: the halves are summed one after the
+  // other and the kernel measured 6-10 % slower (profiles/kernel_numerics_refactor_isa_and_speed.txt), so the two halves stay interleaved here
   const int half = head_dim >> 1, groups = half >> 3;
   const int hidden = n_heads * head_dim;
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -325,22 +304,19 @@ __global__ void rope_kv_segs_slab_kernel(const float* __restrict__ slabs, int sp
 #pragma unroll
     for (int e = 0; e < 8; e += 2) { w0[e >> 1] = f2bf_pk(lo[e], lo[e + 1]); w1[e >> 1] = f2bf_pk(hi[e], hi[e + 1]); }
   } else {
-    int ps = sg.pos[lt];
-    ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+    const int ps = rope_pos(sg.pos[lt], max_pos);
     const float* cp = cos_tab + (size_t)ps * half + gi * 8;
     const float* sp = sin_tab + (size_t)ps * half + gi * 8;
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {
-      // the projection's bf16 outputs first (what the reduce pass stored), then the rotation on those
-      const uint32_t x0 = f2bf_pk(lo[e], lo[e + 1]), x1 = f2bf_pk(hi[e], hi[e + 1]);
-      const float ca = cp[e], sa = sp[e], cb = cp[e + 1], sb = sp[e + 1];
-      w0[e >> 1] = f2bf_pk(rope_first(bf_lo(x0), bf_lo(x1), ca, sa), rope_first(bf_hi(x0), bf_hi(x1), cb, sb));
-      w1[e >> 1] = f2bf_pk(rope_second(bf_lo(x0), bf_lo(x1), ca, sa), rope_second(bf_hi(x0), bf_hi(x1), cb, sb));
+      // the projection's 16-bit outputs first (what the reduce pass stored), then the rotation on those
+      const uint2 o = rope_pk(f2bf_pk(lo[e], lo[e + 1]), f2bf_pk(hi[e], hi[e + 1]), cp[e], sp[e], cp[e + 1], sp[e + 1]);
+      w0[e >> 1] = o.x; w1[e >> 1] = o.y;
     }
   }
   bf16_t* dst;
   if (part == 0) dst = qkv + (size_t)row * 3 * hidden;
-  else dst = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(part == 1 ? sg.kc : sg.vc) + layer_off) + (size_t)sg.slot[lt] * hidden;
+  else dst = kv_row(part == 1 ? sg.kc : sg.vc, layer_off, sg.slot[lt], hidden);
   *reinterpret_cast<uint4*>(dst + d0) = o0;
   *reinterpret_cast<uint4*>(dst + d1) = o1;
 }
@@ -411,25 +387,12 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
 #pragma unroll
     for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(bf2f(e[j])));
   }
-  amax = wave_max_f32(amax);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
-  __syncthreads();
-  amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+  const float sc = e4m3_scale(block_max(amax, red));
   const float inv = 1.0f / sc;
   if (threadIdx.x == 0) scale[blockIdx.x] = sc;
   for (int c = threadIdx.x * 8; c < cols; c += 256 * 8) {
-    uint4 v = *reinterpret_cast<const uint4*>(x + ats_opnd_idx<2>(pk, blockIdx.x, c, ld));
-    const bf16_t* e = reinterpret_cast<const bf16_t*>(&v);
-    float f[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(bf2f(e[j]) * inv, -448.f), 448.f);
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-    *reinterpret_cast<uint2*>(q + ats_opnd_idx<1>(pk, blockIdx.x, c, cols)) = make_uint2((unsigned)lo, (unsigned)hi);
+    const uint4 v = *reinterpret_cast<const uint4*>(x + ats_opnd_idx<2>(pk, blockIdx.x, c, ld));
+    *reinterpret_cast<uint2*>(q + ats_opnd_idx<1>(pk, blockIdx.x, c, cols)) = e4m3_pk8(v, inv);
   }
 }
 
@@ -437,7 +400,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
 // workgroup per row fetches each line twice (through two L2s, the neighbours of a pair landing on different XCDs) -- 2.9 TB/s of algorithmic
 // bytes in the fp8 step's profile.  Here a thread owns 16-byte chunk (tid & 7) of line (tid >> 3) + 32 i: chunks 0-3 are the even row's, 4-7 the
 // odd row's, so its row is fixed; the pair stays in registers between the maximum and the conversion (read once), and 16 consecutive threads
-// fill one whole 128-byte line of the packed e4m3 output.  Bit-identical to quant_rows_fp8_kernel.
+// fill one whole 128-byte line of the packed e4m3 output.  Same rule as quant_rows_fp8_kernel (common.h: e4m3_scale / e4m3_pk8).
 template <int NC>
 __global__ __launch_bounds__(256) void quant_row_pairs_fp8_kernel(const bf16_t* __restrict__ x, int rows, int cols, unsigned char* __restrict__ q,
                                                                   float* __restrict__ scale) {
@@ -456,10 +419,9 @@ __global__ __launch_bounds__(256) void quant_row_pairs_fp8_kernel(const bf16_t* 
     for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(bf2f(e[j])));
   }
   const float m0 = wave_max_f32(odd ? 0.f : amax), m1 = wave_max_f32(odd ? amax : 0.f);
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = m0; red[1][threadIdx.x >> 6] = m1; }
+  block_put(m0, red[0]); block_put(m1, red[1]);                   // two maxima behind one barrier
   __syncthreads();
-  amax = fmaxf(fmaxf(red[odd][0], red[odd][1]), fmaxf(red[odd][2], red[odd][3]));
-  const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+  const float sc = e4m3_scale(red_max(red[odd]));
   const float inv = 1.0f / sc;
   const int row = 2 * blockIdx.x + odd;
   if ((threadIdx.x & 3) == 0 && l0 == 0 && row < rows) scale[row] = sc;      // threads 0 and 4
@@ -469,17 +431,8 @@ __global__ __launch_bounds__(256) void quant_row_pairs_fp8_kernel(const bf16_t* 
   for (int i = 0; i < NC; ++i) {
     const int line = l0 + 32 * i;
     if (line < n_lines && row < rows) {                            // (the pad row of an odd count is read, never written)
-      const bf16_t* e = reinterpret_cast<const bf16_t*>(&v[i]);
-      float f[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(bf2f(e[j]) * inv, -448.f), 448.f);
-      int lo = 0, hi = 0;
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
       const int col = line * 32 + (sub & 3) * 8;                   // first of this chunk's 8 columns
-      *reinterpret_cast<uint2*>(qp + (size_t)(col >> 6) * 128 + odd * 64 + (col & 63)) = make_uint2((unsigned)lo, (unsigned)hi);
+      *reinterpret_cast<uint2*>(qp + (size_t)(col >> 6) * 128 + odd * 64 + (col & 63)) = e4m3_pk8(v[i], inv);
     }
   }
 }

@@ -277,10 +277,7 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const T* __restrict__ A,
         for (int r = 0; r < 4; ++r) {
           int gm = wrow0 + i * 16 + crow + r, gn = wcol0 + j * 16;      // gate group start (multiple of 32)
           if (gm < M && gn < N) {
-            float g = acc[i][j][r], u = acc[i][j + 1][r];
-            if constexpr (sizeof(T) == 2) { g = bf2f(f2bf(g)); u = bf2f(f2bf(u)); }
-            float s = ats_silu<sizeof(T) == 4>(g);
-            Elt<T>::store(C + ats_opnd_idx<sizeof(T)>(pk, gm, (gn >> 1) + ccol, ldc), s * u);
+            Elt<T>::store(C + ats_opnd_idx<sizeof(T)>(pk, gm, (gn >> 1) + ccol, ldc), swiglu<T>(acc[i][j][r], acc[i][j + 1][r]));
           }
         }
   } else {
@@ -296,40 +293,12 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const T* __restrict__ A,
             if constexpr (EPI == EPI_F32) {
               reinterpret_cast<float*>(Cv)[(size_t)gm * ldc + gn] = v;
             } else if constexpr (EPI == EPI_RESID) {
-              T* C = reinterpret_cast<T*>(Cv);
-              if constexpr (sizeof(T) == 2) v = bf2f(f2bf(v));           // HF: o_proj output is bf16 before the add
-              Elt<T>::store(C + (size_t)gm * ldc + gn, Elt<T>::load(C + (size_t)gm * ldc + gn) + v);
+              resid_add(reinterpret_cast<T*>(Cv) + (size_t)gm * ldc + gn, v);
             } else {
               Elt<T>::store(reinterpret_cast<T*>(Cv) + (size_t)gm * ldc + gn, v);
             }
           }
         }
-  }
-}
-
-// V consecutive floats of every slab, summed in slab order.  The loads of four slabs are issued before their adds: with a runtime
-// slab count the plain loop waited out one memory round trip per slab (8 slabs = 8 x ~2 us; seen as 19 us reduce kernels behind
-// 15 us GEMMs in the one-user trace).
-template <int V>
-__device__ __forceinline__ void sum_slabs(const float* __restrict__ p, size_t slab_stride, int splits, float (&acc)[V]) {
-  typedef float vf __attribute__((ext_vector_type(V)));
-#pragma unroll
-  for (int i = 0; i < V; ++i) acc[i] = 0.f;
-  int z = 0;
-  for (; z + 4 <= splits; z += 4) {
-    vf q[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) q[u] = *reinterpret_cast<const vf*>(p + (size_t)(z + u) * slab_stride);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-#pragma unroll
-      for (int i = 0; i < V; ++i) acc[i] += q[u][i];
-    }
-  }
-  for (; z < splits; ++z) {
-    vf q = *reinterpret_cast<const vf*>(p + (size_t)z * slab_stride);
-#pragma unroll
-    for (int i = 0; i < V; ++i) acc[i] += q[i];
   }
 }
 
@@ -352,10 +321,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ partial, void* __
     T* out = reinterpret_cast<T*>(Cv) + ats_opnd_idx<sizeof(T)>(pk, m, o, ldc);     // the SwiGLU output is the down projection's operand (V <= 4 stays inside a k-block)
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      float gj = g[j], uj = u[j];
-      if constexpr (sizeof(T) == 2) { gj = bf2f(f2bf(gj)); uj = bf2f(f2bf(uj)); }
-      float sj = ats_silu<sizeof(T) == 4>(gj);
-      Elt<T>::store(out + j, sj * uj);
+      Elt<T>::store(out + j, swiglu<T>(g[j], u[j]));
     }
   } else {
     size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
@@ -368,10 +334,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ partial, void* __
       if constexpr (EPI == EPI_F32) {
         reinterpret_cast<float*>(Cv)[(size_t)m * ldc + n + j] = v[j];
       } else if constexpr (EPI == EPI_RESID) {
-        T* C = reinterpret_cast<T*>(Cv);
-        float x = v[j];
-        if constexpr (sizeof(T) == 2) x = bf2f(f2bf(x));
-        Elt<T>::store(C + (size_t)m * ldc + n + j, Elt<T>::load(C + (size_t)m * ldc + n + j) + x);
+        resid_add(reinterpret_cast<T*>(Cv) + (size_t)m * ldc + n + j, v[j]);
       } else {
         Elt<T>::store(reinterpret_cast<T*>(Cv) + (size_t)m * ldc + n + j, v[j]);
       }
@@ -441,12 +404,8 @@ __device__ __forceinline__ void big_epilogue(f32x4_t (&acc)[NA][MT2], void* __re
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
               const uint4 p = pack8(4 * q + 2 * h, j), r = rs[h][j];
-              uint4 o;
-              o.x = f2bf_pk(bf_lo(r.x) + bf_lo(p.x), bf_hi(r.x) + bf_hi(p.x));
-              o.y = f2bf_pk(bf_lo(r.y) + bf_lo(p.y), bf_hi(r.y) + bf_hi(p.y));
-              o.z = f2bf_pk(bf_lo(r.z) + bf_lo(p.z), bf_hi(r.z) + bf_hi(p.z));
-              o.w = f2bf_pk(bf_lo(r.w) + bf_lo(p.w), bf_hi(r.w) + bf_hi(p.w));
-              epi_store16(Cb + (size_t)gm * ldc + col8(4 * q + 2 * h), o);
+              epi_store16(Cb + (size_t)gm * ldc + col8(4 * q + 2 * h),
+                          make_uint4(resid_pk(r.x, p.x), resid_pk(r.y, p.y), resid_pk(r.z, p.z), resid_pk(r.w, p.w)));
             }
           }
         }
@@ -467,26 +426,16 @@ __device__ __forceinline__ void big_epilogue(f32x4_t (&acc)[NA][MT2], void* __re
       const int gm = m0 + wm * (MT2 * 16) + j * 16 + lq;
       if (gm >= M) continue;
 #pragma unroll
-      for (int i = 0; i < NA; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int gn = nw + (i >> 2) * 64 + g * 16 + (i & 3) * 4 + r;
-          if (gn >= N) continue;
-          bf16_t* C = Cb + (size_t)gm * ldc + gn;
-          float v = acc[i][j][r];
-          if constexpr (EPI == EPI_RESID) v = bf2f(*C) + bf2f(f2bf(v));
-          *C = f2bf(v);
-        }
+      for (int i = 0; i < NA; ++i) {
+        const int gn = nw + (i >> 2) * 64 + g * 16 + (i & 3) * 4;
+        store4<EPI == EPI_RESID>(Cb + (size_t)gm * ldc + gn, acc[i][j], gn, N, false);
+      }
     }
   } else if constexpr (EPI == EPI_SWIGLU) {
-    // lane (., g) owns outputs q*32 + g*8 + [0, 8) of the wave's NA*8: gate in tiles 4q and 4q+2, up in 4q+1 and 4q+3.  gate and up are rounded to
-    // bf16 first (the reference's two projections are bf16 tensors), packed conversions throughout
+    // lane (., g) owns outputs q*32 + g*8 + [0, 8) of the wave's NA*8: gate in tiles 4q and 4q+2, up in 4q+1 and 4q+3
     bf16_t* C = reinterpret_cast<bf16_t*>(Cv);
     const bool vec16 = (ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(Cv) & 15) == 0;
-    auto silu_mul = [&](int ig, int j, int r) {
-      const uint32_t gp = f2bf_pk(acc[ig][j][r], acc[ig][j][r + 1]), upk = f2bf_pk(acc[ig + 1][j][r], acc[ig + 1][j][r + 1]);
-      return f2bf_pk(ats_silu<false>(bf_lo(gp)) * bf_lo(upk), ats_silu<false>(bf_hi(gp)) * bf_hi(upk));
-    };
+    auto silu_mul = [&](int ig, int j, int r) { return swiglu_pk(acc[ig][j][r], acc[ig][j][r + 1], acc[ig + 1][j][r], acc[ig + 1][j][r + 1]); };
 #pragma unroll
     for (int j = 0; j < MT2; ++j) {
       const int gm = m0 + wm * (MT2 * 16) + j * 16 + lq;
@@ -512,11 +461,7 @@ __device__ __forceinline__ void big_epilogue(f32x4_t (&acc)[NA][MT2], void* __re
       for (int i = 0; i < NA; ++i) {
         const int gn = nw + i * 16 + g * 4;
         if (gn >= N) continue;
-        float* C = reinterpret_cast<float*>(Cv) + (size_t)gm * ldc + gn;
-        if (gn + 3 < N && vec) *reinterpret_cast<float4*>(C) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (gn + r < N) C[r] = acc[i][j][r];
+        store4(reinterpret_cast<float*>(Cv) + (size_t)gm * ldc + gn, acc[i][j], gn, N, vec);
       }
     }
   }
@@ -527,8 +472,8 @@ __device__ __forceinline__ void big_epilogue(f32x4_t (&acc)[NA][MT2], void* __re
 // lies inside one of q / k / v and holds two heads of head_dim 128; wave (wn, wm) accumulated the half (wn & 1) of head (wn >> 1) for the
 // rows of wm.  v tiles go to the cache as they are.  q / k tiles pass through the (drained) ring's LDS as bf16 and are re-divided by
 // ROWS: a wave then rotates both halves of both heads for a quarter of wm's rows, so each (cos, sin) is fetched once per row and pair
-// index instead of once per wave that holds the column (4 x fewer table bytes through the L1 -- the first form's cost).  Numerics are
-// those of ats_gemm + rope_kv_segs_vec_kernel: the projection rounded to bf16, the rotation in fp32 on those values, one more rounding.
+// index instead of once per wave that holds the column (4 x fewer table bytes through the L1 -- the first form's cost).  Numerics:
+// common.h, rope_pk (the separate pass's).
 template <int NA, int MT2>
 __device__ __forceinline__ void qkv_rope_epilogue(f32x4_t (&acc)[NA][MT2], bf16_t* __restrict__ qkv, int M, int ldc, int m0, int n0,
                                                   int wave, int lane, const RopeEpi& rp, unsigned char* smem) {
@@ -545,7 +490,7 @@ __device__ __forceinline__ void qkv_rope_epilogue(f32x4_t (&acc)[NA][MT2], bf16_
       const int row = m0 + wm * (MT2 * 16) + j * 16 + lq;
       if (row >= M) continue;
       const RowInfo ri = rp.rows[row];
-      bf16_t* dst = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ri.vc) + rp.layer_off) + (size_t)ri.slot * H + fsec + wn * 64 + g * 16;
+      bf16_t* dst = kv_row(ri.vc, rp.layer_off, ri.slot, H) + fsec + wn * 64 + g * 16;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const uint2 a = pack4(2 * h, j), b = pack4(2 * h + 1, j);
@@ -568,8 +513,7 @@ __device__ __forceinline__ void qkv_rope_epilogue(f32x4_t (&acc)[NA][MT2], bf16_
     const int row = m0 + wm * (MT2 * 16) + j * 16 + lq;
     if (row >= M) continue;
     const RowInfo ri = rp.rows[row];
-    bf16_t* dst = (sec == 0 ? qkv + (size_t)row * ldc
-                            : reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ri.kc) + rp.layer_off) + (size_t)ri.slot * H) + fsec + g * 16;
+    bf16_t* dst = (sec == 0 ? qkv + (size_t)row * ldc : kv_row(ri.kc, rp.layer_off, ri.slot, H)) + fsec + g * 16;
     const float* cp = rp.cos_tab + (size_t)ri.pos * 64 + g * 16;  // pair index inside the head: g * 16 + i * 4 + r
     const float* sp = rp.sin_tab + (size_t)ri.pos * 64 + g * 16;
 #pragma unroll
@@ -579,19 +523,16 @@ __device__ __forceinline__ void qkv_rope_epilogue(f32x4_t (&acc)[NA][MT2], bf16_
       for (int e = 0; e < 2; ++e) { c[e] = *reinterpret_cast<const float4*>(cp + (2 * h + e) * 4); s[e] = *reinterpret_cast<const float4*>(sp + (2 * h + e) * 4); }
 #pragma unroll
       for (int hd = 0; hd < 2; ++hd) {
-        uint32_t o0[4], o1[4];
+        uint2 o0[2], o1[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const int i = 2 * h + e;
           const uint2 x = ex[((((hd * 2 + 0) * 2 + wm) * MT2 + j) * NA + i) * 64 + lane];      // x[d]      (wave wn = 2 hd)
           const uint2 y = ex[((((hd * 2 + 1) * 2 + wm) * MT2 + j) * NA + i) * 64 + lane];      // x[d + 64] (wave wn = 2 hd + 1)
-          o0[2 * e] = f2bf_pk(rope_first(bf_lo(x.x), bf_lo(y.x), c[e].x, s[e].x), rope_first(bf_hi(x.x), bf_hi(y.x), c[e].y, s[e].y));
-          o0[2 * e + 1] = f2bf_pk(rope_first(bf_lo(x.y), bf_lo(y.y), c[e].z, s[e].z), rope_first(bf_hi(x.y), bf_hi(y.y), c[e].w, s[e].w));
-          o1[2 * e] = f2bf_pk(rope_second(bf_lo(x.x), bf_lo(y.x), c[e].x, s[e].x), rope_second(bf_hi(x.x), bf_hi(y.x), c[e].y, s[e].y));
-          o1[2 * e + 1] = f2bf_pk(rope_second(bf_lo(x.y), bf_lo(y.y), c[e].z, s[e].z), rope_second(bf_hi(x.y), bf_hi(y.y), c[e].w, s[e].w));
+          rope_pk(x, y, c[e], s[e], o0[e], o1[e]);
         }
-        epi_store16(dst + hd * 128 + h * 8, make_uint4(o0[0], o0[1], o0[2], o0[3]));
-        epi_store16(dst + hd * 128 + 64 + h * 8, make_uint4(o1[0], o1[1], o1[2], o1[3]));
+        epi_store16(dst + hd * 128 + h * 8, make_uint4(o0[0].x, o0[0].y, o0[1].x, o0[1].y));
+        epi_store16(dst + hd * 128 + 64 + h * 8, make_uint4(o1[0].x, o1[0].y, o1[1].x, o1[1].y));
       }
     }
   }
@@ -1021,10 +962,7 @@ __device__ __forceinline__ void mx_epilogue(f32x16_t (&acc)[TA][TB], void* __res
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const uint32_t p0 = f2bf_pk(acc[it][jt][4 * q], acc[it][jt][4 * q + 1]), p1 = f2bf_pk(acc[it][jt][4 * q + 2], acc[it][jt][4 * q + 3]);
-            uint2 o;
-            o.x = f2bf_pk(bf_lo(rs[it][jt][q].x) + bf_lo(p0), bf_hi(rs[it][jt][q].x) + bf_hi(p0));
-            o.y = f2bf_pk(bf_lo(rs[it][jt][q].y) + bf_lo(p1), bf_hi(rs[it][jt][q].y) + bf_hi(p1));
-            *reinterpret_cast<uint2*>(Cb + (size_t)gm * ldc + n0w + it * 32 + 8 * q + 4 * h) = o;
+            *reinterpret_cast<uint2*>(Cb + (size_t)gm * ldc + n0w + it * 32 + 8 * q + 4 * h) = make_uint2(resid_pk(rs[it][jt][q].x, p0), resid_pk(rs[it][jt][q].y, p1));
           }
         }
       }
@@ -1045,51 +983,18 @@ __device__ __forceinline__ void mx_epilogue(f32x16_t (&acc)[TA][TB], void* __res
         if (gn0 >= N) continue;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-          uint2 o;
-#pragma unroll
-          for (int r = 0; r < 4; r += 2) {
-            const uint32_t gp = f2bf_pk(acc[it][jt][4 * q + r], acc[it][jt][4 * q + r + 1]);
-            const uint32_t upk = f2bf_pk(acc[it][jt][4 * (q + 2) + r], acc[it][jt][4 * (q + 2) + r + 1]);
-            const float g0 = bf_lo(gp), g1 = bf_hi(gp);
-            const uint32_t res = f2bf_pk(ats_silu<false>(g0) * bf_lo(upk), ats_silu<false>(g1) * bf_hi(upk));
-            if (r == 0) o.x = res; else o.y = res;
-          }
-          *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (gn0 >> 1) + 8 * q + 4 * h, ldc)) = o;      // the down projection's operand
+          const f32x16_t& t = acc[it][jt];
+          *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (gn0 >> 1) + 8 * q + 4 * h, ldc)) =      // the down projection's operand
+              make_uint2(swiglu_pk(t[4 * q], t[4 * q + 1], t[4 * q + 8], t[4 * q + 9]), swiglu_pk(t[4 * q + 2], t[4 * q + 3], t[4 * q + 10], t[4 * q + 11]));
         }
       } else {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int gn = n0w + it * 32 + 8 * q + 4 * h;
           if (gn >= N) continue;
-          const float v0 = acc[it][jt][4 * q], v1 = acc[it][jt][4 * q + 1], v2 = acc[it][jt][4 * q + 2], v3 = acc[it][jt][4 * q + 3];
-          if constexpr (EPI == EPI_F32) {
-            float* C = reinterpret_cast<float*>(Cv) + (size_t)gm * ldc + gn;
-            if (gn + 3 < N && vec) *reinterpret_cast<float4*>(C) = make_float4(v0, v1, v2, v3);
-            else { const float vv[4] = {v0, v1, v2, v3};
-#pragma unroll
-              for (int r = 0; r < 4; ++r) if (gn + r < N) C[r] = vv[r]; }
-          } else {
-            bf16_t* C = reinterpret_cast<bf16_t*>(Cv) + (size_t)gm * ldc + gn;
-            if (gn + 3 < N && vec) {
-              uint2 o;
-              const uint32_t p0 = f2bf_pk(v0, v1), p1 = f2bf_pk(v2, v3);
-              if constexpr (EPI == EPI_RESID) {
-                const uint2 rs = *reinterpret_cast<const uint2*>(C);
-                o.x = f2bf_pk(bf_lo(rs.x) + bf_lo(p0), bf_hi(rs.x) + bf_hi(p0));
-                o.y = f2bf_pk(bf_lo(rs.y) + bf_lo(p1), bf_hi(rs.y) + bf_hi(p1));
-              } else { o.x = p0; o.y = p1; }
-              *reinterpret_cast<uint2*>(C) = o;
-            } else {
-              const float vv[4] = {v0, v1, v2, v3};
-#pragma unroll
-              for (int r = 0; r < 4; ++r)
-                if (gn + r < N) {
-                  float v = vv[r];
-                  if constexpr (EPI == EPI_RESID) v = bf2f(C[r]) + bf2f(f2bf(v));
-                  C[r] = f2bf(v);
-                }
-            }
-          }
+          const f32x4_t v = {acc[it][jt][4 * q], acc[it][jt][4 * q + 1], acc[it][jt][4 * q + 2], acc[it][jt][4 * q + 3]};
+          if constexpr (EPI == EPI_F32) store4(reinterpret_cast<float*>(Cv) + (size_t)gm * ldc + gn, v, gn, N, vec);
+          else store4<EPI == EPI_RESID>(reinterpret_cast<bf16_t*>(Cv) + (size_t)gm * ldc + gn, v, gn, N, vec);
         }
       }
     }
@@ -1114,7 +1019,7 @@ __device__ __forceinline__ void mx_qkv_rope_epilogue(f32x16_t (&acc)[TA][TB], bf
       const int row = m0w + jt * 32 + r32;
       if (row >= M) continue;
       const RowInfo ri = rp.rows[row];
-      bf16_t* dst = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ri.vc) + rp.layer_off) + (size_t)ri.slot * H + fsec + wn * 64 + 4 * h;
+      bf16_t* dst = kv_row(ri.vc, rp.layer_off, ri.slot, H) + fsec + wn * 64 + 4 * h;
 #pragma unroll
       for (int it = 0; it < TA; ++it) {
         mx_scale_tile<TA, TB>(acc[it][jt], sx, sw, row, n0w + it * 32, h, M, N);
@@ -1146,8 +1051,7 @@ __device__ __forceinline__ void mx_qkv_rope_epilogue(f32x16_t (&acc)[TA][TB], bf
     const int row = m0w + jt * 32 + r32;
     if (row >= M) continue;
     const RowInfo ri = rp.rows[row];
-    bf16_t* dst = (sec == 0 ? qkv + (size_t)row * ldc
-                            : reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ri.kc) + rp.layer_off) + (size_t)ri.slot * H) + fsec + it * 32 + 4 * h;
+    bf16_t* dst = (sec == 0 ? qkv + (size_t)row * ldc : kv_row(ri.kc, rp.layer_off, ri.slot, H)) + fsec + it * 32 + 4 * h;
     const float* cp = rp.cos_tab + (size_t)ri.pos * 64 + it * 32 + 4 * h;   // pair index inside the head: it * 32 + 8 q + 4 h + r
     const float* sp = rp.sin_tab + (size_t)ri.pos * 64 + it * 32 + 4 * h;
 #pragma unroll
@@ -1158,10 +1062,7 @@ __device__ __forceinline__ void mx_qkv_rope_epilogue(f32x16_t (&acc)[TA][TB], bf
         const uint2 x = ex[(((((hd * 2 + 0) * 2 + wm) * TB + jt) * TA + it) * 4 + q) * 64 + lane];      // x[d]      (wave wn = 2 hd)
         const uint2 y = ex[(((((hd * 2 + 1) * 2 + wm) * TB + jt) * TA + it) * 4 + q) * 64 + lane];      // x[d + 64] (wave wn = 2 hd + 1)
         uint2 o0, o1;
-        o0.x = f2bf_pk(rope_first(bf_lo(x.x), bf_lo(y.x), c.x, s.x), rope_first(bf_hi(x.x), bf_hi(y.x), c.y, s.y));
-        o0.y = f2bf_pk(rope_first(bf_lo(x.y), bf_lo(y.y), c.z, s.z), rope_first(bf_hi(x.y), bf_hi(y.y), c.w, s.w));
-        o1.x = f2bf_pk(rope_second(bf_lo(x.x), bf_lo(y.x), c.x, s.x), rope_second(bf_hi(x.x), bf_hi(y.x), c.y, s.y));
-        o1.y = f2bf_pk(rope_second(bf_lo(x.y), bf_lo(y.y), c.z, s.z), rope_second(bf_hi(x.y), bf_hi(y.y), c.w, s.w));
+        rope_pk(x, y, c, s, o0, o1);
         *reinterpret_cast<uint2*>(dst + hd * 128 + 8 * q) = o0;
         *reinterpret_cast<uint2*>(dst + hd * 128 + 64 + 8 * q) = o1;
       }
@@ -1433,10 +1334,10 @@ int launch_big_lse(const bf16_t* x, const bf16_t* w, float* c, int m, int n, int
 // split-K reduce + residual add + RMSNorm of the updated row, one workgroup per token row:
 //   h[m][:] += sum_z partial[z][m][:]        (the o_proj / down_proj epilogue)
 //   xn[m][:] = w * (h[m][:] * rsqrt(mean(h^2) + eps))   (the NEXT op's input norm)
-// Saves one launch and one read of h per projection; numerics identical to the unfused pair
-// (statistics are taken from the stored, dtype-rounded h).
-// QUANT (the consumer is a W8A8 projection, one user's fp8 forwards): the normalised row also leaves as OCP e4m3 with its per-token scale --
-// what ats_rmsnorm_quant_fp8 makes of the same h, bit for bit (amax over the bf16-rounded outputs, scale = amax / 448) --; xn may then be null.
+// Saves one launch and one read of h per projection; the rules of the unfused pair (common.h: sum_slabs, resid_add, block_sum; statistics are
+// taken from the stored, dtype-rounded h).
+// QUANT (the consumer is a W8A8 projection, one user's fp8 forwards): the normalised row also leaves as OCP e4m3 with its per-token scale
+// (common.h: e4m3_scale / e4m3_pk4 on the 16-bit-rounded outputs); xn may then be null.
 template <typename T, int NPT, int V, bool QUANT = false>
 __global__ __launch_bounds__(1024) void splitk_resid_rmsnorm_kernel(const float* __restrict__ partial, T* __restrict__ h,
                                                                     const T* __restrict__ norm_w, T* __restrict__ xn, int M, int N,
@@ -1463,23 +1364,13 @@ __global__ __launch_bounds__(1024) void splitk_resid_rmsnorm_kernel(const float*
     if (n < N) {
 #pragma unroll
       for (int j = 0; j < V; ++j) {
-        float v = vals[i * V + j];
-        if constexpr (sizeof(T) == 2) v = bf2f(f2bf(v));
-        v = Elt<T>::load(h + (size_t)m * ldh + n + j) + v;
-        Elt<T>::store(h + (size_t)m * ldh + n + j, v);
-        if constexpr (sizeof(T) == 2) v = bf2f(f2bf(v));
+        const float v = resid_add(h + (size_t)m * ldh + n + j, vals[i * V + j]);      // the stored, rounded h: what the statistics are taken from
         ss += v * v;
         vals[i * V + j] = v;
       }
     }
   }
-  ss = wave_sum_f32(ss);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-  __syncthreads();
-  float tot = 0.f;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) tot += red[w];
-  const float rs = rsqrtf(tot / (float)N + eps);
+  const float rs = rsqrtf(block_sum(ss, red) / (float)N + eps);
   float amax = 0.f;
 #pragma unroll
   for (int i = 0; i < NPT / V; ++i) {
@@ -1488,11 +1379,9 @@ __global__ __launch_bounds__(1024) void splitk_resid_rmsnorm_kernel(const float*
       T* xo = xn + ats_opnd_idx<sizeof(T)>(pk, m, n, N);      // xn: the next projection's operand (V <= 4 consecutive columns stay inside one 64-byte block)
 #pragma unroll
       for (int j = 0; j < V; ++j) {
-        float v = vals[i * V + j] * rs;
-        if constexpr (sizeof(T) == 2) v = bf2f(f2bf(v));
-        v = Elt<T>::load(norm_w + n + j) * v;
+        float v = Elt<T>::load(norm_w + n + j) * round_elt<T>(vals[i * V + j] * rs);
         if constexpr (QUANT) {
-          v = bf2f(f2bf(v));                                  // the stored, 16-bit-rounded output is what gets quantised
+          v = round_elt<T>(v);                                 // the stored, 16-bit-rounded output is what gets quantised
           vals[i * V + j] = v;
           amax = fmaxf(amax, fabsf(v));
           if (xn) Elt<T>::store(xo + j, v);
@@ -1502,28 +1391,15 @@ __global__ __launch_bounds__(1024) void splitk_resid_rmsnorm_kernel(const float*
   }
   if constexpr (QUANT) {
     static_assert(V == 4, "four e4m3 bytes per store");
-    amax = wave_max_f32(amax);
     __syncthreads();                                          // red[] was read by everyone above
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
-    __syncthreads();
-    amax = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) amax = fmaxf(amax, red[w]);
-    const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+    const float sc = e4m3_scale(block_max(amax, red));
     const float inv = 1.0f / sc;
     if (threadIdx.x == 0) qscale[m] = sc;
 #pragma unroll
     for (int i = 0; i < NPT / V; ++i) {
       const int n = (threadIdx.x + i * 1024) * V;
-      if (n < N) {
-        float f[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) f[j] = fminf(fmaxf(vals[i * V + j] * inv, -448.f), 448.f);
-        int w4 = 0;
-        w4 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w4, false);
-        w4 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w4, true);
-        *reinterpret_cast<int*>(q + ats_opnd_idx<1>(pk, m, n, N)) = w4;
-      }
+      if (n < N)
+        *reinterpret_cast<uint32_t*>(q + ats_opnd_idx<1>(pk, m, n, N)) = e4m3_pk4(vals[i * V], vals[i * V + 1], vals[i * V + 2], vals[i * V + 3], inv);
     }
   }
 }
@@ -1714,19 +1590,15 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
       const uint32_t a01 = f2bf_pk(acc[0][j][0], acc[0][j][1]), a23 = f2bf_pk(acc[0][j][2], acc[0][j][3]);     // x[d]: the projection's 16-bit outputs
       const uint32_t b01 = f2bf_pk(acc[1][j][0], acc[1][j][1]), b23 = f2bf_pk(acc[1][j][2], acc[1][j][3]);     // x[d + 64]
       if (sec == 2) {
-        bf16_t* dst = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ri.vc) + rope.layer_off) + (size_t)ri.slot * H + fsec + d0;
+        bf16_t* dst = kv_row(ri.vc, rope.layer_off, ri.slot, H) + fsec + d0;
         *reinterpret_cast<uint2*>(dst) = make_uint2(a01, a23);
         *reinterpret_cast<uint2*>(dst + 64) = make_uint2(b01, b23);
       } else {
         const float4 c = *reinterpret_cast<const float4*>(rope.cos_tab + (size_t)ri.pos * 64 + d0);
         const float4 sn = *reinterpret_cast<const float4*>(rope.sin_tab + (size_t)ri.pos * 64 + d0);
         uint2 o0, o1;
-        o0.x = f2bf_pk(rope_first(bf_lo(a01), bf_lo(b01), c.x, sn.x), rope_first(bf_hi(a01), bf_hi(b01), c.y, sn.y));
-        o0.y = f2bf_pk(rope_first(bf_lo(a23), bf_lo(b23), c.z, sn.z), rope_first(bf_hi(a23), bf_hi(b23), c.w, sn.w));
-        o1.x = f2bf_pk(rope_second(bf_lo(a01), bf_lo(b01), c.x, sn.x), rope_second(bf_hi(a01), bf_hi(b01), c.y, sn.y));
-        o1.y = f2bf_pk(rope_second(bf_lo(a23), bf_lo(b23), c.z, sn.z), rope_second(bf_hi(a23), bf_hi(b23), c.w, sn.w));
-        bf16_t* dst = (sec == 0 ? qkv + (size_t)gm * ldc
-                                : reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ri.kc) + rope.layer_off) + (size_t)ri.slot * H) + fsec + d0;
+        rope_pk(make_uint2(a01, a23), make_uint2(b01, b23), c, sn, o0, o1);
+        bf16_t* dst = (sec == 0 ? qkv + (size_t)gm * ldc : kv_row(ri.kc, rope.layer_off, ri.slot, H)) + fsec + d0;
         *reinterpret_cast<uint2*>(dst) = o0;
         *reinterpret_cast<uint2*>(dst + 64) = o1;
       }
@@ -1743,11 +1615,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
       for (int i = 0; i < NI; ++i) {
         const int gn = nw + i * 16 + g * 4;
         if (gn >= N) continue;
-        float* C = P + (size_t)gm * N + gn;
-        if (gn + 3 < N && (N & 3) == 0) *reinterpret_cast<float4*>(C) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (gn + r < N) C[r] = acc[i][j][r];
+        store4(P + (size_t)gm * N + gn, acc[i][j], gn, N, (N & 3) == 0);
       }
     }
     return;
@@ -1762,13 +1630,9 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
       for (int q = 0; q < NI / 2; ++q) {
         const int gn = nw + q * 32 + g * 4;                            // gate row of r = 0
         if (gn + 16 >= N) continue;                                    // N % 32 == 0: the whole (gate, up) group is inside N or not at all
-        uint32_t o[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const uint32_t gp = f2bf_pk(acc[2 * q][j][2 * h], acc[2 * q][j][2 * h + 1]), up = f2bf_pk(acc[2 * q + 1][j][2 * h], acc[2 * q + 1][j][2 * h + 1]);
-          o[h] = f2bf_pk(ats_silu<false>(bf_lo(gp)) * bf_lo(up), ats_silu<false>(bf_hi(gp)) * bf_hi(up));
-        }
-        *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (nw >> 1) + q * 16 + g * 4, ldc)) = make_uint2(o[0], o[1]);
+        const f32x4_t &ga = acc[2 * q][j], &ua = acc[2 * q + 1][j];
+        *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (nw >> 1) + q * 16 + g * 4, ldc)) =
+            make_uint2(swiglu_pk(ga[0], ga[1], ua[0], ua[1]), swiglu_pk(ga[2], ga[3], ua[2], ua[3]));
       }
     } else {
 #pragma unroll
@@ -1776,18 +1640,10 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
         const int gn = nw + i * 16 + g * 4;
         if (gn >= N) continue;
         if constexpr (EPI == EPI_F32) {
-          float* C = reinterpret_cast<float*>(Cv) + (size_t)gm * ldc + gn;
-          if (gn + 3 < N && (ldc & 3) == 0) *reinterpret_cast<float4*>(C) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-          else
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (gn + r < N) C[r] = acc[i][j][r];
+          store4(reinterpret_cast<float*>(Cv) + (size_t)gm * ldc + gn, acc[i][j], gn, N, (ldc & 3) == 0);
         } else {
           static_assert(EPI == EPI_STORE || EPI == EPI_SWIGLU || EPI == EPI_F32 || EPI == EPI_QKV_ROPE, "store / fp32 / SwiGLU (the RoPE epilogue returned above)");
-          bf16_t* C = reinterpret_cast<bf16_t*>(Cv) + (size_t)gm * ldc + gn;
-          if (gn + 3 < N && (ldc & 3) == 0) *reinterpret_cast<uint2*>(C) = make_uint2(f2bf_pk(acc[i][j][0], acc[i][j][1]), f2bf_pk(acc[i][j][2], acc[i][j][3]));
-          else
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (gn + r < N) C[r] = f2bf(acc[i][j][r]);
+          store4(reinterpret_cast<bf16_t*>(Cv) + (size_t)gm * ldc + gn, acc[i][j], gn, N, (ldc & 3) == 0);
         }
       }
     }
@@ -2585,21 +2441,13 @@ __global__ __launch_bounds__(256) void gemm_w4a8_kernel(const unsigned char* __r
       for (int i = 0; i < NI; ++i) {
         const int gn = nw + i * 16 + g * 4;
         if (gn >= N) continue;
-        if (gn + 3 < N && (ld & 3) == 0) *reinterpret_cast<float4*>(C + gn) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (gn + r < N) C[gn + r] = acc[i][j][r];
+        store4(C + gn, acc[i][j], gn, N, (ld & 3) == 0);
       }
     } else if constexpr (EPI == EPI_SWIGLU) {                          // gate rows 32b .. 32b+15, up rows 32b+16 .. 32b+31 (the packed gate_up order)
       bf16_t* C = reinterpret_cast<bf16_t*>(Cv);
       if (nw + 16 >= N) continue;                                      // N % 32 == 0: the whole (gate, up) group is inside N or not at all
-      uint32_t o[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const uint32_t gp = f2bf_pk(acc[0][j][2 * h], acc[0][j][2 * h + 1]), up = f2bf_pk(acc[1][j][2 * h], acc[1][j][2 * h + 1]);
-        o[h] = f2bf_pk(ats_silu<false>(bf_lo(gp)) * bf_lo(up), ats_silu<false>(bf_hi(gp)) * bf_hi(up));
-      }
-      *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (nw >> 1) + g * 4, ldc)) = make_uint2(o[0], o[1]);
+      const f32x4_t &ga = acc[0][j], &ua = acc[1][j];
+      *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (nw >> 1) + g * 4, ldc)) = make_uint2(swiglu_pk(ga[0], ga[1], ua[0], ua[1]), swiglu_pk(ga[2], ga[3], ua[2], ua[3]));
     } else {
       static_assert(EPI == EPI_STORE || EPI == EPI_RESID, "store / fp32 / residual / SwiGLU");
       bf16_t* C = reinterpret_cast<bf16_t*>(Cv) + (size_t)gm * ldc;
@@ -2607,22 +2455,7 @@ __global__ __launch_bounds__(256) void gemm_w4a8_kernel(const unsigned char* __r
       for (int i = 0; i < NI; ++i) {
         const int gn = nw + i * 16 + g * 4;
         if (gn >= N) continue;
-        float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-        const bool vec = gn + 3 < N && (ldc & 3) == 0;
-        if constexpr (EPI == EPI_RESID) {                              // h = round(h + round(proj)): the ring kernel's residual numerics
-          if (vec) {
-            const uint2 hv = *reinterpret_cast<const uint2*>(C + gn);
-            v[0] = bf_lo(hv.x) + bf2f(f2bf(v[0])); v[1] = bf_hi(hv.x) + bf2f(f2bf(v[1]));
-            v[2] = bf_lo(hv.y) + bf2f(f2bf(v[2])); v[3] = bf_hi(hv.y) + bf2f(f2bf(v[3]));
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (gn + r < N) v[r] = bf2f(C[gn + r]) + bf2f(f2bf(v[r]));
-          }
-        }
-        if (vec) *reinterpret_cast<uint2*>(C + gn) = make_uint2(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]));
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (gn + r < N) C[gn + r] = f2bf(v[r]);
+        store4<EPI == EPI_RESID>(C + gn, acc[i][j], gn, N, (ldc & 3) == 0);
       }
     }
   }
