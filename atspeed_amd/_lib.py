@@ -40,6 +40,8 @@ class GenStats(C.Structure):
 
 # every symbol include/atspeed_hip.h declares: (restype, argtypes)
 _P, _I, _F, _SZ, _U32, _U64 = C.c_void_p, C.c_int32, C.c_float, C.c_size_t, C.c_uint32, C.c_uint64
+# ATSPEED_SEGMENTS of the header: n, six host arrays of per-segment device pointers, three host arrays of counts
+_SEGS = [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P]
 SIGNATURES = {
     "atspeed_version": (C.c_char_p, []),
     "atspeed_last_error": (C.c_char_p, []),
@@ -102,6 +104,14 @@ SIGNATURES = {
     "atspeed_rmsnorm_quant_fp8": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "atspeed_tree_attention": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "atspeed_tree_attention_tiled": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "atspeed_segs_embed": (C.c_int, [_P, _I, _I, _I, _P] + _SEGS + [_P]),
+    "atspeed_segs_gather_logit_rows": (C.c_int, [_P, _I, _I, _P] + _SEGS + [_P]),
+    "atspeed_segs_row_info": (C.c_int, [_P, _I] + _SEGS + [_P]),
+    "atspeed_segs_rope_kv": (C.c_int, [_P, _P, _I, _P, _P, _SZ, _I, _I, _I, _I] + _SEGS + [_P]),
+    "atspeed_segs_tree_attention": (C.c_int, [_P, _I, _SZ, _I, _P, _I, _I, _I, _I, _I, _I, _I] + _SEGS + [_P]),
+    "atspeed_gemm_resid_norm": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _P, _SZ, _I, _P]),
+    "atspeed_gemm_fp8_resid_norm": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _SZ, _I, _P]),
+    "atspeed_gemm_w4a8_resid_norm": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _SZ, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

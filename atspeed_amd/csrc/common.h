@@ -227,6 +227,18 @@ template <typename T> __device__ __forceinline__ float round_elt(float v) {     
   else return v;
 }
 
+// x * rs of the RMSNorm kernels as T holds it: the product is an fp32 value of its own, then rounded to T.  fp16 flavour: left to itself the
+// compiler folds product and conversion into one v_fma_mixlo_f16 in one instantiation of a kernel and keeps v_mul_f32 + v_cvt_f16_f32 in
+// another (splitk_resid_rmsnorm_kernel with / without QUANT), and the two did not give the same bits on every element
+// (tests/test_segs_gpu.py::test_gemm_fp8_resid_norm); the empty asm keeps the product in a register of its own.
+template <typename T> __device__ __forceinline__ float norm_scale(float x, float rs) {
+  float p = x * rs;
+#ifdef ATS_F16_FLAVOUR
+  asm("" : "+v"(p));
+#endif
+  return round_elt<T>(p);
+}
+
 // The rotary pair (x0, x1) = (x[d], x[d + head_dim/2]) of the 16-bit engine, with the contraction spelled out: the separate RoPE pass, the
 // slab-summing one and the qkv GEMMs' fused epilogues must round identically (the compiler is otherwise free to pick which product it fuses).
 __device__ __forceinline__ float rope_first(float x0, float x1, float c, float s) { return __fmaf_rn(x0, c, -__fmul_rn(x1, s)); }    // x0 cos - x1 sin

@@ -33,8 +33,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const T* __restrict__ x, c
   for (int i = threadIdx.x; i < hidden; i += 256) { float v = Elt<T>::load(xr + i); ss += v * v; }
   float rs = rsqrtf(block_sum(ss, red) / (float)hidden + eps);
   for (int i = threadIdx.x; i < hidden; i += 256) {
-    float v = Elt<T>::load(xr + i) * rs;
-    v = round_elt<T>(v);                                // HF casts the normalised value to the input dtype first
+    const float v = norm_scale<T>(Elt<T>::load(xr + i), rs);   // HF casts the normalised value to the input dtype first
     Elt<T>::store(y + ats_opnd_idx<sizeof(T)>(pk, blockIdx.x, i, hidden), Elt<T>::load(w + i) * v);   // y: a GEMM operand (packed when pk)
   }
 }
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bf16_vec_kernel(const bf16_t* __r
       bf16_t* oe = reinterpret_cast<bf16_t*>(&o);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        oe[j] = f2bf(bf2f(we[j]) * bf2f(f2bf(bf2f(e[j]) * rs)));   // HF casts the normalised value first
+        oe[j] = f2bf(bf2f(we[j]) * norm_scale<bf16_t>(bf2f(e[j]), rs));   // HF casts the normalised value first
         if constexpr (QUANT) amax = fmaxf(amax, fabsf(bf2f(oe[j])));
       }
       if (y) *reinterpret_cast<uint4*>(y + ats_opnd_idx<2>(pk & 1, row, (size_t)i * 8, hidden)) = o;   // outputs are GEMM operands: packed when pk

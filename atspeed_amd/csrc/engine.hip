@@ -715,7 +715,6 @@ extern "C" int atspeed_llama_forward(atspeed_llama* m, const int32_t* ids, const
   return llama_forward_segs(m, t, logits_out, (hipStream_t)stream);
 }
 
-static int seg_finish(SegTable& t);
 
 // n independent forwards as ONE batched forward (segment table): sequence i has its own token / position / slot / visibility
 // arrays and a KV arena of its own from the model's pool; logits of its last n_logit[i] rows follow each other in logits_out.
@@ -744,10 +743,107 @@ extern "C" int atspeed_llama_forward_batch(atspeed_llama* m, int32_t n, const in
     sg.n_tok = n_tokens[i]; sg.n_slots = n_slots_visible[i]; sg.n_logit = n_logit_rows[i];
     tot += n_tokens[i]; rows += n_logit_rows[i];
   }
-  ATS_TRY(seg_finish(t));
+  ATS_TRY(ats_seg_finish(t));
   ATS_TRY(ensure_act(m, tot, rows));
   return llama_forward_segs(m, t, logits_out, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------- segment-table kernels, one at a time (tests)
+// The low-level atspeed_segs_* entry points describe their segments as atspeed_llama_forward_batch does -- host arrays of n device pointers
+// and counts -- except that the caches are the caller's.  This builds the table with the engine's own ats_seg_finish and stages it; `need`
+// names the per-segment arrays the wrapper's kernel reads (the others may be NULL).
+enum { SEGS_IDS = 1, SEGS_POS = 2, SEGS_SLOTS = 4, SEGS_VIS = 8, SEGS_KV = 16 };
+static int segs_table(const char* who, int need, int qtile_rows, int32_t n, const int32_t* const* ids, const int32_t* const* pos,
+                      const int32_t* const* slots, const uint64_t* const* vis, void* const* kcache, void* const* vcache, const int32_t* n_tokens,
+                      const int32_t* n_slots_visible, const int32_t* n_logit_rows, hipStream_t st, SegTable& t, const SegTable** dt) {
+  ATS_REQUIRE(n_tokens && n_slots_visible && n_logit_rows, ATSPEED_ERR_INVALID, "%s: null count array", who);
+  ATS_REQUIRE(n >= 1 && n <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "%s: %d segments per call (max %d)", who, n, ATS_MAX_SEGS);
+  ATS_REQUIRE(qtile_rows == 0 || qtile_rows == 64 || qtile_rows == 128 || qtile_rows == 256, ATSPEED_ERR_INVALID, "%s: query tile of %d rows", who, qtile_rows);
+  ATS_REQUIRE((!(need & SEGS_IDS) || ids) && (!(need & SEGS_POS) || pos) && (!(need & SEGS_SLOTS) || slots) && (!(need & SEGS_VIS) || vis) &&
+              (!(need & SEGS_KV) || (kcache && vcache)), ATSPEED_ERR_INVALID, "%s: null segment array", who);
+  t.n = 0;
+  for (int i = 0; i < n; ++i) {
+    ATS_REQUIRE(n_tokens[i] >= 1 && n_slots_visible[i] >= 0 && n_logit_rows[i] >= 0 && n_logit_rows[i] <= n_tokens[i], ATSPEED_ERR_INVALID,
+                "%s: bad counts for segment %d", who, i);
+    ATS_REQUIRE((n_tokens[i] + (qtile_rows ? qtile_rows : 64) - 1) / (qtile_rows ? qtile_rows : 64) <= 256, ATSPEED_ERR_CAPACITY,
+                "%s: segment %d has too many query tiles", who, i);
+    Seg& sg = t.seg[t.n++];
+    sg.ids = ids ? ids[i] : nullptr; sg.pos = pos ? pos[i] : nullptr; sg.slot = slots ? slots[i] : nullptr; sg.vis = vis ? vis[i] : nullptr;
+    sg.kc = kcache ? kcache[i] : nullptr; sg.vc = vcache ? vcache[i] : nullptr;
+    ATS_REQUIRE((!(need & SEGS_IDS) || sg.ids) && (!(need & SEGS_POS) || sg.pos) && (!(need & SEGS_SLOTS) || sg.slot) && (!(need & SEGS_VIS) || sg.vis) &&
+                (!(need & SEGS_KV) || (sg.kc && sg.vc)), ATSPEED_ERR_INVALID, "%s: null array for segment %d", who, i);
+    sg.n_tok = n_tokens[i]; sg.n_slots = n_slots_visible[i]; sg.n_logit = n_logit_rows[i];
+  }
+  ATS_TRY(ats_seg_finish(t, qtile_rows));
+  const void* p = nullptr;
+  ATS_TRY(ats_stage(&t, sizeof(t), &p, st));
+  *dt = (const SegTable*)p;
+  return ATSPEED_OK;
+}
+static bool segs_dtype_ok(int dtype) { return dtype == ATSPEED_F32 || dtype == ATSPEED_BF16 || dtype == ATSPEED_F16; }
+#define ATS_SEGS_PARAMS int32_t n, const int32_t* const* ids, const int32_t* const* pos, const int32_t* const* slots, const uint64_t* const* vis, \
+                        void* const* kcache, void* const* vcache, const int32_t* n_tokens, const int32_t* n_slots_visible, const int32_t* n_logit_rows
+#define ATS_SEGS_ARGS n, ids, pos, slots, vis, kcache, vcache, n_tokens, n_slots_visible, n_logit_rows
+
+// out[row][:] = table[clamp(id of the row, 0, vocab - 1)][:] for the total_tok rows of the segments (embed_segs_kernel); tests/test_segs_gpu.py::test_embed_gather_row_info
+extern "C" int atspeed_segs_embed(const void* table, int32_t hidden, int32_t vocab, int32_t dtype, void* out, ATS_SEGS_PARAMS, void* stream) {
+  ATS_REQUIRE(table && out && hidden > 0 && vocab > 0 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID, "segs_embed: bad arguments");
+  ATS_REQUIRE(hidden * (dtype == ATSPEED_F32 ? 4 : 2) % 16 == 0 && (((uintptr_t)table | (uintptr_t)out) & 15) == 0, ATSPEED_ERR_INVALID,
+              "segs_embed: rows must be whole, aligned 16-byte chunks");
+  SegTable t{}; const SegTable* dt = nullptr;
+  ATS_TRY(segs_table("segs_embed", SEGS_IDS, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
+  return ATS_KD(dtype, ats_embed_segs(table, t, dt, out, hidden, vocab, dtype, (hipStream_t)stream));
+}
+
+// out = the last n_logit_rows[i] rows of every segment of h, one after the other (gather_logit_rows_kernel); ::test_embed_gather_row_info
+extern "C" int atspeed_segs_gather_logit_rows(const void* h, int32_t hidden, int32_t dtype, void* out, ATS_SEGS_PARAMS, void* stream) {
+  ATS_REQUIRE(h && out && hidden > 0 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID, "segs_gather_logit_rows: bad arguments");
+  ATS_REQUIRE(hidden * (dtype == ATSPEED_F32 ? 4 : 2) % 16 == 0 && (((uintptr_t)h | (uintptr_t)out) & 15) == 0, ATSPEED_ERR_INVALID,
+              "segs_gather_logit_rows: rows must be whole, aligned 16-byte chunks");
+  SegTable t{}; const SegTable* dt = nullptr;
+  ATS_TRY(segs_table("segs_gather_logit_rows", 0, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
+  return ATS_KD(dtype, ats_gather_logit_rows(h, t, dt, out, hidden, dtype, (hipStream_t)stream));
+}
+
+// out[row] = {kcache, vcache of the row's segment, clamp(pos, 0, max_pos - 1), slot} (row_info_kernel; record layout: the header); ::test_embed_gather_row_info
+extern "C" int atspeed_segs_row_info(void* out, int32_t max_pos, ATS_SEGS_PARAMS, void* stream) {
+  ATS_REQUIRE(out && max_pos >= 1 && ((uintptr_t)out & 7) == 0, ATSPEED_ERR_INVALID, "segs_row_info: bad arguments");
+  SegTable t{}; const SegTable* dt = nullptr;
+  ATS_TRY(segs_table("segs_row_info", SEGS_POS | SEGS_SLOTS, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
+  return ats_bf16::ats_row_info(t, dt, (RowInfo*)out, max_pos, (hipStream_t)stream);
+}
+
+// the separate RoPE + KV-scatter pass on qkv [total_tok][3 * n_heads * head_dim]: q rotated in place, rotated k and v to row `slot` of the
+// segment's caches at layer_off_bytes (slabs == NULL: ats_rope_kv_segs; else the slab-summing form on fp32 [splits][total_tok][3 hidden]);
+// ::test_rope_kv, ::test_rope_kv_slabs
+extern "C" int atspeed_segs_rope_kv(void* qkv, const float* slabs, int32_t splits, const float* cos_tab, const float* sin_tab, size_t layer_off_bytes,
+                                    int32_t n_heads, int32_t head_dim, int32_t max_pos, int32_t dtype, ATS_SEGS_PARAMS, void* stream) {
+  ATS_REQUIRE(qkv && cos_tab && sin_tab && n_heads >= 1 && head_dim >= 2 && head_dim % 2 == 0 && max_pos >= 1 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID,
+              "segs_rope_kv: bad arguments");
+  ATS_REQUIRE(((uintptr_t)qkv & 15) == 0 && layer_off_bytes % 16 == 0, ATSPEED_ERR_INVALID, "segs_rope_kv: qkv and the layer offset must be 16-byte aligned");
+  ATS_REQUIRE(!slabs || (dtype != ATSPEED_F32 && splits >= 1 && ((uintptr_t)slabs & 15) == 0), ATSPEED_ERR_INVALID, "segs_rope_kv: slabs need a 16-bit type, splits >= 1 and 16-byte alignment");
+  SegTable t{}; const SegTable* dt = nullptr;
+  ATS_TRY(segs_table("segs_rope_kv", SEGS_POS | SEGS_SLOTS | SEGS_KV, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
+  if (slabs) return ATS_KD(dtype, ats_rope_kv_segs_slabs(slabs, splits, qkv, t, dt, cos_tab, sin_tab, layer_off_bytes, n_heads, head_dim, max_pos, (hipStream_t)stream));
+  return ATS_KD(dtype, ats_rope_kv_segs(qkv, t, dt, cos_tab, sin_tab, layer_off_bytes, n_heads, head_dim, max_pos, dtype, (hipStream_t)stream));
+}
+
+// tree attention of every segment's rows over that segment's own caches (at layer_off_bytes), n_slots and visibility words: the lock-step form
+// of atspeed_tree_attention_tiled (qtile_rows 0 / 64 / 128 / 256, rows_per_wave 0 / 16 / 32 as there); packed_out: out in the packed operand
+// layout (16-bit, ldo % 32 == 0).  ::test_tree_attention_segs, ::test_tree_attention_segs_many32
+extern "C" int atspeed_segs_tree_attention(const void* q, int32_t ldq, size_t layer_off_bytes, int32_t vis_words, void* out, int32_t ldo, int32_t n_heads,
+                                           int32_t head_dim, int32_t dtype, int32_t qtile_rows, int32_t rows_per_wave, int32_t packed_out, ATS_SEGS_PARAMS,
+                                           void* stream) {
+  ATS_REQUIRE(q && out && n_heads >= 1 && head_dim >= 1 && vis_words >= 1 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID, "segs_tree_attention: bad arguments");
+  ATS_REQUIRE(ldq >= 3 * n_heads * head_dim && ldo >= n_heads * head_dim && layer_off_bytes % 16 == 0, ATSPEED_ERR_INVALID, "segs_tree_attention: bad strides");
+  ATS_REQUIRE(rows_per_wave == 0 || rows_per_wave == 16 || rows_per_wave == 32, ATSPEED_ERR_INVALID, "segs_tree_attention: %d rows per wave", rows_per_wave);
+  SegTable t{}; const SegTable* dt = nullptr;
+  ATS_TRY(segs_table("segs_tree_attention", SEGS_VIS | SEGS_KV, qtile_rows, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
+  return ATS_KD(dtype, ats_tree_attention_segs(q, ldq, t, dt, layer_off_bytes, vis_words, out, ldo, n_heads, head_dim, dtype, (hipStream_t)stream, rows_per_wave,
+                                               packed_out ? 1 : 0));
+}
+#undef ATS_SEGS_PARAMS
+#undef ATS_SEGS_ARGS
 
 // ---------------------------------------------------------------------------- decoder
 namespace {
@@ -973,7 +1069,7 @@ static Seg make_seg(const TokBuf& tb, int n_tok, int n_slots, int n_logit, const
   s.n_tok = n_tok; s.n_slots = n_slots; s.n_logit = n_logit;
   return s;
 }
-static int seg_finish(SegTable& t) {
+int ats_seg_finish(SegTable& t, int qtile_rows) {
   t.total_tok = t.total_logit = t.n_qtiles = 0;
   int long_segs = 0;
   for (int i = 0; i < t.n; ++i) long_segs += t.seg[i].n_tok > 96 ? 1 : 0;
@@ -983,6 +1079,7 @@ static int seg_finish(SegTable& t) {
   // lock-step batches (thousands of workgroups) run the 32-rows-per-wave kernel: its 4-wave 128-row tile also wins on short segments
   // (the idle waves still carry a quarter of the tile's DMA): 249 vs 286 us at 256 users
   if (t.n >= 16) t.qtile_rows = 128;
+  if (qtile_rows) t.qtile_rows = qtile_rows;
   for (int i = 0; i < t.n; ++i) {
     t.seg[i].row0 = t.total_tok; t.total_tok += t.seg[i].n_tok;
     t.seg[i].logit_row0 = t.total_logit; t.total_logit += t.seg[i].n_logit;
@@ -1122,7 +1219,7 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
         t.seg[t.n++] = sg;
         r.s.n_draft_forwards++;
       }
-      ATS_TRY(seg_finish(t));
+      ATS_TRY(ats_seg_finish(t));
       ATS_TRY(decode_forward(D, t, decs[0]->run.fsm, decs[0]->run.dk, st));
       for (size_t j = 0; j < us.size(); ++j) {
         atspeed_decoder* d = us[j];
@@ -1155,7 +1252,7 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
         t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv);
         r.s.n_target_forwards++;
       }
-      ATS_TRY(seg_finish(t));
+      ATS_TRY(ats_seg_finish(t));
       ATS_TRY(decode_forward(T, t, decs[0]->run.fsm, decs[0]->run.k, st));
       hipEventRecord(g_ev[2], st);
       // ---- 3. verify (:242-456) for the verifying users, one workgroup each
@@ -1346,7 +1443,7 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
     SegTable t{};
     for (int u = 0; u < n; ++u)
       t.seg[t.n++] = make_seg(tb_offset(decs[u]->tin[0], s[u].row0, W), s[u].n_in, s[u].base + s[u].n_in, s[u].nb, decs[u]->tkv);
-    ATS_TRY(seg_finish(t));
+    ATS_TRY(ats_seg_finish(t));
     ATS_TRY(decode_forward(T, t, fsm, k, st));
     for (int u = 0; u < n; ++u) {
       atspeed_decoder* d = decs[u];

@@ -1379,7 +1379,7 @@ __global__ __launch_bounds__(1024) void splitk_resid_rmsnorm_kernel(const float*
       T* xo = xn + ats_opnd_idx<sizeof(T)>(pk, m, n, N);      // xn: the next projection's operand (V <= 4 consecutive columns stay inside one 64-byte block)
 #pragma unroll
       for (int j = 0; j < V; ++j) {
-        float v = Elt<T>::load(norm_w + n + j) * round_elt<T>(vals[i * V + j] * rs);
+        float v = Elt<T>::load(norm_w + n + j) * norm_scale<T>(vals[i * V + j], rs);
         if constexpr (QUANT) {
           v = round_elt<T>(v);                                 // the stored, 16-bit-rounded output is what gets quantised
           vals[i * V + j] = v;
@@ -2015,10 +2015,26 @@ static int reduce_slabs(int epilogue, const char* who, const void* ws, void* c, 
 // the residual projections' tail: h += the slabs' sum (slabs: null when the GEMM applied its residual epilogue itself), then the next op's
 // input norm -- xn and / or the e4m3 rows + scales (fn.q) a following W8A8 projection reads -- fused into that reduce pass where it can be,
 // else the norm kernels
+static bool norm_quant_fused(int n) { return n <= 8192 && n % 8 == 0; }      // the rows ats_rmsnorm_quant_fp8 takes
 static int resid_norm_tail(FusedNorm& fn, const float* slabs, int splits, void* h, int m, int n, int ldh, int dtype, hipStream_t st, int pk) {
   if (slabs) ATS_TRY((reduce_splits<bf16_t, EPI_RESID>(slabs, h, m, n, ldh, splits, st, &fn, pk)));
   if (fn.done) return ATSPEED_OK;
+  if (fn.q && !norm_quant_fused(n)) {          // rows the norm + e4m3 kernel does not take: the norm into xn (resid_norm_outputs_ok: present), then the quantiser
+    ATS_TRY(ats_rmsnorm(h, fn.w, fn.xn, m, n, fn.eps, dtype, st, pk));
+    return ats_quant_rows_fp8(fn.xn, m, n, n, fn.q, fn.qscale, st, pk);
+  }
   return fn.q ? ats_rmsnorm_quant_fp8(h, fn.w, fn.xn, fn.q, fn.qscale, m, n, fn.eps, st, pk) : ats_rmsnorm(h, fn.w, fn.xn, m, n, fn.eps, dtype, st, pk);
+}
+// what a W8A8 / W4A8 residual projection is asked to leave behind, checked BEFORE its first launch (a refused call writes nothing): the norm
+// as xn and / or as e4m3 rows + scales; beyond the norm + e4m3 kernel's rows (8192 columns) the e4m3 form is made from xn, which must then be given;
+// packed outputs are whole 64-byte blocks per row (the quantiser behind the norm kernels refuses anything else, by then too late)
+static int resid_norm_outputs_ok(const char* who, int n, const void* xn, const void* q_out, const float* s_out, int pk) {
+  ATS_REQUIRE(xn || (q_out && s_out), ATSPEED_ERR_INVALID, "%s: no output for the norm", who);
+  ATS_REQUIRE(!pk || ((!xn || n % 32 == 0) && (!q_out || n % 64 == 0)), ATSPEED_ERR_INVALID,
+              "%s: packed rows are whole 64-byte blocks (xn: N %% 32 == 0, e4m3 rows: N %% 64 == 0; N=%d)", who, n);
+  ATS_REQUIRE(!q_out || (s_out && n % 8 == 0), ATSPEED_ERR_INVALID, "%s: e4m3 rows need their scales and N %% 8 == 0 (N=%d)", who, n);
+  ATS_REQUIRE(!q_out || xn || norm_quant_fused(n), ATSPEED_ERR_INVALID, "%s: e4m3 rows of %d columns are quantised from xn, which is null", who, n);
+  return ATSPEED_OK;
 }
 // the operands of an entry point that leaves slabs only: present and 16-byte aligned
 static int slab_operands_ok(const char* who, const void* a, const void* w, const void* ws) {
@@ -2120,6 +2136,9 @@ int ats_gemm_resid_norm(const void* a, const void* w, void* h, int m, int n, int
   FusedNorm fn{norm_w, xn, eps, false};
   const int epc = dtype == ATSPEED_F32 ? 4 : 8;
   const GemmPlan p = plan_gemm(m, n, k, lda, ldh, dtype, EPI_RESID, workspace, workspace_bytes);
+  // (the norm kernels read h densely: only the fused reduce takes a row stride.  Checked before the first launch)
+  ATS_REQUIRE(ldh == n || (p.slab_bytes && n <= 8192 && p.form != G16_RING && k % epc == 0 && lda % epc == 0), ATSPEED_ERR_INVALID,
+              "gemm_resid_norm: ldh=%d != N=%d where the norm is not fused into the reduce pass", ldh, n);
   if (p.form == G16_RING || k % epc != 0 || lda % epc != 0)            // (ats_gemm checks the operands)
     ATS_TRY(ats_gemm(a, w, h, m, n, k, lda, ldh, dtype, EPI_RESID, workspace, workspace_bytes, st, pk, sk));
   else if (dtype == ATSPEED_F32)
@@ -2293,7 +2312,7 @@ int ats_gemm_fp8_partials(const void* xq, const float* sx, const void* wq, const
 int ats_gemm_fp8_resid_norm(const void* xq, const float* sx, const void* wq, const float* sw, void* h, int m, int n, int k, int ldh,
                             const void* norm_w, void* xn, void* q_out, float* s_out, float eps, void* ws, size_t ws_bytes, hipStream_t st, int pk) {
   if (m <= 0) return ATSPEED_OK;
-  ATS_REQUIRE(xn || (q_out && s_out), ATSPEED_ERR_INVALID, "gemm_fp8_resid_norm: no output for the norm");
+  ATS_TRY(resid_norm_outputs_ok("gemm_fp8_resid_norm", n, xn, q_out, s_out, pk));
   FusedNorm fn{norm_w, xn, eps, false, q_out, s_out};
   const Fp8Plan p = plan_fp8(m, n, k, EPI_RESID, ws, ws_bytes);
   // (the weight-streaming split only with its full part count: one part per tile goes through ats_gemm_fp8)
@@ -2304,6 +2323,7 @@ int ats_gemm_fp8_resid_norm(const void* xq, const float* sx, const void* wq, con
     ATS_TRY(launch_fp8_slabs(p, xq, sx, wq, sw, ws, m, n, k, st, pk));
     return resid_norm_tail(fn, (const float*)ws, p.splits, h, m, n, ldh, ATS_HALF, st, pk);
   }
+  ATS_REQUIRE(ldh == n, ATSPEED_ERR_INVALID, "gemm_fp8_resid_norm: ldh=%d != N=%d where the norm is not fused into the reduce pass", ldh, n);
   ATS_TRY(ats_gemm_fp8(xq, sx, wq, sw, h, m, n, k, ldh, EPI_RESID, st, pk, ws, ws_bytes));
   return resid_norm_tail(fn, nullptr, 0, h, m, n, ldh, ATS_HALF, st, pk);
 }
@@ -2574,7 +2594,7 @@ int ats_gemm_w4a8(const void* xq, const float* sx, const void* wq, const void* w
 // quantisation pass on the slabs where the grid is split, else the kernel's residual epilogue followed by the norm kernels
 int ats_gemm_w4a8_resid_norm(const void* xq, const float* sx, const void* wq, const void* wsc, void* h, int m, int n, int k, int ldh,
                              const void* norm_w, void* xn, void* q_out, float* s_out, float eps, void* ws, size_t ws_bytes, hipStream_t st, int pk) {
-  ATS_REQUIRE(xn || (q_out && s_out), ATSPEED_ERR_INVALID, "gemm_w4a8_resid_norm: no output for the norm");
+  ATS_TRY(resid_norm_outputs_ok("gemm_w4a8_resid_norm", n, xn, q_out, s_out, pk));
   ATS_REQUIRE(norm_w, ATSPEED_ERR_INVALID, "gemm_w4a8_resid_norm: null norm weight");
   ATS_TRY(w4a8_check(xq, sx, wq, wsc, h, m, n, k, ldh, EPI_RESID));
   FusedNorm fn{norm_w, xn, eps, false, q_out, s_out};
@@ -2584,6 +2604,7 @@ int ats_gemm_w4a8_resid_norm(const void* xq, const float* sx, const void* wq, co
     ATS_TRY((launch_w4a8<EPI_F32, true>((const unsigned char*)xq, sx, (const unsigned char*)wq, (const unsigned char*)wsc, ws, m, n, k, n, s_, st, pk)));
     return resid_norm_tail(fn, (const float*)ws, s_, h, m, n, ldh, ATS_HALF, st, pk);
   }
+  ATS_REQUIRE(ldh == n, ATSPEED_ERR_INVALID, "gemm_w4a8_resid_norm: ldh=%d != N=%d where the norm is not fused into the reduce pass", ldh, n);
   ATS_TRY(ats_gemm_w4a8(xq, sx, wq, wsc, h, m, n, k, ldh, EPI_RESID, st, pk, nullptr, 0));
   return resid_norm_tail(fn, nullptr, 0, h, m, n, ldh, ATS_HALF, st, pk);
 }
@@ -2616,6 +2637,30 @@ extern "C" int atspeed_gemm_w4a8(const void* xq, const float* sx, const void* wq
                                  int32_t ldc, int32_t epilogue, int32_t dtype, int32_t packed, void* workspace, size_t workspace_bytes, void* stream) {
   ATS_REQUIRE(dtype == ATSPEED_BF16 || dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "gemm_w4a8: dtype must be bf16 or fp16");
   return ATS_KD(dtype, ats_gemm_w4a8(xq, sx, wq, wsc, c, m, n, k, ldc, epilogue, (hipStream_t)stream, packed ? 1 : 0, workspace, workspace_bytes));
+}
+
+// the residual projections' fused forms, as the forwards call them (packed: a / xq, w / wq, xn and q_out in the packed operand layout);
+// tests/test_segs_gpu.py::test_gemm_resid_norm, ::test_gemm_fp8_resid_norm, ::test_gemm_w4a8_resid_norm
+extern "C" int atspeed_gemm_resid_norm(const void* a, const void* w, void* h, int32_t m, int32_t n, int32_t k, int32_t lda, int32_t ldh, int32_t dtype,
+                                       const void* norm_w, void* xn, float eps, void* workspace, size_t workspace_bytes, int32_t packed, void* stream) {
+  ATS_REQUIRE(a && w && h && norm_w && xn && n >= 1 && k >= 1, ATSPEED_ERR_INVALID, "gemm_resid_norm: null argument");
+  ATS_REQUIRE(dtype == ATSPEED_F32 || dtype == ATSPEED_BF16 || dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "gemm_resid_norm: unknown dtype %d", dtype);
+  return ATS_KD(dtype, ats_gemm_resid_norm(a, w, h, m, n, k, lda, ldh, dtype, norm_w, xn, eps, workspace, workspace_bytes, (hipStream_t)stream, packed ? 1 : 0, nullptr));
+}
+
+extern "C" int atspeed_gemm_fp8_resid_norm(const void* xq, const float* sx, const void* wq, const float* sw, void* h, int32_t m, int32_t n, int32_t k, int32_t ldh,
+                                           int32_t dtype, const void* norm_w, void* xn, void* q_out, float* s_out, float eps, void* workspace,
+                                           size_t workspace_bytes, int32_t packed, void* stream) {
+  ATS_REQUIRE(xq && sx && wq && sw && h && norm_w, ATSPEED_ERR_INVALID, "gemm_fp8_resid_norm: null argument");
+  ATS_REQUIRE(dtype == ATSPEED_BF16 || dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "gemm_fp8_resid_norm: dtype must be bf16 or fp16");
+  return ATS_KD(dtype, ats_gemm_fp8_resid_norm(xq, sx, wq, sw, h, m, n, k, ldh, norm_w, xn, q_out, s_out, eps, workspace, workspace_bytes, (hipStream_t)stream, packed ? 1 : 0));
+}
+
+extern "C" int atspeed_gemm_w4a8_resid_norm(const void* xq, const float* sx, const void* wq, const void* wsc, void* h, int32_t m, int32_t n, int32_t k, int32_t ldh,
+                                            int32_t dtype, const void* norm_w, void* xn, void* q_out, float* s_out, float eps, void* workspace,
+                                            size_t workspace_bytes, int32_t packed, void* stream) {
+  ATS_REQUIRE(dtype == ATSPEED_BF16 || dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "gemm_w4a8_resid_norm: dtype must be bf16 or fp16");
+  return ATS_KD(dtype, ats_gemm_w4a8_resid_norm(xq, sx, wq, wsc, h, m, n, k, ldh, norm_w, xn, q_out, s_out, eps, workspace, workspace_bytes, (hipStream_t)stream, packed ? 1 : 0));
 }
 
 extern "C" int atspeed_gemm_fp8_packed(const void* xq, const float* sx, const void* wq, const float* sw, void* c, int32_t m, int32_t n,

@@ -26,6 +26,10 @@ struct SegTable {
 };
 // per batched row, resolved once per forward (ats_row_info): where the row's K / V go and which rotation it takes
 struct RowInfo { void* kc; void* vc; int pos; int slot; };        // caches' layer-0 bases of the row's user; pos clamped to the RoPE table
+static_assert(sizeof(RowInfo) == 24, "RowInfo is part of the C ABI (atspeed_segs_row_info) and one 24-byte load in the qkv epilogues");
+// row0 / logit_row0 of every segment, the totals, the query-tile height and the tile -> (segment, tile of the segment) lists from the segments'
+// n_tok / n_logit (engine.hip).  qtile_rows: 0 = the engine's choice, 64 / 128 / 256 = that height (atspeed_segs_tree_attention)
+int ats_seg_finish(SegTable& t, int qtile_rows = 0);
 struct RopeEpi { const RowInfo* rows = nullptr; const float* cos_tab = nullptr; const float* sin_tab = nullptr; size_t layer_off = 0; int hidden = 0; };
 // copy a host object to device memory, stream ordered (pinned staging ring); returns the device address
 int ats_stage(const void* host_obj, size_t bytes, const void** dev_out, hipStream_t st);

@@ -435,6 +435,62 @@ int atspeed_tree_attention_tiled(const void* q_dev, int32_t ldq, const void* kca
                                  int32_t n_slots, int32_t n_heads, int32_t head_dim, int32_t dtype, int32_t qtile_rows,
                                  int32_t rows_per_wave, void* stream);
 
+/* ---- the kernels behind the segment table, one at a time (tests/test_segs_gpu.py pins each to an fp64 reference).  No reference counterpart:
+ * the reference runs one user per forward.  The segments are described as atspeed_llama_forward_batch describes them -- n (1 .. 256) and HOST
+ * arrays of n per-segment DEVICE pointers (ids, pos, slots: int32 [n_tokens[i]]; vis: uint64 [n_tokens[i]][vis_words]; kcache, vcache: the
+ * segment's K / V cache, layer-0 base, [layers][max_slots][hidden]) and HOST arrays of counts -- except that the caches are the caller's.  Each
+ * call builds the engine's segment table from them (row0 / logit_row0 = running sums, query tiles) and stages it; a per-segment array a call's
+ * kernel does not read may be NULL.  Rows of segment 0, 1, ... follow each other in the batched buffers (total_tok = sum of n_tokens). */
+#define ATSPEED_SEGMENTS                                                                                                                   \
+  int32_t n, const int32_t* const* ids_dev, const int32_t* const* pos_dev, const int32_t* const* slots_dev, const uint64_t* const* vis_bits_dev, \
+      void* const* kcache_dev, void* const* vcache_dev, const int32_t* n_tokens, const int32_t* n_slots_visible, const int32_t* n_logit_rows
+/* out[row][0 .. hidden) = table[clamp(id, 0, vocab - 1)][:] for every row (reads ids); rows >= total_tok are not written.  hidden * element
+ * size % 16 == 0, 16-byte aligned buffers.  ::test_embed_gather_row_info */
+int atspeed_segs_embed(const void* table_dev, int32_t hidden, int32_t vocab, int32_t dtype, void* out_dev, ATSPEED_SEGMENTS, void* stream);
+/* out = the LAST n_logit_rows[i] rows of every segment's rows of h [total_tok][hidden], segment after segment (a segment with 0 logit rows
+ * contributes none); rows >= sum of n_logit_rows are not written.  Reads no per-segment array.  ::test_embed_gather_row_info */
+int atspeed_segs_gather_logit_rows(const void* h_dev, int32_t hidden, int32_t dtype, void* out_dev, ATSPEED_SEGMENTS, void* stream);
+/* out[row] = one 24-byte record per row, what the fused qkv epilogues load: { uint64 kc; uint64 vc; int32 pos; int32 slot; } = the row's
+ * segment's kcache / vcache pointers, its position clamped to [0, max_pos - 1] (the rotation index) and its cache slot (reads pos, slots).
+ * ::test_embed_gather_row_info */
+int atspeed_segs_row_info(void* out_dev, int32_t max_pos, ATSPEED_SEGMENTS, void* stream);
+/* RoPE + KV scatter as a pass of its own (modeling_llama.py apply_rotary_pos_emb + the cache update): qkv [total_tok][3 * n_heads * head_dim] =
+ * q | k | v per row; cos / sin tables fp32 [max_pos][head_dim / 2], row = clamp(pos, 0, max_pos - 1); HF rotate-half pairs (i, i + head_dim / 2):
+ * q is rotated in place, rotated k and v go to row `slot` of the segment's caches at layer_off_bytes (reads pos, slots, kcache, vcache); the k
+ * and v columns of qkv stay as they were.  16-bit with head_dim % 16 == 0 takes the vector kernel, everything else the scalar one.
+ * slabs_dev != NULL (16-bit, head_dim % 16 == 0): the projection as fp32 split-K slabs [splits][total_tok][3 * hidden], summed in ascending
+ * slab order in fp32 and rounded to 16 bits first; then only the q columns of qkv are written.  ::test_rope_kv, ::test_rope_kv_slabs */
+int atspeed_segs_rope_kv(void* qkv_dev, const float* slabs_dev /* may be NULL */, int32_t splits, const float* cos_dev, const float* sin_dev,
+                         size_t layer_off_bytes, int32_t n_heads, int32_t head_dim, int32_t max_pos, int32_t dtype, ATSPEED_SEGMENTS, void* stream);
+/* atspeed_tree_attention_tiled over several segments in one launch: row r of segment i attends to the slots < n_slots_visible[i] of that
+ * segment's own caches (at layer_off_bytes) whose bit is set in its visibility words (reads vis, kcache, vcache).  qtile_rows 0 = the engine's
+ * choice (128 from 16 segments or when half the segments exceed 96 rows, else 64); rows_per_wave as atspeed_tree_attention_tiled.  packed_out =
+ * 1 (16-bit, ldo % 32 == 0): out in the packed operand layout o_proj reads (= atspeed_pack_rows of the row-major result; the pad row of an odd
+ * total_tok is not written).  Rows >= total_tok are not written.  ::test_tree_attention_segs, ::test_tree_attention_segs_many32 */
+int atspeed_segs_tree_attention(const void* q_dev, int32_t ldq, size_t layer_off_bytes, int32_t vis_words, void* out_dev, int32_t ldo,
+                                int32_t n_heads, int32_t head_dim, int32_t dtype, int32_t qtile_rows, int32_t rows_per_wave, int32_t packed_out,
+                                ATSPEED_SEGMENTS, void* stream);
+/* The residual projections as the forwards run them: h[m][0 .. n) += a w^T exactly as atspeed_gemm(..., epilogue 2) on the same operands and
+ * workspace, then xn[m][n] = norm_w * round(h * rsqrt(mean(h^2) + eps)) of the h just stored (HF LlamaRMSNorm on the updated residual stream:
+ * the next op's input).  Where the GEMM leaves split-K slabs and n <= 8192 one kernel sums them, adds the residual and normalises; elsewhere the
+ * norm kernels follow the GEMM, and those read h densely: ldh > n is accepted only where the fused kernel runs, a call is refused before it
+ * writes anything otherwise.  packed = 1 (16-bit; n % 32 == 0): a, w and xn in the packed operand layout (xn has ld = n).
+ * atspeed_gemm_fp8_resid_norm / _w4a8_resid_norm: the same behind atspeed_gemm_fp8 / atspeed_gemm_w4a8 (dtype bf16 / fp16; packed: xq and q_out);
+ * xn may be NULL when q_out and s_out are given: q_out [m][n] e4m3 and s_out [m] = atspeed_quant_rows_fp8 of xn (the next W8A8 projection's
+ * operand; n % 8 == 0, and beyond 8192 columns the e4m3 rows are made from xn, which must then be given; packed: xn needs n % 32 == 0 and q_out
+ * n % 64 == 0).  A call these rules refuse is refused before its first launch: h is untouched.  ::test_gemm_resid_norm, ::test_gemm_fp8_resid_norm, ::test_gemm_w4a8_resid_norm */
+int atspeed_gemm_resid_norm(const void* a_dev, const void* w_dev, void* h_dev, int32_t m, int32_t n, int32_t k, int32_t lda, int32_t ldh,
+                            int32_t dtype, const void* norm_w_dev, void* xn_dev, float eps, void* workspace_dev, size_t workspace_bytes,
+                            int32_t packed, void* stream);
+int atspeed_gemm_fp8_resid_norm(const void* xq_dev, const float* sx_dev, const void* wq_dev, const float* sw_dev, void* h_dev, int32_t m, int32_t n,
+                                int32_t k, int32_t ldh, int32_t dtype, const void* norm_w_dev, void* xn_dev /* may be NULL */,
+                                void* q_out_dev /* may be NULL */, float* s_out_dev /* may be NULL */, float eps, void* workspace_dev,
+                                size_t workspace_bytes, int32_t packed, void* stream);
+int atspeed_gemm_w4a8_resid_norm(const void* xq_dev, const float* sx_dev, const void* wq_dev, const void* wscale_dev, void* h_dev, int32_t m,
+                                 int32_t n, int32_t k, int32_t ldh, int32_t dtype, const void* norm_w_dev, void* xn_dev /* may be NULL */,
+                                 void* q_out_dev /* may be NULL */, float* s_out_dev /* may be NULL */, float eps, void* workspace_dev,
+                                 size_t workspace_bytes, int32_t packed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
