@@ -1,26 +1,35 @@
 // Tree attention over a slot-addressed KV cache.
 //
-// The reference feeds HF attention a dense additive mask [1,1,T,S] of 0 / finfo.min built by
-// concatenating parent rows and identity blocks (beamSD.py:89,204-209,396-400).  Here a query
-// row carries a bitset over cache slots (prompt prefix + one ancestor per accepted/draft
+// The reference feeds HF attention a dense additive mask [1,1,T,S] of 0 / finfo.min built by concatenating parent rows and identity blocks
+// (beamSD.py:89,204-209,396-400).  Here a query row carries a bitset over cache slots (prompt prefix + one ancestor per accepted/draft
 // block + itself); the kernel compacts the set bits and touches only visible slots.
 //
-// Two kernels:
-//  * tree_attn_mfma_kernel (bf16, head_dim 64/128): flash-style, one workgroup per (64 query
-//    rows, head), K tile and transposed V tile staged in LDS, both products on MFMA 16x16x32.
-//    Products are arranged so nothing moves between them: S^T = K.Q^T puts the key on the
-//    accumulator rows and the query on the lane (col = lane & 15), so the softmax statistics of a
-//    query live in the 4 lanes that share lane & 15, and the exponentiated S^T registers ARE the
-//    B operand of O^T = V^T.P^T (k-slots permuted identically on the V^T operand).
-//  * tree_attn_kernel (fp32 parity mode / odd head dims): one wave per (token, head), scalar.
+// Three MFMA forms (16-bit types, head_dim 64/128) and a scalar kernel.  The MFMA forms are flash-style: one workgroup per (query tile of
+// 64 / 128 / 256 rows, head) walks the segment's cache in 64-key tiles, a K tile and a row-major V tile in LDS (AttnTile), online softmax,
+// both products on MFMA.  Products are arranged so nothing moves between them: S^T = K.Q^T puts the key on the accumulator rows and the
+// query on the lane, so the softmax statistics of a query live in the few lanes that share it, and the exponentiated S^T registers ARE
+// the B operand of O^T = V^T.P^T (k-slots permuted identically on the V^T operand, which transposed LDS reads take out of the V tile).
+//  * tree_attn_mfma_kernel<DH, NW>: 16 query rows per wave (MFMA 16x16x32), 4 / 8 / 16 waves; tiles staged through registers into one
+//    static LDS tile.  Softmax in the natural-exponent domain.  Grids above 256 workgroups and the 256-row tile.
+//  * tree_attn_mfma_kernel<DH, NW, 4>: the same products and softmax behind a ring of four tiles filled by LDS-DMA with hand-counted
+//    waits; 4 / 8 waves.  One user's forwards (up to 256 workgroups).
+//  * tree_attn32_kernel<DH, NW>: 32 query rows per wave (MFMA 32x32x16), 2 / 4 / 8 waves; LDS-DMA into a double buffer.  Softmax in the
+//    log2 domain, O rescaled only when a maximum moved.  Lock-step batches (512 workgroups and more).
+//  * tree_attn_kernel<T> (fp32 parity mode / other head dims): one wave per (token, head), scalar, __expf.
+// What the forms share is defined once (AttnTile, ATS_ATTN_DMA_TILE, attn_work_item, attn_rows, vis_tail_mask); the softmax arithmetic is each form's own.
 #include "internal.h"
 #include <type_traits>
 
 namespace ATS_NS {
-
 namespace {
 
 constexpr int kMaxSlots = 2048;
+// slots >= n_slots of the last visibility word (kt of n_tiles 64-slot words) are never visible, whatever the row's bitset holds there
+__device__ __forceinline__ uint64_t vis_tail_mask(uint64_t word, int kt, int n_tiles, int n_slots) {
+  if (kt == n_tiles - 1 && (n_slots & 63)) word &= (~0ull) >> (64 - (n_slots & 63));
+  return word;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void tree_attn_kernel(const T* __restrict__ q, int ldq, const SegTable* __restrict__ tab, size_t layer_off,
                                                         int vis_words, T* __restrict__ out, int ldo, int pk,
@@ -28,9 +37,7 @@ __global__ __launch_bounds__(256) void tree_attn_kernel(const T* __restrict__ q,
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int t = blockIdx.x;                        // global row
-  int si = 0, hi = tab->n;
-  while (hi - si > 1) { int mid = (si + hi) >> 1; if (tab->seg[mid].row0 <= t) si = mid; else hi = mid; }
-  const Seg& sg = tab->seg[si];
+  const Seg& sg = tab->seg[seg_of_row(tab, t)];
   const T* kc = reinterpret_cast<const T*>(reinterpret_cast<const char*>(sg.kc) + layer_off);
   const T* vc = reinterpret_cast<const T*>(reinterpret_cast<const char*>(sg.vc) + layer_off);
   const uint64_t* vis_row = sg.vis + (size_t)(t - sg.row0) * vis_words;
@@ -51,8 +58,7 @@ __global__ __launch_bounds__(256) void tree_attn_kernel(const T* __restrict__ q,
   int n_vis = 0;
   const int words = (n_slots + 63) >> 6;
   for (int w = 0; w < words; ++w) {
-    uint64_t bits = vis_row[w];
-    if (w == words - 1 && (n_slots & 63)) bits &= (~0ull) >> (64 - (n_slots & 63));
+    const uint64_t bits = vis_tail_mask(vis_row[w], w, words, n_slots);
     if ((bits >> lane) & 1ull) slot_list[n_vis + __popcll(bits & ((1ull << lane) - 1ull))] = w * 64 + lane;
     n_vis += __popcll(bits);
   }
@@ -120,6 +126,22 @@ __device__ __forceinline__ void tr_read_2pairs(u32x2_t& a0, u32x2_t& b0, u32x2_t
       : "memory");
 }
 
+// ---- what the MFMA forms share
+// A 64-key tile in LDS: K rows of KCH 16-byte chunks, chunk c of row r at position c ^ (r & swizzle mask) (the mask is the kernel's: its
+// fragment reads apply the same one); then V row-major with a padded row stride.  lds_ring: [nstg][tile][rows][vis_words words].
+template <int DH> struct AttnTile {
+  static constexpr int KCH = DH / 8;                 // 16-byte chunks per K row
+  static constexpr int VROW = DH * 2 + 32;           // V tile row stride in bytes: 8 rows x 32 B of a transposed read cover all 64 banks
+  static constexpr int VCH = VROW / 16;              // 16-byte positions per V row (the last two are padding)
+  static constexpr int KBYTES = 64 * DH * 2, VBYTES = 64 * VROW, TILE = KBYTES + VBYTES;
+  static constexpr int NI = KCH + VCH;               // DMA instructions per tile (K: KCH, V: VCH), dealt round-robin to the waves
+  // DMA instructions ONE wave of nw issues per tile: the first NI % nw waves one more.  The hand-counted vmcnt waits are multiples of these
+  static constexpr int dma_per_wave(int nw, bool first_waves) { return first_waves ? (NI + nw - 1) / nw : NI / nw; }
+  static constexpr size_t lds_double() { return 2 * (size_t)TILE; }                   // tree_attn32_kernel: [2][K tile | V tile]
+  static constexpr size_t lds_ring(int nstg, int rows, int vis_words) { return (size_t)nstg * TILE + (size_t)rows * vis_words * sizeof(uint64_t); }
+};
+constexpr int kAttnLdsCap = 160 * 1024 - 64, kRingStages = 4;         // dynamic LDS a workgroup may ask for; tiles in the DMA ring
+
 // K / V tiles HBM -> LDS by LDS-DMA (global_load_lds_dwordx4: no staging registers).  A DMA instruction fills 64 consecutive 16-byte LDS
 // positions, so a swizzle or a row padding of the LDS image is applied on the source side: lane i of instruction j fetches whatever
 // belongs at position 64 j + i.
@@ -129,8 +151,49 @@ __device__ __forceinline__ void tr_read_2pairs(u32x2_t& a0, u32x2_t& b0, u32x2_t
 #define ATS_ATTN_DMA16(voff, sbase, m0v) \
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(m0v) : "memory")
 
+// The fill of tile kt into tile buffer buf by the kernel's NW waves, as a lambda `(int kt, int buf)` of the kernel it is expanded in: it uses
+// that kernel's kbase / vbase (the head's first byte of slot 0; rows hidden * 2 bytes apart), n_slots, lds0 (LDS address of the buffers), lane
+// and wave_u (wave-uniform, SGPR: the DMA's M0 and branch are scalar).  G: the kernel's AttnTile, SWZ: its K swizzle mask.  Rows past n_slots
+// are fetched from the last valid row: finite, masked out by the visibility word.  (Not a function template: as one, the same text compiled to
+// other address arithmetic inside the hand-counted loops -- profiles/attention_refactor_isa_and_speed.txt.)
+#define ATS_ATTN_DMA_TILE(G, NW, SWZ)                                                                                     \
+  [&](int kt, int buf) {                                                                                                  \
+    _Pragma("unroll") for (int j0 = 0; j0 < G::NI; j0 += NW) {                                                            \
+      const int j = j0 + wave_u;                                                                                          \
+      if (j < G::KCH) {                                                                                                   \
+        const int P = j * 64 + lane, r = P / G::KCH, cs = P % G::KCH;                                                     \
+        const int key = min(kt * 64 + r, n_slots - 1);                                                                    \
+        const unsigned voff = (unsigned)key * (unsigned)(hidden * 2) + ((cs ^ (r & SWZ)) * 16);                           \
+        ATS_ATTN_DMA16(voff, kbase, lds0 + buf * G::TILE + j * 1024);                                                     \
+      } else if (j < G::NI) {                                                                                             \
+        const int P = (j - G::KCH) * 64 + lane, r = P / G::VCH, c = P % G::VCH;                                           \
+        const int key = min(kt * 64 + r, n_slots - 1);                                                                    \
+        const unsigned voff = (unsigned)key * (unsigned)(hidden * 2) + (c < G::KCH ? c * 16 : 0);                         \
+        ATS_ATTN_DMA16(voff, vbase, lds0 + buf * G::TILE + G::KBYTES + (j - G::KCH) * 1024);                              \
+      }                                                                                                                   \
+    }                                                                                                                     \
+  }
+
+// 1-D grid over (head, query tile).  Workgroup L runs on XCD L % 8: give every XCD a contiguous range of work items, heads
+// outermost, so that the query tiles of one (user, head) -- which read the same K/V rows -- run back to back behind one L2
+struct AttnWork { int h, qt; };
+__device__ __forceinline__ AttnWork attn_work_item(int n_qtiles) {
+  const int total = gridDim.x, q8 = total >> 3, r8 = total & 7, x = blockIdx.x & 7;
+  const int wi = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (blockIdx.x >> 3);
+  return AttnWork{wi / n_qtiles, wi - (wi / n_qtiles) * n_qtiles};
+}
+// the query row of a lane: row `row` of wave `wave` in query tile qt of segment sg = tab->seg[tab->qtile_seg[qt]], NW waves of RPW rows.
+// (The kernels read sg's caches and n_slots between the segment lookup and this call, each in its own arithmetic: the compiler schedules
+// the prologue from that order.  tools/isa_compare.py against the previous build is the check to rerun when this is touched.)
+struct AttnRows { int lrow; bool qok; int qrow; const uint64_t* vis_row; };   // row inside the segment; the segment has it; row in the batched buffers
+template <int RPW, int NW>
+__device__ __forceinline__ AttnRows attn_rows(const SegTable* tab, const Seg& sg, int qt, int wave, int row, int vis_words) {
+  const int lrow = tab->qtile_idx[qt] * (RPW * NW) + wave * RPW + row;
+  return AttnRows{lrow, lrow < sg.n_tok, sg.row0 + lrow, sg.vis + (size_t)lrow * vis_words};
+}
+
 // ---------------------------------------------------------------------------- MFMA kernel (bf16)
-// blockIdx.x walks the 64-row query tiles of all segments (tile -> segment through the table's qtile arrays)
+// blockIdx.x walks (head, query tile) of all segments (attn_work_item)
 // NSTG = 0: K / V tiles staged through registers into one static LDS tile, the next tile's loads in flight during a tile's products (two
 // barriers per tile).  NSTG >= 3 (one user's forwards: up to 256 workgroups, one per CU): a RING of NSTG tiles filled by LDS-DMA, NSTG - 1
 // tiles in flight -- with 2-5 tiles of K/V per user the whole cache is on its way before the first product, where the register form exposed
@@ -142,44 +205,33 @@ __global__ __launch_bounds__(64 * NW) void tree_attn_mfma_kernel(const bf16_t* _
                                                              size_t layer_off, int vis_words,
                                                              bf16_t* __restrict__ out, int ldo, int pk,
                                                              int n_heads, float scale) {
-  constexpr int KCH = DH / 8;                 // 16-byte chunks per K row
-  constexpr int VROW = DH * 2 + 32;           // V tile row stride in bytes: 8 rows x 32 B of a transposed read cover all 64 banks
-  constexpr int VCH = VROW / 16;              // 16-byte positions per V row (the last two are padding)
+  using G = AttnTile<DH>;
+  constexpr int KCH = G::KCH, VROW = G::VROW;
   constexpr int DT = DH / 16;                 // output d-tiles
   constexpr int KS = DH / 32;                 // k-steps of the QK product
-  constexpr int KBYTES = 64 * DH * 2, TILE = KBYTES + 64 * VROW;
   constexpr bool RING = NSTG >= 3;
-  __shared__ __attribute__((aligned(16))) unsigned char ks_static[RING ? 16 : 64 * DH * 2];
-  __shared__ __attribute__((aligned(16))) unsigned char vs_static[RING ? 16 : 64 * VROW];   // V tile row-major; consumed column-wise by ds_read_b64_tr_b16
+  constexpr int SWZ = 7;                      // K swizzle mask of this kernel: the DMA fill, the register-staged fill and the S^T fragment reads
+  // (the ring form keeps 16-byte stand-ins: the two staging schemes share this function body, which names both arrays)
+  __shared__ __attribute__((aligned(16))) unsigned char ks_static[RING ? 16 : G::KBYTES];
+  __shared__ __attribute__((aligned(16))) unsigned char vs_static[RING ? 16 : G::VBYTES];   // V tile row-major; consumed column-wise by ds_read_b64_tr_b16
   extern __shared__ __attribute__((aligned(16))) unsigned char ring_smem[];                   // RING: [NSTG][K tile | V tile][16 NW rows x n_tiles visibility words]
   unsigned char* ks_lds = ks_static;
   unsigned char* vs_lds = vs_static;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, lq = lane & 15;
-  // 1-D grid over (head, query tile).  Workgroup L runs on XCD L % 8: give every XCD a contiguous range of work items, heads
-  // outermost, so that the query tiles of one (user, head) -- which read the same K/V rows -- run back to back behind one L2
-  const int n_qt = tab->n_qtiles;
-  int wi;
-  {
-    const int total = gridDim.x, q8 = total >> 3, r8 = total & 7, x = blockIdx.x & 7;
-    wi = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (blockIdx.x >> 3);
-  }
-  const int h = wi / n_qt, qt = wi - h * n_qt;
-  const int hidden = n_heads * DH;
-  const Seg& sg = tab->seg[tab->qtile_seg[qt]];
+  const AttnWork wk = attn_work_item(tab->n_qtiles);
+  const int h = wk.h, hidden = n_heads * DH;
+  const Seg& sg = tab->seg[tab->qtile_seg[wk.qt]];
   const bf16_t* kc = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(sg.kc) + layer_off);
   const bf16_t* vc = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(sg.vc) + layer_off);
   const int n_slots = sg.n_slots;
-  const int lrow = tab->qtile_idx[qt] * (16 * NW) + wave * 16 + lq;  // row inside the segment
-  const bool qok = lrow < sg.n_tok;
-  const int qrow = sg.row0 + lrow;                                           // row in the batched buffers
-  const uint64_t* vis_row = sg.vis + (size_t)lrow * vis_words;
+  const AttnRows rw = attn_rows<16, NW>(tab, sg, wk.qt, wave, lq, vis_words);
 
   s16x8_t qf[KS];
   auto load_q = [&]() {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      if (qok) qf[ks] = *reinterpret_cast<const s16x8_t*>(q + (size_t)qrow * ldq + h * DH + ks * 32 + g * 8);
+      if (rw.qok) qf[ks] = *reinterpret_cast<const s16x8_t*>(q + (size_t)rw.qrow * ldq + h * DH + ks * 32 + g * 8);
       else qf[ks] = s16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
     }
   };
@@ -207,37 +259,19 @@ __global__ __launch_bounds__(64 * NW) void tree_attn_mfma_kernel(const bf16_t* _
       }
     }
   };
-  // RING: the same LDS image by DMA.  NI instructions per tile (K: KCH, V: VCH), dealt round-robin to the waves; rows past n_slots (last
-  // tile) are fetched from the last valid row: finite values, masked out by the visibility word
-  constexpr int NI = KCH + VCH;
+  // RING: the same LDS image by DMA
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const int lds0 = RING ? __builtin_amdgcn_readfirstlane((int)lds_off(ring_smem)) : 0;
   const unsigned long long kbase = (unsigned long long)kc + (size_t)h * DH * 2, vbase = (unsigned long long)vc + (size_t)h * DH * 2;
-  auto dma_tile = [&](int kt, int buf) {
-#pragma unroll
-    for (int j0 = 0; j0 < NI; j0 += NW) {
-      const int j = j0 + wave_u;                       // wave-uniform (SGPR): the DMA's M0 and branch are scalar
-      if (j < KCH) {
-        const int P = j * 64 + lane, r = P / KCH, cs = P % KCH;
-        const int key = min(kt * 64 + r, n_slots - 1);
-        const unsigned voff = (unsigned)key * (unsigned)(hidden * 2) + ((cs ^ (r & 7)) * 16);
-        ATS_ATTN_DMA16(voff, kbase, lds0 + buf * TILE + j * 1024);
-      } else if (j < NI) {
-        const int P = (j - KCH) * 64 + lane, r = P / VCH, c = P % VCH;
-        const int key = min(kt * 64 + r, n_slots - 1);
-        const unsigned voff = (unsigned)key * (unsigned)(hidden * 2) + (c < KCH ? c * 16 : 0);
-        ATS_ATTN_DMA16(voff, vbase, lds0 + buf * TILE + KBYTES + (j - KCH) * 1024);
-      }
-    }
-  };
-  uint64_t* vis_lds = reinterpret_cast<uint64_t*>(ring_smem + (RING ? NSTG : 0) * TILE) + (size_t)(wave * 16 + lq) * n_tiles;   // this lane's row
+  auto dma_tile = ATS_ATTN_DMA_TILE(G, NW, SWZ);
+  uint64_t* vis_lds = reinterpret_cast<uint64_t*>(ring_smem + (RING ? NSTG : 0) * G::TILE) + (size_t)(wave * 16 + lq) * n_tiles;   // this lane's row
   if constexpr (RING) {
     // the first NSTG - 1 tiles leave before anything else is fetched; queries and visibility words travel behind them and everything is
     // awaited once (one memory round trip instead of three in a row), so that no load the compiler knows of is pending inside the ring
 #pragma unroll
     for (int t = 0; t < NSTG - 1; ++t) if (t < n_tiles) dma_tile(t, t);
     load_q();
-    for (int w = g; w < n_tiles; w += 4) vis_lds[w] = qok ? vis_row[w] : 0ull;     // the 4 lanes of a row share its words
+    for (int w = g; w < n_tiles; w += 4) vis_lds[w] = rw.qok ? rw.vis_row[w] : 0ull;     // the 4 lanes of a row share its words
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) asm volatile("" ::"v"(qf[ks]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -247,35 +281,35 @@ __global__ __launch_bounds__(64 * NW) void tree_attn_mfma_kernel(const bf16_t* _
   for (int kt = 0; kt < n_tiles; ++kt) {
     uint64_t word;
     if constexpr (RING) {
-      // tile kt has landed: all but the pieces of the NSTG - 2 younger tiles (this wave issues (NI - wave + NW - 1) / NW pieces per tile)
+      // tile kt has landed: all but the pieces of the NSTG - 2 younger tiles
       if (kt + NSTG - 2 < n_tiles) {
-        if (wave_u < NI % NW) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSTG - 2) * ((NI + NW - 1) / NW)) : "memory");
-        else                  asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSTG - 2) * (NI / NW)) : "memory");
+        if (wave_u < G::NI % NW) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSTG - 2) * G::dma_per_wave(NW, true)) : "memory");
+        else                     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSTG - 2) * G::dma_per_wave(NW, false)) : "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       __syncthreads();                                 // everyone's pieces of tile kt; and tile kt - 1 is fully consumed
       if (kt + NSTG - 1 < n_tiles) dma_tile(kt + NSTG - 1, (kt + NSTG - 1) % NSTG);
-      ks_lds = ring_smem + (kt % NSTG) * TILE;
-      vs_lds = ks_lds + KBYTES;
+      ks_lds = ring_smem + (kt % NSTG) * G::TILE;
+      vs_lds = ks_lds + G::KBYTES;
       word = vis_lds[kt];
     } else {
-    __syncthreads();                                   // previous tile fully consumed
-    // ---- stage K (swizzled rows) and V (row-major, padded rows)
+      __syncthreads();                                   // previous tile fully consumed
+      // ---- stage K (swizzled rows) and V (row-major, padded rows)
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int qi = tid + i * (64 * NW);
-      const int r = qi / KCH, c = qi % KCH;
-      if (qi < 64 * KCH) {
-        *reinterpret_cast<uint4*>(ks_lds + (r * KCH + (c ^ (r & 7))) * 16) = kreg[i];
-        *reinterpret_cast<uint4*>(vs_lds + r * VROW + c * 16) = vreg[i];
+      for (int i = 0; i < NLD; ++i) {
+        const int qi = tid + i * (64 * NW);
+        const int r = qi / KCH, c = qi % KCH;
+        if (qi < 64 * KCH) {
+          *reinterpret_cast<uint4*>(ks_lds + (r * KCH + (c ^ (r & SWZ))) * 16) = kreg[i];
+          *reinterpret_cast<uint4*>(vs_lds + r * VROW + c * 16) = vreg[i];
+        }
       }
+      __syncthreads();
+      if (kt + 1 < n_tiles) load_tile(kt + 1);
+      word = rw.qok ? rw.vis_row[kt] : 0ull;
     }
-    __syncthreads();
-    if (kt + 1 < n_tiles) load_tile(kt + 1);
-    word = qok ? vis_row[kt] : 0ull;
-    }
-    if (kt == n_tiles - 1 && (n_slots & 63)) word &= (~0ull) >> (64 - (n_slots & 63));
+    word = vis_tail_mask(word, kt, n_tiles, n_slots);
     if (__ballot(word != 0ull) == 0ull) continue;      // this wave's 16 rows see nothing here (wave-uniform)
 
     // ---- S^T = K_tile . Q^T : s[c][r] = score(key = kt*64 + c*16 + g*4 + r, query = lq)
@@ -286,7 +320,7 @@ __global__ __launch_bounds__(64 * NW) void tree_attn_mfma_kernel(const bf16_t* _
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         int r = c * 16 + lq, ch = ks * 4 + g;
-        s16x8_t kf = *reinterpret_cast<const s16x8_t*>(ks_lds + (r * KCH + (ch ^ (r & 7))) * 16);
+        s16x8_t kf = *reinterpret_cast<const s16x8_t*>(ks_lds + (r * KCH + (ch ^ (r & SWZ))) * 16);
         s[c] = ATS_MFMA_16x16x32(__builtin_bit_cast(bf16x8_t, kf), __builtin_bit_cast(bf16x8_t, qf[ks]), s[c]);
       }
     }
@@ -345,17 +379,16 @@ __global__ __launch_bounds__(64 * NW) void tree_attn_mfma_kernel(const bf16_t* _
   }
   l_run += __shfl_xor(l_run, 16, 64);
   l_run += __shfl_xor(l_run, 32, 64);
-  if (qok) {
+  if (rw.qok) {
     const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
 #pragma unroll
     for (int d = 0; d < DT; ++d) {
       ushort4 v4;
       v4.x = f2bf(o[d][0] * inv); v4.y = f2bf(o[d][1] * inv); v4.z = f2bf(o[d][2] * inv); v4.w = f2bf(o[d][3] * inv);
-      *reinterpret_cast<ushort4*>(out + ats_opnd_idx<2>(pk, qrow, h * DH + d * 16 + g * 4, ldo)) = v4;
+      *reinterpret_cast<ushort4*>(out + ats_opnd_idx<2>(pk, rw.qrow, h * DH + d * 16 + g * 4, ldo)) = v4;
     }
   }
 }
-
 
 // ---------------------------------------------------------------------------- MFMA kernel, 32 query rows per wave (bf16)
 // Same algorithm on v_mfma_f32_32x32x16_bf16: a wave owns 32 query rows, so one pass over the K / V tile in LDS feeds twice the
@@ -366,67 +399,35 @@ __global__ __launch_bounds__(64 * NW) void tree_attn_mfma_kernel(const bf16_t* _
 //   16t + 8*(j/4) + 4*hi + (j%4)); the A operand takes the same keys out of the row-major V tile with two transposed reads.
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
-// K / V tiles travel HBM -> LDS by LDS-DMA (global_load_lds_dwordx4: no staging registers) into a double buffer, tile kt+1 while
-// tile kt is multiplied; ONE barrier per tile.  A DMA instruction fills 64 consecutive 16-byte LDS positions, so the K swizzle and
-// the V row padding are applied on the source side: lane i of instruction j fetches whatever belongs at position 64 j + i.
+// K / V tiles travel HBM -> LDS by LDS-DMA (ATS_ATTN_DMA_TILE) into a double buffer, tile kt+1 while tile kt is multiplied; ONE barrier per tile.
 template <int DH, int NW>   // NW waves per workgroup = 32*NW query rows per tile
 __global__ __launch_bounds__(64 * NW, 2) void tree_attn32_kernel(const bf16_t* __restrict__ q, int ldq, const SegTable* __restrict__ tab,
                                                                  size_t layer_off, int vis_words, bf16_t* __restrict__ out, int ldo, int pk,
                                                                  int n_heads, float scale) {
-  constexpr int KCH = DH / 8;                 // 16-byte chunks per K row
-  constexpr int VROW = DH * 2 + 32;           // V tile row stride in bytes
-  constexpr int VCH = VROW / 16;              // 16-byte positions per V row (the last two are padding)
+  using G = AttnTile<DH>;
+  constexpr int KCH = G::KCH, VROW = G::VROW;
   constexpr int DB = DH / 32;                 // 32-row blocks of O^T
   constexpr int KS = DH / 16;                 // k-steps of the QK product
-  constexpr int KBYTES = 64 * DH * 2, TILE = KBYTES + 64 * VROW;
-  constexpr int NI = KCH + VCH;               // DMA instructions per tile (K: KCH, V: VCH), dealt round-robin to the waves
+  constexpr int SWZ = KCH - 1;                // K swizzle mask of this kernel: the DMA fill and kpos, which the S^T fragment reads go through
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lc = lane & 31, hi = lane >> 5;
-  const int n_qt = tab->n_qtiles;
-  int wi;
-  {
-    const int total = gridDim.x, q8 = total >> 3, r8 = total & 7, x = blockIdx.x & 7;
-    wi = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (blockIdx.x >> 3);
-  }
-  const int h = wi / n_qt, qt = wi - h * n_qt;
-  const int hidden = n_heads * DH;
-  const Seg& sg = tab->seg[tab->qtile_seg[qt]];
+  const AttnWork wk = attn_work_item(tab->n_qtiles);
+  const int h = wk.h, hidden = n_heads * DH;
+  const Seg& sg = tab->seg[tab->qtile_seg[wk.qt]];
   const unsigned long long kbase = (unsigned long long)sg.kc + layer_off + (size_t)h * DH * 2;
   const unsigned long long vbase = (unsigned long long)sg.vc + layer_off + (size_t)h * DH * 2;
   const int n_slots = sg.n_slots;
-  const int lrow = tab->qtile_idx[qt] * (32 * NW) + wave * 32 + lc;
-  const bool qok = lrow < sg.n_tok;
-  const int qrow = sg.row0 + lrow;
-  const uint64_t* vis_row = sg.vis + (size_t)lrow * vis_words;
+  const AttnRows rw = attn_rows<32, NW>(tab, sg, wk.qt, wave, lc, vis_words);
   const int lds0 = __builtin_amdgcn_readfirstlane((int)lds_off(smem));
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-
-  // rows past n_slots (last tile) are fetched from the last valid row: finite values, masked out by the visibility word
-  auto dma_tile = [&](int kt, int buf) {
-#pragma unroll
-    for (int j0 = 0; j0 < NI; j0 += NW) {
-      const int j = j0 + wave_u;                       // wave-uniform (SGPR): the DMA's M0 and branch are scalar
-      if (j < KCH) {
-        const int P = j * 64 + lane, r = P / KCH, cs = P % KCH;
-        const int key = min(kt * 64 + r, n_slots - 1);
-        const unsigned voff = (unsigned)key * (unsigned)(hidden * 2) + ((cs ^ (r & (KCH - 1))) * 16);
-        ATS_ATTN_DMA16(voff, kbase, lds0 + buf * TILE + j * 1024);
-      } else if (j < NI) {
-        const int P = (j - KCH) * 64 + lane, r = P / VCH, c = P % VCH;
-        const int key = min(kt * 64 + r, n_slots - 1);
-        const unsigned voff = (unsigned)key * (unsigned)(hidden * 2) + (c < KCH ? c * 16 : 0);
-        ATS_ATTN_DMA16(voff, vbase, lds0 + buf * TILE + KBYTES + (j - KCH) * 1024);
-      }
-    }
-  };
-
+  auto dma_tile = ATS_ATTN_DMA_TILE(G, NW, SWZ);
   const int n_tiles = (n_slots + 63) >> 6;
   if (n_tiles > 0) dma_tile(0, 0);
   s16x8_t qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    if (qok) qf[ks] = *reinterpret_cast<const s16x8_t*>(q + (size_t)qrow * ldq + h * DH + ks * 16 + hi * 8);
+    if (rw.qok) qf[ks] = *reinterpret_cast<const s16x8_t*>(q + (size_t)rw.qrow * ldq + h * DH + ks * 16 + hi * 8);
     else qf[ks] = s16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
   }
   f32x16_t o[DB];
@@ -437,15 +438,14 @@ __global__ __launch_bounds__(64 * NW, 2) void tree_attn32_kernel(const bf16_t* _
   const float sl2 = scale * 1.4426950408889634f;        // scores carried in the log2 domain
   float m_run = -INFINITY, l_run = 0.f;
 
-  auto kpos = [](int r, int c) { return (r * KCH + (c ^ (r & (KCH - 1)))) * 16; };
+  auto kpos = [](int r, int c) { return (r * KCH + (c ^ (r & SWZ))) * 16; };
   for (int kt = 0; kt < n_tiles; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile kt have landed
     __syncthreads();                                   // everyone's have, and the other buffer is fully consumed
     if (kt + 1 < n_tiles) dma_tile(kt + 1, (kt + 1) & 1);
-    const unsigned char* ks_lds = smem + (kt & 1) * TILE;
-    const unsigned char* vs_lds = ks_lds + KBYTES;
-    uint64_t word = qok ? vis_row[kt] : 0ull;
-    if (kt == n_tiles - 1 && (n_slots & 63)) word &= (~0ull) >> (64 - (n_slots & 63));
+    const unsigned char* ks_lds = smem + (kt & 1) * G::TILE;
+    const unsigned char* vs_lds = ks_lds + G::KBYTES;
+    const uint64_t word = vis_tail_mask(rw.qok ? rw.vis_row[kt] : 0ull, kt, n_tiles, n_slots);
     if (__ballot(word != 0ull) == 0ull) continue;      // this wave's 32 rows see nothing here (wave-uniform)
 
     // V^T fragments: 16-lane group gg = lane >> 4 takes d-columns 16*(gg & 1) .. +15 of the block and the 4 keys 4*hi .. +3 (second
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tree_attn32_kernel(const bf16_t* _
     }
   }
   l_run += __shfl_xor(l_run, 32, 64);
-  if (qok) {
+  if (rw.qok) {
     const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
 #pragma unroll
     for (int d = 0; d < DB; ++d)
@@ -526,7 +526,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tree_attn32_kernel(const bf16_t* _
         ushort4 v4;
         v4.x = f2bf(o[d][i4 * 4 + 0] * inv); v4.y = f2bf(o[d][i4 * 4 + 1] * inv);
         v4.z = f2bf(o[d][i4 * 4 + 2] * inv); v4.w = f2bf(o[d][i4 * 4 + 3] * inv);
-        *reinterpret_cast<ushort4*>(out + ats_opnd_idx<2>(pk, qrow, h * DH + d * 32 + 8 * i4 + 4 * hi, ldo)) = v4;
+        *reinterpret_cast<ushort4*>(out + ats_opnd_idx<2>(pk, rw.qrow, h * DH + d * 32 + 8 * i4 + 4 * hi, ldo)) = v4;
       }
   }
 }
@@ -545,15 +545,15 @@ int launch_attn(dim3 grid, int block, size_t lds, int lds_limit, hipStream_t st,
 // one selection per kernel family: the caller picks DH from head_dim (64 | 128), the waves of a query tile pick NW
 template <int DH>
 int launch_attn32(int nw, dim3 grid, hipStream_t st, const AttnArgs& a) {            // nw = tile rows / 32: 2 | 4 | 8
-  constexpr int lds_bytes = 2 * (64 * DH * 2 + 64 * (DH * 2 + 32));
+  constexpr int lds_bytes = (int)AttnTile<DH>::lds_double();
   if (nw == 8) return launch_attn<tree_attn32_kernel<DH, 8>>(grid, 512, lds_bytes, lds_bytes, st, a);
   if (nw == 4) return launch_attn<tree_attn32_kernel<DH, 4>>(grid, 256, lds_bytes, lds_bytes, st, a);
   return launch_attn<tree_attn32_kernel<DH, 2>>(grid, 128, lds_bytes, lds_bytes, st, a);
 }
 template <int DH>
 int launch_attn_ring(int nw, dim3 grid, size_t ring_lds, hipStream_t st, const AttnArgs& a) {   // nw = tile rows / 16: 4 | 8
-  if (nw == 8) return launch_attn<tree_attn_mfma_kernel<DH, 8, 4>>(grid, 512, ring_lds, 160 * 1024 - 64, st, a);
-  return launch_attn<tree_attn_mfma_kernel<DH, 4, 4>>(grid, 256, ring_lds, 160 * 1024 - 64, st, a);
+  if (nw == 8) return launch_attn<tree_attn_mfma_kernel<DH, 8, kRingStages>>(grid, 512, ring_lds, kAttnLdsCap, st, a);
+  return launch_attn<tree_attn_mfma_kernel<DH, 4, kRingStages>>(grid, 256, ring_lds, kAttnLdsCap, st, a);
 }
 template <int DH>
 int launch_attn_mfma(int nw, dim3 grid, hipStream_t st, const AttnArgs& a) {         // nw = tile rows / 16: 4 | 8 | 16
@@ -587,10 +587,9 @@ int ats_tree_attention_segs(const void* q, int ldq, const SegTable& t, const Seg
     // one user's forwards (at most one workgroup per CU): the DMA-ring form, the whole K/V of a user in flight before the first product
     constexpr int ring_max_wgs = 256;
     const int nw = t.qtile_rows / 16;
-    const size_t tile = (size_t)64 * head_dim * 2 + (size_t)64 * (head_dim * 2 + 32);
-    const size_t ring_lds = 4 * tile + (size_t)16 * nw * vis_words * sizeof(uint64_t);
+    const size_t ring_lds = head_dim == 128 ? AttnTile<128>::lds_ring(kRingStages, 16 * nw, vis_words) : AttnTile<64>::lds_ring(kRingStages, 16 * nw, vis_words);
     // (not the 256-row tile: 16 waves cap a lane at 128 registers and the compiler's spill traffic would sit in the hand-counted vmcnt window)
-    if (nw <= 8 && (int)(t.n_qtiles * n_heads) <= ring_max_wgs && ring_lds <= 160 * 1024 - 64) {
+    if (nw <= 8 && (int)(t.n_qtiles * n_heads) <= ring_max_wgs && ring_lds <= kAttnLdsCap) {
       ATS_TRY(head_dim == 128 ? launch_attn_ring<128>(nw, mgrid, ring_lds, st, a) : launch_attn_ring<64>(nw, mgrid, ring_lds, st, a));
       ATS_LAUNCH_CHECK();
       return ATSPEED_OK;
@@ -612,24 +611,23 @@ int ats_tree_attention_segs(const void* q, int ldq, const SegTable& t, const Seg
 int ats_tree_attention(const void* q, int ldq, const void* kcache, const void* vcache, const uint64_t* vis,
                        int vis_words, void* out, int ldo, int n_tokens, int n_slots, int n_heads, int head_dim,
                        int dtype, hipStream_t st, int qtile_rows, int rows_per_wave) {
-  SegTable t{};
-  t.n = 1; t.total_tok = n_tokens; t.total_logit = 0;
+  SegTable t{};                    // one segment without logit rows
+  t.n = 1;
   t.seg[0].vis = vis; t.seg[0].kc = const_cast<void*>(kcache); t.seg[0].vc = const_cast<void*>(vcache);
-  t.seg[0].row0 = 0; t.seg[0].n_tok = n_tokens; t.seg[0].n_slots = n_slots;
+  t.seg[0].n_tok = n_tokens; t.seg[0].n_slots = n_slots;
   ATS_REQUIRE(n_slots <= vis_words * 64, ATSPEED_ERR_CAPACITY, "attention: %d slots exceed the visibility bitset (%d words)", n_slots, vis_words);
   ATS_REQUIRE(qtile_rows == 0 || qtile_rows == 64 || qtile_rows == 128 || qtile_rows == 256, ATSPEED_ERR_INVALID, "attention: query tile of %d rows", qtile_rows);
   ATS_REQUIRE(rows_per_wave == 0 || rows_per_wave == 16 || rows_per_wave == 32, ATSPEED_ERR_INVALID, "attention: %d rows per wave", rows_per_wave);
-  t.n_qtiles = 0; t.qtile_rows = qtile_rows ? qtile_rows : (n_tokens > 160 ? 256 : (n_tokens > 96 ? 128 : 64));
-  ATS_REQUIRE((n_tokens + t.qtile_rows - 1) / t.qtile_rows <= ATS_MAX_QTILES && (n_tokens + t.qtile_rows - 1) / t.qtile_rows <= 255, ATSPEED_ERR_CAPACITY,
+  const int height = qtile_rows ? qtile_rows : (n_tokens > 160 ? 256 : (n_tokens > 96 ? 128 : 64));
+  ATS_REQUIRE((n_tokens + height - 1) / height <= ATS_MAX_QTILES && (n_tokens + height - 1) / height <= 255, ATSPEED_ERR_CAPACITY,   // qtile_idx is a byte
               "attention: too many query rows");
-  for (int j = 0; j * t.qtile_rows < n_tokens; ++j) { t.qtile_seg[t.n_qtiles] = 0; t.qtile_idx[t.n_qtiles++] = (unsigned char)j; }
+  ATS_TRY(ats_seg_finish(t, height));         // row0 = logit_row0 = 0, total_tok = n_tokens, total_logit = 0, the tiles of the one segment
   const void* dt = nullptr;
   ATS_TRY(ats_stage(&t, sizeof(t), &dt, st));
   return ats_tree_attention_segs(q, ldq, t, (const SegTable*)dt, 0, vis_words, out, ldo, n_heads, head_dim, dtype, st, rows_per_wave, 0);
 }
 
 }  // namespace ATS_NS
-
 #ifndef ATS_F16_FLAVOUR          // the C ABI exists once; it picks the flavour by the dtype code
 extern "C" int atspeed_tree_attention(const void* q, int32_t ldq, const void* kcache, const void* vcache,
                                       const uint64_t* vis, int32_t vis_words, void* out, int32_t n_tokens,

@@ -138,12 +138,6 @@ int ats_rmsnorm(const void* x, const void* w, void* y, int rows, int hidden, flo
 }
 
 // ---------------------------------------------------------------------------- multi-user (segment) variants
-__device__ __forceinline__ int seg_of_row(const SegTable* t, int row) {
-  int lo = 0, hi = t->n;                           // last segment with row0 <= row
-  while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (t->seg[mid].row0 <= row) lo = mid; else hi = mid; }
-  return lo;
-}
-
 // Per batched row: the caches of the row's user, its cache slot and its (clamped) rotation index -- resolved once per forward so that
 // the qkv projection's epilogue (gemm.hip: EPI_QKV_ROPE) finds them with one 24-byte load instead of a segment search per layer.
 __global__ void row_info_kernel(const SegTable* __restrict__ t, RowInfo* __restrict__ out, int max_pos) {

@@ -24,6 +24,13 @@ struct SegTable {
   Seg seg[ATS_MAX_SEGS];
   unsigned char qtile_seg[ATS_MAX_QTILES], qtile_idx[ATS_MAX_QTILES];
 };
+#if defined(__HIPCC__)
+__device__ __forceinline__ int seg_of_row(const SegTable* t, int row) {        // the segment of a batched row
+  int lo = 0, hi = t->n;                           // last segment with row0 <= row
+  while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (t->seg[mid].row0 <= row) lo = mid; else hi = mid; }
+  return lo;
+}
+#endif
 // per batched row, resolved once per forward (ats_row_info): where the row's K / V go and which rotation it takes
 struct RowInfo { void* kc; void* vc; int pos; int slot; };        // caches' layer-0 bases of the row's user; pos clamped to the RoPE table
 static_assert(sizeof(RowInfo) == 24, "RowInfo is part of the C ABI (atspeed_segs_row_info) and one 24-byte load in the qkv epilogues");
