@@ -17,7 +17,8 @@ reference's per-beam mask calls and `.tolist()` syncs (beamSD.py:62-64,371-372).
 Mask functions that can `compile()` (PositionSetConstraint, SuffixTrieConstraint, prefix_allowed_tokens_fn(trie)) run
 as a device automaton; any other callable is served by `hostmask.py` the way the reference does it (one host call per
 beam per step, all arithmetic still in HIP).  `generation_config.do_sample` selects the sampling branch
-(beamSD.py:65-75,293-321,332-369) with counter-based draws (`seed=` or torch's generator picks the stream).
+(beamSD.py:65-75,293-321,332-369) with counter-based draws (`seed=` or torch's generator picks the stream) and, like the
+reference's `_get_logits_warper`, honours the target config's `temperature`, `top_k` and `top_p` (per-row cutoffs computed on the device).
 No mask at all (`prefix_allowed_tokens_fn=None`, legal in the reference: beamSD.py:460-481) runs on the device too: every token is a
 candidate, the id filter of :80-86 is off as in the reference.  Extra `logits_processor` entries (the reference always passes None,
 inference.py:175-176) are torch callables and are served by the host path: each step's log-softmax rows go through them between the
@@ -25,7 +26,7 @@ library's forward and its expand + top-K.  Sampling with a host-side mask or pro
 counter-based streams (hostmask.py): a callable wrapping a compilable constraint samples exactly what the device path samples for that seed.
 
 The four entry points (BSSD, BSSD_batch, target_generate, target_generate_batch) share their scaffolding: `_mode` (models checked, sampling
-mode), `_setup` (prompts on the device, compiled constraints, the shared `_DeviceFSM`, one `_Decoder` per user, sampling and trace set),
+mode and warpers), `_setup` (prompts on the device, compiled constraints, the shared `_DeviceFSM`, one `_Decoder` per user, sampling and trace set),
 `_host_call` (dispatch to hostmask.py and result conversion), `_chunked` (lists above MAX_USERS_PER_CALL) and `_one_user_call` /
 `_batch_call` (buffers, argument marshalling and the library call: the one-user entry points keep their by-value launches, the batch ones
 take one pointer array entry per user).  `_DeviceFSM` and `_Decoder` cache device objects per constraint and per (model pair, lane) and
@@ -206,9 +207,26 @@ def _prompt_lists(prompts):
     return out
 
 
+def _warpers(gc):
+    """(top_k, top_p) of a generation config as the library takes them: 0 / 1.0 = off (`top_k in (None, 0)`, `top_p in (None, >= 1)`, or a
+    config without the attribute, as `from_synthetic` / `from_state_dict` models have it)."""
+    top_k, top_p = getattr(gc, "top_k", None), getattr(gc, "top_p", None)
+    top_k = 0 if top_k is None else int(top_k)
+    top_p = 1.0 if top_p is None else float(top_p)
+    if top_k < 0 or top_p <= 0.0:
+        raise ValueError(f"generation_config: top_k must be >= 0 and top_p in (0, 1], not {top_k} / {top_p}")
+    return top_k, min(top_p, 1.0)
+
+
+def min_tokens_to_keep(num_beams: int) -> int:
+    """what transformers 4.41's `_get_logits_warper` hands the top-k / top-p warpers of a beam search with one eos id"""
+    return 2 if int(num_beams) > 1 else 1
+
+
 def _mode(seed, *models):
-    """The models checked, then (do_sample, temperature, seed) of the call.  The reference samples when
-    `target_model.generation_config.do_sample` is set (beamSD.py:479-481) with its temperature warper; draws there come from torch's global
+    """The models checked, then (do_sample, temperature, seed, top_k, top_p) of the call.  The reference samples when
+    `target_model.generation_config.do_sample` is set (beamSD.py:479-481) with the warpers `_get_logits_warper` builds from that config:
+    temperature, then top-k, then top-p (0 / 1.0 = off); draws there come from torch's global
     generator, here from a counter-based stream whose 32-bit seed is drawn from that generator (so `torch.manual_seed` makes a call
     repeatable) unless `seed` is given."""
     for m in models:
@@ -216,11 +234,11 @@ def _mode(seed, *models):
             raise TypeError("models must be atspeed_amd.HipLlama (use HipLlama.from_hf(model) for an HF module)")
     gc = models[0].generation_config
     if not getattr(gc, "do_sample", False):
-        return False, 1.0, 0
+        return False, 1.0, 0, 0, 1.0
     if seed is None:
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
     temp = getattr(gc, "temperature", None)
-    return True, 1.0 if temp is None else float(temp), int(seed) & 0xFFFFFFFF
+    return (True, 1.0 if temp is None else float(temp), int(seed) & 0xFFFFFFFF) + _warpers(gc)
 
 
 def _prompt_row(inputs) -> torch.Tensor:
@@ -244,9 +262,14 @@ def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allo
             raise ValueError(f"{who} needs one shared constraint automaton (only the start node may differ per user)")
     dfsm = _DeviceFSM.get(fsms[0], target.dims.vocab_size)
     decs = [_Decoder.get(target, draft, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
-    do, temp, seed = mode
+    do, temp, seed, top_k, top_p = mode
+    off = (0, 1.0, 1)                                      # the one spelling of "both warpers off": a new decoder's state, every greedy call
+    warp = (top_k, top_p, min_tokens_to_keep(target.generation_config.num_beams)) if do and (top_k > 0 or top_p < 1.0) else off
     for u, d in enumerate(decs):
         _lib.check(lib.atspeed_decoder_set_sampling(d.handle, 1 if do else 0, temp, (seed + u) & 0xFFFFFFFF))
+        if getattr(d, "warp", off) != warp:                # the library is told only when the setting changes
+            _lib.check(lib.atspeed_decoder_set_warpers(d.handle, *warp))
+            d.warp = warp
     if trace is not None:
         for d in decs:
             if getattr(d, "trace_on", False) != bool(trace):

@@ -877,6 +877,10 @@ struct atspeed_decoder {
   float* tab_score = nullptr;   // [ATSPEED_MAX_GAMMA][ATS_MAX_CAND] the draft's candidate scores per step (allocated on first use)
   int32_t* tab_off = nullptr;   // [ATSPEED_MAX_GAMMA][MAXB + 1]
   float* tab_lse = nullptr;     // [ATSPEED_MAX_GAMMA]
+  // sampling-mode warpers (atspeed_decoder_set_warpers): off by default; `cutoff` holds one value per logits row of the step or round in flight
+  int top_k = 0; float top_p = 1.f; int min_keep = 1;
+  float* cutoff = nullptr;      // [MAXB + ATSPEED_MAX_GAMMA * MAXB] (allocated on first use)
+  bool warps() const { return sample && (top_k > 0 || top_p < 1.f); }
   struct Run {
     const atspeed_fsm* fsm; int gamma, max_new, k, dk;
     int32_t* out_tokens; float* out_scores; atspeed_gen_stats* stats_out;
@@ -945,7 +949,7 @@ extern "C" int atspeed_decoder_create(atspeed_llama* target, atspeed_llama* draf
 extern "C" void atspeed_decoder_destroy(atspeed_decoder* d) {
   if (!d) return;
   hipDeviceSynchronize();
-  hipFree(d->tab_score); hipFree(d->tab_off); hipFree(d->tab_lse);
+  hipFree(d->tab_score); hipFree(d->tab_off); hipFree(d->tab_lse); hipFree(d->cutoff);
   kv_free(&d->tkv);
   kv_free(&d->dkv);
   hipFree(d->arena);
@@ -964,6 +968,15 @@ extern "C" int atspeed_decoder_set_sampling(atspeed_decoder* d, int32_t do_sampl
     ATS_HIP(hipMalloc((void**)&d->tab_off, sizeof(int32_t) * ATSPEED_MAX_GAMMA * (MAXB + 1)));
     ATS_HIP(hipMalloc((void**)&d->tab_lse, sizeof(float) * ATSPEED_MAX_GAMMA));
   }
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_decoder_set_warpers(atspeed_decoder* d, int32_t top_k, float top_p, int32_t min_tokens_to_keep) {
+  ATS_REQUIRE(d, ATSPEED_ERR_INVALID, "set_warpers: null decoder");
+  ATS_REQUIRE(top_k >= 0 && top_p > 0.f && min_tokens_to_keep >= 1, ATSPEED_ERR_INVALID,
+              "set_warpers: top_k %d must be >= 0 (0 = off), top_p %g in (0, 1] (>= 1 = off), min_tokens_to_keep %d >= 1", top_k, (double)top_p, min_tokens_to_keep);
+  d->top_k = top_k; d->top_p = top_p < 1.f ? top_p : 1.f; d->min_keep = min_tokens_to_keep;
+  if ((d->top_k > 0 || d->top_p < 1.f) && !d->cutoff) ATS_HIP(hipMalloc((void**)&d->cutoff, sizeof(float) * (MAXB + ATSPEED_MAX_GAMMA * MAXB)));
   return ATSPEED_OK;
 }
 
@@ -1118,7 +1131,36 @@ static BeamStepArgs beam_step_args(const atspeed_decoder* d, const atspeed_llama
   a.fsm = fsm->dev; a.filter_ids = fsm->dev.n_nodes == 0 ? 0 : 1;
   a.mail = d->mail_dev; a.vis_words = d->W;
   if (d->sample) { a.sample = 1; a.temperature = d->temperature; }
+  if (d->warps()) a.cutoff = d->cutoff;
   return a;
+}
+// sampling-mode warpers: the cutoff job in front of a sampled beam step (one segment: the step's source beams) ...
+static WarpCutArgs warp_cut_args(const atspeed_decoder* d, const BeamStepArgs& s) {
+  WarpCutArgs w{};
+  w.seg[0] = WarpSeg{s.src.node, s.n_src}; w.n_seg = 1;
+  w.logits = s.logits; w.ld = s.ld; w.lse = s.lse; w.fsm = s.fsm;
+  w.temperature = d->temperature; w.top_k = d->top_k; w.top_p = d->top_p; w.min_keep = d->min_keep; w.cutoff = d->cutoff;
+  return w;
+}
+// ... and in front of a sampled verify walk (the round beams' rows, then every draft block's)
+static WarpCutArgs warp_cut_args(const atspeed_decoder* d, const VerifyArgs& v) {
+  WarpCutArgs w{};
+  w.seg[0] = WarpSeg{v.blk[0].node, v.nb};
+  for (int i = 1; i <= v.dl; ++i) w.seg[i] = WarpSeg{v.blk[i].node, v.dk};
+  w.n_seg = v.dl + 1;
+  w.logits = v.logits; w.ld = v.ld; w.lse = v.lse; w.fsm = v.fsm;
+  w.temperature = d->temperature; w.top_k = d->top_k; w.top_p = d->top_p; w.min_keep = d->min_keep; w.cutoff = d->cutoff;
+  return w;
+}
+// one job by value, several through one staged launch; no job (greedy, or both warpers off): no launch
+static int warp_cutoffs(const std::vector<WarpCutArgs>& w, hipStream_t st) {
+  if (w.empty()) return ATSPEED_OK;
+  if (w.size() == 1) return ats_row_warp_cutoff(w[0], st);
+  int max_rows = 0;
+  for (const WarpCutArgs& a : w) { int rows = 0; for (int s = 0; s < a.n_seg; ++s) rows += a.seg[s].n; max_rows = std::max(max_rows, rows); }
+  const WarpCutArgs* dw = nullptr;
+  ATS_TRY(stage_args(w, &dw, st));
+  return ats_row_warp_cutoff_multi(dw, (int)w.size(), max_rows, st);
 }
 // the step also writes the next forward's inputs: the parents' rows start at in_row0 of tb, the k new rows go to out_row0 (KV slots from out_slot0)
 static void beam_step_emit(BeamStepArgs& a, const TokBuf& tb, int in_row0, int out_row0, int out_slot0) {
@@ -1207,6 +1249,7 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
     for (int i = 0; i < max_dl; ++i) {
       SegTable t{};
       std::vector<BeamStepArgs> args;
+      std::vector<WarpCutArgs> wargs;
       std::vector<atspeed_decoder*> us;
       for (atspeed_decoder* d : ver) if (d->run.dl > i) us.push_back(d);
       for (atspeed_decoder* d : us) {
@@ -1230,8 +1273,10 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
           a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, i, 1);
           a.tab_score = d->tab_score + (size_t)i * ATS_MAX_CAND; a.tab_off = d->tab_off + (size_t)i * (MAXB + 1); a.tab_lse = d->tab_lse + i;
         }
+        if (a.cutoff) wargs.push_back(warp_cut_args(d, a));
         args.push_back(a);
       }
+      ATS_TRY(warp_cutoffs(wargs, st));
       const BeamStepArgs* dev_args = nullptr;
       ATS_TRY(stage_args(args, &dev_args, st));
       ATS_TRY(ats_beam_step_multi(dev_args, (int)args.size(), st));
@@ -1257,6 +1302,7 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
       hipEventRecord(g_ev[2], st);
       // ---- 3. verify (:242-456) for the verifying users, one workgroup each
       std::vector<VerifyArgs> vargs;
+      std::vector<WarpCutArgs> wargs;                  // sampling-mode warpers: the cutoffs of this round's verify walks and final steps
       for (size_t j = 0; j < ver.size(); ++j) {
         atspeed_decoder* d = ver[j];
         atspeed_decoder::Run& r = d->run;
@@ -1277,12 +1323,8 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
             va.dtab_lse[i] = d->tab_lse + i;
           }
         }
+        if (d->warps()) { va.cutoff = d->cutoff; wargs.push_back(warp_cut_args(d, va)); }
         vargs.push_back(va);
-      }
-      if (!vargs.empty()) {
-        const VerifyArgs* dv = nullptr;
-        ATS_TRY(stage_args(vargs, &dv, st));
-        ATS_TRY(ats_verify_walk_multi(dv, (int)vargs.size(), st));
       }
       std::vector<BeamStepArgs> fargs;
       for (size_t j = 0; j < fin.size(); ++j) {
@@ -1290,7 +1332,14 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
         atspeed_decoder::Run& r = d->run;
         BeamStepArgs a = beam_step_args(d, T, t.seg[ver.size() + j], r.fsm, d->round_beams[r.cur], d->round_beams[r.cur ^ 1], r.gen, r.k);   // emits nothing
         if (a.sample) a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, 0, 0);
+        if (a.cutoff) wargs.push_back(warp_cut_args(d, a));
         fargs.push_back(a);
+      }
+      ATS_TRY(warp_cutoffs(wargs, st));
+      if (!vargs.empty()) {
+        const VerifyArgs* dv = nullptr;
+        ATS_TRY(stage_args(vargs, &dv, st));
+        ATS_TRY(ats_verify_walk_multi(dv, (int)vargs.size(), st));
       }
       if (!fargs.empty()) {
         const BeamStepArgs* df = nullptr;
@@ -1439,6 +1488,7 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
   std::vector<St> s(n);
   for (int u = 0; u < n; ++u) s[u] = St{0, prompt_lens[u], 1, 0, 0};
   std::vector<BeamStepArgs> args(n);
+  std::vector<WarpCutArgs> wargs;
   for (int g = 0; g < max_new; ++g) {                                                // beamSD.py:579-588
     SegTable t{};
     for (int u = 0; u < n; ++u)
@@ -1451,8 +1501,11 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
       a = beam_step_args(d, T, t.seg[u], fsm, d->round_beams[s[u].cur], d->round_beams[s[u].cur ^ 1], g, k);
       beam_step_emit(a, d->tin[0], s[u].row0 + s[u].n_in - s[u].nb, s[u].row0 + s[u].n_in, s[u].base + s[u].n_in);
       if (a.sample) a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, g, 0, 0);
+      if (a.cutoff) wargs.push_back(warp_cut_args(d, a));
       s[u].row0 += s[u].n_in; s[u].base += s[u].n_in; s[u].n_in = k; s[u].nb = k; s[u].cur ^= 1;
     }
+    ATS_TRY(warp_cutoffs(wargs, st));
+    wargs.clear();
     if (n == 1) ATS_TRY(ats_beam_step(args[0], st));
     else {
       const BeamStepArgs* dev_args = nullptr;

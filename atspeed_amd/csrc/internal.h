@@ -139,6 +139,7 @@ struct BeamStepArgs {
   // softmax(score / temperature); tab_* (optional) keep the draft's whole candidate distribution for the verification
   int sample;  float temperature;  uint32_t rng_sub;
   float* tab_score;  int32_t* tab_off;  float* tab_lse;   // [candidates in expand order], [n_src + 1], [1]
+  const float* cutoff;                        // sampling-mode warpers: [n_src] per-row cutoffs of the tempered scores (ats_row_warp_cutoff); NULL = off
 };
 int ats_beam_step(const BeamStepArgs& a, hipStream_t st);
 // one workgroup per user; `dev_args` is a DEVICE array of n argument blocks
@@ -159,11 +160,30 @@ struct VerifyArgs {
   // sampling verification (beamSD.py:293-321,332-369)
   int sample;  float temperature;  uint32_t seed;  int round;
   const float* dtab_score[ATSPEED_MAX_GAMMA];  const int32_t* dtab_off[ATSPEED_MAX_GAMMA];  const float* dtab_lse[ATSPEED_MAX_GAMMA];
+  const float* cutoff;                        // sampling-mode warpers: per-row cutoffs aligned with `logits` (ats_row_warp_cutoff); NULL = off
   // decision trace (atspeed_decoder_set_trace level 1, greedy walk only): step i's k picks as [i][3][ATSPEED_MAX_BEAMS] words
   // (score bits, parent = index into blk[i], token; flat < 0 picks have token -1); NULL = off
   int32_t* vtrace;
 };
 int ats_verify_walk_multi(const VerifyArgs* dev_args, int n, hipStream_t st);
+
+// Sampling-mode warpers (top-k, then top-p with min_keep; transformers' TopKLogitsWarper / TopPLogitsWarper after the temperature,
+// beamSD.py:65-66,293-294) as ONE cutoff per logits row: a candidate of the row survives iff its tempered score
+// (logit - lse) / temperature is at or above cutoff[row]; -inf = nothing cut.  The rows of a job are consecutive rows of `logits`, in
+// segments: row j of segment s sits at the automaton node seg[s].node[j] (a beam step: one segment, the source beams; a verify round: the
+// round beams, then one segment per draft block).
+struct WarpSeg { const int32_t* node; int n; };
+struct WarpCutArgs {
+  WarpSeg seg[ATSPEED_MAX_GAMMA + 1];  int n_seg;
+  const float* logits;  int ld;  const float* lse;
+  FsmDev fsm;
+  float temperature;  int top_k;  float top_p;  int min_keep;   // top_k <= 0 / top_p >= 1: that warper is off
+  float* cutoff;                                                // [rows of all segments]
+};
+int ats_row_warp_cutoff(const WarpCutArgs& a, hipStream_t st);
+// one grid column per job; `dev_args` is a DEVICE array of n argument blocks, max_rows the largest row count among them
+int ats_row_warp_cutoff_multi(const WarpCutArgs* dev_args, int n, int max_rows, hipStream_t st);
+extern std::atomic<long long> g_ats_warp_launches;             // scan.hip: launches of the cutoff kernel (atspeed_warp_cutoff_launches)
 
 int ats_init_prompt(TokBuf tb, const int32_t* prompt, int prompt_len, int vis_words, BeamSet beams, int start_node,
                     int vocab, Mailbox* mail, hipStream_t st);

@@ -179,6 +179,7 @@ struct ExpandShared {
   float lse[MAXB];
   int rp[MAXB];         // first edge of the row's node (fsm.row_ptr[node]) and its number of children
   int deg[MAXB];
+  float cut[MAXB];      // sampling-mode warpers: the row's cutoff of the tempered score (-inf = none)
   int status;
   float red_m[kScanWaves], red_s[kScanWaves];   // block reductions of the sampling paths
   float red_out;
@@ -293,10 +294,12 @@ __device__ __forceinline__ Pick decode_pick(unsigned long long key, const FsmDev
 struct CandRegs { int flat[kCPT]; float sc[kCPT]; };
 
 __device__ void expand_candidates(ExpandShared& sh, int n_rows, const float* __restrict__ logits, int ld,
-                                  const float* __restrict__ lse, const FsmDev& fsm, float temperature, CandRegs& cr) {
+                                  const float* __restrict__ lse, const FsmDev& fsm, float temperature, const float* __restrict__ cutoff,
+                                  CandRegs& cr) {
   const int tid = threadIdx.x;
   if (tid < n_rows) {                                 // as in expand_and_select: every row fetches its own edge range
     sh.lse[tid] = lse[sh.lrow[tid]];
+    sh.cut[tid] = cutoff ? cutoff[sh.lrow[tid]] : -INFINITY;
     const int nd = sh.node[tid], e0 = fsm.row_ptr[nd];
     sh.rp[tid] = e0;
     sh.deg[tid] = fsm.row_ptr[nd + 1] - e0;
@@ -325,7 +328,8 @@ __device__ void expand_candidates(ExpandShared& sh, int n_rows, const float* __r
       while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (sh.off[mid] <= c) lo = mid; else hi = mid; }
       int r = lo;
       int tok = fsm.tok[sh.rp[r] + (c - sh.off[r])];
-      cr.sc[i] = (logits[(size_t)sh.lrow[r] * ld + tok] - sh.lse[r]) / temperature + sh.bscore[r];
+      const float s = (logits[(size_t)sh.lrow[r] * ld + tok] - sh.lse[r]) / temperature;
+      cr.sc[i] = s < sh.cut[r] ? -INFINITY : s + sh.bscore[r];         // below the row's cutoff: absent
       cr.flat[i] = sh.brow[r] * fsm.vocab + tok;
     }
   }
@@ -396,10 +400,11 @@ __device__ Pick pick_of_flat(int flat, const FsmDev& fsm, const ExpandShared& sh
   int r = -1;
   for (int q = 0; q < n_rows; ++q) if (sh.brow[q] == p.parent) { r = q; break; }
   if (r < 0) { p.score = -INFINITY; p.node = 0; return p; }
-  p.score = (logits[(size_t)sh.lrow[r] * ld + p.tok] - sh.lse[r]) / temperature + sh.bscore[r];
+  const float s = (logits[(size_t)sh.lrow[r] * ld + p.tok] - sh.lse[r]) / temperature;
+  p.score = s + sh.bscore[r];
   int e = find_edge(fsm, sh.node[r], p.tok);
   p.node = e >= 0 ? fsm.nxt[e] : 0;
-  if (e < 0) p.score = -INFINITY;
+  if (e < 0 || s < sh.cut[r]) p.score = -INFINITY;
   return p;
 }
 
@@ -431,6 +436,240 @@ __device__ void emit_vis(const int* parents /*LDS*/, int k, const TokBuf& in, in
   }
 }
 
+// ---------------------------------------------------------------------------- sampling-mode warpers (top-k, top-p)
+// One cutoff per score row (internal.h WarpCutArgs).  The row's entries are the children of its automaton node, scored
+// s = (logit - lse) / temperature exactly as expand_candidates forms them; -inf and NaN entries are no candidates.
+//   top-k: k' = max(top_k, min_keep); with at least k' finite entries the k'-th largest is the threshold (ties with it survive), with
+//          fewer nothing is cut (transformers' `scores < topk(scores, k')[0][..., -1]` on the full row: its k'-th largest is -inf then).
+//   top-p: over what top-k left, p = softmax(s); in DESCENDING score order an entry is kept while the probability mass strictly above it
+//          is below top_p, the first min_keep always (TopPLogitsWarper removes, ascending, the entries whose cumulative sum is
+//          <= 1 - top_p and never the last min_keep: the same boundary seen from the other end).
+// The cutoff is the score of the last kept entry, so entries tied with it survive as well.
+// Nucleus sum order: fp32, over the survivors in descending score order, in runs of at most 1024 (one entry per thread): inside a run
+// each wave adds its 64 entries with a Hillis-Steele ladder over the lanes, the 16 wave sums are then added in wave order onto the mass
+// carried in from the earlier runs; a group of equal scores that ends a run is added entry by entry.  The normaliser (sum of
+// exp(s - max) over the survivors) is a butterfly over the lanes of each wave and then the wave sums in wave order.
+// A row of at most 1024 entries is sorted in LDS; a longer one takes a 4 x 8-bit radix select on ford(s) for the top-k threshold and for
+// the lower end of every run, so no child-list length is assumed.
+struct WarpShared {
+  uint32_t key[kScanThreads];     // a descending run of keys (0 = none)
+  int hist[256];
+  float redf[kScanWaves];
+  int redi[kScanWaves];
+  int cnt;                        // compaction cursor / first entry the nucleus drops
+  int pick, above;                // radix select: the bin that holds the rank, keys above that bin
+};
+struct WarpRow {
+  const float* logits; const int32_t* tok; int deg; float lse, temperature;
+  __device__ __forceinline__ uint32_t key(int j) const {          // 0 = not a candidate
+    const float s = (logits[tok[j]] - lse) / temperature;
+    return s > -INFINITY ? ford(s) : 0u;
+  }
+};
+
+__device__ float warp_block_sum(WarpShared& sh, float v) {
+  v = wave_sum_f32(v);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) sh.redf[wave] = v;
+  __syncthreads();
+  float t = 0.f;
+  for (int w = 0; w < kScanWaves; ++w) t += sh.redf[w];
+  return t;
+}
+__device__ int warp_block_sum_i(WarpShared& sh, int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) sh.redi[wave] = v;
+  __syncthreads();
+  int t = 0;
+  for (int w = 0; w < kScanWaves; ++w) t += sh.redi[w];
+  return t;
+}
+__device__ uint32_t warp_block_max_u32(WarpShared& sh, uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)v, o, 64); v = u > v ? u : v; }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) sh.redi[wave] = (int)v;
+  __syncthreads();
+  uint32_t t = 0;
+  for (int w = 0; w < kScanWaves; ++w) t = (uint32_t)sh.redi[w] > t ? (uint32_t)sh.redi[w] : t;
+  return t;
+}
+
+// sh.key[0 .. n2) descending, n2 a power of two <= kScanThreads (bitonic network, one entry per thread)
+__device__ void warp_sort_desc(WarpShared& sh, int n2) {
+  const int tid = threadIdx.x;
+  for (int k = 2; k <= n2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      const int o = tid ^ j;
+      if (tid < n2 && o > tid) {
+        const uint32_t a = sh.key[tid], b = sh.key[o];
+        if (((tid & k) == 0) ? a < b : a > b) { sh.key[tid] = b; sh.key[o] = a; }
+      }
+    }
+  __syncthreads();
+}
+
+// the r-th largest (r >= 1) of the row's keys in [1, upper); the caller has counted at least r of them.  *n_above = keys in (result, upper).
+__device__ uint32_t warp_radix_select(WarpShared& sh, const WarpRow& row, unsigned long long upper, int r, int* n_above) {
+  const int tid = threadIdx.x;
+  unsigned long long prefix = 0;
+  int above = 0;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    __syncthreads();
+    if (tid < 256) sh.hist[tid] = 0;
+    if (tid == 0) { sh.pick = 0; sh.above = above; }
+    __syncthreads();
+    for (int j = tid; j < row.deg; j += kScanThreads) {
+      const unsigned long long o = row.key(j);
+      if (o != 0 && o < upper && (o >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&sh.hist[(int)((o >> shift) & 255)], 1);
+    }
+    __syncthreads();
+    if (tid < 256) {                                   // the bin b with  above + |bins above b| < r <= that + |b|
+      int gt = above;
+      for (int b = tid + 1; b < 256; ++b) gt += sh.hist[b];
+      if (gt < r && r <= gt + sh.hist[tid]) { sh.pick = tid; sh.above = gt; }
+    }
+    __syncthreads();
+    prefix |= (unsigned long long)sh.pick << shift;
+    above = sh.above;
+  }
+  *n_above = above;
+  return (uint32_t)prefix;
+}
+
+// sh.key[0 .. n) is a descending run of surviving keys; `rank` survivors of mass `head` lie above it.  Returns how many leading entries of
+// the run the nucleus keeps, *mass = the mass of the whole run (sum order: see the section comment).
+__device__ int warp_nucleus_run(WarpShared& sh, int n, float m, float Z, float head, int rank, float top_p, int min_keep, float* mass) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float p = tid < n ? expf(ford_inv(sh.key[tid]) - m) / Z : 0.f;
+  float inc = p;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const float u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+  const float lower = __shfl_up(inc, 1, 64);
+  __syncthreads();
+  if (lane == 63) sh.redf[wave] = inc;
+  if (tid == 0) sh.cnt = n;
+  __syncthreads();
+  float base = head, tot = 0.f;
+  for (int w = 0; w < kScanWaves; ++w) { if (w < wave) base += sh.redf[w]; tot += sh.redf[w]; }
+  const float before = lane ? base + lower : base;
+  if (tid < n && !(before < top_p || rank + tid < min_keep)) atomicMin(&sh.cnt, tid);
+  __syncthreads();
+  *mass = tot;
+  return sh.cnt;
+}
+
+__device__ void row_warp_cutoff_body(const WarpCutArgs& a, int r) {
+  __shared__ WarpShared sh;
+  const int tid = threadIdx.x;
+  int sg = 0, r0 = r;
+  while (sg < a.n_seg - 1 && r0 >= a.seg[sg].n) { r0 -= a.seg[sg].n; ++sg; }
+  const int node = a.seg[sg].node ? a.seg[sg].node[r0] : 0;
+  const int e0 = a.fsm.row_ptr[node];
+  const WarpRow row{a.logits + (size_t)r * a.ld, a.fsm.tok + e0, a.fsm.row_ptr[node + 1] - e0, a.lse[r], a.temperature};
+  const bool use_p = a.top_p < 1.f;
+  const int kk = a.top_k > 0 ? max(a.top_k, a.min_keep) : 0;     // 0 = top-k off
+  // finite entries and the largest key
+  int nf = 0;
+  uint32_t kmax = 0;
+  for (int j = tid; j < row.deg; j += kScanThreads) { const uint32_t o = row.key(j); nf += o ? 1 : 0; kmax = o > kmax ? o : kmax; }
+  nf = warp_block_sum_i(sh, nf);
+  kmax = warp_block_max_u32(sh, kmax);
+  float cut = -INFINITY;
+  const bool cut_k = kk > 0 && kk <= nf;
+  if (nf > 0 && (cut_k || use_p)) {
+    const float m = ford_inv(kmax);
+    if (row.deg <= kScanThreads) {
+      int n2 = 1;
+      while (n2 < row.deg) n2 <<= 1;
+      sh.key[tid] = tid < row.deg ? row.key(tid) : 0u;
+      warp_sort_desc(sh, n2);
+      int n_surv = nf;
+      if (cut_k) {
+        const uint32_t tk = sh.key[kk - 1];
+        n_surv = __syncthreads_count(sh.key[tid] >= tk);
+        cut = ford_inv(tk);
+      }
+      if (use_p) {
+        const float Z = warp_block_sum(sh, tid < n_surv ? expf(ford_inv(sh.key[tid]) - m) : 0.f);
+        float mass;
+        const int n_keep = warp_nucleus_run(sh, n_surv, m, Z, 0.f, 0, a.top_p, a.min_keep, &mass);
+        cut = ford_inv(sh.key[max(n_keep, 1) - 1]);
+      }
+    } else {
+      uint32_t tk = 1;                                 // survivors of top-k: keys >= tk
+      int above;
+      if (cut_k) { tk = warp_radix_select(sh, row, 1ull << 32, kk, &above); cut = ford_inv(tk); }
+      if (use_p) {
+        float z = 0.f;
+        for (int j = tid; j < row.deg; j += kScanThreads) { const uint32_t o = row.key(j); z += o >= tk ? expf(ford_inv(o) - m) : 0.f; }
+        const float Z = warp_block_sum(sh, z);
+        unsigned long long upper = 1ull << 32;         // survivors not yet walked: keys in [tk, upper)
+        float head = 0.f;
+        int rank = 0;
+        uint32_t last = kmax;
+        for (;;) {
+          int rem = 0;
+          for (int j = tid; j < row.deg; j += kScanThreads) { const uint32_t o = row.key(j); rem += (o >= tk && o < upper) ? 1 : 0; }
+          rem = warp_block_sum_i(sh, rem);
+          if (rem == 0) break;                         // every survivor of top-k is kept
+          // the next run: the keys in (lo, upper), fewer than 1024, and then the group of keys equal to lo; a last run takes [tk, upper)
+          const bool more = rem > kScanThreads;
+          uint32_t lo = tk;
+          if (more) lo = warp_radix_select(sh, row, upper, kScanThreads, &above);
+          __syncthreads();
+          sh.key[tid] = 0u;
+          if (tid == 0) sh.cnt = 0;
+          __syncthreads();
+          int n_eq = 0;
+          for (int j = tid; j < row.deg; j += kScanThreads) {
+            const uint32_t o = row.key(j);
+            n_eq += (more && o == lo) ? 1 : 0;
+            if (o < upper && (more ? o > lo : o >= lo)) { const int at = atomicAdd(&sh.cnt, 1); if (at < kScanThreads) sh.key[at] = o; }
+          }
+          n_eq = warp_block_sum_i(sh, n_eq);
+          const int n = min(sh.cnt, kScanThreads);
+          int n2 = 1;
+          while (n2 < n) n2 <<= 1;
+          warp_sort_desc(sh, n2);
+          float mass;
+          const int n_keep = warp_nucleus_run(sh, n, m, Z, head, rank, a.top_p, a.min_keep, &mass);
+          if (n_keep > 0) last = sh.key[n_keep - 1];
+          if (n_keep < n || !more) break;              // the boundary lies inside this run, or nothing is left below it
+          head += mass; rank += n;
+          if (!(head < a.top_p || rank < a.min_keep)) break;
+          last = lo;
+          const float p = expf(ford_inv(lo) - m) / Z;
+          for (int i = 0; i < n_eq; ++i) head += p;
+          rank += n_eq;
+          upper = lo;
+        }
+        cut = ford_inv(last);
+      }
+    }
+  }
+  if (tid == 0) a.cutoff[r] = cut;
+}
+
+__global__ __launch_bounds__(kScanThreads) void row_warp_cutoff_kernel(WarpCutArgs a) { row_warp_cutoff_body(a, blockIdx.x); }
+__global__ __launch_bounds__(kScanThreads) void row_warp_cutoff_multi_kernel(const WarpCutArgs* __restrict__ args) {
+  __shared__ WarpCutArgs a;                        // grid column = job: copy its argument block first
+  const int words = sizeof(WarpCutArgs) / 4;
+  for (int i = threadIdx.x; i < words; i += blockDim.x)
+    reinterpret_cast<uint32_t*>(&a)[i] = reinterpret_cast<const uint32_t*>(args + blockIdx.y)[i];
+  __syncthreads();
+  int rows = 0;
+  for (int s2 = 0; s2 < a.n_seg; ++s2) rows += a.seg[s2].n;
+  if ((int)blockIdx.x < rows) row_warp_cutoff_body(a, blockIdx.x);
+}
+
 // ---------------------------------------------------------------------------- beam step
 __device__ void beam_step_body(const BeamStepArgs& a);
 
@@ -459,7 +698,7 @@ __device__ void beam_step_body(const BeamStepArgs& a) {
   Pick pk;
   if (a.sample) {                                                        // beamSD.py:65-75
     CandRegs cr;
-    expand_candidates(sh, a.n_src, a.logits, a.ld, a.lse, a.fsm, a.temperature, cr);
+    expand_candidates(sh, a.n_src, a.logits, a.ld, a.lse, a.fsm, a.temperature, a.cutoff, cr);
     if (a.tab_score) {                                                   // the draft's whole distribution, for verify
       const float L = block_lse(sh, cr.sc);
       const int total = min(sh.off[a.n_src], kMaxCand);
@@ -562,7 +801,7 @@ __device__ void verify_sample_body(const VerifyArgs& a) {
     }
     __syncthreads();
     CandRegs cr;
-    expand_candidates(sh, n_rows, a.logits, a.ld, a.lse, a.fsm, a.temperature, cr);
+    expand_candidates(sh, n_rows, a.logits, a.ld, a.lse, a.fsm, a.temperature, a.cutoff, cr);
     if (i == a.dl) {                                                     // bonus draw from the target (:303-309)
       sample_topn(sh, cr, cr.sc, k, ats_rng_sub(a.seed, ATS_RNG_BONUS, a.round, i, 0));
       if (tid < k) {
@@ -882,6 +1121,50 @@ int ats_row_topk(const float* logits, int n_rows, int vocab, int ld, int kk, int
   row_topk_kernel<<<n_rows, kScanThreads, 0, st>>>(logits, vocab, ld, kk, out);
   ATS_LAUNCH_CHECK();
   return ATSPEED_OK;
+}
+
+std::atomic<long long> g_ats_warp_launches{0};
+
+static int warp_cut_check(const WarpCutArgs& a, int* rows_out) {
+  ATS_REQUIRE(a.n_seg >= 1 && a.n_seg <= ATSPEED_MAX_GAMMA + 1 && a.fsm.n_nodes > 0, ATSPEED_ERR_INVALID, "warp cutoffs: need an automaton and 1..%d row segments",
+              ATSPEED_MAX_GAMMA + 1);
+  ATS_REQUIRE(a.temperature > 0.f && a.top_k >= 0 && a.top_p > 0.f && a.min_keep >= 1, ATSPEED_ERR_INVALID,
+              "warp cutoffs: temperature %g / top_k %d / top_p %g / min_tokens_to_keep %d out of range", (double)a.temperature, a.top_k, (double)a.top_p, a.min_keep);
+  int rows = 0;
+  for (int s = 0; s < a.n_seg; ++s) { ATS_REQUIRE(a.seg[s].n >= 0, ATSPEED_ERR_INVALID, "warp cutoffs: negative row count"); rows += a.seg[s].n; }
+  *rows_out = rows;
+  return ATSPEED_OK;
+}
+
+int ats_row_warp_cutoff(const WarpCutArgs& a, hipStream_t st) {
+  int rows = 0;
+  ATS_TRY(warp_cut_check(a, &rows));
+  if (rows == 0) return ATSPEED_OK;
+  row_warp_cutoff_kernel<<<rows, kScanThreads, 0, st>>>(a);
+  ATS_LAUNCH_CHECK();
+  g_ats_warp_launches.fetch_add(1, std::memory_order_relaxed);
+  return ATSPEED_OK;
+}
+
+int ats_row_warp_cutoff_multi(const WarpCutArgs* dev_args, int n, int max_rows, hipStream_t st) {
+  if (n <= 0 || max_rows <= 0) return ATSPEED_OK;
+  ATS_REQUIRE(n <= 65535, ATSPEED_ERR_CAPACITY, "warp cutoffs: %d jobs per launch (max 65535)", n);
+  row_warp_cutoff_multi_kernel<<<dim3(max_rows, n), kScanThreads, 0, st>>>(dev_args);
+  ATS_LAUNCH_CHECK();
+  g_ats_warp_launches.fetch_add(1, std::memory_order_relaxed);
+  return ATSPEED_OK;
+}
+
+extern "C" int64_t atspeed_warp_cutoff_launches(void) { return (int64_t)g_ats_warp_launches.load(std::memory_order_relaxed); }
+
+extern "C" int atspeed_warp_cutoffs(const float* logits, int32_t ld, const float* lse, int32_t n_rows, const atspeed_fsm* fsm, const int32_t* nodes,
+                                    float temperature, int32_t top_k, float top_p, int32_t min_keep, float* cutoffs, void* stream) {
+  ATS_REQUIRE(logits && lse && fsm && nodes && cutoffs && n_rows >= 0 && ld > 0, ATSPEED_ERR_INVALID, "warp_cutoffs: bad arguments");
+  WarpCutArgs a{};
+  a.seg[0] = WarpSeg{nodes, n_rows}; a.n_seg = 1;
+  a.logits = logits; a.ld = ld; a.lse = lse; a.fsm = fsm->dev;
+  a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.min_keep = min_keep; a.cutoff = cutoffs;
+  return ats_row_warp_cutoff(a, (hipStream_t)stream);
 }
 
 int ats_beam_step(const BeamStepArgs& a, hipStream_t st) {

@@ -19,7 +19,8 @@ Stage times (`draft/target/verify_time_cost`, the CSV columns inference.py:183-1
 synchronisation at the end of each stage, as the reference's Timer measures them (beamSD.py:12-37).
 
 Sampling mode (`generation_config.do_sample`, beamSD.py:65-75,293-321,332-369) with a host-side mask or processors: forwards and the
-full-vocabulary log-softmax stay in the library; the tempered, masked rows of a step (<= DK x V fp32, 5 MB) come to the host, where the draws
+full-vocabulary log-softmax stay in the library; the tempered, masked rows of a step (<= DK x V fp32, 5 MB) come to the host, where
+transformers' own TopKLogitsWarper / TopPLogitsWarper warp them when the config sets `top_k` / `top_p` (`_hf_warpers`) and the draws
 are made from the SAME counter-based streams the device kernels use (`_HashRng`: (seed, purpose, round, step, model) -> sub-seed, one hash per
 candidate id; scan.hip) -- so a callable that wraps a compilable constraint samples exactly what the device path samples for that seed
 (tests/test_bssd_gpu.py).
@@ -176,11 +177,26 @@ def _expand(model, logits, lse, row_ids, beam_scores, seqs, fn, procs, k):
     return _expand_prune(model, logits, lse, row_ids, beam_scores, _allowed_lists(fn, seqs), k)
 
 
+def _hf_warpers(top_k: int, top_p: float, min_keep: int) -> List[Callable]:
+    """what `_get_logits_warper` puts after the temperature for a beam search: transformers' own top-k, then top-p (0 / >= 1 = off)"""
+    out: List[Callable] = []
+    if top_k or top_p < 1.0:
+        from transformers import TopKLogitsWarper, TopPLogitsWarper
+        if top_k:
+            out.append(TopKLogitsWarper(top_k=int(top_k), min_tokens_to_keep=int(min_keep)))
+        if top_p < 1.0:
+            out.append(TopPLogitsWarper(top_p=float(top_p), min_tokens_to_keep=int(min_keep)))
+    return out
+
+
 def _tempered_rows(model: HipLlama, logits, lse, row_ids: Sequence[int], seqs: np.ndarray, fn: Optional[Callable], procs: Sequence[Callable],
-                   temperature: float) -> np.ndarray:
-    """processed rows -> temperature warper (:65-66, :293-294) -> host fp32 [n, V]"""
+                   temperature: float, warpers: Sequence[Callable] = ()) -> np.ndarray:
+    """processed rows -> temperature warper (:65-66, :293-294) -> top-k / top-p warpers on the host rows -> host fp32 [n, V]"""
     with torch.cuda.device(model.device):
-        return (_processed_rows(model, logits, lse, row_ids, seqs, fn, procs) / float(temperature)).cpu().numpy()
+        rows = (_processed_rows(model, logits, lse, row_ids, seqs, fn, procs) / float(temperature)).cpu()
+    for w in warpers:
+        rows = w(None, rows)
+    return rows.numpy()
 
 
 def _keep_ids(t: np.ndarray, s: Optional[np.ndarray] = None) -> np.ndarray:
@@ -259,12 +275,13 @@ def _greedy_step(model, inp, k, beam_scores, beam_seq, stream, fn, procs) -> Dic
     return _one_step(model, inp, k, beam_scores, beam_seq, pick)
 
 
-def _sample_step(model, inp, k, beam_scores, beam_seq, stream, fn, procs, temperature, rng) -> Dict:
+def _sample_step(model, inp, k, beam_scores, beam_seq, stream, fn, procs, temperature, rng, warpers=()) -> Dict:
     """a step with do_sample (:65-75): k draws without replacement from softmax of the flattened scores; stream = (round, step, model tag)"""
     V = model.dims.vocab_size
 
     def pick(logits, lse, n, seqs):
-        flat = (_tempered_rows(model, logits, lse, range(n), seqs, fn, procs, temperature) + np.asarray(beam_scores, np.float32)[:, None]).reshape(-1)
+        flat = (_tempered_rows(model, logits, lse, range(n), seqs, fn, procs, temperature, warpers)
+                + np.asarray(beam_scores, np.float32)[:, None]).reshape(-1)
         rng.begin(P_STEP, *stream)
         idx = rng.multinomial_log(flat, k)
         s = flat[idx]
@@ -291,19 +308,22 @@ def _final_sort(seq: np.ndarray, scores: np.ndarray):
     return seq[o], scores[o]
 
 
-def _sampling_kw(fn, procs, sample) -> Dict:
-    temperature, seed = sample
-    return dict(fn=fn, procs=procs, temperature=temperature, rng=_HashRng(seed))
+def _sampling_kw(fn, procs, sample, num_beams: int) -> Dict:
+    """`sample` = (temperature, seed) or (temperature, seed, top_k, top_p); the warpers' min_tokens_to_keep follows the TARGET's beam count, as
+    the reference builds one warper list from the target's config for both models (beamSD.py:479-481)"""
+    temperature, seed = sample[:2]
+    top_k, top_p = sample[2:] if len(sample) > 2 else (0, 1.0)
+    return dict(fn=fn, procs=procs, temperature=temperature, rng=_HashRng(seed), warpers=_hf_warpers(top_k, top_p, 2 if num_beams > 1 else 1))
 
 
 def target_generate_host_mask(model: HipLlama, prompt: np.ndarray, max_new_tokens: int, fn: Optional[Callable],
                               procs: Sequence[Callable] = (), sample=None) -> Dict:
     """target_generate (beamSD.py:544-595) with the mask function / logits processors on the host; `sample` = (temperature, seed) with
-    `generation_config.do_sample`."""
+    `generation_config.do_sample`, optionally followed by (top_k, top_p)."""
     if sample is None:
         seq, scores = _beam_search(model, prompt, max_new_tokens, partial(_greedy_step, fn=fn, procs=procs))
     else:
-        seq, scores = _final_sort(*_beam_search(model, prompt, max_new_tokens, partial(_sample_step, **_sampling_kw(fn, procs, sample))))
+        seq, scores = _final_sort(*_beam_search(model, prompt, max_new_tokens, partial(_sample_step, **_sampling_kw(fn, procs, sample, int(model.generation_config.num_beams)))))
     return dict(beam_sequence=seq, beam_scores=scores)
 
 
@@ -351,13 +371,13 @@ def _greedy_decide(target, logits, lse, k, step: _VerifyStep, fn, procs):
     return s[order], parents, t, hit
 
 
-def _sample_decide(target, logits, lse, k, step: _VerifyStep, fn, procs, temperature, rng):
+def _sample_decide(target, logits, lse, k, step: _VerifyStep, fn, procs, temperature, rng, warpers=()):
     """verify with do_sample (beamSD.py:293-321 distributions, :332-369 accept / resample, :303-309 bonus draw).  One documented deviation,
     as on the device path: with no residual mass left the remaining draws come from the target distribution (the reference resamples
     uniformly over the whole vocabulary, -inf scores included)."""
     V = target.dims.vocab_size
     stream, drafted = step.stream, step.drafted
-    bs = _tempered_rows(target, logits, lse, step.rows, step.seqs, fn, procs, temperature) + np.asarray(step.scores, np.float32)[:, None]
+    bs = _tempered_rows(target, logits, lse, step.rows, step.seqs, fn, procs, temperature, warpers) + np.asarray(step.scores, np.float32)[:, None]
     if step.hit is not None:                                                        # :311-321: into the draft's beam space
         tbs = np.full((step.n_draft, V), -np.inf, dtype=np.float32)
         tbs[step.hit] = bs
@@ -486,7 +506,7 @@ def bssd_host_mask(target: HipLlama, draft: HipLlama, prompt: np.ndarray, gamma:
     if sample is None:
         kw = dict(fn=fn, procs=procs)
         return _bssd(target, draft, prompt, gamma, max_new_tokens, partial(_greedy_step, **kw), partial(_greedy_decide, **kw))
-    kw = _sampling_kw(fn, procs, sample)
+    kw = _sampling_kw(fn, procs, sample, int(target.generation_config.num_beams))
     out = _bssd(target, draft, prompt, gamma, max_new_tokens, partial(_sample_step, **kw), partial(_sample_decide, **kw))
     out["beam_sequence"], out["beam_scores"] = _final_sort(out["beam_sequence"], out["beam_scores"])
     return out

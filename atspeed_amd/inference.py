@@ -58,6 +58,11 @@ def parse(argv=None):
     ap.add_argument("--dtype", choices=("auto", "fp16", "bf16", "fp32"), default="auto",
                     help="engine arithmetic.  auto: a checkpoint runs in the type it is stored in (fp16 -- what the reference loads, inference.py:75-100 -- "
                          "takes the engine's fp16 flavour and keeps every weight bit; bf16 and fp32 likewise), synthetic weights are bf16")
+    ap.add_argument("--do_sample", action="store_true", help="sampling branch (the reference's flag, inference.py:149): beams are drawn, not the top-K")
+    ap.add_argument("--temperature", type=float, default=1.0, help="with --do_sample (inference.py:150)")
+    ap.add_argument("--top_k", type=int, default=None, help="with --do_sample: top-k warper (0 = off); default: the model's generation config "
+                                                             "(an HF checkpoint's default is 50, synthetic weights have none)")
+    ap.add_argument("--top_p", type=float, default=None, help="with --do_sample: top-p warper (1.0 = off); default: the model's generation config")
     ap.add_argument("--baseline", action="store_true", help="also time target_generate per user (speedup / overhead columns)")
     ap.add_argument("--output_dir", type=str, default="AnaResult")
     args = ap.parse_args(argv)
@@ -65,6 +70,8 @@ def parse(argv=None):
         ap.error("--target_fp8 makes its e4m3 copies from 16-bit weights: use --dtype auto, fp16 or bf16")
     if args.target_fp4 and args.dtype == "fp32":
         ap.error("--target_fp4 makes its MXFP4 copies from 16-bit weights: use --dtype auto, fp16 or bf16")
+    if (args.top_k is not None or args.top_p is not None) and not args.do_sample:
+        ap.error("--top_k / --top_p warp sampled scores: they need --do_sample")
     if args.target_fp4 and args.target_fp8:
         ap.error("--target_fp4 and --target_fp8 are exclusive: choose one target precision")
     return args
@@ -91,6 +98,13 @@ def load_models(args, vocab_size: int, beam: int, dev, max_prompt: int = 0):
         drf = HipLlama.from_synthetic(synth.llama_68m(vocab_size), args.seed + 1, dtype=syn, num_beams=args.draft_beam_size, resid_scale=rs, **kw)
         tgt = HipLlama.from_synthetic(synth.llama_7b(vocab_size, args.target_layers), args.seed, dtype=syn, num_beams=beam, resid_scale=rs,
                                       align_to=drf if args.aligned is not None else None, **kw)
+    if args.do_sample:                      # inference.py:149-150; the warpers are read from the target's config (beamSD.py:479-481)
+        for m in (tgt, drf):
+            m.generation_config.do_sample, m.generation_config.temperature = True, args.temperature
+            if args.top_k is not None:
+                m.generation_config.top_k = args.top_k
+            if args.top_p is not None:
+                m.generation_config.top_p = args.top_p
     if args.target_fp8:
         tgt.enable_fp8()
     if args.target_fp4:

@@ -196,6 +196,12 @@ class HipLlama:
         m.generation_config.do_sample = bool(getattr(hf_model.generation_config, "do_sample", False))
         temp = getattr(hf_model.generation_config, "temperature", None)
         m.generation_config.temperature = 1.0 if temp is None else float(temp)
+        # the sampling-mode warpers `_get_logits_warper` reads: an HF config defaults to top_k = 50, top_p = 1.0 (beamSD._warpers)
+        # transformers 4.41 holds these defaults in the config itself; 5.x leaves an unset field None and fills the same values in when
+        # generating.  Either way None on the HF config means the default, so an unset top_k is 50: set `top_k = 0` for the temperature alone.
+        for name, default in (("top_k", 50), ("top_p", 1.0)):
+            v = getattr(hf_model.generation_config, name, None)
+            setattr(m.generation_config, name, default if v is None else v)
         return m
 
     @classmethod

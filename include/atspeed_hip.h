@@ -272,6 +272,28 @@ void atspeed_decoder_destroy(atspeed_decoder* d);
  * rand / randperm draws (statistical parity).  Applies to the bssd and target_generate calls made with this decoder. */
 int atspeed_decoder_set_sampling(atspeed_decoder* d, int32_t do_sample, float temperature, uint32_t seed);
 
+/* Sampling-mode warpers of a decoder: what transformers' `_get_logits_warper` puts after the temperature for a beam search,
+ * TopKLogitsWarper(top_k, min_tokens_to_keep) then TopPLogitsWarper(top_p, min_tokens_to_keep) (beamSD.py:479-481, applied at :65-66 and
+ * :293-294).  top_k = 0 and top_p >= 1 switch a warper off (the default: both off, nothing new is launched and every result is what it was
+ * without this call); min_tokens_to_keep is 2 for a beam search with more than one beam, else 1.  Only sampled calls look at them: in
+ * every sampled step and verify walk a candidate below its row's cutoff is absent (score -inf, probability 0) for the draws, the
+ * draft's q, the target's p, the residual and the bonus draw. */
+int atspeed_decoder_set_warpers(atspeed_decoder* d, int32_t top_k, float top_p, int32_t min_tokens_to_keep);
+
+/* The kernel behind it, bare: cutoffs_out[r] for r < n_rows, where row r of `logits` (leading dimension ld, normaliser lse[r]) sits at
+ * automaton node nodes[r] and its entries are that node's children scored s = (logit - lse) / temperature.
+ *   top-k: k' = max(top_k, min_tokens_to_keep); with at least k' finite entries everything strictly below the k'-th largest is cut
+ *          (ties with it survive), with fewer nothing is;
+ *   top-p: on what top-k left, in descending order an entry is kept while the softmax mass strictly above it is below top_p, the first
+ *          min_tokens_to_keep always.
+ * A candidate survives iff s >= cutoffs_out[r]; -inf = nothing cut (both warpers off, or a row without finite entries).  Rows of any
+ * length: up to 1024 children are sorted in LDS, longer lists go through a radix select.  atspeed_warp_cutoff_launches: launches of
+ * this kernel by the process so far, decoders included (greedy calls and calls with both warpers off make none). */
+int atspeed_warp_cutoffs(const float* logits_dev, int32_t ld, const float* lse_dev, int32_t n_rows, const atspeed_fsm* fsm,
+                         const int32_t* nodes_dev, float temperature, int32_t top_k, float top_p, int32_t min_tokens_to_keep,
+                         float* cutoffs_out_dev, void* stream);
+int64_t atspeed_warp_cutoff_launches(void);
+
 typedef struct atspeed_gen_stats {
   int32_t n_run;               /* verification rounds (beamSD.py:527)                 */
   int32_t total_accept_steps;  /* sum of n_matches (beamSD.py:528)                    */
