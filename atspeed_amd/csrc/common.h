@@ -112,6 +112,38 @@ template <int ESZ>
 __host__ __device__ inline size_t ats_opnd_idx(int pk, size_t row, size_t col, size_t ld) {
   return pk ? ats_pk_byte(row, col * ESZ, ld * ESZ) / ESZ : row * ld + col;
 }
+// The same map as the GEMM kernels' loads and LDS-DMAs use it, in their own index type I (32-bit lane offsets in the LDS-DMA kernels, size_t
+// elsewhere): the 16-byte chunk c of the RB bytes of row `row` that one LDS row holds (RB = 64 or 128, c < RB / 16), ld_bytes per row:
+//   ats_chunk_byte<RB>(pk, row, ld_bytes, c) == pk ? ats_pk_byte(row, c * 16, ld_bytes) : row * ld_bytes + c * 16
+// and the next RB bytes of the row lie ats_kadv<RB>(pk) further on: RB row-major, 2 RB packed (ats_pk_byte(r, b + 64, .) - ats_pk_byte(r, b, .)
+// == 128).  ats_pk_byte itself where a kernel computes in size_t anyway (gemm_w4a8_kernel).
+template <int RB, typename I, typename R>
+__host__ __device__ inline I ats_chunk_byte(int pk, R row, I ld_bytes, int c) {
+  static_assert(RB == 64 || RB == 128, "one or two 64-byte k-blocks per LDS row");
+  if constexpr (RB == 64) return (pk ? (I)(row >> 1) * (ld_bytes * 2) + (row & 1) * 64 : (I)row * ld_bytes) + (c * 16);
+  else return pk ? (I)(row >> 1) * (ld_bytes * 2) + (row & 1) * 64 + (I)(c >> 2) * 128 + (c & 3) * 16 : (I)row * ld_bytes + (I)c * 16;
+}
+template <int RB> __host__ __device__ constexpr int ats_kadv(int pk) { return pk ? 2 * RB : RB; }
+
+// ---------------------------------------------------------------- GEMM work division (host + device: the walk can be checked on the CPU)
+// Workgroup id -> tile (tn, tm) of the ring GEMMs' tiles_n x tiles_m grid, in two steps.  xcd_run: workgroup L runs on XCD L % 8 (private 4 MB
+// L2); every XCD gets a contiguous run of the nwg positions, the first nwg % 8 of them one position longer.  band_tile: the positions walk
+// bands of GM token-tile rows (the last band may be lower), W-panel-major inside a band.  A bijection of [0, nwg) onto the grid.
+struct GemmTile { int tn, tm; };
+__host__ __device__ inline int xcd_run(int bid, int nwg) {
+  const int q = nwg / 8, r = nwg % 8, x = bid % 8;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
+}
+__host__ __device__ inline GemmTile band_tile(int pos, int tiles_n, int tiles_m, int GM) {
+  const int band = pos / (GM * tiles_n), rem = pos % (GM * tiles_n);
+  const int left = tiles_m - band * GM, band_rows = GM < left ? GM : left;
+  return GemmTile{rem / band_rows, band * GM + rem % band_rows};
+}
+__host__ __device__ inline GemmTile tile_walk(int bid, int tiles_n, int tiles_m, int GM) {
+  return band_tile(xcd_run(bid, tiles_n * tiles_m), tiles_n, tiles_m, GM);
+}
+// `units` units of k dealt to n_split parts: part z takes [part_begin(z), part_begin(z + 1)), the parts' sizes differing by one unit at most
+__host__ __device__ inline int part_begin(int z, int units, int n_split) { return (int)((long long)z * units / n_split); }
 
 // counter-based hash shared by the synthetic-weight fill and the sampling kernels (= atspeed_amd/synth.py:hash_u32)
 __host__ __device__ inline uint32_t ats_fmix32(uint32_t h) {
@@ -279,6 +311,19 @@ __device__ __forceinline__ uint32_t swiglu_pk(float g0, float g1, float u0, floa
 template <typename T> __device__ __forceinline__ float swiglu(float g, float u) {      // the caller's store rounds
   return ats_silu<sizeof(T) == 4>(round_elt<T>(g)) * round_elt<T>(u);
 }
+// four adjacent accumulators -> two packed 16-bit words (a lane's four columns of a row); the (gate, up) form: four SwiGLU outputs
+__device__ __forceinline__ uint2 f2bf_pk4(float a, float b, float c, float d) { return make_uint2(f2bf_pk(a, b), f2bf_pk(c, d)); }
+__device__ __forceinline__ uint2 f2bf_pk4(const f32x4_t& v) { return f2bf_pk4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ uint2 swiglu_pk4(const f32x4_t& g, const f32x4_t& u) {
+  return make_uint2(swiglu_pk(g[0], g[1], u[0], u[1]), swiglu_pk(g[2], g[3], u[2], u[3]));
+}
+
+// Online softmax: (mx, sm) = running maximum and sum of exp(x - mx); merged with another such pair (om, os).  Two empty pairs stay empty.
+__device__ __forceinline__ void lse_merge(float& mx, float& sm, float om, float os) {
+  const float nm = fmaxf(mx, om);
+  sm = (nm > -INFINITY) ? sm * __expf(mx - nm) + os * __expf(om - nm) : 0.f;
+  mx = nm;
+}
 
 // OCP e4m3 with a per-row scale: scale = max|x| / 448 (1 for an all-zero row), q = e4m3(clamp(x / scale, +-448)), x the 16-bit-rounded value
 // (the fused producers quantise what the separate pass would read back).  inv = 1 / scale.
@@ -312,7 +357,7 @@ __device__ __forceinline__ void store4(float* p, const f32x4_t& v, int gn, int N
 template <bool RESID = false>
 __device__ __forceinline__ void store4(bf16_t* p, const f32x4_t& v, int gn, int N, bool vec) {
   if (gn + 3 < N && vec) {
-    uint2 o = make_uint2(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]));
+    uint2 o = f2bf_pk4(v);
     if constexpr (RESID) { const uint2 h = *reinterpret_cast<const uint2*>(p); o.x = resid_pk(h.x, o.x); o.y = resid_pk(h.y, o.y); }
     *reinterpret_cast<uint2*>(p) = o;
   } else {
@@ -323,6 +368,17 @@ __device__ __forceinline__ void store4(bf16_t* p, const f32x4_t& v, int gn, int 
         else p[r] = f2bf(v[r]);
       }
   }
+}
+// A GEMM epilogue's output by its kind, c = the output's base and idx the element: fp32 store (F32), residual add on what c holds (RESID),
+// else a plain store as T.  One value; and a lane's four adjacent columns (store4's arguments).
+template <typename T, bool F32, bool RESID> __device__ __forceinline__ void store_epi(void* c, size_t idx, float v) {
+  if constexpr (F32) reinterpret_cast<float*>(c)[idx] = v;
+  else if constexpr (RESID) resid_add(reinterpret_cast<T*>(c) + idx, v);
+  else Elt<T>::store(reinterpret_cast<T*>(c) + idx, v);
+}
+template <bool F32, bool RESID> __device__ __forceinline__ void store4_epi(void* c, size_t idx, const f32x4_t& v, int gn, int N, bool vec) {
+  if constexpr (F32) store4(reinterpret_cast<float*>(c) + idx, v, gn, N, vec);
+  else store4<RESID>(reinterpret_cast<bf16_t*>(c) + idx, v, gn, N, vec);
 }
 
 // Sum / maximum over a workgroup of NW waves through its __shared__ red[NW].  The per-wave partials are combined left to right, ((r0 + r1) + r2) + ...:

@@ -34,6 +34,20 @@ static float big_rounds(int tiles) {
   return (float)full + (rem ? 0.55f + 0.45f * (float)rem / 256.f : 0.f);
 }
 static bool big_use_256_rows(int t256, int t128) { return big_rounds(t256) <= 0.65f * big_rounds(t128); }
+// tile counts of the 256-wide ring kernels at (m, n): weight panels, token-tile rows and tiles with 256- and with 128-row token tiles
+struct RingGrid {
+  int tn, tm256, tm128, t256, t128;
+  RingGrid(int m, int n) : tn((n + 255) / 256), tm256((m + 255) / 256), tm128((m + 127) / 128), t256(tn * tm256), t128(tn * tm128) {}
+  int tm(bool rows256) const { return rows256 ? tm256 : tm128; }
+};
+// the K-cut forms of both ring kernels: 128-row token tiles while two parts of them fit a round of 256 workgroups, else 256-row ones; as many
+// parts as fit the round, max_parts at most; 0: fewer than two
+static int cut_split_count(const RingGrid& g, int max_parts, bool* rows256) {
+  const bool r256 = g.t128 > 128;
+  if (rows256) *rows256 = r256;
+  const int s_ = std::min(256 / (r256 ? g.t256 : g.t128), max_parts);
+  return s_ >= 2 ? s_ : 0;
+}
 
 // ---- split-K tail of the ring kernel (gemm_ring_kernel<..., SK = true>): plan and cost model, host side.
 // The kernel accepts any even deal of the tail's k-units over G workgroups; the plans made here are the ALIGNED ones, G = R x S: each of the
@@ -143,8 +157,10 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const T* __restrict__ A,
   // per-thread source offsets (bytes) of its 16-byte chunks at k-tile 0, computed once: row-major  row * ld * esz + chunk * 16;
   // packed  (row >> 1) * 2 * ld * esz + (row & 1) * 64 + (chunk >> 2) * 128 + (chunk & 3) * 16  (a 128-byte k-tile is two 64-byte blocks,
   // each in the line its row pair shares).  A k-tile later is 128 bytes further on row-major rows, 256 on packed ones.
+  // (= ats_chunk_byte<128> + this part's first k byte, restated: through the helper the prologue came out 8-36 instructions longer and
+  // three of the one-user target's shapes 0.3-1.7 % slower, profiles/gemm_refactor_isa_and_speed.txt; as written the kernel is the parent's)
   constexpr int ESZ = (int)sizeof(T);
-  const size_t kstep = pk ? 256 : 128;
+  const size_t kstep = ats_kadv<kRowBytes>(pk);
   size_t aoff[Cfg::A_PER_THREAD], woff[Cfg::W_PER_THREAD];
   const size_t k0b = (size_t)kz0 * ESZ;                       // multiple of 128 (k_per_split is a multiple of BK)
 #pragma unroll
@@ -288,16 +304,7 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const T* __restrict__ A,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           int gm = wrow0 + i * 16 + crow + r, gn = wcol0 + j * 16 + ccol;
-          if (gm < M && gn < N) {
-            float v = acc[i][j][r];
-            if constexpr (EPI == EPI_F32) {
-              reinterpret_cast<float*>(Cv)[(size_t)gm * ldc + gn] = v;
-            } else if constexpr (EPI == EPI_RESID) {
-              resid_add(reinterpret_cast<T*>(Cv) + (size_t)gm * ldc + gn, v);
-            } else {
-              Elt<T>::store(reinterpret_cast<T*>(Cv) + (size_t)gm * ldc + gn, v);
-            }
-          }
+          if (gm < M && gn < N) store_epi<T, EPI == EPI_F32, EPI == EPI_RESID>(Cv, (size_t)gm * ldc + gn, acc[i][j][r]);
         }
   }
 }
@@ -330,15 +337,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ partial, void* __
     float v[V];
     sum_slabs<V>(partial + i, mn, splits, v);
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      if constexpr (EPI == EPI_F32) {
-        reinterpret_cast<float*>(Cv)[(size_t)m * ldc + n + j] = v[j];
-      } else if constexpr (EPI == EPI_RESID) {
-        resid_add(reinterpret_cast<T*>(Cv) + (size_t)m * ldc + n + j, v[j]);
-      } else {
-        Elt<T>::store(reinterpret_cast<T*>(Cv) + (size_t)m * ldc + n + j, v[j]);
-      }
-    }
+    for (int j = 0; j < V; ++j) store_epi<T, EPI == EPI_F32, EPI == EPI_RESID>(Cv, (size_t)m * ldc + n + j, v[j]);
   }
 }
 
@@ -380,10 +379,7 @@ __device__ __forceinline__ void big_epilogue(f32x4_t (&acc)[NA][MT2], void* __re
     bf16_t* Cb = reinterpret_cast<bf16_t*>(Cv);
     if ((ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(Cv) & 15) == 0 && nw + NA * 16 <= N) {
       // lane (., g) owns columns nw + q*64 + g*16 + [0, 16): tiles 4q + (0, 1) are the first eight, 4q + (2, 3) the second eight
-      auto pack8 = [&](int i0, int j) {
-        return make_uint4(f2bf_pk(acc[i0][j][0], acc[i0][j][1]), f2bf_pk(acc[i0][j][2], acc[i0][j][3]),
-                          f2bf_pk(acc[i0 + 1][j][0], acc[i0 + 1][j][1]), f2bf_pk(acc[i0 + 1][j][2], acc[i0 + 1][j][3]));
-      };
+      auto pack8 = [&](int i0, int j) { const uint2 a = f2bf_pk4(acc[i0][j]), b = f2bf_pk4(acc[i0 + 1][j]); return make_uint4(a.x, a.y, b.x, b.y); };
       auto col8 = [&](int i0) { return nw + (i0 >> 2) * 64 + g * 16 + ((i0 & 3) >> 1) * 8; };
       if constexpr (EPI == EPI_RESID) {
         // read-modify-write of h: the loads of a row group must not wait behind the previous group's stores (same pointer: the compiler
@@ -435,7 +431,6 @@ __device__ __forceinline__ void big_epilogue(f32x4_t (&acc)[NA][MT2], void* __re
     // lane (., g) owns outputs q*32 + g*8 + [0, 8) of the wave's NA*8: gate in tiles 4q and 4q+2, up in 4q+1 and 4q+3
     bf16_t* C = reinterpret_cast<bf16_t*>(Cv);
     const bool vec16 = (ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(Cv) & 15) == 0;
-    auto silu_mul = [&](int ig, int j, int r) { return swiglu_pk(acc[ig][j][r], acc[ig][j][r + 1], acc[ig + 1][j][r], acc[ig + 1][j][r + 1]); };
 #pragma unroll
     for (int j = 0; j < MT2; ++j) {
       const int gm = m0 + wm * (MT2 * 16) + j * 16 + lq;
@@ -444,7 +439,8 @@ __device__ __forceinline__ void big_epilogue(f32x4_t (&acc)[NA][MT2], void* __re
       for (int q = 0; q < NA / 4; ++q) {
         if (nw + q * 64 + (g >> 1) * 32 >= N) continue;            // N % 32 == 0: a (gate, up) group of 16 outputs is inside N or not at all
         const int oc = (nw >> 1) + q * 32 + g * 8;
-        const uint4 o = make_uint4(silu_mul(4 * q, j, 0), silu_mul(4 * q, j, 2), silu_mul(4 * q + 2, j, 0), silu_mul(4 * q + 2, j, 2));
+        const uint2 lo = swiglu_pk4(acc[4 * q][j], acc[4 * q + 1][j]), hi = swiglu_pk4(acc[4 * q + 2][j], acc[4 * q + 3][j]);
+        const uint4 o = make_uint4(lo.x, lo.y, hi.x, hi.y);
         bf16_t* dst = C + ats_opnd_idx<2>(pk, gm, oc, ldc);        // the down projection's operand: packed when pk (8 outputs stay inside a 64-byte block)
         if (vec16) epi_store16(dst, o);
         else { *reinterpret_cast<uint2*>(dst) = make_uint2(o.x, o.y); *reinterpret_cast<uint2*>(dst + 4) = make_uint2(o.z, o.w); }
@@ -483,7 +479,7 @@ __device__ __forceinline__ void qkv_rope_epilogue(f32x4_t (&acc)[NA][MT2], bf16_
   const int H = rp.hidden;
   const int sec = n0 / H;                                         // 0 q, 1 k, 2 v (uniform over the workgroup)
   const int fsec = n0 - sec * H;                                  // the tile's first column inside q / k / v
-  auto pack4 = [&](int i, int j) { return make_uint2(f2bf_pk(acc[i][j][0], acc[i][j][1]), f2bf_pk(acc[i][j][2], acc[i][j][3])); };
+  auto pack4 = [&](int i, int j) { return f2bf_pk4(acc[i][j]); };
   if (sec == 2) {
 #pragma unroll
     for (int j = 0; j < MT2; ++j) {
@@ -499,7 +495,7 @@ __device__ __forceinline__ void qkv_rope_epilogue(f32x4_t (&acc)[NA][MT2], bf16_
     }
     return;
   }
-  uint2* ex = reinterpret_cast<uint2*>(smem);                     // [wave][j][i][lane]: 8 x MT2 x 4 x 64 x 8 B = 128 / 64 KB, within the ring's own size
+  uint2* ex = reinterpret_cast<uint2*>(smem);                     // [wave][j][i][lane]: 8 x MT2 x 4 x 64 x 8 B = RingTile::EXCH, inside the ring
   __syncthreads();                                                // slower waves may still be reading the ring's last stages
 #pragma unroll
   for (int j = 0; j < MT2; ++j)
@@ -561,9 +557,10 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
 //     32 MFMAs of k-step s, so neither is a burst;
 //   * one barrier per k-step both publishes k-step s+2 and retires the reads of k-step s+1.
 // Both operands arrive by LDS-DMA (global_load_lds_dwordx4, saddr + 32-bit lane offset, M0 = destination): no VGPR round
-// trip.  LDS image of a stage: W rows then X rows, 64 B each; the 16-byte chunk c of row r sits at position
-// c ^ f((r>>2)&3), f = {2,0,1,3}, applied on the per-lane SOURCE address (the DMA destination is lane-linear) and on the
-// fragment reads: conflict-free for ds_read_b128's lane groups ({0-3,12-15,20-27},...) with 64-byte rows (PMC: 0 conflicts).
+// trip.  LDS image of a stage (RingTile below: STAGE, RING, and what the epilogues put in or behind the ring): W rows then X rows,
+// 64 B each; the 16-byte chunk c of row r sits at position c ^ f((r>>2)&3), f = {2,0,1,3} (ring_swz), applied on the per-lane SOURCE
+// address (RingTile::dma_src; the DMA destination is lane-linear) and on the fragment reads (ATS_RING_FRAG_OFF): conflict-free for
+// ds_read_b128's lane groups ({0-3,12-15,20-27},...) with 64-byte rows (PMC: 0 conflicts).
 // Workgroup ids are remapped so that each XCD (private 4 MB L2) walks a contiguous run of tiles, inside it bands of GM
 // tile rows, W-panel-major: the ~32 tiles an XCD runs at once share GM X panels and 8 W panels.
 // Result on MI355X: MFMA pipe 74 % busy at ~1.55 GHz (the chip lowers its clock under this load), 1.15-1.25 PF on the
@@ -574,6 +571,76 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
 // -Winline-asm "clobber list contains reserved registers ... may lead to undefined behaviour".)
 #define ATS_DMA16(voff, sbase, m0v) \
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(m0v) : "memory")
+
+// Geometry of the four-stage ring, for both ring kernels and their launchers: WN x WM waves, a wave holding NA x MT2 16-row tiles (the
+// block-scaled kernel: the same rows as 32-row tiles).  The 256 x 256 / 256 x 128 tile is RingTile<8> / RingTile<4>, the panel form
+// RingTile<6, 2, 4> (128 weight rows x 384 token rows).
+__device__ __forceinline__ int ring_swz(int row) { return (0xD2 >> (((row >> 2) & 3) * 2)) & 3; }   // f = {2,0,1,3} packed in 0b11010010
+template <int MT2, int WN = 4, int WM = 2, int NA = 4> struct RingTile {
+  static constexpr int RB = 64, NSTG = 4;                        // bytes of K per LDS row: a stage is one k-step of RB bytes; stages
+  static constexpr int BT = WN * NA * 16;                        // weight rows per workgroup: 256 (4 x 2 waves) or 128 (panel form, 2 x 4)
+  static constexpr int XR = WM * MT2 * 16;                       // token rows per workgroup (256 or 128; panel: 384)
+  static constexpr int NWV = WN * WM;                            // waves per workgroup
+  static constexpr int WP = (BT / 16) / NWV, XP = XR / (16 * NWV), NP = WP + XP;   // DMA pieces (16 rows x RB = 1 KB) per wave per k-step: W, X, both
+  static_assert((BT / 16) % NWV == 0 && XR % (16 * NWV) == 0 && XP >= 1, "whole DMA pieces per wave");
+  static constexpr int STAGE = (BT + XR) * RB, RING = NSTG * STAGE;   // a stage: W rows then X rows (32 or 24 KB)
+  static constexpr int RED = XR * 4 * 2 * (int)sizeof(float);    // LSE epilogue: [XR rows][4 wn] (max, sum exp) BEHIND the ring, which slower waves may still read
+  static constexpr int EXCH = NWV * MT2 * NA * 64 * 8;           // RoPE epilogues: every wave's tiles as 16-bit values, 8 bytes per lane and tile, IN the drained ring
+  static_assert(EXCH <= RING, "the RoPE exchange buffer must fit the ring");
+  static_assert(RING + RED <= 160 * 1024, "a CU's LDS");
+  static constexpr int lds(bool lse) { return RING + (lse ? RED : 0); }          // dynamic LDS of a launch
+  static constexpr int in_flight(int ksteps) { return ksteps * NP; }             // vmcnt that leaves a wave's pieces of that many k-steps in flight
+  // the chunk swizzle, on both sides of a stage: chunk c of LDS row r sits at position c ^ ring_swz(r).  The DMA destination is lane-linear
+  // (lane l of a piece -> row l >> 2, position l & 3), so a lane fetches the chunk that belongs at its position, from operand row gr
+  __device__ static __forceinline__ unsigned dma_src(int pk, int gr, unsigned ld_bytes, int row, int lane) {
+    return ats_chunk_byte<RB>(pk, gr, ld_bytes, (lane & 3) ^ ring_swz(row));
+  }
+};
+// ... and a fragment read takes chunk `chunk` of LDS row `row` from
+#define ATS_RING_FRAG_OFF(G, row, chunk) ((row) * G::RB + (((chunk) ^ ring_swz(row)) * 16))
+// The ring's DMA side and schedule, ONE definition expanded in both ring kernels (macros, not function templates: see ATS_ATTN_DMA_TILE in
+// attn.hip; here: a function's arithmetic is simplified before it is inlined, and (wave * WP + j) * 1024 then no longer shares wave * WP + j
+// with the piece's row).  They use the kernel's lbase, wave, woff[] / xoff[], m0w[] / m0x[], wb / xb, kadv, ks0, nks and its
+// read_one(stage, buffer, r).
+// M0 (the LDS destination, in stage 0) of the wave's W / X piece j; wave-uniform
+#define ATS_RING_M0W(G, j) __builtin_amdgcn_readfirstlane((int)lbase + (wave * G::WP + j) * 1024)
+#define ATS_RING_M0X(G, j) __builtin_amdgcn_readfirstlane((int)lbase + G::BT * G::RB + (wave * G::XP + j) * 1024)
+// piece d of k-step ks into stage q (q, d compile-time after unrolling), as a lambda
+#define ATS_RING_DMA_PIECE(G)                                                                                                    \
+  [&](int q, int ks, int d) {                                                                                                    \
+    if (d < G::WP) ATS_DMA16(woff[d % G::WP], wb + (unsigned long long)ks * kadv, m0w[d % G::WP] + q * G::STAGE);                \
+    else           ATS_DMA16(xoff[(d - G::WP) % G::XP], xb + (unsigned long long)ks * kadv, m0x[(d - G::WP) % G::XP] + q * G::STAGE); \
+  }
+// end of a k-step's segment: VM = vmcnt to wait for before the closing barrier (-1: no wait, no barrier)
+#define ATS_RING_SEGMENT_END(RD, VM)                                                                     \
+  if (RD) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                             \
+  if ((VM) >= 0) {                                                                                       \
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((VM) < 0 ? 0 : (VM)) : "memory");                           \
+    asm volatile("s_barrier" ::: "memory");                                                              \
+  }
+// prologue (k-steps ks0 .. ks0 + 3 into stages 0 .. 3, the NRD fragment reads of k-step ks0), steady loop (a segment issues the DMA of
+// k-step + 4 into the stage it consumes: three k-steps stay in flight, two across a barrier) and drain.  SEG(Q, DMA, RD, VM, ks) is the
+// kernel's segment; the waits are hand-counted from G::NP.  Leaves `ks` declared.
+#define ATS_RING_LOOP(G, SEG, NRD)                                                                       \
+  _Pragma("unroll") for (int q = 0; q < G::NSTG; ++q)                                                    \
+    _Pragma("unroll") for (int d = 0; d < G::NP; ++d) dma_piece(q, ks0 + q, d);                          \
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::in_flight(3)) : "memory");                                 \
+  asm volatile("s_barrier" ::: "memory");                                                                \
+  _Pragma("unroll") for (int r = 0; r < (NRD); ++r) read_one(0, 0, r);                                   \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::in_flight(2)) : "memory");                                 \
+  asm volatile("s_barrier" ::: "memory");                 /* k-step 1 published, stage 0 read by everyone */ \
+  int ks = ks0;                                                                                          \
+  for (; ks + 4 < nks; ks += 4) {                                                                        \
+    SEG(0, true, true, G::in_flight(2), ks);                                                             \
+    SEG(1, true, true, G::in_flight(2), ks + 1);                                                         \
+    SEG(2, true, true, G::in_flight(2), ks + 2);                                                         \
+    SEG(3, true, true, G::in_flight(2), ks + 3);                                                         \
+  }                                                                                                      \
+  SEG(0, false, true, G::in_flight(1), ks);                                                              \
+  SEG(1, false, true, G::in_flight(0), ks + 1);                                                          \
+  SEG(2, false, true, -1, ks + 2);                                                                       \
+  SEG(3, false, false, -1, ks + 3);
 
 // SPLITK (one user's tokens, M <= 256: every launch is one pass over W and HBM-bound): the grid is tiles x n_split, part z
 // accumulates the k-steps of its share of the 128-k units and stores fp32 partials to slab z of Cv ([z][M][N]); the deep
@@ -612,15 +679,9 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
   static_assert((EPI != EPI_F32_LSE && EPI != EPI_QKV_ROPE) || (WN == 4 && WM == 2), "the LSE / RoPE epilogues are written for the 4 x 2 wave grid");
   // pk: X and W (and the SwiGLU output) are in the packed operand layout -- every 1 KB DMA piece is then eight FULL 128-byte lines
   // (two rows x 64 bytes each) instead of sixteen half lines: 83 against 55 GB/s per CU from L2 (tools/probe/dma_depth.hip)
-  constexpr int BT = WN * NA * 16, RB = 64, ESZ = 2;             // weight rows per workgroup: 256 (4 x 2 waves) or 128 (panel form, 2 x 4)
-  constexpr int BK = RB / ESZ;                                   // k per stage: 32
-  constexpr int XR = WM * MT2 * 16;                              // token rows per workgroup (256 or 128; panel: 384 or 512)
-  constexpr int NWV = WN * WM;                                   // waves per workgroup: 8 or 4
-  constexpr int WP = (BT / 16) / NWV;                            // W DMA pieces (16 rows each) per wave per k-step
-  static_assert((BT / 16) % NWV == 0 && XR % (16 * NWV) == 0, "whole DMA pieces per wave");
-  constexpr int XP = XR / (16 * NWV);                            // X DMA pieces per wave per k-step
-  constexpr int NP = WP + XP;                                    // DMA pieces per wave per k-step
-  constexpr int STAGE = (BT + XR) * RB;                          // 32 or 24 KB
+  using G = RingTile<MT2, WN, WM, NA>;
+  constexpr int BT = G::BT, RB = G::RB, XR = G::XR, NWV = G::NWV, WP = G::WP, XP = G::XP, NP = G::NP, STAGE = G::STAGE;
+  constexpr int ESZ = 2, BK = RB / ESZ;                          // k per stage: 32
   constexpr int NR = NA + MT2;                                   // fragment reads per wave per k-step
   constexpr int NMF = NA * MT2;                                  // MFMAs per wave per k-step
   constexpr int RG = (NMF * 3 / 4) / NR;                         // one read every RG MFMAs, from the segment's start (RG = 1: +0.0-0.6 %, not kept)
@@ -640,19 +701,18 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
     if (bid >= sk.n_dp) {
       const int j = bid - sk.n_dp;
       sk_g = (sk.G & 7) ? j : (j & 7) * (sk.G >> 3) + (j >> 3);    // G % 8 == 0: consecutive ranges on ids 8 apart (one XCD)
-      sk_u = (int)((long long)sk_g * sk.TU / sk.G);
-      sk_ue = (int)((long long)(sk_g + 1) * sk.TU / sk.G);
+      sk_u = part_begin(sk_g, sk.TU, sk.G);
+      sk_ue = part_begin(sk_g + 1, sk.TU, sk.G);
       sk_tail = true;
     }
   }
   const int wn = wave / WM, wm = wave % WM;
-  auto swz = [](int row) { return (0xD2 >> (((row >> 2) & 3) * 2)) & 3; };   // f = {2,0,1,3} packed in 0b11010010
   const unsigned lbase = lds_addr(smem);
   int m0w[WP], m0x[XP];
 #pragma unroll
-  for (int j = 0; j < WP; ++j) m0w[j] = __builtin_amdgcn_readfirstlane((int)lbase + (wave * WP + j) * 1024);
+  for (int j = 0; j < WP; ++j) m0w[j] = ATS_RING_M0W(G, j);
 #pragma unroll
-  for (int j = 0; j < XP; ++j) m0x[j] = __builtin_amdgcn_readfirstlane((int)lbase + BT * RB + (wave * XP + j) * 1024);
+  for (int j = 0; j < XP; ++j) m0x[j] = ATS_RING_M0X(G, j);
   bool sk_more;
   do {                                                             // one pass unless SK: a tail workgroup's range may end one tile and start the next
   sk_more = false;
@@ -671,18 +731,13 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
     } else {
       bid = (bid & 7) * (sk.n_dp >> 3) + (bid >> 3);               // n_dp % 256 == 0: XCD x walks positions [x n_dp / 8, (x + 1) n_dp / 8)
     }
-  } else {
-    const int q = nwg / 8, r = nwg % 8, x = bid % 8;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-  }
-  const int band = bid / (GM * tiles_n), rem = bid % (GM * tiles_n);
-  const int band_rows = min(GM, tiles_m - band * GM);
-  const int tn = rem / band_rows, tm = band * GM + rem % band_rows;
-  const int n0 = tn * BT, m0 = tm * XR;
+  } else bid = xcd_run(bid, nwg);
+  const GemmTile tile = band_tile(bid, tiles_n, tiles_m, GM);      // (common.h; the stream-K branch has its own first step)
+  const int tn = tile.tn, n0 = tn * BT, m0 = tile.tm * XR;
   if constexpr (SPLITK) {
-    const int units = nks >> 2;                                  // launcher: n_split <= units
-    ks0 = 4 * (int)((long long)zpart * units / n_split);
-    nks = 4 * (int)((long long)(zpart + 1) * units / n_split);
+    const int units = nks >> 2;                                  // of 4 k-steps; launcher: n_split <= units
+    ks0 = 4 * part_begin(zpart, units, n_split);
+    nks = 4 * part_begin(zpart + 1, units, n_split);
   }
 
   // per-lane DMA source offsets (bytes): piece = 16 rows x 64 B, lane l -> row l>>2, stored position l&3
@@ -691,17 +746,17 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
   for (int j = 0; j < WP; ++j) {
     const int row = (wave * WP + j) * 16 + (lane >> 2);          // LDS row; its weight row follows the epilogue's row order (ring_src_row)
     const int gr = min(n0 + (row & ~63) + ring_src_row<ORD>(row & 63), N - 1);
-    woff[j] = (pk ? (unsigned)(gr >> 1) * (unsigned)(K * ESZ * 2) + (gr & 1) * 64 : (unsigned)gr * (unsigned)(K * ESZ)) + (((lane & 3) ^ swz(row)) * 16);
+    woff[j] = G::dma_src(pk, gr, (unsigned)(K * ESZ), row, lane);
   }
 #pragma unroll
   for (int j = 0; j < XP; ++j) {
     const int row = (wave * XP + j) * 16 + (lane >> 2), gr = min(m0 + row, M - 1);
-    xoff[j] = (pk ? (unsigned)(gr >> 1) * (unsigned)(ldx * ESZ * 2) + (gr & 1) * 64 : (unsigned)gr * (unsigned)(ldx * ESZ)) + (((lane & 3) ^ swz(row)) * 16);
+    xoff[j] = G::dma_src(pk, gr, (unsigned)(ldx * ESZ), row, lane);
   }
   const unsigned long long wb = (unsigned long long)W, xb = (unsigned long long)X;
-  const unsigned long long kadv = pk ? 2 * RB : RB;               // bytes from one k-step's 64-byte block of a row to the next
+  const unsigned long long kadv = ats_kadv<RB>(pk);               // bytes from one k-step's 64-byte block of a row to the next
   // fragment addresses: lane (lq, g) reads chunk g of row lq of each 16-row tile
-  const unsigned lp = lq * RB + ((g ^ swz(lq)) * 16);
+  const unsigned lp = ATS_RING_FRAG_OFF(G, lq, g);
   unsigned aA[2], aB[2];                                          // stages {0,1} and {2,3}
   aA[0] = lbase + (wn * NA * 16) * RB + lp;
   aB[0] = lbase + BT * RB + (wm * MT2 * 16) * RB + lp;
@@ -715,10 +770,7 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
     for (int j = 0; j < MT2; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   u32x4_t fa[2][NA], fb[2][MT2];
 
-  auto dma_piece = [&](int q, int ks, int d) {                    // piece d of k-step ks into stage q (q, d compile-time after unrolling)
-    if (d < WP) ATS_DMA16(woff[d % WP], wb + (unsigned long long)ks * kadv, m0w[d % WP] + q * STAGE);
-    else        ATS_DMA16(xoff[(d - WP) % XP], xb + (unsigned long long)ks * kadv, m0x[(d - WP) % XP] + q * STAGE);
-  };
+  auto dma_piece = ATS_RING_DMA_PIECE(G);
   auto read_one = [&](int q, int buf, int r) {                    // fragment read r of stage q into register buffer buf
     const unsigned a = aA[q >> 1], b = aB[q >> 1];
     const int so = (q & 1) * STAGE;
@@ -740,8 +792,7 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
     }
 #undef ATS_RD
   };
-  // one k-step: MFMAs of stage Q from register buffer Q&1, reads of stage Q+1 into the other buffer, DMA of k-step
-  // ks+4 into stage Q; VM = vmcnt to wait for before the closing barrier (-1: no wait, no barrier)
+  // one k-step: MFMAs of stage Q from register buffer Q&1, reads of stage Q+1 into the other buffer, DMA of k-step ks+4 into stage Q
 #define ATS_RING_SEGMENT(Q, DMA, RD, VM, ks)                                                            \
   {                                                                                                      \
     _Pragma("unroll") for (int i = 0; i < NA; ++i) _Pragma("unroll") for (int j = 0; j < MT2; ++j) {     \
@@ -751,37 +802,9 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
         dma_piece((Q), (ks) + 4, (idx - NR * RG) / DG);                                                  \
       ATS_MFMA_BF16(acc[i][j], fa[(Q) & 1][i], fb[(Q) & 1][j]);                                          \
     }                                                                                                    \
-    if (RD) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                           \
-    if ((VM) >= 0) {                                                                                     \
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((VM) < 0 ? 0 : (VM)) : "memory");                         \
-      asm volatile("s_barrier" ::: "memory");                                                            \
-    }                                                                                                    \
+    ATS_RING_SEGMENT_END(RD, VM)                                                                         \
   }
-
-  // prologue: k-steps 0..3 into stages 0..3; fragments of k-step 0
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int d = 0; d < NP; ++d) dma_piece(q, ks0 + q, d);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NP) : "memory");
-  asm volatile("s_barrier" ::: "memory");
-#pragma unroll
-  for (int r = 0; r < NR; ++r) read_one(0, 0, r);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
-  asm volatile("s_barrier" ::: "memory");                          // k-step 1 published, stage 0 read by everyone
-
-  int ks = ks0;
-  for (; ks + 4 < nks; ks += 4) {
-    ATS_RING_SEGMENT(0, true, true, 2 * NP, ks);
-    ATS_RING_SEGMENT(1, true, true, 2 * NP, ks + 1);
-    ATS_RING_SEGMENT(2, true, true, 2 * NP, ks + 2);
-    ATS_RING_SEGMENT(3, true, true, 2 * NP, ks + 3);
-  }
-  ATS_RING_SEGMENT(0, false, true, NP, ks);
-  ATS_RING_SEGMENT(1, false, true, 0, ks + 1);
-  ATS_RING_SEGMENT(2, false, true, -1, ks + 2);
-  ATS_RING_SEGMENT(3, false, false, -1, ks + 3);
+  ATS_RING_LOOP(G, ATS_RING_SEGMENT, NR)
 #undef ATS_RING_SEGMENT
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");               // MFMA results -> VALU reads (the compiler cannot see the asm MFMAs)
 
@@ -814,7 +837,7 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
       __syncthreads();
       sk_epilogue = *flag == parts - 1;
       if (sk_epilogue) {
-        auto slot_of = [&](int gp) { return (gp * 2 + (((int)((long long)gp * sk.TU / sk.G)) / sk.U == sk_tt ? 0 : 1)) * SLOT; };
+        auto slot_of = [&](int gp) { return (gp * 2 + (part_begin(gp, sk.TU, sk.G) / sk.U == sk_tt ? 0 : 1)) * SLOT; };
         auto part_load = [&](int slot, int idx) {
           const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, (slot + idx * NT + tid) * 16, 0, 16);
           f32x4_t f;
@@ -861,7 +884,7 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
     // tile can ever be asked for (tile_store[tn]: tiles holding a token of the constraint automaton).  A wave holds 64 of the tile's
     // 256 columns for its rows: lane-local over the 16 registers, across the four column groups g by two shuffles, across the four
     // waves wn through 8 KB of LDS behind the ring (the ring itself may still be read by slower waves).
-    float* red = reinterpret_cast<float*>(smem + 4 * STAGE);      // [XR rows][4 wn][2]
+    float* red = reinterpret_cast<float*>(smem + G::RING);        // [XR rows][4 wn][2]: G::RED bytes
 #pragma unroll
     for (int j = 0; j < MT2; ++j) {
       float mx = -INFINITY;
@@ -878,7 +901,7 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
       }
 #pragma unroll
       for (int o = 16; o <= 32; o <<= 1) {
-        const float om = __shfl_xor(mx, o, 64), os = __shfl_xor(sm, o, 64);
+        const float om = __shfl_xor(mx, o, 64), os = __shfl_xor(sm, o, 64);     // = lse_merge (common.h), restated: calling it re-shaped this epilogue's branches
         const float nm = fmaxf(mx, om);
         sm = (nm > -INFINITY) ? sm * __expf(mx - nm) + os * __expf(om - nm) : 0.f;
         mx = nm;
@@ -890,7 +913,7 @@ __global__ __launch_bounds__(WN * WM * 64, 1) void gemm_ring_kernel(const void* 
       const float2* src = reinterpret_cast<const float2*>(red) + (size_t)tid * 4;
       float mx = src[0].x, sm = src[0].y;
 #pragma unroll
-      for (int q = 1; q < 4; ++q) {
+      for (int q = 1; q < 4; ++q) {                                // = lse_merge, restated likewise
         const float nm = fmaxf(mx, src[q].x);
         sm = (nm > -INFINITY) ? sm * __expf(mx - nm) + src[q].y * __expf(src[q].x - nm) : 0.f;
         mx = nm;
@@ -961,8 +984,8 @@ __device__ __forceinline__ void mx_epilogue(f32x16_t (&acc)[TA][TB], void* __res
           mx_scale_tile<TA, TB>(acc[it][jt], sx, sw, gm, n0w + it * 32, h, M, N);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const uint32_t p0 = f2bf_pk(acc[it][jt][4 * q], acc[it][jt][4 * q + 1]), p1 = f2bf_pk(acc[it][jt][4 * q + 2], acc[it][jt][4 * q + 3]);
-            *reinterpret_cast<uint2*>(Cb + (size_t)gm * ldc + n0w + it * 32 + 8 * q + 4 * h) = make_uint2(resid_pk(rs[it][jt][q].x, p0), resid_pk(rs[it][jt][q].y, p1));
+            const uint2 p = f2bf_pk4(acc[it][jt][4 * q], acc[it][jt][4 * q + 1], acc[it][jt][4 * q + 2], acc[it][jt][4 * q + 3]);
+            *reinterpret_cast<uint2*>(Cb + (size_t)gm * ldc + n0w + it * 32 + 8 * q + 4 * h) = make_uint2(resid_pk(rs[it][jt][q].x, p.x), resid_pk(rs[it][jt][q].y, p.y));
           }
         }
       }
@@ -984,8 +1007,8 @@ __device__ __forceinline__ void mx_epilogue(f32x16_t (&acc)[TA][TB], void* __res
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           const f32x16_t& t = acc[it][jt];
-          *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (gn0 >> 1) + 8 * q + 4 * h, ldc)) =      // the down projection's operand
-              make_uint2(swiglu_pk(t[4 * q], t[4 * q + 1], t[4 * q + 8], t[4 * q + 9]), swiglu_pk(t[4 * q + 2], t[4 * q + 3], t[4 * q + 10], t[4 * q + 11]));
+          const f32x4_t ga = {t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]}, ua = {t[4 * q + 8], t[4 * q + 9], t[4 * q + 10], t[4 * q + 11]};
+          *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (gn0 >> 1) + 8 * q + 4 * h, ldc)) = swiglu_pk4(ga, ua);      // the down projection's operand
         }
       } else {
 #pragma unroll
@@ -993,8 +1016,7 @@ __device__ __forceinline__ void mx_epilogue(f32x16_t (&acc)[TA][TB], void* __res
           const int gn = n0w + it * 32 + 8 * q + 4 * h;
           if (gn >= N) continue;
           const f32x4_t v = {acc[it][jt][4 * q], acc[it][jt][4 * q + 1], acc[it][jt][4 * q + 2], acc[it][jt][4 * q + 3]};
-          if constexpr (EPI == EPI_F32) store4(reinterpret_cast<float*>(Cv) + (size_t)gm * ldc + gn, v, gn, N, vec);
-          else store4<EPI == EPI_RESID>(reinterpret_cast<bf16_t*>(Cv) + (size_t)gm * ldc + gn, v, gn, N, vec);
+          store4_epi<EPI == EPI_F32, EPI == EPI_RESID>(Cv, (size_t)gm * ldc + gn, v, gn, N, vec);
         }
       }
     }
@@ -1025,12 +1047,12 @@ __device__ __forceinline__ void mx_qkv_rope_epilogue(f32x16_t (&acc)[TA][TB], bf
         mx_scale_tile<TA, TB>(acc[it][jt], sx, sw, row, n0w + it * 32, h, M, N);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<uint2*>(dst + it * 32 + 8 * q) = make_uint2(f2bf_pk(acc[it][jt][4 * q], acc[it][jt][4 * q + 1]), f2bf_pk(acc[it][jt][4 * q + 2], acc[it][jt][4 * q + 3]));
+          *reinterpret_cast<uint2*>(dst + it * 32 + 8 * q) = f2bf_pk4(acc[it][jt][4 * q], acc[it][jt][4 * q + 1], acc[it][jt][4 * q + 2], acc[it][jt][4 * q + 3]);
       }
     }
     return;
   }
-  uint2* ex = reinterpret_cast<uint2*>(smem);                     // [wave][jt][it][q][lane]: 8 x TB x 2 x 4 x 64 x 8 B = 128 / 64 KB
+  uint2* ex = reinterpret_cast<uint2*>(smem);                     // [wave][jt][it][q][lane]: 8 x TB x 2 x 4 x 64 x 8 B = RingTile::EXCH, inside the ring
   __syncthreads();                                                // slower waves may still be reading the ring's last stages
 #pragma unroll
   for (int jt = 0; jt < TB; ++jt) {
@@ -1040,7 +1062,7 @@ __device__ __forceinline__ void mx_qkv_rope_epilogue(f32x16_t (&acc)[TA][TB], bf
       mx_scale_tile<TA, TB>(acc[it][jt], sx, sw, row, n0w + it * 32, h, M, N);
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        ex[(((wave * TB + jt) * TA + it) * 4 + q) * 64 + lane] = make_uint2(f2bf_pk(acc[it][jt][4 * q], acc[it][jt][4 * q + 1]), f2bf_pk(acc[it][jt][4 * q + 2], acc[it][jt][4 * q + 3]));
+        ex[(((wave * TB + jt) * TA + it) * 4 + q) * 64 + lane] = f2bf_pk4(acc[it][jt][4 * q], acc[it][jt][4 * q + 1], acc[it][jt][4 * q + 2], acc[it][jt][4 * q + 3]);
     }
   }
   __syncthreads();
@@ -1080,12 +1102,10 @@ __global__ __launch_bounds__(NWV * 64, 1) void gemm_ring_mx_kernel(const void* _
                                                               int tiles_n, int tiles_m, int GM, int pk, RopeEpi rope = RopeEpi{}, int n_split = 1) {
   static_assert(NWV == 8, "eight-wave form only (see gemm_ring_kernel)");
   static_assert(!SPLITK || EPI == EPI_F32, "split-K parts leave fp32 slabs");
-  constexpr int BT = 256, RB = 64;                                // 64-byte LDS rows = 64 k of e4m3 per stage
-  constexpr int XR = 2 * MT2 * 16;                               // token rows per workgroup (256 or 128)
-  constexpr int WP = 16 / NWV, XP = XR / (16 * NWV), NP = WP + XP;   // DMA pieces (16 rows x 64 B) per wave per k-step
-  constexpr int STAGE = (BT + XR) * RB;
+  using G = RingTile<MT2>;                                        // 64-byte LDS rows = 64 k of e4m3 per stage
+  static_assert(G::NWV == NWV, "the 4 x 2 wave grid");
+  constexpr int BT = G::BT, RB = G::RB, XR = G::XR, WP = G::WP, XP = G::XP, NP = G::NP, STAGE = G::STAGE;
   constexpr int TA = 16 / NWV, TB = MT2 / 2;                     // 32x32 tiles per wave: weight rows x token rows (NWV/2 waves along n, 2 along m)
-  static_assert(XP >= 1, "token tile too small for this wave count");
   constexpr int NR = 2 * (TA + TB);                              // ds_read_b128 per wave per k-step
   constexpr int NMF = TA * TB;                                   // MFMAs per wave per k-step
   constexpr int NIT = NR + NP;                                   // reads + DMA pieces placed between the MFMAs of a k-step
@@ -1095,42 +1115,35 @@ __global__ __launch_bounds__(NWV * 64, 1) void gemm_ring_mx_kernel(const void* _
   const int nwg = tiles_n * tiles_m;
   int bid = blockIdx.x, zpart = 0;
   if constexpr (SPLITK) { zpart = bid / nwg; bid -= zpart * nwg; }
-  {
-    const int q = nwg / 8, r = nwg % 8, x = bid % 8;             // XCD-contiguous runs of tiles (see gemm_ring_kernel)
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-  }
-  const int band = bid / (GM * tiles_n), rem = bid % (GM * tiles_n);
-  const int band_rows = min(GM, tiles_m - band * GM);
-  const int tn = rem / band_rows, tm = band * GM + rem % band_rows;
-  const int n0 = tn * BT, m0 = tm * XR;
+  const GemmTile tile = tile_walk(bid, tiles_n, tiles_m, GM);     // XCD-contiguous runs of tiles, bands of GM token-tile rows (common.h)
+  const int n0 = tile.tn * BT, m0 = tile.tm * XR;
   const int wn = wave >> 1, wm = wave & 1;                        // NWV/2 waves along the weight rows, 2 along the token rows
   int ks0 = 0, nks = K / 64;                                      // launcher: K % 256 == 0; nks = END of this part's k-steps
   if constexpr (SPLITK) {
-    const int units = nks >> 2;                                   // launcher: n_split <= units
-    ks0 = 4 * (int)((long long)zpart * units / n_split);
-    nks = 4 * (int)((long long)(zpart + 1) * units / n_split);
+    const int units = nks >> 2;                                   // of 4 k-steps; launcher: n_split <= units
+    ks0 = 4 * part_begin(zpart, units, n_split);
+    nks = 4 * part_begin(zpart + 1, units, n_split);
   }
 
-  auto swz = [](int row) { return (0xD2 >> (((row >> 2) & 3) * 2)) & 3; };   // f = {2,0,1,3}
   unsigned woff[WP], xoff[XP];
-  int m0w_[WP], m0x_[XP];
+  int m0w[WP], m0x[XP];
   const unsigned lbase = lds_addr(smem);
 #pragma unroll
   for (int j = 0; j < WP; ++j) {
     const int row = (wave * WP + j) * 16 + (lane >> 2), gr = min(n0 + row, N - 1);
-    woff[j] = (pk ? (unsigned)(gr >> 1) * (unsigned)(K * 2) + (gr & 1) * 64 : (unsigned)gr * (unsigned)K) + (((lane & 3) ^ swz(row)) * 16);
-    m0w_[j] = __builtin_amdgcn_readfirstlane((int)lbase + (wave * WP + j) * 1024);
+    woff[j] = G::dma_src(pk, gr, (unsigned)K, row, lane);
+    m0w[j] = ATS_RING_M0W(G, j);
   }
 #pragma unroll
   for (int j = 0; j < XP; ++j) {
     const int row = (wave * XP + j) * 16 + (lane >> 2), gr = min(m0 + row, M - 1);
-    xoff[j] = (pk ? (unsigned)(gr >> 1) * (unsigned)(K * 2) + (gr & 1) * 64 : (unsigned)gr * (unsigned)K) + (((lane & 3) ^ swz(row)) * 16);
-    m0x_[j] = __builtin_amdgcn_readfirstlane((int)lbase + BT * RB + (wave * XP + j) * 1024);
+    xoff[j] = G::dma_src(pk, gr, (unsigned)K, row, lane);
+    m0x[j] = ATS_RING_M0X(G, j);
   }
   const unsigned long long wb = (unsigned long long)W, xb = (unsigned long long)X;
-  const unsigned long long kadv = pk ? 2 * RB : RB;               // packed operands: full 128-byte lines per DMA piece (see gemm_ring_kernel)
+  const unsigned long long kadv = ats_kadv<RB>(pk);               // packed operands: full 128-byte lines per DMA piece (see gemm_ring_kernel)
   // fragment addresses: lane (r32, h) reads chunks 2h and 2h+1 of row r32 of each 32-row tile
-  const unsigned lp_lo = r32 * RB + (((2 * h) ^ swz(r32)) * 16), lp_hi = r32 * RB + (((2 * h + 1) ^ swz(r32)) * 16);
+  const unsigned lp_lo = ATS_RING_FRAG_OFF(G, r32, 2 * h), lp_hi = ATS_RING_FRAG_OFF(G, r32, 2 * h + 1);
   unsigned aAl[2], aAh[2], aBl[2], aBh[2];                        // stages {0,1} and {2,3}
   aAl[0] = lbase + (wn * TA * 32) * RB + lp_lo;  aAh[0] = lbase + (wn * TA * 32) * RB + lp_hi;
   aBl[0] = lbase + BT * RB + (wm * TB * 32) * RB + lp_lo;  aBh[0] = lbase + BT * RB + (wm * TB * 32) * RB + lp_hi;
@@ -1146,10 +1159,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void gemm_ring_mx_kernel(const void* _
   u32x4_t fal[2][TA], fah[2][TA], fbl[2][TB], fbh[2][TB];
   const unsigned unit_scale = 0x7f7f7f7fu;                        // E8M0 1.0 for every 32-k block of both operands
 
-  auto dma_piece = [&](int q, int ks, int d) {
-    if (d < WP) ATS_DMA16(woff[d % WP], wb + (unsigned long long)ks * kadv, m0w_[d % WP] + q * STAGE);
-    else        ATS_DMA16(xoff[(d - WP) % XP], xb + (unsigned long long)ks * kadv, m0x_[(d - WP) % XP] + q * STAGE);
-  };
+  auto dma_piece = ATS_RING_DMA_PIECE(G);
   auto read_one = [&](int q, int buf, int r) {                    // read r of stage q into register buffer buf (all compile-time after unrolling)
     const int so = (q & 1) * STAGE, tile = r >> 1;
     if (r < 2 * TA) {
@@ -1163,7 +1173,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void gemm_ring_mx_kernel(const void* _
   };
 #define ATS_CAT8(lo, hi) __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7)
   // one k-step: MFMAs of stage Q from register buffer Q&1; item t (reads of stage Q+1, then the DMA pieces of k-step ks+4 into
-  // stage Q) is issued in front of MFMA t*NMF/NIT; VM = vmcnt to wait for before the closing barrier (-1: no wait, no barrier)
+  // stage Q) is issued in front of MFMA t*NMF/NIT
 #define ATS_MX_SEGMENT(Q, DMA, RD, VM, ks)                                                               \
   {                                                                                                      \
     _Pragma("unroll") for (int i = 0; i < TA; ++i) _Pragma("unroll") for (int j = 0; j < TB; ++j) {      \
@@ -1176,37 +1186,9 @@ __global__ __launch_bounds__(NWV * 64, 1) void gemm_ring_mx_kernel(const void* _
       }                                                                                                  \
       ATS_MFMA_MX(acc[i][j], ATS_CAT8(fal[(Q) & 1][i], fah[(Q) & 1][i]), ATS_CAT8(fbl[(Q) & 1][j], fbh[(Q) & 1][j]), unit_scale); \
     }                                                                                                    \
-    if (RD) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                           \
-    if ((VM) >= 0) {                                                                                     \
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((VM) < 0 ? 0 : (VM)) : "memory");                         \
-      asm volatile("s_barrier" ::: "memory");                                                            \
-    }                                                                                                    \
+    ATS_RING_SEGMENT_END(RD, VM)                                                                         \
   }
-
-  // prologue: k-steps 0..3 into stages 0..3; fragments of k-step 0
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int d = 0; d < NP; ++d) dma_piece(q, ks0 + q, d);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NP) : "memory");
-  asm volatile("s_barrier" ::: "memory");
-#pragma unroll
-  for (int r = 0; r < NR; ++r) read_one(0, 0, r);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
-  asm volatile("s_barrier" ::: "memory");
-
-  int ks = ks0;
-  for (; ks + 4 < nks; ks += 4) {
-    ATS_MX_SEGMENT(0, true, true, 2 * NP, ks);
-    ATS_MX_SEGMENT(1, true, true, 2 * NP, ks + 1);
-    ATS_MX_SEGMENT(2, true, true, 2 * NP, ks + 2);
-    ATS_MX_SEGMENT(3, true, true, 2 * NP, ks + 3);
-  }
-  ATS_MX_SEGMENT(0, false, true, NP, ks);
-  ATS_MX_SEGMENT(1, false, true, 0, ks + 1);
-  ATS_MX_SEGMENT(2, false, true, -1, ks + 2);
-  ATS_MX_SEGMENT(3, false, false, -1, ks + 3);
+  ATS_RING_LOOP(G, ATS_MX_SEGMENT, NR)
 #undef ATS_MX_SEGMENT
 #undef ATS_CAT8
   asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");   // 16-pass MFMA results -> VALU reads (the compiler cannot see the asm MFMAs)
@@ -1214,9 +1196,9 @@ __global__ __launch_bounds__(NWV * 64, 1) void gemm_ring_mx_kernel(const void* _
   if constexpr (EPI == EPI_QKV_ROPE) {
     mx_qkv_rope_epilogue<TA, TB>(acc, reinterpret_cast<bf16_t*>(Cv), M, N, ldc, m0, n0, wave, lane, sx, sw, rope, smem);
   } else {
-    const int m0w = m0 + wm * (TB * 32), n0w = n0 + wn * (TA * 32);
-    if constexpr (SPLITK) mx_epilogue<EPI_F32, TA, TB>(acc, reinterpret_cast<float*>(Cv) + (size_t)zpart * M * N, M, N, N, m0w, n0w, lane, sx, sw, 0);
-    else                  mx_epilogue<EPI, TA, TB>(acc, Cv, M, N, ldc, m0w, n0w, lane, sx, sw, pk);
+    const int wm0 = m0 + wm * (TB * 32), wn0 = n0 + wn * (TA * 32);      // the wave's first token row and weight row
+    if constexpr (SPLITK) mx_epilogue<EPI_F32, TA, TB>(acc, reinterpret_cast<float*>(Cv) + (size_t)zpart * M * N, M, N, N, wm0, wn0, lane, sx, sw, 0);
+    else                  mx_epilogue<EPI, TA, TB>(acc, Cv, M, N, ldc, wm0, wn0, lane, sx, sw, pk);
   }
 }
 
@@ -1270,16 +1252,21 @@ int launch_big(const bf16_t* x, const bf16_t* w, void* c, int m, int n, int k, i
 #define ATS_RING_GM 4
 #endif
   constexpr int gm = ATS_RING_GM;
-  const int tiles_n = (n + 255) / 256;
-  constexpr int LDS8 = EPI == EPI_F32_LSE ? 136 * 1024 : 128 * 1024, LDS4 = EPI == EPI_F32_LSE ? 100 * 1024 : 96 * 1024;
+  constexpr int LDS8 = RingTile<8>::lds(EPI == EPI_F32_LSE), LDS4 = RingTile<4>::lds(EPI == EPI_F32_LSE);
   ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, 8, false>>(LDS8)));
   ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, 4, false>>(LDS4)));
   ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, 8, false, false, 4, true>>(LDS8)));
   ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, 4, false, false, 4, true>>(LDS4)));
-  const int t256 = tiles_n * ((m + 255) / 256), t128 = tiles_n * ((m + 127) / 128);
-  const BigChoice ch = big_choose(t256, t128, k);
-  const bool use256 = ch.rows256;
+  const RingGrid g(m, n);
+  const BigChoice ch = big_choose(g.t256, g.t128, k);
   const float* none = nullptr;
+  auto launch = [&](auto mt2, auto sk_on, int grid, const SkTail& tail) {      // MT2 = 8 / 4: 256- / 128-row token tiles; with the stream-K tail or without
+    constexpr int MT2 = decltype(mt2)::value;
+    hipLaunchKernelGGL((gemm_ring_kernel<EPI, MT2, false, false, 4, decltype(sk_on)::value>), dim3(grid), dim3(512), RingTile<MT2>::lds(EPI == EPI_F32_LSE), st, (const void*)x,
+                       (const void*)w, none, none, c, m, n, k, ldx, ldc, g.tn, g.tm(MT2 == 8), gm, 1, lse_part, tile_store, pk, rope, tail);
+  };
+  const std::integral_constant<int, 8> rows256{};
+  const std::integral_constant<int, 4> rows128{};
   if (ch.sk.on && (arena != nullptr || !stream_is_capturing(st))) {
     // split-K tail: n_dp whole tiles + G workgroups that share the k-steps of the remaining ones evenly.  With the caller's arena plain
     // stream order is all there is; the shared one needs bookkeeping + enqueue as one step (see SkShared)
@@ -1287,9 +1274,8 @@ int launch_big(const bf16_t* x, const bf16_t* w, void* c, int m, int n, int k, i
     if (!arena) { lk.lock(); arena = sk_shared_arena(st); }
     if (arena) {
       const SkTail tail{ch.sk.n_dp, ch.sk.G, ch.sk.U, ch.sk.TU, arena->ws, arena->cnt};
-      const int grid = ch.sk.n_dp + ch.sk.G;
-      if (use256) hipLaunchKernelGGL((gemm_ring_kernel<EPI, 8, false, false, 4, true>), dim3(grid), dim3(512), LDS8, st, (const void*)x, (const void*)w, none, none, c, m, n, k, ldx, ldc, tiles_n, (m + 255) / 256, gm, 1, lse_part, tile_store, pk, rope, tail);
-      else        hipLaunchKernelGGL((gemm_ring_kernel<EPI, 4, false, false, 4, true>), dim3(grid), dim3(512), LDS4, st, (const void*)x, (const void*)w, none, none, c, m, n, k, ldx, ldc, tiles_n, (m + 127) / 128, gm, 1, lse_part, tile_store, pk, rope, tail);
+      if (ch.rows256) launch(rows256, std::true_type{}, ch.sk.n_dp + ch.sk.G, tail);
+      else            launch(rows128, std::true_type{}, ch.sk.n_dp + ch.sk.G, tail);
       ATS_LAUNCH_CHECK();
       ats_count_path(ATS_PATH_RING_SK);
       return ATSPEED_OK;
@@ -1297,8 +1283,8 @@ int launch_big(const bf16_t* x, const bf16_t* w, void* c, int m, int n, int k, i
   }
   // (a four-wave form, one wave per SIMD with 128 x 128 per wave and the accumulators in AGPRs, was 3 % slower on every projection and is
   // not instantiated any more: profiles/README.md)
-  if (use256) hipLaunchKernelGGL((gemm_ring_kernel<EPI, 8, false>), dim3(t256), dim3(512), LDS8, st, (const void*)x, (const void*)w, none, none, c, m, n, k, ldx, ldc, tiles_n, (m + 255) / 256, gm, 1, lse_part, tile_store, pk, rope);
-  else        hipLaunchKernelGGL((gemm_ring_kernel<EPI, 4, false>), dim3(t128), dim3(512), LDS4, st, (const void*)x, (const void*)w, none, none, c, m, n, k, ldx, ldc, tiles_n, (m + 127) / 128, gm, 1, lse_part, tile_store, pk, rope);
+  if (ch.rows256) launch(rows256, std::false_type{}, g.t256, SkTail{});
+  else            launch(rows128, std::false_type{}, g.t128, SkTail{});
   ATS_LAUNCH_CHECK();
   ats_count_path(ATS_PATH_RING);
   return ATSPEED_OK;
@@ -1311,9 +1297,7 @@ __global__ __launch_bounds__(256) void lse_combine_kernel(const float2* __restri
   float mx = -INFINITY, sm = 0.f;
   for (int t = lane; t < tiles_n; t += 64) {
     const float2 p = part[(size_t)row * tiles_n + t];
-    const float nm = fmaxf(mx, p.x);
-    sm = (nm > -INFINITY) ? sm * __expf(mx - nm) + p.y * __expf(p.x - nm) : 0.f;
-    mx = nm;
+    lse_merge(mx, sm, p.x, p.y);
   }
   const float gm = wave_max_f32(mx);
   sm = (mx > -INFINITY) ? sm * expf(mx - gm) : 0.f;
@@ -1324,9 +1308,8 @@ __global__ __launch_bounds__(256) void lse_combine_kernel(const float2* __restri
 // lm_head over the batched rows with the normaliser fused into the epilogue (gemm_ring_kernel<EPI_F32_LSE>)
 int launch_big_lse(const bf16_t* x, const bf16_t* w, float* c, int m, int n, int k, int ldx, int ldc, float* part, const unsigned char* tile_store,
                    float* lse, hipStream_t st, int pk, const SkArena* arena) {
-  const int tiles_n = (n + 255) / 256;
   ATS_TRY(launch_big<EPI_F32_LSE>(x, w, (void*)c, m, n, k, ldx, ldc, st, pk, RopeEpi{}, part, tile_store, arena));
-  lse_combine_kernel<<<(m + 3) / 4, 256, 0, st>>>(reinterpret_cast<const float2*>(part), m, tiles_n, lse);
+  lse_combine_kernel<<<(m + 3) / 4, 256, 0, st>>>(reinterpret_cast<const float2*>(part), m, RingGrid(m, n).tn, lse);
   ATS_LAUNCH_CHECK();
   return ATSPEED_OK;
 }
@@ -1408,14 +1391,16 @@ template <int EPI>
 int launch_big_fp8(const unsigned char* x, const float* sx, const unsigned char* w, const float* sw, void* c, int m, int n, int k,
                    int ldc, hipStream_t st, int pk, const RopeEpi& rope = RopeEpi{}) {
   constexpr int gm = 4;
-  const int tiles_n = (n + 255) / 256;
-  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI, 8>>(128 * 1024)));
-  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI, 4>>(96 * 1024)));
-  const int t256 = tiles_n * ((m + 255) / 256), t128 = tiles_n * ((m + 127) / 128);
-  if (big_use_256_rows(t256, t128))
-    hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI, 8>), dim3(t256), dim3(512), 128 * 1024, st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, ldc, tiles_n, (m + 255) / 256, gm, pk, rope);
-  else
-    hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI, 4>), dim3(t128), dim3(512), 96 * 1024, st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, ldc, tiles_n, (m + 127) / 128, gm, pk, rope);
+  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI, 8>>(RingTile<8>::lds(false))));
+  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI, 4>>(RingTile<4>::lds(false))));
+  const RingGrid g(m, n);
+  auto launch = [&](auto mt2, int grid) {
+    constexpr int MT2 = decltype(mt2)::value;
+    hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI, MT2>), dim3(grid), dim3(512), RingTile<MT2>::lds(false), st, (const void*)x, (const void*)w, sx, sw, c, m, n, k, ldc, g.tn,
+                       g.tm(MT2 == 8), gm, pk, rope);
+  };
+  if (big_use_256_rows(g.t256, g.t128)) launch(std::integral_constant<int, 8>{}, g.t256);
+  else                                  launch(std::integral_constant<int, 4>{}, g.t128);
   ATS_LAUNCH_CHECK();
   ats_count_path(ATS_PATH_FP8_RING);
   return ATSPEED_OK;
@@ -1452,6 +1437,14 @@ int launch_big_fp8(const unsigned char* x, const float* sx, const unsigned char*
 // meet two to a bank -- the same k permutation on both operands, so the product is unchanged.  The fp32 scales multiply the accumulators
 // (acc * sx[m] * sw[n]) before the epilogue, also on the fp32 split-K partials (the sum is linear), so every consumer is the bf16 form's.
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
+// geometry of that ring, for the kernel and its launchers: NST stages of BM token rows then BN weight rows, 128 bytes of K each; 2 x WM waves
+template <int BM, int BN, int NST, int WM = 2> struct WdmaTile {
+  static constexpr int RB = 128, NWAVE = 2 * WM;
+  static constexpr int STAGE = (BM + BN) * RB, LDS = NST * STAGE;      // LDS: the launch's dynamic LDS
+  static constexpr int NPIECE = (BM + BN) / 8, NP = NPIECE / NWAVE;    // 1 KB pieces (8 rows) per stage; per wave
+  static constexpr int VM_AHEAD = (NST - 2) * NP;                      // vmcnt that leaves a wave's pieces of NST - 2 tiles in flight
+  static_assert(NPIECE % NWAVE == 0 && VM_AHEAD <= 63 && BM % (16 * WM) == 0 && LDS <= 160 * 1024, "pieces per wave / vmcnt range / a CU's LDS");
+};
 template <int BM, int BN, int NST, int EPI, bool SPLIT = false, int WM = 2, bool F8 = false>
 __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restrict__ X, const void* __restrict__ W, void* __restrict__ Cv,
                                                              int M, int N, int K, int ldx, int ldc, int pk, int n_split,
@@ -1464,11 +1457,10 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
   // no exchange between lanes or waves.  Numerics = the plain store + rope_kv_segs_vec_kernel: the projection rounded to the 16-bit type,
   // the rotation in fp32 on those values (rope_first / rope_second), one more rounding -- bit-identical (tests/test_closures_gpu.py).
   static_assert(EPI != EPI_QKV_ROPE || (F8 && !SPLIT && BN == 64), "RoPE epilogue: the W8A8 no-split form with 64-row weight tiles");
-  constexpr int RB = 128, STAGE = (BM + BN) * RB, NWAVE = 2 * WM;
+  using G = WdmaTile<BM, BN, NST, WM>;
+  constexpr int RB = G::RB, STAGE = G::STAGE, NP = G::NP;
   constexpr int ESZ = F8 ? 1 : 2, BK = RB / ESZ;                       // k per stage: 64 (16-bit) or 128 (e4m3)
-  constexpr int NPIECE = (BM + BN) / 8, NP = NPIECE / NWAVE;           // 1 KB pieces per stage; per wave
   constexpr int NI = BN / 2 / 16, MI = BM / WM / 16;                   // wave tile (2 x WM waves): BN/2 weight rows x BM/WM token rows
-  static_assert(NPIECE % NWAVE == 0 && (NST - 2) * NP <= 63 && BM % (16 * WM) == 0, "pieces per wave / vmcnt range");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave / WM, wm = wave % WM, lq = lane & 15, g = lane >> 4;
@@ -1476,8 +1468,8 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
   int kt0 = 0, n_kt = K / BK;                                          // launcher: K % BK == 0; this part's tiles are kt0 .. kt0 + n_kt - 1
   if constexpr (SPLIT) {
     const int all = n_kt, z = blockIdx.y;
-    kt0 = (int)((long long)z * all / n_split);
-    n_kt = (int)((long long)(z + 1) * all / n_split) - kt0;
+    kt0 = part_begin(z, all, n_split);
+    n_kt = part_begin(z + 1, all, n_split) - kt0;
   }
   const unsigned lbase = lds_addr(smem);
 
@@ -1496,12 +1488,12 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
     }
     const int gr = w ? min(wr, N - 1) : min(row, M - 1);
     const unsigned ldb = (w ? (unsigned)K : (unsigned)ldx) * ESZ;      // row bytes
-    voff[j] = pk ? (unsigned)(gr >> 1) * (ldb * 2u) + (gr & 1) * 64 + (unsigned)(c >> 2) * 128 + (c & 3) * 16 : (unsigned)gr * ldb + c * 16;
+    voff[j] = ats_chunk_byte<RB>(pk, gr, ldb, c);
     m0p[j] = __builtin_amdgcn_readfirstlane((int)lbase + piece * 1024);
     is_w[j] = __builtin_amdgcn_readfirstlane(piece * 8 >= BM ? 1 : 0) != 0;
   }
   const unsigned long long wb = (unsigned long long)W, xb = (unsigned long long)X;
-  const unsigned long long kstep = pk ? 256 : 128;                     // bytes from one 128-byte tile of a row to the next
+  const unsigned long long kstep = ats_kadv<RB>(pk);                   // bytes from one 128-byte tile of a row to the next
   auto issue = [&](int kt) {                                           // kt: tile index inside this part
     const int so = (kt % NST) * STAGE;
 #pragma unroll
@@ -1517,7 +1509,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
 #pragma unroll
   for (int t = 0; t < NST - 1; ++t) if (t < n_kt) issue(t);           // (a part shorter than the ring only ever waits vmcnt(0) below)
   for (int kt = 0; kt < n_kt; ++kt) {
-    if (kt + NST - 2 < n_kt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * NP) : "memory");   // tiles kt+1 .. kt+NST-2 may still fly
+    if (kt + NST - 2 < n_kt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::VM_AHEAD) : "memory");   // tiles kt+1 .. kt+NST-2 may still fly
     else                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");                            // everyone's pieces of tile kt; and stage (kt-1) % NST is read out
     if (kt + NST - 1 < n_kt) issue(kt + NST - 1);
@@ -1588,7 +1580,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
       if (gm >= M) continue;
       const RowInfo ri = rope.rows[gm];
       const uint32_t a01 = f2bf_pk(acc[0][j][0], acc[0][j][1]), a23 = f2bf_pk(acc[0][j][2], acc[0][j][3]);     // x[d]: the projection's 16-bit outputs
-      const uint32_t b01 = f2bf_pk(acc[1][j][0], acc[1][j][1]), b23 = f2bf_pk(acc[1][j][2], acc[1][j][3]);     // x[d + 64]
+      const uint32_t b01 = f2bf_pk(acc[1][j][0], acc[1][j][1]), b23 = f2bf_pk(acc[1][j][2], acc[1][j][3]);     // x[d + 64]  (= f2bf_pk4, restated: profiles/gemm_refactor_isa_and_speed.txt)
       if (sec == 2) {
         bf16_t* dst = kv_row(ri.vc, rope.layer_off, ri.slot, H) + fsec + d0;
         *reinterpret_cast<uint2*>(dst) = make_uint2(a01, a23);
@@ -1630,16 +1622,14 @@ __global__ __launch_bounds__(128 * WM) void gemm_wdma_kernel(const void* __restr
       for (int q = 0; q < NI / 2; ++q) {
         const int gn = nw + q * 32 + g * 4;                            // gate row of r = 0
         if (gn + 16 >= N) continue;                                    // N % 32 == 0: the whole (gate, up) group is inside N or not at all
-        const f32x4_t &ga = acc[2 * q][j], &ua = acc[2 * q + 1][j];
-        *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (nw >> 1) + q * 16 + g * 4, ldc)) =
-            make_uint2(swiglu_pk(ga[0], ga[1], ua[0], ua[1]), swiglu_pk(ga[2], ga[3], ua[2], ua[3]));
+        *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (nw >> 1) + q * 16 + g * 4, ldc)) = swiglu_pk4(acc[2 * q][j], acc[2 * q + 1][j]);
       }
     } else {
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         const int gn = nw + i * 16 + g * 4;
         if (gn >= N) continue;
-        if constexpr (EPI == EPI_F32) {
+        if constexpr (EPI == EPI_F32) {                                // = store4_epi (common.h), restated: profiles/gemm_refactor_isa_and_speed.txt
           store4(reinterpret_cast<float*>(Cv) + (size_t)gm * ldc + gn, acc[i][j], gn, N, (ldc & 3) == 0);
         } else {
           static_assert(EPI == EPI_STORE || EPI == EPI_SWIGLU || EPI == EPI_F32 || EPI == EPI_QKV_ROPE, "store / fp32 / SwiGLU (the RoPE epilogue returned above)");
@@ -1726,7 +1716,7 @@ static int ring_split_count(int m, int n, int k) {
   constexpr int min_n = 8192;
   constexpr int max_s = 256;
   if (m < min_m || m > max_m || k % 128 != 0 || k < 256 || n < min_n || !dma_offsets_fit(n, k, 2)) return 0;
-  const int tiles = ((n + 255) / 256) * ((m + 255) / 256), units = k / 128;
+  const int tiles = RingGrid(m, n).t256, units = k / 128;
   int s = 256 / tiles;
   if (s > units) s = units;
   if (s > max_s) s = max_s;
@@ -1735,16 +1725,18 @@ static int ring_split_count(int m, int n, int k) {
 // the slab launch of both split forms of the ring kernel (ring_split_count above: tile_rows 256 above 128 tokens, group height 1;
 // kcut_split_count below: tile_rows from its rows256, group height 4): grid = weight tiles x token tiles x parts
 static int launch_ring_split(const bf16_t* a, const bf16_t* w, float* partial, int m, int n, int k, int lda, int splits, int tile_rows, int group_m, hipStream_t st, int pk) {
-  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 8, false, true>>(128 * 1024)));
-  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 4, false, true>>(96 * 1024)));
-  const int tiles_n = (n + 255) / 256, tiles_m = (m + tile_rows - 1) / tile_rows;
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 8, false, true>>(RingTile<8>::lds(false))));
+  ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI_F32, 4, false, true>>(RingTile<4>::lds(false))));
+  const RingGrid g(m, n);
   const float* none = nullptr;
-  auto launch = [&](auto mt2, int lds) {
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, decltype(mt2)::value, false, true>), dim3(tiles_n * tiles_m * splits), dim3(512), lds, st, (const void*)a, (const void*)w,
-                       none, none, (void*)partial, m, n, k, lda, n, tiles_n, tiles_m, group_m, splits, (float*)nullptr, (const unsigned char*)nullptr, pk);
+  auto launch = [&](auto mt2) {
+    constexpr int MT2 = decltype(mt2)::value;
+    const int tiles_m = g.tm(MT2 == 8);
+    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, MT2, false, true>), dim3(g.tn * tiles_m * splits), dim3(512), RingTile<MT2>::lds(false), st, (const void*)a, (const void*)w,
+                       none, none, (void*)partial, m, n, k, lda, n, g.tn, tiles_m, group_m, splits, (float*)nullptr, (const unsigned char*)nullptr, pk);
   };
-  if (tile_rows == 256) launch(std::integral_constant<int, 8>{}, 128 * 1024);
-  else                  launch(std::integral_constant<int, 4>{}, 96 * 1024);
+  if (tile_rows == 256) launch(std::integral_constant<int, 8>{});
+  else                  launch(std::integral_constant<int, 4>{});
   ATS_LAUNCH_CHECK();
   ats_count_path(ATS_PATH_RING_SPLIT);
   return ATSPEED_OK;
@@ -1762,12 +1754,7 @@ static int kcut_split_count(int m, int n, int k, int lda, bool* rows256 = nullpt
   const int on = ats_switch(ATS_SW_GEMM_KCUT);
   if (!on || n < 1024 || k % 128 != 0 || k < 2048 || (lda % 8) != 0 || (n % 4) != 0 || !dma_offsets_fit(n, k, 2) || !dma_offsets_fit(m, lda, 2)) return 0;
   if (on < 2 && panel_applies(m, n, k, lda)) return 0;
-  const int tn = (n + 255) / 256, t256 = tn * ((m + 255) / 256), t128 = tn * ((m + 127) / 128);
-  const bool r256 = t128 > 128;
-  const int tiles = r256 ? t256 : t128;
-  if (rows256) *rows256 = r256;
-  const int s_ = std::min(256 / tiles, (k / 128) / 4);
-  return s_ >= 2 ? s_ : 0;
+  return cut_split_count(RingGrid(m, n), (k / 128) / 4, rows256);      // at least 4 units (512 k) per part
 }
 
 // the LDS-tiled kernel; SPLIT (p.splits > 1) stores fp32 slabs [z][M][N] to `partial`, the caller reduces them
@@ -1811,7 +1798,7 @@ static bool wdma_applies(int m, int n, int k, int lda, int epilogue) {
 }
 template <int BM, int BN, int NST, int EPI, int WM = 2>
 int launch_wdma_cfg(const bf16_t* a, const bf16_t* w, void* c, int m, int n, int k, int lda, int ldc, hipStream_t st, int pk) {
-  constexpr int lds = NST * (BM + BN) * 128;
+  constexpr int lds = WdmaTile<BM, BN, NST, WM>::LDS;
   ATS_TRY((ats_lds_limit<gemm_wdma_kernel<BM, BN, NST, EPI, false, WM>>(lds)));
   hipLaunchKernelGGL((gemm_wdma_kernel<BM, BN, NST, EPI, false, WM>), dim3((n + BN - 1) / BN), dim3(128 * WM), lds, st, (const void*)a, (const void*)w, c, m, n, k, lda, ldc, pk, 1,
                      (const float*)nullptr, (const float*)nullptr, RopeEpi{});
@@ -1833,7 +1820,7 @@ static int wdma_split_count(int m, int n, int k, int lda) {
 }
 template <int BM, int NST, int WM = 2>
 int launch_wdma_split_cfg(const bf16_t* a, const bf16_t* w, float* partial, int m, int n, int k, int lda, int splits, hipStream_t st, int pk) {
-  constexpr int lds = NST * (BM + 128) * 128;
+  constexpr int lds = WdmaTile<BM, 128, NST, WM>::LDS;
   ATS_TRY((ats_lds_limit<gemm_wdma_kernel<BM, 128, NST, EPI_F32, true, WM>>(lds)));
   hipLaunchKernelGGL((gemm_wdma_kernel<BM, 128, NST, EPI_F32, true, WM>), dim3((n + 127) / 128, splits), dim3(128 * WM), lds, st, (const void*)a, (const void*)w, (void*)partial,
                      m, n, k, lda, n, pk, splits, (const float*)nullptr, (const float*)nullptr, RopeEpi{});
@@ -1888,7 +1875,7 @@ static int panel_split_count(int n, int k) {                           // 1: no 
 template <int EPI, bool SPLIT>
 int launch_panel(const bf16_t* x, const bf16_t* w, void* c, int m, int n, int k, int ldx, int ldc, int splits, hipStream_t st, int pk) {
   constexpr int MT2 = 6;
-  constexpr int lds = 4 * (128 + 4 * MT2 * 16) * 64;                   // 128 KB at 384 token rows
+  constexpr int lds = RingTile<MT2, 2, 4>::lds(false);                 // 128 KB at 384 token rows
   ATS_TRY((ats_lds_limit<gemm_ring_kernel<EPI, MT2, false, SPLIT, 4, false, 2, 4>>(lds)));
   const int tiles_n = (n + 127) / 128;
   const float* none = nullptr;
@@ -1902,8 +1889,8 @@ int launch_panel(const bf16_t* x, const bf16_t* w, void* c, int m, int n, int k,
 // the 256-wide ring kernel (launch_big) vs the 128-wide LDS-tiled kernel (with split-K): the ring kernel wins once its tile grid keeps a fair share
 // of the 256 CUs busy -- crossover measured at ~50-60 % (tools/gemm_ab.py: o_proj, down, qkv, gate_up at 512-1920 tokens)
 static bool ring_fills(int m, int n) {
-  const int tn = (n + 255) / 256;
-  return big_fill_pct(tn * ((m + 255) / 256)) >= 60 || big_fill_pct(tn * ((m + 127) / 128)) >= 60;
+  const RingGrid g(m, n);
+  return big_fill_pct(g.t256) >= 60 || big_fill_pct(g.t128) >= 60;
 }
 static bool big_kernel_applies(int m, int n, int k, int lda, int ldc, int epilogue, bool lm_head) {
   // from 257 tokens (two token tiles): measured against the split-K mode at 300-500 tokens, gate_up 115-138 -> 96-108 us, qkv 80 -> 75 us
@@ -1919,7 +1906,7 @@ static bool big_kernel_applies(int m, int n, int k, int lda, int ldc, int epilog
   // from 257 tokens), where it overtakes the LDS-tiled split-K kernel + reduce pass (tools/sk_sweep.py: o_proj at 320 tokens 36.7 -> 34.1 us,
   // down 73.6 -> 70.3; at 400 tokens 33.7 -> 29.6 and 68.4 -> 59.7)
   constexpr int sk_min_tiles = 48;
-  const int t128 = ((n + 255) / 256) * ((m + 127) / 128);
+  const int t128 = RingGrid(m, n).t128;
   return t128 >= sk_min_tiles && sk_any_plan(t128, k);
 }
 
@@ -2108,7 +2095,7 @@ int ats_gemm_qkv_rope(const void* x, const void* wqkv, void* qkv, int m, int hid
   return launch_big<EPI_QKV_ROPE>((const bf16_t*)x, (const bf16_t*)wqkv, qkv, m, 3 * hidden, hidden, hidden, 3 * hidden, st, pk, rope, nullptr, nullptr, sk);
 }
 
-size_t ats_lmhead_lse_part_bytes(int m, int n) { return (size_t)m * ((n + 255) / 256) * 2 * sizeof(float); }
+size_t ats_lmhead_lse_part_bytes(int m, int n) { return (size_t)m * RingGrid(m, n).tn * 2 * sizeof(float); }
 
 // logits = a * w^T (fp32) and lse[row] = log sum exp over ALL n columns of the row.  On the batched path (bf16, ring kernel) the
 // normaliser comes out of the GEMM epilogue and only the 256-column tiles flagged in tile_store (device bytes, one per tile; NULL = all)
@@ -2154,28 +2141,25 @@ int ats_gemm_resid_norm(const void* a, const void* w, void* h, int m, int n, int
 static int mx_split_count(int m, int n, int k, bool* rows256 = nullptr) {   // 0: this shape takes the plain ring kernel (or is not an fp8 shape at all)
   if (m < 257 || k % 256 != 0 || !dma_offsets_fit(n, k, 1) || !dma_offsets_fit(m, k, 1)) return 0;
   if (ring_fills(m, n)) return 0;
-  const int tn = (n + 255) / 256, t256 = tn * ((m + 255) / 256), t128 = tn * ((m + 127) / 128);
+  const RingGrid g(m, n);
   // measured (tools/gemm_fp8_ab.py with / without a workspace, us per launch incl. the reduce): down 70.9 -> 37.4 at 300 tokens, 72.1 -> 42.7 at 456,
   // 76.5 -> 54.4 at 640, 77.7 -> 66.2 at 912; o_proj (K = 4096: short parts) 30.7 -> 27.6 at 300, 36.2 -> 32.4 at 456 but 35.5 -> 39.1 at 640; qkv (96
   // tiles of 256 rows already) 32.3 -> 50.1 at 300: only really thin grids, and K = 4096 only up to 512 tokens
-  if (t256 > 64 || (k < 8192 && m > 512)) return 0;
-  const bool r256 = t128 > 128;                                        // 128-row token tiles while two parts of them fit a round, else 256-row ones
-  const int tiles = r256 ? t256 : t128;
-  if (rows256) *rows256 = r256;
-  const int s_ = std::min(256 / tiles, (k / 256) / 2);                // at least 2 units (512 k) per part
-  return s_ >= 2 ? s_ : 0;
+  if (g.t256 > 64 || (k < 8192 && m > 512)) return 0;
+  return cut_split_count(g, (k / 256) / 2, rows256);                   // at least 2 units (512 k) per part
 }
 static int launch_mx_split(const unsigned char* x, const float* sx, const unsigned char* w, const float* sw, float* partial, int m, int n, int k,
                            int splits, bool r256, hipStream_t st, int pk) {
-  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI_F32, 4, 8, true>>(96 * 1024)));
-  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI_F32, 8, 8, true>>(128 * 1024)));
-  const int tiles_n = (n + 255) / 256, tiles_m = r256 ? (m + 255) / 256 : (m + 127) / 128;
-  auto launch = [&](auto mt2, int lds) {
-    hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI_F32, decltype(mt2)::value, 8, true>), dim3(tiles_n * tiles_m * splits), dim3(512), lds, st, (const void*)x, (const void*)w,
-                       sx, sw, (void*)partial, m, n, k, n, tiles_n, tiles_m, 4, pk, RopeEpi{}, splits);
+  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI_F32, 4, 8, true>>(RingTile<4>::lds(false))));
+  ATS_TRY((ats_lds_limit<gemm_ring_mx_kernel<EPI_F32, 8, 8, true>>(RingTile<8>::lds(false))));
+  const RingGrid g(m, n);
+  const int tiles_m = g.tm(r256);
+  auto launch = [&](auto mt2) {
+    hipLaunchKernelGGL((gemm_ring_mx_kernel<EPI_F32, decltype(mt2)::value, 8, true>), dim3(g.tn * tiles_m * splits), dim3(512), RingTile<decltype(mt2)::value>::lds(false), st,
+                       (const void*)x, (const void*)w, sx, sw, (void*)partial, m, n, k, n, g.tn, tiles_m, 4, pk, RopeEpi{}, splits);
   };
-  if (r256) launch(std::integral_constant<int, 8>{}, 128 * 1024);
-  else      launch(std::integral_constant<int, 4>{}, 96 * 1024);
+  if (r256) launch(std::integral_constant<int, 8>{});
+  else      launch(std::integral_constant<int, 4>{});
   ATS_LAUNCH_CHECK();
   ats_count_path(ATS_PATH_FP8_RING_SPLIT);
   return ATSPEED_OK;
@@ -2201,7 +2185,7 @@ static int wdma8_split_count(int n, int k) {                           // 1: no 
 template <int BM, int NST, int EPI, bool SPLIT, int WM = 2, int BN = 128>
 int launch_wdma8_cfg(const unsigned char* xq, const float* sx, const unsigned char* wq, const float* sw, void* c, int m, int n, int k, int ldc,
                      int splits, hipStream_t st, int pk, const RopeEpi& rope = RopeEpi{}) {
-  constexpr int lds = NST * (BM + BN) * 128;
+  constexpr int lds = WdmaTile<BM, BN, NST, WM>::LDS;
   ATS_TRY((ats_lds_limit<gemm_wdma_kernel<BM, BN, NST, EPI, SPLIT, WM, true>>(lds)));
   hipLaunchKernelGGL((gemm_wdma_kernel<BM, BN, NST, EPI, SPLIT, WM, true>), dim3((n + BN - 1) / BN, SPLIT ? splits : 1), dim3(128 * WM), lds, st, (const void*)xq, (const void*)wq,
                      c, m, n, k, k, ldc, pk, splits, sx, sw, rope);
@@ -2374,7 +2358,6 @@ int ats_gemm_fp8_qkv_rope(const void* xq, const float* sx, const void* wq, const
 // weight row (two 64-byte MFMA steps) and two per token row; latency is hidden by occupancy, not by a ring.  SPLIT: part z of the grid's y takes
 // 256-k tiles z * n / parts .. (z + 1) * n / parts and stores scaled fp32 slabs [z][M][N] for the W8A8 path's reduce kernels; otherwise the
 // epilogue (store / fp32 / residual / SwiGLU) is applied in the kernel.  Vector stores only.
-typedef int i32x8_w4_t __attribute__((ext_vector_type(8)));
 template <int MI, int EPI, bool SPLIT>
 __global__ __launch_bounds__(256) void gemm_w4a8_kernel(const unsigned char* __restrict__ X, const float* __restrict__ sx, const unsigned char* __restrict__ W,
                                                         const unsigned char* __restrict__ S, void* __restrict__ Cv, int M, int N, int K, int ldc, int pk,
@@ -2386,8 +2369,8 @@ __global__ __launch_bounds__(256) void gemm_w4a8_kernel(const unsigned char* __r
   int kt0 = 0, n_kt = K / 256;
   if constexpr (SPLIT) {
     const int all = n_kt, z = blockIdx.y;
-    kt0 = (int)((long long)z * all / n_split);
-    n_kt = (int)((long long)(z + 1) * all / n_split) - kt0;
+    kt0 = part_begin(z, all, n_split);
+    n_kt = part_begin(z + 1, all, n_split) - kt0;
   }
   const size_t wrow = (size_t)K / 2, srow = (size_t)K / 32;
   const unsigned char* wp[NI];
@@ -2399,13 +2382,13 @@ __global__ __launch_bounds__(256) void gemm_w4a8_kernel(const unsigned char* __r
     sp[i] = S + r * srow + (size_t)kt0 * 8 + g;
   }
   const unsigned char* xp[MI];
-  const size_t xstep = pk ? 256 : 128;                                 // bytes from one 128-k step of a token row to the next
+  const size_t xstep = ats_kadv<128>(pk);                              // bytes from one 128-k step of a token row to the next
 #pragma unroll
   for (int j = 0; j < MI; ++j) {
     const size_t r = (size_t)min(mw + j * 16 + lq, M - 1);
     xp[j] = X + (pk ? ats_pk_byte(r, (size_t)g * 16, K) : r * K + g * 16) + (size_t)kt0 * 2 * xstep;
   }
-  const size_t xhi = pk ? 128 : 64;                                    // chunk 4 + g, 64 bytes of k further
+  const size_t xhi = ats_kadv<64>(pk);                                 // chunk 4 + g, 64 bytes of k further
 
   f32x4_t acc[NI][MI];
 #pragma unroll
@@ -2434,10 +2417,10 @@ __global__ __launch_bounds__(256) void gemm_w4a8_kernel(const unsigned char* __r
     for (int s = 0; s < 2; ++s)
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
-        const i32x8_w4_t a = {(int)wv[s][i][0], (int)wv[s][i][1], (int)wv[s][i][2], (int)wv[s][i][3], 0, 0, 0, 0};
+        const i32x8_t a = {(int)wv[s][i][0], (int)wv[s][i][1], (int)wv[s][i][2], (int)wv[s][i][3], 0, 0, 0, 0};
 #pragma unroll
         for (int j = 0; j < MI; ++j) {
-          const i32x8_w4_t b = {(int)xlo[s][j][0], (int)xlo[s][j][1], (int)xlo[s][j][2], (int)xlo[s][j][3],
+          const i32x8_t b = {(int)xlo[s][j][0], (int)xlo[s][j][1], (int)xlo[s][j][2], (int)xlo[s][j][3],
                                 (int)xhv[s][j][0], (int)xhv[s][j][1], (int)xhv[s][j][2], (int)xhv[s][j][3]};
           acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc[i][j], 4, 0, 0, sv[s][i], 0, 0x7f7f7f7f);
         }
@@ -2454,28 +2437,19 @@ __global__ __launch_bounds__(256) void gemm_w4a8_kernel(const unsigned char* __r
     for (int i = 0; i < NI; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[i][j][r] *= fx;
-    if constexpr (SPLIT || EPI == EPI_F32) {
-      float* C = SPLIT ? reinterpret_cast<float*>(Cv) + (size_t)blockIdx.y * M * N + (size_t)gm * N : reinterpret_cast<float*>(Cv) + (size_t)gm * ldc;
+    if constexpr (!SPLIT && EPI == EPI_SWIGLU) {                       // gate rows 32b .. 32b+15, up rows 32b+16 .. 32b+31 (the packed gate_up order)
+      bf16_t* C = reinterpret_cast<bf16_t*>(Cv);
+      if (nw + 16 >= N) continue;                                      // N % 32 == 0: the whole (gate, up) group is inside N or not at all
+      *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (nw >> 1) + g * 4, ldc)) = swiglu_pk4(acc[0][j], acc[1][j]);
+    } else {
+      static_assert(SPLIT || EPI == EPI_F32 || EPI == EPI_STORE || EPI == EPI_RESID, "store / fp32 / residual / SwiGLU");
+      void* C = SPLIT ? reinterpret_cast<float*>(Cv) + (size_t)blockIdx.y * M * N : Cv;   // SPLIT: fp32 slab z, rows of N
       const int ld = SPLIT ? N : ldc;
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         const int gn = nw + i * 16 + g * 4;
         if (gn >= N) continue;
-        store4(C + gn, acc[i][j], gn, N, (ld & 3) == 0);
-      }
-    } else if constexpr (EPI == EPI_SWIGLU) {                          // gate rows 32b .. 32b+15, up rows 32b+16 .. 32b+31 (the packed gate_up order)
-      bf16_t* C = reinterpret_cast<bf16_t*>(Cv);
-      if (nw + 16 >= N) continue;                                      // N % 32 == 0: the whole (gate, up) group is inside N or not at all
-      const f32x4_t &ga = acc[0][j], &ua = acc[1][j];
-      *reinterpret_cast<uint2*>(C + ats_opnd_idx<2>(pk, gm, (nw >> 1) + g * 4, ldc)) = make_uint2(swiglu_pk(ga[0], ga[1], ua[0], ua[1]), swiglu_pk(ga[2], ga[3], ua[2], ua[3]));
-    } else {
-      static_assert(EPI == EPI_STORE || EPI == EPI_RESID, "store / fp32 / residual / SwiGLU");
-      bf16_t* C = reinterpret_cast<bf16_t*>(Cv) + (size_t)gm * ldc;
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const int gn = nw + i * 16 + g * 4;
-        if (gn >= N) continue;
-        store4<EPI == EPI_RESID>(C + gn, acc[i][j], gn, N, (ldc & 3) == 0);
+        store4_epi<SPLIT || EPI == EPI_F32, !SPLIT && EPI == EPI_RESID>(C, (size_t)gm * ld + gn, acc[i][j], gn, N, (ld & 3) == 0);
       }
     }
   }

@@ -82,6 +82,7 @@ def _gemm(lib, a, w, epi, dtype, resid=None, n_out=None):
 
 SHAPES = [(900, 1000, 512), (1024, 2304, 768), (1543, 300, 1024), (1, 128, 128), (5, 200, 96), (16, 384, 352), (20, 4096, 768), (40, 2304, 768), (61, 768, 3072),
           (100, 512, 4096), (228, 1024, 1024), (228, 4096, 4096), (130, 32256, 128), (121, 32859, 768),
+          (7, 250, 768),      # N % 4 != 0 behind a split-K plan of the LDS-tiled kernel: the element-wise reduce pass (splitk_reduce_kernel<.., V = 1>)
           (257, 640, 1376),
           # one user's wide projections: ring kernel in split-K mode (33-256 tokens, N >= 8192, K % 128 == 0)
           (40, 8192, 512), (100, 12288, 1024), (129, 8448, 256), (228, 12288, 640), (256, 9000, 384),
