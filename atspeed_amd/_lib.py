@@ -38,6 +38,18 @@ class GenStats(C.Structure):
                 ("status", C.c_int32)]
 
 
+class SessionCounters(C.Structure):
+    _fields_ = [("rounds", C.c_int64), ("target_forwards", C.c_int64), ("draft_forwards", C.c_int64), ("lane_rounds", C.c_int64),
+                ("users_admitted", C.c_int64), ("users_retired", C.c_int64), ("allocs_after_create", C.c_int64),
+                ("arena_reserved", C.c_int32), ("arena_failed", C.c_int32), ("n_lanes", C.c_int32), ("lanes_occupied", C.c_int32),
+                ("queued", C.c_int64)]
+
+
+class SessionDone(C.Structure):
+    _fields_ = [("ticket", C.c_int64), ("lane", C.c_int32), ("status", C.c_int32), ("rounds_queued", C.c_int64),
+                ("rounds_in_lane", C.c_int64)]
+
+
 # every symbol include/atspeed_hip.h declares: (restype, argtypes)
 _P, _I, _F, _SZ, _U32, _U64 = C.c_void_p, C.c_int32, C.c_float, C.c_size_t, C.c_uint32, C.c_uint64
 # ATSPEED_SEGMENTS of the header: n, six host arrays of per-segment device pointers, three host arrays of counts
@@ -89,6 +101,12 @@ SIGNATURES = {
     "atspeed_warp_cutoff_launches": (C.c_int64, []),
     "atspeed_bssd_generate": (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, C.POINTER(GenStats), _P]),
     "atspeed_bssd_generate_batch": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "atspeed_session_create": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _P, C.POINTER(_P)]),
+    "atspeed_session_submit": (C.c_int, [_P, _P, _I, _I, _U32, _P, _P, C.POINTER(GenStats), C.POINTER(C.c_int64)]),
+    "atspeed_session_round": (C.c_int, [_P, C.POINTER(SessionDone), _I, C.POINTER(_I)]),
+    "atspeed_session_drain": (C.c_int, [_P, C.POINTER(SessionDone), _I, C.POINTER(_I)]),
+    "atspeed_session_get_counters": (C.c_int, [_P, C.POINTER(SessionCounters)]),
+    "atspeed_session_destroy": (None, [_P]),
     "atspeed_target_generate": (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, C.POINTER(GenStats), _P]),
     "atspeed_target_generate_batch": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "atspeed_assemble_sequences": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),

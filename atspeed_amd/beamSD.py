@@ -25,6 +25,9 @@ inference.py:175-176) are torch callables and are served by the host path: each 
 library's forward and its expand + top-K.  Sampling with a host-side mask or processors draws on the host from the device's
 counter-based streams (hostmask.py): a callable wrapping a compilable constraint samples exactly what the device path samples for that seed.
 
+`BSSDSession` is the queue form of BSSD_batch (lanes refilled at round boundaries, users submitted at any time); `BSSD_batch(..., lanes=N)`
+runs a list through one.
+
 The four entry points (BSSD, BSSD_batch, target_generate, target_generate_batch) share their scaffolding: `_mode` (models checked, sampling
 mode and warpers), `_setup` (prompts on the device, compiled constraints, the shared `_DeviceFSM`, one `_Decoder` per user, sampling and trace set),
 `_host_call` (dispatch to hostmask.py and result conversion), `_chunked` (lists above MAX_USERS_PER_CALL) and `_one_user_call` /
@@ -248,6 +251,23 @@ def _prompt_row(inputs) -> torch.Tensor:
     return ids
 
 
+def _set_decoders(decs, mode, num_beams: int, seeds, trace=None) -> None:
+    """Put decoders into a call's sampling mode (decoder i draws from stream seeds[i]), its warpers and, with `trace` not None, its decision
+    trace setting.  The library is told about warpers and trace only when the setting changes."""
+    lib = _lib.load()
+    do, temp, _, top_k, top_p = mode
+    off = (0, 1.0, 1)                                      # the one spelling of "both warpers off": a new decoder's state, every greedy call
+    warp = (top_k, top_p, min_tokens_to_keep(num_beams)) if do and (top_k > 0 or top_p < 1.0) else off
+    for d, seed in zip(decs, seeds):
+        _lib.check(lib.atspeed_decoder_set_sampling(d.handle, 1 if do else 0, temp, int(seed) & 0xFFFFFFFF))
+        if getattr(d, "warp", off) != warp:
+            _lib.check(lib.atspeed_decoder_set_warpers(d.handle, *warp))
+            d.warp = warp
+        if trace is not None and getattr(d, "trace_on", False) != bool(trace):
+            _lib.check(lib.atspeed_decoder_set_trace(d.handle, 1 if trace else 0))
+            d.trace_on = bool(trace)
+
+
 def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allowed_tokens_fn, mode, who: str, trace=None) -> SimpleNamespace:
     """The device path's call setup, for one user or a lock-step batch: prompts on the device, each user's compiled constraint (the mask
     functions look at the prompt -- position of "Response:", data.py:97-102 -- with one D2H copy per call, where the reference does one per beam
@@ -262,19 +282,7 @@ def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allo
             raise ValueError(f"{who} needs one shared constraint automaton (only the start node may differ per user)")
     dfsm = _DeviceFSM.get(fsms[0], target.dims.vocab_size)
     decs = [_Decoder.get(target, draft, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
-    do, temp, seed, top_k, top_p = mode
-    off = (0, 1.0, 1)                                      # the one spelling of "both warpers off": a new decoder's state, every greedy call
-    warp = (top_k, top_p, min_tokens_to_keep(target.generation_config.num_beams)) if do and (top_k > 0 or top_p < 1.0) else off
-    for u, d in enumerate(decs):
-        _lib.check(lib.atspeed_decoder_set_sampling(d.handle, 1 if do else 0, temp, (seed + u) & 0xFFFFFFFF))
-        if getattr(d, "warp", off) != warp:                # the library is told only when the setting changes
-            _lib.check(lib.atspeed_decoder_set_warpers(d.handle, *warp))
-            d.warp = warp
-    if trace is not None:
-        for d in decs:
-            if getattr(d, "trace_on", False) != bool(trace):
-                _lib.check(lib.atspeed_decoder_set_trace(d.handle, 1 if trace else 0))
-                d.trace_on = bool(trace)
+    _set_decoders(decs, mode, target.generation_config.num_beams, [mode[2] + u for u in range(len(decs))], trace)
     return SimpleNamespace(dev=dev, prompts=prompts, fsms=fsms, dfsm=dfsm, decs=decs)
 
 
@@ -407,16 +415,193 @@ def BSSD(target_model, draft_model, inputs: Dict, gamma: int, max_new_tokens: in
 beam_sd_generate = BSSD
 
 
+class BSSDSession:
+    """A queue of BSSD users over `lanes` decoders (`atspeed_session_*`): `submit(inputs)` only queues a user and returns its ticket, `step()`
+    runs ONE round -- every free lane first takes the next queued user, in submission order; then the draft steps, the one packed target
+    forward and the verify walks of all occupied lanes -- and returns `[(ticket, result)]` for the users that finished in it, `drain()` steps
+    until queue and lanes are empty.  A user that finishes frees its lane at the next round boundary instead of waiting for the slowest user
+    of its chunk, and users may be submitted while others are decoding.
+
+    Every result equals the user's own `BSSD` call (scores to fp32 rounding, as `BSSD_batch`) and has `BSSD_batch`'s keys plus `lane`,
+    `rounds_in_lane` (rounds it took part in) and `rounds_queued` (rounds the session ran while it waited); `time_cost` runs from submit to
+    the step that returned it.  With `do_sample` the user of ticket t draws from stream `seed + t - 1` whichever lane it lands on (`submit`'s
+    own `seed=` overrides that).
+
+    Device path only (the rules of `_setup`): a mask callable that cannot `compile()`, extra logits processors and `trace_decisions` raise
+    ValueError, and so does a user whose constraint is not the automaton of the session's first user (start nodes may differ).
+    `max_prompt` (default: the decoders' usual capacity, min(max_tokens, 512)) bounds the prompts the session takes: a longer one makes
+    `submit` raise AtSpeedError (ERR_CAPACITY) and leaves the session usable.  The library session is created with the first submit (the
+    automaton is known then) and makes every allocation its rounds need there; `counters()` reports what ran.  The session owns its lanes'
+    decoders (about 270 MB of KV memory each at the Llama-7B dims) until `close()`; it is a context manager."""
+
+    def __init__(self, target_model, draft_model, lanes: int, gamma: int, max_new_tokens: int, prefix_allowed_tokens_fn=None,
+                 max_prompt: Optional[int] = None, seed=None, logits_processor=None, trace_decisions: bool = False, _cached_decoders: bool = False):
+        self.mode = _mode(seed, target_model, draft_model)
+        if _host_path(logits_processor, prefix_allowed_tokens_fn):
+            raise ValueError("BSSDSession runs on the device only: the mask must be able to compile() itself and there is no logits_processor")
+        if trace_decisions:
+            raise ValueError("BSSDSession keeps no decision trace: use BSSD / BSSD_batch with trace_decisions=True")
+        if not 1 <= int(lanes) <= MAX_USERS_PER_CALL:
+            raise ValueError(f"BSSDSession: lanes must be in 1 .. {MAX_USERS_PER_CALL}, not {lanes}")
+        self.target, self.draft, self.fn = target_model, draft_model, prefix_allowed_tokens_fn
+        self.n_lanes, self.gamma, self.max_new_tokens = int(lanes), int(gamma), int(max_new_tokens)
+        self.k = int(target_model.generation_config.num_beams)
+        self.dk = int(draft_model.generation_config.num_beams)
+        self.max_prompt = int(max_prompt) if max_prompt is not None else min(target_model.max_tokens, 512)
+        self.dev = target_model.device
+        self._cached_decoders = _cached_decoders
+        self._owner = self._decs = self._dfsm = self._fsm0 = None
+        self._users: Dict[int, SimpleNamespace] = {}
+        self._done_buf = (_lib.SessionDone * (2 * self.n_lanes))()      # a round's users, and those a failed round before it left
+        self._submitted, self._closed = 0, False
+
+    # ---- the library session, made when the first user shows which automaton the session runs on
+    def _create(self, fsm: ConstraintFSM) -> None:
+        lib = _lib.load()
+        self._fsm0, self._dfsm = fsm, _DeviceFSM.get(fsm, self.target.dims.vocab_size)
+        if self._cached_decoders:          # BSSD_batch(lanes=N): the lanes BSSD_batch itself would use
+            self._decs = [_Decoder.get(self.target, self.draft, self.max_prompt, lane=i) for i in range(self.n_lanes)]
+        else:
+            self._decs = [_Decoder(self.target, self.draft, self.max_prompt) for _ in range(self.n_lanes)]
+        _set_decoders(self._decs, self.mode, self.k, [self.mode[2]] * self.n_lanes, trace=False)    # the user's own seed comes with its admission
+        with torch.cuda.device(self.dev):
+            self._owner = _lib.Handle.create("atspeed_session_destroy", lib.atspeed_session_create,
+                                             (C.c_void_p * self.n_lanes)(*[d.handle for d in self._decs]), self.n_lanes, self._dfsm.handle,
+                                             self.gamma, self.max_new_tokens, self.k, self.dk, self.max_prompt, _lib.stream_ptr(self.dev))
+
+    def _submit(self, prompt: torch.Tensor, fsm: ConstraintFSM, ids32: torch.Tensor, toks: torch.Tensor, scores: torch.Tensor, seed=None) -> int:
+        if self._closed:
+            raise RuntimeError("BSSDSession is closed")
+        if self._fsm0 is None:
+            self._create(fsm)
+        elif fsm.row_ptr is not self._fsm0.row_ptr:
+            raise ValueError("BSSDSession needs one shared constraint automaton (only the start node may differ per user)")
+        if seed is None:
+            seed = self.mode[2] + self._submitted
+        user = SimpleNamespace(prompt=prompt, ids32=ids32, toks=toks, scores=scores, stats=_lib.GenStats(), t0=time.time())
+        ticket = C.c_int64(0)
+        # host only: the library queues the user and launches nothing, so no device guard (one per user would be the call's largest cost)
+        _lib.check(_lib.load().atspeed_session_submit(self._owner.ptr, ids32.data_ptr(), int(prompt.numel()), fsm.start, int(seed) & 0xFFFFFFFF,
+                                                      toks.data_ptr(), scores.data_ptr(), C.byref(user.stats), C.byref(ticket)))
+        self._submitted += 1
+        self._users[ticket.value] = user
+        return ticket.value
+
+    @torch.no_grad()
+    def submit(self, inputs: Dict, seed=None) -> int:
+        """Queue one user; nothing is launched.  Returns its ticket."""
+        prompt = _prompt_row(inputs).to(self.dev)
+        fsm = _compile_constraint(self.fn, prompt.tolist())
+        with torch.cuda.device(self.dev):
+            ids32 = prompt.to(torch.int32).contiguous()
+            toks = torch.empty(self.k, self.max_new_tokens, dtype=torch.int32, device=self.dev)
+            scores = torch.empty(self.k, dtype=torch.float32, device=self.dev)
+        return self._submit(prompt, fsm, ids32, toks, scores, seed)
+
+    def _finished(self, buf, n: int, assemble: bool):
+        out, now = [], time.time()
+        for rec in buf[:n]:
+            u = self._users.pop(int(rec.ticket))
+            r = {"beam_scores": u.scores}
+            if assemble:
+                r["beam_sequence"] = torch.cat((u.prompt.to(torch.int64)[None, :].repeat(self.k, 1), u.toks.to(torch.int64)), dim=1)
+            r.update(_bssd_stats(u.stats, self.k))
+            r.update({"status": int(rec.status), "time_cost": now - u.t0, "lane": int(rec.lane),
+                      "rounds_in_lane": int(rec.rounds_in_lane), "rounds_queued": int(rec.rounds_queued)})
+            out.append((int(rec.ticket), r))
+        return out
+
+    @torch.no_grad()
+    def step(self, _assemble: bool = True):
+        """Admission, one round, retirement: [(ticket, result)] of the users that finished.  Nothing queued and no lane occupied: []."""
+        if self._owner is None or self._owner.ptr is None:
+            return []
+        return self._run(_lib.load().atspeed_session_round, self._done_buf, _assemble)
+
+    def _run(self, call, buf, assemble: bool):
+        """`call` = atspeed_session_round / _drain with room for len(buf) records.  A round that fails raises here; the users it held come
+        back from the next step() / drain() with the error as their `status` (no valid beams), the queued ones are decoded as usual."""
+        n = C.c_int32(0)
+        with torch.cuda.device(self.dev):
+            _lib.check(call(self._owner.ptr, buf, len(buf), C.byref(n)))
+        return self._finished(buf, n.value, assemble)
+
+    @torch.no_grad()
+    def drain(self, _assemble: bool = True):
+        """Rounds until the queue and the lanes are empty (`atspeed_session_drain`): [(ticket, result)] in the order the users finished."""
+        if self._owner is None or self._owner.ptr is None or not self._users:
+            return []
+        return self._run(_lib.load().atspeed_session_drain, (_lib.SessionDone * len(self._users))(), _assemble)
+
+    def counters(self) -> Dict:
+        """What the session ran so far (`atspeed_session_counters`); before the first submit everything is 0."""
+        c = _lib.SessionCounters()
+        if self._owner is not None and self._owner.ptr is not None:
+            _lib.check(_lib.load().atspeed_session_get_counters(self._owner.ptr, C.byref(c)))
+        return {name: int(getattr(c, name)) for name, _ in _lib.SessionCounters._fields_}
+
+    def close(self) -> None:
+        """Destroy the library session, then the lanes it owns.  Users still queued or in lanes get no result."""
+        self._closed = True
+        if self._owner is not None:
+            self._owner.close()
+        self._users.clear()
+        self._decs = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes: int):
+    """`BSSD_batch(..., lanes=N)`: the whole list through one session of N lanes, results in list order.  The prompts, token blocks and
+    scores are the batch call's buffers (one allocation each) and the result tensors come from its one assemble launch."""
+    if not inputs_list:
+        return []
+    t0 = time.time()
+    dev = target_model.device
+    prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
+    fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
+    n_lanes = max(1, min(int(lanes), len(prompts), MAX_USERS_PER_CALL))
+    with BSSDSession(target_model, draft_model, n_lanes, gamma, max_new_tokens, prefix_allowed_tokens_fn,
+                     max_prompt=max(int(p.numel()) for p in prompts), seed=seed, _cached_decoders=True) as ses:
+        k = ses.k
+        with torch.cuda.device(dev):
+            ids32, toks, scores, keep = _batch_buffers(prompts, k, int(max_new_tokens), dev)
+        tickets = [ses._submit(p, f, i32, toks[u], scores[u]) for u, (p, f, i32) in enumerate(zip(prompts, fsms, ids32))]
+        done = dict(ses.drain(_assemble=False))
+        wall = time.time() - t0
+        outs = _batch_results(keep, toks, scores, k)
+        for out, t in zip(outs, tickets):
+            out.update({key: v for key, v in done[t].items() if key != "beam_scores"})
+            out["time_cost"] = wall / len(outs)
+        outs[0]["session_counters"] = ses.counters()
+    return outs
+
+
 @torch.no_grad()
 def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_tokens: int,
-               prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False):
+               prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False, lanes: Optional[int] = None):
     """BSSD for several independent users at once (one result dict per user, same keys as BSSD).
 
     The reference decodes users strictly one after another (inference.py:162-176).  Here the users advance in
     lock step: each has its own decoder (private KV caches and beam state) and every draft step / target
     verification of a round is ONE forward over the tokens of all users (`atspeed_bssd_generate_batch`), so the
     weights are streamed once per forward instead of once per user.  Token ids, n_matches and draft candidates
-    are identical to calling BSSD() per user (scores agree to fp32 rounding: the GEMM tiling depends on the batch)."""
+    are identical to calling BSSD() per user (scores agree to fp32 rounding: the GEMM tiling depends on the batch).
+
+    `lanes=N` (default None: the lock-step path above, unchanged) runs the list through a `BSSDSession` of N lanes instead: user u + N starts
+    as soon as one of the first N finishes, not when all of them have.  Same results and keys (plus the session's `lane`, `rounds_in_lane`,
+    `rounds_queued`; the first result also carries `session_counters`), user u still draws from stream seed + u.  One difference: a session
+    refuses a prompt at submit when its rounds COULD run out of KV slots (prompt length + (max_new_tokens - 1) x draft beams > max_slots,
+    AtSpeedError ERR_CAPACITY, nothing decoded), where the lock-step path only fails if that user's acceptance really takes it there."""
+    if lanes is not None:
+        if trace_decisions:
+            raise ValueError("BSSD_batch(lanes=N) keeps no decision trace")
+        return _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes)
     mode = _mode(seed, target_model, draft_model)
     if len(inputs_list) > MAX_USERS_PER_CALL:
         return _chunked(lambda chunk, s: BSSD_batch(target_model, draft_model, chunk, gamma, max_new_tokens, prefix_allowed_tokens_fn,

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "session_queue.h"
 
 // ---------------------------------------------------------------------------- errors / misc
 static thread_local std::string g_last_error;
@@ -26,6 +27,9 @@ void atspeed_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* atspeed_last_error(void) { return g_last_error.c_str(); }
+// internal.h: activation buffers, a model's and the device's shared split-K arena, staging ring, stage and profiling events, the graph capture
+// stream and every instantiated graph, a decoder's sampling tables (atspeed_session_counters::allocs_after_create)
+std::atomic<long long> g_ats_lazy_allocs{0};
 // 0.2 (round 6): atspeed_gemm_fp8 / atspeed_gemm_fp8_packed take (workspace, bytes) before the stream (changed in round 5 without a bump);
 // atspeed_set_switch / atspeed_get_switch; atspeed_llama_enable_fp8 on fp16 models
 extern "C" const char* atspeed_version(void) { return "atspeed_hip 0.2 (gfx950)"; }
@@ -98,6 +102,7 @@ static int stage_slot(const void* host_obj, size_t bytes, hipStream_t st, StageR
   ATS_REQUIRE(dev >= 0, ATSPEED_ERR_NO_DEVICE, "staging: no current HIP device, or its id is >= %d", ATS_MAX_DEVICES);
   StageRing& r = g_stage_dev[dev];
   if (!r.dev) {                                          // (a pinned side whose device side did not fit is kept for the next try)
+    g_ats_lazy_allocs++;
     if (!r.host) ATS_HIP(hipHostMalloc((void**)&r.host, kStageBytes));
     ATS_HIP(hipMalloc((void**)&r.dev, kStageBytes));
     r.cap = kStageBytes; r.used = 0;
@@ -327,7 +332,7 @@ struct ProfBracket {
   ProfBracket(atspeed_llama* m, int kind, int rows, hipStream_t st_) : cx(m->act), st(st_), on(m->prof_on), idx(0) {
     if (!on) return;
     idx = cx->prof_kind.size();
-    while (cx->prof_ev.size() < 2 * (idx + 1)) { hipEvent_t e; hipEventCreate(&e); cx->prof_ev.push_back(e); }
+    while (cx->prof_ev.size() < 2 * (idx + 1)) { hipEvent_t e; hipEventCreate(&e); cx->prof_ev.push_back(e); g_ats_lazy_allocs++; }
     cx->prof_kind.push_back(kind); cx->prof_m.push_back(rows);
     hipEventRecord(cx->prof_ev[2 * idx], st);
   }
@@ -373,6 +378,7 @@ static int ensure_act(atspeed_llama* m, int tok, int rows) {
   if (m->act && m->act->cap_tok >= tok && m->act->cap_rows >= rows) return ATSPEED_OK;
   if (m->act) { prof_harvest(m); ATS_HIP(hipDeviceSynchronize()); act_free(m->act); m->act = nullptr; }
   const atspeed_llama_config& c = m->cfg;
+  g_ats_lazy_allocs++;
   Building<ActCtx> cx(new ActCtx(), act_free);
   // 25 % headroom: the next batch's token count differs by a few prompt tokens, and growing costs a device synchronisation plus
   // the re-allocation of every activation buffer (seen as 30-40 ms hiccups inside timed regions)
@@ -414,6 +420,7 @@ static void sk_arena_lazy(atspeed_llama* m, int T, hipStream_t st) {
   if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return; }
   if (cs != hipStreamCaptureStatusNone) return;
   cx->sk_tried = true;
+  g_ats_lazy_allocs++;
   if (hipMalloc((void**)&cx->sk.ws, ATS_SK_ARENA_BYTES) != hipSuccess || hipMalloc((void**)&cx->sk.cnt, ATS_SK_ARENA_COUNTERS * sizeof(int)) != hipSuccess ||
       hipMemsetAsync(cx->sk.cnt, 0, ATS_SK_ARENA_COUNTERS * sizeof(int), st) != hipSuccess) {
     (void)hipGetLastError();
@@ -663,6 +670,7 @@ static int llama_forward_segs(atspeed_llama* m, const SegTable& t, float* logits
     const ActCtx::GraphKey key(T, t.total_logit, t.n, t.n_qtiles, t.qtile_rows, !m->fp4.empty() ? 2 : m->fp8.empty() ? 0 : 1);
     auto it = cx->graphs.find(key);
     if (it == cx->graphs.end() && cx->graphs.size() < 64 && ++cx->graph_seen[key] >= 2) {   // a shape seen twice recurs (K + dl*DK tokens)
+      g_ats_lazy_allocs++;                             // the capture stream (first time) and this shape's graph
       if (!cx->cap_stream) ATS_HIP(hipStreamCreateWithFlags(&cx->cap_stream, hipStreamNonBlocking));
       ATS_HIP(hipStreamBeginCapture(cx->cap_stream, hipStreamCaptureModeThreadLocal));
       const int rc = llama_forward_body(m, t, dtab, nullptr, cx->cap_stream, nullptr);
@@ -964,6 +972,7 @@ extern "C" int atspeed_decoder_set_sampling(atspeed_decoder* d, int32_t do_sampl
   ATS_REQUIRE(!do_sample || (temperature > 0.f && temperature == temperature), ATSPEED_ERR_INVALID, "set_sampling: temperature must be positive");
   d->sample = do_sample != 0; d->temperature = do_sample ? temperature : 1.f; d->seed = seed;
   if (d->sample && !d->tab_score) {
+    g_ats_lazy_allocs++;
     ATS_HIP(hipMalloc((void**)&d->tab_score, sizeof(float) * ATSPEED_MAX_GAMMA * ATS_MAX_CAND));
     ATS_HIP(hipMalloc((void**)&d->tab_off, sizeof(int32_t) * ATSPEED_MAX_GAMMA * (MAXB + 1)));
     ATS_HIP(hipMalloc((void**)&d->tab_lse, sizeof(float) * ATSPEED_MAX_GAMMA));
@@ -976,7 +985,10 @@ extern "C" int atspeed_decoder_set_warpers(atspeed_decoder* d, int32_t top_k, fl
   ATS_REQUIRE(top_k >= 0 && top_p > 0.f && min_tokens_to_keep >= 1, ATSPEED_ERR_INVALID,
               "set_warpers: top_k %d must be >= 0 (0 = off), top_p %g in (0, 1] (>= 1 = off), min_tokens_to_keep %d >= 1", top_k, (double)top_p, min_tokens_to_keep);
   d->top_k = top_k; d->top_p = top_p < 1.f ? top_p : 1.f; d->min_keep = min_tokens_to_keep;
-  if ((d->top_k > 0 || d->top_p < 1.f) && !d->cutoff) ATS_HIP(hipMalloc((void**)&d->cutoff, sizeof(float) * (MAXB + ATSPEED_MAX_GAMMA * MAXB)));
+  if ((d->top_k > 0 || d->top_p < 1.f) && !d->cutoff) {
+    g_ats_lazy_allocs++;
+    ATS_HIP(hipMalloc((void**)&d->cutoff, sizeof(float) * (MAXB + ATSPEED_MAX_GAMMA * MAXB)));
+  }
   return ATSPEED_OK;
 }
 
@@ -1063,7 +1075,7 @@ static int stage_events(hipEvent_t** out) {
   const int dev = ats_cur_device();
   ATS_REQUIRE(dev >= 0, ATSPEED_ERR_NO_DEVICE, "stage events: no current HIP device, or its id is >= %d", ATS_MAX_DEVICES);
   StageEvents& s = g_ev_dev[dev];
-  if (!s.init) { for (auto& e : s.ev) ATS_HIP(hipEventCreate(&e)); s.init = true; }
+  if (!s.init) { g_ats_lazy_allocs++; for (auto& e : s.ev) ATS_HIP(hipEventCreate(&e)); s.init = true; }
   *out = s.ev;
   return ATSPEED_OK;
 }
@@ -1209,14 +1221,236 @@ static int bssd_begin(atspeed_decoder* d, const int32_t* prompt, int P, const at
   return ATSPEED_OK;
 }
 
-// BSSD (beamSD.py:458-542) for n users in lock step: every draft step and every target verification of the round
-// is ONE forward over the tokens of all users that need it (weights are streamed once per forward, not per user).
-static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
+// activation capacity of both models for the largest possible batched forward of a group of n users whose prompts hold up to n0 tokens
+static int bssd_ensure_capacity(atspeed_llama* T, atspeed_llama* D, int n, int n0, int gamma, int k, int dk) {
+  ATS_TRY(ensure_act(T, n * (std::max(n0, k) + gamma * dk), n * (MAXB + gamma * dk)));
+  ATS_TRY(ensure_act(D, n * std::max(std::max(n0, dk + k), dk), n * MAXB));
+  return ATSPEED_OK;
+}
+
+// what differs between the callers of a round, and what a round reports back
+struct RoundCtl {
+  bool flat_trace;          // copy the draft's flat ids to the per-round trace (atspeed_decoder_trace; groups of up to 4 users)
+  bool keep_filtered;       // a user that loses every beam to the id filter ends alone with ATSPEED_ERR_FILTERED; else the round returns the error
+  bool any = false;         // out: a user of the group is not done yet
+  int target_forwards = 0, draft_forwards = 0;   // out: forwards this round launched
+};
+
+// ONE round of BSSD (beamSD.py:458-542) over the n decoders handed to it (users that are done are skipped): every draft step and the target
+// verification of the round is ONE forward over the tokens of all users that need it (weights are streamed once per forward, not per user),
+// then verify and final steps, the exports of the users that finish, the round's single synchronisation and the per-user bookkeeping.
+// The activation buffers must hold the round (bssd_ensure_capacity).
+static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t* g_ev, RoundCtl& ctl) {
   atspeed_llama *T = decs[0]->target, *D = decs[0]->draft;
   const int W = decs[0]->W;
+  std::vector<atspeed_decoder*> ver, fin;          // users doing a verify round / the final single step this round
+  int max_dl = 0;
+  for (int u = 0; u < n; ++u) {
+    atspeed_decoder* d = decs[u];
+    atspeed_decoder::Run& r = d->run;
+    if (r.done) continue;
+    r.final_step = r.export_only = false;
+    if (r.gen >= r.max_new) { r.final_step = r.export_only = true; continue; }
+    r.dl = std::min(r.gamma, r.max_new - r.gen - 1);                               // beamSD.py:504
+    if (r.dl == 0) { r.final_step = true; fin.push_back(d); continue; }            // :505-509
+    ATS_REQUIRE(r.n0 + r.dl * r.dk <= d->tok_cap, ATSPEED_ERR_CAPACITY, "bssd: packed target input too long");
+    ATS_REQUIRE(r.base + r.n0 + r.dl * r.dk <= T->cfg.max_slots, ATSPEED_ERR_CAPACITY,
+                "bssd: KV slots exhausted (%d needed, %d available)", r.base + r.n0 + r.dl * r.dk, T->cfg.max_slots);
+    ver.push_back(d);
+    max_dl = std::max(max_dl, r.dl);
+  }
+  hipEventRecord(g_ev[0], st);
+  // ---- 1. draft: step i of one_step_beam_search for every user that still drafts (:108-179)
+  for (int i = 0; i < max_dl; ++i) {
+    SegTable t{};
+    std::vector<BeamStepArgs> args;
+    std::vector<WarpCutArgs> wargs;
+    std::vector<atspeed_decoder*> us;
+    for (atspeed_decoder* d : ver) if (d->run.dl > i) us.push_back(d);
+    for (atspeed_decoder* d : us) {
+      atspeed_decoder::Run& r = d->run;
+      TokBuf& tin = d->tin[r.cur];
+      Seg sg;
+      if (i == 0) sg = r.reingest ? make_seg(d->dround, r.dk + r.k, r.base + r.n0, r.nb, d->dkv)
+                                  : make_seg(tin, r.n0, r.base + r.n0, r.nb, d->dkv);
+      else        sg = make_seg(tb_offset(tin, r.n0 + (i - 1) * r.dk, W), r.dk, r.base + r.n0 + i * r.dk, r.dk, d->dkv);
+      t.seg[t.n++] = sg;
+      r.s.n_draft_forwards++;
+    }
+    ATS_TRY(ats_seg_finish(t));
+    ATS_TRY(decode_forward(D, t, decs[0]->run.fsm, decs[0]->run.dk, st));
+    ctl.draft_forwards++;
+    for (size_t j = 0; j < us.size(); ++j) {
+      atspeed_decoder* d = us[j];
+      atspeed_decoder::Run& r = d->run;
+      BeamStepArgs a = beam_step_args(d, D, t.seg[j], r.fsm, i == 0 ? d->round_beams[r.cur] : d->blk[i], d->blk[i + 1], r.gen + i, r.dk);
+      beam_step_emit(a, d->tin[r.cur], i == 0 ? r.n0 - r.nb : r.n0 + (i - 1) * r.dk, r.n0 + i * r.dk, r.base + r.n0 + i * r.dk);
+      if (a.sample) {
+        a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, i, 1);
+        a.tab_score = d->tab_score + (size_t)i * ATS_MAX_CAND; a.tab_off = d->tab_off + (size_t)i * (MAXB + 1); a.tab_lse = d->tab_lse + i;
+      }
+      if (a.cutoff) wargs.push_back(warp_cut_args(d, a));
+      args.push_back(a);
+    }
+    ATS_TRY(warp_cutoffs(wargs, st));
+    const BeamStepArgs* dev_args = nullptr;
+    ATS_TRY(stage_args(args, &dev_args, st));
+    ATS_TRY(ats_beam_step_multi(dev_args, (int)args.size(), st));
+  }
+  hipEventRecord(g_ev[1], st);
+  // ---- 2. target: ONE forward over (round inputs ++ draft blocks) of every verifying user and the inputs of
+  //         every user on its final step (:190-232, :505-509)
+  if (!ver.empty() || !fin.empty()) {
+    SegTable t{};
+    for (atspeed_decoder* d : ver) {
+      atspeed_decoder::Run& r = d->run;
+      int Tn = r.n0 + r.dl * r.dk;
+      t.seg[t.n++] = make_seg(d->tin[r.cur], Tn, r.base + Tn, r.nb + r.dl * r.dk, d->tkv);
+      r.s.n_target_forwards++;
+    }
+    for (atspeed_decoder* d : fin) {
+      atspeed_decoder::Run& r = d->run;
+      t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv);
+      r.s.n_target_forwards++;
+    }
+    ATS_TRY(ats_seg_finish(t));
+    ATS_TRY(decode_forward(T, t, decs[0]->run.fsm, decs[0]->run.k, st));
+    ctl.target_forwards++;
+    hipEventRecord(g_ev[2], st);
+    // ---- 3. verify (:242-456) for the verifying users, one workgroup each
+    std::vector<VerifyArgs> vargs;
+    std::vector<WarpCutArgs> wargs;                  // sampling-mode warpers: the cutoffs of this round's verify walks and final steps
+    for (size_t j = 0; j < ver.size(); ++j) {
+      atspeed_decoder* d = ver[j];
+      atspeed_decoder::Run& r = d->run;
+      const RowViews rv = seg_rows(T, t.seg[j]);
+      VerifyArgs va{};
+      va.blk[0] = d->round_beams[r.cur];
+      for (int i = 1; i <= r.dl; ++i) va.blk[i] = d->blk[i];
+      va.nb = r.nb; va.dl = r.dl; va.k = r.k; va.dk = r.dk; va.gen_len0 = r.gen;
+      va.logits = rv.logits; va.ld = T->logits_ld; va.lse = rv.lse; va.fsm = r.fsm->dev;
+      va.row_cand = rv.row_cand; va.n_row_cand = r.k;
+      va.cur = d->tin[r.cur]; va.n0 = r.n0; va.next = d->tin[r.cur ^ 1]; va.dnext = d->dround; va.vis_words = W;
+      va.res = d->round_beams[r.cur ^ 1]; va.mail = d->mail_dev;
+      va.vtrace = (d->trace_level >= 1 && !d->sample) ? d->vtrace_dev : nullptr;
+      if (d->sample) {
+        va.sample = 1; va.temperature = d->temperature; va.seed = d->seed; va.round = r.s.n_run;
+        for (int i = 0; i < r.dl; ++i) {
+          va.dtab_score[i] = d->tab_score + (size_t)i * ATS_MAX_CAND; va.dtab_off[i] = d->tab_off + (size_t)i * (MAXB + 1);
+          va.dtab_lse[i] = d->tab_lse + i;
+        }
+      }
+      if (d->warps()) { va.cutoff = d->cutoff; wargs.push_back(warp_cut_args(d, va)); }
+      vargs.push_back(va);
+    }
+    std::vector<BeamStepArgs> fargs;
+    for (size_t j = 0; j < fin.size(); ++j) {
+      atspeed_decoder* d = fin[j];
+      atspeed_decoder::Run& r = d->run;
+      BeamStepArgs a = beam_step_args(d, T, t.seg[ver.size() + j], r.fsm, d->round_beams[r.cur], d->round_beams[r.cur ^ 1], r.gen, r.k);   // emits nothing
+      if (a.sample) a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, 0, 0);
+      if (a.cutoff) wargs.push_back(warp_cut_args(d, a));
+      fargs.push_back(a);
+    }
+    ATS_TRY(warp_cutoffs(wargs, st));
+    if (!vargs.empty()) {
+      const VerifyArgs* dv = nullptr;
+      ATS_TRY(stage_args(vargs, &dv, st));
+      ATS_TRY(ats_verify_walk_multi(dv, (int)vargs.size(), st));
+    }
+    if (!fargs.empty()) {
+      const BeamStepArgs* df = nullptr;
+      ATS_TRY(stage_args(fargs, &df, st));
+      ATS_TRY(ats_beam_step_multi(df, (int)fargs.size(), st));
+    }
+    for (atspeed_decoder* d : fin) { d->run.cur ^= 1; d->run.gen += 1; }
+  } else {
+    hipEventRecord(g_ev[2], st);
+  }
+  hipEventRecord(g_ev[3], st);
+  // ---- 4. outputs of finished users, mailboxes, the round's single synchronisation
+  std::vector<ExportBeamsArgs> ex;                  // users finishing this round: one export launch for all of them
+  for (int u = 0; u < n; ++u) {
+    atspeed_decoder* d = decs[u];
+    atspeed_decoder::Run& r = d->run;
+    if (!r.done && r.final_step) ex.push_back(ExportBeamsArgs{d->round_beams[r.cur], r.out_tokens, r.out_scores, d->sample ? 1 : 0});
+  }
+  if (!ex.empty()) ATS_TRY(export_beams(ex, decs[0]->run.k, decs[0]->run.max_new, st));
+  for (int u = 0; u < n; ++u) {
+    atspeed_decoder* d = decs[u];
+    atspeed_decoder::Run& r = d->run;
+    if (r.done) continue;
+    if (r.final_step) {}
+    else if (ctl.flat_trace)              // trace of the draft's flat ids (parity tests drive one user at a time; batches skip the copies)
+      for (int i = 1; i <= r.dl; ++i)
+        ATS_HIP(hipMemcpyAsync(d->trace_host + (i - 1) * MAXB, d->blk[i].flat, sizeof(int32_t) * r.dk, hipMemcpyDeviceToHost, st));
+    if (d->trace_level >= 1 && !r.export_only)
+      ATS_HIP(hipMemcpyAsync(d->dump_host, d->beam_area, d->beam_area_bytes, hipMemcpyDeviceToHost, st));
+  }
+  ATS_HIP(hipStreamSynchronize(st));
+  ats_stage_reset();
+  float ms_d = 0.f, ms_t = 0.f, ms_v = 0.f;
+  hipEventElapsedTime(&ms_d, g_ev[0], g_ev[1]);
+  hipEventElapsedTime(&ms_t, g_ev[1], g_ev[2]);
+  hipEventElapsedTime(&ms_v, g_ev[2], g_ev[3]);
+  int n_act = 0;
+  for (int u = 0; u < n; ++u) if (!decs[u]->run.done) ++n_act;
+  ctl.any = false;
+  for (int u = 0; u < n; ++u) {
+    atspeed_decoder* d = decs[u];
+    atspeed_decoder::Run& r = d->run;
+    if (r.done) continue;
+    if (ctl.keep_filtered && d->mail_host->status == ATSPEED_ERR_FILTERED) {
+      // a lock-step batch does not die with one user: this user lost every beam of a step to the id filter (beamSD.py:80-86; the
+      // reference dies on a shape mismatch there) and ends with no valid beam, the others go on (the one-user call returns the error)
+      r.s.n_valid = 0; r.s.status = ATSPEED_ERR_FILTERED;
+      ATS_TRY(blank_outputs(r.out_tokens, r.out_scores, r.k, r.max_new, st));
+      r.s.total_ms = r.s.draft_ms + r.s.target_ms + r.s.verify_ms;
+      if (r.stats_out) *r.stats_out = r.s;
+      r.done = true;
+      continue;
+    }
+    ATS_TRY(mailbox_status(d));
+    // stage times: the group's stage time shared equally by the users that were active in the round
+    r.s.draft_ms += ms_d / n_act; r.s.target_ms += ms_t / n_act; r.s.verify_ms += ms_v / n_act;
+    if (r.final_step) {
+      // `cur` was flipped when the step was launched: the parents are round_beams[cur ^ 1], the result round_beams[cur]
+      if (d->trace_level >= 1 && !r.export_only) decisions_append(d, 1, r.nb, 0, 0, r.gen - 1, r.k, r.dk, {r.cur ^ 1, r.cur});
+      r.s.n_valid = d->mail_host->n_valid;
+      r.s.total_ms = r.s.draft_ms + r.s.target_ms + r.s.verify_ms;
+      if (r.stats_out) *r.stats_out = r.s;
+      r.done = true;
+      continue;
+    }
+    const int nm = d->mail_host->n_matches, dl = r.dl, dk = r.dk;
+    if (ctl.flat_trace) {
+      d->trace.push_back(dl); d->trace.push_back(nm); d->trace.push_back(r.nb);
+      for (int i = 0; i < dl; ++i) for (int j = 0; j < dk; ++j) d->trace.push_back(d->trace_host[i * MAXB + j]);
+    }
+    if (d->trace_level >= 1) {
+      std::vector<int> blocks{r.cur};
+      for (int i = 1; i <= dl; ++i) blocks.push_back(2 + i);
+      blocks.push_back(r.cur ^ 1);
+      decisions_append(d, 0, r.nb, dl, nm, r.gen, r.k, dk, blocks);
+    }
+    if (r.s.n_run < ATSPEED_MAX_NEW_TOKENS) r.s.accept_steps[r.s.n_run] = nm;
+    r.s.n_run++;
+    r.s.total_accept_steps += nm;
+    r.base += r.n0 + nm * dk;             // compact: keep up to the end of block nm
+    r.n0 = r.k; r.nb = r.k;
+    r.gen += nm + 1;                      // :522
+    r.reingest = (nm == dl);
+    r.cur ^= 1;
+    ctl.any = true;
+  }
+  return ATSPEED_OK;
+}
+
+// n users in lock step from their first round to the last one's end (the one-user and the batch call): a user leaves when its last round
+// ends, nobody takes its place
+static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
   hipEvent_t* g_ev = nullptr;
   ATS_TRY(stage_events(&g_ev));
-  // capacity for the largest possible batched forward of this group
   int cap_t = 0, cap_r = 0, cap_d = 0;
   for (int u = 0; u < n; ++u) {
     const atspeed_decoder::Run& r = decs[u]->run;
@@ -1224,209 +1458,10 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
     cap_r += MAXB + r.gamma * r.dk;
     cap_d += std::max(std::max(r.n0, r.dk + r.k), r.dk);
   }
-  ATS_TRY(ensure_act(T, cap_t, cap_r));
-  ATS_TRY(ensure_act(D, cap_d, n * MAXB));
-  bool any = true;
-  while (any) {
-    std::vector<atspeed_decoder*> ver, fin;          // users doing a verify round / the final single step this round
-    int max_dl = 0;
-    for (int u = 0; u < n; ++u) {
-      atspeed_decoder* d = decs[u];
-      atspeed_decoder::Run& r = d->run;
-      if (r.done) continue;
-      r.final_step = r.export_only = false;
-      if (r.gen >= r.max_new) { r.final_step = r.export_only = true; continue; }
-      r.dl = std::min(r.gamma, r.max_new - r.gen - 1);                               // beamSD.py:504
-      if (r.dl == 0) { r.final_step = true; fin.push_back(d); continue; }            // :505-509
-      ATS_REQUIRE(r.n0 + r.dl * r.dk <= d->tok_cap, ATSPEED_ERR_CAPACITY, "bssd: packed target input too long");
-      ATS_REQUIRE(r.base + r.n0 + r.dl * r.dk <= T->cfg.max_slots, ATSPEED_ERR_CAPACITY,
-                  "bssd: KV slots exhausted (%d needed, %d available)", r.base + r.n0 + r.dl * r.dk, T->cfg.max_slots);
-      ver.push_back(d);
-      max_dl = std::max(max_dl, r.dl);
-    }
-    hipEventRecord(g_ev[0], st);
-    // ---- 1. draft: step i of one_step_beam_search for every user that still drafts (:108-179)
-    for (int i = 0; i < max_dl; ++i) {
-      SegTable t{};
-      std::vector<BeamStepArgs> args;
-      std::vector<WarpCutArgs> wargs;
-      std::vector<atspeed_decoder*> us;
-      for (atspeed_decoder* d : ver) if (d->run.dl > i) us.push_back(d);
-      for (atspeed_decoder* d : us) {
-        atspeed_decoder::Run& r = d->run;
-        TokBuf& tin = d->tin[r.cur];
-        Seg sg;
-        if (i == 0) sg = r.reingest ? make_seg(d->dround, r.dk + r.k, r.base + r.n0, r.nb, d->dkv)
-                                    : make_seg(tin, r.n0, r.base + r.n0, r.nb, d->dkv);
-        else        sg = make_seg(tb_offset(tin, r.n0 + (i - 1) * r.dk, W), r.dk, r.base + r.n0 + i * r.dk, r.dk, d->dkv);
-        t.seg[t.n++] = sg;
-        r.s.n_draft_forwards++;
-      }
-      ATS_TRY(ats_seg_finish(t));
-      ATS_TRY(decode_forward(D, t, decs[0]->run.fsm, decs[0]->run.dk, st));
-      for (size_t j = 0; j < us.size(); ++j) {
-        atspeed_decoder* d = us[j];
-        atspeed_decoder::Run& r = d->run;
-        BeamStepArgs a = beam_step_args(d, D, t.seg[j], r.fsm, i == 0 ? d->round_beams[r.cur] : d->blk[i], d->blk[i + 1], r.gen + i, r.dk);
-        beam_step_emit(a, d->tin[r.cur], i == 0 ? r.n0 - r.nb : r.n0 + (i - 1) * r.dk, r.n0 + i * r.dk, r.base + r.n0 + i * r.dk);
-        if (a.sample) {
-          a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, i, 1);
-          a.tab_score = d->tab_score + (size_t)i * ATS_MAX_CAND; a.tab_off = d->tab_off + (size_t)i * (MAXB + 1); a.tab_lse = d->tab_lse + i;
-        }
-        if (a.cutoff) wargs.push_back(warp_cut_args(d, a));
-        args.push_back(a);
-      }
-      ATS_TRY(warp_cutoffs(wargs, st));
-      const BeamStepArgs* dev_args = nullptr;
-      ATS_TRY(stage_args(args, &dev_args, st));
-      ATS_TRY(ats_beam_step_multi(dev_args, (int)args.size(), st));
-    }
-    hipEventRecord(g_ev[1], st);
-    // ---- 2. target: ONE forward over (round inputs ++ draft blocks) of every verifying user and the inputs of
-    //         every user on its final step (:190-232, :505-509)
-    if (!ver.empty() || !fin.empty()) {
-      SegTable t{};
-      for (atspeed_decoder* d : ver) {
-        atspeed_decoder::Run& r = d->run;
-        int Tn = r.n0 + r.dl * r.dk;
-        t.seg[t.n++] = make_seg(d->tin[r.cur], Tn, r.base + Tn, r.nb + r.dl * r.dk, d->tkv);
-        r.s.n_target_forwards++;
-      }
-      for (atspeed_decoder* d : fin) {
-        atspeed_decoder::Run& r = d->run;
-        t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv);
-        r.s.n_target_forwards++;
-      }
-      ATS_TRY(ats_seg_finish(t));
-      ATS_TRY(decode_forward(T, t, decs[0]->run.fsm, decs[0]->run.k, st));
-      hipEventRecord(g_ev[2], st);
-      // ---- 3. verify (:242-456) for the verifying users, one workgroup each
-      std::vector<VerifyArgs> vargs;
-      std::vector<WarpCutArgs> wargs;                  // sampling-mode warpers: the cutoffs of this round's verify walks and final steps
-      for (size_t j = 0; j < ver.size(); ++j) {
-        atspeed_decoder* d = ver[j];
-        atspeed_decoder::Run& r = d->run;
-        const RowViews rv = seg_rows(T, t.seg[j]);
-        VerifyArgs va{};
-        va.blk[0] = d->round_beams[r.cur];
-        for (int i = 1; i <= r.dl; ++i) va.blk[i] = d->blk[i];
-        va.nb = r.nb; va.dl = r.dl; va.k = r.k; va.dk = r.dk; va.gen_len0 = r.gen;
-        va.logits = rv.logits; va.ld = T->logits_ld; va.lse = rv.lse; va.fsm = r.fsm->dev;
-        va.row_cand = rv.row_cand; va.n_row_cand = r.k;
-        va.cur = d->tin[r.cur]; va.n0 = r.n0; va.next = d->tin[r.cur ^ 1]; va.dnext = d->dround; va.vis_words = W;
-        va.res = d->round_beams[r.cur ^ 1]; va.mail = d->mail_dev;
-        va.vtrace = (d->trace_level >= 1 && !d->sample) ? d->vtrace_dev : nullptr;
-        if (d->sample) {
-          va.sample = 1; va.temperature = d->temperature; va.seed = d->seed; va.round = r.s.n_run;
-          for (int i = 0; i < r.dl; ++i) {
-            va.dtab_score[i] = d->tab_score + (size_t)i * ATS_MAX_CAND; va.dtab_off[i] = d->tab_off + (size_t)i * (MAXB + 1);
-            va.dtab_lse[i] = d->tab_lse + i;
-          }
-        }
-        if (d->warps()) { va.cutoff = d->cutoff; wargs.push_back(warp_cut_args(d, va)); }
-        vargs.push_back(va);
-      }
-      std::vector<BeamStepArgs> fargs;
-      for (size_t j = 0; j < fin.size(); ++j) {
-        atspeed_decoder* d = fin[j];
-        atspeed_decoder::Run& r = d->run;
-        BeamStepArgs a = beam_step_args(d, T, t.seg[ver.size() + j], r.fsm, d->round_beams[r.cur], d->round_beams[r.cur ^ 1], r.gen, r.k);   // emits nothing
-        if (a.sample) a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, 0, 0);
-        if (a.cutoff) wargs.push_back(warp_cut_args(d, a));
-        fargs.push_back(a);
-      }
-      ATS_TRY(warp_cutoffs(wargs, st));
-      if (!vargs.empty()) {
-        const VerifyArgs* dv = nullptr;
-        ATS_TRY(stage_args(vargs, &dv, st));
-        ATS_TRY(ats_verify_walk_multi(dv, (int)vargs.size(), st));
-      }
-      if (!fargs.empty()) {
-        const BeamStepArgs* df = nullptr;
-        ATS_TRY(stage_args(fargs, &df, st));
-        ATS_TRY(ats_beam_step_multi(df, (int)fargs.size(), st));
-      }
-      for (atspeed_decoder* d : fin) { d->run.cur ^= 1; d->run.gen += 1; }
-    } else {
-      hipEventRecord(g_ev[2], st);
-    }
-    hipEventRecord(g_ev[3], st);
-    // ---- 4. outputs of finished users, mailboxes, the round's single synchronisation
-    std::vector<ExportBeamsArgs> ex;                  // users finishing this round: one export launch for all of them
-    for (int u = 0; u < n; ++u) {
-      atspeed_decoder* d = decs[u];
-      atspeed_decoder::Run& r = d->run;
-      if (!r.done && r.final_step) ex.push_back(ExportBeamsArgs{d->round_beams[r.cur], r.out_tokens, r.out_scores, d->sample ? 1 : 0});
-    }
-    if (!ex.empty()) ATS_TRY(export_beams(ex, decs[0]->run.k, decs[0]->run.max_new, st));
-    for (int u = 0; u < n; ++u) {
-      atspeed_decoder* d = decs[u];
-      atspeed_decoder::Run& r = d->run;
-      if (r.done) continue;
-      if (r.final_step) {}
-      else if (n <= 4)                      // trace of the draft's flat ids (parity tests drive one user at a time; batches skip the copies)
-        for (int i = 1; i <= r.dl; ++i)
-          ATS_HIP(hipMemcpyAsync(d->trace_host + (i - 1) * MAXB, d->blk[i].flat, sizeof(int32_t) * r.dk, hipMemcpyDeviceToHost, st));
-      if (d->trace_level >= 1 && !r.export_only)
-        ATS_HIP(hipMemcpyAsync(d->dump_host, d->beam_area, d->beam_area_bytes, hipMemcpyDeviceToHost, st));
-    }
-    ATS_HIP(hipStreamSynchronize(st));
-    ats_stage_reset();
-    float ms_d = 0.f, ms_t = 0.f, ms_v = 0.f;
-    hipEventElapsedTime(&ms_d, g_ev[0], g_ev[1]);
-    hipEventElapsedTime(&ms_t, g_ev[1], g_ev[2]);
-    hipEventElapsedTime(&ms_v, g_ev[2], g_ev[3]);
-    int n_act = 0;
-    for (int u = 0; u < n; ++u) if (!decs[u]->run.done) ++n_act;
-    any = false;
-    for (int u = 0; u < n; ++u) {
-      atspeed_decoder* d = decs[u];
-      atspeed_decoder::Run& r = d->run;
-      if (r.done) continue;
-      if (n > 1 && d->mail_host->status == ATSPEED_ERR_FILTERED) {
-        // a lock-step batch does not die with one user: this user lost every beam of a step to the id filter (beamSD.py:80-86; the
-        // reference dies on a shape mismatch there) and ends with no valid beam, the others go on (the one-user call returns the error)
-        r.s.n_valid = 0; r.s.status = ATSPEED_ERR_FILTERED;
-        ATS_TRY(blank_outputs(r.out_tokens, r.out_scores, r.k, r.max_new, st));
-        r.s.total_ms = r.s.draft_ms + r.s.target_ms + r.s.verify_ms;
-        if (r.stats_out) *r.stats_out = r.s;
-        r.done = true;
-        continue;
-      }
-      ATS_TRY(mailbox_status(d));
-      // stage times: the group's stage time shared equally by the users that were active in the round
-      r.s.draft_ms += ms_d / n_act; r.s.target_ms += ms_t / n_act; r.s.verify_ms += ms_v / n_act;
-      if (r.final_step) {
-        // `cur` was flipped when the step was launched: the parents are round_beams[cur ^ 1], the result round_beams[cur]
-        if (d->trace_level >= 1 && !r.export_only) decisions_append(d, 1, r.nb, 0, 0, r.gen - 1, r.k, r.dk, {r.cur ^ 1, r.cur});
-        r.s.n_valid = d->mail_host->n_valid;
-        r.s.total_ms = r.s.draft_ms + r.s.target_ms + r.s.verify_ms;
-        if (r.stats_out) *r.stats_out = r.s;
-        r.done = true;
-        continue;
-      }
-      const int nm = d->mail_host->n_matches, dl = r.dl, dk = r.dk;
-      if (n <= 4) {
-        d->trace.push_back(dl); d->trace.push_back(nm); d->trace.push_back(r.nb);
-        for (int i = 0; i < dl; ++i) for (int j = 0; j < dk; ++j) d->trace.push_back(d->trace_host[i * MAXB + j]);
-      }
-      if (d->trace_level >= 1) {
-        std::vector<int> blocks{r.cur};
-        for (int i = 1; i <= dl; ++i) blocks.push_back(2 + i);
-        blocks.push_back(r.cur ^ 1);
-        decisions_append(d, 0, r.nb, dl, nm, r.gen, r.k, dk, blocks);
-      }
-      if (r.s.n_run < ATSPEED_MAX_NEW_TOKENS) r.s.accept_steps[r.s.n_run] = nm;
-      r.s.n_run++;
-      r.s.total_accept_steps += nm;
-      r.base += r.n0 + nm * dk;             // compact: keep up to the end of block nm
-      r.n0 = r.k; r.nb = r.k;
-      r.gen += nm + 1;                      // :522
-      r.reingest = (nm == dl);
-      r.cur ^= 1;
-      any = true;
-    }
-  }
+  ATS_TRY(ensure_act(decs[0]->target, cap_t, cap_r));
+  ATS_TRY(ensure_act(decs[0]->draft, cap_d, n * MAXB));
+  RoundCtl ctl{n <= 4, n > 1};
+  do ATS_TRY(bssd_round(decs, n, st, g_ev, ctl)); while (ctl.any);
   return ATSPEED_OK;
 }
 
@@ -1453,6 +1488,181 @@ extern "C" int atspeed_bssd_generate(atspeed_decoder* d, const int32_t* prompt, 
                                      int32_t* out_tokens, float* out_scores, atspeed_gen_stats* stats, void* stream) {
   ATS_TRY(bssd_begin(d, prompt, P, fsm, start_node, gamma, max_new, k, dk, out_tokens, out_scores, stats, (hipStream_t)stream));
   return bssd_group_run(&d, 1, (hipStream_t)stream);
+}
+
+// ---- sessions (include/atspeed_hip.h "sessions"): the same round over a fixed set of lanes, each free lane refilled from a host queue at the
+// round boundary.  The tables (lanes, tickets, queue) are host-only code in session_queue.h; here is what touches the device.
+namespace {
+struct SessionJob {          // a submitted user, as it waits in the queue and then sits in its lane
+  const int32_t* prompt = nullptr; int P = 0, start_node = 0; uint32_t seed = 0;
+  int32_t* out_tokens = nullptr; float* out_scores = nullptr; atspeed_gen_stats* stats = nullptr;
+};
+}  // namespace
+struct atspeed_session {
+  std::vector<atspeed_decoder*> lanes;
+  const atspeed_fsm* fsm = nullptr;
+  int gamma = 0, max_new = 0, k = 0, dk = 0, max_prompt = 0;
+  hipStream_t st = nullptr;
+  ats_session::Queue<SessionJob> q;
+  int64_t target_forwards = 0, draft_forwards = 0, allocs_after_create = 0;
+  bool arena_failed = false;
+  explicit atspeed_session(int n) : q(n) {}
+};
+
+// the split-K arena a model's forwards of >= 257 tokens take, reserved ahead of the first of them; false: wanted and not to be had
+static bool session_reserve_arena(atspeed_llama* m, int worst_tokens, hipStream_t st) {
+  const bool wanted = worst_tokens >= 257 && m->cfg.dtype != ATSPEED_F32 && m->cfg.hidden % 128 == 0;     // as sk_arena_lazy
+  if (!wanted) return true;
+  sk_arena_lazy(m, worst_tokens, st);
+  return m->act->sk.ws != nullptr;
+}
+
+extern "C" int atspeed_session_create(atspeed_decoder* const* lanes, int32_t n_lanes, const atspeed_fsm* fsm, int32_t gamma, int32_t max_new,
+                                      int32_t k, int32_t dk, int32_t max_prompt, void* stream, atspeed_session** out) {
+  ATS_REQUIRE(lanes && fsm && out, ATSPEED_ERR_INVALID, "session_create: null argument");
+  ATS_REQUIRE(n_lanes >= 1 && n_lanes <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "session_create: %d lanes (1 .. %d)", n_lanes, ATS_MAX_SEGS);
+  ATS_REQUIRE(max_prompt >= 1, ATSPEED_ERR_INVALID, "session_create: max_prompt %d must be positive", max_prompt);
+  ATS_REQUIRE(max_new >= 1 && max_new <= LMAX, ATSPEED_ERR_CAPACITY, "session_create: max_new_tokens %d out of [1,%d]", max_new, LMAX);
+  ATS_REQUIRE(k >= 1 && k <= MAXB, ATSPEED_ERR_CAPACITY, "session_create: beam size %d out of [1,%d]", k, MAXB);
+  ATS_REQUIRE(dk >= k && dk <= MAXB, ATSPEED_ERR_CAPACITY, "session_create: draft beam size %d must be in [k=%d, %d]", dk, k, MAXB);
+  ATS_REQUIRE(gamma >= 1 && gamma <= ATSPEED_MAX_GAMMA, ATSPEED_ERR_CAPACITY, "session_create: gamma %d out of [1,%d]", gamma, ATSPEED_MAX_GAMMA);
+  for (int i = 0; i < n_lanes; ++i) {
+    const atspeed_decoder *d = lanes[i], *d0 = lanes[0];
+    ATS_REQUIRE(d && d->draft && d->target == d0->target && d->draft == d0->draft, ATSPEED_ERR_INVALID,
+                "session_create: lanes must be decoders of one target/draft pair");
+    for (int j = 0; j < i; ++j) ATS_REQUIRE(lanes[i] != lanes[j], ATSPEED_ERR_INVALID, "session_create: decoder %d used twice", i);
+    ATS_REQUIRE(d->max_prompt >= max_prompt, ATSPEED_ERR_CAPACITY, "session_create: lane %d holds prompts of %d tokens, the session asks for %d",
+                i, d->max_prompt, max_prompt);
+    ATS_REQUIRE(d->sample == d0->sample && d->temperature == d0->temperature && d->top_k == d0->top_k && d->top_p == d0->top_p &&
+                d->min_keep == d0->min_keep, ATSPEED_ERR_INVALID, "session_create: lane %d differs from lane 0 in sampling mode, temperature or warpers", i);
+  }
+  atspeed_llama *T = lanes[0]->target, *D = lanes[0]->draft;
+  ATS_REQUIRE(fsm->dev.vocab == T->cfg.vocab_size, ATSPEED_ERR_INVALID, "session_create: constraint vocab %d != model vocab %d", fsm->dev.vocab,
+              T->cfg.vocab_size);
+  ATS_REQUIRE(!(lanes[0]->sample && fsm->dev.n_nodes == 0), ATSPEED_ERR_INVALID,
+              "session_create: sampling needs a constraint automaton (mask-free search is greedy only)");
+  Building<atspeed_session> s(new atspeed_session(n_lanes), atspeed_session_destroy);
+  s->lanes.assign(lanes, lanes + n_lanes);
+  s->fsm = fsm; s->gamma = gamma; s->max_new = max_new; s->k = k; s->dk = dk; s->max_prompt = max_prompt; s->st = (hipStream_t)stream;
+  // everything a round allocates on demand, now: activations for the worst round, stage events, the staging ring, the split-K arenas
+  ATS_TRY(bssd_ensure_capacity(T, D, n_lanes, max_prompt, gamma, k, dk));
+  hipEvent_t* ev = nullptr;
+  ATS_TRY(stage_events(&ev));
+  const int32_t zero = 0; const void* staged = nullptr;
+  ATS_TRY(ats_stage(&zero, sizeof(zero), &staged, s->st));
+  const bool got_t = session_reserve_arena(T, n_lanes * (std::max(max_prompt, k) + gamma * dk), s->st);
+  const bool got_d = session_reserve_arena(D, n_lanes * std::max(max_prompt, dk + k), s->st);
+  ATS_HIP(hipStreamSynchronize(s->st));
+  ats_stage_reset();
+  g_last_error.clear();
+  if (!got_t || !got_d) {
+    s->arena_failed = true;
+    atspeed_set_error("session_create: no room for the %s model's split-K arena (%zu MB): thin GEMM grids of rounds above 256 tokens take the "
+                      "device's shared arena or the plain grid", got_t ? "draft" : "target", ATS_SK_ARENA_BYTES >> 20);
+  }
+  *out = s.release();
+  return ATSPEED_OK;
+}
+
+extern "C" void atspeed_session_destroy(atspeed_session* s) { delete s; }
+
+extern "C" int atspeed_session_submit(atspeed_session* s, const int32_t* prompt, int32_t P, int32_t start_node, uint32_t seed,
+                                      int32_t* out_tokens, float* out_scores, atspeed_gen_stats* stats, int64_t* ticket_out) {
+  ATS_REQUIRE(s && ticket_out, ATSPEED_ERR_INVALID, "session_submit: null argument");
+  ATS_TRY(check_common(s->lanes[0], prompt, P, s->fsm, start_node, s->max_new, s->k, out_tokens, out_scores));
+  ATS_REQUIRE(P <= s->max_prompt, ATSPEED_ERR_CAPACITY, "session_submit: prompt length %d exceeds the session's max_prompt %d", P, s->max_prompt);
+  // a user's rounds need up to P + (max_new - 1) * dk KV slots (every draft block of the call kept): refused here, where it costs nobody else
+  // a round, rather than inside one
+  const int slots = P + (s->max_new - 1) * s->dk, max_slots = s->lanes[0]->target->cfg.max_slots;
+  ATS_REQUIRE(slots <= max_slots, ATSPEED_ERR_CAPACITY, "session_submit: prompt of %d tokens can need %d KV slots (%d available)", P, slots, max_slots);
+  *ticket_out = s->q.submit(SessionJob{prompt, P, start_node, seed, out_tokens, out_scores, stats});
+  return ATSPEED_OK;
+}
+
+// admission, one round over the occupied lanes, retirement
+static int session_round(atspeed_session* s) {
+  hipEvent_t* g_ev = nullptr;
+  ATS_TRY(stage_events(&g_ev));
+  std::vector<atspeed_decoder*> fresh;
+  std::vector<const int32_t*> prompts; std::vector<int32_t> lens, starts;
+  ATS_TRY(s->q.admit([&](int lane, int64_t, SessionJob& j) {
+    atspeed_decoder* d = s->lanes[lane];
+    d->seed = j.seed;                                   // draws follow the user, not the lane
+    ATS_TRY(bssd_begin(d, j.prompt, j.P, s->fsm, j.start_node, s->gamma, s->max_new, s->k, s->dk, j.out_tokens, j.out_scores, j.stats, s->st, false));
+    fresh.push_back(d); prompts.push_back(j.prompt); lens.push_back(j.P); starts.push_back(j.start_node);
+    return (int)ATSPEED_OK;
+  }));
+  if (!fresh.empty()) ATS_TRY(init_prompts_multi(fresh.data(), (int)fresh.size(), prompts.data(), lens.data(), starts.data(), s->st));
+  std::vector<atspeed_decoder*> decs; std::vector<int> lane_of;
+  for (int l = 0; l < s->q.n_lanes(); ++l) if (s->q.lane_busy(l)) { decs.push_back(s->lanes[l]); lane_of.push_back(l); }
+  if (decs.empty()) return ATSPEED_OK;
+  ATS_TRY(bssd_ensure_capacity(decs[0]->target, decs[0]->draft, s->q.n_lanes(), s->max_prompt, s->gamma, s->k, s->dk));   // create made it: a no-op
+  s->q.begin_round();
+  RoundCtl ctl{false, true};
+  ATS_TRY(bssd_round(decs.data(), (int)decs.size(), s->st, g_ev, ctl));
+  s->target_forwards += ctl.target_forwards; s->draft_forwards += ctl.draft_forwards;
+  for (size_t i = 0; i < decs.size(); ++i) if (decs[i]->run.done) s->q.retire(lane_of[i], decs[i]->run.s.status);
+  return ATSPEED_OK;
+}
+
+// session_round with the allocation count around it; a failed round ends the users in lanes with its status (their state on the device is
+// not to be trusted): their records are handed out by the next call, so every ticket still comes back exactly once
+static int session_round_guarded(atspeed_session* s) {
+  const long long a0 = g_ats_lazy_allocs.load();
+  const int rc = session_round(s);
+  s->allocs_after_create += g_ats_lazy_allocs.load() - a0;
+  if (rc != ATSPEED_OK) {
+    const std::string why = g_last_error;
+    (void)hipStreamSynchronize(s->st); (void)hipGetLastError();
+    ats_stage_reset();
+    for (int l = 0; l < s->q.n_lanes(); ++l)
+      if (s->q.lane_busy(l)) {
+        atspeed_decoder::Run& r = s->lanes[l]->run;
+        r.done = true; r.s.status = rc; r.s.n_valid = 0;
+        if (r.stats_out) *r.stats_out = r.s;
+        s->q.retire(l, rc);
+      }
+    g_last_error = why;
+  }
+  return rc;
+}
+
+// the finished users not yet reported, oldest first, as the ABI's records
+static int session_take_done(atspeed_session* s, atspeed_session_done* out, int cap) {
+  int n = 0;
+  for (ats_session::Done d; n < cap && s->q.take_done(&d, 1) == 1; ++n)
+    out[n] = atspeed_session_done{d.ticket, d.lane, d.status, d.rounds_queued, d.rounds_in_lane};
+  return n;
+}
+
+extern "C" int atspeed_session_round(atspeed_session* s, atspeed_session_done* done_out, int32_t cap, int32_t* n_out) {
+  ATS_REQUIRE(s && n_out, ATSPEED_ERR_INVALID, "session_round: null argument");
+  *n_out = 0;
+  const int64_t in_lanes = std::min<int64_t>(s->q.n_lanes(), s->q.pending());
+  ATS_REQUIRE(in_lanes + s->q.done_waiting() == 0 || (done_out && cap >= in_lanes + s->q.done_waiting()), ATSPEED_ERR_CAPACITY,
+              "session_round: room for %d records, %lld users can finish", cap, (long long)(in_lanes + s->q.done_waiting()));
+  if (!s->q.idle()) ATS_TRY(session_round_guarded(s));
+  *n_out = session_take_done(s, done_out, cap);
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_session_drain(atspeed_session* s, atspeed_session_done* done_out, int32_t cap, int32_t* n_out) {
+  ATS_REQUIRE(s && n_out, ATSPEED_ERR_INVALID, "session_drain: null argument");
+  *n_out = 0;
+  const int64_t all = s->q.pending() + s->q.done_waiting();
+  ATS_REQUIRE(all == 0 || (done_out && cap >= all), ATSPEED_ERR_CAPACITY, "session_drain: room for %d records, %lld users pending", cap, (long long)all);
+  while (!s->q.idle()) ATS_TRY(session_round_guarded(s));
+  *n_out = session_take_done(s, done_out, cap);
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_session_get_counters(const atspeed_session* s, atspeed_session_counters* out) {
+  ATS_REQUIRE(s && out, ATSPEED_ERR_INVALID, "session_get_counters: null argument");
+  const atspeed_llama* T = s->lanes[0]->target;
+  *out = atspeed_session_counters{s->q.rounds(), s->target_forwards, s->draft_forwards, s->q.lane_rounds(), s->q.admitted(), s->q.retired(),
+                                  s->allocs_after_create, T->act && T->act->sk.ws ? 1 : 0, s->arena_failed ? 1 : 0, s->q.n_lanes(), s->q.occupied(),
+                                  s->q.queued()};
+  return ATSPEED_OK;
 }
 
 // ---- target_generate (beamSD.py:544-595) for n users in lock step: step g of every user is ONE forward + one beam-step launch

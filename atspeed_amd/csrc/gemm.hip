@@ -1216,6 +1216,7 @@ static const SkArena* sk_shared_arena(hipStream_t st) {              // g_sk_mu 
   SkShared& w = g_sk[d];
   if (w.failed) return nullptr;
   if (!w.a.ws) {
+    g_ats_lazy_allocs++;
     float* ws = nullptr; int* cnt = nullptr; hipEvent_t ev = nullptr;
     if (hipMalloc((void**)&ws, ATS_SK_ARENA_BYTES) != hipSuccess || hipMalloc((void**)&cnt, ATS_SK_ARENA_COUNTERS * sizeof(int)) != hipSuccess ||
         hipMemset(cnt, 0, ATS_SK_ARENA_COUNTERS * sizeof(int)) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {

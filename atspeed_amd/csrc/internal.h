@@ -57,6 +57,9 @@ enum { ATS_PATH_RING = 0, ATS_PATH_RING_SK = 1, ATS_PATH_WDMA = 2, ATS_PATH_WDMA
        ATS_PATH_FP4 = 12 /* W4A8 (gemm_w4a8_kernel), any form */,
        ATS_N_PATHS = 16 };
 extern std::atomic<long long> g_ats_path_cnt[ATS_N_PATHS];          // engine.hip
+// device / pinned allocations, events, streams and graphs the library makes ON DEMAND, process-wide (engine.hip; every site that can be reached
+// from a decode round counts itself here): a session reads it around its rounds, where it must not move
+extern std::atomic<long long> g_ats_lazy_allocs;
 inline void ats_count_path(int p) { g_ats_path_cnt[p].fetch_add(1, std::memory_order_relaxed); }
 
 // Process-wide tuning / test switches (engine.hip): each is an int initialised ONCE from its environment variable and changeable afterwards

@@ -38,6 +38,9 @@ def parse(argv=None):
     ap.add_argument("--L", type=int, default=0)
     ap.add_argument("--R", type=int, default=None)
     ap.add_argument("--users_per_batch", type=int, default=128, help="users decoded in lock step (1 = the reference's loop)")
+    ap.add_argument("--stream_lanes", type=int, default=None, metavar="N",
+                    help="beam-SD through a session of N lanes instead of lock-step batches: a finished user's lane is refilled at the next round "
+                         "boundary (BSSD_batch(..., lanes=N)); --users_per_batch is then unused")
     ap.add_argument("--strict_trie", action="store_true", help="strict item trie instead of the position-set mask")
     ap.add_argument("--decoder", choices=("bssd", "beam"), default="bssd",
                     help="bssd = beam speculative decoding (the reference's method); beam = plain constrained beam search of the target in lock "
@@ -72,6 +75,8 @@ def parse(argv=None):
         ap.error("--target_fp4 makes its MXFP4 copies from 16-bit weights: use --dtype auto, fp16 or bf16")
     if (args.top_k is not None or args.top_p is not None) and not args.do_sample:
         ap.error("--top_k / --top_p warp sampled scores: they need --do_sample")
+    if args.stream_lanes is not None and (args.decoder != "bssd" or args.stream_lanes < 1):
+        ap.error("--stream_lanes N needs --decoder bssd and N >= 1")
     if args.target_fp4 and args.target_fp8:
         ap.error("--target_fp4 and --target_fp8 are exclusive: choose one target precision")
     return args
@@ -142,7 +147,8 @@ def main(argv=None):
     max_prompt = longest_prompt(data, args.L + lo, args.L + hi, tok)
     for beam in ast.literal_eval(args.run_beam_sizes):          # the reference eval()s this flag (inference.py:151); a literal list is all it needs
         tgt, drf = load_models(args, data.index.vocab_size, beam, dev, max_prompt)
-        res = run_inference(tgt, drf, data, args.gamma, 4, args.L + lo, args.L + hi, args.users_per_batch, fn, tok, args.baseline, dev, args.decoder)
+        res = run_inference(tgt, drf, data, args.gamma, 4, args.L + lo, args.L + hi, args.users_per_batch, fn, tok, args.baseline, dev, args.decoder,
+                            stream_lanes=args.stream_lanes)
         c = res.counters()
         per_rank = all_gather_counters(Counters(len(res.rows), int(sum(r["n_run"] for r in res.rows)),
                                                 int(sum(r["total_accept_steps"] for r in res.rows)), int(res.wall_s * 1e9)), dev)

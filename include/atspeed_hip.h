@@ -323,6 +323,73 @@ int atspeed_bssd_generate_batch(atspeed_decoder** decoders, int32_t n, const int
                                 int32_t* const* out_tokens_dev, float* const* out_scores_dev,
                                 atspeed_gen_stats* stats_host /* [n] */, void* stream);
 
+/* ------------------------------------------------------------------ sessions: a queue of users over a fixed set of lanes
+ * atspeed_bssd_generate_batch decodes a fixed list in lock step: a user that finishes leaves its place empty until the slowest user of the
+ * call is done.  A session keeps `n_lanes` decoders (lanes) busy instead: users are submitted to a host queue at any time, and at every round
+ * boundary each free lane takes the next queued user (in submission order) before the round runs.  A round is exactly the round of the batch
+ * call -- draft steps, ONE packed target forward, verify / final steps, exports, one stream synchronisation -- over the occupied lanes; a user's
+ * prompt is ingested inside its first round's forwards.  Every user's result equals its own atspeed_bssd_generate call (scores to fp32
+ * rounding, as in the batch call).  No reference counterpart (the reference decodes one user at a time, inference.py:162-176).
+ *
+ * Ownership: the lanes' decoders, the automaton and the models belong to the caller and must outlive the session; the session never creates or
+ * destroys a decoder, and a lane must not be used by another call while the session holds a user on it.  Per user, prompt_dev, out_tokens_dev
+ * [k][max_new_tokens], out_scores_dev [k] and stats_host must stay valid from submit until the user's ticket has been returned by
+ * atspeed_session_round / _drain (the statistics are written by then; the result block is written -- for a filtered user blanked -- in stream order,
+ * so it is read on the session's stream or after synchronising it).  One host thread drives a session.
+ *
+ * atspeed_session_create: lanes[n_lanes] (1 .. 256) of ONE target / draft pair, each with max_prompt capacity >= `max_prompt`, all in the
+ * same sampling mode, temperature and warpers (else ATSPEED_ERR_INVALID).  Makes every allocation a round can need: the models' activation
+ * buffers for the worst round (n_lanes x (max(max_prompt, k) + gamma x dk) target tokens), the staging ring and stage events, and -- when that
+ * round reaches 257 tokens on a 16-bit model -- the split-K arena that otherwise appears in front of the first large forward.  An arena that
+ * cannot be had does not fail the call: atspeed_last_error says so and the counter arena_failed is set.
+ * atspeed_session_submit: queues one user (launches nothing) and returns its ticket (1, 2, ... in submission order) in *ticket_out.  `seed` is
+ * the user's sampling stream (ignored by greedy lanes): it is put on the lane the user is admitted to, so draws follow users, not lanes.  A
+ * prompt longer than max_prompt returns ATSPEED_ERR_CAPACITY and leaves the session as it was; so does a prompt whose rounds could need more KV
+ * slots than the models have (prompt_len + (max_new_tokens - 1) x dk: every draft block of the call kept) -- the lock-step calls find that only in
+ * the round that runs out, where it would end every user of the round.
+ * atspeed_session_round: admission (per free lane the next queued user; one prompt-init launch for all of them), one round, retirement.  One record per user that
+ * finished goes to done_out[0 .. *n_out) (cap >= n_lanes always suffices; with less room the call is refused before it launches anything):
+ * its ticket, the lane it held, its status, and how many rounds of the session it waited in the queue and spent in its lane.
+ * A user whose step lost every beam to the id filter retires with stats.status = ATSPEED_ERR_FILTERED, n_valid = 0 and a blanked result block
+ * (scores -inf, tokens 0), as in the batch call; the other lanes go on.  With nothing queued and no lane occupied the call does nothing and
+ * returns ATSPEED_OK with *n_out = 0.  Any other error is returned by the call and ends the users then in lanes: the lanes are freed,
+ * and the NEXT round / drain call hands out their records with that error as status (stats_host->status likewise, n_valid = 0, result block
+ * undefined), so every ticket still comes back exactly once; queued users are untouched.
+ * atspeed_session_drain: rounds until queue and lanes are empty; records as above, cap >= users pending (queued + in lanes), else
+ * ATSPEED_ERR_CAPACITY before anything is launched.  A round that fails ends the drain with its error; the records of that round's users and of
+ * users that finished in earlier rounds of that drain are handed out by the next round / drain call.
+ * Stage times: a round's stage time is shared equally by the users active in it; n_target_forwards / n_draft_forwards stay per user. */
+typedef struct atspeed_session atspeed_session;
+typedef struct atspeed_session_counters {
+  int64_t rounds;                  /* rounds that ran (empty rounds do not count)                                  */
+  int64_t target_forwards;         /* packed target forwards launched (one per round)                               */
+  int64_t draft_forwards;          /* draft forwards launched (up to gamma per round)                               */
+  int64_t lane_rounds;             /* sum over rounds of the lanes occupied in it                                   */
+  int64_t users_admitted, users_retired;
+  int64_t allocs_after_create;     /* on-demand allocations the library made while this session's rounds ran: stays 0.  Counted: activation
+                                      buffers, a model's and the device's shared split-K arena, staging ring, stage and profiling events, graph
+                                      capture stream and graph instantiations (switch "graphs"), decoders' sampling tables.  The count is
+                                      process-wide: what another host thread makes the library allocate during a round is charged here too */
+  int32_t arena_reserved;          /* 1: the target owns its split-K arena                                          */
+  int32_t arena_failed;            /* 1: create wanted the arena and could not get it                               */
+  int32_t n_lanes, lanes_occupied; /* now                                                                           */
+  int64_t queued;                  /* users submitted and not yet admitted                                          */
+} atspeed_session_counters;
+int atspeed_session_create(atspeed_decoder* const* lanes, int32_t n_lanes, const atspeed_fsm* fsm, int32_t gamma, int32_t max_new_tokens,
+                           int32_t k, int32_t dk, int32_t max_prompt, void* stream, atspeed_session** out);
+int atspeed_session_submit(atspeed_session* s, const int32_t* prompt_ids_dev, int32_t prompt_len, int32_t start_node, uint32_t seed,
+                           int32_t* out_tokens_dev, float* out_scores_dev, atspeed_gen_stats* stats_host, int64_t* ticket_out);
+typedef struct atspeed_session_done {
+  int64_t ticket;
+  int32_t lane, status;            /* ATSPEED_OK, ATSPEED_ERR_FILTERED, or the error of the round that ended it (= stats_host->status) */
+  int64_t rounds_queued;           /* rounds the session ran between this user's submit and its admission           */
+  int64_t rounds_in_lane;          /* rounds it took part in                                                        */
+} atspeed_session_done;
+int atspeed_session_round(atspeed_session* s, atspeed_session_done* done_out, int32_t cap, int32_t* n_out);
+int atspeed_session_drain(atspeed_session* s, atspeed_session_done* done_out, int32_t cap, int32_t* n_out);
+int atspeed_session_get_counters(const atspeed_session* s, atspeed_session_counters* out);
+void atspeed_session_destroy(atspeed_session* s);   /* frees the session's own tables only: the lanes' decoders are not touched */
+
 int atspeed_target_generate(atspeed_decoder* d, const int32_t* prompt_ids_dev, int32_t prompt_len,
                             const atspeed_fsm* fsm, int32_t start_node, int32_t max_new_tokens, int32_t k,
                             int32_t* out_tokens_dev, float* out_scores_dev, atspeed_gen_stats* stats_host,
