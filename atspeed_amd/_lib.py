@@ -16,6 +16,7 @@ LIB_PATH = os.path.abspath(os.environ["ATSPEED_LIB"]) if os.environ.get("ATSPEED
 ATSPEED_F32, ATSPEED_BF16, ATSPEED_F16 = 0, 1, 2
 WEIGHTS_ROW_MAJOR, WEIGHTS_PACKED = 0, 1
 MAX_BEAMS, MAX_NEW_TOKENS, MAX_GAMMA = 64, 16, 8
+LORA_MAX_RANK = 64
 ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_CONSTRAINT, ERR_NO_DEVICE, ERR_FILTERED = -1, -2, -3, -4, -5, -6
 EPI_STORE, EPI_F32, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3
 
@@ -29,6 +30,10 @@ class LlamaConfig(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("n_layers", C.c_int32), ("n_heads", C.c_int32),
                 ("ffn", C.c_int32), ("rope_theta", C.c_float), ("rms_eps", C.c_float), ("dtype", C.c_int32),
                 ("max_slots", C.c_int32), ("max_tokens", C.c_int32), ("max_logit_rows", C.c_int32), ("weight_layout", C.c_int32)]
+
+
+class LoraLayer(C.Structure):
+    _fields_ = [("a_q", C.c_void_p), ("b_q", C.c_void_p), ("a_k", C.c_void_p), ("b_k", C.c_void_p), ("a_v", C.c_void_p), ("b_v", C.c_void_p)]
 
 
 class GenStats(C.Structure):
@@ -81,6 +86,11 @@ SIGNATURES = {
     "atspeed_gemm_w4a8": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "atspeed_llama_rope_fused_launches": (C.c_int64, [_P, _I]),
     "atspeed_llama_sk_arena_bytes": (C.c_int64, [_P]),
+    "atspeed_llama_set_lora": (C.c_int, [_P, _I, _F, C.POINTER(LoraLayer), _P]),
+    "atspeed_llama_clear_lora": (C.c_int, [_P]),
+    "atspeed_llama_lora_launches": (C.c_int64, [_P, _I]),
+    "atspeed_lora_shrink": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
+    "atspeed_segs_lora_rope_kv": (C.c_int, [_P, _P, _P, _P, _P, _I, _F, _P, _P, _SZ, _I, _I, _I, _I] + _SEGS + [_P]),
     "atspeed_quant_rows_fp8": (C.c_int, [_P, _I, _I, _P, _P, _P]),
     "atspeed_quant_rows_fp8_packed": (C.c_int, [_P, _I, _I, _P, _P, _P]),
     "atspeed_gemm_fp8": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),

@@ -302,6 +302,21 @@ template <typename T> __device__ __forceinline__ float resid_add(T* h, float pro
   return round_elt<T>(v);
 }
 
+// LoRA side path beside a q / k / v projection (lora.hip; peft's `result + lora_B(lora_A(x)) * scaling` in T with fp32 accumulation inside
+// each matmul).  Every intermediate is a T tensor:
+//   u = round(sum_k xn[k] A[j][k])            lora_A's output: lora_u<T> of the fp32 sum (xn = the layer's RMSNorm output as rmsnorm_kernel rounds it)
+//   d = round(sum_j u[j] B[c][j])             lora_B's output
+//   y = round(base16 + round(scaling * d))    base16 = the projection's T output; RoPE (rope_pk) then works on y
+// lora_add takes the fp32 sum of d.  The fp32 engine (parity mode) rounds nothing.
+template <typename T> __device__ __forceinline__ float lora_u(float acc) { return round_elt<T>(acc); }
+template <typename T> __device__ __forceinline__ float lora_add(float base16, float d_acc, float scaling) {
+  float p = scaling * round_elt<T>(d_acc);
+  if constexpr (sizeof(T) == 2) {
+    asm("" : "+v"(p));                       // the scaled product is a value of its own before it is rounded (as norm_scale)
+    return round_elt<T>(base16 + round_elt<T>(p));
+  } else return base16 + p;
+}
+
 // SwiGLU: gate and up rounded to T first (the reference's two projections are T tensors), SiLU and the product in fp32, one rounding.  The
 // fp32 engine (parity mode) rounds nothing and takes the exact quotient.
 __device__ __forceinline__ uint32_t swiglu_pk(float g0, float g1, float u0, float u1) {

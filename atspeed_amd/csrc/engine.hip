@@ -251,6 +251,7 @@ struct ActCtx {
   float* lse_part = nullptr; size_t lse_part_bytes = 0;   // [cap_rows][vocab tiles] (max, sum exp) partials of the fused lm_head epilogue
   int32_t* row_cand = nullptr;                   // [cap_rows][ATSPEED_MAX_BEAMS] best tokens per logit row (mask-free search only)
   RowInfo* rowinfo = nullptr;                    // [cap_tok] cache / slot / rotation of each batched row (qkv projection's fused epilogue)
+  void* lora_u = nullptr;                        // [cap_tok][3 * 64] lora_A outputs of a model with an adapter (lora_u_ensure: atspeed_llama_set_lora, or with the buffers above)
   void* xq = nullptr; float* sx = nullptr;       // fp8 activations [cap_tok][max(hidden, ffn)] + per-token scales
   void* ws = nullptr; size_t ws_bytes = 0;       // split-K slabs
   SkArena sk;                                    // the ring kernel's split-K tail (16-bit models: internal.h SkArena): allocated in front of the first forward of
@@ -291,6 +292,14 @@ struct atspeed_llama {
   // optional MXFP4 copies (e2m1 nibbles [rows][K / 2] + E8M0 scale bytes [rows][K / 32], gemm.hip "W4A8") (atspeed_llama_enable_fp4); exclusive with fp8
   using Fp4Layer = QuantLayer<void>;
   std::vector<Fp4Layer> fp4;
+  // optional LoRA adapter kept beside the base (atspeed_llama_set_lora): library-owned zero-padded copies in ONE device block, per layer the
+  // stacked A_cat [3 R16][hidden] (q, k, v; an absent module's rows are zero) and B_m [hidden][R16] (NULL = module not adapted)
+  struct LoraLayer { const void* a_cat = nullptr; const void* b[3] = {nullptr, nullptr, nullptr}; };
+  std::vector<LoraLayer> lora;                   // empty = no adapter: the forward is then launch for launch what it was without this feature
+  void* lora_mem = nullptr;
+  int lora_r16 = 0;
+  float lora_scaling = 0.f;
+  long lora_cnt = 0;                             // shrink + expand launches (atspeed_llama_lora_launches)
   KvCache kv0;                                   // cache of the plain atspeed_llama_forward API
   std::vector<KvCache> kv_pool;                  // one more cache per segment of atspeed_llama_forward_batch (grown on demand)
   ActCtx* act;                                   // grown on demand (ensure_act)
@@ -364,13 +373,20 @@ static size_t gemm_ws_for(const atspeed_llama_config& c, int max_tok, int max_ro
 static void act_free(ActCtx* cx) {
   if (!cx) return;
   hipFree(cx->h); hipFree(cx->xn); hipFree(cx->qkv); hipFree(cx->att); hipFree(cx->act); hipFree(cx->gath);
-  hipFree(cx->logits); hipFree(cx->lse); hipFree(cx->lse_part); hipFree(cx->ws); hipFree(cx->xq); hipFree(cx->sx); hipFree(cx->rowinfo);
+  hipFree(cx->logits); hipFree(cx->lse); hipFree(cx->lse_part); hipFree(cx->ws); hipFree(cx->xq); hipFree(cx->sx); hipFree(cx->rowinfo); hipFree(cx->lora_u);
   hipFree(cx->row_cand); hipFree(cx->sk.ws); hipFree(cx->sk.cnt);
   for (hipEvent_t e : cx->prof_ev) hipEventDestroy(e);
   for (auto& g : cx->graphs) hipGraphExecDestroy(g.second);
   if (cx->cap_stream) hipStreamDestroy(cx->cap_stream);
   hipFree(cx->segtab_dev);
   delete cx;
+}
+
+// lora_A's outputs of every token the context can hold, at the largest rank (3 x 64 per token): an adapter of another rank needs no new buffer
+static int lora_u_ensure(atspeed_llama* m, ActCtx* cx) {
+  if (cx->lora_u) return ATSPEED_OK;
+  ATS_HIP(hipMalloc(&cx->lora_u, (size_t)cx->cap_tok * 3 * ATSPEED_LORA_MAX_RANK * m->esz));
+  return ATSPEED_OK;
 }
 
 // make sure the model's activation context can hold `tok` tokens and `rows` logit rows (device must be idle on it)
@@ -403,6 +419,7 @@ static int ensure_act(atspeed_llama* m, int tok, int rows) {
   cx->ws_bytes = gemm_ws_for(c, cx->cap_tok, cx->cap_rows);
   ATS_HIP(hipMalloc(&cx->ws, cx->ws_bytes));
   ATS_HIP(hipMalloc((void**)&cx->segtab_dev, sizeof(SegTable)));
+  if (!m->lora.empty()) ATS_TRY(lora_u_ensure(m, cx.get()));
   m->act = cx.release();
   return ATSPEED_OK;
 }
@@ -498,6 +515,7 @@ extern "C" void atspeed_llama_destroy(atspeed_llama* m) {
   act_free(m->act);
   quant_layers_free(m->fp8);
   quant_layers_free(m->fp4);
+  hipFree(m->lora_mem);
   hipFree(m->cos_tab); hipFree(m->sin_tab);
   delete m;
 }
@@ -633,6 +651,86 @@ extern "C" int atspeed_llama_enable_fp4(atspeed_llama* m, void* stream) {
     }
     return ATS_KD(m->cfg.dtype, ats_quant_weights_mxfp4(w, rows, cols, *q, *sc, st, m->pk));
   });
+}
+
+// ---- LoRA adapter beside the base (lora.hip) ----
+// a model's captured forwards hold the launch sequence of the moment of their capture: setting or clearing an adapter changes it
+static void graphs_drop(atspeed_llama* m) {
+  ActCtx* cx = m->act;
+  if (!cx) return;
+  for (auto& g : cx->graphs) hipGraphExecDestroy(g.second);
+  cx->graphs.clear();
+  cx->graph_seen.clear();
+}
+
+extern "C" int atspeed_llama_clear_lora(atspeed_llama* m) {
+  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "clear_lora: null model");
+  if (m->lora.empty()) return ATSPEED_OK;
+  ATS_HIP(hipDeviceSynchronize());                 // forwards in flight read the copies
+  graphs_drop(m);
+  m->lora.clear();
+  hipFree(m->lora_mem);
+  m->lora_mem = nullptr;
+  m->lora_r16 = 0; m->lora_scaling = 0.f;
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_llama_set_lora(atspeed_llama* m, int32_t rank, float scaling, const atspeed_lora_layer* layers, void* stream) {
+  ATS_REQUIRE(m && layers, ATSPEED_ERR_INVALID, "set_lora: null argument");
+  ATS_REQUIRE(rank >= 1 && rank <= ATSPEED_LORA_MAX_RANK, ATSPEED_ERR_INVALID, "set_lora: rank %d (1 .. %d)", rank, ATSPEED_LORA_MAX_RANK);
+  ATS_REQUIRE(scaling == scaling && scaling - scaling == 0.f, ATSPEED_ERR_INVALID, "set_lora: scaling must be finite");
+  const int L = m->cfg.n_layers, H = m->cfg.hidden, r16 = (rank + 15) / 16 * 16;
+  const size_t e = m->esz;
+  bool any = false;
+  for (int l = 0; l < L; ++l) {
+    const void* const ab[3][2] = {{layers[l].a_q, layers[l].b_q}, {layers[l].a_k, layers[l].b_k}, {layers[l].a_v, layers[l].b_v}};
+    for (int k = 0; k < 3; ++k) {
+      ATS_REQUIRE(!ab[k][0] == !ab[k][1], ATSPEED_ERR_INVALID, "set_lora: layer %d has one half of a module's (A, B) pair", l);
+      any = any || ab[k][0];
+    }
+  }
+  ATS_REQUIRE(any, ATSPEED_ERR_INVALID, "set_lora: no module is adapted (atspeed_llama_clear_lora removes an adapter)");
+  hipStream_t st = (hipStream_t)stream;
+  // the new copies are built aside; the model changes only after they are complete
+  const size_t a_bytes = (size_t)3 * r16 * H * e, b_bytes = (size_t)H * r16 * e;       // multiples of 16 bytes (hidden % 8 == 0, r16 % 16 == 0)
+  const size_t per_layer = a_bytes + 3 * b_bytes;
+  char* mem = nullptr;
+  ATS_HIP(hipMalloc((void**)&mem, per_layer * L));
+  std::vector<atspeed_llama::LoraLayer> ll(L);
+  auto fill = [&]() -> int {
+    ATS_HIP(hipMemsetAsync(mem, 0, per_layer * L, st));
+    for (int l = 0; l < L; ++l) {
+      char* base = mem + per_layer * l;
+      const void* const ab[3][2] = {{layers[l].a_q, layers[l].b_q}, {layers[l].a_k, layers[l].b_k}, {layers[l].a_v, layers[l].b_v}};
+      ll[l].a_cat = base;
+      for (int k = 0; k < 3; ++k) {
+        if (!ab[k][0]) continue;
+        char* bdst = base + a_bytes + k * b_bytes;
+        ATS_HIP(hipMemcpyAsync(base + (size_t)k * r16 * H * e, ab[k][0], (size_t)rank * H * e, hipMemcpyDeviceToDevice, st));              // A [rank][H] -> rows of A_cat
+        ATS_HIP(hipMemcpy2DAsync(bdst, r16 * e, ab[k][1], rank * e, rank * e, H, hipMemcpyDeviceToDevice, st));                          // B [H][rank] -> [H][R16]
+        ll[l].b[k] = bdst;
+      }
+    }
+    ATS_HIP(hipStreamSynchronize(st));             // the caller's tensors may go once this returns
+    return ATSPEED_OK;
+  };
+  int rc = fill();
+  if (rc == ATSPEED_OK && m->act) rc = lora_u_ensure(m, m->act);
+  if (rc == ATSPEED_OK && hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); atspeed_set_error("set_lora: device synchronisation failed"); rc = ATSPEED_ERR_HIP; }
+  if (rc != ATSPEED_OK) { hipFree(mem); return rc; }
+  graphs_drop(m);
+  hipFree(m->lora_mem);                            // a second adapter replaces the first
+  m->lora_mem = mem;
+  m->lora = std::move(ll);
+  m->lora_r16 = r16; m->lora_scaling = scaling;
+  return ATSPEED_OK;
+}
+
+extern "C" int64_t atspeed_llama_lora_launches(atspeed_llama* m, int32_t reset) {
+  if (!m) return -1;
+  const int64_t n = m->lora_cnt;
+  if (reset) m->lora_cnt = 0;
+  return n;
 }
 
 // One forward over the tokens of every segment (user) of the table.  Logits of each segment's last n_logit rows land
@@ -849,6 +947,19 @@ extern "C" int atspeed_segs_tree_attention(const void* q, int32_t ldq, size_t la
   ATS_TRY(segs_table("segs_tree_attention", SEGS_VIS | SEGS_KV, qtile_rows, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
   return ATS_KD(dtype, ats_tree_attention_segs(q, ldq, t, dt, layer_off_bytes, vis_words, out, ldo, n_heads, head_dim, dtype, (hipStream_t)stream, rows_per_wave,
                                                packed_out ? 1 : 0));
+}
+
+// atspeed_segs_rope_kv with the adapter's expand in front (lora_rope_kv_segs kernels; header: the memory contract); tests/test_lora_gpu.py
+extern "C" int atspeed_segs_lora_rope_kv(void* qkv, const void* u, const void* b_q, const void* b_k, const void* b_v, int32_t r16, float scaling,
+                                         const float* cos_tab, const float* sin_tab, size_t layer_off_bytes, int32_t n_heads, int32_t head_dim,
+                                         int32_t max_pos, int32_t dtype, ATS_SEGS_PARAMS, void* stream) {
+  ATS_REQUIRE(qkv && u && cos_tab && sin_tab && n_heads >= 1 && head_dim >= 2 && head_dim % 2 == 0 && max_pos >= 1 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID,
+              "segs_lora_rope_kv: bad arguments");
+  ATS_REQUIRE(((uintptr_t)qkv & 15) == 0 && layer_off_bytes % 16 == 0, ATSPEED_ERR_INVALID, "segs_lora_rope_kv: qkv and the layer offset must be 16-byte aligned");
+  SegTable t{}; const SegTable* dt = nullptr;
+  ATS_TRY(segs_table("segs_lora_rope_kv", SEGS_POS | SEGS_SLOTS | SEGS_KV, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
+  return ATS_KD(dtype, ats_lora_rope_kv_segs(qkv, u, b_q, b_k, b_v, r16, scaling, t, dt, cos_tab, sin_tab, layer_off_bytes, n_heads, head_dim, max_pos, dtype,
+                                             (hipStream_t)stream));
 }
 #undef ATS_SEGS_PARAMS
 #undef ATS_SEGS_ARGS

@@ -10,6 +10,25 @@ static int proj_fp8(atspeed_llama* m, const void* x, const void* wq, const float
   return ats_gemm_fp8(cx->xq, cx->sx, wq, sw, out, M, N, K, ldc, epi, st, m->pk, cx->ws, cx->ws_bytes);
 }
 
+// The RoPE + KV-scatter pass of a layer whose qkv projection stored plain 16-bit (fp32) outputs: with an adapter (atspeed_llama_set_lora) the
+// pass that adds lora_B's term first
+static int rope_pass(atspeed_llama* m, int l, const SegTable& t, const SegTable* dtab, size_t loff, hipStream_t st) {
+  const atspeed_llama_config& c = m->cfg;
+  ActCtx* cx = m->act;
+  if (m->lora.empty()) return ats_rope_kv_segs(cx->qkv, t, dtab, m->cos_tab, m->sin_tab, loff, c.n_heads, m->head_dim, c.max_slots, c.dtype, st);
+  const atspeed_llama::LoraLayer& a = m->lora[l];
+  m->lora_cnt++;
+  return ats_lora_rope_kv_segs(cx->qkv, cx->lora_u, a.b[0], a.b[1], a.b[2], m->lora_r16, m->lora_scaling, t, dtab, m->cos_tab, m->sin_tab, loff,
+                               c.n_heads, m->head_dim, c.max_slots, c.dtype, st);
+}
+// lora_A of a layer's normed input for q, k and v at once, from the residual stream (so it does not matter whether the forward left xn or xq / sx)
+static int lora_shrink(atspeed_llama* m, int l, int T, hipStream_t st) {
+  if (m->lora.empty()) return ATSPEED_OK;
+  m->lora_cnt++;
+  return ats_lora_shrink(m->act->h, m->layers[l].input_norm, m->lora[l].a_cat, m->act->lora_u, T, m->cfg.hidden, 3 * m->lora_r16, m->cfg.rms_eps,
+                         m->cfg.dtype, st);
+}
+
 // One layer of the 4-bit target (atspeed_llama_enable_fp4): all four projections W4A8 at every size, the activations exactly the W8A8 ones
 // (per-token e4m3 from the fused RMSNorm / residual reduce or ats_quant_rows_fp8).  qkv: plain 16-bit store, then the RoPE / KV pass (the
 // projection rounded to 16 bits, the rotation in fp32).  On entry cx->xq / cx->sx hold the layer's normed input when xq_ready, else cx->xn does.
@@ -19,11 +38,12 @@ static int layer_fp4(atspeed_llama* m, int l, const SegTable& t, const SegTable*
   const atspeed_llama::Fp4Layer& f = m->fp4[l];
   const int T = t.total_tok, H = c.hidden, pk = m->pk;
   const bool q_next = H <= 8192;                           // the fused norm + e4m3 quantisation exists up to hidden 8192
+  ATS_TRY(lora_shrink(m, l, T, st));
   { ProfBracket pb(m, 0, T, st);
     m->fp4_cnt[0]++;
     if (!xq_ready) ATS_TRY(ats_quant_rows_fp8(cx->xn, T, H, H, cx->xq, cx->sx, st, pk));
     ATS_TRY(ats_gemm_w4a8(cx->xq, cx->sx, f.wqkv, f.sqkv, cx->qkv, T, 3 * H, H, 3 * H, EPI_STORE, st, pk, cx->ws, cx->ws_bytes)); }
-  ATS_TRY(ats_rope_kv_segs(cx->qkv, t, dtab, m->cos_tab, m->sin_tab, loff, c.n_heads, m->head_dim, c.max_slots, c.dtype, st));
+  ATS_TRY(rope_pass(m, l, t, dtab, loff, st));
   ATS_TRY(ats_tree_attention_segs(cx->qkv, 3 * H, t, dtab, loff, m->vis_words, cx->att, H, c.n_heads, m->head_dim, c.dtype, st, 0, pk));
   { ProfBracket pb(m, 1, T, st);     // h += att Wo^T ; then gate_up's input norm (e4m3 rows + scales, or xn)
     m->fp4_cnt[1]++;
@@ -72,14 +92,17 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
   else ATS_TRY(ats_rmsnorm(cx->h, m->layers[0].input_norm, cx->xn, T, H, c.rms_eps, dt, st, pk));
   // RoPE and the KV scatter ride in the qkv projection's epilogue (one pass over qkv / one launch less per layer): the ring kernels of the batched
   // 16-bit and W8A8 forwards, and since round 6 ONE user's W8A8 projection on the weight-streaming kernel (gemm_wdma_kernel<..., EPI_QKV_ROPE, F8>)
-  const bool qkv_rope_fused = f4 ? false : qkv_in_fp8 ? ats_gemm_fp8_qkv_rope_applies(T, H, m->head_dim) : ats_gemm_qkv_rope_applies(T, H, m->head_dim, dt);
+  // a model with an adapter: the plain 16-bit store, then the pass that adds the adapter's term before it rotates (no fused epilogue, no slabs)
+  const bool lora = !m->lora.empty();
+  const bool qkv_rope_fused = f4 || lora ? false : qkv_in_fp8 ? ats_gemm_fp8_qkv_rope_applies(T, H, m->head_dim) : ats_gemm_qkv_rope_applies(T, H, m->head_dim, dt);
   if (qkv_rope_fused) ATS_TRY(ats_row_info(t, dtab, cx->rowinfo, c.max_slots, st));
   for (int l = 0; l < c.n_layers; ++l) {
     const atspeed_llama_layer_weights& w = m->layers[l];
     const size_t loff = (size_t)l * m->layer_kv_bytes;
     if (f4) { ATS_TRY(layer_fp4(m, l, t, dtab, loff, xq_ready, st)); continue; }
     // cx->xn holds rmsnorm(h) * input_norm here (from the embed above or the previous layer's fused down_proj epilogue)
-    const bool fuse_qkv_reduce = ats_switch(ATS_SW_FUSE_QKV_REDUCE) != 0;
+    const bool fuse_qkv_reduce = !lora && ats_switch(ATS_SW_FUSE_QKV_REDUCE) != 0;
+    ATS_TRY(lora_shrink(m, l, T, st));
     int qkv_splits = 0;
     { ProfBracket pb(m, 0, T, st);
       if (qkv_in_fp8) {
@@ -110,7 +133,7 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
     else if (qkv_splits > 0)
       ATS_TRY(ats_rope_kv_segs_slabs((const float*)cx->ws, qkv_splits, cx->qkv, t, dtab, m->cos_tab, m->sin_tab, loff, c.n_heads, m->head_dim, c.max_slots, st));
     else
-      ATS_TRY(ats_rope_kv_segs(cx->qkv, t, dtab, m->cos_tab, m->sin_tab, loff, c.n_heads, m->head_dim, c.max_slots, dt, st));
+      ATS_TRY(rope_pass(m, l, t, dtab, loff, st));
     ATS_TRY(ats_tree_attention_segs(cx->qkv, 3 * H, t, dtab, loff, m->vis_words, cx->att, H, c.n_heads, m->head_dim, dt, st, 0, pk));
     { ProfBracket pb(m, 1, T, st);     // h += att Wo^T ; xn = rmsnorm(h) * post_norm
       if (o_in_fp8) {

@@ -17,6 +17,16 @@ int ats_rmsnorm(const void* x, const void* w, void* y, int rows, int hidden, flo
 // row-major [rows][row_bytes] -> packed operand layout (common.h ats_pk_byte) or back; out of place, row_bytes % 64 == 0
 int ats_pack_rows(const void* src, void* dst, int rows, int row_bytes, int to_packed, hipStream_t st);
 
+// ---- lora.hip -------------------------------------------------------------------------
+// u [rows][r3] = round(A_cat . xn^T) per row, xn = the RMSNorm of h's row under norm_w (recomputed: independent of what the forward left in xn / xq);
+// r3 = 3 x the padded rank (48, 96, 144 or 192), A_cat [r3][hidden]
+int ats_lora_shrink(const void* h, const void* norm_w, const void* a_cat, void* u, int rows, int hidden, int r3, float eps, int dtype,
+                    hipStream_t st);
+// ats_rope_kv_segs with y = base + scaling * (B_m u_m) in front for every module whose B_m [hidden][r16] is not NULL (common.h: lora_add)
+int ats_lora_rope_kv_segs(void* qkv, const void* u, const void* bq, const void* bk, const void* bv, int r16, float scaling, const SegTable& t,
+                          const SegTable* dt, const float* cos_tab, const float* sin_tab, size_t layer_off_bytes, int n_heads, int head_dim,
+                          int max_pos, int dtype, hipStream_t st);
+
 // ---- gemm.hip -------------------------------------------------------------------------
 size_t ats_gemm_workspace_bytes(int m, int n, int k, int dtype);
 // pk = 1: a and w (and a SwiGLU output) are in the packed operand layout of common.h (bf16 / fp8 engine); 0: row-major (HF layout, fp32 mode, ABI tests)

@@ -58,6 +58,10 @@ def parse(argv=None):
                     help="W4A8 target projections: OCP MXFP4 weights (e2m1, one E8M0 scale per 32 k) against the W8A8 e4m3 activations, on the "
                          "block-scaled MFMA; bf16 and fp16 targets only, exclusive with --target_fp8.  Opt-in: MXFP4 without rotation or outlier "
                          "handling costs model quality on real checkpoints")
+    ap.add_argument("--target_lora", type=str, default=None, metavar="DIR",
+                    help="a peft LoRA adapter directory (adapter_config.json + adapter_model.safetensors / .bin; q_proj / k_proj / v_proj) run "
+                         "UNMERGED beside the target, as the reference's PeftModel.from_pretrained target does (inference.py:86-100); the adapter "
+                         "stays 16-bit beside a --target_fp8 / --target_fp4 base")
     ap.add_argument("--dtype", choices=("auto", "fp16", "bf16", "fp32"), default="auto",
                     help="engine arithmetic.  auto: a checkpoint runs in the type it is stored in (fp16 -- what the reference loads, inference.py:75-100 -- "
                          "takes the engine's fp16 flavour and keeps every weight bit; bf16 and fp32 likewise), synthetic weights are bf16")
@@ -110,6 +114,8 @@ def load_models(args, vocab_size: int, beam: int, dev, max_prompt: int = 0):
                 m.generation_config.top_k = args.top_k
             if args.top_p is not None:
                 m.generation_config.top_p = args.top_p
+    if args.target_lora:                    # before the base is quantised: the adapter never goes through e4m3 / e2m1
+        tgt.load_lora(args.target_lora)
     if args.target_fp8:
         tgt.enable_fp8()
     if args.target_fp4:

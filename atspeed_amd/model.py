@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, synth
+from . import lora as _lora
 
 
 def _gen_config(num_beams: int = 1) -> SimpleNamespace:
@@ -103,6 +104,7 @@ class HipLlama:
             self._owner = _lib.Handle.create("atspeed_llama_destroy", lib.atspeed_llama_create, C.byref(cfg), packed["embed"].data_ptr(),
                                              packed["final_norm"].data_ptr(), packed["lm_head"].data_ptr(), layers)
         self.logits_ld = int(lib.atspeed_llama_logits_ld(self._handle))
+        self.lora = None               # SimpleNamespace(r, lora_alpha, scaling, modules) while an adapter is loaded (load_lora)
 
     @staticmethod
     def _pack_rows(t: torch.Tensor) -> torch.Tensor:
@@ -291,6 +293,42 @@ class HipLlama:
     def fp4_counters(self, reset: bool = False) -> Dict[str, Dict[str, int]]:
         """Launches of each layer projection that ran as W4A8 / as 16-bit GEMMs since the last reset (atspeed_llama_fp4_counters)."""
         return self._quant_counters("fp4", reset)
+
+    # ---- LoRA adapter beside the base ------------------------------------------------
+    def load_lora(self, adapter, r: Optional[int] = None, lora_alpha: Optional[float] = None, use_rslora: bool = False) -> "HipLlama":
+        """Run this model with a LoRA adapter on q_proj / k_proj / v_proj WITHOUT merging it (peft's `result + lora_B(lora_A(x)) * scaling`,
+        what the reference's `PeftModel.from_pretrained` target computes, code/inference.py:86-100): the adapter stays in the model's 16-bit
+        type beside a base that may be 16-bit, W8A8 (`enable_fp8`) or W4A8 (`enable_fp4`), loaded before or after those.
+
+        `adapter`: a peft directory (`adapter_config.json` + `adapter_model.safetensors` / `.bin`), or a dict of peft-named tensors
+        (`...layers.{l}.self_attn.{q,k,v}_proj.lora_{A,B}[.default].weight`) together with `r` and `lora_alpha`.  Values are converted to the
+        engine dtype through fp32.  A second adapter replaces the first.  NotImplementedError: target modules other than q / k / v,
+        `use_dora`, `bias != "none"`, `modules_to_save`, rank > 64."""
+        ad = _lora.read(adapter, self.dims.n_layers, self.dims.hidden, r, lora_alpha, use_rslora)
+        arr = (_lib.LoraLayer * self.dims.n_layers)()
+        keep = []
+        with torch.cuda.device(self._device):
+            for l, lw in enumerate(ad.layers):
+                for m in _lora.MODULES:
+                    if m in lw:
+                        a, b = (t.to(self._device, torch.float32).to(self._dtype).contiguous() for t in lw[m])
+                        keep += [a, b]
+                        setattr(arr[l], "a_" + m, a.data_ptr())
+                        setattr(arr[l], "b_" + m, b.data_ptr())
+            _lib.check(_lib.load().atspeed_llama_set_lora(self._handle, ad.r, ad.scaling, arr, _lib.stream_ptr(self._device)))
+        del keep                       # the library holds copies of its own
+        self.lora = SimpleNamespace(r=ad.r, lora_alpha=ad.lora_alpha, scaling=ad.scaling, modules=ad.modules)
+        return self
+
+    def unload_lora(self) -> "HipLlama":
+        """Remove the adapter: later forwards are bit for bit those of a model that never had one."""
+        _lib.check(_lib.load().atspeed_llama_clear_lora(self._handle))
+        self.lora = None
+        return self
+
+    def lora_launches(self, reset: bool = False) -> int:
+        """Adapter kernels launched since the last reset: 2 per layer per forward with an adapter, 0 without (atspeed_llama_lora_launches)."""
+        return int(_lib.load().atspeed_llama_lora_launches(self._handle, 1 if reset else 0))
 
     def rope_fused_launches(self, reset: bool = False) -> int:
         """qkv projections that carried RoPE + the KV scatter in their epilogue since the last reset (atspeed_llama_rope_fused_launches)."""

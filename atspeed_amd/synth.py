@@ -255,3 +255,15 @@ def perturbed_state_dict(sd: Dict[str, np.ndarray], seed: int, sigma: float) -> 
         noise = hash_normal(w.size, tensor_seed(seed, "noise." + name), 1.0).reshape(w.shape)
         out[name] = (w + np.float32(sigma) * np.float32(w.astype(np.float64).std()) * noise).astype(np.float32)
     return out
+
+
+def synthetic_lora(d: LlamaDims, seed: int, r: int = 8, modules: Sequence[str] = ("q", "v"), std: float = 0.02) -> Dict[str, np.ndarray]:
+    """A LoRA adapter in peft's naming for tests and tools: fp32 `lora_A [r, hidden]` and `lora_B [hidden, r]` ~ N(0, std^2) for every layer
+    and every module of `modules` (a subset of q, k, v).  B is NOT zero (peft initialises it to zero: such an adapter would change nothing)."""
+    out: Dict[str, np.ndarray] = {}
+    for l in range(d.n_layers):
+        for m in modules:
+            p = f"base_model.model.model.layers.{l}.self_attn.{m}_proj."
+            out[p + "lora_A.weight"] = hash_normal(r * d.hidden, tensor_seed(seed, p + "lora_A"), std).reshape(r, d.hidden)
+            out[p + "lora_B.weight"] = hash_normal(d.hidden * r, tensor_seed(seed, p + "lora_B"), std).reshape(d.hidden, r)
+    return out

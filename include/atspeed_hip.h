@@ -202,6 +202,31 @@ int64_t atspeed_llama_rope_fused_launches(atspeed_llama* m, int32_t reset);
  * draft or a one-user target never holds one; thin ring-kernel grids of a model without one take the device's shared arena or the plain grid) */
 int64_t atspeed_llama_sk_arena_bytes(const atspeed_llama* m);
 
+/* ---- LoRA adapter kept beside the base weights (peft's unmerged forward: the reference wraps its 8-bit base with
+ * PeftModel.from_pretrained, code/inference.py:86-100).  For an adapted module m of q / k / v of a layer, in the model's dtype T with fp32
+ * accumulation inside each product (round = to T; the fp32 engine rounds nothing):
+ *   u = round(A_m xn),  d = round(B_m u),  y = round(base + round(scaling * d))
+ * xn = the layer's input RMSNorm output, base = the projection's T output (16-bit, W8A8 or W4A8 base alike); RoPE and the KV scatter then
+ * work on y.  A model with an adapter runs per layer one shrink launch (all three modules), the qkv projection with its plain store, and the
+ * RoPE pass that adds the adapter's term first -- no fused RoPE epilogue, no split-K slab hand-off.  A model without one runs launch for
+ * launch as if this section did not exist. */
+#define ATSPEED_LORA_MAX_RANK 64
+/* one layer's adapter, DEVICE pointers in the model's dtype, HF / peft layout: A [rank][hidden] (lora_A.weight), B [hidden][rank]
+ * (lora_B.weight), row-major and dense; a NULL (A, B) pair = that module is not adapted (one NULL half of a pair is refused) */
+typedef struct atspeed_lora_layer { const void *a_q, *b_q, *a_k, *b_k, *a_v, *b_v; } atspeed_lora_layer;
+/* Give the model an adapter, replacing the one it has: layers = HOST array of cfg.n_layers entries.  Memory contract: the library copies
+ * every A and B into zero-padded device copies of its own (one allocation, (3 * R16 * hidden + 3 * hidden * R16) elements per layer, R16 = rank
+ * rounded up to 16) on `stream` and waits for the copies, so the caller's tensors may be freed on return; it also allocates the model's
+ * lora_A output buffer (once, sized for rank 64) -- nothing is allocated inside a forward afterwards.  Waits for the device to be idle and
+ * drops the model's captured graphs.  On failure the model is as it was.  1 <= rank <= ATSPEED_LORA_MAX_RANK, finite scaling (alpha / rank,
+ * or alpha / sqrt(rank) for rslora), at least one adapted module. */
+int atspeed_llama_set_lora(atspeed_llama* m, int32_t rank, float scaling, const atspeed_lora_layer* layers, void* stream);
+/* remove the adapter (no-op without one): waits for the device, frees the copies, drops the captured graphs; later forwards are bit for bit
+ * those of a model that never had one */
+int atspeed_llama_clear_lora(atspeed_llama* m);
+/* shrink + expand launches since the last reset (2 per layer per forward with an adapter, 0 without); -1 on a NULL model */
+int64_t atspeed_llama_lora_launches(atspeed_llama* m, int32_t reset);
+
 /* lm_head fused with the full-vocabulary normaliser of beamSD.py:58,285 (log_softmax over ALL columns, before masking): bf16
  * x [rows, hidden] times w [vocab, hidden]^T -> fp32 logits (row stride ld) and lse[row] = log sum_v exp(logits[row][v]).  On the
  * batched path (rows >= 257 and a tile grid that fills the chip) the (max, sum exp) partials come out of the GEMM epilogue, the
@@ -506,6 +531,14 @@ int atspeed_rmsnorm(const void* x_dev, const void* w_dev, void* y_dev, int32_t r
  * gate_up projections); y_dev may be NULL; q / scale equal atspeed_quant_rows_fp8 of the bf16 norm output bit for bit */
 int atspeed_rmsnorm_quant_fp8(const void* x_dev, const void* w_dev, void* y_dev, void* q_dev, float* scale_dev, int32_t rows,
                               int32_t hidden, float eps, void* stream);
+/* The adapter's shrink kernel alone: u[row][j] = round(sum_k xn[row][k] a_cat[j][k]), xn = norm_w * round(h * rsqrt(mean(h^2) + eps)) rounded
+ * as atspeed_rmsnorm rounds it (the row statistic is the kernel's own fp32 sum), for rows x r3 outputs; r3 = 48, 96, 144 or 192 (3 modules x
+ * the rank rounded up to 16).  Memory contract: reads h [rows][hidden], norm_w [hidden], a_cat [r3][hidden] (dense, row-major, dtype);
+ * writes exactly u [rows][r3] (dense), nothing else; an all-zero row of a_cat gives exact zeros in its column.  16-bit with hidden % 128 == 0
+ * and 16-byte aligned inputs takes the MFMA kernel (16 rows per workgroup; rows past `rows` are neither read nor written), everything else,
+ * fp32 included, one workgroup per row.  Two runs give the same bits. */
+int atspeed_lora_shrink(const void* h_dev, const void* norm_w_dev, const void* a_cat_dev, void* u_dev, int32_t rows, int32_t hidden, int32_t r3,
+                        float eps, int32_t dtype, void* stream);
 /* tree attention over a slot-addressed KV cache ([max_slots][hidden] per K and V)
  * Memory contract (tests/test_guard_bands_gpu.py::test_tree_attention_mfma_guard_bands, ::test_tree_attention_scalar_guard_bands): q rows are ldq
  * >= 3 * hidden elements apart (tested: a multiple of 8), 16-byte aligned; out gets [n_tokens][hidden] and nothing else; q rows >=
@@ -551,6 +584,15 @@ int atspeed_segs_row_info(void* out_dev, int32_t max_pos, ATSPEED_SEGMENTS, void
  * slab order in fp32 and rounded to 16 bits first; then only the q columns of qkv are written.  ::test_rope_kv, ::test_rope_kv_slabs */
 int atspeed_segs_rope_kv(void* qkv_dev, const float* slabs_dev /* may be NULL */, int32_t splits, const float* cos_dev, const float* sin_dev,
                          size_t layer_off_bytes, int32_t n_heads, int32_t head_dim, int32_t max_pos, int32_t dtype, ATSPEED_SEGMENTS, void* stream);
+/* atspeed_segs_rope_kv (slabs == NULL form) with the adapter's expand in front: for every module whose b_*_dev is not NULL, column c of the
+ * module becomes y = round(base + round(scaling * round(sum_j u[row][module * r16 + j] * b[c][j]))) before q and k are rotated and k, v are
+ * scattered; a module with a NULL b takes atspeed_segs_rope_kv's path bit for bit.  Memory contract: reads u_dev [total_tok][3 * r16] (q, k, v
+ * thirds) and b_*_dev [n_heads * head_dim][r16] (dense, pad columns zero; r16 = 16, 32, 48 or 64; 16-byte aligned on the 16-bit vector
+ * path); writes what atspeed_segs_rope_kv writes: the q columns of qkv (the k and v columns stay the projection's) and row `slot` of the
+ * segment's caches.  16-bit with head_dim % 16 == 0 takes the vector kernel, everything else the scalar one. */
+int atspeed_segs_lora_rope_kv(void* qkv_dev, const void* u_dev, const void* b_q_dev, const void* b_k_dev, const void* b_v_dev, int32_t r16,
+                              float scaling, const float* cos_dev, const float* sin_dev, size_t layer_off_bytes, int32_t n_heads, int32_t head_dim,
+                              int32_t max_pos, int32_t dtype, ATSPEED_SEGMENTS, void* stream);
 /* atspeed_tree_attention_tiled over several segments in one launch: row r of segment i attends to the slots < n_slots_visible[i] of that
  * segment's own caches (at layer_off_bytes) whose bit is set in its visibility words (reads vis, kcache, vcache).  qtile_rows 0 = the engine's
  * choice (128 from 16 segments or when half the segments exceed 96 rows, else 64); rows_per_wave as atspeed_tree_attention_tiled.  packed_out =
