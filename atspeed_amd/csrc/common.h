@@ -246,6 +246,12 @@ __device__ __forceinline__ uint32_t ford(float f) {
   uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// ford for a selection key whose ties go to the lower id: -0.0 and +0.0 are EQUAL values, so both take +0.0's key (ford alone ranks
+// +0.0 above -0.0).  The test is on the bits, an integer compare no floating-point simplification can fold; every other input maps as in ford.
+__device__ __forceinline__ uint32_t ford_key(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return ford(__uint_as_float(u == 0x80000000u ? 0u : u));
+}
 __device__ __forceinline__ float ford_inv(uint32_t o) {
   uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
   return __uint_as_float(u);

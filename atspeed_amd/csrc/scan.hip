@@ -228,7 +228,9 @@ __device__ void expand_and_select(ExpandShared& sh, int n_rows, const float* __r
       int tok = free_mode ? row_cand[(size_t)sh.lrow[r] * MAXB + (c - sh.off[r])] : fsm.tok[sh.rp[r] + (c - sh.off[r])];
       if (tok >= 0) {
         float sc = (logits[(size_t)sh.lrow[r] * ld + tok] - sh.lse[r]) + sh.bscore[r];
-        uint32_t o = ford(sc);
+        // -0.0 reaches here only as (-0.0 - +0.0) + -0.0 (x - y of unequal values is never zero and x - x is +0.0), e.g. a processor-rewritten
+        // row with lse = 0: it ties with +0.0 by flat id, and comes out as +0.0
+        uint32_t o = ford_key(sc);
         uint32_t flat = (uint32_t)sh.brow[r] * (uint32_t)fsm.vocab + (uint32_t)tok;
         if (o > kOrdNegInf || sc != sc) key = ((unsigned long long)o << 32) | (unsigned long long)(~flat);
       }
@@ -256,7 +258,7 @@ __global__ __launch_bounds__(kScanThreads) void row_topk_kernel(const float* __r
       unsigned long long key = 0;
       if (col < vocab) {
         const float v = row[col];
-        const uint32_t o = ford(v);
+        const uint32_t o = ford_key(v);                // equal values, the two zeros included, rank by column
         if (o > kOrdNegInf || v != v) key = ((unsigned long long)o << 32) | (unsigned long long)(~(uint32_t)col);
       }
       keys[i] = key;
@@ -382,7 +384,8 @@ __device__ void sample_topn(ExpandShared& sh, const CandRegs& cr, const float (&
     unsigned long long key = 0;
     if (cr.flat[i] >= 0 && logw[i] > -INFINITY) {
       float kf = logw[i] + ats_gumbel(ats_hash_u32((uint32_t)cr.flat[i], sub));
-      key = ((unsigned long long)ford(kf) << 32) | (unsigned long long)(~(uint32_t)cr.flat[i]);
+      // the CPU restatement compares the noisy keys as values: a -0.0 ties with a +0.0
+      key = ((unsigned long long)ford_key(kf) << 32) | (unsigned long long)(~(uint32_t)cr.flat[i]);
     }
     keys[i] = key;
   }
@@ -463,7 +466,7 @@ struct WarpRow {
   const float* logits; const int32_t* tok; int deg; float lse, temperature;
   __device__ __forceinline__ uint32_t key(int j) const {          // 0 = not a candidate
     const float s = (logits[tok[j]] - lse) / temperature;
-    return s > -INFINITY ? ford(s) : 0u;
+    return s > -INFINITY ? ford_key(s) : 0u;         // a -0.0 (logit -0.0, lse +0.0) is tied with +0.0, as in expand_candidates' `s < cut`
   }
 };
 

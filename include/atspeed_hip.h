@@ -267,7 +267,8 @@ int atspeed_beam_expand_prune(const float* logits_dev, int32_t ld, const float* 
 /* The same without a mask (beamSD.py:58,69-78 with an empty processor list; also the expand of rows that a host-side logits
  * processor has already rewritten: pass lse = 0): candidates are ALL `vocab` columns of each row; -inf entries are never picked.
  * atspeed_row_topk: out_tokens[r][ATSPEED_MAX_BEAMS] = the k best columns of row r (value desc, column asc; -1 = fewer finite ones) --
- * the k best (row, token) pairs lie among them.  row_cand_ws_dev: n_rows * ATSPEED_MAX_BEAMS int32 of scratch. */
+ * the k best (row, token) pairs lie among them.  Equal values rank by column, lowest first, and -0.0 equals +0.0 (a plateau of a
+ * rewritten row yields its lowest columns).  row_cand_ws_dev: n_rows * ATSPEED_MAX_BEAMS int32 of scratch. */
 int atspeed_row_topk(const float* scores_dev, int32_t n_rows, int32_t vocab, int32_t ld, int32_t k, int32_t* out_tokens_dev, void* stream);
 int atspeed_beam_expand_prune_free(const float* logits_dev, int32_t ld, const float* lse_dev, const float* beam_score_dev, int32_t n_rows,
                                    int32_t vocab, int32_t k, int32_t* row_cand_ws_dev, float* out_score_dev, int32_t* out_parent_dev,
