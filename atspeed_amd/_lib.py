@@ -19,6 +19,7 @@ MAX_BEAMS, MAX_NEW_TOKENS, MAX_GAMMA = 64, 16, 8
 LORA_MAX_RANK = 64
 ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_CONSTRAINT, ERR_NO_DEVICE, ERR_FILTERED = -1, -2, -3, -4, -5, -6
 EPI_STORE, EPI_F32, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3
+MASK_BLOCK, MASK_ALLOW = 0, 1
 
 
 class LlamaLayerWeights(C.Structure):
@@ -117,6 +118,13 @@ SIGNATURES = {
     "atspeed_session_drain": (C.c_int, [_P, C.POINTER(SessionDone), _I, C.POINTER(_I)]),
     "atspeed_session_get_counters": (C.c_int, [_P, C.POINTER(SessionCounters)]),
     "atspeed_session_destroy": (None, [_P]),
+    "atspeed_node_masks_create": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, C.POINTER(_P)]),
+    "atspeed_node_masks_destroy": (None, [_P]),
+    "atspeed_node_masks_read": (C.c_int, [_P, _I, _P, _I]),
+    "atspeed_decoder_set_node_mask": (C.c_int, [_P, _P, _I]),
+    "atspeed_session_submit_masked": (C.c_int, [_P, _P, _I, _I, _U32, _P, _P, C.POINTER(GenStats), _P, _I, C.POINTER(C.c_int64)]),
+    "atspeed_beam_expand_prune_masked": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "atspeed_warp_cutoffs_masked": (C.c_int, [_P, _I, _P, _I, _P, _P, _F, _I, _F, _I, _P, _P, _I, _P]),
     "atspeed_target_generate": (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, C.POINTER(GenStats), _P]),
     "atspeed_target_generate_batch": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "atspeed_assemble_sequences": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),

@@ -34,6 +34,11 @@ mode and warpers), `_setup` (prompts on the device, compiled constraints, the sh
 `_batch_call` (buffers, argument marshalling and the library call: the one-user entry points keep their by-value launches, the batch ones
 take one pointer array entry per user).  `_DeviceFSM` and `_Decoder` cache device objects per constraint and per (model pair, lane) and
 hold what they were built from weakly; the objects themselves are owned by `_lib.Handle`.
+
+Item filters (`exclude_items=` / `allow_items=`, include/atspeed_hip.h "item filters"): per user a list of token sequences -- what a beam
+generates after the prompt, e.g. an item's code tokens -- that the user must not be recommended, or the only ones it may be.  They become
+per-user node bitsets over the shared automaton (`_item_filters`, built on the device), so filtered users keep their place in lock-step
+batches and sessions; draft and target see the same bits, so BSSD under a filter is plain beam search under that filter.
 """
 from __future__ import annotations
 
@@ -47,7 +52,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .generation_trie import ConstraintFSM, free_constraint
+from .generation_trie import ConstraintFSM, SuffixTrieConstraint, WholeSentenceTrieConstraint, free_constraint
 from .model import HipLlama
 
 
@@ -268,13 +273,17 @@ def _set_decoders(decs, mode, num_beams: int, seeds, trace=None) -> None:
             d.trace_on = bool(trace)
 
 
-def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allowed_tokens_fn, mode, who: str, trace=None) -> SimpleNamespace:
+def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allowed_tokens_fn, mode, who: str, trace=None,
+           filters=None, first_user: int = 0) -> SimpleNamespace:
     """The device path's call setup, for one user or a lock-step batch: prompts on the device, each user's compiled constraint (the mask
     functions look at the prompt -- position of "Response:", data.py:97-102 -- with one D2H copy per call, where the reference does one per beam
     per step, generation_trie.py:94, data.py:98), the ONE automaton they share (they may differ in their start node only), one decoder per
-    user (lane), set to the call's sampling mode (user u draws from stream seed + u) and, for BSSD (`trace` not None), its decision trace."""
-    lib = _lib.load()
+    user (lane), set to the call's sampling mode (user u draws from stream seed + u) and, for BSSD (`trace` not None), its decision trace.
+    `filters` (`_filter_specs`): the users' item filters are built and set on their decoders; the caller clears them (`_clear_filters`)
+    when its library call has returned."""
     dev = target.device
+    if filters is not None:
+        _check_filter_constraint(prefix_allowed_tokens_fn, who)
     prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
     fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
     for f in fsms[1:]:
@@ -283,7 +292,100 @@ def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allo
     dfsm = _DeviceFSM.get(fsms[0], target.dims.vocab_size)
     decs = [_Decoder.get(target, draft, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
     _set_decoders(decs, mode, target.generation_config.num_beams, [mode[2] + u for u in range(len(decs))], trace)
-    return SimpleNamespace(dev=dev, prompts=prompts, fsms=fsms, dfsm=dfsm, decs=decs)
+    owners = []
+    if filters is not None:
+        owners, per_user = _item_filters(dfsm, [f.start for f in fsms], filters, dev, who, first_user)
+        _set_filters(decs, per_user)
+    return SimpleNamespace(dev=dev, prompts=prompts, fsms=fsms, dfsm=dfsm, decs=decs, filter_owners=owners)
+
+
+# ---------------------------------------------------------------- item filters
+def _filter_specs(n: int, exclude_items, allow_items, per_user: bool, who: str):
+    """One entry per user: None (unfiltered) or (mode, [token sequence, ...]).  The one-user calls take the list itself, the batch calls one
+    list (or None) per user; a user has an exclude list or an allow list, never both."""
+    if exclude_items is None and allow_items is None:
+        return None
+    if not per_user:
+        if exclude_items is not None and allow_items is not None:
+            raise ValueError(f"{who}: exclude_items and allow_items are mutually exclusive")
+        exclude_items, allow_items = [exclude_items], [allow_items]
+    specs = []
+    for name, lists in (("exclude_items", exclude_items), ("allow_items", allow_items)):
+        if lists is not None and len(lists) != n:
+            raise ValueError(f"{who}: {name} needs one list (or None) per user: {len(lists)} for {n} users")
+    for u in range(n):
+        ex = exclude_items[u] if exclude_items is not None else None
+        al = allow_items[u] if allow_items is not None else None
+        if ex is not None and al is not None:
+            raise ValueError(f"{who}: exclude_items and allow_items are mutually exclusive (user {u} has both)")
+        if ex is None and al is None:
+            specs.append(None)
+        else:
+            mode, seqs = (_lib.MASK_BLOCK, ex) if ex is not None else (_lib.MASK_ALLOW, al)
+            specs.append((mode, [[int(t) for t in q] for q in seqs]))
+    return specs if any(sp is not None for sp in specs) else None
+
+
+def _check_filter_constraint(prefix_allowed_tokens_fn, who: str) -> None:
+    """A filter's sequences are walked as items through the automaton: that needs a strict item trie (a tree below the start node)."""
+    fn = prefix_allowed_tokens_fn
+    if not isinstance(fn, (SuffixTrieConstraint, WholeSentenceTrieConstraint)) or fn.trie._chained():
+        raise ValueError(f"{who}: exclude_items / allow_items need a SuffixTrieConstraint or an unchained WholeSentenceTrieConstraint "
+                         f"(the nodes of {type(fn).__name__ if fn is not None else 'a mask-free search'}"
+                         f"{' with a chained trie' if hasattr(fn, 'trie') else ''} are not items)")
+
+
+def _refuse_host_filters(specs, who: str) -> None:
+    if specs is not None:
+        raise NotImplementedError(f"{who}: exclude_items / allow_items run on the device path only (a mask that can compile() itself, no "
+                                  "extra logits_processor); on the host path put the filter into the mask callable")
+
+
+def _item_filters(dfsm: _DeviceFSM, starts, specs, dev, who: str, first_user: int = 0):
+    """The node bitsets of a call's filtered users -> (owners, per user None or (masks pointer, index)).  The users of one mode are built by
+    ONE create call (a call whose users are all excluded-from or all allowed-to makes exactly one); `owners` keeps the library objects
+    alive.  A user whose filter leaves it nothing raises ValueError before anything is launched."""
+    lib = _lib.load()
+    owners, per_user = [], [None] * len(specs)
+    for mode in (_lib.MASK_BLOCK, _lib.MASK_ALLOW):
+        users = [u for u, sp in enumerate(specs) if sp is not None and sp[0] == mode]
+        if not users:
+            continue
+        toks, seq_off, user_off = [], [0], [0]
+        for u in users:
+            for q in specs[u][1]:
+                toks += q
+                seq_off.append(len(toks))
+            user_off.append(len(seq_off) - 1)
+        a_tok = np.asarray(toks if toks else [0], np.int32)
+        a_soff, a_uoff = np.asarray(seq_off, np.int32), np.asarray(user_off, np.int32)
+        a_start = np.asarray([starts[u] for u in users], np.int32)
+        unknown, status = np.zeros(len(users), np.int32), np.zeros(len(users), np.int32)
+        with torch.cuda.device(dev):
+            owner = _lib.Handle.create("atspeed_node_masks_destroy", lib.atspeed_node_masks_create, dfsm.handle, len(users), a_start.ctypes.data,
+                                       a_tok.ctypes.data, a_soff.ctypes.data, a_uoff.ctypes.data, mode, unknown.ctypes.data,
+                                       status.ctypes.data, _lib.stream_ptr(dev))
+        owners.append(owner)
+        for i, u in enumerate(users):
+            if status[i] != 0:
+                what = ("exclude_items blocks every item the constraint allows" if mode == _lib.MASK_BLOCK
+                        else f"allow_items holds no sequence the constraint knows ({int(unknown[i])} unknown)")
+                raise ValueError(f"{who}: user {first_user + u}: {what}: the constraint is unsatisfiable")
+            per_user[u] = (owner.ptr, i)
+    return owners, per_user
+
+
+def _set_filters(decs, per_user) -> None:
+    lib = _lib.load()
+    for d, pu in zip(decs, per_user):
+        _lib.check(lib.atspeed_decoder_set_node_mask(d.handle, pu[0] if pu else None, pu[1] if pu else 0))
+
+
+def _clear_filters(decs) -> None:
+    """A cached decoder must not keep a call's filter: a later unfiltered call on it is unfiltered (and the masks die with the call)."""
+    lib = _lib.load()
+    for d in decs:
+        lib.atspeed_decoder_set_node_mask(d.handle, None, 0)
 
 
 def _host_call(host_fn, models, inputs: Dict, args, logits_processor, prefix_allowed_tokens_fn, mode) -> Dict:
@@ -310,8 +412,12 @@ def _one_user_call(entry, c: SimpleNamespace, k: int, max_new_tokens: int, *midd
         toks = torch.empty(k, max_new_tokens, dtype=torch.int32, device=dev)
         scores = torch.empty(k, dtype=torch.float32, device=dev)
         stats = _lib.GenStats()
-        _lib.check(entry(c.decs[0].handle, ids32.data_ptr(), int(prompt.numel()), c.dfsm.handle, c.fsms[0].start, *middle,
-                         toks.data_ptr(), scores.data_ptr(), C.byref(stats), _lib.stream_ptr(dev)))
+        try:
+            _lib.check(entry(c.decs[0].handle, ids32.data_ptr(), int(prompt.numel()), c.dfsm.handle, c.fsms[0].start, *middle,
+                             toks.data_ptr(), scores.data_ptr(), C.byref(stats), _lib.stream_ptr(dev)))
+        finally:
+            if c.filter_owners:
+                _clear_filters(c.decs)
     seq = torch.cat((prompt.to(torch.int64)[None, :].repeat(k, 1), toks.to(torch.int64)), dim=1)
     return {"beam_sequence": seq, "beam_scores": scores}, stats
 
@@ -356,13 +462,22 @@ def _batch_call(entry, c: SimpleNamespace, k: int, max_new_tokens: int, *middle)
     with torch.cuda.device(c.dev):
         ids32, toks, scores, keep = _batch_buffers(c.prompts, k, max_new_tokens, c.dev)
         stats = (_lib.GenStats * n)()
-        _lib.check(entry(ptrs(*[d.handle for d in c.decs]), n, ptrs(*[t.data_ptr() for t in ids32]),
-                         ints(*[int(p.numel()) for p in c.prompts]), c.dfsm.handle, ints(*[f.start for f in c.fsms]), *middle,
-                         ptrs(*[t.data_ptr() for t in toks]), ptrs(*[t.data_ptr() for t in scores]), stats, _lib.stream_ptr(c.dev)))
+        try:
+            _lib.check(entry(ptrs(*[d.handle for d in c.decs]), n, ptrs(*[t.data_ptr() for t in ids32]),
+                             ints(*[int(p.numel()) for p in c.prompts]), c.dfsm.handle, ints(*[f.start for f in c.fsms]), *middle,
+                             ptrs(*[t.data_ptr() for t in toks]), ptrs(*[t.data_ptr() for t in scores]), stats, _lib.stream_ptr(c.dev)))
+        finally:
+            if c.filter_owners:
+                _clear_filters(c.decs)
     return (keep, toks, scores, k), stats
 
 
 MAX_USERS_PER_CALL = 256
+
+
+def _chunk_of(lists, i: int, n: int):
+    """users [i, i + n) of a per-user argument that may be None"""
+    return None if lists is None else lists[i:i + n]
 
 
 def _chunked(call, inputs_list, mode):
@@ -370,7 +485,7 @@ def _chunked(call, inputs_list, mode):
     of the list still drawing from stream seed + u."""
     outs = []
     for i in range(0, len(inputs_list), MAX_USERS_PER_CALL):
-        outs += call(inputs_list[i:i + MAX_USERS_PER_CALL], (mode[2] + i) if mode[0] else None)
+        outs += call(inputs_list[i:i + MAX_USERS_PER_CALL], (mode[2] + i) if mode[0] else None, i)
     return outs
 
 
@@ -398,15 +513,18 @@ def _bssd_stats(st, k: int) -> Dict:
 @Timer()
 @torch.no_grad()
 def BSSD(target_model, draft_model, inputs: Dict, gamma: int, max_new_tokens: int,
-         logits_processor=None, prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False) -> Dict:
+         logits_processor=None, prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False,
+         exclude_items=None, allow_items=None) -> Dict:
     mode = _mode(seed, target_model, draft_model)
+    filters = _filter_specs(1, exclude_items, allow_items, False, "BSSD")
     if _host_path(logits_processor, prefix_allowed_tokens_fn):
+        _refuse_host_filters(filters, "BSSD")
         from .hostmask import bssd_host_mask
         return _host_call(bssd_host_mask, (target_model, draft_model), inputs, (int(gamma), int(max_new_tokens)), logits_processor,
                           prefix_allowed_tokens_fn, mode)
     k = int(target_model.generation_config.num_beams)                 # beamSD.py:482
     dk = int(draft_model.generation_config.num_beams)                 # beamSD.py:483
-    c = _setup(target_model, draft_model, [inputs], prefix_allowed_tokens_fn, mode, "BSSD", trace_decisions)
+    c = _setup(target_model, draft_model, [inputs], prefix_allowed_tokens_fn, mode, "BSSD", trace_decisions, filters)
     out, stats = _one_user_call(_lib.load().atspeed_bssd_generate, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     out.update(_bssd_stats(stats, k))
     return out
@@ -469,7 +587,9 @@ class BSSDSession:
                                              (C.c_void_p * self.n_lanes)(*[d.handle for d in self._decs]), self.n_lanes, self._dfsm.handle,
                                              self.gamma, self.max_new_tokens, self.k, self.dk, self.max_prompt, _lib.stream_ptr(self.dev))
 
-    def _submit(self, prompt: torch.Tensor, fsm: ConstraintFSM, ids32: torch.Tensor, toks: torch.Tensor, scores: torch.Tensor, seed=None) -> int:
+    def _submit(self, prompt: torch.Tensor, fsm: ConstraintFSM, ids32: torch.Tensor, toks: torch.Tensor, scores: torch.Tensor, seed=None,
+                mask=None, mask_owners=()) -> int:
+        """`mask`: None or (masks pointer, user index) of the user's item filter; `mask_owners` stay alive until its ticket has come back"""
         if self._closed:
             raise RuntimeError("BSSDSession is closed")
         if self._fsm0 is None:
@@ -478,25 +598,39 @@ class BSSDSession:
             raise ValueError("BSSDSession needs one shared constraint automaton (only the start node may differ per user)")
         if seed is None:
             seed = self.mode[2] + self._submitted
-        user = SimpleNamespace(prompt=prompt, ids32=ids32, toks=toks, scores=scores, stats=_lib.GenStats(), t0=time.time())
+        user = SimpleNamespace(prompt=prompt, ids32=ids32, toks=toks, scores=scores, stats=_lib.GenStats(), t0=time.time(), mask_owners=mask_owners)
         ticket = C.c_int64(0)
         # host only: the library queues the user and launches nothing, so no device guard (one per user would be the call's largest cost)
-        _lib.check(_lib.load().atspeed_session_submit(self._owner.ptr, ids32.data_ptr(), int(prompt.numel()), fsm.start, int(seed) & 0xFFFFFFFF,
-                                                      toks.data_ptr(), scores.data_ptr(), C.byref(user.stats), C.byref(ticket)))
+        _lib.check(_lib.load().atspeed_session_submit_masked(self._owner.ptr, ids32.data_ptr(), int(prompt.numel()), fsm.start, int(seed) & 0xFFFFFFFF,
+                                                             toks.data_ptr(), scores.data_ptr(), C.byref(user.stats),
+                                                             mask[0] if mask else None, mask[1] if mask else 0, C.byref(ticket)))
         self._submitted += 1
         self._users[ticket.value] = user
         return ticket.value
 
     @torch.no_grad()
-    def submit(self, inputs: Dict, seed=None) -> int:
-        """Queue one user; nothing is launched.  Returns its ticket."""
+    def submit(self, inputs: Dict, seed=None, exclude_items=None, allow_items=None) -> int:
+        """Queue one user; no forward is launched.  Returns its ticket.  `exclude_items` / `allow_items`: the user's item filter (a list of
+        token sequences; its node bitset is built here and follows the user to whichever lane it lands on)."""
+        filters = _filter_specs(1, exclude_items, allow_items, False, "BSSDSession.submit")
         prompt = _prompt_row(inputs).to(self.dev)
         fsm = _compile_constraint(self.fn, prompt.tolist())
         with torch.cuda.device(self.dev):
             ids32 = prompt.to(torch.int32).contiguous()
             toks = torch.empty(self.k, self.max_new_tokens, dtype=torch.int32, device=self.dev)
             scores = torch.empty(self.k, dtype=torch.float32, device=self.dev)
-        return self._submit(prompt, fsm, ids32, toks, scores, seed)
+        mask, owners = None, ()
+        if filters is not None:
+            _check_filter_constraint(self.fn, "BSSDSession.submit")
+            if self._closed:
+                raise RuntimeError("BSSDSession is closed")
+            if self._fsm0 is None:
+                self._create(fsm)
+            elif fsm.row_ptr is not self._fsm0.row_ptr:
+                raise ValueError("BSSDSession needs one shared constraint automaton (only the start node may differ per user)")
+            owners, per_user = _item_filters(self._dfsm, [fsm.start], filters, self.dev, "BSSDSession.submit", self._submitted)
+            mask = per_user[0]
+        return self._submit(prompt, fsm, ids32, toks, scores, seed, mask, tuple(owners))
 
     def _finished(self, buf, n: int, assemble: bool):
         out, now = [], time.time()
@@ -556,7 +690,7 @@ class BSSDSession:
         return False
 
 
-def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes: int):
+def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes: int, filters=None):
     """`BSSD_batch(..., lanes=N)`: the whole list through one session of N lanes, results in list order.  The prompts, token blocks and
     scores are the batch call's buffers (one allocation each) and the result tensors come from its one assemble launch."""
     if not inputs_list:
@@ -571,8 +705,14 @@ def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tok
         k = ses.k
         with torch.cuda.device(dev):
             ids32, toks, scores, keep = _batch_buffers(prompts, k, int(max_new_tokens), dev)
-        tickets = [ses._submit(p, f, i32, toks[u], scores[u]) for u, (p, f, i32) in enumerate(zip(prompts, fsms, ids32))]
+        per_user, owners = [None] * len(prompts), []
+        if filters is not None:            # the whole list's bitsets up front; they outlive the drain
+            _check_filter_constraint(prefix_allowed_tokens_fn, "BSSD_batch")
+            ses._create(fsms[0])
+            owners, per_user = _item_filters(ses._dfsm, [f.start for f in fsms], filters, dev, "BSSD_batch")
+        tickets = [ses._submit(p, f, i32, toks[u], scores[u], mask=per_user[u]) for u, (p, f, i32) in enumerate(zip(prompts, fsms, ids32))]
         done = dict(ses.drain(_assemble=False))
+        del owners
         wall = time.time() - t0
         outs = _batch_results(keep, toks, scores, k)
         for out, t in zip(outs, tickets):
@@ -584,7 +724,8 @@ def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tok
 
 @torch.no_grad()
 def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_tokens: int,
-               prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False, lanes: Optional[int] = None):
+               prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False, lanes: Optional[int] = None,
+               exclude_items=None, allow_items=None, _first_user: int = 0):
     """BSSD for several independent users at once (one result dict per user, same keys as BSSD).
 
     The reference decodes users strictly one after another (inference.py:162-176).  Here the users advance in
@@ -597,19 +738,24 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
     as soon as one of the first N finishes, not when all of them have.  Same results and keys (plus the session's `lane`, `rounds_in_lane`,
     `rounds_queued`; the first result also carries `session_counters`), user u still draws from stream seed + u.  One difference: a session
     refuses a prompt at submit when its rounds COULD run out of KV slots (prompt length + (max_new_tokens - 1) x draft beams > max_slots,
-    AtSpeedError ERR_CAPACITY, nothing decoded), where the lock-step path only fails if that user's acceptance really takes it there."""
+    AtSpeedError ERR_CAPACITY, nothing decoded), where the lock-step path only fails if that user's acceptance really takes it there.
+
+    `exclude_items` / `allow_items`: one list of token sequences (or None = unfiltered) per user, on either path; a user has one or the other."""
     if lanes is not None:
         if trace_decisions:
             raise ValueError("BSSD_batch(lanes=N) keeps no decision trace")
-        return _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes)
+        return _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes,
+                                 _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch"))
     mode = _mode(seed, target_model, draft_model)
     if len(inputs_list) > MAX_USERS_PER_CALL:
-        return _chunked(lambda chunk, s: BSSD_batch(target_model, draft_model, chunk, gamma, max_new_tokens, prefix_allowed_tokens_fn,
-                                                    seed=s, trace_decisions=trace_decisions), inputs_list, mode)
+        return _chunked(lambda chunk, s, i: BSSD_batch(target_model, draft_model, chunk, gamma, max_new_tokens, prefix_allowed_tokens_fn,
+                                                       seed=s, trace_decisions=trace_decisions, exclude_items=_chunk_of(exclude_items, i, len(chunk)),
+                                                       allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i), inputs_list, mode)
+    filters = _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch")
     k = int(target_model.generation_config.num_beams)
     dk = int(draft_model.generation_config.num_beams)
     t0 = time.time()
-    c = _setup(target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, mode, "BSSD_batch", trace_decisions)
+    c = _setup(target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, mode, "BSSD_batch", trace_decisions, filters, _first_user)
     raw, stats = _batch_call(_lib.load().atspeed_bssd_generate_batch, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     wall = time.time() - t0
     outs = _batch_results(*raw)
@@ -622,30 +768,37 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
 @Timer()
 @torch.no_grad()
 def target_generate(model, inputs: Dict, max_new_tokens: int, logits_processor=None,
-                    prefix_allowed_tokens_fn=None, seed=None) -> Dict:
+                    prefix_allowed_tokens_fn=None, seed=None, exclude_items=None, allow_items=None) -> Dict:
     mode = _mode(seed, model)
+    filters = _filter_specs(1, exclude_items, allow_items, False, "target_generate")
     if _host_path(logits_processor, prefix_allowed_tokens_fn):
+        _refuse_host_filters(filters, "target_generate")
         from .hostmask import target_generate_host_mask
         return _host_call(target_generate_host_mask, (model,), inputs, (int(max_new_tokens),), logits_processor, prefix_allowed_tokens_fn,
                           mode)
     k = int(model.generation_config.num_beams)                        # beamSD.py:553
-    c = _setup(model, None, [inputs], prefix_allowed_tokens_fn, mode, "target_generate")
+    c = _setup(model, None, [inputs], prefix_allowed_tokens_fn, mode, "target_generate", filters=filters)
     out, stats = _one_user_call(_lib.load().atspeed_target_generate, c, k, max_new_tokens, int(max_new_tokens), k)
     out.update({"n_valid": int(stats.n_valid), "device_time_cost": stats.total_ms * 1e-3})
     return out
 
 
-def target_generate_batch(model, inputs_list, max_new_tokens: int, prefix_allowed_tokens_fn=None, seed=None):
+def target_generate_batch(model, inputs_list, max_new_tokens: int, prefix_allowed_tokens_fn=None, seed=None, exclude_items=None,
+                          allow_items=None, _first_user: int = 0):
     """`target_generate` for several independent users in lock step (one result dict per user): position g of every
     user's constrained beam search is ONE forward.  This is the loop `code/generate_teacher_data.py:211-244` runs over
-    a whole training set with HF `generate`; token ids equal per-user `target_generate` calls."""
+    a whole training set with HF `generate`; token ids equal per-user `target_generate` calls.  `exclude_items` / `allow_items`: one list of
+    token sequences (or None = unfiltered) per user."""
     mode = _mode(seed, model)
     if len(inputs_list) > MAX_USERS_PER_CALL:
-        return _chunked(lambda chunk, s: target_generate_batch(model, chunk, max_new_tokens, prefix_allowed_tokens_fn, seed=s),
+        return _chunked(lambda chunk, s, i: target_generate_batch(model, chunk, max_new_tokens, prefix_allowed_tokens_fn, seed=s,
+                                                                  exclude_items=_chunk_of(exclude_items, i, len(chunk)),
+                                                                  allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i),
                         inputs_list, mode)
+    filters = _filter_specs(len(inputs_list), exclude_items, allow_items, True, "target_generate_batch")
     k = int(model.generation_config.num_beams)
     t0 = time.time()
-    c = _setup(model, None, inputs_list, prefix_allowed_tokens_fn, mode, "target_generate_batch")
+    c = _setup(model, None, inputs_list, prefix_allowed_tokens_fn, mode, "target_generate_batch", filters=filters, first_user=_first_user)
     raw, stats = _batch_call(_lib.load().atspeed_target_generate_batch, c, k, max_new_tokens, int(max_new_tokens), k)
     wall = time.time() - t0
     outs = _batch_results(*raw)

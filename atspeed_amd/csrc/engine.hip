@@ -1000,6 +1000,10 @@ struct atspeed_decoder {
   int top_k = 0; float top_p = 1.f; int min_keep = 1;
   float* cutoff = nullptr;      // [MAXB + ATSPEED_MAX_GAMMA * MAXB] (allocated on first use)
   bool warps() const { return sample && (top_k > 0 || top_p < 1.f); }
+  // item filter (atspeed_decoder_set_node_mask; a session puts its user's there): none by default
+  const atspeed_node_masks* masks = nullptr; int mask_user = 0;
+  // the automaton as this user's kernels take it by value: the shared arrays and the user's own blocked-node bits
+  FsmDev fsm_dev(const atspeed_fsm* fsm) const { FsmDev f = fsm->dev; f.blocked = ats_mask_bits(masks, mask_user); return f; }
   struct Run {
     const atspeed_fsm* fsm; int gamma, max_new, k, dk;
     int32_t* out_tokens; float* out_scores; atspeed_gen_stats* stats_out;
@@ -1103,6 +1107,13 @@ extern "C" int atspeed_decoder_set_warpers(atspeed_decoder* d, int32_t top_k, fl
   return ATSPEED_OK;
 }
 
+extern "C" int atspeed_decoder_set_node_mask(atspeed_decoder* d, const atspeed_node_masks* masks, int32_t user) {
+  ATS_REQUIRE(d, ATSPEED_ERR_INVALID, "set_node_mask: null decoder");
+  ATS_REQUIRE(!masks || (user >= 0 && user < masks->n_users), ATSPEED_ERR_INVALID, "set_node_mask: user %d out of [0, %d)", user, masks ? masks->n_users : 0);
+  d->masks = masks; d->mask_user = masks ? user : 0;
+  return ATSPEED_OK;
+}
+
 extern "C" int atspeed_decoder_set_trace(atspeed_decoder* d, int32_t level) {
   ATS_REQUIRE(d && (level == 0 || level == 1), ATSPEED_ERR_INVALID, "set_trace: level must be 0 or 1");
   if (level == 1 && !d->dump_host) ATS_HIP(hipHostMalloc((void**)&d->dump_host, d->beam_area_bytes));
@@ -1150,6 +1161,7 @@ static int check_common(atspeed_decoder* d, const int32_t* prompt, int P, const 
               fsm->dev.vocab, d->target->cfg.vocab_size);
   ATS_REQUIRE(start_node >= 0 && start_node < std::max(fsm->dev.n_nodes, 1), ATSPEED_ERR_INVALID, "generate: start node out of range");
   ATS_REQUIRE(!(d->sample && fsm->dev.n_nodes == 0), ATSPEED_ERR_INVALID, "generate: sampling needs a constraint automaton (mask-free search is greedy only)");
+  ATS_REQUIRE(!d->masks || d->masks->fsm == fsm, ATSPEED_ERR_INVALID, "generate: the decoder's item filter was built on another automaton");
   return ATSPEED_OK;
 }
 
@@ -1251,7 +1263,7 @@ static BeamStepArgs beam_step_args(const atspeed_decoder* d, const atspeed_llama
   BeamStepArgs a{};
   a.src = src; a.n_src = sg.n_logit; a.gen_len = gen_len; a.dst = dst; a.k = k;
   a.logits = rv.logits; a.ld = m->logits_ld; a.lse = rv.lse; a.row_cand = rv.row_cand; a.n_row_cand = k;
-  a.fsm = fsm->dev; a.filter_ids = fsm->dev.n_nodes == 0 ? 0 : 1;
+  a.fsm = d->fsm_dev(fsm); a.filter_ids = fsm->dev.n_nodes == 0 ? 0 : 1;
   a.mail = d->mail_dev; a.vis_words = d->W;
   if (d->sample) { a.sample = 1; a.temperature = d->temperature; }
   if (d->warps()) a.cutoff = d->cutoff;
@@ -1439,7 +1451,7 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
       va.blk[0] = d->round_beams[r.cur];
       for (int i = 1; i <= r.dl; ++i) va.blk[i] = d->blk[i];
       va.nb = r.nb; va.dl = r.dl; va.k = r.k; va.dk = r.dk; va.gen_len0 = r.gen;
-      va.logits = rv.logits; va.ld = T->logits_ld; va.lse = rv.lse; va.fsm = r.fsm->dev;
+      va.logits = rv.logits; va.ld = T->logits_ld; va.lse = rv.lse; va.fsm = d->fsm_dev(r.fsm);
       va.row_cand = rv.row_cand; va.n_row_cand = r.k;
       va.cur = d->tin[r.cur]; va.n0 = r.n0; va.next = d->tin[r.cur ^ 1]; va.dnext = d->dround; va.vis_words = W;
       va.res = d->round_beams[r.cur ^ 1]; va.mail = d->mail_dev;
@@ -1607,6 +1619,7 @@ namespace {
 struct SessionJob {          // a submitted user, as it waits in the queue and then sits in its lane
   const int32_t* prompt = nullptr; int P = 0, start_node = 0; uint32_t seed = 0;
   int32_t* out_tokens = nullptr; float* out_scores = nullptr; atspeed_gen_stats* stats = nullptr;
+  const atspeed_node_masks* masks = nullptr; int mask_user = 0;     // the user's item filter (atspeed_session_submit_masked)
 };
 }  // namespace
 struct atspeed_session {
@@ -1677,17 +1690,25 @@ extern "C" int atspeed_session_create(atspeed_decoder* const* lanes, int32_t n_l
 
 extern "C" void atspeed_session_destroy(atspeed_session* s) { delete s; }
 
-extern "C" int atspeed_session_submit(atspeed_session* s, const int32_t* prompt, int32_t P, int32_t start_node, uint32_t seed,
-                                      int32_t* out_tokens, float* out_scores, atspeed_gen_stats* stats, int64_t* ticket_out) {
+extern "C" int atspeed_session_submit_masked(atspeed_session* s, const int32_t* prompt, int32_t P, int32_t start_node, uint32_t seed,
+                                             int32_t* out_tokens, float* out_scores, atspeed_gen_stats* stats, const atspeed_node_masks* masks,
+                                             int32_t user, int64_t* ticket_out) {
   ATS_REQUIRE(s && ticket_out, ATSPEED_ERR_INVALID, "session_submit: null argument");
+  ATS_REQUIRE(!masks || masks->fsm == s->fsm, ATSPEED_ERR_INVALID, "session_submit: the item filter was built on another automaton");
+  ATS_REQUIRE(!masks || (user >= 0 && user < masks->n_users), ATSPEED_ERR_INVALID, "session_submit: filter user %d out of [0, %d)", user, masks ? masks->n_users : 0);
   ATS_TRY(check_common(s->lanes[0], prompt, P, s->fsm, start_node, s->max_new, s->k, out_tokens, out_scores));
   ATS_REQUIRE(P <= s->max_prompt, ATSPEED_ERR_CAPACITY, "session_submit: prompt length %d exceeds the session's max_prompt %d", P, s->max_prompt);
   // a user's rounds need up to P + (max_new - 1) * dk KV slots (every draft block of the call kept): refused here, where it costs nobody else
   // a round, rather than inside one
   const int slots = P + (s->max_new - 1) * s->dk, max_slots = s->lanes[0]->target->cfg.max_slots;
   ATS_REQUIRE(slots <= max_slots, ATSPEED_ERR_CAPACITY, "session_submit: prompt of %d tokens can need %d KV slots (%d available)", P, slots, max_slots);
-  *ticket_out = s->q.submit(SessionJob{prompt, P, start_node, seed, out_tokens, out_scores, stats});
+  *ticket_out = s->q.submit(SessionJob{prompt, P, start_node, seed, out_tokens, out_scores, stats, masks, masks ? user : 0});
   return ATSPEED_OK;
+}
+
+extern "C" int atspeed_session_submit(atspeed_session* s, const int32_t* prompt, int32_t P, int32_t start_node, uint32_t seed,
+                                      int32_t* out_tokens, float* out_scores, atspeed_gen_stats* stats, int64_t* ticket_out) {
+  return atspeed_session_submit_masked(s, prompt, P, start_node, seed, out_tokens, out_scores, stats, nullptr, 0, ticket_out);
 }
 
 // admission, one round over the occupied lanes, retirement
@@ -1699,6 +1720,7 @@ static int session_round(atspeed_session* s) {
   ATS_TRY(s->q.admit([&](int lane, int64_t, SessionJob& j) {
     atspeed_decoder* d = s->lanes[lane];
     d->seed = j.seed;                                   // draws follow the user, not the lane
+    d->masks = j.masks; d->mask_user = j.mask_user;     // and so does its item filter: on at admission, off at retirement
     ATS_TRY(bssd_begin(d, j.prompt, j.P, s->fsm, j.start_node, s->gamma, s->max_new, s->k, s->dk, j.out_tokens, j.out_scores, j.stats, s->st, false));
     fresh.push_back(d); prompts.push_back(j.prompt); lens.push_back(j.P); starts.push_back(j.start_node);
     return (int)ATSPEED_OK;
@@ -1712,7 +1734,8 @@ static int session_round(atspeed_session* s) {
   RoundCtl ctl{false, true};
   ATS_TRY(bssd_round(decs.data(), (int)decs.size(), s->st, g_ev, ctl));
   s->target_forwards += ctl.target_forwards; s->draft_forwards += ctl.draft_forwards;
-  for (size_t i = 0; i < decs.size(); ++i) if (decs[i]->run.done) s->q.retire(lane_of[i], decs[i]->run.s.status);
+  for (size_t i = 0; i < decs.size(); ++i)
+    if (decs[i]->run.done) { decs[i]->masks = nullptr; decs[i]->mask_user = 0; s->q.retire(lane_of[i], decs[i]->run.s.status); }
   return ATSPEED_OK;
 }
 
@@ -1731,6 +1754,7 @@ static int session_round_guarded(atspeed_session* s) {
         atspeed_decoder::Run& r = s->lanes[l]->run;
         r.done = true; r.s.status = rc; r.s.n_valid = 0;
         if (r.stats_out) *r.stats_out = r.s;
+        s->lanes[l]->masks = nullptr; s->lanes[l]->mask_user = 0;
         s->q.retire(l, rc);
       }
     g_last_error = why;

@@ -94,12 +94,35 @@ struct FsmDev {
   // one_step_beam_search's post-top-k id filter (beamSD.py:80-86 hard-codes `tok >= 32000 | tok == 2`): picks with a token below
   // filter_min that is not filter_eos are dropped; filter_min <= 0 keeps everything (atspeed_fsm_set_id_filter)
   int32_t filter_min, filter_eos;
+  // per-user item filter (atspeed_node_masks): bit n set = node n is blocked for this user, an edge into it is no candidate; NULL = no filter.
+  // Last member: the copies made by value for each user (BeamStepArgs / VerifyArgs / WarpCutArgs) carry it to every walk of the automaton
+  const uint32_t* blocked;
 };
 struct atspeed_fsm {
   FsmDev dev;
   int32_t *d_row_ptr, *d_tok, *d_nxt;
   unsigned char* d_tile_store;   // [ceil(vocab / 256)] device bytes: 1 = some edge token lies in columns [256 t, 256 t + 256) (the logit tiles a step can read)
 };
+
+// Per-user node bitsets of an item filter (include/atspeed_hip.h "item filters"), built on the device by ats_node_masks_build.  One device block:
+// the bitsets first, then what the builder reads and its scratch (sequences, walked paths, allow mode's K and E sets).
+struct atspeed_node_masks {
+  const atspeed_fsm* fsm;      // the automaton the node ids belong to
+  int n_users, words;          // words = ceil(n_nodes / 32) per user
+  uint32_t* bits;              // [n_users][words], device
+  void* block;                 // the allocation
+};
+struct NodeMaskBuild {
+  FsmDev fsm;
+  const int32_t* start;  const int32_t* seq_tok;  const int32_t* seq_off;  const int32_t* user_off;   // device copies of create's host arrays
+  int32_t* path;               // [sequences][ATSPEED_MAX_NEW_TOKENS + 1] nodes a sequence walks through, the start node first
+  int32_t* len;                // [sequences] tokens of a known sequence, -1 = unknown
+  uint32_t* bits;  uint32_t* kept;  uint32_t* ends;     // [n_users][words]: the result; allow mode's K and E
+  int32_t* unknown;  int32_t* status;                    // [n_users]
+  int words, mode;
+};
+int ats_node_masks_build(const NodeMaskBuild& b, int n_users, hipStream_t st);
+inline const uint32_t* ats_mask_bits(const atspeed_node_masks* m, int user) { return m ? m->bits + (size_t)user * m->words : nullptr; }
 
 struct TokBuf {       // inputs of a forward: one row per token
   int32_t* ids;

@@ -8,6 +8,7 @@
 // (torch.topk leaves it unspecified).  Key 0 = no candidate.
 #include "internal.h"
 #include <cstdlib>
+#include <memory>
 
 namespace {
 
@@ -169,6 +170,9 @@ __device__ __forceinline__ int find_edge(const FsmDev& f, int node, int tok) {
   return -1;
 }
 
+// item filter: is `node` blocked for the user this automaton copy belongs to?  Callers test f.blocked first (uniform: NULL = no filter)
+__device__ __forceinline__ bool node_blocked(const uint32_t* __restrict__ blocked, int node) { return (blocked[node >> 5] >> (node & 31)) & 1u; }
+
 struct ExpandShared {
   TopkShared topk;
   int off[MAXB + 1];
@@ -225,7 +229,9 @@ __device__ void expand_and_select(ExpandShared& sh, int n_rows, const float* __r
       int lo = 0, hi = n_rows;                        // last r with off[r] <= c
       while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (sh.off[mid] <= c) lo = mid; else hi = mid; }
       int r = lo;
-      int tok = free_mode ? row_cand[(size_t)sh.lrow[r] * MAXB + (c - sh.off[r])] : fsm.tok[sh.rp[r] + (c - sh.off[r])];
+      const int e = sh.rp[r] + (c - sh.off[r]);
+      int tok = free_mode ? row_cand[(size_t)sh.lrow[r] * MAXB + (c - sh.off[r])] : fsm.tok[e];
+      if (fsm.blocked && node_blocked(fsm.blocked, fsm.nxt[e])) tok = -1;       // item filter: an edge into a blocked node is no candidate
       if (tok >= 0) {
         float sc = (logits[(size_t)sh.lrow[r] * ld + tok] - sh.lse[r]) + sh.bscore[r];
         // -0.0 reaches here only as (-0.0 - +0.0) + -0.0 (x - y of unequal values is never zero and x - x is +0.0), e.g. a processor-rewritten
@@ -329,9 +335,11 @@ __device__ void expand_candidates(ExpandShared& sh, int n_rows, const float* __r
       int lo = 0, hi = n_rows;
       while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (sh.off[mid] <= c) lo = mid; else hi = mid; }
       int r = lo;
-      int tok = fsm.tok[sh.rp[r] + (c - sh.off[r])];
+      const int e = sh.rp[r] + (c - sh.off[r]);
+      int tok = fsm.tok[e];
       const float s = (logits[(size_t)sh.lrow[r] * ld + tok] - sh.lse[r]) / temperature;
       cr.sc[i] = s < sh.cut[r] ? -INFINITY : s + sh.bscore[r];         // below the row's cutoff: absent
+      if (fsm.blocked && node_blocked(fsm.blocked, fsm.nxt[e])) cr.sc[i] = -INFINITY;       // item filter: absent in the same way
       cr.flat[i] = sh.brow[r] * fsm.vocab + tok;
     }
   }
@@ -408,6 +416,7 @@ __device__ Pick pick_of_flat(int flat, const FsmDev& fsm, const ExpandShared& sh
   int e = find_edge(fsm, sh.node[r], p.tok);
   p.node = e >= 0 ? fsm.nxt[e] : 0;
   if (e < 0 || s < sh.cut[r]) p.score = -INFINITY;
+  if (fsm.blocked && e >= 0 && node_blocked(fsm.blocked, p.node)) p.score = -INFINITY;      // item filter
   return p;
 }
 
@@ -464,7 +473,9 @@ struct WarpShared {
 };
 struct WarpRow {
   const float* logits; const int32_t* tok; int deg; float lse, temperature;
+  const int32_t* nxt; const uint32_t* blocked;                    // item filter (NULL = none): child j leads to node nxt[j]
   __device__ __forceinline__ uint32_t key(int j) const {          // 0 = not a candidate
+    if (blocked && node_blocked(blocked, nxt[j])) return 0u;      // the cutoffs are taken over the unblocked children only
     const float s = (logits[tok[j]] - lse) / temperature;
     return s > -INFINITY ? ford_key(s) : 0u;         // a -0.0 (logit -0.0, lse +0.0) is tied with +0.0, as in expand_candidates' `s < cut`
   }
@@ -576,7 +587,8 @@ __device__ void row_warp_cutoff_body(const WarpCutArgs& a, int r) {
   while (sg < a.n_seg - 1 && r0 >= a.seg[sg].n) { r0 -= a.seg[sg].n; ++sg; }
   const int node = a.seg[sg].node ? a.seg[sg].node[r0] : 0;
   const int e0 = a.fsm.row_ptr[node];
-  const WarpRow row{a.logits + (size_t)r * a.ld, a.fsm.tok + e0, a.fsm.row_ptr[node + 1] - e0, a.lse[r], a.temperature};
+  const WarpRow row{a.logits + (size_t)r * a.ld, a.fsm.tok + e0, a.fsm.row_ptr[node + 1] - e0, a.lse[r], a.temperature,
+                    a.fsm.nxt + e0, a.fsm.blocked};
   const bool use_p = a.top_p < 1.f;
   const int kk = a.top_k > 0 ? max(a.top_k, a.min_keep) : 0;     // 0 = top-k off
   // finite entries and the largest key
@@ -1104,6 +1116,88 @@ __global__ void accept_kernel(const int32_t* __restrict__ tflat, const float* __
   }
 }
 
+// ---------------------------------------------------------------------------- item filters: per-user node bitsets
+// One workgroup per user (semantics: include/atspeed_hip.h "item filters").  Every pass strides over the user's sequences with uniform bounds
+// and ends at a workgroup barrier.  Bits are set with vector atomics and read back with device-scope atomic loads (a plain load could be
+// served from a line the vector cache fetched before another wave's atomic reached L2); an OR is idempotent and commutative, and every
+// pass reads only what earlier passes finished, so the result does not depend on the order in which threads run.
+constexpr int kMaskThreads = 256;
+__device__ __forceinline__ void mask_set(uint32_t* bits, int node) { atomicOr(bits + (node >> 5), 1u << (node & 31)); }
+__device__ __forceinline__ bool mask_get(const uint32_t* bits, int node) {
+  return (__hip_atomic_load(bits + (node >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (node & 31)) & 1u;
+}
+__global__ __launch_bounds__(kMaskThreads) void node_masks_kernel(NodeMaskBuild b) {
+  __shared__ int n_unknown, n_known;
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int s0 = b.user_off[u], s1 = b.user_off[u + 1], start = b.start[u];
+  uint32_t* bits = b.bits + (size_t)u * b.words;
+  uint32_t* kept = b.kept + (size_t)u * b.words;
+  uint32_t* ends = b.ends + (size_t)u * b.words;
+  const bool allow = b.mode == ATSPEED_MASK_ALLOW;
+  if (tid == 0) { n_unknown = 0; n_known = 0; }
+  __syncthreads();
+  // walk: path[s][0 .. len] of a known sequence; its end node goes into B (block) or E (allow), its path nodes into K (allow)
+  for (int s = s0 + tid; s < s1; s += kMaskThreads) {
+    const int t0 = b.seq_off[s], L = b.seq_off[s + 1] - t0;          // 1 .. LMAX (checked by the host)
+    int32_t* path = b.path + (size_t)s * (LMAX + 1);
+    int node = start, d = 0;
+    path[0] = node;
+    for (; d < L; ++d) {
+      const int e = find_edge(b.fsm, node, b.seq_tok[t0 + d]);
+      if (e < 0) break;
+      node = b.fsm.nxt[e];
+      path[d + 1] = node;
+    }
+    const bool known = d == L;
+    b.len[s] = known ? L : -1;
+    if (!known) { atomicAdd(&n_unknown, 1); continue; }
+    atomicAdd(&n_known, 1);
+    if (allow) {
+      for (int i = 0; i <= L; ++i) mask_set(kept, path[i]);
+      mask_set(ends, node);
+    } else {
+      mask_set(bits, node);
+    }
+  }
+  __threadfence();
+  __syncthreads();
+  if (allow) {
+    // a child of a path node that is no end node, and not itself on a path, is blocked
+    for (int s = s0 + tid; s < s1; s += kMaskThreads) {
+      const int L = b.len[s];
+      const int32_t* path = b.path + (size_t)s * (LMAX + 1);
+      for (int d = 0; d < L; ++d) {
+        const int node = path[d];
+        if (mask_get(ends, node)) continue;
+        for (int e = b.fsm.row_ptr[node]; e < b.fsm.row_ptr[node + 1]; ++e) {
+          const int c = b.fsm.nxt[e];
+          if (!mask_get(kept, c)) mask_set(bits, c);
+        }
+      }
+    }
+  } else {
+    // closure, deepest ancestors first: a path node all of whose children are blocked is blocked (below the start node the automaton is a
+    // tree, so the children of a depth-d node were settled by pass d + 1)
+    for (int d = LMAX - 1; d >= 0; --d) {
+      for (int s = s0 + tid; s < s1; s += kMaskThreads) {
+        if (b.len[s] <= d) continue;
+        const int node = b.path[(size_t)s * (LMAX + 1) + d];
+        bool all = true;
+        for (int e = b.fsm.row_ptr[node]; e < b.fsm.row_ptr[node + 1] && all; ++e) all = mask_get(bits, b.fsm.nxt[e]);
+        if (all) mask_set(bits, node);
+      }
+      __threadfence();
+      __syncthreads();
+    }
+  }
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    b.unknown[u] = n_unknown;
+    b.status[u] = (allow ? n_known == 0 : mask_get(bits, start)) ? ATSPEED_ERR_CONSTRAINT : ATSPEED_OK;
+  }
+}
+
 }  // namespace
 
 int ats_lse_rows(const float* logits, int n_rows, int vocab, int ld, float* lse, hipStream_t st) {
@@ -1127,6 +1221,98 @@ int ats_row_topk(const float* logits, int n_rows, int vocab, int ld, int kk, int
 }
 
 std::atomic<long long> g_ats_warp_launches{0};
+
+// ---- item filters (include/atspeed_hip.h): per-user node bitsets, built on the device where the automaton lives
+int ats_node_masks_build(const NodeMaskBuild& b, int n_users, hipStream_t st) {
+  if (n_users <= 0) return ATSPEED_OK;
+  node_masks_kernel<<<n_users, kMaskThreads, 0, st>>>(b);
+  ATS_LAUNCH_CHECK();
+  return ATSPEED_OK;
+}
+
+extern "C" void atspeed_node_masks_destroy(atspeed_node_masks* m) {
+  if (!m) return;
+  hipFree(m->block);
+  delete m;
+}
+
+extern "C" int atspeed_node_masks_create(const atspeed_fsm* fsm, int32_t n_users, const int32_t* start_nodes, const int32_t* seq_tokens,
+                                         const int32_t* seq_offsets, const int32_t* user_seq_offsets, int32_t mode, int32_t* unknown_out,
+                                         int32_t* status_out, void* stream, atspeed_node_masks** out) {
+  ATS_REQUIRE(fsm && start_nodes && seq_offsets && user_seq_offsets && status_out && out, ATSPEED_ERR_INVALID, "node_masks_create: null argument");
+  ATS_REQUIRE(fsm->dev.n_nodes > 0, ATSPEED_ERR_INVALID, "node_masks_create: a mask-free automaton has no nodes to filter");
+  ATS_REQUIRE(n_users >= 1, ATSPEED_ERR_INVALID, "node_masks_create: %d users", n_users);
+  ATS_REQUIRE(mode == ATSPEED_MASK_BLOCK || mode == ATSPEED_MASK_ALLOW, ATSPEED_ERR_INVALID, "node_masks_create: mode %d is neither ATSPEED_MASK_BLOCK nor ATSPEED_MASK_ALLOW", mode);
+  ATS_REQUIRE(user_seq_offsets[0] == 0 && seq_offsets[0] == 0, ATSPEED_ERR_INVALID, "node_masks_create: offsets must start at 0");
+  for (int u = 0; u < n_users; ++u) {
+    ATS_REQUIRE(user_seq_offsets[u + 1] >= user_seq_offsets[u], ATSPEED_ERR_INVALID, "node_masks_create: user offsets not monotone at user %d", u);
+    ATS_REQUIRE(start_nodes[u] >= 0 && start_nodes[u] < fsm->dev.n_nodes, ATSPEED_ERR_INVALID, "node_masks_create: start node of user %d out of range", u);
+  }
+  const int n_seq = user_seq_offsets[n_users];
+  for (int s = 0; s < n_seq; ++s) {
+    const int64_t len = (int64_t)seq_offsets[s + 1] - seq_offsets[s];
+    ATS_REQUIRE(len >= 1, ATSPEED_ERR_INVALID, "node_masks_create: sequence %d is empty", s);
+    ATS_REQUIRE(len <= LMAX, ATSPEED_ERR_INVALID, "node_masks_create: sequence %d holds %lld tokens (max %d)", s, (long long)len, LMAX);
+  }
+  const int n_tok = seq_offsets[n_seq];
+  ATS_REQUIRE(n_tok == 0 || seq_tokens, ATSPEED_ERR_INVALID, "node_masks_create: null token array");
+  hipStream_t st = (hipStream_t)stream;
+  std::unique_ptr<atspeed_node_masks, void (*)(atspeed_node_masks*)> m(new atspeed_node_masks(), atspeed_node_masks_destroy);
+  m->fsm = fsm; m->n_users = n_users; m->words = (fsm->dev.n_nodes + 31) / 32; m->bits = nullptr; m->block = nullptr;
+  // one block: the bitsets, allow mode's two scratch sets, then the int32 arrays
+  const size_t set_words = (size_t)n_users * m->words;
+  const size_t n_sets = mode == ATSPEED_MASK_ALLOW ? 3 : 1;
+  const size_t ints = (size_t)n_users /*start*/ + (size_t)std::max(n_tok, 1) + (size_t)(n_seq + 1) + (size_t)(n_users + 1) +
+                      (size_t)std::max(n_seq, 1) * (LMAX + 1) /*path*/ + (size_t)std::max(n_seq, 1) /*len*/ + 2 * (size_t)n_users /*unknown, status*/;
+  const size_t bytes = (n_sets * set_words + ints) * 4;
+  ATS_HIP(hipMalloc(&m->block, bytes));
+  ATS_HIP(hipMemsetAsync(m->block, 0, n_sets * set_words * 4, st));
+  uint32_t* w = (uint32_t*)m->block;
+  m->bits = w;
+  NodeMaskBuild b{};
+  b.fsm = fsm->dev; b.words = m->words; b.mode = mode;
+  b.bits = w; w += set_words;
+  b.kept = b.ends = b.bits;                      // block mode never touches them
+  if (mode == ATSPEED_MASK_ALLOW) { b.kept = w; w += set_words; b.ends = w; w += set_words; }
+  int32_t* p = (int32_t*)w;
+  int32_t* d_start = p; p += n_users;
+  int32_t* d_tok = p; p += std::max(n_tok, 1);
+  int32_t* d_soff = p; p += n_seq + 1;
+  int32_t* d_uoff = p; p += n_users + 1;
+  b.path = p; p += (size_t)std::max(n_seq, 1) * (LMAX + 1);
+  b.len = p; p += std::max(n_seq, 1);
+  b.unknown = p; p += n_users;
+  b.status = p; p += n_users;
+  b.start = d_start; b.seq_tok = d_tok; b.seq_off = d_soff; b.user_off = d_uoff;
+  ATS_HIP(hipMemcpyAsync(d_start, start_nodes, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
+  if (n_tok > 0) ATS_HIP(hipMemcpyAsync(d_tok, seq_tokens, sizeof(int32_t) * n_tok, hipMemcpyHostToDevice, st));
+  ATS_HIP(hipMemcpyAsync(d_soff, seq_offsets, sizeof(int32_t) * (n_seq + 1), hipMemcpyHostToDevice, st));
+  ATS_HIP(hipMemcpyAsync(d_uoff, user_seq_offsets, sizeof(int32_t) * (n_users + 1), hipMemcpyHostToDevice, st));
+  ATS_TRY(ats_node_masks_build(b, n_users, st));
+  ATS_HIP(hipMemcpyAsync(status_out, b.status, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
+  if (unknown_out) ATS_HIP(hipMemcpyAsync(unknown_out, b.unknown, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
+  ATS_HIP(hipStreamSynchronize(st));
+  *out = m.release();
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_node_masks_read(const atspeed_node_masks* m, int32_t user, uint32_t* words_out, int32_t n_words) {
+  ATS_REQUIRE(m && words_out, ATSPEED_ERR_INVALID, "node_masks_read: null argument");
+  ATS_REQUIRE(user >= 0 && user < m->n_users, ATSPEED_ERR_INVALID, "node_masks_read: user %d out of [0, %d)", user, m->n_users);
+  ATS_REQUIRE(n_words == m->words, ATSPEED_ERR_INVALID, "node_masks_read: a user's bitset holds %d words, not %d", m->words, n_words);
+  ATS_HIP(hipMemcpy(words_out, ats_mask_bits(m, user), sizeof(uint32_t) * m->words, hipMemcpyDeviceToHost));
+  return ATSPEED_OK;
+}
+
+// the filter of `user` on a by-value copy of the automaton, for the bare kernel entries
+static int masked_fsm(const atspeed_fsm* fsm, const atspeed_node_masks* masks, int user, const char* who, FsmDev* out) {
+  *out = fsm->dev;
+  if (!masks) return ATSPEED_OK;
+  ATS_REQUIRE(masks->fsm == fsm, ATSPEED_ERR_INVALID, "%s: the masks were built on another automaton", who);
+  ATS_REQUIRE(user >= 0 && user < masks->n_users, ATSPEED_ERR_INVALID, "%s: user %d out of [0, %d)", who, user, masks->n_users);
+  out->blocked = ats_mask_bits(masks, user);
+  return ATSPEED_OK;
+}
 
 static int warp_cut_check(const WarpCutArgs& a, int* rows_out) {
   ATS_REQUIRE(a.n_seg >= 1 && a.n_seg <= ATSPEED_MAX_GAMMA + 1 && a.fsm.n_nodes > 0, ATSPEED_ERR_INVALID, "warp cutoffs: need an automaton and 1..%d row segments",
@@ -1160,14 +1346,21 @@ int ats_row_warp_cutoff_multi(const WarpCutArgs* dev_args, int n, int max_rows, 
 
 extern "C" int64_t atspeed_warp_cutoff_launches(void) { return (int64_t)g_ats_warp_launches.load(std::memory_order_relaxed); }
 
-extern "C" int atspeed_warp_cutoffs(const float* logits, int32_t ld, const float* lse, int32_t n_rows, const atspeed_fsm* fsm, const int32_t* nodes,
-                                    float temperature, int32_t top_k, float top_p, int32_t min_keep, float* cutoffs, void* stream) {
+extern "C" int atspeed_warp_cutoffs_masked(const float* logits, int32_t ld, const float* lse, int32_t n_rows, const atspeed_fsm* fsm, const int32_t* nodes,
+                                           float temperature, int32_t top_k, float top_p, int32_t min_keep, float* cutoffs,
+                                           const atspeed_node_masks* masks, int32_t user, void* stream) {
   ATS_REQUIRE(logits && lse && fsm && nodes && cutoffs && n_rows >= 0 && ld > 0, ATSPEED_ERR_INVALID, "warp_cutoffs: bad arguments");
   WarpCutArgs a{};
   a.seg[0] = WarpSeg{nodes, n_rows}; a.n_seg = 1;
-  a.logits = logits; a.ld = ld; a.lse = lse; a.fsm = fsm->dev;
+  a.logits = logits; a.ld = ld; a.lse = lse;
+  ATS_TRY(masked_fsm(fsm, masks, user, "warp_cutoffs_masked", &a.fsm));
   a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.min_keep = min_keep; a.cutoff = cutoffs;
   return ats_row_warp_cutoff(a, (hipStream_t)stream);
+}
+
+extern "C" int atspeed_warp_cutoffs(const float* logits, int32_t ld, const float* lse, int32_t n_rows, const atspeed_fsm* fsm, const int32_t* nodes,
+                                    float temperature, int32_t top_k, float top_p, int32_t min_keep, float* cutoffs, void* stream) {
+  return atspeed_warp_cutoffs_masked(logits, ld, lse, n_rows, fsm, nodes, temperature, top_k, top_p, min_keep, cutoffs, nullptr, 0, stream);
 }
 
 int ats_beam_step(const BeamStepArgs& a, hipStream_t st) {
@@ -1262,10 +1455,10 @@ extern "C" int atspeed_accept(const int32_t* target_flat, const float* target_sc
   return ats_accept(target_flat, target_score, k, draft_flat, dk, hit, score_by_hit, accept, (hipStream_t)stream);
 }
 
-extern "C" int atspeed_beam_expand_prune(const float* logits, int32_t ld, const float* lse, const float* beam_score,
-                                         const int32_t* beam_node, int32_t n_rows, const atspeed_fsm* fsm, int32_t k,
-                                         float* out_score, int32_t* out_parent, int32_t* out_token, int32_t* out_node,
-                                         int32_t* out_flat, void* stream) {
+extern "C" int atspeed_beam_expand_prune_masked(const float* logits, int32_t ld, const float* lse, const float* beam_score,
+                                                const int32_t* beam_node, int32_t n_rows, const atspeed_fsm* fsm, int32_t k,
+                                                float* out_score, int32_t* out_parent, int32_t* out_token, int32_t* out_node,
+                                                int32_t* out_flat, const atspeed_node_masks* masks, int32_t user, void* stream) {
   ATS_REQUIRE(logits && lse && beam_score && beam_node && fsm && out_score && out_parent && out_token && out_node && out_flat,
               ATSPEED_ERR_INVALID, "beam_expand_prune: null argument");
   BeamStepArgs a{};
@@ -1274,13 +1467,21 @@ extern "C" int atspeed_beam_expand_prune(const float* logits, int32_t ld, const 
   a.src.seq = nullptr;
   a.n_src = n_rows; a.gen_len = 0;
   a.logits = logits; a.ld = ld; a.lse = lse;
-  a.fsm = fsm->dev;
+  ATS_TRY(masked_fsm(fsm, masks, user, "beam_expand_prune_masked", &a.fsm));
   a.k = k;
   a.dst.score = out_score; a.dst.parent = out_parent; a.dst.tok = out_token; a.dst.node = out_node; a.dst.flat = out_flat;
   a.dst.seq = nullptr;
   a.emit = 0; a.mail = nullptr; a.vis_words = 0;
   ATS_REQUIRE(fsm->dev.n_nodes > 0, ATSPEED_ERR_INVALID, "beam_expand_prune: a mask-free automaton needs atspeed_beam_expand_prune_free");
   return ats_beam_step(a, (hipStream_t)stream);
+}
+
+extern "C" int atspeed_beam_expand_prune(const float* logits, int32_t ld, const float* lse, const float* beam_score,
+                                         const int32_t* beam_node, int32_t n_rows, const atspeed_fsm* fsm, int32_t k,
+                                         float* out_score, int32_t* out_parent, int32_t* out_token, int32_t* out_node,
+                                         int32_t* out_flat, void* stream) {
+  return atspeed_beam_expand_prune_masked(logits, ld, lse, beam_score, beam_node, n_rows, fsm, k, out_score, out_parent, out_token, out_node, out_flat,
+                                          nullptr, 0, stream);
 }
 
 extern "C" int atspeed_row_topk(const float* scores, int32_t n_rows, int32_t vocab, int32_t ld, int32_t k, int32_t* out_tokens, void* stream) {

@@ -117,6 +117,7 @@ class TestUser:
     uid: int
     history: List[int]          # item ids, oldest first, already cut to max_his_len
     labels: List[int]           # test items (ground truth)
+    full_history: List[int] = field(default_factory=list)   # every train + valid item, not cut: what `exclude_history` blocks
 
 
 class SeqRecTestData:
@@ -129,10 +130,9 @@ class SeqRecTestData:
         for uid in test:                                         # dict order, as the reference iterates
             items = test[uid]
             if len(items):
-                history = list(train.get(uid, [])) + list(valid.get(uid, []))
-                if max_his_len > 0:
-                    history = history[-max_his_len:]
-                self.users.append(TestUser(uid, history, list(items)))
+                full = list(train.get(uid, [])) + list(valid.get(uid, []))
+                history = full[-max_his_len:] if max_his_len > 0 else full
+                self.users.append(TestUser(uid, history, list(items), full))
 
     @classmethod
     def load(cls, data_path: str, dataset: str, index_file: str = ".LCRec-1e-3lr.json", **kw) -> "SeqRecTestData":
@@ -280,14 +280,16 @@ def longest_prompt(data: "SeqRecTestData", L: int = 0, R: Optional[int] = None, 
 
 def run_inference(target, draft, data: SeqRecTestData, gamma: int = 4, max_new_tokens: int = 4, L: int = 0, R: Optional[int] = None,
                   users_per_batch: int = 128, prefix_allowed_tokens_fn=None, tokenizer=None, baseline: bool = False,
-                  device=None, decoder: str = "bssd", stream_lanes: Optional[int] = None) -> InferenceResult:
+                  device=None, decoder: str = "bssd", stream_lanes: Optional[int] = None, exclude_history: bool = False) -> InferenceResult:
     """Users [L, R) of the test set through beam-SD (inference.py:123-124,162-187), `users_per_batch` at a time in lock step.
     `baseline=True` also runs `target_generate` per user and records its time and the speed-up columns.
     `decoder="beam"`: the same users through the plain constrained beam search of the target (`target_generate_batch`, beamSD.py:544-595) --
     the same items (the method is lossless), and on MI355X the faster decoder once a lock-step batch is MFMA-bound (bench.py's
     `speedup_curve`): speculation pays while the target forward is a weight stream.
     `stream_lanes=N` (beam-SD only): all users through ONE session of N lanes (`BSSD_batch(..., lanes=N)`): a user that finishes hands its lane to
-    the next one at the round boundary, `users_per_batch` is not used.  Same predictions."""
+    the next one at the round boundary, `users_per_batch` is not used.  Same predictions.
+    `exclude_history=True`: no user is recommended an item of its own train + valid history (all of it, not the `max_his_len` cut the
+    prompt shows): each user's items go to the decoder as `exclude_items`.  Needs the strict item trie (`data.strict_trie_fn()`)."""
     import torch
     from .beamSD import BSSD_batch, target_generate, target_generate_batch
     if decoder not in ("bssd", "beam"):
@@ -302,19 +304,23 @@ def run_inference(target, draft, data: SeqRecTestData, gamma: int = 4, max_new_t
     sel = data.users[L:stop_r]
     res = InferenceResult()
     prompts = [{"input_ids": torch.from_numpy(encode_prompt(data, u, tokenizer, enc))[None].to(dev)} for u in sel]
+    # the history items' code tokens; items that share a code tuple are one item to the generator, so listing each tuple once is enough
+    excl = [[list(c) for c in sorted({data.index.item_codes[i] for i in u.full_history if i in data.index.item_codes})] for u in sel] \
+        if exclude_history else None
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     if stream_lanes is not None:
         users_per_batch = max(len(sel), 1)                      # one call: the session is the batching
     for lo in range(0, len(sel), users_per_batch):
         if decoder == "beam":
-            outs = target_generate_batch(target, prompts[lo:lo + users_per_batch], max_new_tokens, prefix_allowed_tokens_fn=fn)
+            outs = target_generate_batch(target, prompts[lo:lo + users_per_batch], max_new_tokens, prefix_allowed_tokens_fn=fn,
+                                         exclude_items=excl[lo:lo + users_per_batch] if excl is not None else None)
             for o in outs:                                  # the CSV columns of the beam-SD path (inference.py:152-156): no draft, no verification
                 o.update(draft_time_cost=0.0, target_time_cost=o["device_time_cost"], verify_time_cost=0.0, n_run=0, total_accept_steps=0,
                          total_accept_tokens=0, ave_accept_tokens=0.0)
         else:
             outs = BSSD_batch(target, draft, prompts[lo:lo + users_per_batch], gamma, max_new_tokens, prefix_allowed_tokens_fn=fn,
-                              lanes=stream_lanes)
+                              lanes=stream_lanes, exclude_items=excl[lo:lo + users_per_batch] if excl is not None else None)
         for u, pr, o in zip(sel[lo:lo + users_per_batch], prompts[lo:lo + users_per_batch], outs):
             P = pr["input_ids"].shape[1]
             # a user the library ended without a valid beam (status != 0: every beam of a step lost to the id filter, beamSD.py:80-86, where the

@@ -42,6 +42,9 @@ def parse(argv=None):
                     help="beam-SD through a session of N lanes instead of lock-step batches: a finished user's lane is refilled at the next round "
                          "boundary (BSSD_batch(..., lanes=N)); --users_per_batch is then unused")
     ap.add_argument("--strict_trie", action="store_true", help="strict item trie instead of the position-set mask")
+    ap.add_argument("--exclude_history", action="store_true",
+                    help="never recommend a user an item of its own train + valid history (all of it, not the --max_his_len cut): a per-user item "
+                         "filter on the device, users stay in lock step; needs --strict_trie")
     ap.add_argument("--decoder", choices=("bssd", "beam"), default="bssd",
                     help="bssd = beam speculative decoding (the reference's method); beam = plain constrained beam search of the target in lock "
                          "step: identical items, and on MI355X the faster of the two once a batch of users makes the target forward MFMA-bound "
@@ -81,6 +84,8 @@ def parse(argv=None):
         ap.error("--top_k / --top_p warp sampled scores: they need --do_sample")
     if args.stream_lanes is not None and (args.decoder != "bssd" or args.stream_lanes < 1):
         ap.error("--stream_lanes N needs --decoder bssd and N >= 1")
+    if args.exclude_history and not args.strict_trie:
+        ap.error("--exclude_history filters items, and only the strict item trie's nodes are items: it needs --strict_trie")
     if args.target_fp4 and args.target_fp8:
         ap.error("--target_fp4 and --target_fp8 are exclusive: choose one target precision")
     return args
@@ -154,7 +159,7 @@ def main(argv=None):
     for beam in ast.literal_eval(args.run_beam_sizes):          # the reference eval()s this flag (inference.py:151); a literal list is all it needs
         tgt, drf = load_models(args, data.index.vocab_size, beam, dev, max_prompt)
         res = run_inference(tgt, drf, data, args.gamma, 4, args.L + lo, args.L + hi, args.users_per_batch, fn, tok, args.baseline, dev, args.decoder,
-                            stream_lanes=args.stream_lanes)
+                            stream_lanes=args.stream_lanes, exclude_history=args.exclude_history)
         c = res.counters()
         per_rank = all_gather_counters(Counters(len(res.rows), int(sum(r["n_run"] for r in res.rows)),
                                                 int(sum(r["total_accept_steps"] for r in res.rows)), int(res.wall_s * 1e9)), dev)

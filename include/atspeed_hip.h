@@ -416,6 +416,62 @@ int atspeed_session_drain(atspeed_session* s, atspeed_session_done* done_out, in
 int atspeed_session_get_counters(const atspeed_session* s, atspeed_session_counters* out);
 void atspeed_session_destroy(atspeed_session* s);   /* frees the session's own tables only: the lanes' decoders are not touched */
 
+/* ------------------------------------------------------------------ item filters: exclude or allow lists per user
+ * All users of a call share ONE automaton and differ in their start node; a filter adds, per user, a bitset over the automaton's node ids
+ * (bit 1 = blocked) that every walk of the automaton consults.  No reference counterpart: there a per-user filter is a Python closure around
+ * the mask function, called per beam per step.
+ *
+ * A filter is a list of token sequences: the tokens a beam generates after the prompt (for a strict item trie an item's code tokens, with or
+ * without the EOS), each walked through the automaton from the user's start node.
+ *   - a sequence with a token that has no edge is UNKNOWN: ignored, and counted per user (unknown_out);
+ *   - an empty sequence, or one longer than ATSPEED_MAX_NEW_TOKENS, is ATSPEED_ERR_INVALID;
+ *   - the END NODE of a sequence is the node it leads to; it need not be a leaf.
+ * ATSPEED_MASK_BLOCK: B = the end nodes of the known sequences, closed bottom-up along the listed paths: a node on a listed path, the start
+ *   node included, all of whose children are in B, is in B -- so a live beam never stands on a node with no way on.  No sequences: all bits
+ *   0, the run equals an unfiltered one.
+ * ATSPEED_MASK_ALLOW: K = every node on a known path (the start node included), E = the end nodes.  A node is blocked iff it is a child of a
+ *   node in K \ E and not itself in K.  An end node's own children stay free (with a sequence that is a prefix of another, the end node
+ *   wins there); nodes that are no children of a path node keep bit 0, they cannot be reached.
+ * Bits at or above n_nodes are 0.  status_out[u] = ATSPEED_ERR_CONSTRAINT when user u's start node ends up blocked (block mode) or the user
+ * has no known sequence (allow mode), else ATSPEED_OK: HF's "returned an empty list" case, for the caller to refuse before it launches.
+ * The automaton must be a tree below the start nodes (whatever atspeed_trie_flatten produces is one).
+ *
+ * Decoding: a candidate (row r, child edge e) is absent iff the bit of the node the edge leads to is set -- treated exactly like a candidate
+ * below a warper cutoff: no key, score -inf, probability 0; the warper cutoffs are taken over the unblocked children only.  A live row all of
+ * whose children are blocked contributes nothing and raises no error; with fewer than k survivors the tail picks are "not a beam" (flat -1)
+ * and n_valid says how many are real.  Draft and target see the same bits, so beam-SD under a filter equals plain beam search under it.
+ *
+ * atspeed_node_masks_create: all arrays are HOST pointers.  User u owns sequences [user_seq_offsets[u], user_seq_offsets[u + 1]); sequence s
+ *   is seq_tokens[seq_offsets[s] .. seq_offsets[s + 1]).  The bitsets are built on the device (the automaton lives there; the library keeps
+ *   no host copy), one workgroup per user; the call synchronises `stream`.  Every allocation is made here.
+ * atspeed_node_masks_read: user's ceil(n_nodes / 32) words to the host (tests).
+ * atspeed_decoder_set_node_mask: the filter of `user` for the generate calls made with this decoder (one user, batch, target_generate(_batch)),
+ *   like the sampling mode; masks = NULL clears it.  The masks must have been built on the automaton the call uses (else the call returns
+ *   ATSPEED_ERR_INVALID) and stay alive while set.
+ * atspeed_session_submit_masked: atspeed_session_submit with a filter (masks = NULL: none).  It goes onto the lane at the user's admission and
+ *   off at its retirement -- it follows the user, not the lane -- and must stay valid until the ticket has come back. */
+typedef struct atspeed_node_masks atspeed_node_masks;
+#define ATSPEED_MASK_BLOCK 0
+#define ATSPEED_MASK_ALLOW 1
+int atspeed_node_masks_create(const atspeed_fsm* fsm, int32_t n_users, const int32_t* start_nodes, const int32_t* seq_tokens,
+                              const int32_t* seq_offsets, const int32_t* user_seq_offsets, int32_t mode, int32_t* unknown_out /* [n_users], may be NULL */,
+                              int32_t* status_out /* [n_users] */, void* stream, atspeed_node_masks** out);
+void atspeed_node_masks_destroy(atspeed_node_masks* masks);
+int atspeed_node_masks_read(const atspeed_node_masks* masks, int32_t user, uint32_t* words_out_host, int32_t n_words);
+int atspeed_decoder_set_node_mask(atspeed_decoder* d, const atspeed_node_masks* masks, int32_t user);
+int atspeed_session_submit_masked(atspeed_session* s, const int32_t* prompt_ids_dev, int32_t prompt_len, int32_t start_node, uint32_t seed,
+                                  int32_t* out_tokens_dev, float* out_scores_dev, atspeed_gen_stats* stats_host,
+                                  const atspeed_node_masks* masks, int32_t user, int64_t* ticket_out);
+/* The step and the cutoff kernel alone under a filter (tests): their unmasked twins' arguments plus (masks, user); masks = NULL: the twin. */
+int atspeed_beam_expand_prune_masked(const float* logits_dev, int32_t ld, const float* lse_dev,
+                                     const float* beam_score_dev, const int32_t* beam_node_dev, int32_t n_rows,
+                                     const atspeed_fsm* fsm, int32_t k,
+                                     float* out_score_dev, int32_t* out_parent_dev, int32_t* out_token_dev,
+                                     int32_t* out_node_dev, int32_t* out_flat_dev, const atspeed_node_masks* masks, int32_t user, void* stream);
+int atspeed_warp_cutoffs_masked(const float* logits_dev, int32_t ld, const float* lse_dev, int32_t n_rows, const atspeed_fsm* fsm,
+                                const int32_t* nodes_dev, float temperature, int32_t top_k, float top_p, int32_t min_tokens_to_keep,
+                                float* cutoffs_out_dev, const atspeed_node_masks* masks, int32_t user, void* stream);
+
 int atspeed_target_generate(atspeed_decoder* d, const int32_t* prompt_ids_dev, int32_t prompt_len,
                             const atspeed_fsm* fsm, int32_t start_node, int32_t max_new_tokens, int32_t k,
                             int32_t* out_tokens_dev, float* out_scores_dev, atspeed_gen_stats* stats_host,
