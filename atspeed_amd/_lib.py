@@ -41,14 +41,14 @@ class GenStats(C.Structure):
     _fields_ = [("n_run", C.c_int32), ("total_accept_steps", C.c_int32), ("accept_steps", C.c_int32 * MAX_NEW_TOKENS),
                 ("n_valid", C.c_int32), ("n_target_forwards", C.c_int32), ("n_draft_forwards", C.c_int32),
                 ("draft_ms", C.c_float), ("target_ms", C.c_float), ("verify_ms", C.c_float), ("total_ms", C.c_float),
-                ("status", C.c_int32)]
+                ("status", C.c_int32), ("n_target_passes", C.c_int32)]
 
 
 class SessionCounters(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("target_forwards", C.c_int64), ("draft_forwards", C.c_int64), ("lane_rounds", C.c_int64),
                 ("users_admitted", C.c_int64), ("users_retired", C.c_int64), ("allocs_after_create", C.c_int64),
                 ("arena_reserved", C.c_int32), ("arena_failed", C.c_int32), ("n_lanes", C.c_int32), ("lanes_occupied", C.c_int32),
-                ("queued", C.c_int64)]
+                ("queued", C.c_int64), ("target_passes", C.c_int64)]
 
 
 class SessionDone(C.Structure):
@@ -131,6 +131,8 @@ SIGNATURES = {
     "atspeed_decoder_trace": (C.c_int, [_P, _P, _I]),
     "atspeed_decoder_set_trace": (C.c_int, [_P, _I]),
     "atspeed_decoder_decisions": (C.c_int64, [_P, _P, C.c_int64]),
+    "atspeed_decoder_kv_bytes": (C.c_int64, [_P, _I]),
+    "atspeed_decoder_kv_copy": (C.c_int, [_P, _I, _I, _P, _P, _P]),
     "atspeed_gemm": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "atspeed_gemm_path_counters": (C.c_int, [_P, _I, _I]),
     "atspeed_set_switch": (C.c_int, [C.c_char_p, _I]),

@@ -506,6 +506,7 @@ def _bssd_stats(st, k: int) -> Dict:
         "n_valid": int(st.n_valid),
         "n_target_forwards": int(st.n_target_forwards),
         "n_draft_forwards": int(st.n_draft_forwards),
+        "n_target_passes": int(st.n_target_passes),
     }
 
 
@@ -535,8 +536,8 @@ beam_sd_generate = BSSD
 
 class BSSDSession:
     """A queue of BSSD users over `lanes` decoders (`atspeed_session_*`): `submit(inputs)` only queues a user and returns its ticket, `step()`
-    runs ONE round -- every free lane first takes the next queued user, in submission order; then the draft steps, the one packed target
-    forward and the verify walks of all occupied lanes -- and returns `[(ticket, result)]` for the users that finished in it, `drain()` steps
+    runs ONE round -- every free lane first takes the next queued user, in submission order; then the draft steps, the one target
+    forward (packed, or in phases where staged verification applies: switch `verify_staged`) and the verify walks of all occupied lanes -- and returns `[(ticket, result)]` for the users that finished in it, `drain()` steps
     until queue and lanes are empty.  A user that finishes frees its lane at the next round boundary instead of waiting for the slowest user
     of its chunk, and users may be submitted while others are decoding.
 

@@ -36,11 +36,20 @@ extern "C" const char* atspeed_version(void) { return "atspeed_hip 0.2 (gfx950)"
 
 // ---- process-wide switches (internal.h: ATS_SW_*)
 namespace {
+// Staged verification's two measured constants (DESIGN.md "Staged verification"; profiles/staged_verify_ab.txt).  T*: only a greedy lock-step
+// round whose packed target forward would hold more tokens than this may verify block by block (below it a forward is bound by the weight
+// stream and a speculative row costs nothing).  The pass cost: what one more phase costs, in tokens of a compute-bound forward -- a round is
+// staged when the rows it expects to skip (from the target's recent accepted steps) outnumber that per expected extra phase
+constexpr int ATS_VERIFY_STAGED_TOKENS = 4096;
+constexpr int ATS_VERIFY_STAGED_PASS_TOKENS = 1024;
 struct SwDef { const char* name; const char* env; int dflt; };
 const SwDef kSwitches[ATS_N_SW] = {{"gemm_sk", "ATSPEED_GEMM_SK", 1},           {"gemm_sk_g", nullptr, 0},
                                    {"gemm_panel", "ATSPEED_GEMM_PANEL", 1},     {"gemm_force_mt", "ATSPEED_GEMM_FORCE_MT", 0},
                                    {"graphs", "ATSPEED_GRAPHS", 0},             {"fuse_qkv_rope", "ATSPEED_FUSE_QKV_ROPE", 1},
-                                   {"gemm_kcut", "ATSPEED_GEMM_KCUT", 2},       {"fuse_qkv_reduce", "ATSPEED_FUSE_QKV_REDUCE", 1}};
+                                   {"gemm_kcut", "ATSPEED_GEMM_KCUT", 2},       {"fuse_qkv_reduce", "ATSPEED_FUSE_QKV_REDUCE", 1},
+                                   {"verify_staged", "ATSPEED_VERIFY_STAGED", 1},
+                                   {"verify_staged_tokens", "ATSPEED_VERIFY_STAGED_TOKENS", ATS_VERIFY_STAGED_TOKENS},
+                                   {"verify_staged_pass_tokens", "ATSPEED_VERIFY_STAGED_PASS_TOKENS", ATS_VERIFY_STAGED_PASS_TOKENS}};
 std::atomic<int> g_switch[ATS_N_SW];
 std::once_flag g_switch_once;
 void switches_init() {
@@ -315,6 +324,9 @@ struct atspeed_llama {
   long fp8_cnt[4] = {0, 0, 0, 0}, other_cnt[4] = {0, 0, 0, 0};
   long fp4_cnt[4] = {0, 0, 0, 0};                // the same for the W4A8 projections (atspeed_llama_fp4_counters; `other` is shared)
   long rope_fused_cnt = 0;                       // qkv projections that carried RoPE + the KV scatter in their epilogue (atspeed_llama_rope_fused_launches)
+  // staged verification's memory (bssd_round_staged): over the recent greedy verify walks on this target, decayed per round, how often a
+  // draft block j was drafted and how often the walk needed its rows (n_matches >= j)
+  double stg_drafted[ATSPEED_MAX_GAMMA + 1] = {}, stg_needed[ATSPEED_MAX_GAMMA + 1] = {};
   bool fwd_log_on = false;                       // (tokens, logit rows) of every forward while on (atspeed_llama_forward_log)
   std::vector<int32_t> fwd_log;
 };
@@ -736,18 +748,22 @@ extern "C" int64_t atspeed_llama_lora_launches(atspeed_llama* m, int32_t reset) 
 // One forward over the tokens of every segment (user) of the table.  Logits of each segment's last n_logit rows land
 // in act->logits rows [logit_row0, ..) (or in logits_out), their log-sum-exp in act->lse.
 static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTable* dtab, float* logits_out, hipStream_t st,
-                              const unsigned char* tile_store);
+                              const unsigned char* tile_store, int logit_row_off);
 
 // tile_store (device bytes, one per 256 vocabulary columns; NULL = every column): which logit tiles the caller will read.  The decoder
 // passes its automaton's (atspeed_fsm::d_tile_store): rows then get their full-vocabulary normaliser from the lm_head epilogue and
 // only those tiles are written to the logits buffer.
-static int llama_forward_segs(atspeed_llama* m, const SegTable& t, float* logits_out, hipStream_t st, const unsigned char* tile_store = nullptr) {
+// logit_row_off: the forward's logit rows (and their lse) start at that row of the model's buffers instead of row 0 -- a phase of a staged
+// verification round keeps the rows of the phases before it (decoder forwards only: logits_out == NULL)
+static int llama_forward_segs(atspeed_llama* m, const SegTable& t, float* logits_out, hipStream_t st, const unsigned char* tile_store = nullptr,
+                              int logit_row_off = 0) {
   const atspeed_llama_config& c = m->cfg;
   ActCtx* cx = m->act;
   const int T = t.total_tok;
   ATS_REQUIRE(T >= 1 && T <= cx->cap_tok, ATSPEED_ERR_CAPACITY, "forward: %d tokens exceed the activation capacity %d", T, cx->cap_tok);
-  ATS_REQUIRE(t.total_logit >= 0 && t.total_logit <= cx->cap_rows, ATSPEED_ERR_CAPACITY, "forward: %d logit rows exceed the capacity %d",
-              t.total_logit, cx->cap_rows);
+  ATS_REQUIRE(logit_row_off >= 0 && (logit_row_off == 0 || !logits_out), ATSPEED_ERR_INVALID, "forward: bad logit row offset %d", logit_row_off);
+  ATS_REQUIRE(t.total_logit >= 0 && logit_row_off + t.total_logit <= cx->cap_rows, ATSPEED_ERR_CAPACITY, "forward: %d logit rows exceed the capacity %d",
+              logit_row_off + t.total_logit, cx->cap_rows);
   for (int i = 0; i < t.n; ++i) {
     ATS_REQUIRE(t.seg[i].n_tok >= 1 && t.seg[i].n_slots >= 1 && t.seg[i].n_slots <= c.max_slots, ATSPEED_ERR_CAPACITY,
                 "forward: segment %d has %d tokens / %d slots (max_slots %d)", i, t.seg[i].n_tok, t.seg[i].n_slots, c.max_slots);
@@ -764,14 +780,14 @@ static int llama_forward_segs(atspeed_llama* m, const SegTable& t, float* logits
   // not host launch cost, and a graph keeps every node boundary
   const int use_graphs = ats_switch(ATS_SW_GRAPHS);                // (atspeed_set_switch("graphs", 1): the tests compare both modes in one process)
   constexpr int graph_max_tok = 512;
-  if (use_graphs && !m->prof_on && logits_out == nullptr && T <= graph_max_tok) {
+  if (use_graphs && !m->prof_on && logits_out == nullptr && logit_row_off == 0 && T <= graph_max_tok) {
     const ActCtx::GraphKey key(T, t.total_logit, t.n, t.n_qtiles, t.qtile_rows, !m->fp4.empty() ? 2 : m->fp8.empty() ? 0 : 1);
     auto it = cx->graphs.find(key);
     if (it == cx->graphs.end() && cx->graphs.size() < 64 && ++cx->graph_seen[key] >= 2) {   // a shape seen twice recurs (K + dl*DK tokens)
       g_ats_lazy_allocs++;                             // the capture stream (first time) and this shape's graph
       if (!cx->cap_stream) ATS_HIP(hipStreamCreateWithFlags(&cx->cap_stream, hipStreamNonBlocking));
       ATS_HIP(hipStreamBeginCapture(cx->cap_stream, hipStreamCaptureModeThreadLocal));
-      const int rc = llama_forward_body(m, t, dtab, nullptr, cx->cap_stream, nullptr);
+      const int rc = llama_forward_body(m, t, dtab, nullptr, cx->cap_stream, nullptr, 0);
       hipGraph_t g = nullptr;
       hipError_t e = hipStreamEndCapture(cx->cap_stream, &g);
       if (rc != ATSPEED_OK) { if (g) hipGraphDestroy(g); return rc; }
@@ -787,7 +803,7 @@ static int llama_forward_segs(atspeed_llama* m, const SegTable& t, float* logits
       return ATSPEED_OK;
     }
   }
-  return llama_forward_body(m, t, dtab, logits_out, st, logits_out ? nullptr : tile_store);
+  return llama_forward_body(m, t, dtab, logits_out, st, logits_out ? nullptr : tile_store, logit_row_off);
 }
 
 namespace fwd_bf16 {
@@ -799,9 +815,9 @@ using namespace ats_f16;
 #include "engine_forward.inc"
 }
 static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTable* dtab, float* logits_out, hipStream_t st,
-                              const unsigned char* tile_store) {
-  return m->cfg.dtype == ATSPEED_F16 ? fwd_f16::llama_forward_body(m, t, dtab, logits_out, st, tile_store)
-                                     : fwd_bf16::llama_forward_body(m, t, dtab, logits_out, st, tile_store);
+                              const unsigned char* tile_store, int logit_row_off) {
+  return m->cfg.dtype == ATSPEED_F16 ? fwd_f16::llama_forward_body(m, t, dtab, logits_out, st, tile_store, logit_row_off)
+                                     : fwd_bf16::llama_forward_body(m, t, dtab, logits_out, st, tile_store, logit_row_off);
 }
 
 extern "C" int atspeed_llama_forward(atspeed_llama* m, const int32_t* ids, const int32_t* pos, const int32_t* slots,
@@ -1114,6 +1130,24 @@ extern "C" int atspeed_decoder_set_node_mask(atspeed_decoder* d, const atspeed_n
   return ATSPEED_OK;
 }
 
+// the decoder's private K / V arenas, copied to or from the caller's device buffers (tests fill them with a sentinel and read back which slots
+// a call wrote)
+extern "C" int64_t atspeed_decoder_kv_bytes(const atspeed_decoder* d, int32_t draft) {
+  if (!d || (draft && !d->draft)) return -1;
+  const atspeed_llama* m = draft ? d->draft : d->target;
+  return (int64_t)m->cfg.n_layers * (int64_t)m->layer_kv_bytes;
+}
+extern "C" int atspeed_decoder_kv_copy(atspeed_decoder* d, int32_t draft, int32_t to_cache, void* k_dev, void* v_dev, void* stream) {
+  ATS_REQUIRE(d && k_dev && v_dev, ATSPEED_ERR_INVALID, "decoder_kv_copy: null argument");
+  ATS_REQUIRE(!draft || d->draft, ATSPEED_ERR_INVALID, "decoder_kv_copy: the decoder has no draft model");
+  const KvCache& kv = draft ? d->dkv : d->tkv;
+  const size_t bytes = (size_t)atspeed_decoder_kv_bytes(d, draft);
+  hipStream_t st = (hipStream_t)stream;
+  ATS_HIP(hipMemcpyAsync(to_cache ? kv.k : k_dev, to_cache ? k_dev : kv.k, bytes, hipMemcpyDeviceToDevice, st));
+  ATS_HIP(hipMemcpyAsync(to_cache ? kv.v : v_dev, to_cache ? v_dev : kv.v, bytes, hipMemcpyDeviceToDevice, st));
+  return ATSPEED_OK;
+}
+
 extern "C" int atspeed_decoder_set_trace(atspeed_decoder* d, int32_t level) {
   ATS_REQUIRE(d && (level == 0 || level == 1), ATSPEED_ERR_INVALID, "set_trace: level must be 0 or 1");
   if (level == 1 && !d->dump_host) ATS_HIP(hipHostMalloc((void**)&d->dump_host, d->beam_area_bytes));
@@ -1242,16 +1276,20 @@ int ats_seg_finish(SegTable& t, int qtile_rows) {
 // ---- one decode step: forward, then every user's beam step on its rows of the result
 // where a segment's logit rows, their normalisers and their candidate lists start in the model's buffers
 struct RowViews { const float* logits; const float* lse; const int32_t* row_cand; };
-static RowViews seg_rows(const atspeed_llama* m, const Seg& sg) {
+static RowViews seg_rows(const atspeed_llama* m, const Seg& sg, int row_off = 0) {
   const ActCtx* cx = m->act;
-  return RowViews{cx->logits + (size_t)sg.logit_row0 * m->logits_ld, cx->lse + sg.logit_row0, cx->row_cand + (size_t)sg.logit_row0 * MAXB};
+  const size_t r0 = (size_t)row_off + sg.logit_row0;
+  return RowViews{cx->logits + r0 * m->logits_ld, cx->lse + r0, cx->row_cand + r0 * MAXB};
 }
 
 // the forward of a decode step: only the logit tiles the automaton can read are written; a mask-free search takes its candidates from
 // the kk best tokens of every row instead
-static int decode_forward(atspeed_llama* m, const SegTable& t, const atspeed_fsm* fsm, int kk, hipStream_t st) {
-  ATS_TRY(llama_forward_segs(m, t, nullptr, st, fsm->d_tile_store));
-  if (fsm->dev.n_nodes == 0) ATS_TRY(ats_row_topk(m->act->logits, t.total_logit, m->cfg.vocab_size, m->logits_ld, kk, m->act->row_cand, st));
+// row_off: the step's logit rows, normalisers and candidate lists start at that row of the model's buffers (staged verification's phases)
+static int decode_forward(atspeed_llama* m, const SegTable& t, const atspeed_fsm* fsm, int kk, hipStream_t st, int row_off = 0) {
+  ATS_TRY(llama_forward_segs(m, t, nullptr, st, fsm->d_tile_store, row_off));
+  if (fsm->dev.n_nodes == 0)
+    ATS_TRY(ats_row_topk(m->act->logits + (size_t)row_off * m->logits_ld, t.total_logit, m->cfg.vocab_size, m->logits_ld, kk,
+                         m->act->row_cand + (size_t)row_off * MAXB, st));
   return ATSPEED_OK;
 }
 
@@ -1355,9 +1393,43 @@ static int bssd_ensure_capacity(atspeed_llama* T, atspeed_llama* D, int n, int n
 struct RoundCtl {
   bool flat_trace;          // copy the draft's flat ids to the per-round trace (atspeed_decoder_trace; groups of up to 4 users)
   bool keep_filtered;       // a user that loses every beam to the id filter ends alone with ATSPEED_ERR_FILTERED; else the round returns the error
+  bool lock_step;           // the batch call or a session: the round may verify in stages (the one-user call never does)
   bool any = false;         // out: a user of the group is not done yet
-  int target_forwards = 0, draft_forwards = 0;   // out: forwards this round launched
+  int target_forwards = 0, draft_forwards = 0;   // out: forwards this round launched (a staged round's phases are one target forward ...
+  int target_passes = 0;                         // ... and one pass over the target's weights each)
 };
+
+// Staged verification: does this round verify block by block?  Greedy users on a plain 16-bit or fp32 target only: a sampled round's
+// draws keep their order in the packed forward, and W8A8 / W4A8 / LoRA targets stay packed (their kernels are chosen by the forward's token count;
+// not measured here).  Switch "verify_staged": 0 never, 2 always, 1 (auto) when both hold:
+//   - the packed forward would exceed "verify_staged_tokens" tokens (T*);
+//   - by the target's recent walks (stg_needed / stg_drafted: block j is needed with probability Q_j; no history: never) the rows the round
+//     expects to skip, sum over users and blocks of (1 - Q_j) x DK, exceed "verify_staged_pass_tokens" per phase it expects to add (the
+//     blocks j that at least half a user is expected to need).  Where every block is accepted nothing can be skipped and the round stays
+//     packed; where the walks stop at step 0 no phase is added and every round above T* is staged.
+static bool bssd_round_staged(const std::vector<atspeed_decoder*>& ver, const std::vector<atspeed_decoder*>& fin) {
+  const int mode = ats_switch(ATS_SW_VERIFY_STAGED);
+  if (mode <= 0 || ver.empty()) return false;
+  const atspeed_llama* T = ver[0]->target;
+  if (!T->fp8.empty() || !T->fp4.empty() || !T->lora.empty()) return false;
+  long long tok = 0;
+  for (const atspeed_decoder* d : ver) { if (d->sample) return false; tok += d->run.n0 + d->run.dl * d->run.dk; }
+  for (const atspeed_decoder* d : fin) { if (d->sample) return false; tok += d->run.n0; }
+  if (mode >= 2) return true;
+  if (tok <= ats_switch(ATS_SW_VERIFY_STAGED_TOKENS)) return false;
+  const int pass_tok = ats_switch(ATS_SW_VERIFY_STAGED_PASS_TOKENS);
+  if (pass_tok <= 0) return true;
+  double skipped = 0., users_at[ATSPEED_MAX_GAMMA + 1] = {};
+  for (const atspeed_decoder* d : ver)
+    for (int j = 1; j <= d->run.dl; ++j) {
+      const double q = T->stg_drafted[j] >= 1. ? T->stg_needed[j] / T->stg_drafted[j] : 0.;
+      skipped += (1. - q) * d->run.dk;
+      users_at[j] += q;
+    }
+  int extra = 0;
+  for (int j = 1; j <= ATSPEED_MAX_GAMMA; ++j) extra += users_at[j] >= 0.5 ? 1 : 0;
+  return skipped > (double)extra * pass_tok;
+}
 
 // ONE round of BSSD (beamSD.py:458-542) over the n decoders handed to it (users that are done are skipped): every draft step and the target
 // verification of the round is ONE forward over the tokens of all users that need it (weights are streamed once per forward, not per user),
@@ -1421,72 +1493,118 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
     ATS_TRY(ats_beam_step_multi(dev_args, (int)args.size(), st));
   }
   hipEventRecord(g_ev[1], st);
-  // ---- 2. target: ONE forward over (round inputs ++ draft blocks) of every verifying user and the inputs of
-  //         every user on its final step (:190-232, :505-509)
+  hipEventRecord(g_ev[5], st);                     // the draft's end (g_ev[1] moves on to the start of a staged round's last phase)
+  // ---- 2. target forward and 3. verify (:190-232, :242-456, :505-509).  Packed: ONE forward over (round inputs ++ draft blocks) of every
+  //         verifying user and the inputs of every user on its final step, then every walk.  Staged (bssd_round_staged): phase 0 forwards the
+  //         round inputs only, phase p >= 1 draft block p of the users whose walk is still pending; each phase ends with the walks of its users
+  //         over the blocks that have rows so far and -- but for the last -- one mailbox read-back
+  float ms_t = 0.f, ms_v = 0.f;                    // target / verify time of the phases already read back
   if (!ver.empty() || !fin.empty()) {
-    SegTable t{};
-    for (atspeed_decoder* d : ver) {
-      atspeed_decoder::Run& r = d->run;
-      int Tn = r.n0 + r.dl * r.dk;
-      t.seg[t.n++] = make_seg(d->tin[r.cur], Tn, r.base + Tn, r.nb + r.dl * r.dk, d->tkv);
-      r.s.n_target_forwards++;
-    }
-    for (atspeed_decoder* d : fin) {
-      atspeed_decoder::Run& r = d->run;
-      t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv);
-      r.s.n_target_forwards++;
-    }
-    ATS_TRY(ats_seg_finish(t));
-    ATS_TRY(decode_forward(T, t, decs[0]->run.fsm, decs[0]->run.k, st));
-    ctl.target_forwards++;
-    hipEventRecord(g_ev[2], st);
-    // ---- 3. verify (:242-456) for the verifying users, one workgroup each
-    std::vector<VerifyArgs> vargs;
-    std::vector<WarpCutArgs> wargs;                  // sampling-mode warpers: the cutoffs of this round's verify walks and final steps
-    for (size_t j = 0; j < ver.size(); ++j) {
-      atspeed_decoder* d = ver[j];
-      atspeed_decoder::Run& r = d->run;
-      const RowViews rv = seg_rows(T, t.seg[j]);
-      VerifyArgs va{};
-      va.blk[0] = d->round_beams[r.cur];
-      for (int i = 1; i <= r.dl; ++i) va.blk[i] = d->blk[i];
-      va.nb = r.nb; va.dl = r.dl; va.k = r.k; va.dk = r.dk; va.gen_len0 = r.gen;
-      va.logits = rv.logits; va.ld = T->logits_ld; va.lse = rv.lse; va.fsm = d->fsm_dev(r.fsm);
-      va.row_cand = rv.row_cand; va.n_row_cand = r.k;
-      va.cur = d->tin[r.cur]; va.n0 = r.n0; va.next = d->tin[r.cur ^ 1]; va.dnext = d->dround; va.vis_words = W;
-      va.res = d->round_beams[r.cur ^ 1]; va.mail = d->mail_dev;
-      va.vtrace = (d->trace_level >= 1 && !d->sample) ? d->vtrace_dev : nullptr;
-      if (d->sample) {
-        va.sample = 1; va.temperature = d->temperature; va.seed = d->seed; va.round = r.s.n_run;
-        for (int i = 0; i < r.dl; ++i) {
-          va.dtab_score[i] = d->tab_score + (size_t)i * ATS_MAX_CAND; va.dtab_off[i] = d->tab_off + (size_t)i * (MAXB + 1);
-          va.dtab_lse[i] = d->tab_lse + i;
-        }
+    const bool staged = ctl.lock_step && bssd_round_staged(ver, fin);
+    std::vector<VerifyArgs> vall(ver.size());      // every verifying user's walk, built in phase 0; a later phase adds its block's rows
+    std::vector<size_t> pend(ver.size());          // indices into ver: the users of the phase
+    for (size_t j = 0; j < ver.size(); ++j) pend[j] = j;
+    int row_off = 0;                               // logit rows the earlier phases of the round hold
+    for (int p = 0;; ++p) {
+      SegTable t{};
+      for (size_t j : pend) {
+        atspeed_decoder* d = ver[j];
+        atspeed_decoder::Run& r = d->run;
+        const int Tn = r.n0 + r.dl * r.dk;
+        if (!staged)     t.seg[t.n++] = make_seg(d->tin[r.cur], Tn, r.base + Tn, r.nb + r.dl * r.dk, d->tkv);
+        else if (p == 0) t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv);
+        else             t.seg[t.n++] = make_seg(tb_offset(d->tin[r.cur], r.n0 + (p - 1) * r.dk, W), r.dk, r.base + r.n0 + p * r.dk, r.dk, d->tkv);
+        if (p == 0) r.s.n_target_forwards++;
+        r.s.n_target_passes++;
       }
-      if (d->warps()) { va.cutoff = d->cutoff; wargs.push_back(warp_cut_args(d, va)); }
-      vargs.push_back(va);
+      if (p == 0) for (atspeed_decoder* d : fin) {
+        atspeed_decoder::Run& r = d->run;
+        t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv);
+        r.s.n_target_forwards++; r.s.n_target_passes++;
+      }
+      ATS_TRY(ats_seg_finish(t));
+      ATS_TRY(decode_forward(T, t, decs[0]->run.fsm, decs[0]->run.k, st, row_off));
+      if (p == 0) ctl.target_forwards++;
+      ctl.target_passes++;
+      hipEventRecord(g_ev[2], st);
+      // ---- 3. verify for the phase's users, one workgroup each
+      std::vector<VerifyArgs> vargs;
+      std::vector<WarpCutArgs> wargs;                  // sampling-mode warpers: the cutoffs of this round's verify walks and final steps
+      const ActCtx* cx = T->act;
+      for (size_t i = 0; i < pend.size(); ++i) {
+        atspeed_decoder* d = ver[pend[i]];
+        atspeed_decoder::Run& r = d->run;
+        VerifyArgs& va = vall[pend[i]];
+        if (p == 0) {
+          va.blk[0] = d->round_beams[r.cur];
+          for (int b = 1; b <= r.dl; ++b) va.blk[b] = d->blk[b];
+          va.nb = r.nb; va.dl = r.dl; va.k = r.k; va.dk = r.dk; va.gen_len0 = r.gen;
+          va.ld = T->logits_ld; va.fsm = d->fsm_dev(r.fsm); va.n_row_cand = r.k;
+          va.cur = d->tin[r.cur]; va.n0 = r.n0; va.next = d->tin[r.cur ^ 1]; va.dnext = d->dround; va.vis_words = W;
+          va.res = d->round_beams[r.cur ^ 1]; va.mail = d->mail_dev;
+          va.vtrace = (d->trace_level >= 1 && !d->sample) ? d->vtrace_dev : nullptr;
+          if (d->sample) {
+            va.sample = 1; va.temperature = d->temperature; va.seed = d->seed; va.round = r.s.n_run;
+            for (int b = 0; b < r.dl; ++b) {
+              va.dtab_score[b] = d->tab_score + (size_t)b * ATS_MAX_CAND; va.dtab_off[b] = d->tab_off + (size_t)b * (MAXB + 1);
+              va.dtab_lse[b] = d->tab_lse + b;
+            }
+          }
+        }
+        if (!staged) {                                 // the walk's rows start at the user's first row; block b's follow block b - 1's
+          const RowViews rv = seg_rows(T, t.seg[i]);
+          va.logits = rv.logits; va.lse = rv.lse; va.row_cand = rv.row_cand;
+          for (int b = 1; b <= r.dl; ++b) va.blk_row0[b] = r.nb + (b - 1) * r.dk;
+          va.blocks_ready = r.dl + 1;
+        } else {                                       // rows counted from the buffers' start: block p's are where this phase's forward puts them
+          va.logits = cx->logits; va.lse = cx->lse; va.row_cand = cx->row_cand;
+          va.blk_row0[p] = row_off + t.seg[i].logit_row0;
+          va.blocks_ready = p + 1;
+        }
+        if (d->warps()) { va.cutoff = d->cutoff; wargs.push_back(warp_cut_args(d, va)); }
+        vargs.push_back(va);
+      }
+      std::vector<BeamStepArgs> fargs;
+      if (p == 0) for (size_t j = 0; j < fin.size(); ++j) {
+        atspeed_decoder* d = fin[j];
+        atspeed_decoder::Run& r = d->run;
+        BeamStepArgs a = beam_step_args(d, T, t.seg[ver.size() + j], r.fsm, d->round_beams[r.cur], d->round_beams[r.cur ^ 1], r.gen, r.k);   // emits nothing
+        if (a.sample) a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, 0, 0);
+        if (a.cutoff) wargs.push_back(warp_cut_args(d, a));
+        fargs.push_back(a);
+      }
+      ATS_TRY(warp_cutoffs(wargs, st));
+      if (!vargs.empty()) {
+        const VerifyArgs* dv = nullptr;
+        ATS_TRY(stage_args(vargs, &dv, st));
+        ATS_TRY(ats_verify_walk_multi(dv, (int)vargs.size(), st));
+      }
+      if (!fargs.empty()) {
+        const BeamStepArgs* df = nullptr;
+        ATS_TRY(stage_args(fargs, &df, st));
+        ATS_TRY(ats_beam_step_multi(df, (int)fargs.size(), st));
+      }
+      if (p == 0) for (atspeed_decoder* d : fin) { d->run.cur ^= 1; d->run.gen += 1; }
+      // a walk can be pending only where the user has a block without rows left
+      bool more = false;
+      for (size_t j : pend) more = more || (staged && ver[j]->run.dl > p);
+      if (!more) break;
+      // ---- hand-over: the phase's mailbox read-back; the next phase is built for the users still pending
+      hipEventRecord(g_ev[3], st);
+      ATS_HIP(hipStreamSynchronize(st));
+      ats_stage_reset();
+      float a_ms = 0.f, b_ms = 0.f;
+      hipEventElapsedTime(&a_ms, g_ev[1], g_ev[2]);
+      hipEventElapsedTime(&b_ms, g_ev[2], g_ev[3]);
+      ms_t += a_ms; ms_v += b_ms;
+      std::vector<size_t> next;
+      for (size_t j : pend) if (ver[j]->mail_host->n_matches == ATS_WALK_PENDING && ver[j]->mail_host->status == 0) next.push_back(j);
+      row_off += t.total_logit;
+      pend.swap(next);
+      hipEventRecord(g_ev[1], st);                   // the next phase's start (the last phase's brackets are read with the round's own read-back)
+      hipEventRecord(g_ev[2], st);
+      if (pend.empty()) break;
     }
-    std::vector<BeamStepArgs> fargs;
-    for (size_t j = 0; j < fin.size(); ++j) {
-      atspeed_decoder* d = fin[j];
-      atspeed_decoder::Run& r = d->run;
-      BeamStepArgs a = beam_step_args(d, T, t.seg[ver.size() + j], r.fsm, d->round_beams[r.cur], d->round_beams[r.cur ^ 1], r.gen, r.k);   // emits nothing
-      if (a.sample) a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, 0, 0);
-      if (a.cutoff) wargs.push_back(warp_cut_args(d, a));
-      fargs.push_back(a);
-    }
-    ATS_TRY(warp_cutoffs(wargs, st));
-    if (!vargs.empty()) {
-      const VerifyArgs* dv = nullptr;
-      ATS_TRY(stage_args(vargs, &dv, st));
-      ATS_TRY(ats_verify_walk_multi(dv, (int)vargs.size(), st));
-    }
-    if (!fargs.empty()) {
-      const BeamStepArgs* df = nullptr;
-      ATS_TRY(stage_args(fargs, &df, st));
-      ATS_TRY(ats_beam_step_multi(df, (int)fargs.size(), st));
-    }
-    for (atspeed_decoder* d : fin) { d->run.cur ^= 1; d->run.gen += 1; }
   } else {
     hipEventRecord(g_ev[2], st);
   }
@@ -1512,12 +1630,15 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
   }
   ATS_HIP(hipStreamSynchronize(st));
   ats_stage_reset();
-  float ms_d = 0.f, ms_t = 0.f, ms_v = 0.f;
-  hipEventElapsedTime(&ms_d, g_ev[0], g_ev[1]);
-  hipEventElapsedTime(&ms_t, g_ev[1], g_ev[2]);
-  hipEventElapsedTime(&ms_v, g_ev[2], g_ev[3]);
+  float ms_d = 0.f, ms_tl = 0.f, ms_vl = 0.f;
+  hipEventElapsedTime(&ms_d, g_ev[0], g_ev[5]);
+  hipEventElapsedTime(&ms_tl, g_ev[1], g_ev[2]);
+  hipEventElapsedTime(&ms_vl, g_ev[2], g_ev[3]);
+  ms_t += ms_tl; ms_v += ms_vl;
   int n_act = 0;
   for (int u = 0; u < n; ++u) if (!decs[u]->run.done) ++n_act;
+  if (!ver.empty() && !ver[0]->sample)             // staged verification's memory: a round of walks halves the weight of what came before
+    for (int j = 1; j <= ATSPEED_MAX_GAMMA; ++j) { T->stg_drafted[j] *= 0.5; T->stg_needed[j] *= 0.5; }
   ctl.any = false;
   for (int u = 0; u < n; ++u) {
     atspeed_decoder* d = decs[u];
@@ -1546,6 +1667,8 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
       continue;
     }
     const int nm = d->mail_host->n_matches, dl = r.dl, dk = r.dk;
+    ATS_REQUIRE(nm >= 0 && nm <= dl, ATSPEED_ERR_HIP, "bssd: a verify walk reported %d accepted steps of %d", nm, dl);
+    if (!d->sample) for (int j = 1; j <= dl; ++j) { T->stg_drafted[j] += 1.; T->stg_needed[j] += nm >= j ? 1. : 0.; }
     if (ctl.flat_trace) {
       d->trace.push_back(dl); d->trace.push_back(nm); d->trace.push_back(r.nb);
       for (int i = 0; i < dl; ++i) for (int j = 0; j < dk; ++j) d->trace.push_back(d->trace_host[i * MAXB + j]);
@@ -1571,7 +1694,7 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
 
 // n users in lock step from their first round to the last one's end (the one-user and the batch call): a user leaves when its last round
 // ends, nobody takes its place
-static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
+static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st, bool lock_step) {
   hipEvent_t* g_ev = nullptr;
   ATS_TRY(stage_events(&g_ev));
   int cap_t = 0, cap_r = 0, cap_d = 0;
@@ -1583,7 +1706,7 @@ static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st) {
   }
   ATS_TRY(ensure_act(decs[0]->target, cap_t, cap_r));
   ATS_TRY(ensure_act(decs[0]->draft, cap_d, n * MAXB));
-  RoundCtl ctl{n <= 4, n > 1};
+  RoundCtl ctl{n <= 4, n > 1, lock_step};
   do ATS_TRY(bssd_round(decs, n, st, g_ev, ctl)); while (ctl.any);
   return ATSPEED_OK;
 }
@@ -1603,14 +1726,14 @@ extern "C" int atspeed_bssd_generate_batch(atspeed_decoder** decs, int32_t n, co
                        stats ? &stats[i] : nullptr, st, false));
   }
   ATS_TRY(init_prompts_multi(decs, n, prompts, prompt_lens, start_nodes, st));
-  return bssd_group_run(decs, n, st);
+  return bssd_group_run(decs, n, st, true);
 }
 
 extern "C" int atspeed_bssd_generate(atspeed_decoder* d, const int32_t* prompt, int32_t P, const atspeed_fsm* fsm,
                                      int32_t start_node, int32_t gamma, int32_t max_new, int32_t k, int32_t dk,
                                      int32_t* out_tokens, float* out_scores, atspeed_gen_stats* stats, void* stream) {
   ATS_TRY(bssd_begin(d, prompt, P, fsm, start_node, gamma, max_new, k, dk, out_tokens, out_scores, stats, (hipStream_t)stream));
-  return bssd_group_run(&d, 1, (hipStream_t)stream);
+  return bssd_group_run(&d, 1, (hipStream_t)stream, false);
 }
 
 // ---- sessions (include/atspeed_hip.h "sessions"): the same round over a fixed set of lanes, each free lane refilled from a host queue at the
@@ -1628,7 +1751,7 @@ struct atspeed_session {
   int gamma = 0, max_new = 0, k = 0, dk = 0, max_prompt = 0;
   hipStream_t st = nullptr;
   ats_session::Queue<SessionJob> q;
-  int64_t target_forwards = 0, draft_forwards = 0, allocs_after_create = 0;
+  int64_t target_forwards = 0, target_passes = 0, draft_forwards = 0, allocs_after_create = 0;
   bool arena_failed = false;
   explicit atspeed_session(int n) : q(n) {}
 };
@@ -1731,9 +1854,9 @@ static int session_round(atspeed_session* s) {
   if (decs.empty()) return ATSPEED_OK;
   ATS_TRY(bssd_ensure_capacity(decs[0]->target, decs[0]->draft, s->q.n_lanes(), s->max_prompt, s->gamma, s->k, s->dk));   // create made it: a no-op
   s->q.begin_round();
-  RoundCtl ctl{false, true};
+  RoundCtl ctl{false, true, true};
   ATS_TRY(bssd_round(decs.data(), (int)decs.size(), s->st, g_ev, ctl));
-  s->target_forwards += ctl.target_forwards; s->draft_forwards += ctl.draft_forwards;
+  s->target_forwards += ctl.target_forwards; s->draft_forwards += ctl.draft_forwards; s->target_passes += ctl.target_passes;
   for (size_t i = 0; i < decs.size(); ++i)
     if (decs[i]->run.done) { decs[i]->masks = nullptr; decs[i]->mask_user = 0; s->q.retire(lane_of[i], decs[i]->run.s.status); }
   return ATSPEED_OK;
@@ -1796,7 +1919,7 @@ extern "C" int atspeed_session_get_counters(const atspeed_session* s, atspeed_se
   const atspeed_llama* T = s->lanes[0]->target;
   *out = atspeed_session_counters{s->q.rounds(), s->target_forwards, s->draft_forwards, s->q.lane_rounds(), s->q.admitted(), s->q.retired(),
                                   s->allocs_after_create, T->act && T->act->sk.ws ? 1 : 0, s->arena_failed ? 1 : 0, s->q.n_lanes(), s->q.occupied(),
-                                  s->q.queued()};
+                                  s->q.queued(), s->target_passes};
   return ATSPEED_OK;
 }
 
@@ -1878,7 +2001,7 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
     if (stats) {
       atspeed_gen_stats gs;
       memset(&gs, 0, sizeof(gs));
-      gs.n_target_forwards = max_new; gs.n_valid = filtered ? 0 : decs[u]->mail_host->n_valid;
+      gs.n_target_forwards = gs.n_target_passes = max_new; gs.n_valid = filtered ? 0 : decs[u]->mail_host->n_valid;
       gs.status = filtered ? ATSPEED_ERR_FILTERED : ATSPEED_OK;
       gs.total_ms = gs.target_ms = ms / n;                      // the group's time shared equally by its users
       stats[u] = gs;

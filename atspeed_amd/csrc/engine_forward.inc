@@ -70,7 +70,7 @@ static int layer_fp4(atspeed_llama* m, int l, const SegTable& t, const SegTable*
 
 // the launches of one forward (also the body of a captured graph: no allocation, no synchronisation, no staging in here)
 static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTable* dtab, float* logits_out, hipStream_t st,
-                              const unsigned char* tile_store) {
+                              const unsigned char* tile_store, int logit_row_off) {
   const atspeed_llama_config& c = m->cfg;
   ActCtx* cx = m->act;
   const int T = t.total_tok;
@@ -179,15 +179,16 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
     const int R = t.total_logit;
     ATS_TRY(ats_gather_logit_rows(cx->h, t, dtab, cx->gath, H, dt, st));
     ATS_TRY(ats_rmsnorm(cx->gath, m->final_norm, cx->xn, R, H, c.rms_eps, dt, st, pk));
-    float* lo = logits_out ? logits_out : cx->logits;
+    float* lo = logits_out ? logits_out : cx->logits + (size_t)logit_row_off * m->logits_ld;
+    float* lse = cx->lse + logit_row_off;
     if (tile_store) {      // decoder forwards: logits + full-vocabulary normaliser (beamSD.py:58,285) from ONE kernel where the batch is large enough
       ProfBracket pb(m, 4, R, st);
-      ATS_TRY(ats_lmhead_lse(cx->xn, m->lm_head, lo, R, c.vocab_size, H, H, m->logits_ld, dt, tile_store, cx->lse_part, cx->lse_part_bytes, cx->lse,
+      ATS_TRY(ats_lmhead_lse(cx->xn, m->lm_head, lo, R, c.vocab_size, H, H, m->logits_ld, dt, tile_store, cx->lse_part, cx->lse_part_bytes, lse,
                              cx->ws, cx->ws_bytes, st, nullptr, pk, sk));
     } else {
       { ProfBracket pb(m, 4, R, st);
         ATS_TRY(ats_gemm(cx->xn, m->lm_head, lo, R, c.vocab_size, H, H, m->logits_ld, dt, EPI_F32, cx->ws, cx->ws_bytes, st, pk, sk)); }
-      ATS_TRY(ats_lse_rows(lo, R, c.vocab_size, m->logits_ld, cx->lse, st));     // beamSD.py:58,285: full-vocab normaliser
+      ATS_TRY(ats_lse_rows(lo, R, c.vocab_size, m->logits_ld, lse, st));     // beamSD.py:58,285: full-vocab normaliser
     }
   }
   return ATSPEED_OK;

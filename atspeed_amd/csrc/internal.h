@@ -72,6 +72,9 @@ enum { ATS_SW_GEMM_SK = 0,        // "gemm_sk"       ATSPEED_GEMM_SK (1): ring k
        ATS_SW_FUSE_QKV_ROPE,      // "fuse_qkv_rope" ATSPEED_FUSE_QKV_ROPE (1): RoPE + KV scatter in the qkv projection's epilogue
        ATS_SW_GEMM_KCUT,          // "gemm_kcut"     ATSPEED_GEMM_KCUT (2): bf16 N <= 4096 projections at 257-1100 tokens cut in K over the whole chip
        ATS_SW_FUSE_QKV_REDUCE,    // "fuse_qkv_reduce" ATSPEED_FUSE_QKV_REDUCE (1): one user's qkv split-K slabs are summed by the RoPE kernel instead of a reduce launch
+       ATS_SW_VERIFY_STAGED,      // "verify_staged" ATSPEED_VERIFY_STAGED (1): lock-step greedy rounds verify block by block -- 0 never, 1 rounds above the threshold, 2 always
+       ATS_SW_VERIFY_STAGED_TOKENS, // "verify_staged_tokens" ATSPEED_VERIFY_STAGED_TOKENS: the threshold T* -- only a round whose packed target forward would exceed it is staged
+       ATS_SW_VERIFY_STAGED_PASS_TOKENS, // "verify_staged_pass_tokens" ATSPEED_VERIFY_STAGED_PASS_TOKENS: rows a staged round must expect to skip per phase it expects to add; 0 = T* alone decides
        ATS_N_SW };
 int ats_switch(int id);
 
@@ -175,6 +178,9 @@ struct VerifyArgs {
   BeamSet blk[ATSPEED_MAX_GAMMA + 1];         // blk[0] round beams, blk[i] draft step i
   int nb, dl, k, dk, gen_len0;
   const float* logits;  int ld;  const float* lse;   // rows: block 0 (nb), then dl blocks of dk
+  // greedy walk only: block i's first row of logits / lse / row_cand (packed: 0, nb, nb + dk, ...; a staged round: where that phase's forward
+  // put them), and how many blocks have rows yet.  A walk that needs block i >= blocks_ready writes n_matches = ATS_WALK_PENDING and nothing else
+  int blk_row0[ATSPEED_MAX_GAMMA + 1];  int blocks_ready;
   FsmDev fsm;
   TokBuf cur;  int n0;                        // packed target inputs of this round
   TokBuf next;                                // next round's target inputs (k rows)
@@ -191,6 +197,7 @@ struct VerifyArgs {
   // (score bits, parent = index into blk[i], token; flat < 0 picks have token -1); NULL = off
   int32_t* vtrace;
 };
+constexpr int ATS_WALK_PENDING = -1;         // Mailbox::n_matches of a greedy walk that stopped at a block without rows (staged verification)
 int ats_verify_walk_multi(const VerifyArgs* dev_args, int n, hipStream_t st);
 
 // Sampling-mode warpers (top-k, then top-p with min_keep; transformers' TopKLogitsWarper / TopPLogitsWarper after the temperature,

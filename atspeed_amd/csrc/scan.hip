@@ -960,13 +960,19 @@ __device__ void verify_walk_body(const VerifyArgs& a) {
   Pick pk;
   pk.flat = -1; pk.score = -INFINITY; pk.parent = 0; pk.tok = 0; pk.node = 0;
   for (int i = 0; i <= a.dl; ++i) {
+    // staged verification: block i's rows come with a later forward.  Nothing has been written yet (the trace's picks are rewritten by the
+    // walk that finishes, which starts from step 0 again and so takes every decision exactly as the one-forward round does)
+    if (i >= a.blocks_ready) {                                           // uniform
+      if (tid == 0) { a.mail->n_matches = ATS_WALK_PENDING; if (sh.status != 0) a.mail->status = sh.status; }
+      return;
+    }
     const int n_rows = i == 0 ? a.nb : k;
     __syncthreads();
     if (tid < n_rows) {                                                  // beamSD.py:279-296
       int br = i == 0 ? tid : hit[tid];
       sh.brow[tid] = br;
       sh.node[tid] = a.blk[i].node[br];
-      sh.lrow[tid] = i == 0 ? tid : a.nb + (i - 1) * dk + br;
+      sh.lrow[tid] = a.blk_row0[i] + br;
       sh.bscore[tid] = i == 0 ? a.blk[0].score[tid] : sbh[tid];
     }
     __syncthreads();

@@ -330,6 +330,8 @@ typedef struct atspeed_gen_stats {
   int32_t status;              /* batched calls: ATSPEED_OK, or ATSPEED_ERR_FILTERED for a user whose step lost every beam to the id
                                   filter of beamSD.py:80-86 -- that user ends with n_valid = 0, the rest of the batch finishes (the
                                   one-user calls return the error instead)                */
+  int32_t n_target_passes;     /* passes over the target's weights that included this user: n_target_forwards, plus one per further phase
+                                  of a round verified in stages (switch "verify_staged")  */
 } atspeed_gen_stats;
 
 /* prompt_ids_dev: [prompt_len] int32.  out_tokens_dev: [k][max_new_tokens] int32 generated
@@ -340,6 +342,10 @@ int atspeed_bssd_generate(atspeed_decoder* d, const int32_t* prompt_ids_dev, int
                           int32_t k, int32_t dk, int32_t* out_tokens_dev, float* out_scores_dev,
                           atspeed_gen_stats* stats_host, void* stream);
 
+/* Staged verification (switches "verify_staged", "verify_staged_tokens", "verify_staged_pass_tokens"): a greedy round of
+ * atspeed_bssd_generate_batch or of a session may forward the round inputs first and then one draft block per phase, only for the users whose
+ * verify walk still needs it; each phase but the last ends with one more synchronisation of the stream.  Tokens, accepted steps and
+ * n_target_forwards are the packed round's, scores to fp32 rounding; n_target_passes counts the phases.  atspeed_bssd_generate never stages. */
 /* n independent users, one decoder each, interleaved on the decoders' private streams (the reference runs users
  * strictly one after another, inference.py:162-176): hides the per-round mailbox sync and the launch latency of
  * the small forwards, and lets forwards of different users overlap.  Results equal n sequential calls. */
@@ -353,7 +359,8 @@ int atspeed_bssd_generate_batch(atspeed_decoder** decoders, int32_t n, const int
  * atspeed_bssd_generate_batch decodes a fixed list in lock step: a user that finishes leaves its place empty until the slowest user of the
  * call is done.  A session keeps `n_lanes` decoders (lanes) busy instead: users are submitted to a host queue at any time, and at every round
  * boundary each free lane takes the next queued user (in submission order) before the round runs.  A round is exactly the round of the batch
- * call -- draft steps, ONE packed target forward, verify / final steps, exports, one stream synchronisation -- over the occupied lanes; a user's
+ * call -- draft steps, ONE target forward (packed, or verified in stages: below), verify / final steps, exports, one stream synchronisation per
+ * phase -- over the occupied lanes; a user's
  * prompt is ingested inside its first round's forwards.  Every user's result equals its own atspeed_bssd_generate call (scores to fp32
  * rounding, as in the batch call).  No reference counterpart (the reference decodes one user at a time, inference.py:162-176).
  *
@@ -388,7 +395,7 @@ int atspeed_bssd_generate_batch(atspeed_decoder** decoders, int32_t n, const int
 typedef struct atspeed_session atspeed_session;
 typedef struct atspeed_session_counters {
   int64_t rounds;                  /* rounds that ran (empty rounds do not count)                                  */
-  int64_t target_forwards;         /* packed target forwards launched (one per round)                               */
+  int64_t target_forwards;         /* target forwards launched (one per round, whether packed or verified in stages)  */
   int64_t draft_forwards;          /* draft forwards launched (up to gamma per round)                               */
   int64_t lane_rounds;             /* sum over rounds of the lanes occupied in it                                   */
   int64_t users_admitted, users_retired;
@@ -400,6 +407,8 @@ typedef struct atspeed_session_counters {
   int32_t arena_failed;            /* 1: create wanted the arena and could not get it                               */
   int32_t n_lanes, lanes_occupied; /* now                                                                           */
   int64_t queued;                  /* users submitted and not yet admitted                                          */
+  int64_t target_passes;           /* passes over the target's weights launched: target_forwards, plus one per further phase of a round
+                                      verified in stages (switch "verify_staged")                                    */
 } atspeed_session_counters;
 int atspeed_session_create(atspeed_decoder* const* lanes, int32_t n_lanes, const atspeed_fsm* fsm, int32_t gamma, int32_t max_new_tokens,
                            int32_t k, int32_t dk, int32_t max_prompt, void* stream, atspeed_session** out);
@@ -507,6 +516,12 @@ int atspeed_decoder_trace(atspeed_decoder* d, int32_t* rounds_out, int32_t cap);
  * block i), token[64] (-1 = no pick)}, valid for steps 0..n_matches. */
 int atspeed_decoder_set_trace(atspeed_decoder* d, int32_t level);
 int64_t atspeed_decoder_decisions(atspeed_decoder* d, int32_t* out, int64_t cap_words);
+/* The decoder's private K / V arenas of its target (draft = 0) or draft model (test hook).  Each arena is [n_layers][max_slots][hidden] elements
+ * of the model's type, row s of a layer = KV slot s; atspeed_decoder_kv_bytes is one arena's size (-1: no such model).  atspeed_decoder_kv_copy
+ * copies both arenas from (to_cache = 1) or to (0) the caller's device buffers of that size, stream ordered: a test fills them with a sentinel
+ * and reads back which slots a call wrote (a round verified in stages leaves the slots of blocks it never forwarded untouched). */
+int64_t atspeed_decoder_kv_bytes(const atspeed_decoder* d, int32_t draft);
+int atspeed_decoder_kv_copy(atspeed_decoder* d, int32_t draft, int32_t to_cache, void* k_dev, void* v_dev, void* stream);
 
 /* ------------------------------------------------------------------ low-level ops (tests, benches)
  * C[M,N] = A[M,K] * W[N,K]^T on MFMA; epilogue: 0 store (dtype), 1 fp32 store, 2 residual add into
@@ -533,7 +548,9 @@ int atspeed_gemm_path_counters(int64_t* out, int32_t n, int32_t reset);
  * variable is the way to set it for a whole run) and changeable afterwards only through this call (tests and sweeps that compare two
  * settings in one process) -- the dispatch path never calls getenv.  Names: "gemm_sk" (ATSPEED_GEMM_SK, 1), "gemm_sk_g" (no variable; test
  * hook, 0), "gemm_panel" (ATSPEED_GEMM_PANEL, 1), "gemm_force_mt" (ATSPEED_GEMM_FORCE_MT, 0), "graphs" (ATSPEED_GRAPHS, 0),
- * "fuse_qkv_rope" (ATSPEED_FUSE_QKV_ROPE, 1), "fuse_qkv_reduce" (ATSPEED_FUSE_QKV_REDUCE, 1), "gemm_kcut" (ATSPEED_GEMM_KCUT, 2); meanings in INTEGRATION.md.  Unknown name: ATSPEED_ERR_INVALID. */
+ * "fuse_qkv_rope" (ATSPEED_FUSE_QKV_ROPE, 1), "fuse_qkv_reduce" (ATSPEED_FUSE_QKV_REDUCE, 1), "gemm_kcut" (ATSPEED_GEMM_KCUT, 2),
+ * "verify_staged" (ATSPEED_VERIFY_STAGED, 1), "verify_staged_tokens" (ATSPEED_VERIFY_STAGED_TOKENS, the measured threshold T*),
+ * "verify_staged_pass_tokens" (ATSPEED_VERIFY_STAGED_PASS_TOKENS, the measured cost of a phase in tokens); meanings in INTEGRATION.md.  Unknown name: ATSPEED_ERR_INVALID. */
 int atspeed_set_switch(const char* name, int32_t value);
 int atspeed_get_switch(const char* name, int32_t* value_out);
 /* atspeed_gemm / atspeed_gemm_fp8 on operands in the packed layout (a / xq and w / wq through atspeed_pack_rows; K % 32 == 0, for fp8 K % 64 == 0):
