@@ -77,6 +77,7 @@ SIGNATURES = {
     "atspeed_llama_forward": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "atspeed_llama_forward_batch": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "atspeed_llama_logits": (_P, [_P]),
+    "atspeed_llama_read": (C.c_int, [_P, _I, _I, _P, _SZ, _P]),
     "atspeed_probe_mfma_bf16": (C.c_int, [_I, _P, C.c_size_t, _P, _P]),
     "atspeed_probe_hbm_read": (C.c_int, [_P, C.c_size_t, _I, _P, _P, _P]),
     "atspeed_llama_enable_fp8": (C.c_int, [_P, _P]),
@@ -147,6 +148,7 @@ SIGNATURES = {
     "atspeed_tree_attention_tiled": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "atspeed_segs_embed": (C.c_int, [_P, _I, _I, _I, _P] + _SEGS + [_P]),
     "atspeed_segs_gather_logit_rows": (C.c_int, [_P, _I, _I, _P] + _SEGS + [_P]),
+    "atspeed_segs_gather_tail_rows": (C.c_int, [_P, _P, _I, _I, _I, _P, _P] + _SEGS + [_P]),
     "atspeed_segs_row_info": (C.c_int, [_P, _I] + _SEGS + [_P]),
     "atspeed_segs_rope_kv": (C.c_int, [_P, _P, _I, _P, _P, _SZ, _I, _I, _I, _I] + _SEGS + [_P]),
     "atspeed_segs_tree_attention": (C.c_int, [_P, _I, _SZ, _I, _P, _I, _I, _I, _I, _I, _I, _I] + _SEGS + [_P]),

@@ -344,17 +344,37 @@ int ats_rope_kv_segs(void* qkv, const SegTable& t, const SegTable* dt, const flo
   return ATSPEED_OK;
 }
 
+// the token row that logit row lr comes from: the last n_logit rows of every segment follow each other
+__device__ inline int logit_src_row(const SegTable* __restrict__ t, int lr) {
+  int lo = 0, hi = t->n;
+  while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (t->seg[mid].logit_row0 <= lr) lo = mid; else hi = mid; }
+  const Seg& sg = t->seg[lo];
+  return sg.row0 + sg.n_tok - sg.n_logit + (lr - sg.logit_row0);
+}
+
 // copy the last n_logit rows of every segment to consecutive rows (input of the final norm + lm_head)
 __global__ void gather_logit_rows_kernel(const uint4* __restrict__ h, const SegTable* __restrict__ t, uint4* __restrict__ out,
                                          int chunks_per_row) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= t->total_logit * chunks_per_row) return;
   int lr = i / chunks_per_row, c = i - lr * chunks_per_row;
-  int lo = 0, hi = t->n;
-  while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (t->seg[mid].logit_row0 <= lr) lo = mid; else hi = mid; }
-  const Seg& sg = t->seg[lo];
-  int src_row = sg.row0 + sg.n_tok - sg.n_logit + (lr - sg.logit_row0);
-  out[i] = h[(size_t)src_row * chunks_per_row + c];
+  out[i] = h[(size_t)logit_src_row(t, lr) * chunks_per_row + c];
+}
+
+// The same rows of the residual stream h (row-major) AND of the attention output att (the o_proj operand: packed when pk) in one launch: what
+// the row-pruned tail of the last layer reads (engine_forward.inc).  One thread per 16-byte chunk of a logit row moves that chunk of both
+// buffers; a chunk never leaves its 64-byte k-block, so the packed map is applied to whole chunks.  Rows >= total_logit of the outputs
+// (the pad row of an odd count included) are not written.
+__global__ void gather_tail_rows_kernel(const uint4* __restrict__ h, const uint4* __restrict__ att, const SegTable* __restrict__ t,
+                                        uint4* __restrict__ h_out, uint4* __restrict__ att_out, int chunks_per_row, int pk) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= t->total_logit * chunks_per_row) return;
+  int lr = i / chunks_per_row, c = i - lr * chunks_per_row;
+  const size_t src_row = (size_t)logit_src_row(t, lr), row_bytes = (size_t)chunks_per_row << 4;
+  h_out[i] = h[src_row * chunks_per_row + c];
+  const size_t s = pk ? ats_pk_byte(src_row, (size_t)c << 4, row_bytes) >> 4 : src_row * chunks_per_row + c;
+  const size_t d = pk ? ats_pk_byte((size_t)lr, (size_t)c << 4, row_bytes) >> 4 : (size_t)i;
+  att_out[d] = att[s];
 }
 
 int ats_gather_logit_rows(const void* h, const SegTable& t, const SegTable* dt, void* out, int hidden, int dtype, hipStream_t st) {
@@ -362,6 +382,18 @@ int ats_gather_logit_rows(const void* h, const SegTable& t, const SegTable* dt, 
   int total = t.total_logit * cpr;
   if (total <= 0) return ATSPEED_OK;
   gather_logit_rows_kernel<<<(total + 255) / 256, 256, 0, st>>>((const uint4*)h, dt, (uint4*)out, cpr);
+  ATS_LAUNCH_CHECK();
+  return ATSPEED_OK;
+}
+
+int ats_gather_tail_rows(const void* h, const void* att, const SegTable& t, const SegTable* dt, void* h_out, void* att_out, int hidden, int dtype,
+                         hipStream_t st, int pk) {
+  const int row_bytes = hidden * (dtype == ATSPEED_F32 ? 4 : 2);
+  ATS_REQUIRE(row_bytes % 16 == 0 && (!pk || row_bytes % 64 == 0), ATSPEED_ERR_INVALID,
+              "gather_tail_rows: rows of %d bytes (whole 16-byte chunks; packed operands: whole 64-byte blocks)", row_bytes);
+  const int cpr = row_bytes / 16, total = t.total_logit * cpr;
+  if (total <= 0) return ATSPEED_OK;
+  gather_tail_rows_kernel<<<(total + 255) / 256, 256, 0, st>>>((const uint4*)h, (const uint4*)att, dt, (uint4*)h_out, (uint4*)att_out, cpr, pk);
   ATS_LAUNCH_CHECK();
   return ATSPEED_OK;
 }

@@ -42,6 +42,19 @@ namespace {
 // staged when the rows it expects to skip (from the target's recent accepted steps) outnumber that per expected extra phase
 constexpr int ATS_VERIFY_STAGED_TOKENS = 4096;
 constexpr int ATS_VERIFY_STAGED_PASS_TOKENS = 1024;
+// Row-pruned tail of the last layer: only a forward of more tokens than this runs the last layer's o_proj / gate_up /
+// down over its logit rows alone.  Measured (profiles/tail_rows_ab.txt section 1: one prefill forward of Llama-7B bf16, one logit row per
+// user, full and pruned form alternating in one process, median ms of 5-9 calls, spread = max - min of the full runs):
+//   tokens   100    188    336    454    696    902    1732   3392   6454   13784   26566
+//   full     4.797  5.959  7.788  8.435  12.322 13.332 21.105 36.228 65.847 135.824 255.000
+//   pruned   4.797  5.905  7.717  8.363  12.110 13.100 20.711 35.387 64.587 133.040 249.646
+//   spread   0.103  0.231  0.061  0.057  0.140  0.329  0.061  0.578  0.790  0.331   1.014
+// Up to 256 tokens every projection streams its weights whatever M is and nothing is gained (0.00-0.05 ms, inside the spread); from the first
+// size the ring kernels take (257 tokens) the pruned form is never slower than the full runs' spread and wins 0.9 % at 336 tokens, 1.7-2.3 %
+// from 696 on.  The staged rule's 4096 was the candidate; the table puts the boundary at the kernel families' own, 256.  The default is 512:
+// ONE user's forwards (at most 512 tokens: the one-user models' max_tokens and the graph replay's bound) stay launch for launch what they
+// were, which costs the 257-512 band its 0.07 ms; 696 tokens, the first measured size above, wins beyond the spread.
+constexpr int ATS_TAIL_ROWS_TOKENS = 512;
 struct SwDef { const char* name; const char* env; int dflt; };
 const SwDef kSwitches[ATS_N_SW] = {{"gemm_sk", "ATSPEED_GEMM_SK", 1},           {"gemm_sk_g", nullptr, 0},
                                    {"gemm_panel", "ATSPEED_GEMM_PANEL", 1},     {"gemm_force_mt", "ATSPEED_GEMM_FORCE_MT", 0},
@@ -49,7 +62,8 @@ const SwDef kSwitches[ATS_N_SW] = {{"gemm_sk", "ATSPEED_GEMM_SK", 1},           
                                    {"gemm_kcut", "ATSPEED_GEMM_KCUT", 2},       {"fuse_qkv_reduce", "ATSPEED_FUSE_QKV_REDUCE", 1},
                                    {"verify_staged", "ATSPEED_VERIFY_STAGED", 1},
                                    {"verify_staged_tokens", "ATSPEED_VERIFY_STAGED_TOKENS", ATS_VERIFY_STAGED_TOKENS},
-                                   {"verify_staged_pass_tokens", "ATSPEED_VERIFY_STAGED_PASS_TOKENS", ATS_VERIFY_STAGED_PASS_TOKENS}};
+                                   {"verify_staged_pass_tokens", "ATSPEED_VERIFY_STAGED_PASS_TOKENS", ATS_VERIFY_STAGED_PASS_TOKENS},
+                                   {"tail_rows_tokens", "ATSPEED_TAIL_ROWS_TOKENS", ATS_TAIL_ROWS_TOKENS}};
 std::atomic<int> g_switch[ATS_N_SW];
 std::once_flag g_switch_once;
 void switches_init() {
@@ -255,6 +269,7 @@ struct KvCache { void* k = nullptr; void* v = nullptr; };
 struct ActCtx {
   int cap_tok = 0, cap_rows = 0;
   void *h = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *act = nullptr, *gath = nullptr;
+  void* att_tail = nullptr;                      // [cap_rows][hidden] the logit rows of att, compact: the o_proj operand of a row-pruned last layer
   float* logits = nullptr;                       // [cap_rows][logits_ld]
   float* lse = nullptr;                          // [cap_rows]
   float* lse_part = nullptr; size_t lse_part_bytes = 0;   // [cap_rows][vocab tiles] (max, sum exp) partials of the fused lm_head epilogue
@@ -269,7 +284,8 @@ struct ActCtx {
   // 20-140 tokens and launch-bound); the segment table lives at a fixed device address so that it is data, not a kernel argument
   SegTable* segtab_dev = nullptr;
   hipStream_t cap_stream = nullptr;
-  typedef std::tuple<int, int, int, int, int, int> GraphKey;      // tokens, logit rows, segments, query tiles, tile rows, weight scheme (0 16-bit, 1 fp8, 2 fp4)
+  // tokens, logit rows, segments, query tiles, tile rows, weight scheme (0 16-bit, 1 fp8, 2 fp4), last layer's tail row-pruned (forward_prunes_tail)
+  typedef std::tuple<int, int, int, int, int, int, int> GraphKey;
   std::map<GraphKey, hipGraphExec_t> graphs;
   std::map<GraphKey, int> graph_seen;
   // optional per-GEMM hipEvent brackets (bench.py roofline): 0 qkv, 1 o_proj, 2 gate_up, 3 down, 4 lm_head
@@ -384,7 +400,7 @@ static size_t gemm_ws_for(const atspeed_llama_config& c, int max_tok, int max_ro
 
 static void act_free(ActCtx* cx) {
   if (!cx) return;
-  hipFree(cx->h); hipFree(cx->xn); hipFree(cx->qkv); hipFree(cx->att); hipFree(cx->act); hipFree(cx->gath);
+  hipFree(cx->h); hipFree(cx->xn); hipFree(cx->qkv); hipFree(cx->att); hipFree(cx->act); hipFree(cx->gath); hipFree(cx->att_tail);
   hipFree(cx->logits); hipFree(cx->lse); hipFree(cx->lse_part); hipFree(cx->ws); hipFree(cx->xq); hipFree(cx->sx); hipFree(cx->rowinfo); hipFree(cx->lora_u);
   hipFree(cx->row_cand); hipFree(cx->sk.ws); hipFree(cx->sk.cnt);
   for (hipEvent_t e : cx->prof_ev) hipEventDestroy(e);
@@ -420,6 +436,7 @@ static int ensure_act(atspeed_llama* m, int tok, int rows) {
   ATS_HIP(hipMalloc(&cx->att, T * H * e));
   ATS_HIP(hipMalloc(&cx->act, T * (size_t)c.ffn * e));
   ATS_HIP(hipMalloc(&cx->gath, (size_t)cx->cap_rows * H * e));
+  ATS_HIP(hipMalloc(&cx->att_tail, (size_t)cx->cap_rows * H * e));
   ATS_HIP(hipMalloc((void**)&cx->logits, (size_t)cx->cap_rows * m->logits_ld * sizeof(float)));
   ATS_HIP(hipMalloc((void**)&cx->lse, (size_t)cx->cap_rows * sizeof(float)));
   ATS_HIP(hipMalloc((void**)&cx->row_cand, (size_t)cx->cap_rows * ATSPEED_MAX_BEAMS * sizeof(int32_t)));
@@ -605,6 +622,21 @@ extern "C" int64_t atspeed_llama_rope_fused_launches(atspeed_llama* m, int32_t r
 
 extern "C" float* atspeed_llama_logits(atspeed_llama* m) { return m && m->act ? m->act->logits : nullptr; }
 extern "C" int32_t atspeed_llama_logits_ld(const atspeed_llama* m) { return m ? m->logits_ld : 0; }
+// the first `bytes` of one of the handle's buffers to dst, ordered on the stream (tests compare what two forms of a forward left)
+extern "C" int atspeed_llama_read(atspeed_llama* m, int32_t what, int32_t index, void* dst, size_t bytes, void* stream) {
+  ATS_REQUIRE(m && m->act && dst, ATSPEED_ERR_INVALID, "llama_read: null argument");
+  const void* src = nullptr; size_t cap = 0;
+  if (what == ATSPEED_READ_LOGITS) { src = m->act->logits; cap = (size_t)m->act->cap_rows * m->logits_ld * sizeof(float); }
+  else if (what == ATSPEED_READ_LSE) { src = m->act->lse; cap = (size_t)m->act->cap_rows * sizeof(float); }
+  else if (what == ATSPEED_READ_HIDDEN) { src = m->act->h; cap = (size_t)m->act->cap_tok * m->cfg.hidden * m->esz; }
+  else if (what == ATSPEED_READ_BATCH_K || what == ATSPEED_READ_BATCH_V) {
+    ATS_REQUIRE(index >= 0 && index < (int)m->kv_pool.size(), ATSPEED_ERR_INVALID, "llama_read: the pool holds %d caches, not %d", (int)m->kv_pool.size(), index + 1);
+    src = what == ATSPEED_READ_BATCH_K ? m->kv_pool[index].k : m->kv_pool[index].v; cap = (size_t)m->cfg.n_layers * m->layer_kv_bytes;
+  }
+  ATS_REQUIRE(src && bytes <= cap, ATSPEED_ERR_INVALID, "llama_read: buffer %d holds %zu bytes, %zu asked", what, cap, bytes);
+  ATS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return ATSPEED_OK;
+}
 
 // The quantised copies of every layer, made by `quant` (allocates one projection's copy and scales, launches its quantiser on st).  They are
 // built aside and reach *dst only after the last quantiser has run: on any failure the copies made so far are freed and the model is as before.
@@ -747,6 +779,21 @@ extern "C" int64_t atspeed_llama_lora_launches(atspeed_llama* m, int32_t reset) 
 
 // One forward over the tokens of every segment (user) of the table.  Logits of each segment's last n_logit rows land
 // in act->logits rows [logit_row0, ..) (or in logits_out), their log-sum-exp in act->lse.
+// What act->h holds afterwards is NOT part of the contract and nothing reads it (no hidden-state export, lora_shrink reads it only inside
+// the forward, the teacher path and the tests read logits): after an ordinary forward it is the residual stream behind the last layer, after
+// a row-pruned one (forward_prunes_tail) the residual stream in front of the last layer's o_proj -- the last layer's output then exists
+// only for the logit rows, in act->gath.
+//
+// Row-pruned tail: a token row that gets no logits is needed in the LAST layer only for its K and V, which the qkv projection scatters to the
+// cache.  Where the rule below holds, the last layer's o_proj, post-attention norm, gate_up, SwiGLU and down run over the R logit rows alone
+// (gathered from act->att / act->h into act->att_tail / act->gath); qkv, RoPE, the KV scatter and the attention run over all T rows as in
+// every layer, so the caches are bit for bit what the full forward leaves.  Only the last layer: row r's K/V in layer l needs row r's whole
+// output of layer l - 1.  The rule: a 16-bit or fp32 target without adapter and without W8A8 / W4A8 copies (their kernels are chosen by the
+// forward's token count and their layer bodies carry xq_ready state: left on the full path, as staged verification leaves them), at most half
+// of the rows get logits, and the forward holds more than "tail_rows_tokens" tokens (below, a projection is bound by its weight stream).
+static bool forward_prunes_tail(const atspeed_llama* m, const SegTable& t) {
+  return m->fp8.empty() && m->fp4.empty() && m->lora.empty() && 2 * t.total_logit <= t.total_tok && t.total_tok > ats_switch(ATS_SW_TAIL_ROWS_TOKENS);
+}
 static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTable* dtab, float* logits_out, hipStream_t st,
                               const unsigned char* tile_store, int logit_row_off);
 
@@ -781,7 +828,8 @@ static int llama_forward_segs(atspeed_llama* m, const SegTable& t, float* logits
   const int use_graphs = ats_switch(ATS_SW_GRAPHS);                // (atspeed_set_switch("graphs", 1): the tests compare both modes in one process)
   constexpr int graph_max_tok = 512;
   if (use_graphs && !m->prof_on && logits_out == nullptr && logit_row_off == 0 && T <= graph_max_tok) {
-    const ActCtx::GraphKey key(T, t.total_logit, t.n, t.n_qtiles, t.qtile_rows, !m->fp4.empty() ? 2 : m->fp8.empty() ? 0 : 1);
+    const ActCtx::GraphKey key(T, t.total_logit, t.n, t.n_qtiles, t.qtile_rows, !m->fp4.empty() ? 2 : m->fp8.empty() ? 0 : 1,
+                               forward_prunes_tail(m, t) ? 1 : 0);
     auto it = cx->graphs.find(key);
     if (it == cx->graphs.end() && cx->graphs.size() < 64 && ++cx->graph_seen[key] >= 2) {   // a shape seen twice recurs (K + dl*DK tokens)
       g_ats_lazy_allocs++;                             // the capture stream (first time) and this shape's graph
@@ -925,6 +973,18 @@ extern "C" int atspeed_segs_gather_logit_rows(const void* h, int32_t hidden, int
   SegTable t{}; const SegTable* dt = nullptr;
   ATS_TRY(segs_table("segs_gather_logit_rows", 0, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
   return ATS_KD(dtype, ats_gather_logit_rows(h, t, dt, out, hidden, dtype, (hipStream_t)stream));
+}
+
+// the same rows of h (row-major) and of att (packed = 1: in the packed operand layout) to h_out / att_out in one launch (gather_tail_rows_kernel);
+// tests/test_tail_rows_gpu.py::test_gather_guard_band
+extern "C" int atspeed_segs_gather_tail_rows(const void* h, const void* att, int32_t hidden, int32_t dtype, int32_t packed, void* h_out, void* att_out,
+                                             ATS_SEGS_PARAMS, void* stream) {
+  ATS_REQUIRE(h && att && h_out && att_out && hidden > 0 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID, "segs_gather_tail_rows: bad arguments");
+  ATS_REQUIRE((((uintptr_t)h | (uintptr_t)att | (uintptr_t)h_out | (uintptr_t)att_out) & 15) == 0, ATSPEED_ERR_INVALID,
+              "segs_gather_tail_rows: buffers must be 16-byte aligned");
+  SegTable t{}; const SegTable* dt = nullptr;
+  ATS_TRY(segs_table("segs_gather_tail_rows", 0, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
+  return ATS_KD(dtype, ats_gather_tail_rows(h, att, t, dt, h_out, att_out, hidden, dtype, (hipStream_t)stream, packed ? 1 : 0));
 }
 
 // out[row] = {kcache, vcache of the row's segment, clamp(pos, 0, max_pos - 1), slot} (row_info_kernel; record layout: the header); ::test_embed_gather_row_info

@@ -96,6 +96,55 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
   const bool lora = !m->lora.empty();
   const bool qkv_rope_fused = f4 || lora ? false : qkv_in_fp8 ? ats_gemm_fp8_qkv_rope_applies(T, H, m->head_dim) : ats_gemm_qkv_rope_applies(T, H, m->head_dim, dt);
   if (qkv_rope_fused) ATS_TRY(ats_row_info(t, dtab, cx->rowinfo, c.max_slots, st));
+  // the row-pruned tail of the last layer (engine.hip: forward_prunes_tail): its back part runs over the R logit rows only
+  const bool prune_tail = forward_prunes_tail(m, t);
+  const int R = t.total_logit;
+  // A layer behind its attention, over the M rows of (h: residual stream, att: attention output): o_proj + post-attention norm, gate_up + SwiGLU,
+  // down (+ the next layer's input norm).  Every layer calls it on (T, cx->h, cx->att); the pruned last layer on (R, cx->gath, cx->att_tail).
+  // xn, act, xq / sx are used from row 0 either way.
+  auto layer_back = [&](int l, int M, void* h, const void* att) -> int {
+    const atspeed_llama_layer_weights& w = m->layers[l];
+    { ProfBracket pb(m, 1, M, st);     // h += att Wo^T ; xn = rmsnorm(h) * post_norm
+      if (o_in_fp8) {
+        m->fp8_cnt[1]++;
+        ATS_TRY(ats_quant_rows_fp8(att, M, H, H, cx->xq, cx->sx, st, pk));
+        ATS_TRY(ats_gemm_fp8_resid_norm(cx->xq, cx->sx, m->fp8[l].wo, m->fp8[l].so, h, M, H, H, H, w.post_norm, f8_gu ? nullptr : cx->xn,
+                                        f8_gu ? cx->xq : nullptr, f8_gu ? cx->sx : nullptr, c.rms_eps, cx->ws, cx->ws_bytes, st, pk));
+        xq_ready = f8_gu;
+      } else {
+        m->other_cnt[1]++;
+        ATS_TRY(ats_gemm_resid_norm(att, w.wo, h, M, H, H, H, H, dt, w.post_norm, cx->xn, c.rms_eps, cx->ws, cx->ws_bytes, st, pk, sk));
+        xq_ready = false;
+      } }
+    { ProfBracket pb(m, 2, M, st);
+      if (gu_in_fp8) {
+        m->fp8_cnt[2]++;
+        ATS_TRY(proj_fp8(m, xq_ready ? nullptr : cx->xn, m->fp8[l].wgu, m->fp8[l].sgu, cx->act, M, 2 * c.ffn, H, c.ffn, EPI_SWIGLU, st));
+      } else {
+        m->other_cnt[2]++;
+        ATS_TRY(ats_gemm(cx->xn, w.wgu, cx->act, M, 2 * c.ffn, H, H, c.ffn, dt, EPI_SWIGLU, cx->ws, cx->ws_bytes, st, pk, sk));
+      } }
+    { ProfBracket pb(m, 3, M, st);     // h += act Wd^T ; xn = rmsnorm(h) * next layer's input_norm
+      (down_in_fp8 ? m->fp8_cnt : m->other_cnt)[3]++;
+      if (down_in_fp8) {
+        if (l + 1 < c.n_layers) {
+          ATS_TRY(ats_quant_rows_fp8(cx->act, M, c.ffn, c.ffn, cx->xq, cx->sx, st, pk));
+          ATS_TRY(ats_gemm_fp8_resid_norm(cx->xq, cx->sx, m->fp8[l].wd, m->fp8[l].sd, h, M, H, c.ffn, H, m->layers[l + 1].input_norm,
+                                          f8_qkv ? nullptr : cx->xn, f8_qkv ? cx->xq : nullptr, f8_qkv ? cx->sx : nullptr, c.rms_eps, cx->ws, cx->ws_bytes, st, pk));
+          xq_ready = f8_qkv;
+        } else {
+          ATS_TRY(proj_fp8(m, cx->act, m->fp8[l].wd, m->fp8[l].sd, h, M, H, c.ffn, H, EPI_RESID, st));
+          xq_ready = false;
+        }
+      } else if (l + 1 < c.n_layers) {
+        ATS_TRY(ats_gemm_resid_norm(cx->act, w.wd, h, M, H, c.ffn, c.ffn, H, dt, m->layers[l + 1].input_norm, cx->xn, c.rms_eps,
+                                    cx->ws, cx->ws_bytes, st, pk, sk));
+        xq_ready = false;
+      } else {
+        ATS_TRY(ats_gemm(cx->act, w.wd, h, M, H, c.ffn, c.ffn, H, dt, EPI_RESID, cx->ws, cx->ws_bytes, st, pk, sk));
+      } }
+    return ATSPEED_OK;
+  };
   for (int l = 0; l < c.n_layers; ++l) {
     const atspeed_llama_layer_weights& w = m->layers[l];
     const size_t loff = (size_t)l * m->layer_kv_bytes;
@@ -135,49 +184,16 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
     else
       ATS_TRY(rope_pass(m, l, t, dtab, loff, st));
     ATS_TRY(ats_tree_attention_segs(cx->qkv, 3 * H, t, dtab, loff, m->vis_words, cx->att, H, c.n_heads, m->head_dim, dt, st, 0, pk));
-    { ProfBracket pb(m, 1, T, st);     // h += att Wo^T ; xn = rmsnorm(h) * post_norm
-      if (o_in_fp8) {
-        m->fp8_cnt[1]++;
-        ATS_TRY(ats_quant_rows_fp8(cx->att, T, H, H, cx->xq, cx->sx, st, pk));
-        ATS_TRY(ats_gemm_fp8_resid_norm(cx->xq, cx->sx, m->fp8[l].wo, m->fp8[l].so, cx->h, T, H, H, H, w.post_norm, f8_gu ? nullptr : cx->xn,
-                                        f8_gu ? cx->xq : nullptr, f8_gu ? cx->sx : nullptr, c.rms_eps, cx->ws, cx->ws_bytes, st, pk));
-        xq_ready = f8_gu;
-      } else {
-        m->other_cnt[1]++;
-        ATS_TRY(ats_gemm_resid_norm(cx->att, w.wo, cx->h, T, H, H, H, H, dt, w.post_norm, cx->xn, c.rms_eps, cx->ws, cx->ws_bytes, st, pk, sk));
-        xq_ready = false;
-      } }
-    { ProfBracket pb(m, 2, T, st);
-      if (gu_in_fp8) {
-        m->fp8_cnt[2]++;
-        ATS_TRY(proj_fp8(m, xq_ready ? nullptr : cx->xn, m->fp8[l].wgu, m->fp8[l].sgu, cx->act, T, 2 * c.ffn, H, c.ffn, EPI_SWIGLU, st));
-      } else {
-        m->other_cnt[2]++;
-        ATS_TRY(ats_gemm(cx->xn, w.wgu, cx->act, T, 2 * c.ffn, H, H, c.ffn, dt, EPI_SWIGLU, cx->ws, cx->ws_bytes, st, pk, sk));
-      } }
-    { ProfBracket pb(m, 3, T, st);     // h += act Wd^T ; xn = rmsnorm(h) * next layer's input_norm
-      (down_in_fp8 ? m->fp8_cnt : m->other_cnt)[3]++;
-      if (down_in_fp8) {
-        if (l + 1 < c.n_layers) {
-          ATS_TRY(ats_quant_rows_fp8(cx->act, T, c.ffn, c.ffn, cx->xq, cx->sx, st, pk));
-          ATS_TRY(ats_gemm_fp8_resid_norm(cx->xq, cx->sx, m->fp8[l].wd, m->fp8[l].sd, cx->h, T, H, c.ffn, H, m->layers[l + 1].input_norm,
-                                          f8_qkv ? nullptr : cx->xn, f8_qkv ? cx->xq : nullptr, f8_qkv ? cx->sx : nullptr, c.rms_eps, cx->ws, cx->ws_bytes, st, pk));
-          xq_ready = f8_qkv;
-        } else {
-          ATS_TRY(proj_fp8(m, cx->act, m->fp8[l].wd, m->fp8[l].sd, cx->h, T, H, c.ffn, H, EPI_RESID, st));
-          xq_ready = false;
-        }
-      } else if (l + 1 < c.n_layers) {
-        ATS_TRY(ats_gemm_resid_norm(cx->act, w.wd, cx->h, T, H, c.ffn, c.ffn, H, dt, m->layers[l + 1].input_norm, cx->xn, c.rms_eps,
-                                    cx->ws, cx->ws_bytes, st, pk, sk));
-        xq_ready = false;
-      } else {
-        ATS_TRY(ats_gemm(cx->act, w.wd, cx->h, T, H, c.ffn, c.ffn, H, dt, EPI_RESID, cx->ws, cx->ws_bytes, st, pk, sk));
-      } }
+    if (prune_tail && l + 1 == c.n_layers) {     // nobody reads the other rows of the last layer's output (their K / V are in the cache)
+      if (R == 0) break;
+      ATS_TRY(ats_gather_tail_rows(cx->h, cx->att, t, dtab, cx->gath, cx->att_tail, H, dt, st, pk));
+      ATS_TRY(layer_back(l, R, cx->gath, cx->att_tail));
+    } else {
+      ATS_TRY(layer_back(l, T, cx->h, cx->att));
+    }
   }
-  if (t.total_logit > 0) {
-    const int R = t.total_logit;
-    ATS_TRY(ats_gather_logit_rows(cx->h, t, dtab, cx->gath, H, dt, st));
+  if (R > 0) {
+    if (!prune_tail) ATS_TRY(ats_gather_logit_rows(cx->h, t, dtab, cx->gath, H, dt, st));     // (the pruned tail left the last layer's output in gath)
     ATS_TRY(ats_rmsnorm(cx->gath, m->final_norm, cx->xn, R, H, c.rms_eps, dt, st, pk));
     float* lo = logits_out ? logits_out : cx->logits + (size_t)logit_row_off * m->logits_ld;
     float* lse = cx->lse + logit_row_off;

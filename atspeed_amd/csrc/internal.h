@@ -75,6 +75,7 @@ enum { ATS_SW_GEMM_SK = 0,        // "gemm_sk"       ATSPEED_GEMM_SK (1): ring k
        ATS_SW_VERIFY_STAGED,      // "verify_staged" ATSPEED_VERIFY_STAGED (1): lock-step greedy rounds verify block by block -- 0 never, 1 rounds above the threshold, 2 always
        ATS_SW_VERIFY_STAGED_TOKENS, // "verify_staged_tokens" ATSPEED_VERIFY_STAGED_TOKENS: the threshold T* -- only a round whose packed target forward would exceed it is staged
        ATS_SW_VERIFY_STAGED_PASS_TOKENS, // "verify_staged_pass_tokens" ATSPEED_VERIFY_STAGED_PASS_TOKENS: rows a staged round must expect to skip per phase it expects to add; 0 = T* alone decides
+       ATS_SW_TAIL_ROWS_TOKENS,   // "tail_rows_tokens" ATSPEED_TAIL_ROWS_TOKENS: a forward of more tokens runs the last layer's o_proj / MLP over its logit rows only -- 0 always, a huge value never
        ATS_N_SW };
 int ats_switch(int id);
 

@@ -13,6 +13,9 @@ int ats_rope_kv_segs(void* qkv, const SegTable& t, const SegTable* dt, const flo
                      int n_heads, int head_dim, int max_pos, int dtype, hipStream_t st);
 int ats_row_info(const SegTable& t, const SegTable* dt, RowInfo* out, int max_pos, hipStream_t st);
 int ats_gather_logit_rows(const void* h, const SegTable& t, const SegTable* dt, void* out, int hidden, int dtype, hipStream_t st);
+// the same rows of h (row-major) and of att (a GEMM operand: packed when pk) to consecutive rows of h_out / att_out, in one launch
+int ats_gather_tail_rows(const void* h, const void* att, const SegTable& t, const SegTable* dt, void* h_out, void* att_out, int hidden, int dtype,
+                         hipStream_t st, int pk = 0);
 int ats_rmsnorm(const void* x, const void* w, void* y, int rows, int hidden, float eps, int dtype, hipStream_t st, int pk = 0);   // pk: y in the packed operand layout
 // row-major [rows][row_bytes] -> packed operand layout (common.h ats_pk_byte) or back; out of place, row_bytes % 64 == 0
 int ats_pack_rows(const void* src, void* dst, int rows, int row_bytes, int to_packed, hipStream_t st);

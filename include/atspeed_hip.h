@@ -148,6 +148,13 @@ int atspeed_llama_forward_batch(atspeed_llama* m, int32_t n, const int32_t* cons
                                 const int32_t* const* slots_dev, const uint64_t* const* vis_bits_dev, const int32_t* n_tokens,
                                 const int32_t* n_slots_visible, const int32_t* n_logit_rows, float* logits_out_dev, void* stream);
 float* atspeed_llama_logits(atspeed_llama* m);
+/* Copy the first `bytes` of one of the handle's buffers to dst_dev, ordered on `stream` (what tests compare after a forward): the logits buffer
+ * (atspeed_llama_logits()), the log-sum-exp over the whole vocabulary of each logit row of the last forward (fp32 [n_logit_rows]), or the K / V
+ * arena `index` of the pool atspeed_llama_forward_batch gives its sequences ([layers][max_slots][hidden] in the model's type each; zero-filled
+ * when created), or the residual-stream buffer [tokens][hidden] in the model's type: after a forward it holds the last layer's output, after a
+ * row-pruned one (switch "tail_rows_tokens") the residual stream in front of the last layer's o_proj -- no part of the engine reads it.  More bytes than the buffer holds, or an arena the pool does not have: ATSPEED_ERR_INVALID. */
+enum { ATSPEED_READ_LOGITS = 0, ATSPEED_READ_LSE = 1, ATSPEED_READ_BATCH_K = 2, ATSPEED_READ_BATCH_V = 3, ATSPEED_READ_HIDDEN = 4 };
+int atspeed_llama_read(atspeed_llama* m, int32_t what, int32_t index, void* dst_dev, size_t bytes, void* stream);
 /* hipEvent brackets around the forward's five GEMM kinds (0 qkv, 1 o_proj, 2 gate_up+SwiGLU, 3 down,
  * 4 lm_head), recorded on the launch stream.  Returns the sums since the last reset in ms_out[5] /
  * count_out[5] / rows_out[5] (sum of M); enable = 1/0 switches the brackets on/off and resets,
@@ -550,7 +557,10 @@ int atspeed_gemm_path_counters(int64_t* out, int32_t n, int32_t reset);
  * hook, 0), "gemm_panel" (ATSPEED_GEMM_PANEL, 1), "gemm_force_mt" (ATSPEED_GEMM_FORCE_MT, 0), "graphs" (ATSPEED_GRAPHS, 0),
  * "fuse_qkv_rope" (ATSPEED_FUSE_QKV_ROPE, 1), "fuse_qkv_reduce" (ATSPEED_FUSE_QKV_REDUCE, 1), "gemm_kcut" (ATSPEED_GEMM_KCUT, 2),
  * "verify_staged" (ATSPEED_VERIFY_STAGED, 1), "verify_staged_tokens" (ATSPEED_VERIFY_STAGED_TOKENS, the measured threshold T*),
- * "verify_staged_pass_tokens" (ATSPEED_VERIFY_STAGED_PASS_TOKENS, the measured cost of a phase in tokens); meanings in INTEGRATION.md.  Unknown name: ATSPEED_ERR_INVALID. */
+ * "verify_staged_pass_tokens" (ATSPEED_VERIFY_STAGED_PASS_TOKENS, the measured cost of a phase in tokens),
+ * "tail_rows_tokens" (ATSPEED_TAIL_ROWS_TOKENS, 512: a forward of more tokens, at most half of whose rows get logits, runs the last layer's
+ * o_proj / gate_up / down over its logit rows only -- 0 every such forward, a huge value none; 16-bit and fp32 models without W8A8 / W4A8
+ * copies and without adapter); meanings in INTEGRATION.md.  Unknown name: ATSPEED_ERR_INVALID. */
 int atspeed_set_switch(const char* name, int32_t value);
 int atspeed_get_switch(const char* name, int32_t* value_out);
 /* atspeed_gemm / atspeed_gemm_fp8 on operands in the packed layout (a / xq and w / wq through atspeed_pack_rows; K % 32 == 0, for fp8 K % 64 == 0):
@@ -646,6 +656,12 @@ int atspeed_segs_embed(const void* table_dev, int32_t hidden, int32_t vocab, int
 /* out = the LAST n_logit_rows[i] rows of every segment's rows of h [total_tok][hidden], segment after segment (a segment with 0 logit rows
  * contributes none); rows >= sum of n_logit_rows are not written.  Reads no per-segment array.  ::test_embed_gather_row_info */
 int atspeed_segs_gather_logit_rows(const void* h_dev, int32_t hidden, int32_t dtype, void* out_dev, ATSPEED_SEGMENTS, void* stream);
+/* The two gathers of a row-pruned last layer in one launch: the same rows as atspeed_segs_gather_logit_rows, of h [total_tok][hidden] (row-major)
+ * to h_out and of att [total_tok][hidden] to att_out; packed = 1: att and att_out are GEMM operands in the packed layout (atspeed_pack_rows;
+ * hidden * element size % 64 == 0, both buffers hold an even number of rows), else row-major.  Rows >= sum of n_logit_rows of either output,
+ * the pad row of an odd count included, are not written.  tests/test_tail_rows_gpu.py::test_gather_guard_band */
+int atspeed_segs_gather_tail_rows(const void* h_dev, const void* att_dev, int32_t hidden, int32_t dtype, int32_t packed, void* h_out_dev,
+                                  void* att_out_dev, ATSPEED_SEGMENTS, void* stream);
 /* out[row] = one 24-byte record per row, what the fused qkv epilogues load: { uint64 kc; uint64 vc; int32 pos; int32 slot; } = the row's
  * segment's kcache / vcache pointers, its position clamped to [0, max_pos - 1] (the rotation index) and its cache slot (reads pos, slots).
  * ::test_embed_gather_row_info */
