@@ -17,6 +17,7 @@ ATSPEED_F32, ATSPEED_BF16, ATSPEED_F16 = 0, 1, 2
 WEIGHTS_ROW_MAJOR, WEIGHTS_PACKED = 0, 1
 MAX_BEAMS, MAX_NEW_TOKENS, MAX_GAMMA = 64, 16, 8
 LORA_MAX_RANK = 64
+LORA_MAX_ADAPTERS = 16
 ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_CONSTRAINT, ERR_NO_DEVICE, ERR_FILTERED = -1, -2, -3, -4, -5, -6
 EPI_STORE, EPI_F32, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3
 MASK_BLOCK, MASK_ALLOW = 0, 1
@@ -37,6 +38,11 @@ class LoraLayer(C.Structure):
     _fields_ = [("a_q", C.c_void_p), ("b_q", C.c_void_p), ("a_k", C.c_void_p), ("b_k", C.c_void_p), ("a_v", C.c_void_p), ("b_v", C.c_void_p)]
 
 
+class LoraSlot(C.Structure):
+    """atspeed_lora_slot: one resident adapter of one layer as the segmented adapter kernels read it"""
+    _fields_ = [("a_cat", C.c_void_p), ("b_q", C.c_void_p), ("b_k", C.c_void_p), ("b_v", C.c_void_p), ("r16", C.c_int32), ("scaling", C.c_float)]
+
+
 class GenStats(C.Structure):
     _fields_ = [("n_run", C.c_int32), ("total_accept_steps", C.c_int32), ("accept_steps", C.c_int32 * MAX_NEW_TOKENS),
                 ("n_valid", C.c_int32), ("n_target_forwards", C.c_int32), ("n_draft_forwards", C.c_int32),
@@ -54,6 +60,13 @@ class SessionCounters(C.Structure):
 class SessionDone(C.Structure):
     _fields_ = [("ticket", C.c_int64), ("lane", C.c_int32), ("status", C.c_int32), ("rounds_queued", C.c_int64),
                 ("rounds_in_lane", C.c_int64)]
+
+
+class SessionUser(C.Structure):
+    """atspeed_session_user: everything a session's user brings (atspeed_session_submit_ex)"""
+    _fields_ = [("struct_size", C.c_size_t), ("prompt_ids_dev", C.c_void_p), ("prompt_len", C.c_int32), ("start_node", C.c_int32),
+                ("seed", C.c_uint32), ("out_tokens_dev", C.c_void_p), ("out_scores_dev", C.c_void_p), ("stats_host", C.POINTER(GenStats)),
+                ("masks", C.c_void_p), ("mask_user", C.c_int32), ("adapter", C.c_int32)]
 
 
 # every symbol include/atspeed_hip.h declares: (restype, argtypes)
@@ -93,6 +106,14 @@ SIGNATURES = {
     "atspeed_llama_lora_launches": (C.c_int64, [_P, _I]),
     "atspeed_lora_shrink": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
     "atspeed_segs_lora_rope_kv": (C.c_int, [_P, _P, _P, _P, _P, _I, _F, _P, _P, _SZ, _I, _I, _I, _I] + _SEGS + [_P]),
+    "atspeed_llama_add_lora": (C.c_int, [_P, _I, _F, C.POINTER(LoraLayer), _P, C.POINTER(_I)]),
+    "atspeed_llama_remove_lora": (C.c_int, [_P, _I]),
+    "atspeed_llama_lora_slots": (_I, [_P]),
+    "atspeed_llama_forward_batch_adapters": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "atspeed_decoder_set_adapter": (C.c_int, [_P, _I]),
+    "atspeed_session_submit_ex": (C.c_int, [_P, C.POINTER(SessionUser), C.POINTER(C.c_int64)]),
+    "atspeed_segs_lora_shrink_multi": (C.c_int, [_P, _P, C.POINTER(LoraSlot), _I, _P, _I, _F, _I, _P] + _SEGS + [_P]),
+    "atspeed_segs_lora_rope_kv_multi": (C.c_int, [_P, _P, C.POINTER(LoraSlot), _I, _P, _P, _SZ, _I, _I, _I, _I, _P] + _SEGS + [_P]),
     "atspeed_quant_rows_fp8": (C.c_int, [_P, _I, _I, _P, _P, _P]),
     "atspeed_quant_rows_fp8_packed": (C.c_int, [_P, _I, _I, _P, _P, _P]),
     "atspeed_gemm_fp8": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),

@@ -39,6 +39,10 @@ Item filters (`exclude_items=` / `allow_items=`, include/atspeed_hip.h "item fil
 generates after the prompt, e.g. an item's code tokens -- that the user must not be recommended, or the only ones it may be.  They become
 per-user node bitsets over the shared automaton (`_item_filters`, built on the device), so filtered users keep their place in lock-step
 batches and sessions; draft and target see the same bits, so BSSD under a filter is plain beam search under that filter.
+
+Resident adapters (`adapter=` / `adapters=`, include/atspeed_hip.h "several RESIDENT adapters on one model"): per user the name of one of the
+LoRA adapters `HipLlama.add_lora` keeps on the target, or None.  It becomes the slot in the user's segment of every target forward
+(`_adapter_slots`, `_set_adapters`; sessions carry it in the submit record), so users of different fine-tunes share a batch or a session.
 """
 from __future__ import annotations
 
@@ -274,13 +278,14 @@ def _set_decoders(decs, mode, num_beams: int, seeds, trace=None) -> None:
 
 
 def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allowed_tokens_fn, mode, who: str, trace=None,
-           filters=None, first_user: int = 0) -> SimpleNamespace:
+           filters=None, first_user: int = 0, adapters=None) -> SimpleNamespace:
     """The device path's call setup, for one user or a lock-step batch: prompts on the device, each user's compiled constraint (the mask
     functions look at the prompt -- position of "Response:", data.py:97-102 -- with one D2H copy per call, where the reference does one per beam
     per step, generation_trie.py:94, data.py:98), the ONE automaton they share (they may differ in their start node only), one decoder per
     user (lane), set to the call's sampling mode (user u draws from stream seed + u) and, for BSSD (`trace` not None), its decision trace.
     `filters` (`_filter_specs`): the users' item filters are built and set on their decoders; the caller clears them (`_clear_filters`)
-    when its library call has returned."""
+    when its library call has returned.  `adapters` (`_adapter_slots`): the users' resident adapter slots, None = nobody names one; set on
+    every call."""
     dev = target.device
     if filters is not None:
         _check_filter_constraint(prefix_allowed_tokens_fn, who)
@@ -292,6 +297,7 @@ def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allo
     dfsm = _DeviceFSM.get(fsms[0], target.dims.vocab_size)
     decs = [_Decoder.get(target, draft, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
     _set_decoders(decs, mode, target.generation_config.num_beams, [mode[2] + u for u in range(len(decs))], trace)
+    _set_adapters(decs, adapters)
     owners = []
     if filters is not None:
         owners, per_user = _item_filters(dfsm, [f.start for f in fsms], filters, dev, who, first_user)
@@ -386,6 +392,43 @@ def _clear_filters(decs) -> None:
     lib = _lib.load()
     for d in decs:
         lib.atspeed_decoder_set_node_mask(d.handle, None, 0)
+
+
+# ---------------------------------------------------------------- resident adapters (HipLlama.add_lora), one per user
+def _adapter_slots(target, adapters, n: int, per_user: bool, who: str):
+    """The call's `adapter=` (one name or None) / `adapters=` (a list with one name or None per user) -> None when no user names an
+    adapter, else the target's slot per user.  Wrong list length: ValueError; a name the target does not hold: KeyError naming the ones it does."""
+    if not per_user:
+        adapters = None if adapters is None else [adapters]
+    if adapters is None:
+        return None
+    if isinstance(adapters, str) or len(adapters) != n:
+        raise ValueError(f"{who}: adapters needs one name (or None) per user: "
+                         f"{'a single name' if isinstance(adapters, str) else len(adapters)} for {n} users")
+    if all(a is None for a in adapters):
+        return None
+    known = getattr(target, "adapters", {})
+    for a in adapters:
+        if a is not None and a not in known:
+            raise KeyError(f"{who}: no resident adapter named {a!r} on the target model (HipLlama.add_lora); resident: {sorted(known)}")
+    return [0 if a is None else int(known[a]) for a in adapters]
+
+
+def _refuse_host_adapters(slots, who: str) -> None:
+    if slots is not None:
+        raise NotImplementedError(f"{who}: adapter= / adapters= run on the device path only (a mask that can compile() itself, no extra "
+                                  "logits_processor); on the host path give the model one adapter with load_lora")
+
+
+def _set_adapters(decs, slots) -> None:
+    """Every call sets its decoders' adapter, to 0 when it names none: a cached decoder must not keep an earlier call's.  The library is told
+    only when the slot changes (`adapter_slot`: what the decoder holds; None after a session used it, which sets its lanes' itself)."""
+    lib = _lib.load()
+    for i, d in enumerate(decs):
+        slot = slots[i] if slots is not None else 0
+        if getattr(d, "adapter_slot", 0) != slot:
+            _lib.check(lib.atspeed_decoder_set_adapter(d.handle, slot))
+            d.adapter_slot = slot
 
 
 def _host_call(host_fn, models, inputs: Dict, args, logits_processor, prefix_allowed_tokens_fn, mode) -> Dict:
@@ -515,17 +558,19 @@ def _bssd_stats(st, k: int) -> Dict:
 @torch.no_grad()
 def BSSD(target_model, draft_model, inputs: Dict, gamma: int, max_new_tokens: int,
          logits_processor=None, prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False,
-         exclude_items=None, allow_items=None) -> Dict:
+         exclude_items=None, allow_items=None, adapter=None) -> Dict:
     mode = _mode(seed, target_model, draft_model)
     filters = _filter_specs(1, exclude_items, allow_items, False, "BSSD")
+    slots = _adapter_slots(target_model, adapter, 1, False, "BSSD")
     if _host_path(logits_processor, prefix_allowed_tokens_fn):
         _refuse_host_filters(filters, "BSSD")
+        _refuse_host_adapters(slots, "BSSD")
         from .hostmask import bssd_host_mask
         return _host_call(bssd_host_mask, (target_model, draft_model), inputs, (int(gamma), int(max_new_tokens)), logits_processor,
                           prefix_allowed_tokens_fn, mode)
     k = int(target_model.generation_config.num_beams)                 # beamSD.py:482
     dk = int(draft_model.generation_config.num_beams)                 # beamSD.py:483
-    c = _setup(target_model, draft_model, [inputs], prefix_allowed_tokens_fn, mode, "BSSD", trace_decisions, filters)
+    c = _setup(target_model, draft_model, [inputs], prefix_allowed_tokens_fn, mode, "BSSD", trace_decisions, filters, adapters=slots)
     out, stats = _one_user_call(_lib.load().atspeed_bssd_generate, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     out.update(_bssd_stats(stats, k))
     return out
@@ -583,14 +628,18 @@ class BSSDSession:
         else:
             self._decs = [_Decoder(self.target, self.draft, self.max_prompt) for _ in range(self.n_lanes)]
         _set_decoders(self._decs, self.mode, self.k, [self.mode[2]] * self.n_lanes, trace=False)    # the user's own seed comes with its admission
+        for d in self._decs:               # ... and so does its adapter: a lane starts without one (a cached decoder may hold an earlier call's),
+            _lib.check(lib.atspeed_decoder_set_adapter(d.handle, 0))     # the library sets and clears it per user, a later call sets it anew
+            d.adapter_slot = None
         with torch.cuda.device(self.dev):
             self._owner = _lib.Handle.create("atspeed_session_destroy", lib.atspeed_session_create,
                                              (C.c_void_p * self.n_lanes)(*[d.handle for d in self._decs]), self.n_lanes, self._dfsm.handle,
                                              self.gamma, self.max_new_tokens, self.k, self.dk, self.max_prompt, _lib.stream_ptr(self.dev))
 
     def _submit(self, prompt: torch.Tensor, fsm: ConstraintFSM, ids32: torch.Tensor, toks: torch.Tensor, scores: torch.Tensor, seed=None,
-                mask=None, mask_owners=()) -> int:
-        """`mask`: None or (masks pointer, user index) of the user's item filter; `mask_owners` stay alive until its ticket has come back"""
+                mask=None, mask_owners=(), adapter: int = 0) -> int:
+        """`mask`: None or (masks pointer, user index) of the user's item filter; `mask_owners` stay alive until its ticket has come back;
+        `adapter`: the user's resident adapter slot on the target (0 = none)"""
         if self._closed:
             raise RuntimeError("BSSDSession is closed")
         if self._fsm0 is None:
@@ -602,18 +651,22 @@ class BSSDSession:
         user = SimpleNamespace(prompt=prompt, ids32=ids32, toks=toks, scores=scores, stats=_lib.GenStats(), t0=time.time(), mask_owners=mask_owners)
         ticket = C.c_int64(0)
         # host only: the library queues the user and launches nothing, so no device guard (one per user would be the call's largest cost)
-        _lib.check(_lib.load().atspeed_session_submit_masked(self._owner.ptr, ids32.data_ptr(), int(prompt.numel()), fsm.start, int(seed) & 0xFFFFFFFF,
-                                                             toks.data_ptr(), scores.data_ptr(), C.byref(user.stats),
-                                                             mask[0] if mask else None, mask[1] if mask else 0, C.byref(ticket)))
+        rec = _lib.SessionUser(C.sizeof(_lib.SessionUser), ids32.data_ptr(), int(prompt.numel()), fsm.start, int(seed) & 0xFFFFFFFF,
+                               toks.data_ptr(), scores.data_ptr(), C.pointer(user.stats), mask[0] if mask else None, mask[1] if mask else 0,
+                               int(adapter))
+        _lib.check(_lib.load().atspeed_session_submit_ex(self._owner.ptr, C.byref(rec), C.byref(ticket)))
         self._submitted += 1
         self._users[ticket.value] = user
         return ticket.value
 
     @torch.no_grad()
-    def submit(self, inputs: Dict, seed=None, exclude_items=None, allow_items=None) -> int:
+    def submit(self, inputs: Dict, seed=None, exclude_items=None, allow_items=None, adapter=None) -> int:
         """Queue one user; no forward is launched.  Returns its ticket.  `exclude_items` / `allow_items`: the user's item filter (a list of
-        token sequences; its node bitset is built here and follows the user to whichever lane it lands on)."""
+        token sequences; its node bitset is built here and follows the user to whichever lane it lands on).  `adapter`: the name of the
+        resident adapter (`HipLlama.add_lora` on the target) the user runs under, None = none; it follows the user likewise, and must stay
+        resident until the user's ticket has come back."""
         filters = _filter_specs(1, exclude_items, allow_items, False, "BSSDSession.submit")
+        slots = _adapter_slots(self.target, adapter, 1, False, "BSSDSession.submit")
         prompt = _prompt_row(inputs).to(self.dev)
         fsm = _compile_constraint(self.fn, prompt.tolist())
         with torch.cuda.device(self.dev):
@@ -631,7 +684,7 @@ class BSSDSession:
                 raise ValueError("BSSDSession needs one shared constraint automaton (only the start node may differ per user)")
             owners, per_user = _item_filters(self._dfsm, [fsm.start], filters, self.dev, "BSSDSession.submit", self._submitted)
             mask = per_user[0]
-        return self._submit(prompt, fsm, ids32, toks, scores, seed, mask, tuple(owners))
+        return self._submit(prompt, fsm, ids32, toks, scores, seed, mask, tuple(owners), slots[0] if slots is not None else 0)
 
     def _finished(self, buf, n: int, assemble: bool):
         out, now = [], time.time()
@@ -691,7 +744,7 @@ class BSSDSession:
         return False
 
 
-def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes: int, filters=None):
+def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes: int, filters=None, adapters=None):
     """`BSSD_batch(..., lanes=N)`: the whole list through one session of N lanes, results in list order.  The prompts, token blocks and
     scores are the batch call's buffers (one allocation each) and the result tensors come from its one assemble launch."""
     if not inputs_list:
@@ -711,7 +764,8 @@ def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tok
             _check_filter_constraint(prefix_allowed_tokens_fn, "BSSD_batch")
             ses._create(fsms[0])
             owners, per_user = _item_filters(ses._dfsm, [f.start for f in fsms], filters, dev, "BSSD_batch")
-        tickets = [ses._submit(p, f, i32, toks[u], scores[u], mask=per_user[u]) for u, (p, f, i32) in enumerate(zip(prompts, fsms, ids32))]
+        tickets = [ses._submit(p, f, i32, toks[u], scores[u], mask=per_user[u], adapter=adapters[u] if adapters is not None else 0)
+                   for u, (p, f, i32) in enumerate(zip(prompts, fsms, ids32))]
         done = dict(ses.drain(_assemble=False))
         del owners
         wall = time.time() - t0
@@ -726,7 +780,7 @@ def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tok
 @torch.no_grad()
 def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_tokens: int,
                prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False, lanes: Optional[int] = None,
-               exclude_items=None, allow_items=None, _first_user: int = 0):
+               exclude_items=None, allow_items=None, _first_user: int = 0, adapters=None):
     """BSSD for several independent users at once (one result dict per user, same keys as BSSD).
 
     The reference decodes users strictly one after another (inference.py:162-176).  Here the users advance in
@@ -741,22 +795,26 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
     refuses a prompt at submit when its rounds COULD run out of KV slots (prompt length + (max_new_tokens - 1) x draft beams > max_slots,
     AtSpeedError ERR_CAPACITY, nothing decoded), where the lock-step path only fails if that user's acceptance really takes it there.
 
-    `exclude_items` / `allow_items`: one list of token sequences (or None = unfiltered) per user, on either path; a user has one or the other."""
+    `exclude_items` / `allow_items`: one list of token sequences (or None = unfiltered) per user, on either path; a user has one or the other.
+    `adapters`: one resident adapter's name (`HipLlama.add_lora`) or None per user, on either path: every user of the batch runs the target
+    under its own adapter, the draft is never adapted."""
+    slots = _adapter_slots(target_model, adapters, len(inputs_list), True, "BSSD_batch")
     if lanes is not None:
         if trace_decisions:
             raise ValueError("BSSD_batch(lanes=N) keeps no decision trace")
         return _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes,
-                                 _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch"))
+                                 _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch"), slots)
     mode = _mode(seed, target_model, draft_model)
     if len(inputs_list) > MAX_USERS_PER_CALL:
         return _chunked(lambda chunk, s, i: BSSD_batch(target_model, draft_model, chunk, gamma, max_new_tokens, prefix_allowed_tokens_fn,
                                                        seed=s, trace_decisions=trace_decisions, exclude_items=_chunk_of(exclude_items, i, len(chunk)),
-                                                       allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i), inputs_list, mode)
+                                                       allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i,
+                                                       adapters=_chunk_of(adapters, i, len(chunk))), inputs_list, mode)
     filters = _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch")
     k = int(target_model.generation_config.num_beams)
     dk = int(draft_model.generation_config.num_beams)
     t0 = time.time()
-    c = _setup(target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, mode, "BSSD_batch", trace_decisions, filters, _first_user)
+    c = _setup(target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, mode, "BSSD_batch", trace_decisions, filters, _first_user, slots)
     raw, stats = _batch_call(_lib.load().atspeed_bssd_generate_batch, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     wall = time.time() - t0
     outs = _batch_results(*raw)
@@ -769,37 +827,41 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
 @Timer()
 @torch.no_grad()
 def target_generate(model, inputs: Dict, max_new_tokens: int, logits_processor=None,
-                    prefix_allowed_tokens_fn=None, seed=None, exclude_items=None, allow_items=None) -> Dict:
+                    prefix_allowed_tokens_fn=None, seed=None, exclude_items=None, allow_items=None, adapter=None) -> Dict:
     mode = _mode(seed, model)
     filters = _filter_specs(1, exclude_items, allow_items, False, "target_generate")
+    slots = _adapter_slots(model, adapter, 1, False, "target_generate")
     if _host_path(logits_processor, prefix_allowed_tokens_fn):
         _refuse_host_filters(filters, "target_generate")
+        _refuse_host_adapters(slots, "target_generate")
         from .hostmask import target_generate_host_mask
         return _host_call(target_generate_host_mask, (model,), inputs, (int(max_new_tokens),), logits_processor, prefix_allowed_tokens_fn,
                           mode)
     k = int(model.generation_config.num_beams)                        # beamSD.py:553
-    c = _setup(model, None, [inputs], prefix_allowed_tokens_fn, mode, "target_generate", filters=filters)
+    c = _setup(model, None, [inputs], prefix_allowed_tokens_fn, mode, "target_generate", filters=filters, adapters=slots)
     out, stats = _one_user_call(_lib.load().atspeed_target_generate, c, k, max_new_tokens, int(max_new_tokens), k)
     out.update({"n_valid": int(stats.n_valid), "device_time_cost": stats.total_ms * 1e-3})
     return out
 
 
 def target_generate_batch(model, inputs_list, max_new_tokens: int, prefix_allowed_tokens_fn=None, seed=None, exclude_items=None,
-                          allow_items=None, _first_user: int = 0):
+                          allow_items=None, _first_user: int = 0, adapters=None):
     """`target_generate` for several independent users in lock step (one result dict per user): position g of every
     user's constrained beam search is ONE forward.  This is the loop `code/generate_teacher_data.py:211-244` runs over
     a whole training set with HF `generate`; token ids equal per-user `target_generate` calls.  `exclude_items` / `allow_items`: one list of
-    token sequences (or None = unfiltered) per user."""
+    token sequences (or None = unfiltered) per user.  `adapters`: one resident adapter's name (`HipLlama.add_lora`) or None per user."""
     mode = _mode(seed, model)
+    slots = _adapter_slots(model, adapters, len(inputs_list), True, "target_generate_batch")
     if len(inputs_list) > MAX_USERS_PER_CALL:
         return _chunked(lambda chunk, s, i: target_generate_batch(model, chunk, max_new_tokens, prefix_allowed_tokens_fn, seed=s,
                                                                   exclude_items=_chunk_of(exclude_items, i, len(chunk)),
-                                                                  allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i),
+                                                                  allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i,
+                                                                  adapters=_chunk_of(adapters, i, len(chunk))),
                         inputs_list, mode)
     filters = _filter_specs(len(inputs_list), exclude_items, allow_items, True, "target_generate_batch")
     k = int(model.generation_config.num_beams)
     t0 = time.time()
-    c = _setup(model, None, inputs_list, prefix_allowed_tokens_fn, mode, "target_generate_batch", filters=filters, first_user=_first_user)
+    c = _setup(model, None, inputs_list, prefix_allowed_tokens_fn, mode, "target_generate_batch", filters=filters, first_user=_first_user, adapters=slots)
     raw, stats = _batch_call(_lib.load().atspeed_target_generate_batch, c, k, max_new_tokens, int(max_new_tokens), k)
     wall = time.time() - t0
     outs = _batch_results(*raw)

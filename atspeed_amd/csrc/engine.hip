@@ -325,6 +325,15 @@ struct atspeed_llama {
   int lora_r16 = 0;
   float lora_scaling = 0.f;
   long lora_cnt = 0;                             // shrink + expand launches (atspeed_llama_lora_launches)
+  // resident adapters picked per user (atspeed_llama_add_lora), exclusive with the model-wide one above: slot s (1 .. 16) owns one device block
+  // laid out as set_lora's; slot_tab is the DEVICE table the segmented kernels read, [n_layers][17] entries (entry 0 = none), at a fixed address
+  // from the first add to the model's end and rewritten by add / remove alone
+  struct LoraSlot { void* mem = nullptr; int r16 = 0; float scaling = 0.f; };
+  LoraSlot slots[ATSPEED_LORA_MAX_ADAPTERS + 1];
+  int n_slots = 0;                               // occupied
+  atspeed_lora_slot* slot_tab = nullptr;
+  bool has_lora() const { return !lora.empty() || n_slots > 0; }   // the forward takes the adapter side path (either kind)
+  bool slot_ok(int s) const { return s == 0 || (s >= 1 && s <= ATSPEED_LORA_MAX_ADAPTERS && slots[s].mem); }
   KvCache kv0;                                   // cache of the plain atspeed_llama_forward API
   std::vector<KvCache> kv_pool;                  // one more cache per segment of atspeed_llama_forward_batch (grown on demand)
   ActCtx* act;                                   // grown on demand (ensure_act)
@@ -448,7 +457,7 @@ static int ensure_act(atspeed_llama* m, int tok, int rows) {
   cx->ws_bytes = gemm_ws_for(c, cx->cap_tok, cx->cap_rows);
   ATS_HIP(hipMalloc(&cx->ws, cx->ws_bytes));
   ATS_HIP(hipMalloc((void**)&cx->segtab_dev, sizeof(SegTable)));
-  if (!m->lora.empty()) ATS_TRY(lora_u_ensure(m, cx.get()));
+  if (m->has_lora()) ATS_TRY(lora_u_ensure(m, cx.get()));
   m->act = cx.release();
   return ATSPEED_OK;
 }
@@ -545,6 +554,8 @@ extern "C" void atspeed_llama_destroy(atspeed_llama* m) {
   quant_layers_free(m->fp8);
   quant_layers_free(m->fp4);
   hipFree(m->lora_mem);
+  for (auto& sl : m->slots) hipFree(sl.mem);
+  hipFree(m->slot_tab);
   hipFree(m->cos_tab); hipFree(m->sin_tab);
   delete m;
 }
@@ -719,22 +730,25 @@ extern "C" int atspeed_llama_clear_lora(atspeed_llama* m) {
   return ATSPEED_OK;
 }
 
-extern "C" int atspeed_llama_set_lora(atspeed_llama* m, int32_t rank, float scaling, const atspeed_lora_layer* layers, void* stream) {
-  ATS_REQUIRE(m && layers, ATSPEED_ERR_INVALID, "set_lora: null argument");
-  ATS_REQUIRE(rank >= 1 && rank <= ATSPEED_LORA_MAX_RANK, ATSPEED_ERR_INVALID, "set_lora: rank %d (1 .. %d)", rank, ATSPEED_LORA_MAX_RANK);
-  ATS_REQUIRE(scaling == scaling && scaling - scaling == 0.f, ATSPEED_ERR_INVALID, "set_lora: scaling must be finite");
+// what atspeed_llama_set_lora and atspeed_llama_add_lora share: the checks, then the library's zero-padded copies of one adapter in ONE new
+// device block (*mem_out; per layer A_cat, then the three B), complete and waited for, with the model's lora_A output buffer made sure of and
+// the device idle.  The model itself is not changed: on failure nothing is left behind.
+static int lora_build(atspeed_llama* m, const char* who, int32_t rank, float scaling, const atspeed_lora_layer* layers, hipStream_t st,
+                      char** mem_out, std::vector<atspeed_llama::LoraLayer>* ll_out) {
+  ATS_REQUIRE(m && layers, ATSPEED_ERR_INVALID, "%s: null argument", who);
+  ATS_REQUIRE(rank >= 1 && rank <= ATSPEED_LORA_MAX_RANK, ATSPEED_ERR_INVALID, "%s: rank %d (1 .. %d)", who, rank, ATSPEED_LORA_MAX_RANK);
+  ATS_REQUIRE(scaling == scaling && scaling - scaling == 0.f, ATSPEED_ERR_INVALID, "%s: scaling must be finite", who);
   const int L = m->cfg.n_layers, H = m->cfg.hidden, r16 = (rank + 15) / 16 * 16;
   const size_t e = m->esz;
   bool any = false;
   for (int l = 0; l < L; ++l) {
     const void* const ab[3][2] = {{layers[l].a_q, layers[l].b_q}, {layers[l].a_k, layers[l].b_k}, {layers[l].a_v, layers[l].b_v}};
     for (int k = 0; k < 3; ++k) {
-      ATS_REQUIRE(!ab[k][0] == !ab[k][1], ATSPEED_ERR_INVALID, "set_lora: layer %d has one half of a module's (A, B) pair", l);
+      ATS_REQUIRE(!ab[k][0] == !ab[k][1], ATSPEED_ERR_INVALID, "%s: layer %d has one half of a module's (A, B) pair", who, l);
       any = any || ab[k][0];
     }
   }
-  ATS_REQUIRE(any, ATSPEED_ERR_INVALID, "set_lora: no module is adapted (atspeed_llama_clear_lora removes an adapter)");
-  hipStream_t st = (hipStream_t)stream;
+  ATS_REQUIRE(any, ATSPEED_ERR_INVALID, "%s: no module is adapted (atspeed_llama_clear_lora / _remove_lora take an adapter away)", who);
   // the new copies are built aside; the model changes only after they are complete
   const size_t a_bytes = (size_t)3 * r16 * H * e, b_bytes = (size_t)H * r16 * e;       // multiples of 16 bytes (hidden % 8 == 0, r16 % 16 == 0)
   const size_t per_layer = a_bytes + 3 * b_bytes;
@@ -760,15 +774,77 @@ extern "C" int atspeed_llama_set_lora(atspeed_llama* m, int32_t rank, float scal
   };
   int rc = fill();
   if (rc == ATSPEED_OK && m->act) rc = lora_u_ensure(m, m->act);
-  if (rc == ATSPEED_OK && hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); atspeed_set_error("set_lora: device synchronisation failed"); rc = ATSPEED_ERR_HIP; }
+  if (rc == ATSPEED_OK && hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); atspeed_set_error("%s: device synchronisation failed", who); rc = ATSPEED_ERR_HIP; }
   if (rc != ATSPEED_OK) { hipFree(mem); return rc; }
+  *mem_out = mem;
+  *ll_out = std::move(ll);
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_llama_set_lora(atspeed_llama* m, int32_t rank, float scaling, const atspeed_lora_layer* layers, void* stream) {
+  ATS_REQUIRE(!m || m->n_slots == 0, ATSPEED_ERR_INVALID, "set_lora: the model holds %d resident adapters (atspeed_llama_add_lora): a model-wide adapter "
+              "and resident slots exclude each other", m->n_slots);
+  char* mem = nullptr;
+  std::vector<atspeed_llama::LoraLayer> ll;
+  ATS_TRY(lora_build(m, "set_lora", rank, scaling, layers, (hipStream_t)stream, &mem, &ll));
   graphs_drop(m);
   hipFree(m->lora_mem);                            // a second adapter replaces the first
   m->lora_mem = mem;
   m->lora = std::move(ll);
-  m->lora_r16 = r16; m->lora_scaling = scaling;
+  m->lora_r16 = (rank + 15) / 16 * 16; m->lora_scaling = scaling;
   return ATSPEED_OK;
 }
+
+// ---- resident adapters, picked per user (header: "several RESIDENT adapters on one model")
+// the device table as the host knows the slots: written whole, with the device idle (add / remove wait for it first)
+static int slot_tab_write(atspeed_llama* m, int slot, const std::vector<atspeed_llama::LoraLayer>* ll) {
+  constexpr int NS = ATSPEED_LORA_MAX_ADAPTERS + 1;
+  for (int l = 0; l < m->cfg.n_layers; ++l) {
+    atspeed_lora_slot e{};                         // ll == NULL: the entry of a freed slot, all zero
+    if (ll) e = atspeed_lora_slot{(*ll)[l].a_cat, (*ll)[l].b[0], (*ll)[l].b[1], (*ll)[l].b[2], m->slots[slot].r16, m->slots[slot].scaling};
+    ATS_HIP(hipMemcpy(m->slot_tab + (size_t)l * NS + slot, &e, sizeof(e), hipMemcpyHostToDevice));
+  }
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_llama_add_lora(atspeed_llama* m, int32_t rank, float scaling, const atspeed_lora_layer* layers, void* stream, int32_t* slot_out) {
+  ATS_REQUIRE(m && slot_out, ATSPEED_ERR_INVALID, "add_lora: null argument");
+  ATS_REQUIRE(m->lora.empty(), ATSPEED_ERR_INVALID, "add_lora: the model holds a model-wide adapter (atspeed_llama_set_lora): a model-wide adapter and "
+              "resident slots exclude each other");
+  int slot = 0;
+  for (int s = 1; s <= ATSPEED_LORA_MAX_ADAPTERS && !slot; ++s) if (!m->slots[s].mem) slot = s;
+  ATS_REQUIRE(slot, ATSPEED_ERR_CAPACITY, "add_lora: all %d slots are occupied", ATSPEED_LORA_MAX_ADAPTERS);
+  constexpr int NS = ATSPEED_LORA_MAX_ADAPTERS + 1;
+  if (!m->slot_tab) {
+    const size_t bytes = (size_t)m->cfg.n_layers * NS * sizeof(atspeed_lora_slot);
+    ATS_HIP(hipMalloc((void**)&m->slot_tab, bytes));
+    ATS_HIP(hipMemset(m->slot_tab, 0, bytes));
+  }
+  char* mem = nullptr;
+  std::vector<atspeed_llama::LoraLayer> ll;
+  ATS_TRY(lora_build(m, "add_lora", rank, scaling, layers, (hipStream_t)stream, &mem, &ll));
+  m->slots[slot] = atspeed_llama::LoraSlot{mem, (rank + 15) / 16 * 16, scaling};
+  const int rc = slot_tab_write(m, slot, &ll);
+  if (rc != ATSPEED_OK) { hipFree(mem); m->slots[slot] = atspeed_llama::LoraSlot{}; return rc; }
+  graphs_drop(m);
+  m->n_slots++;
+  *slot_out = slot;
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_llama_remove_lora(atspeed_llama* m, int32_t slot) {
+  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "remove_lora: null model");
+  ATS_REQUIRE(slot >= 1 && slot <= ATSPEED_LORA_MAX_ADAPTERS && m->slots[slot].mem, ATSPEED_ERR_INVALID, "remove_lora: slot %d is not occupied", slot);
+  ATS_HIP(hipDeviceSynchronize());                 // forwards in flight read the copies and the table
+  graphs_drop(m);
+  ATS_TRY(slot_tab_write(m, slot, nullptr));
+  hipFree(m->slots[slot].mem);
+  m->slots[slot] = atspeed_llama::LoraSlot{};
+  m->n_slots--;
+  return ATSPEED_OK;
+}
+
+extern "C" int32_t atspeed_llama_lora_slots(const atspeed_llama* m) { return m ? m->n_slots : -1; }
 
 extern "C" int64_t atspeed_llama_lora_launches(atspeed_llama* m, int32_t reset) {
   if (!m) return -1;
@@ -792,7 +868,7 @@ extern "C" int64_t atspeed_llama_lora_launches(atspeed_llama* m, int32_t reset) 
 // forward's token count and their layer bodies carry xq_ready state: left on the full path, as staged verification leaves them), at most half
 // of the rows get logits, and the forward holds more than "tail_rows_tokens" tokens (below, a projection is bound by its weight stream).
 static bool forward_prunes_tail(const atspeed_llama* m, const SegTable& t) {
-  return m->fp8.empty() && m->fp4.empty() && m->lora.empty() && 2 * t.total_logit <= t.total_tok && t.total_tok > ats_switch(ATS_SW_TAIL_ROWS_TOKENS);
+  return m->fp8.empty() && m->fp4.empty() && !m->has_lora() && 2 * t.total_logit <= t.total_tok && t.total_tok > ats_switch(ATS_SW_TAIL_ROWS_TOKENS);
 }
 static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTable* dtab, float* logits_out, hipStream_t st,
                               const unsigned char* tile_store, int logit_row_off);
@@ -893,9 +969,19 @@ extern "C" int atspeed_llama_forward_batch(atspeed_llama* m, int32_t n, const in
                                            const int32_t* const* slots, const uint64_t* const* vis, const int32_t* n_tokens,
                                            const int32_t* n_slots_visible, const int32_t* n_logit_rows, float* logits_out,
                                            void* stream) {
+  return atspeed_llama_forward_batch_adapters(m, n, ids, pos, slots, vis, n_tokens, n_slots_visible, n_logit_rows, nullptr, logits_out, stream);
+}
+
+// the same with one resident adapter slot per sequence (adapters == NULL: none)
+extern "C" int atspeed_llama_forward_batch_adapters(atspeed_llama* m, int32_t n, const int32_t* const* ids, const int32_t* const* pos,
+                                                    const int32_t* const* slots, const uint64_t* const* vis, const int32_t* n_tokens,
+                                                    const int32_t* n_slots_visible, const int32_t* n_logit_rows, const int32_t* adapters,
+                                                    float* logits_out, void* stream) {
   ATS_REQUIRE(m && ids && pos && slots && vis && n_tokens && n_slots_visible && n_logit_rows && logits_out, ATSPEED_ERR_INVALID,
               "forward_batch: null argument");
   ATS_REQUIRE(n >= 1 && n <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "forward_batch: %d sequences per call (max %d)", n, ATS_MAX_SEGS);
+  for (int i = 0; adapters && i < n; ++i)
+    ATS_REQUIRE(m->slot_ok(adapters[i]), ATSPEED_ERR_INVALID, "forward_batch: sequence %d names adapter slot %d, which is not occupied", i, adapters[i]);
   while ((int)m->kv_pool.size() < n) {
     KvCache kv;
     ATS_TRY(kv_create(m, &kv));
@@ -911,6 +997,7 @@ extern "C" int atspeed_llama_forward_batch(atspeed_llama* m, int32_t n, const in
     Seg& sg = t.seg[t.n++];
     sg.ids = ids[i]; sg.pos = pos[i]; sg.slot = slots[i]; sg.vis = vis[i]; sg.kc = m->kv_pool[i].k; sg.vc = m->kv_pool[i].v;
     sg.n_tok = n_tokens[i]; sg.n_slots = n_slots_visible[i]; sg.n_logit = n_logit_rows[i];
+    sg.adapter = adapters ? adapters[i] : 0;
     tot += n_tokens[i]; rows += n_logit_rows[i];
   }
   ATS_TRY(ats_seg_finish(t));
@@ -925,7 +1012,8 @@ extern "C" int atspeed_llama_forward_batch(atspeed_llama* m, int32_t n, const in
 enum { SEGS_IDS = 1, SEGS_POS = 2, SEGS_SLOTS = 4, SEGS_VIS = 8, SEGS_KV = 16 };
 static int segs_table(const char* who, int need, int qtile_rows, int32_t n, const int32_t* const* ids, const int32_t* const* pos,
                       const int32_t* const* slots, const uint64_t* const* vis, void* const* kcache, void* const* vcache, const int32_t* n_tokens,
-                      const int32_t* n_slots_visible, const int32_t* n_logit_rows, hipStream_t st, SegTable& t, const SegTable** dt) {
+                      const int32_t* n_slots_visible, const int32_t* n_logit_rows, hipStream_t st, SegTable& t, const SegTable** dt,
+                      const int32_t* adapters = nullptr /* [n] resident adapter slot per segment: the _multi adapter kernels */) {
   ATS_REQUIRE(n_tokens && n_slots_visible && n_logit_rows, ATSPEED_ERR_INVALID, "%s: null count array", who);
   ATS_REQUIRE(n >= 1 && n <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "%s: %d segments per call (max %d)", who, n, ATS_MAX_SEGS);
   ATS_REQUIRE(qtile_rows == 0 || qtile_rows == 64 || qtile_rows == 128 || qtile_rows == 256, ATSPEED_ERR_INVALID, "%s: query tile of %d rows", who, qtile_rows);
@@ -943,6 +1031,7 @@ static int segs_table(const char* who, int need, int qtile_rows, int32_t n, cons
     ATS_REQUIRE((!(need & SEGS_IDS) || sg.ids) && (!(need & SEGS_POS) || sg.pos) && (!(need & SEGS_SLOTS) || sg.slot) && (!(need & SEGS_VIS) || sg.vis) &&
                 (!(need & SEGS_KV) || (sg.kc && sg.vc)), ATSPEED_ERR_INVALID, "%s: null array for segment %d", who, i);
     sg.n_tok = n_tokens[i]; sg.n_slots = n_slots_visible[i]; sg.n_logit = n_logit_rows[i];
+    sg.adapter = adapters ? adapters[i] : 0;
   }
   ATS_TRY(ats_seg_finish(t, qtile_rows));
   const void* p = nullptr;
@@ -1037,6 +1126,60 @@ extern "C" int atspeed_segs_lora_rope_kv(void* qkv, const void* u, const void* b
   return ATS_KD(dtype, ats_lora_rope_kv_segs(qkv, u, b_q, b_k, b_v, r16, scaling, t, dt, cos_tab, sin_tab, layer_off_bytes, n_heads, head_dim, max_pos, dtype,
                                              (hipStream_t)stream));
 }
+
+// the caller's HOST slot array checked and staged as the fixed-size device table the segmented adapter kernels index (entries from n_slots on:
+// none); *aligned: every a_cat and B is 16-byte aligned
+static int segs_lora_slots(const char* who, const atspeed_lora_slot* slots, int32_t n_slots, const int32_t* seg_adapters, int32_t n, bool need_a,
+                           hipStream_t st, const atspeed_lora_slot** dev_out, bool* aligned) {
+  constexpr int NS = ATSPEED_LORA_MAX_ADAPTERS + 1;
+  ATS_REQUIRE(slots && seg_adapters && n_slots >= 1 && n_slots <= NS, ATSPEED_ERR_INVALID, "%s: needs 1 .. %d slots and one slot index per segment", who, NS);
+  atspeed_lora_slot tab[NS] = {};
+  *aligned = true;
+  for (int s = 1; s < n_slots; ++s) {
+    tab[s] = slots[s];
+    if (!slots[s].a_cat && !slots[s].b_q && !slots[s].b_k && !slots[s].b_v) { tab[s] = atspeed_lora_slot{}; continue; }     // an empty entry: no segment may name it
+    ATS_REQUIRE(slots[s].r16 >= 16 && slots[s].r16 <= ATSPEED_LORA_MAX_RANK && slots[s].r16 % 16 == 0, ATSPEED_ERR_INVALID,
+                "%s: slot %d has a padded rank of %d (16, 32, 48 or 64)", who, s, slots[s].r16);
+    ATS_REQUIRE(!need_a || slots[s].a_cat, ATSPEED_ERR_INVALID, "%s: slot %d has no a_cat", who, s);
+    if ((((uintptr_t)slots[s].a_cat | (uintptr_t)slots[s].b_q | (uintptr_t)slots[s].b_k | (uintptr_t)slots[s].b_v) & 15) != 0) *aligned = false;
+  }
+  for (int i = 0; i < n && i < ATS_MAX_SEGS; ++i)
+    ATS_REQUIRE(seg_adapters[i] >= 0 && seg_adapters[i] < n_slots && (seg_adapters[i] == 0 || tab[seg_adapters[i]].r16), ATSPEED_ERR_INVALID,
+                "%s: segment %d names slot %d, which the table does not hold", who, i, seg_adapters[i]);
+  const void* p = nullptr;
+  ATS_TRY(ats_stage(tab, sizeof(tab), &p, st));
+  *dev_out = (const atspeed_lora_slot*)p;
+  return ATSPEED_OK;
+}
+
+// lora_shrink with the adapter picked per segment (lora_shrink_segs kernels; header: the memory contract); tests/test_lora_multi_gpu.py
+extern "C" int atspeed_segs_lora_shrink_multi(const void* h, const void* norm_w, const atspeed_lora_slot* lora_slots, int32_t n_slots, void* u, int32_t hidden,
+                                              float eps, int32_t dtype, const int32_t* seg_adapters, ATS_SEGS_PARAMS, void* stream) {
+  ATS_REQUIRE(h && norm_w && u && hidden > 0 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID, "segs_lora_shrink_multi: bad arguments");
+  const atspeed_lora_slot* dslots = nullptr;
+  bool aligned = false;
+  ATS_TRY(segs_lora_slots("segs_lora_shrink_multi", lora_slots, n_slots, seg_adapters, n, true, (hipStream_t)stream, &dslots, &aligned));
+  SegTable t{}; const SegTable* dt = nullptr;
+  ATS_TRY(segs_table("segs_lora_shrink_multi", 0, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt, seg_adapters));
+  return ATS_KD(dtype, ats_lora_shrink_segs(h, norm_w, dslots, aligned, u, t, dt, hidden, eps, dtype, (hipStream_t)stream));
+}
+
+// atspeed_segs_lora_rope_kv with the adapter picked per segment (lora_rope_kv_segs_multi kernels); tests/test_lora_multi_gpu.py
+extern "C" int atspeed_segs_lora_rope_kv_multi(void* qkv, const void* u, const atspeed_lora_slot* lora_slots, int32_t n_slots, const float* cos_tab,
+                                               const float* sin_tab, size_t layer_off_bytes, int32_t n_heads, int32_t head_dim, int32_t max_pos,
+                                               int32_t dtype, const int32_t* seg_adapters, ATS_SEGS_PARAMS, void* stream) {
+  ATS_REQUIRE(qkv && u && cos_tab && sin_tab && n_heads >= 1 && head_dim >= 2 && head_dim % 2 == 0 && max_pos >= 1 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID,
+              "segs_lora_rope_kv_multi: bad arguments");
+  ATS_REQUIRE(((uintptr_t)qkv & 15) == 0 && layer_off_bytes % 16 == 0, ATSPEED_ERR_INVALID, "segs_lora_rope_kv_multi: qkv and the layer offset must be 16-byte aligned");
+  const atspeed_lora_slot* dslots = nullptr;
+  bool aligned = false;
+  ATS_TRY(segs_lora_slots("segs_lora_rope_kv_multi", lora_slots, n_slots, seg_adapters, n, false, (hipStream_t)stream, &dslots, &aligned));
+  ATS_REQUIRE(aligned || dtype == ATSPEED_F32 || head_dim % 16 != 0, ATSPEED_ERR_INVALID, "segs_lora_rope_kv_multi: every B must be 16-byte aligned");
+  SegTable t{}; const SegTable* dt = nullptr;
+  ATS_TRY(segs_table("segs_lora_rope_kv_multi", SEGS_POS | SEGS_SLOTS | SEGS_KV, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt, seg_adapters));
+  return ATS_KD(dtype, ats_lora_rope_kv_segs_multi(qkv, u, dslots, t, dt, cos_tab, sin_tab, layer_off_bytes, n_heads, head_dim, max_pos, dtype,
+                                                   (hipStream_t)stream));
+}
 #undef ATS_SEGS_PARAMS
 #undef ATS_SEGS_ARGS
 
@@ -1078,6 +1221,9 @@ struct atspeed_decoder {
   bool warps() const { return sample && (top_k > 0 || top_p < 1.f); }
   // item filter (atspeed_decoder_set_node_mask; a session puts its user's there): none by default
   const atspeed_node_masks* masks = nullptr; int mask_user = 0;
+  // the target's resident adapter this user runs under (atspeed_decoder_set_adapter; a session puts its user's there): 0 = none.  It rides in
+  // the user's segment of every target forward; the draft's segments keep 0
+  int adapter = 0;
   // the automaton as this user's kernels take it by value: the shared arrays and the user's own blocked-node bits
   FsmDev fsm_dev(const atspeed_fsm* fsm) const { FsmDev f = fsm->dev; f.blocked = ats_mask_bits(masks, mask_user); return f; }
   struct Run {
@@ -1190,6 +1336,13 @@ extern "C" int atspeed_decoder_set_node_mask(atspeed_decoder* d, const atspeed_n
   return ATSPEED_OK;
 }
 
+extern "C" int atspeed_decoder_set_adapter(atspeed_decoder* d, int32_t slot) {
+  ATS_REQUIRE(d, ATSPEED_ERR_INVALID, "set_adapter: null decoder");
+  ATS_REQUIRE(slot >= 0 && slot <= ATSPEED_LORA_MAX_ADAPTERS, ATSPEED_ERR_INVALID, "set_adapter: slot %d out of [0, %d]", slot, ATSPEED_LORA_MAX_ADAPTERS);
+  d->adapter = slot;                               // whether the target holds it is looked up when a generate call starts
+  return ATSPEED_OK;
+}
+
 // the decoder's private K / V arenas, copied to or from the caller's device buffers (tests fill them with a sentinel and read back which slots
 // a call wrote)
 extern "C" int64_t atspeed_decoder_kv_bytes(const atspeed_decoder* d, int32_t draft) {
@@ -1256,6 +1409,8 @@ static int check_common(atspeed_decoder* d, const int32_t* prompt, int P, const 
   ATS_REQUIRE(start_node >= 0 && start_node < std::max(fsm->dev.n_nodes, 1), ATSPEED_ERR_INVALID, "generate: start node out of range");
   ATS_REQUIRE(!(d->sample && fsm->dev.n_nodes == 0), ATSPEED_ERR_INVALID, "generate: sampling needs a constraint automaton (mask-free search is greedy only)");
   ATS_REQUIRE(!d->masks || d->masks->fsm == fsm, ATSPEED_ERR_INVALID, "generate: the decoder's item filter was built on another automaton");
+  ATS_REQUIRE(d->target->slot_ok(d->adapter), ATSPEED_ERR_INVALID, "generate: the decoder names adapter slot %d, which its target does not hold "
+              "(atspeed_llama_add_lora / atspeed_decoder_set_adapter)", d->adapter);
   return ATSPEED_OK;
 }
 
@@ -1305,10 +1460,10 @@ static int stage_args(const std::vector<A>& v, const A** dev_out, hipStream_t st
   return ATSPEED_OK;
 }
 
-static Seg make_seg(const TokBuf& tb, int n_tok, int n_slots, int n_logit, const KvCache& kv) {
+static Seg make_seg(const TokBuf& tb, int n_tok, int n_slots, int n_logit, const KvCache& kv, int adapter = 0) {
   Seg s{};
   s.ids = tb.ids; s.pos = tb.pos; s.slot = tb.slot; s.vis = tb.vis; s.kc = kv.k; s.vc = kv.v;
-  s.n_tok = n_tok; s.n_slots = n_slots; s.n_logit = n_logit;
+  s.n_tok = n_tok; s.n_slots = n_slots; s.n_logit = n_logit; s.adapter = adapter;
   return s;
 }
 int ats_seg_finish(SegTable& t, int qtile_rows) {
@@ -1471,7 +1626,7 @@ static bool bssd_round_staged(const std::vector<atspeed_decoder*>& ver, const st
   const int mode = ats_switch(ATS_SW_VERIFY_STAGED);
   if (mode <= 0 || ver.empty()) return false;
   const atspeed_llama* T = ver[0]->target;
-  if (!T->fp8.empty() || !T->fp4.empty() || !T->lora.empty()) return false;
+  if (!T->fp8.empty() || !T->fp4.empty() || T->has_lora()) return false;
   long long tok = 0;
   for (const atspeed_decoder* d : ver) { if (d->sample) return false; tok += d->run.n0 + d->run.dl * d->run.dk; }
   for (const atspeed_decoder* d : fin) { if (d->sample) return false; tok += d->run.n0; }
@@ -1504,6 +1659,8 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
     atspeed_decoder* d = decs[u];
     atspeed_decoder::Run& r = d->run;
     if (r.done) continue;
+    // (a slot removed under a user that is in a lane: the caller's error, found here before the round launches anything)
+    ATS_REQUIRE(T->slot_ok(d->adapter), ATSPEED_ERR_INVALID, "bssd: a user names adapter slot %d, which the target no longer holds", d->adapter);
     r.final_step = r.export_only = false;
     if (r.gen >= r.max_new) { r.final_step = r.export_only = true; continue; }
     r.dl = std::min(r.gamma, r.max_new - r.gen - 1);                               // beamSD.py:504
@@ -1571,15 +1728,15 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
         atspeed_decoder* d = ver[j];
         atspeed_decoder::Run& r = d->run;
         const int Tn = r.n0 + r.dl * r.dk;
-        if (!staged)     t.seg[t.n++] = make_seg(d->tin[r.cur], Tn, r.base + Tn, r.nb + r.dl * r.dk, d->tkv);
-        else if (p == 0) t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv);
-        else             t.seg[t.n++] = make_seg(tb_offset(d->tin[r.cur], r.n0 + (p - 1) * r.dk, W), r.dk, r.base + r.n0 + p * r.dk, r.dk, d->tkv);
+        if (!staged)     t.seg[t.n++] = make_seg(d->tin[r.cur], Tn, r.base + Tn, r.nb + r.dl * r.dk, d->tkv, d->adapter);
+        else if (p == 0) t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv, d->adapter);
+        else             t.seg[t.n++] = make_seg(tb_offset(d->tin[r.cur], r.n0 + (p - 1) * r.dk, W), r.dk, r.base + r.n0 + p * r.dk, r.dk, d->tkv, d->adapter);
         if (p == 0) r.s.n_target_forwards++;
         r.s.n_target_passes++;
       }
       if (p == 0) for (atspeed_decoder* d : fin) {
         atspeed_decoder::Run& r = d->run;
-        t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv);
+        t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv, d->adapter);
         r.s.n_target_forwards++; r.s.n_target_passes++;
       }
       ATS_TRY(ats_seg_finish(t));
@@ -1803,6 +1960,7 @@ struct SessionJob {          // a submitted user, as it waits in the queue and t
   const int32_t* prompt = nullptr; int P = 0, start_node = 0; uint32_t seed = 0;
   int32_t* out_tokens = nullptr; float* out_scores = nullptr; atspeed_gen_stats* stats = nullptr;
   const atspeed_node_masks* masks = nullptr; int mask_user = 0;     // the user's item filter (atspeed_session_submit_masked)
+  int adapter = 0;                                                   // the user's resident adapter slot (atspeed_session_submit_ex)
 };
 }  // namespace
 struct atspeed_session {
@@ -1876,7 +2034,24 @@ extern "C" void atspeed_session_destroy(atspeed_session* s) { delete s; }
 extern "C" int atspeed_session_submit_masked(atspeed_session* s, const int32_t* prompt, int32_t P, int32_t start_node, uint32_t seed,
                                              int32_t* out_tokens, float* out_scores, atspeed_gen_stats* stats, const atspeed_node_masks* masks,
                                              int32_t user, int64_t* ticket_out) {
-  ATS_REQUIRE(s && ticket_out, ATSPEED_ERR_INVALID, "session_submit: null argument");
+  atspeed_session_user u{};
+  u.struct_size = sizeof(u);
+  u.prompt_ids_dev = prompt; u.prompt_len = P; u.start_node = start_node; u.seed = seed;
+  u.out_tokens_dev = out_tokens; u.out_scores_dev = out_scores; u.stats_host = stats; u.masks = masks; u.mask_user = user;
+  return atspeed_session_submit_ex(s, &u, ticket_out);
+}
+
+// the one submit entry: every per-user property in a struct (members past the caller's struct_size are 0)
+extern "C" int atspeed_session_submit_ex(atspeed_session* s, const atspeed_session_user* user_in, int64_t* ticket_out) {
+  ATS_REQUIRE(s && user_in && ticket_out, ATSPEED_ERR_INVALID, "session_submit: null argument");
+  ATS_REQUIRE(user_in->struct_size >= offsetof(atspeed_session_user, masks), ATSPEED_ERR_INVALID, "session_submit: struct_size %zu is too small",
+              user_in->struct_size);
+  atspeed_session_user uu{};
+  memcpy(&uu, user_in, std::min(user_in->struct_size, sizeof(uu)));
+  const int32_t* prompt = uu.prompt_ids_dev; const int32_t P = uu.prompt_len, start_node = uu.start_node, user = uu.mask_user; const uint32_t seed = uu.seed;
+  int32_t* out_tokens = uu.out_tokens_dev; float* out_scores = uu.out_scores_dev; atspeed_gen_stats* stats = uu.stats_host;
+  const atspeed_node_masks* masks = uu.masks;
+  ATS_REQUIRE(s->lanes[0]->target->slot_ok(uu.adapter), ATSPEED_ERR_INVALID, "session_submit: adapter slot %d is not occupied on the session's target", uu.adapter);
   ATS_REQUIRE(!masks || masks->fsm == s->fsm, ATSPEED_ERR_INVALID, "session_submit: the item filter was built on another automaton");
   ATS_REQUIRE(!masks || (user >= 0 && user < masks->n_users), ATSPEED_ERR_INVALID, "session_submit: filter user %d out of [0, %d)", user, masks ? masks->n_users : 0);
   ATS_TRY(check_common(s->lanes[0], prompt, P, s->fsm, start_node, s->max_new, s->k, out_tokens, out_scores));
@@ -1885,7 +2060,7 @@ extern "C" int atspeed_session_submit_masked(atspeed_session* s, const int32_t* 
   // a round, rather than inside one
   const int slots = P + (s->max_new - 1) * s->dk, max_slots = s->lanes[0]->target->cfg.max_slots;
   ATS_REQUIRE(slots <= max_slots, ATSPEED_ERR_CAPACITY, "session_submit: prompt of %d tokens can need %d KV slots (%d available)", P, slots, max_slots);
-  *ticket_out = s->q.submit(SessionJob{prompt, P, start_node, seed, out_tokens, out_scores, stats, masks, masks ? user : 0});
+  *ticket_out = s->q.submit(SessionJob{prompt, P, start_node, seed, out_tokens, out_scores, stats, masks, masks ? user : 0, uu.adapter});
   return ATSPEED_OK;
 }
 
@@ -1904,6 +2079,7 @@ static int session_round(atspeed_session* s) {
     atspeed_decoder* d = s->lanes[lane];
     d->seed = j.seed;                                   // draws follow the user, not the lane
     d->masks = j.masks; d->mask_user = j.mask_user;     // and so does its item filter: on at admission, off at retirement
+    d->adapter = j.adapter;                             // and its resident adapter
     ATS_TRY(bssd_begin(d, j.prompt, j.P, s->fsm, j.start_node, s->gamma, s->max_new, s->k, s->dk, j.out_tokens, j.out_scores, j.stats, s->st, false));
     fresh.push_back(d); prompts.push_back(j.prompt); lens.push_back(j.P); starts.push_back(j.start_node);
     return (int)ATSPEED_OK;
@@ -1918,7 +2094,7 @@ static int session_round(atspeed_session* s) {
   ATS_TRY(bssd_round(decs.data(), (int)decs.size(), s->st, g_ev, ctl));
   s->target_forwards += ctl.target_forwards; s->draft_forwards += ctl.draft_forwards; s->target_passes += ctl.target_passes;
   for (size_t i = 0; i < decs.size(); ++i)
-    if (decs[i]->run.done) { decs[i]->masks = nullptr; decs[i]->mask_user = 0; s->q.retire(lane_of[i], decs[i]->run.s.status); }
+    if (decs[i]->run.done) { decs[i]->masks = nullptr; decs[i]->mask_user = 0; decs[i]->adapter = 0; s->q.retire(lane_of[i], decs[i]->run.s.status); }
   return ATSPEED_OK;
 }
 
@@ -1937,7 +2113,7 @@ static int session_round_guarded(atspeed_session* s) {
         atspeed_decoder::Run& r = s->lanes[l]->run;
         r.done = true; r.s.status = rc; r.s.n_valid = 0;
         if (r.stats_out) *r.stats_out = r.s;
-        s->lanes[l]->masks = nullptr; s->lanes[l]->mask_user = 0;
+        s->lanes[l]->masks = nullptr; s->lanes[l]->mask_user = 0; s->lanes[l]->adapter = 0;
         s->q.retire(l, rc);
       }
     g_last_error = why;
@@ -2020,7 +2196,7 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
   for (int g = 0; g < max_new; ++g) {                                                // beamSD.py:579-588
     SegTable t{};
     for (int u = 0; u < n; ++u)
-      t.seg[t.n++] = make_seg(tb_offset(decs[u]->tin[0], s[u].row0, W), s[u].n_in, s[u].base + s[u].n_in, s[u].nb, decs[u]->tkv);
+      t.seg[t.n++] = make_seg(tb_offset(decs[u]->tin[0], s[u].row0, W), s[u].n_in, s[u].base + s[u].n_in, s[u].nb, decs[u]->tkv, decs[u]->adapter);
     ATS_TRY(ats_seg_finish(t));
     ATS_TRY(decode_forward(T, t, fsm, k, st));
     for (int u = 0; u < n; ++u) {

@@ -15,16 +15,23 @@ static int proj_fp8(atspeed_llama* m, const void* x, const void* wq, const float
 static int rope_pass(atspeed_llama* m, int l, const SegTable& t, const SegTable* dtab, size_t loff, hipStream_t st) {
   const atspeed_llama_config& c = m->cfg;
   ActCtx* cx = m->act;
-  if (m->lora.empty()) return ats_rope_kv_segs(cx->qkv, t, dtab, m->cos_tab, m->sin_tab, loff, c.n_heads, m->head_dim, c.max_slots, c.dtype, st);
-  const atspeed_llama::LoraLayer& a = m->lora[l];
+  if (!m->has_lora()) return ats_rope_kv_segs(cx->qkv, t, dtab, m->cos_tab, m->sin_tab, loff, c.n_heads, m->head_dim, c.max_slots, c.dtype, st);
   m->lora_cnt++;
+  if (m->n_slots > 0)            // resident adapters: each row's slot from the segment table (atspeed_llama_add_lora)
+    return ats_lora_rope_kv_segs_multi(cx->qkv, cx->lora_u, m->slot_tab + (size_t)l * (ATSPEED_LORA_MAX_ADAPTERS + 1), t, dtab, m->cos_tab,
+                                       m->sin_tab, loff, c.n_heads, m->head_dim, c.max_slots, c.dtype, st);
+  const atspeed_llama::LoraLayer& a = m->lora[l];
   return ats_lora_rope_kv_segs(cx->qkv, cx->lora_u, a.b[0], a.b[1], a.b[2], m->lora_r16, m->lora_scaling, t, dtab, m->cos_tab, m->sin_tab, loff,
                                c.n_heads, m->head_dim, c.max_slots, c.dtype, st);
 }
 // lora_A of a layer's normed input for q, k and v at once, from the residual stream (so it does not matter whether the forward left xn or xq / sx)
-static int lora_shrink(atspeed_llama* m, int l, int T, hipStream_t st) {
-  if (m->lora.empty()) return ATSPEED_OK;
+static int lora_shrink(atspeed_llama* m, int l, const SegTable& t, const SegTable* dtab, hipStream_t st) {
+  if (!m->has_lora()) return ATSPEED_OK;
+  const int T = t.total_tok;
   m->lora_cnt++;
+  if (m->n_slots > 0)
+    return ats_lora_shrink_segs(m->act->h, m->layers[l].input_norm, m->slot_tab + (size_t)l * (ATSPEED_LORA_MAX_ADAPTERS + 1), true, m->act->lora_u,
+                                t, dtab, m->cfg.hidden, m->cfg.rms_eps, m->cfg.dtype, st);
   return ats_lora_shrink(m->act->h, m->layers[l].input_norm, m->lora[l].a_cat, m->act->lora_u, T, m->cfg.hidden, 3 * m->lora_r16, m->cfg.rms_eps,
                          m->cfg.dtype, st);
 }
@@ -38,7 +45,7 @@ static int layer_fp4(atspeed_llama* m, int l, const SegTable& t, const SegTable*
   const atspeed_llama::Fp4Layer& f = m->fp4[l];
   const int T = t.total_tok, H = c.hidden, pk = m->pk;
   const bool q_next = H <= 8192;                           // the fused norm + e4m3 quantisation exists up to hidden 8192
-  ATS_TRY(lora_shrink(m, l, T, st));
+  ATS_TRY(lora_shrink(m, l, t, dtab, st));
   { ProfBracket pb(m, 0, T, st);
     m->fp4_cnt[0]++;
     if (!xq_ready) ATS_TRY(ats_quant_rows_fp8(cx->xn, T, H, H, cx->xq, cx->sx, st, pk));
@@ -93,7 +100,7 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
   // RoPE and the KV scatter ride in the qkv projection's epilogue (one pass over qkv / one launch less per layer): the ring kernels of the batched
   // 16-bit and W8A8 forwards, and since round 6 ONE user's W8A8 projection on the weight-streaming kernel (gemm_wdma_kernel<..., EPI_QKV_ROPE, F8>)
   // a model with an adapter: the plain 16-bit store, then the pass that adds the adapter's term before it rotates (no fused epilogue, no slabs)
-  const bool lora = !m->lora.empty();
+  const bool lora = m->has_lora();
   const bool qkv_rope_fused = f4 || lora ? false : qkv_in_fp8 ? ats_gemm_fp8_qkv_rope_applies(T, H, m->head_dim) : ats_gemm_qkv_rope_applies(T, H, m->head_dim, dt);
   if (qkv_rope_fused) ATS_TRY(ats_row_info(t, dtab, cx->rowinfo, c.max_slots, st));
   // the row-pruned tail of the last layer (engine.hip: forward_prunes_tail): its back part runs over the R logit rows only
@@ -151,7 +158,7 @@ static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTabl
     if (f4) { ATS_TRY(layer_fp4(m, l, t, dtab, loff, xq_ready, st)); continue; }
     // cx->xn holds rmsnorm(h) * input_norm here (from the embed above or the previous layer's fused down_proj epilogue)
     const bool fuse_qkv_reduce = !lora && ats_switch(ATS_SW_FUSE_QKV_REDUCE) != 0;
-    ATS_TRY(lora_shrink(m, l, T, st));
+    ATS_TRY(lora_shrink(m, l, t, dtab, st));
     int qkv_splits = 0;
     { ProfBracket pb(m, 0, T, st);
       if (qkv_in_fp8) {

@@ -16,6 +16,7 @@ struct Seg {
   int row0, n_tok;             // rows [row0, row0 + n_tok) of the batched activations
   int n_slots;                 // slots visible to this user's rows
   int logit_row0, n_logit;     // the last n_logit tokens get logits, at rows [logit_row0, ..) of the logits buffer
+  int adapter;                 // this user's resident LoRA slot (atspeed_llama_add_lora), 0 = none: read by the segmented adapter kernels alone
 };
 struct SegTable {
   int n, total_tok, total_logit;

@@ -105,6 +105,8 @@ class HipLlama:
                                              packed["final_norm"].data_ptr(), packed["lm_head"].data_ptr(), layers)
         self.logits_ld = int(lib.atspeed_llama_logits_ld(self._handle))
         self.lora = None               # SimpleNamespace(r, lora_alpha, scaling, modules) while an adapter is loaded (load_lora)
+        self.adapters: Dict[str, int] = {}        # resident adapters (add_lora): name -> library slot 1 .. 16
+        self.adapter_info: Dict[str, SimpleNamespace] = {}   # name -> SimpleNamespace(r, lora_alpha, scaling, modules)
 
     @staticmethod
     def _pack_rows(t: torch.Tensor) -> torch.Tensor:
@@ -305,26 +307,74 @@ class HipLlama:
         engine dtype through fp32.  A second adapter replaces the first.  NotImplementedError: target modules other than q / k / v,
         `use_dora`, `bias != "none"`, `modules_to_save`, rank > 64."""
         ad = _lora.read(adapter, self.dims.n_layers, self.dims.hidden, r, lora_alpha, use_rslora)
-        arr = (_lib.LoraLayer * self.dims.n_layers)()
-        keep = []
         with torch.cuda.device(self._device):
-            for l, lw in enumerate(ad.layers):
-                for m in _lora.MODULES:
-                    if m in lw:
-                        a, b = (t.to(self._device, torch.float32).to(self._dtype).contiguous() for t in lw[m])
-                        keep += [a, b]
-                        setattr(arr[l], "a_" + m, a.data_ptr())
-                        setattr(arr[l], "b_" + m, b.data_ptr())
+            arr, keep = self._lora_layers(ad)
             _lib.check(_lib.load().atspeed_llama_set_lora(self._handle, ad.r, ad.scaling, arr, _lib.stream_ptr(self._device)))
         del keep                       # the library holds copies of its own
         self.lora = SimpleNamespace(r=ad.r, lora_alpha=ad.lora_alpha, scaling=ad.scaling, modules=ad.modules)
         return self
+
+    def _lora_layers(self, ad):
+        """a loaded adapter's tensors on the device in the engine dtype, as the library's per-layer pointer array (+ the tensors, to keep)"""
+        arr = (_lib.LoraLayer * self.dims.n_layers)()
+        keep = []
+        for l, lw in enumerate(ad.layers):
+            for m in _lora.MODULES:
+                if m in lw:
+                    a, b = (t.to(self._device, torch.float32).to(self._dtype).contiguous() for t in lw[m])
+                    keep += [a, b]
+                    setattr(arr[l], "a_" + m, a.data_ptr())
+                    setattr(arr[l], "b_" + m, b.data_ptr())
+        return arr, keep
 
     def unload_lora(self) -> "HipLlama":
         """Remove the adapter: later forwards are bit for bit those of a model that never had one."""
         _lib.check(_lib.load().atspeed_llama_clear_lora(self._handle))
         self.lora = None
         return self
+
+    # ---- resident adapters, picked per user -------------------------------------------
+    def add_lora(self, adapter, name: str, r: Optional[int] = None, lora_alpha: Optional[float] = None, use_rslora: bool = False) -> "HipLlama":
+        """Keep one more adapter RESIDENT on this model under `name` (up to 16 at once, each with its own rank and scaling): the users of
+        one forward, lock-step batch or session then each run under the adapter they name -- `adapter=` / `adapters=` of BSSD, BSSD_batch,
+        target_generate(_batch) and BSSDSession.submit -- or under none.  `adapter`, `r`, `lora_alpha`, `use_rslora` and the refusals are
+        `load_lora`'s.  `adapters` maps name -> slot.  A duplicate name is a ValueError; a model-wide `load_lora` adapter and resident
+        ones exclude each other (AtSpeedError ERR_INVALID), the 17th is AtSpeedError ERR_CAPACITY."""
+        if not isinstance(name, str) or not name:
+            raise ValueError(f"add_lora: the adapter's name must be a non-empty string, not {name!r}")
+        if name in self.adapters:
+            raise ValueError(f"add_lora: an adapter named {name!r} is resident already (slot {self.adapters[name]}): remove_lora it first")
+        ad = _lora.read(adapter, self.dims.n_layers, self.dims.hidden, r, lora_alpha, use_rslora)
+        self.adapters[name] = self._resident_add(ad)
+        self.adapter_info[name] = SimpleNamespace(r=ad.r, lora_alpha=ad.lora_alpha, scaling=ad.scaling, modules=ad.modules)
+        return self
+
+    def remove_lora(self, name: str) -> "HipLlama":
+        """Free the resident adapter `name`.  No user of a call or session in flight may name it.  With the last one gone the model runs
+        bit for bit, and launch for launch, as one that never had an adapter."""
+        self._resident_remove(self.adapter_slot(name))
+        del self.adapters[name], self.adapter_info[name]
+        return self
+
+    def adapter_slot(self, name: Optional[str]) -> int:
+        """the library slot of a resident adapter's name; None -> 0 (no adapter).  KeyError (naming the known ones) for an unknown name"""
+        if name is None:
+            return 0
+        try:
+            return self.adapters[name]
+        except (KeyError, TypeError):
+            raise KeyError(f"no resident adapter named {name!r} on this model (add_lora); resident: {sorted(self.adapters)}") from None
+
+    def _resident_add(self, ad) -> int:
+        slot = C.c_int32(0)
+        with torch.cuda.device(self._device):
+            arr, keep = self._lora_layers(ad)
+            _lib.check(_lib.load().atspeed_llama_add_lora(self._handle, ad.r, ad.scaling, arr, _lib.stream_ptr(self._device), C.byref(slot)))
+        del keep                       # the library holds copies of its own
+        return int(slot.value)
+
+    def _resident_remove(self, slot: int) -> None:
+        _lib.check(_lib.load().atspeed_llama_remove_lora(self._handle, slot))
 
     def lora_launches(self, reset: bool = False) -> int:
         """Adapter kernels launched since the last reset: 2 per layer per forward with an adapter, 0 without (atspeed_llama_lora_launches)."""
@@ -415,12 +465,16 @@ class HipLlama:
         Returns fp32 logits [n_logit_rows, vocab] of the last rows."""
         return self.forward_padded(ids, pos, slots, vis_bits, n_slots, n_logit_rows)[:, : self.dims.vocab_size]
 
-    def forward_raw_batch(self, seqs, return_all: bool = False):
+    def forward_raw_batch(self, seqs, return_all: bool = False, adapters=None):
         """Several independent sequences in ONE forward.  `seqs`: list of (ids, pos, slots, vis_bits, n_slots, n_logit_rows) with CPU
         tensors shaped as in `forward_raw`.  Returns one fp32 [n_logit_rows, vocab] view per sequence (views of one buffer), or with
-        `return_all` the buffer itself, [sum of n_logit_rows, vocab], sequences one after the other."""
-        lib = _lib.load()
+        `return_all` the buffer itself, [sum of n_logit_rows, vocab], sequences one after the other.  `adapters`: one resident adapter's
+        name (`add_lora`) or None per sequence."""
         n = len(seqs)
+        if adapters is not None and len(adapters) != n:
+            raise ValueError(f"forward_raw_batch: adapters needs one name (or None) per sequence: {len(adapters)} for {n} sequences")
+        ad = np.array([self.adapter_slot(a) for a in adapters] if adapters is not None else [0] * n, dtype=np.int32)
+        lib = _lib.load()
         W = self.max_slots // 64
         for ids, pos, slots, vis, _, _ in seqs:
             assert ids.dtype == pos.dtype == slots.dtype == torch.int32 and vis.dtype == torch.int64
@@ -439,8 +493,9 @@ class HipLlama:
             a_vis = ptrs(vis.data_ptr(), W * 8)
             rows = int(nl.sum())
             raw = torch.empty(rows * self.logits_ld, dtype=torch.float32, device=self._device)
-            _lib.check(lib.atspeed_llama_forward_batch(self._handle, n, a_ids, a_pos, a_slot, a_vis, nt.ctypes.data, ns.ctypes.data,
-                                                       nl.ctypes.data, raw.data_ptr(), _lib.stream_ptr(self._device)))
+            _lib.check(lib.atspeed_llama_forward_batch_adapters(self._handle, n, a_ids, a_pos, a_slot, a_vis, nt.ctypes.data, ns.ctypes.data,
+                                                                nl.ctypes.data, ad.ctypes.data if adapters is not None else None,
+                                                                raw.data_ptr(), _lib.stream_ptr(self._device)))
         out = raw.view(rows, self.logits_ld)[:, : self.dims.vocab_size]
         if return_all:
             return out

@@ -234,6 +234,41 @@ int atspeed_llama_clear_lora(atspeed_llama* m);
 /* shrink + expand launches since the last reset (2 per layer per forward with an adapter, 0 without); -1 on a NULL model */
 int64_t atspeed_llama_lora_launches(atspeed_llama* m, int32_t reset);
 
+/* ---- several RESIDENT adapters on one model, picked per user.  A model holds up to ATSPEED_LORA_MAX_ADAPTERS adapters in
+ * slots 1 .. 16, each with its own rank and scaling; every user of a forward, a lock-step batch or a session names one of them (or 0 = none)
+ * and the two side-path kernels pick the adapter per token row.  The arithmetic per row is that of the model-wide adapter above.
+ * atspeed_llama_add_lora: atspeed_llama_set_lora's arguments, checks and memory contract (library-owned zero-padded copies in one allocation
+ *   per adapter, made on `stream` and waited for: the caller's tensors may be freed on return; the lora_A output buffer is made sure of here,
+ *   nothing is allocated inside a forward afterwards); the adapter goes into the lowest free slot, returned in *slot_out.  No free slot:
+ *   ATSPEED_ERR_CAPACITY, and the model is as it was.
+ * atspeed_llama_remove_lora: frees the slot (ATSPEED_ERR_INVALID for one that is not occupied).  Removing a slot that a decoder still names
+ *   makes that decoder's next generate call return ATSPEED_ERR_INVALID before anything is launched; removing one that a queued or in-lane
+ *   user of a live session names is the caller's error: the round that finds it returns ATSPEED_ERR_INVALID and ends the users in lanes, as
+ *   any failed round does.
+ * Both wait for the device to be idle and drop the model's captured graphs.  The kernels read the slots from a device table the model owns,
+ *   at a fixed address and rewritten by these two calls alone, and the user's slot from the segment table, so a captured forward stays valid
+ *   whatever the users of a later replay name.
+ * The model-wide adapter and resident slots exclude each other: atspeed_llama_set_lora on a model with occupied slots and atspeed_llama_add_lora
+ *   on a model that holds a model-wide adapter return ATSPEED_ERR_INVALID.
+ * A model with at least one occupied slot runs every forward as a model with an adapter does (one shrink and one expand launch per layer,
+ *   counted by atspeed_llama_lora_launches; plain qkv store, no fused RoPE epilogue, no row-pruned tail, no staged verification), whatever
+ *   its users name; rows of slot 0 take the unadapted arithmetic bit for bit.  After the last slot is removed the model runs launch for launch
+ *   as one that never had an adapter. */
+#define ATSPEED_LORA_MAX_ADAPTERS 16
+/* one slot of one layer as the kernels read it (the model's table, and the bare kernel entry points below): DEVICE pointers in the model's
+ * dtype to the stacked zero-padded A_cat [3 r16][hidden] (q, k, v thirds; an absent module's rows are zero) and B_m [hidden][r16] (NULL =
+ * module not adapted), r16 = rank rounded up to 16 (16 .. 64); entry 0 of a table means "none" and is never read */
+typedef struct atspeed_lora_slot { const void *a_cat, *b_q, *b_k, *b_v; int32_t r16; float scaling; } atspeed_lora_slot;
+int atspeed_llama_add_lora(atspeed_llama* m, int32_t rank, float scaling, const atspeed_lora_layer* layers, void* stream, int32_t* slot_out);
+int atspeed_llama_remove_lora(atspeed_llama* m, int32_t slot);
+int32_t atspeed_llama_lora_slots(const atspeed_llama* m);          /* occupied slots; -1 on a NULL model */
+/* atspeed_llama_forward_batch with one resident slot per sequence: adapters = HOST array [n] of slots (0 = none), NULL = all 0.  A slot that is
+ * not occupied: ATSPEED_ERR_INVALID before anything is launched. */
+int atspeed_llama_forward_batch_adapters(atspeed_llama* m, int32_t n, const int32_t* const* ids_dev, const int32_t* const* pos_dev,
+                                         const int32_t* const* slots_dev, const uint64_t* const* vis_bits_dev, const int32_t* n_tokens,
+                                         const int32_t* n_slots_visible, const int32_t* n_logit_rows, const int32_t* adapters /* [n], NULL = all 0 */,
+                                         float* logits_out_dev, void* stream);
+
 /* lm_head fused with the full-vocabulary normaliser of beamSD.py:58,285 (log_softmax over ALL columns, before masking): bf16
  * x [rows, hidden] times w [vocab, hidden]^T -> fp32 logits (row stride ld) and lse[row] = log sum_v exp(logits[row][v]).  On the
  * batched path (rows >= 257 and a tile grid that fills the chip) the (max, sum exp) partials come out of the GEMM epilogue, the
@@ -478,6 +513,23 @@ int atspeed_decoder_set_node_mask(atspeed_decoder* d, const atspeed_node_masks* 
 int atspeed_session_submit_masked(atspeed_session* s, const int32_t* prompt_ids_dev, int32_t prompt_len, int32_t start_node, uint32_t seed,
                                   int32_t* out_tokens_dev, float* out_scores_dev, atspeed_gen_stats* stats_host,
                                   const atspeed_node_masks* masks, int32_t user, int64_t* ticket_out);
+/* ---- a user's resident adapter (atspeed_llama_add_lora).
+ * atspeed_decoder_set_adapter: the slot of the decoder's TARGET that the generate calls made with this decoder run under (atspeed_bssd_generate,
+ *   _batch, atspeed_target_generate, _batch and every target forward they make); 0, the default, = none.  The draft model is never adapted.
+ *   Like the sampling mode it stays until it is set again.  The slot is looked up when a generate call starts: one that is not occupied then
+ *   makes the call return ATSPEED_ERR_INVALID before anything is launched.
+ * atspeed_session_submit_ex: the session's one submit entry with every per-user property in a struct (struct_size = sizeof(atspeed_session_user):
+ *   a shorter struct of an older caller leaves the members it does not have at 0); atspeed_session_submit and _submit_masked forward to it with
+ *   adapter 0.  The adapter follows the user to whichever lane admits it, as the seed and the filter do, and is validated here. */
+int atspeed_decoder_set_adapter(atspeed_decoder* d, int32_t slot);
+typedef struct atspeed_session_user {
+  size_t struct_size;              /* sizeof(atspeed_session_user) of the caller's build                                */
+  const int32_t* prompt_ids_dev; int32_t prompt_len; int32_t start_node; uint32_t seed;
+  int32_t* out_tokens_dev; float* out_scores_dev; atspeed_gen_stats* stats_host;
+  const atspeed_node_masks* masks; int32_t mask_user;   /* item filter, NULL = none (atspeed_session_submit_masked)     */
+  int32_t adapter;                 /* resident slot of the session's target, 0 = none                                    */
+} atspeed_session_user;
+int atspeed_session_submit_ex(atspeed_session* s, const atspeed_session_user* u, int64_t* ticket_out);
 /* The step and the cutoff kernel alone under a filter (tests): their unmasked twins' arguments plus (masks, user); masks = NULL: the twin. */
 int atspeed_beam_expand_prune_masked(const float* logits_dev, int32_t ld, const float* lse_dev,
                                      const float* beam_score_dev, const int32_t* beam_node_dev, int32_t n_rows,
@@ -683,6 +735,22 @@ int atspeed_segs_rope_kv(void* qkv_dev, const float* slabs_dev /* may be NULL */
 int atspeed_segs_lora_rope_kv(void* qkv_dev, const void* u_dev, const void* b_q_dev, const void* b_k_dev, const void* b_v_dev, int32_t r16,
                               float scaling, const float* cos_dev, const float* sin_dev, size_t layer_off_bytes, int32_t n_heads, int32_t head_dim,
                               int32_t max_pos, int32_t dtype, ATSPEED_SEGMENTS, void* stream);
+/* The two adapter kernels with the adapter picked PER SEGMENT (resident adapters, atspeed_llama_add_lora; tests/test_lora_multi_gpu.py):
+ * slots_host = HOST array of n_slots (1 .. ATSPEED_LORA_MAX_ADAPTERS + 1) entries, index 0 ignored; seg_adapters = HOST array [n] of indices
+ * into it (0 = none).  The calls stage the slot array to the device.  u_dev has a FIXED row stride of 3 * ATSPEED_LORA_MAX_RANK elements,
+ * whatever the ranks: row r of a segment with slot a holds that slot's 3 * r16 outputs (q, k, v thirds of r16 each) from element 0 on.
+ * atspeed_segs_lora_shrink_multi: atspeed_lora_shrink per row with the row's slot's a_cat and r16.  Writes u_dev [row][0 .. 3 r16) of the rows
+ *   whose segment names a slot > 0 and nothing else: rows of slot 0 and the columns from 3 r16 on are not written.  A row's result does not
+ *   depend on its place in the batch nor on what the other rows name: it equals atspeed_lora_shrink of that row with that slot bit for bit.
+ *   16-bit with hidden % 128 == 0 and 16-byte aligned h, norm_w, u and a_cat takes the MFMA kernel, everything else one workgroup per row.
+ * atspeed_segs_lora_rope_kv_multi: atspeed_segs_lora_rope_kv per row with (b_q, b_k, b_v, r16, scaling) of the row's slot; a row of slot 0
+ *   and a module whose b is NULL in the row's slot take atspeed_segs_rope_kv's path bit for bit.  u rows of slot 0 are never read.  On the
+ *   16-bit vector path (head_dim % 16 == 0) u_dev and every b must be 16-byte aligned. */
+int atspeed_segs_lora_shrink_multi(const void* h_dev, const void* norm_w_dev, const atspeed_lora_slot* slots_host, int32_t n_slots, void* u_dev,
+                                   int32_t hidden, float eps, int32_t dtype, const int32_t* seg_adapters, ATSPEED_SEGMENTS, void* stream);
+int atspeed_segs_lora_rope_kv_multi(void* qkv_dev, const void* u_dev, const atspeed_lora_slot* slots_host, int32_t n_slots, const float* cos_dev,
+                                    const float* sin_dev, size_t layer_off_bytes, int32_t n_heads, int32_t head_dim, int32_t max_pos, int32_t dtype,
+                                    const int32_t* seg_adapters, ATSPEED_SEGMENTS, void* stream);
 /* atspeed_tree_attention_tiled over several segments in one launch: row r of segment i attends to the slots < n_slots_visible[i] of that
  * segment's own caches (at layer_off_bytes) whose bit is set in its visibility words (reads vis, kcache, vcache).  qtile_rows 0 = the engine's
  * choice (128 from 16 segments or when half the segments exceed 96 rows, else 64); rows_per_wave as atspeed_tree_attention_tiled.  packed_out =
