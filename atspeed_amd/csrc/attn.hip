@@ -13,8 +13,9 @@
 //    static LDS tile.  Softmax in the natural-exponent domain.  Grids above 256 workgroups and the 256-row tile.
 //  * tree_attn_mfma_kernel<DH, NW, 4>: the same products and softmax behind a ring of four tiles filled by LDS-DMA with hand-counted
 //    waits; 4 / 8 waves.  One user's forwards (up to 256 workgroups).
-//  * tree_attn32_kernel<DH, NW>: 32 query rows per wave (MFMA 32x32x16), 2 / 4 / 8 waves; LDS-DMA into a double buffer.  Softmax in the
-//    log2 domain, O rescaled only when a maximum moved.  Lock-step batches (512 workgroups and more).
+//  * tree_attn32_kernel<DH, NW, NBUF>: 32 query rows per wave (MFMA 32x32x16), 2 / 4 / 8 waves; LDS-DMA into a double buffer (4 / 8 waves) or
+//    into ONE tile buffer (2 waves: the 64-row tile of short segments, four workgroups per CU).  Softmax in the log2 domain, O rescaled only
+//    when a maximum moved.  Lock-step batches (512 workgroups and more).
 //  * tree_attn_kernel<T> (fp32 parity mode / other head dims): one wave per (token, head), scalar, __expf.
 // What the forms share is defined once (AttnTile, ATS_ATTN_DMA_TILE, attn_work_item, attn_rows, vis_tail_mask); the softmax arithmetic is each form's own.
 #include "internal.h"
@@ -137,7 +138,7 @@ template <int DH> struct AttnTile {
   static constexpr int NI = KCH + VCH;               // DMA instructions per tile (K: KCH, V: VCH), dealt round-robin to the waves
   // DMA instructions ONE wave of nw issues per tile: the first NI % nw waves one more.  The hand-counted vmcnt waits are multiples of these
   static constexpr int dma_per_wave(int nw, bool first_waves) { return first_waves ? (NI + nw - 1) / nw : NI / nw; }
-  static constexpr size_t lds_double() { return 2 * (size_t)TILE; }                   // tree_attn32_kernel: [2][K tile | V tile]
+  static constexpr size_t lds_tiles(int nbuf) { return (size_t)nbuf * TILE; }          // tree_attn32_kernel: [NBUF][K tile | V tile]
   static constexpr size_t lds_ring(int nstg, int rows, int vis_words) { return (size_t)nstg * TILE + (size_t)rows * vis_words * sizeof(uint64_t); }
 };
 constexpr int kAttnLdsCap = 160 * 1024 - 64, kRingStages = 4;         // dynamic LDS a workgroup may ask for; tiles in the DMA ring
@@ -399,8 +400,11 @@ __global__ __launch_bounds__(64 * NW) void tree_attn_mfma_kernel(const bf16_t* _
 //   16t + 8*(j/4) + 4*hi + (j%4)); the A operand takes the same keys out of the row-major V tile with two transposed reads.
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
-// K / V tiles travel HBM -> LDS by LDS-DMA (ATS_ATTN_DMA_TILE) into a double buffer, tile kt+1 while tile kt is multiplied; ONE barrier per tile.
-template <int DH, int NW>   // NW waves per workgroup = 32*NW query rows per tile
+// K / V tiles travel HBM -> LDS by LDS-DMA (ATS_ATTN_DMA_TILE).  NBUF = 2: into a double buffer, tile kt+1 while tile kt is multiplied; ONE barrier
+// per tile.  NBUF = 1 (the 64-row tile of short segments): ONE tile buffer, fetched and awaited in front of its products, two barriers per tile.
+// Nothing overlaps inside the workgroup: a CU holds four such workgroups (34 816 B of LDS each) where it holds two double-buffered ones, and
+// the tiles in flight on a CU -- what bounds this kernel -- are the workgroups' (DESIGN.md section 17).
+template <int DH, int NW, int NBUF = 2>   // NW waves per workgroup = 32*NW query rows per tile
 __global__ __launch_bounds__(64 * NW, 2) void tree_attn32_kernel(const bf16_t* __restrict__ q, int ldq, const SegTable* __restrict__ tab,
                                                                  size_t layer_off, int vis_words, bf16_t* __restrict__ out, int ldo, int pk,
                                                                  int n_heads, float scale) {
@@ -409,7 +413,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tree_attn32_kernel(const bf16_t* _
   constexpr int DB = DH / 32;                 // 32-row blocks of O^T
   constexpr int KS = DH / 16;                 // k-steps of the QK product
   constexpr int SWZ = KCH - 1;                // K swizzle mask of this kernel: the DMA fill and kpos, which the S^T fragment reads go through
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][K tile | V tile]
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [NBUF][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lc = lane & 31, hi = lane >> 5;
   const AttnWork wk = attn_work_item(tab->n_qtiles);
@@ -423,7 +427,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tree_attn32_kernel(const bf16_t* _
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   auto dma_tile = ATS_ATTN_DMA_TILE(G, NW, SWZ);
   const int n_tiles = (n_slots + 63) >> 6;
-  if (n_tiles > 0) dma_tile(0, 0);
+  if (NBUF == 2 && n_tiles > 0) dma_tile(0, 0);        // (one buffer: the query fragments leave first, tile 0 in the loop)
   s16x8_t qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -440,12 +444,23 @@ __global__ __launch_bounds__(64 * NW, 2) void tree_attn32_kernel(const bf16_t* _
 
   auto kpos = [](int r, int c) { return (r * KCH + (c ^ (r & SWZ))) * 16; };
   for (int kt = 0; kt < n_tiles; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile kt have landed
-    __syncthreads();                                   // everyone's have, and the other buffer is fully consumed
-    if (kt + 1 < n_tiles) dma_tile(kt + 1, (kt + 1) & 1);
-    const unsigned char* ks_lds = smem + (kt & 1) * G::TILE;
+    uint64_t word;
+    if constexpr (NBUF == 1) {
+      // both barriers stand in front of the wave-uniform `continue`s below: a wave whose rows see nothing of a tile still arrives at them
+      __syncthreads();                                   // everyone is done with the previous tile
+      dma_tile(kt, 0);
+      word = rw.qok ? rw.vis_row[kt] : 0ull;             // (travels with the tile)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile kt have landed
+      __syncthreads();                                   // everyone's have
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile kt have landed
+      __syncthreads();                                   // everyone's have, and the other buffer is fully consumed
+      if (kt + 1 < n_tiles) dma_tile(kt + 1, (kt + 1) & 1);
+      word = rw.qok ? rw.vis_row[kt] : 0ull;
+    }
+    const unsigned char* ks_lds = smem + (NBUF == 2 ? kt & 1 : 0) * G::TILE;
     const unsigned char* vs_lds = ks_lds + G::KBYTES;
-    const uint64_t word = vis_tail_mask(rw.qok ? rw.vis_row[kt] : 0ull, kt, n_tiles, n_slots);
+    word = vis_tail_mask(word, kt, n_tiles, n_slots);
     if (__ballot(word != 0ull) == 0ull) continue;      // this wave's 32 rows see nothing here (wave-uniform)
 
     // V^T fragments: 16-lane group gg = lane >> 4 takes d-columns 16*(gg & 1) .. +15 of the block and the 4 keys 4*hi .. +3 (second
@@ -545,10 +560,11 @@ int launch_attn(dim3 grid, int block, size_t lds, int lds_limit, hipStream_t st,
 // one selection per kernel family: the caller picks DH from head_dim (64 | 128), the waves of a query tile pick NW
 template <int DH>
 int launch_attn32(int nw, dim3 grid, hipStream_t st, const AttnArgs& a) {            // nw = tile rows / 32: 2 | 4 | 8
-  constexpr int lds_bytes = (int)AttnTile<DH>::lds_double();
-  if (nw == 8) return launch_attn<tree_attn32_kernel<DH, 8>>(grid, 512, lds_bytes, lds_bytes, st, a);
-  if (nw == 4) return launch_attn<tree_attn32_kernel<DH, 4>>(grid, 256, lds_bytes, lds_bytes, st, a);
-  return launch_attn<tree_attn32_kernel<DH, 2>>(grid, 128, lds_bytes, lds_bytes, st, a);
+  constexpr int lds2 = (int)AttnTile<DH>::lds_tiles(2), lds1 = (int)AttnTile<DH>::lds_tiles(1);
+  ats_count_path(nw == 2 ? ATS_PATH_ATTN32_1BUF : ATS_PATH_ATTN32_2BUF);
+  if (nw == 8) return launch_attn<tree_attn32_kernel<DH, 8>>(grid, 512, lds2, lds2, st, a);
+  if (nw == 4) return launch_attn<tree_attn32_kernel<DH, 4>>(grid, 256, lds2, lds2, st, a);
+  return launch_attn<tree_attn32_kernel<DH, 2, 1>>(grid, 128, lds1, lds1, st, a);      // 64-row tiles: the single-buffered form
 }
 template <int DH>
 int launch_attn_ring(int nw, dim3 grid, size_t ring_lds, hipStream_t st, const AttnArgs& a) {   // nw = tile rows / 16: 4 | 8

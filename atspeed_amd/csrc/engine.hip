@@ -63,7 +63,8 @@ const SwDef kSwitches[ATS_N_SW] = {{"gemm_sk", "ATSPEED_GEMM_SK", 1},           
                                    {"verify_staged", "ATSPEED_VERIFY_STAGED", 1},
                                    {"verify_staged_tokens", "ATSPEED_VERIFY_STAGED_TOKENS", ATS_VERIFY_STAGED_TOKENS},
                                    {"verify_staged_pass_tokens", "ATSPEED_VERIFY_STAGED_PASS_TOKENS", ATS_VERIFY_STAGED_PASS_TOKENS},
-                                   {"tail_rows_tokens", "ATSPEED_TAIL_ROWS_TOKENS", ATS_TAIL_ROWS_TOKENS}};
+                                   {"tail_rows_tokens", "ATSPEED_TAIL_ROWS_TOKENS", ATS_TAIL_ROWS_TOKENS},
+                                   {"attn_short", "ATSPEED_ATTN_SHORT", 1}};
 std::atomic<int> g_switch[ATS_N_SW];
 std::once_flag g_switch_once;
 void switches_init() {
@@ -1476,6 +1477,12 @@ int ats_seg_finish(SegTable& t, int qtile_rows) {
   // lock-step batches (thousands of workgroups) run the 32-rows-per-wave kernel: its 4-wave 128-row tile also wins on short segments
   // (the idle waves still carry a quarter of the tile's DMA): 249 vs 286 us at 256 users
   if (t.n >= 16) t.qtile_rows = 128;
+  // (that was the 64-row tile behind a double buffer).  Where every segment fits a 64-row tile (a round's 20-row inputs, a phase's 40-row
+  // block) the batch takes 64-row tiles all the same: their 32-rows-per-wave launch is single-buffered now, four workgroups per CU instead
+  // of two -- 150 vs 191 us at 256 users x 20 rows, 201 vs 241 us at 40 rows (profiles/attn_short_ab.txt)
+  int max_tok = 0;
+  for (int i = 0; i < t.n; ++i) max_tok = std::max(max_tok, t.seg[i].n_tok);
+  if (t.n >= 16 && max_tok <= 64 && ats_switch(ATS_SW_ATTN_SHORT)) t.qtile_rows = 64;
   if (qtile_rows) t.qtile_rows = qtile_rows;
   for (int i = 0; i < t.n; ++i) {
     t.seg[i].row0 = t.total_tok; t.total_tok += t.seg[i].n_tok;

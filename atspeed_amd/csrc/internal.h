@@ -56,6 +56,7 @@ constexpr int ATS_SK_ARENA_COUNTERS = 256;
 enum { ATS_PATH_RING = 0, ATS_PATH_RING_SK = 1, ATS_PATH_WDMA = 2, ATS_PATH_WDMA_SPLIT = 3, ATS_PATH_RING_SPLIT = 4, ATS_PATH_TILED = 5,
        ATS_PATH_FP8_RING = 6, ATS_PATH_FP8_WDMA = 7, ATS_PATH_FP8_WDMA_SPLIT = 8, ATS_PATH_PANEL = 9, ATS_PATH_PANEL_SPLIT = 10, ATS_PATH_FP8_RING_SPLIT = 11,
        ATS_PATH_FP4 = 12 /* W4A8 (gemm_w4a8_kernel), any form */,
+       ATS_PATH_ATTN32_1BUF = 13, ATS_PATH_ATTN32_2BUF = 14 /* launches of tree_attn32_kernel by tile buffers: the same counters tell a test which attention form a table took */,
        ATS_N_PATHS = 16 };
 extern std::atomic<long long> g_ats_path_cnt[ATS_N_PATHS];          // engine.hip
 // device / pinned allocations, events, streams and graphs the library makes ON DEMAND, process-wide (engine.hip; every site that can be reached
@@ -77,6 +78,7 @@ enum { ATS_SW_GEMM_SK = 0,        // "gemm_sk"       ATSPEED_GEMM_SK (1): ring k
        ATS_SW_VERIFY_STAGED_TOKENS, // "verify_staged_tokens" ATSPEED_VERIFY_STAGED_TOKENS: the threshold T* -- only a round whose packed target forward would exceed it is staged
        ATS_SW_VERIFY_STAGED_PASS_TOKENS, // "verify_staged_pass_tokens" ATSPEED_VERIFY_STAGED_PASS_TOKENS: rows a staged round must expect to skip per phase it expects to add; 0 = T* alone decides
        ATS_SW_TAIL_ROWS_TOKENS,   // "tail_rows_tokens" ATSPEED_TAIL_ROWS_TOKENS: a forward of more tokens runs the last layer's o_proj / MLP over its logit rows only -- 0 always, a huge value never
+       ATS_SW_ATTN_SHORT,         // "attn_short" ATSPEED_ATTN_SHORT (1): a lock-step table of segments of at most 64 rows takes 64-row query tiles (the single-buffered 32-rows-per-wave launch) -- 0 = 128-row tiles as before
        ATS_N_SW };
 int ats_switch(int id);
 

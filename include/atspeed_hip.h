@@ -601,7 +601,8 @@ int atspeed_gemm(const void* a_dev, const void* w_dev, void* c_dev, int32_t m, i
 /* Which kernel family the library's GEMM launches took since the last reset (dispatch is a fitted cost model: tests assert the path they
  * mean to exercise).  out[i], i < n: 0 ring kernel, 1 ring kernel with its split-K tail, 2 weight-streaming kernel, 3 the same split in K,
  * 4 ring kernel in split-K mode, 5 LDS-tiled kernel, 6 fp8 ring kernel, 7 / 8 fp8 weight-streaming kernel / split, 9 / 10 panel kernel /
- * split, 11 fp8 ring kernel cut in K, 12 W4A8 kernel (any form).  Returns the number of counters the library keeps. */
+ * split, 11 fp8 ring kernel cut in K, 12 W4A8 kernel (any form); 13 / 14 count launches of the 32-rows-per-wave attention kernel, by its
+ * single-buffered 64-row tile / its double-buffered 128- and 256-row tiles.  Returns the number of counters the library keeps. */
 int atspeed_gemm_path_counters(int64_t* out, int32_t n, int32_t reset);
 /* Process-wide tuning / test switches.  Each is an int read ONCE from its environment variable when the library first needs one (the
  * variable is the way to set it for a whole run) and changeable afterwards only through this call (tests and sweeps that compare two
@@ -612,7 +613,8 @@ int atspeed_gemm_path_counters(int64_t* out, int32_t n, int32_t reset);
  * "verify_staged_pass_tokens" (ATSPEED_VERIFY_STAGED_PASS_TOKENS, the measured cost of a phase in tokens),
  * "tail_rows_tokens" (ATSPEED_TAIL_ROWS_TOKENS, 512: a forward of more tokens, at most half of whose rows get logits, runs the last layer's
  * o_proj / gate_up / down over its logit rows only -- 0 every such forward, a huge value none; 16-bit and fp32 models without W8A8 / W4A8
- * copies and without adapter); meanings in INTEGRATION.md.  Unknown name: ATSPEED_ERR_INVALID. */
+ * copies and without adapter), "attn_short" (ATSPEED_ATTN_SHORT, 1: a lock-step batch whose segments all have at most 64 rows attends in
+ * 64-row query tiles, 0 in 128-row tiles; bit-identical); meanings in INTEGRATION.md.  Unknown name: ATSPEED_ERR_INVALID. */
 int atspeed_set_switch(const char* name, int32_t value);
 int atspeed_get_switch(const char* name, int32_t* value_out);
 /* atspeed_gemm / atspeed_gemm_fp8 on operands in the packed layout (a / xq and w / wq through atspeed_pack_rows; K % 32 == 0, for fp8 K % 64 == 0):
