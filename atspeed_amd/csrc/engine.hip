@@ -1115,13 +1115,21 @@ extern "C" int atspeed_segs_tree_attention(const void* q, int32_t ldq, size_t la
                                                packed_out ? 1 : 0));
 }
 
-// atspeed_segs_rope_kv with the adapter's expand in front (lora_rope_kv_segs kernels; header: the memory contract); tests/test_lora_gpu.py
+// what atspeed_segs_lora_rope_kv and its per-segment form ask of the arguments they share
+static int segs_lora_rope_args(const char* who, const void* qkv, const void* u, const float* cos_tab, const float* sin_tab, size_t layer_off_bytes,
+                               int32_t n_heads, int32_t head_dim, int32_t max_pos, int32_t dtype) {
+  ATS_REQUIRE(qkv && u && cos_tab && sin_tab && n_heads >= 1 && head_dim >= 2 && head_dim % 2 == 0 && max_pos >= 1 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID,
+              "%s: bad arguments", who);
+  ATS_REQUIRE(((uintptr_t)qkv & 15) == 0 && layer_off_bytes % 16 == 0, ATSPEED_ERR_INVALID, "%s: qkv and the layer offset must be 16-byte aligned", who);
+  return ATSPEED_OK;
+}
+
+// atspeed_segs_rope_kv with the adapter's expand in front (lora_rope_kv_segs kernels with one adapter for every row; header: the memory
+// contract); tests/test_lora_gpu.py
 extern "C" int atspeed_segs_lora_rope_kv(void* qkv, const void* u, const void* b_q, const void* b_k, const void* b_v, int32_t r16, float scaling,
                                          const float* cos_tab, const float* sin_tab, size_t layer_off_bytes, int32_t n_heads, int32_t head_dim,
                                          int32_t max_pos, int32_t dtype, ATS_SEGS_PARAMS, void* stream) {
-  ATS_REQUIRE(qkv && u && cos_tab && sin_tab && n_heads >= 1 && head_dim >= 2 && head_dim % 2 == 0 && max_pos >= 1 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID,
-              "segs_lora_rope_kv: bad arguments");
-  ATS_REQUIRE(((uintptr_t)qkv & 15) == 0 && layer_off_bytes % 16 == 0, ATSPEED_ERR_INVALID, "segs_lora_rope_kv: qkv and the layer offset must be 16-byte aligned");
+  ATS_TRY(segs_lora_rope_args("segs_lora_rope_kv", qkv, u, cos_tab, sin_tab, layer_off_bytes, n_heads, head_dim, max_pos, dtype));
   SegTable t{}; const SegTable* dt = nullptr;
   ATS_TRY(segs_table("segs_lora_rope_kv", SEGS_POS | SEGS_SLOTS | SEGS_KV, 0, ATS_SEGS_ARGS, (hipStream_t)stream, t, &dt));
   return ATS_KD(dtype, ats_lora_rope_kv_segs(qkv, u, b_q, b_k, b_v, r16, scaling, t, dt, cos_tab, sin_tab, layer_off_bytes, n_heads, head_dim, max_pos, dtype,
@@ -1153,7 +1161,7 @@ static int segs_lora_slots(const char* who, const atspeed_lora_slot* slots, int3
   return ATSPEED_OK;
 }
 
-// lora_shrink with the adapter picked per segment (lora_shrink_segs kernels; header: the memory contract); tests/test_lora_multi_gpu.py
+// lora_shrink with the adapter picked per segment (the shrink kernels over LoraBySeg; header: the memory contract); tests/test_lora_multi_gpu.py
 extern "C" int atspeed_segs_lora_shrink_multi(const void* h, const void* norm_w, const atspeed_lora_slot* lora_slots, int32_t n_slots, void* u, int32_t hidden,
                                               float eps, int32_t dtype, const int32_t* seg_adapters, ATS_SEGS_PARAMS, void* stream) {
   ATS_REQUIRE(h && norm_w && u && hidden > 0 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID, "segs_lora_shrink_multi: bad arguments");
@@ -1165,13 +1173,11 @@ extern "C" int atspeed_segs_lora_shrink_multi(const void* h, const void* norm_w,
   return ATS_KD(dtype, ats_lora_shrink_segs(h, norm_w, dslots, aligned, u, t, dt, hidden, eps, dtype, (hipStream_t)stream));
 }
 
-// atspeed_segs_lora_rope_kv with the adapter picked per segment (lora_rope_kv_segs_multi kernels); tests/test_lora_multi_gpu.py
+// atspeed_segs_lora_rope_kv with the adapter picked per segment (the same kernels over LoraBySeg); tests/test_lora_multi_gpu.py
 extern "C" int atspeed_segs_lora_rope_kv_multi(void* qkv, const void* u, const atspeed_lora_slot* lora_slots, int32_t n_slots, const float* cos_tab,
                                                const float* sin_tab, size_t layer_off_bytes, int32_t n_heads, int32_t head_dim, int32_t max_pos,
                                                int32_t dtype, const int32_t* seg_adapters, ATS_SEGS_PARAMS, void* stream) {
-  ATS_REQUIRE(qkv && u && cos_tab && sin_tab && n_heads >= 1 && head_dim >= 2 && head_dim % 2 == 0 && max_pos >= 1 && segs_dtype_ok(dtype), ATSPEED_ERR_INVALID,
-              "segs_lora_rope_kv_multi: bad arguments");
-  ATS_REQUIRE(((uintptr_t)qkv & 15) == 0 && layer_off_bytes % 16 == 0, ATSPEED_ERR_INVALID, "segs_lora_rope_kv_multi: qkv and the layer offset must be 16-byte aligned");
+  ATS_TRY(segs_lora_rope_args("segs_lora_rope_kv_multi", qkv, u, cos_tab, sin_tab, layer_off_bytes, n_heads, head_dim, max_pos, dtype));
   const atspeed_lora_slot* dslots = nullptr;
   bool aligned = false;
   ATS_TRY(segs_lora_slots("segs_lora_rope_kv_multi", lora_slots, n_slots, seg_adapters, n, false, (hipStream_t)stream, &dslots, &aligned));

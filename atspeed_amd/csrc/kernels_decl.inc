@@ -29,9 +29,9 @@ int ats_lora_shrink(const void* h, const void* norm_w, const void* a_cat, void* 
 int ats_lora_rope_kv_segs(void* qkv, const void* u, const void* bq, const void* bk, const void* bv, int r16, float scaling, const SegTable& t,
                           const SegTable* dt, const float* cos_tab, const float* sin_tab, size_t layer_off_bytes, int n_heads, int head_dim,
                           int max_pos, int dtype, hipStream_t st);
-// the two above with the adapter picked per row (Seg::adapter -> dev_slots[adapter], DEVICE table of ATSPEED_LORA_MAX_ADAPTERS + 1 entries, entry
-// 0 = none); u has a fixed row stride of 3 x 64 elements, rows of slot 0 are neither written nor read.  slots_aligned: every a_cat is 16-byte
-// aligned (the MFMA shrink's operand loads)
+// the two above with the adapter picked per row -- the same kernels over the adapter source LoraBySeg instead of LoraOne (Seg::adapter ->
+// dev_slots[adapter], DEVICE table of ATSPEED_LORA_MAX_ADAPTERS + 1 entries, entry 0 = none); u has a fixed row stride of 3 x 64 elements, rows
+// of slot 0 are neither written nor read.  slots_aligned: every a_cat is 16-byte aligned (the MFMA shrink's operand loads)
 int ats_lora_shrink_segs(const void* h, const void* norm_w, const atspeed_lora_slot* dev_slots, bool slots_aligned, void* u, const SegTable& t,
                          const SegTable* dt, int hidden, float eps, int dtype, hipStream_t st);
 int ats_lora_rope_kv_segs_multi(void* qkv, const void* u, const atspeed_lora_slot* dev_slots, const SegTable& t, const SegTable* dt,

@@ -57,7 +57,7 @@ def _a_cat(rng, rank, hidden, dtype, modules=("q", "v")):
     return r16, a
 
 
-@pytest.mark.parametrize("rank", [4, 8, 16, 40, 64])
+@pytest.mark.parametrize("rank", [4, 8, 16, 24, 40, 64])
 @pytest.mark.parametrize("hidden", [256, 768, 4096])
 @pytest.mark.parametrize("dtype", ["bf16", "fp16", "fp32"])
 def test_lora_shrink_kernel(lib, dtype, hidden, rank):

@@ -47,6 +47,11 @@ SLOTS = {1: dict(rank=8, modules="qv", scaling=2.0), 2: dict(rank=40, modules="q
 # A: 64 rows; the first 16-row tile holds three different adapters, none among them, and a segment straddles tiles.  B: 35 rows, a partial
 # last tile, and the same adapter on both sides of another one inside a tile
 LAYOUTS = {"A": ([5, 4, 7, 19, 16, 1, 12], [1, 2, 0, 2, 1, 3, 3]), "B": ([3, 30, 2], [2, 1, 2])}
+# both slots pad to R16 = 32: rank 24 on q, v and rank 32 on k only.  25 rows: the first 16-row tile mixes both adapters, the same adapter sits
+# on both sides of the other one, the last tile is partial
+SLOTS_R32 = {1: dict(rank=24, modules="qv", scaling=2.0), 2: dict(rank=32, modules="k", scaling=0.5)}
+LAYOUTS["R32"] = ([7, 9, 9], [1, 2, 1])
+SHAPES_R32 = [(4, 64, "bf16"), (4, 64, "fp16"), (5, 40, "bf16")]
 SHAPES = [(4, 64, "bf16"), (4, 64, "fp16"), (12, 64, "bf16"), (12, 64, "fp16"), (5, 40, "bf16"), (5, 40, "fp16"), (12, 64, "fp32")]
 LAYER = 1
 
@@ -87,10 +92,10 @@ class Segs:
         return np.concatenate([[a] * t for a, t in zip(adapters, self.n_tok)])
 
 
-def _slot_weights(rng, H, dtype):
+def _slot_weights(rng, H, dtype, slots):
     """per slot: (r16, a_cat64, a_cat tensor, {module: (b64, b tensor)}) laid out as the library lays its copies out (pad rows / columns zero)"""
     out = {}
-    for s, sp in SLOTS.items():
+    for s, sp in slots.items():
         rank, r16 = sp["rank"], (sp["rank"] + 15) // 16 * 16
         a = np.zeros((3 * r16, H), dtype=np.float32)
         bs = {}
@@ -107,7 +112,8 @@ def _slot_weights(rng, H, dtype):
 class KernelCase:
     """inputs of one (layout, shape, dtype) on the device, the slot table, and the two segmented kernels' results"""
 
-    def __init__(self, lib, layout, n_heads, head_dim, dtype):
+    def __init__(self, lib, layout, n_heads, head_dim, dtype, slots=SLOTS):
+        self.slots = slots
         self.lib, self.dtype, self.td, self.code = lib, dtype, TD[dtype], _lib.dtype_code(TD[dtype])
         self.n_heads, self.head_dim, self.H = n_heads, head_dim, n_heads * head_dim
         n_tok, self.adapters = LAYOUTS[layout]
@@ -117,12 +123,12 @@ class KernelCase:
         self.h64, self.h_t = _fmt(rng.standard_normal((S.total, H)) * (0.5 + rng.random((S.total, 1)) * 3), dtype)
         self.w64, self.w_t = _fmt(1 + 0.1 * rng.standard_normal(H), dtype)
         self.qkv64, self.qkv_t = _fmt(rng.standard_normal((S.total, 3 * H)), dtype)
-        self.W = _slot_weights(rng, H, dtype)
+        self.W = _slot_weights(rng, H, dtype, slots)
         self.dev = {s: (w[2].cuda(), {m: b[1].cuda() for m, b in w[3].items()}) for s, w in self.W.items()}
         self.tab = (_lib.LoraSlot * 4)()
         for s, (a, bs) in self.dev.items():
             ptr = lambda m: bs[m].data_ptr() if m in bs else None
-            self.tab[s] = _lib.LoraSlot(a.data_ptr(), ptr("q"), ptr("k"), ptr("v"), self.W[s][0], SLOTS[s]["scaling"])
+            self.tab[s] = _lib.LoraSlot(a.data_ptr(), ptr("q"), ptr("k"), ptr("v"), self.W[s][0], slots[s]["scaling"])
         self.seg_ad = (C.c_int32 * S.n)(*self.adapters)
         cos, sin = (torch.from_numpy(t).cuda() for t in SC.rope_tables(head_dim))
         self.cos, self.sin = cos, sin
@@ -172,10 +178,10 @@ class KernelCase:
 def kernel_cases(lib):
     cache = {}
 
-    def get(layout, n_heads, head_dim, dtype):
+    def get(layout, n_heads, head_dim, dtype, slots=SLOTS):
         key = (layout, n_heads, head_dim, dtype)
         if key not in cache:
-            cache[key] = KernelCase(lib, layout, n_heads, head_dim, dtype)
+            cache[key] = KernelCase(lib, layout, n_heads, head_dim, dtype, slots)
         return cache[key]
     return get
 
@@ -188,7 +194,17 @@ def test_segmented_kernels_equal_the_single_adapter_kernels_per_segment(lib, ker
     adapter a; for adapter 0, q and the caches are bit-identical to atspeed_segs_rope_kv and the segment's u rows still hold the guard
     poison; of an adapted row only [0, 3 r16) of u is written.  The expand is fed the single-adapter kernels' u scattered into a poisoned
     buffer, so that a row of adapter 0 that is read shows as a NaN."""
-    kc_ = kernel_cases(layout, n_heads, head_dim, dtype)
+    _segmented_equal_single(lib, kernel_cases(layout, n_heads, head_dim, dtype))
+
+
+@pytest.mark.parametrize("n_heads,head_dim,dtype", SHAPES_R32, ids=[f"{h * d}_{t}" for h, d, t in SHAPES_R32])
+def test_segmented_kernels_equal_the_single_adapter_kernels_at_a_padded_rank_of_32(lib, kernel_cases, n_heads, head_dim, dtype):
+    """the same assertions with SLOTS_R32 on layout R32: lora_shrink_mfma_kernel<6> and the segmented MFMA shrink's 6-tile pass (hidden 256,
+    with the vector expand) and the scalar 16-bit forms (200 = 5 x 40); SLOTS pads to 16, 48 and 64 only"""
+    _segmented_equal_single(lib, kernel_cases("R32", n_heads, head_dim, dtype, SLOTS_R32))
+
+
+def _segmented_equal_single(lib, kc_):
     S, H, td = kc_.S, kc_.H, kc_.td
     vu = kc_.shrink_multi()
     u_multi = vu.t.clone()
@@ -219,7 +235,7 @@ def test_segmented_kernels_equal_the_single_adapter_kernels_per_segment(lib, ker
         else:
             bs = kc_.dev[a][1]
             ptr = [bs[m].data_ptr() if m in bs else None for m in "qkv"]
-            _lib.check(lib.atspeed_segs_lora_rope_kv(q1.data_ptr(), singles[i].data_ptr(), *ptr, kc_.W[a][0], SLOTS[a]["scaling"], *kc_.tail,
+            _lib.check(lib.atspeed_segs_lora_rope_kv(q1.data_ptr(), singles[i].data_ptr(), *ptr, kc_.W[a][0], kc_.slots[a]["scaling"], *kc_.tail,
                                                      *S.args(k1, v1, only=i), _st()))
         torch.cuda.synchronize()
         assert_same(f"q of segment {i} (adapter {a})", q[rows, :H].cpu(), q1[:, :H].cpu())
@@ -230,7 +246,8 @@ def test_segmented_kernels_equal_the_single_adapter_kernels_per_segment(lib, ker
             kp, vp = S.caches(1)
             _lib.check(lib.atspeed_segs_rope_kv(plain.data_ptr(), None, 0, *kc_.tail, *S.args(kp, vp, only=i), _st()))
             torch.cuda.synchronize()
-            assert not torch.equal(vc[i], vp[0]), f"segment {i}: the adapter must move v"
+            for m, got, base in (("k", kc[i], kp[0]), ("v", vc[i], vp[0])):
+                assert m not in kc_.slots[a]["modules"] or not torch.equal(got, base), f"segment {i}: the adapter must move {m}"
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16", "fp32"])
