@@ -10,7 +10,7 @@ from .generation_trie import (ConstraintFSM, PositionSetConstraint, SuffixTrieCo
 
 __all__ = ["Trie", "prefix_allowed_tokens_fn", "PositionSetConstraint", "SuffixTrieConstraint",
            "WholeSentenceTrieConstraint", "ConstraintFSM", "BSSD", "BSSD_batch", "BSSDSession", "beam_sd_generate", "target_generate", "target_generate_batch",
-           "Timer", "HipLlama"]
+           "Timer", "HipLlama", "PromptPrefix"]
 
 
 def __getattr__(name):
@@ -18,7 +18,7 @@ def __getattr__(name):
     if name in ("BSSD", "BSSD_batch", "BSSDSession", "beam_sd_generate", "target_generate", "target_generate_batch", "Timer", "one_step_beam_search"):
         from . import beamSD
         return getattr(beamSD, name)
-    if name in ("HipLlama",):
+    if name in ("HipLlama", "PromptPrefix"):
         from . import model
         return getattr(model, name)
     raise AttributeError(name)

@@ -63,10 +63,16 @@ class SessionDone(C.Structure):
 
 
 class SessionUser(C.Structure):
-    """atspeed_session_user: everything a session's user brings (atspeed_session_submit_ex)"""
+    """atspeed_session_user as it was before prompt prefixes: everything a session's user brings (atspeed_session_submit_ex).  The record is
+    versioned by struct_size, so this shorter one stays valid: the library reads the members it does not have as 0"""
     _fields_ = [("struct_size", C.c_size_t), ("prompt_ids_dev", C.c_void_p), ("prompt_len", C.c_int32), ("start_node", C.c_int32),
                 ("seed", C.c_uint32), ("out_tokens_dev", C.c_void_p), ("out_scores_dev", C.c_void_p), ("stats_host", C.POINTER(GenStats)),
                 ("masks", C.c_void_p), ("mask_user", C.c_int32), ("adapter", C.c_int32)]
+
+
+class SessionUserPrefix(C.Structure):
+    """atspeed_session_user of today's header: SessionUser and the trailing prompt-prefix pair (a user that names a PromptPrefix)"""
+    _fields_ = SessionUser._fields_ + [("target_prefix", C.c_void_p), ("draft_prefix", C.c_void_p)]
 
 
 # every symbol include/atspeed_hip.h declares: (restype, argtypes)
@@ -111,7 +117,7 @@ SIGNATURES = {
     "atspeed_llama_lora_slots": (_I, [_P]),
     "atspeed_llama_forward_batch_adapters": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "atspeed_decoder_set_adapter": (C.c_int, [_P, _I]),
-    "atspeed_session_submit_ex": (C.c_int, [_P, C.POINTER(SessionUser), C.POINTER(C.c_int64)]),
+    "atspeed_session_submit_ex": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),      # SessionUser or SessionUserPrefix, by reference
     "atspeed_segs_lora_shrink_multi": (C.c_int, [_P, _P, C.POINTER(LoraSlot), _I, _P, _I, _F, _I, _P] + _SEGS + [_P]),
     "atspeed_segs_lora_rope_kv_multi": (C.c_int, [_P, _P, C.POINTER(LoraSlot), _I, _P, _P, _SZ, _I, _I, _I, _I, _P] + _SEGS + [_P]),
     "atspeed_quant_rows_fp8": (C.c_int, [_P, _I, _I, _P, _P, _P]),
@@ -155,6 +161,14 @@ SIGNATURES = {
     "atspeed_decoder_decisions": (C.c_int64, [_P, _P, C.c_int64]),
     "atspeed_decoder_kv_bytes": (C.c_int64, [_P, _I]),
     "atspeed_decoder_kv_copy": (C.c_int, [_P, _I, _I, _P, _P, _P]),
+    "atspeed_prefix_create": (C.c_int, [_P, _P, _I, _I, _P, C.POINTER(_P)]),
+    "atspeed_prefix_destroy": (None, [_P]),
+    "atspeed_prefix_info": (C.c_int, [_P, C.POINTER(_I), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "atspeed_prefix_read": (C.c_int, [_P, _P, _P, _P, _P]),
+    "atspeed_decoder_set_prefix": (C.c_int, [_P, _P, _P]),
+    "atspeed_prefix_to_batch_arenas": (C.c_int, [_P, _I, _I, _P]),
+    "atspeed_kv_rows_scatter": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "atspeed_kv_rows_gather": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "atspeed_gemm": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "atspeed_gemm_path_counters": (C.c_int, [_P, _I, _I]),
     "atspeed_set_switch": (C.c_int, [C.c_char_p, _I]),

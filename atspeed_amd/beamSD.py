@@ -43,6 +43,10 @@ batches and sessions; draft and target see the same bits, so BSSD under a filter
 Resident adapters (`adapter=` / `adapters=`, include/atspeed_hip.h "several RESIDENT adapters on one model"): per user the name of one of the
 LoRA adapters `HipLlama.add_lora` keeps on the target, or None.  It becomes the slot in the user's segment of every target forward
 (`_adapter_slots`, `_set_adapters`; sessions carry it in the submit record), so users of different fine-tunes share a batch or a session.
+
+Prompt prefixes (`prefix=` / `prefixes=`, include/atspeed_hip.h "prompt prefixes"): a `PromptPrefix` holds the K / V rows of a prompt opening
+that many users share; a user that names one gets the rows copied into its KV arenas and prefills only the rest of its prompt
+(`_prefix_list`, `_set_prefixes`; sessions carry it in the submit record).  Results are those of the full-prompt call.
 """
 from __future__ import annotations
 
@@ -57,7 +61,7 @@ import torch
 
 from . import _lib
 from .generation_trie import ConstraintFSM, SuffixTrieConstraint, WholeSentenceTrieConstraint, free_constraint
-from .model import HipLlama
+from .model import HipLlama, PromptPrefix
 
 
 class Timer:
@@ -278,18 +282,20 @@ def _set_decoders(decs, mode, num_beams: int, seeds, trace=None) -> None:
 
 
 def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allowed_tokens_fn, mode, who: str, trace=None,
-           filters=None, first_user: int = 0, adapters=None) -> SimpleNamespace:
+           filters=None, first_user: int = 0, adapters=None, prefix=None, prefixes=None) -> SimpleNamespace:
     """The device path's call setup, for one user or a lock-step batch: prompts on the device, each user's compiled constraint (the mask
     functions look at the prompt -- position of "Response:", data.py:97-102 -- with one D2H copy per call, where the reference does one per beam
     per step, generation_trie.py:94, data.py:98), the ONE automaton they share (they may differ in their start node only), one decoder per
     user (lane), set to the call's sampling mode (user u draws from stream seed + u) and, for BSSD (`trace` not None), its decision trace.
     `filters` (`_filter_specs`): the users' item filters are built and set on their decoders; the caller clears them (`_clear_filters`)
     when its library call has returned.  `adapters` (`_adapter_slots`): the users' resident adapter slots, None = nobody names one; set on
-    every call."""
+    every call.  `prefix` / `prefixes`: the users' prompt prefixes (`_prefix_list`), set on their decoders here and cleared by the caller
+    (`_clear_call`) like the filters."""
     dev = target.device
     if filters is not None:
         _check_filter_constraint(prefix_allowed_tokens_fn, who)
     prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
+    plist = _prefix_list(prefix, prefixes, len(prompts), target, draft, adapters, [int(p.numel()) for p in prompts], who)
     fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
     for f in fsms[1:]:
         if f.row_ptr is not fsms[0].row_ptr:
@@ -302,7 +308,17 @@ def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allo
     if filters is not None:
         owners, per_user = _item_filters(dfsm, [f.start for f in fsms], filters, dev, who, first_user)
         _set_filters(decs, per_user)
-    return SimpleNamespace(dev=dev, prompts=prompts, fsms=fsms, dfsm=dfsm, decs=decs, filter_owners=owners)
+    if plist is not None:
+        _set_prefixes(decs, plist, draft is not None)
+    return SimpleNamespace(dev=dev, prompts=prompts, fsms=fsms, dfsm=dfsm, decs=decs, filter_owners=owners, prefixes=plist)
+
+
+def _clear_call(c: SimpleNamespace) -> None:
+    """what a call put on its (cached) decoders for its own duration: item filters and prompt prefixes"""
+    if c.filter_owners:
+        _clear_filters(c.decs)
+    if c.prefixes is not None:
+        _clear_prefixes(c.decs)
 
 
 # ---------------------------------------------------------------- item filters
@@ -431,6 +447,64 @@ def _set_adapters(decs, slots) -> None:
             d.adapter_slot = slot
 
 
+# ---------------------------------------------------------------- prompt prefixes (PromptPrefix), one per user
+def _prefix_list(prefix, prefixes, n: int, target, draft, slots, prompt_lens, who: str):
+    """The call's `prefix=` (one PromptPrefix for every user) / `prefixes=` (a list with one PromptPrefix or None per user) -> None when no
+    user names one, else one per user.  ValueError: both given, a wrong list length, a prefix of other models (`draft` None: the target's
+    half alone counts), a prefix without the draft's half in a beam-SD call, a prefix built under another adapter than the user's, a stale
+    prefix, a prompt that is not longer than its prefix."""
+    if prefix is not None and prefixes is not None:
+        raise ValueError(f"{who}: prefix= (one for all users) and prefixes= (one per user) are mutually exclusive")
+    if prefix is not None:
+        prefixes = [prefix] * n
+    if prefixes is None:
+        return None
+    if isinstance(prefixes, PromptPrefix) or len(prefixes) != n:
+        raise ValueError(f"{who}: prefixes needs one PromptPrefix (or None) per user: "
+                         f"{'a single object' if isinstance(prefixes, PromptPrefix) else len(prefixes)} for {n} users")
+    if all(p is None for p in prefixes):
+        return None
+    for u, p in enumerate(prefixes):
+        if p is None:
+            continue
+        if not isinstance(p, PromptPrefix):
+            raise TypeError(f"{who}: user {u}: a prefix is an atspeed_amd.PromptPrefix, not {type(p).__name__}")
+        if p.target is not target or (draft is not None and p.draft is not None and p.draft is not draft):
+            raise ValueError(f"{who}: user {u}: the prompt prefix was built on other models than the call's")
+        if draft is not None and p.draft is None:
+            raise ValueError(f"{who}: user {u}: the prompt prefix holds the target's half alone (PromptPrefix(target, None, ...)): a beam-SD "
+                             "call needs the draft's too")
+        slot = slots[u] if slots is not None else 0
+        if p.slot != slot:
+            raise ValueError(f"{who}: user {u}: the prompt prefix was built under adapter {p.adapter!r}, the user runs under "
+                             f"{'another one' if slot else 'none'}")
+        if p.info()["stale"] or (draft is not None and p.info(True)["stale"]):
+            raise ValueError(f"{who}: user {u}: the prompt prefix is stale (its model's quantisation or adapter changed after it was built): "
+                             "build a new PromptPrefix")
+        if prompt_lens is not None and p.length > prompt_lens[u] - 1:
+            raise ValueError(f"{who}: user {u}: a prefix of {p.length} tokens needs a prompt of at least {p.length + 1}, got {prompt_lens[u]}")
+    return list(prefixes)
+
+
+def _refuse_host_prefixes(prefix, who: str) -> None:
+    if prefix is not None:
+        raise NotImplementedError(f"{who}: prefix= / prefixes= run on the device path only (a mask that can compile() itself, no extra "
+                                  "logits_processor)")
+
+
+def _set_prefixes(decs, prefixes, bssd: bool) -> None:
+    lib = _lib.load()
+    for d, p in zip(decs, prefixes):
+        _lib.check(lib.atspeed_decoder_set_prefix(d.handle, p.handle() if p else None, p.handle(True) if p and bssd else None))
+
+
+def _clear_prefixes(decs) -> None:
+    """A cached decoder must not keep a call's prefix: a later call without one prefills its whole prompt (and the prefix may die)."""
+    lib = _lib.load()
+    for d in decs:
+        lib.atspeed_decoder_set_prefix(d.handle, None, None)
+
+
 def _host_call(host_fn, models, inputs: Dict, args, logits_processor, prefix_allowed_tokens_fn, mode) -> Dict:
     """Arbitrary Python callables (a mask closure, extra logits processors) are served like the reference does, one host call per beam per
     step: `host_fn(*models, prompt, *args, fn, processors, sample)` of hostmask.py, its arrays back on the device.  With do_sample the draws happen
@@ -459,8 +533,7 @@ def _one_user_call(entry, c: SimpleNamespace, k: int, max_new_tokens: int, *midd
             _lib.check(entry(c.decs[0].handle, ids32.data_ptr(), int(prompt.numel()), c.dfsm.handle, c.fsms[0].start, *middle,
                              toks.data_ptr(), scores.data_ptr(), C.byref(stats), _lib.stream_ptr(dev)))
         finally:
-            if c.filter_owners:
-                _clear_filters(c.decs)
+            _clear_call(c)
     seq = torch.cat((prompt.to(torch.int64)[None, :].repeat(k, 1), toks.to(torch.int64)), dim=1)
     return {"beam_sequence": seq, "beam_scores": scores}, stats
 
@@ -510,8 +583,7 @@ def _batch_call(entry, c: SimpleNamespace, k: int, max_new_tokens: int, *middle)
                              ints(*[int(p.numel()) for p in c.prompts]), c.dfsm.handle, ints(*[f.start for f in c.fsms]), *middle,
                              ptrs(*[t.data_ptr() for t in toks]), ptrs(*[t.data_ptr() for t in scores]), stats, _lib.stream_ptr(c.dev)))
         finally:
-            if c.filter_owners:
-                _clear_filters(c.decs)
+            _clear_call(c)
     return (keep, toks, scores, k), stats
 
 
@@ -558,19 +630,20 @@ def _bssd_stats(st, k: int) -> Dict:
 @torch.no_grad()
 def BSSD(target_model, draft_model, inputs: Dict, gamma: int, max_new_tokens: int,
          logits_processor=None, prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False,
-         exclude_items=None, allow_items=None, adapter=None) -> Dict:
+         exclude_items=None, allow_items=None, adapter=None, prefix=None) -> Dict:
     mode = _mode(seed, target_model, draft_model)
     filters = _filter_specs(1, exclude_items, allow_items, False, "BSSD")
     slots = _adapter_slots(target_model, adapter, 1, False, "BSSD")
     if _host_path(logits_processor, prefix_allowed_tokens_fn):
         _refuse_host_filters(filters, "BSSD")
         _refuse_host_adapters(slots, "BSSD")
+        _refuse_host_prefixes(prefix, "BSSD")
         from .hostmask import bssd_host_mask
         return _host_call(bssd_host_mask, (target_model, draft_model), inputs, (int(gamma), int(max_new_tokens)), logits_processor,
                           prefix_allowed_tokens_fn, mode)
     k = int(target_model.generation_config.num_beams)                 # beamSD.py:482
     dk = int(draft_model.generation_config.num_beams)                 # beamSD.py:483
-    c = _setup(target_model, draft_model, [inputs], prefix_allowed_tokens_fn, mode, "BSSD", trace_decisions, filters, adapters=slots)
+    c = _setup(target_model, draft_model, [inputs], prefix_allowed_tokens_fn, mode, "BSSD", trace_decisions, filters, adapters=slots, prefix=prefix)
     out, stats = _one_user_call(_lib.load().atspeed_bssd_generate, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     out.update(_bssd_stats(stats, k))
     return out
@@ -637,9 +710,9 @@ class BSSDSession:
                                              self.gamma, self.max_new_tokens, self.k, self.dk, self.max_prompt, _lib.stream_ptr(self.dev))
 
     def _submit(self, prompt: torch.Tensor, fsm: ConstraintFSM, ids32: torch.Tensor, toks: torch.Tensor, scores: torch.Tensor, seed=None,
-                mask=None, mask_owners=(), adapter: int = 0) -> int:
+                mask=None, mask_owners=(), adapter: int = 0, prefix=None) -> int:
         """`mask`: None or (masks pointer, user index) of the user's item filter; `mask_owners` stay alive until its ticket has come back;
-        `adapter`: the user's resident adapter slot on the target (0 = none)"""
+        `adapter`: the user's resident adapter slot on the target (0 = none); `prefix`: its checked PromptPrefix or None, kept alive likewise"""
         if self._closed:
             raise RuntimeError("BSSDSession is closed")
         if self._fsm0 is None:
@@ -648,26 +721,32 @@ class BSSDSession:
             raise ValueError("BSSDSession needs one shared constraint automaton (only the start node may differ per user)")
         if seed is None:
             seed = self.mode[2] + self._submitted
-        user = SimpleNamespace(prompt=prompt, ids32=ids32, toks=toks, scores=scores, stats=_lib.GenStats(), t0=time.time(), mask_owners=mask_owners)
+        user = SimpleNamespace(prompt=prompt, ids32=ids32, toks=toks, scores=scores, stats=_lib.GenStats(), t0=time.time(), mask_owners=mask_owners,
+                               prefix=prefix)
         ticket = C.c_int64(0)
         # host only: the library queues the user and launches nothing, so no device guard (one per user would be the call's largest cost)
-        rec = _lib.SessionUser(C.sizeof(_lib.SessionUser), ids32.data_ptr(), int(prompt.numel()), fsm.start, int(seed) & 0xFFFFFFFF,
-                               toks.data_ptr(), scores.data_ptr(), C.pointer(user.stats), mask[0] if mask else None, mask[1] if mask else 0,
-                               int(adapter))
+        fields = (ids32.data_ptr(), int(prompt.numel()), fsm.start, int(seed) & 0xFFFFFFFF, toks.data_ptr(), scores.data_ptr(), C.pointer(user.stats),
+                  mask[0] if mask else None, mask[1] if mask else 0, int(adapter))
+        if prefix is None:                 # the record without the prefix pair: the library reads the pair as NULL
+            rec = _lib.SessionUser(C.sizeof(_lib.SessionUser), *fields)
+        else:
+            rec = _lib.SessionUserPrefix(C.sizeof(_lib.SessionUserPrefix), *fields, prefix.handle(), prefix.handle(True))
         _lib.check(_lib.load().atspeed_session_submit_ex(self._owner.ptr, C.byref(rec), C.byref(ticket)))
         self._submitted += 1
         self._users[ticket.value] = user
         return ticket.value
 
     @torch.no_grad()
-    def submit(self, inputs: Dict, seed=None, exclude_items=None, allow_items=None, adapter=None) -> int:
+    def submit(self, inputs: Dict, seed=None, exclude_items=None, allow_items=None, adapter=None, prefix=None) -> int:
         """Queue one user; no forward is launched.  Returns its ticket.  `exclude_items` / `allow_items`: the user's item filter (a list of
         token sequences; its node bitset is built here and follows the user to whichever lane it lands on).  `adapter`: the name of the
         resident adapter (`HipLlama.add_lora` on the target) the user runs under, None = none; it follows the user likewise, and must stay
-        resident until the user's ticket has come back."""
+        resident until the user's ticket has come back.  `prefix`: the `PromptPrefix` the user's prompt opens with; the session keeps it
+        alive until the ticket has come back."""
         filters = _filter_specs(1, exclude_items, allow_items, False, "BSSDSession.submit")
         slots = _adapter_slots(self.target, adapter, 1, False, "BSSDSession.submit")
         prompt = _prompt_row(inputs).to(self.dev)
+        plist = _prefix_list(prefix, None, 1, self.target, self.draft, slots, [int(prompt.numel())], "BSSDSession.submit")
         fsm = _compile_constraint(self.fn, prompt.tolist())
         with torch.cuda.device(self.dev):
             ids32 = prompt.to(torch.int32).contiguous()
@@ -684,7 +763,8 @@ class BSSDSession:
                 raise ValueError("BSSDSession needs one shared constraint automaton (only the start node may differ per user)")
             owners, per_user = _item_filters(self._dfsm, [fsm.start], filters, self.dev, "BSSDSession.submit", self._submitted)
             mask = per_user[0]
-        return self._submit(prompt, fsm, ids32, toks, scores, seed, mask, tuple(owners), slots[0] if slots is not None else 0)
+        return self._submit(prompt, fsm, ids32, toks, scores, seed, mask, tuple(owners), slots[0] if slots is not None else 0,
+                            plist[0] if plist is not None else None)
 
     def _finished(self, buf, n: int, assemble: bool):
         out, now = [], time.time()
@@ -744,7 +824,8 @@ class BSSDSession:
         return False
 
 
-def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes: int, filters=None, adapters=None):
+def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes: int, filters=None, adapters=None,
+                      prefix=None, prefixes=None):
     """`BSSD_batch(..., lanes=N)`: the whole list through one session of N lanes, results in list order.  The prompts, token blocks and
     scores are the batch call's buffers (one allocation each) and the result tensors come from its one assemble launch."""
     if not inputs_list:
@@ -753,6 +834,7 @@ def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tok
     dev = target_model.device
     prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
     fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
+    plist = _prefix_list(prefix, prefixes, len(prompts), target_model, draft_model, adapters, [int(p.numel()) for p in prompts], "BSSD_batch")
     n_lanes = max(1, min(int(lanes), len(prompts), MAX_USERS_PER_CALL))
     with BSSDSession(target_model, draft_model, n_lanes, gamma, max_new_tokens, prefix_allowed_tokens_fn,
                      max_prompt=max(int(p.numel()) for p in prompts), seed=seed, _cached_decoders=True) as ses:
@@ -764,7 +846,8 @@ def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tok
             _check_filter_constraint(prefix_allowed_tokens_fn, "BSSD_batch")
             ses._create(fsms[0])
             owners, per_user = _item_filters(ses._dfsm, [f.start for f in fsms], filters, dev, "BSSD_batch")
-        tickets = [ses._submit(p, f, i32, toks[u], scores[u], mask=per_user[u], adapter=adapters[u] if adapters is not None else 0)
+        tickets = [ses._submit(p, f, i32, toks[u], scores[u], mask=per_user[u], adapter=adapters[u] if adapters is not None else 0,
+                               prefix=plist[u] if plist is not None else None)
                    for u, (p, f, i32) in enumerate(zip(prompts, fsms, ids32))]
         done = dict(ses.drain(_assemble=False))
         del owners
@@ -780,7 +863,7 @@ def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tok
 @torch.no_grad()
 def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_tokens: int,
                prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False, lanes: Optional[int] = None,
-               exclude_items=None, allow_items=None, _first_user: int = 0, adapters=None):
+               exclude_items=None, allow_items=None, _first_user: int = 0, adapters=None, prefix=None, prefixes=None):
     """BSSD for several independent users at once (one result dict per user, same keys as BSSD).
 
     The reference decodes users strictly one after another (inference.py:162-176).  Here the users advance in
@@ -797,24 +880,27 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
 
     `exclude_items` / `allow_items`: one list of token sequences (or None = unfiltered) per user, on either path; a user has one or the other.
     `adapters`: one resident adapter's name (`HipLlama.add_lora`) or None per user, on either path: every user of the batch runs the target
-    under its own adapter, the draft is never adapted."""
+    under its own adapter, the draft is never adapted.
+    `prefix` (one `PromptPrefix` for every user) / `prefixes` (one or None per user), on either path: the users' shared prompt openings,
+    whose K / V are copied into the users' arenas instead of being prefilled."""
     slots = _adapter_slots(target_model, adapters, len(inputs_list), True, "BSSD_batch")
     if lanes is not None:
         if trace_decisions:
             raise ValueError("BSSD_batch(lanes=N) keeps no decision trace")
         return _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes,
-                                 _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch"), slots)
+                                 _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch"), slots, prefix, prefixes)
     mode = _mode(seed, target_model, draft_model)
     if len(inputs_list) > MAX_USERS_PER_CALL:
         return _chunked(lambda chunk, s, i: BSSD_batch(target_model, draft_model, chunk, gamma, max_new_tokens, prefix_allowed_tokens_fn,
                                                        seed=s, trace_decisions=trace_decisions, exclude_items=_chunk_of(exclude_items, i, len(chunk)),
                                                        allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i,
-                                                       adapters=_chunk_of(adapters, i, len(chunk))), inputs_list, mode)
+                                                       adapters=_chunk_of(adapters, i, len(chunk)), prefix=prefix,
+                                                       prefixes=_chunk_of(prefixes, i, len(chunk))), inputs_list, mode)
     filters = _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch")
     k = int(target_model.generation_config.num_beams)
     dk = int(draft_model.generation_config.num_beams)
     t0 = time.time()
-    c = _setup(target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, mode, "BSSD_batch", trace_decisions, filters, _first_user, slots)
+    c = _setup(target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, mode, "BSSD_batch", trace_decisions, filters, _first_user, slots, prefix, prefixes)
     raw, stats = _batch_call(_lib.load().atspeed_bssd_generate_batch, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     wall = time.time() - t0
     outs = _batch_results(*raw)
@@ -827,41 +913,45 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
 @Timer()
 @torch.no_grad()
 def target_generate(model, inputs: Dict, max_new_tokens: int, logits_processor=None,
-                    prefix_allowed_tokens_fn=None, seed=None, exclude_items=None, allow_items=None, adapter=None) -> Dict:
+                    prefix_allowed_tokens_fn=None, seed=None, exclude_items=None, allow_items=None, adapter=None, prefix=None) -> Dict:
     mode = _mode(seed, model)
     filters = _filter_specs(1, exclude_items, allow_items, False, "target_generate")
     slots = _adapter_slots(model, adapter, 1, False, "target_generate")
     if _host_path(logits_processor, prefix_allowed_tokens_fn):
         _refuse_host_filters(filters, "target_generate")
         _refuse_host_adapters(slots, "target_generate")
+        _refuse_host_prefixes(prefix, "target_generate")
         from .hostmask import target_generate_host_mask
         return _host_call(target_generate_host_mask, (model,), inputs, (int(max_new_tokens),), logits_processor, prefix_allowed_tokens_fn,
                           mode)
     k = int(model.generation_config.num_beams)                        # beamSD.py:553
-    c = _setup(model, None, [inputs], prefix_allowed_tokens_fn, mode, "target_generate", filters=filters, adapters=slots)
+    c = _setup(model, None, [inputs], prefix_allowed_tokens_fn, mode, "target_generate", filters=filters, adapters=slots, prefix=prefix)
     out, stats = _one_user_call(_lib.load().atspeed_target_generate, c, k, max_new_tokens, int(max_new_tokens), k)
     out.update({"n_valid": int(stats.n_valid), "device_time_cost": stats.total_ms * 1e-3})
     return out
 
 
 def target_generate_batch(model, inputs_list, max_new_tokens: int, prefix_allowed_tokens_fn=None, seed=None, exclude_items=None,
-                          allow_items=None, _first_user: int = 0, adapters=None):
+                          allow_items=None, _first_user: int = 0, adapters=None, prefix=None, prefixes=None):
     """`target_generate` for several independent users in lock step (one result dict per user): position g of every
     user's constrained beam search is ONE forward.  This is the loop `code/generate_teacher_data.py:211-244` runs over
     a whole training set with HF `generate`; token ids equal per-user `target_generate` calls.  `exclude_items` / `allow_items`: one list of
-    token sequences (or None = unfiltered) per user.  `adapters`: one resident adapter's name (`HipLlama.add_lora`) or None per user."""
+    token sequences (or None = unfiltered) per user.  `adapters`: one resident adapter's name (`HipLlama.add_lora`) or None per user.
+    `prefix` (one `PromptPrefix` for every user) / `prefixes` (one or None per user): the users' shared prompt openings."""
     mode = _mode(seed, model)
     slots = _adapter_slots(model, adapters, len(inputs_list), True, "target_generate_batch")
     if len(inputs_list) > MAX_USERS_PER_CALL:
         return _chunked(lambda chunk, s, i: target_generate_batch(model, chunk, max_new_tokens, prefix_allowed_tokens_fn, seed=s,
                                                                   exclude_items=_chunk_of(exclude_items, i, len(chunk)),
                                                                   allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i,
-                                                                  adapters=_chunk_of(adapters, i, len(chunk))),
+                                                                  adapters=_chunk_of(adapters, i, len(chunk)), prefix=prefix,
+                                                                  prefixes=_chunk_of(prefixes, i, len(chunk))),
                         inputs_list, mode)
     filters = _filter_specs(len(inputs_list), exclude_items, allow_items, True, "target_generate_batch")
     k = int(model.generation_config.num_beams)
     t0 = time.time()
-    c = _setup(model, None, inputs_list, prefix_allowed_tokens_fn, mode, "target_generate_batch", filters=filters, first_user=_first_user, adapters=slots)
+    c = _setup(model, None, inputs_list, prefix_allowed_tokens_fn, mode, "target_generate_batch", filters=filters, first_user=_first_user, adapters=slots,
+               prefix=prefix, prefixes=prefixes)
     raw, stats = _batch_call(_lib.load().atspeed_target_generate_batch, c, k, max_new_tokens, int(max_new_tokens), k)
     wall = time.time() - t0
     outs = _batch_results(*raw)

@@ -506,6 +506,45 @@ int ats_pack_rows(const void* src, void* dst, int rows, int row_bytes, int to_pa
   return ATSPEED_OK;
 }
 
+// ---------------------------------------------------------------------------- K/V rows between a compact store and engine-layout arenas
+// A prompt prefix's K / V (engine.hip: atspeed_prefix) live compact, [layers][len][row_bytes]; a user's arena is [layers][max_slots][row_bytes].
+// One thread per 16-byte chunk of the store; grid.y = 0 moves K, 1 moves V.  Scatter: the chunk is loaded once and stored to the same place of
+// every user's arena (users = DEVICE array of n arena pairs).  Gather (to_store): the chunk comes from user 0's arena.  Plain vector loads and
+// stores; only rows [0, len) of each layer are touched on the arena side, only the store's own chunks on the other.
+__global__ __launch_bounds__(256) void kv_rows_copy_kernel(uint4* __restrict__ store_k, uint4* __restrict__ store_v, const KvRowsUser* __restrict__ users,
+                                                           int n_users, size_t chunks_per_layer /* len * chunks per row */, size_t total_chunks,
+                                                           size_t arena_layer_chunks /* max_slots * chunks per row */, int to_store) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total_chunks) return;
+  const size_t layer = i / chunks_per_layer;
+  const size_t a = layer * arena_layer_chunks + (i - layer * chunks_per_layer);       // the chunk's place in an arena
+  const int is_v = blockIdx.y;
+  uint4* __restrict__ store = is_v ? store_v : store_k;
+  if (to_store) {
+    const uint4* src = (const uint4*)(is_v ? users[0].v : users[0].k);
+    store[i] = src[a];
+    return;
+  }
+  const uint4 val = store[i];
+  for (int u = 0; u < n_users; ++u) {
+    uint4* dst = (uint4*)(is_v ? users[u].v : users[u].k);
+    dst[a] = val;
+  }
+}
+
+int ats_kv_rows_copy(void* store_k, void* store_v, const KvRowsUser* dev_users, int n_users, int len, int layers, int row_bytes, int max_slots,
+                     int to_store, hipStream_t st) {
+  ATS_REQUIRE(store_k && store_v && dev_users && n_users >= 1 && layers >= 1 && row_bytes > 0 && row_bytes % 16 == 0, ATSPEED_ERR_INVALID,
+              "kv_rows_copy: bad arguments (rows must be whole 16-byte chunks)");
+  ATS_REQUIRE(len >= 1 && len <= max_slots, ATSPEED_ERR_INVALID, "kv_rows_copy: %d rows do not fit an arena of %d slots", len, max_slots);
+  ATS_REQUIRE((((uintptr_t)store_k | (uintptr_t)store_v) & 15) == 0, ATSPEED_ERR_INVALID, "kv_rows_copy: the store must be 16-byte aligned");
+  const size_t cpr = (size_t)row_bytes >> 4, per_layer = (size_t)len * cpr, total = per_layer * layers;
+  kv_rows_copy_kernel<<<dim3((unsigned)((total + 255) / 256), 2), 256, 0, st>>>((uint4*)store_k, (uint4*)store_v, dev_users, n_users, per_layer, total,
+                                                                               (size_t)max_slots * cpr, to_store);
+  ATS_LAUNCH_CHECK();
+  return ATSPEED_OK;
+}
+
 int ats_fill_hash_normal(void* dst, size_t n, uint32_t seed, float scale, float add, int dtype, uint64_t offset, hipStream_t st) {
   ATS_REQUIRE(dst && (dtype == ATSPEED_F32 || dtype == ATS_HALF), ATSPEED_ERR_INVALID, "fill: bad arguments");
   if (n == 0) return ATSPEED_OK;

@@ -333,6 +333,9 @@ struct atspeed_llama {
   LoraSlot slots[ATSPEED_LORA_MAX_ADAPTERS + 1];
   int n_slots = 0;                               // occupied
   atspeed_lora_slot* slot_tab = nullptr;
+  // what a prompt prefix (atspeed_prefix) remembers of the adapters that produced it: bumped by set_lora / clear_lora, and per slot by the
+  // add_lora / remove_lora of that slot
+  long lora_gen = 0, slot_gen[ATSPEED_LORA_MAX_ADAPTERS + 1] = {};
   bool has_lora() const { return !lora.empty() || n_slots > 0; }   // the forward takes the adapter side path (either kind)
   bool slot_ok(int s) const { return s == 0 || (s >= 1 && s <= ATSPEED_LORA_MAX_ADAPTERS && slots[s].mem); }
   KvCache kv0;                                   // cache of the plain atspeed_llama_forward API
@@ -725,6 +728,7 @@ extern "C" int atspeed_llama_clear_lora(atspeed_llama* m) {
   ATS_HIP(hipDeviceSynchronize());                 // forwards in flight read the copies
   graphs_drop(m);
   m->lora.clear();
+  m->lora_gen++;
   hipFree(m->lora_mem);
   m->lora_mem = nullptr;
   m->lora_r16 = 0; m->lora_scaling = 0.f;
@@ -792,6 +796,7 @@ extern "C" int atspeed_llama_set_lora(atspeed_llama* m, int32_t rank, float scal
   hipFree(m->lora_mem);                            // a second adapter replaces the first
   m->lora_mem = mem;
   m->lora = std::move(ll);
+  m->lora_gen++;
   m->lora_r16 = (rank + 15) / 16 * 16; m->lora_scaling = scaling;
   return ATSPEED_OK;
 }
@@ -829,6 +834,7 @@ extern "C" int atspeed_llama_add_lora(atspeed_llama* m, int32_t rank, float scal
   if (rc != ATSPEED_OK) { hipFree(mem); m->slots[slot] = atspeed_llama::LoraSlot{}; return rc; }
   graphs_drop(m);
   m->n_slots++;
+  m->slot_gen[slot]++;
   *slot_out = slot;
   return ATSPEED_OK;
 }
@@ -842,6 +848,7 @@ extern "C" int atspeed_llama_remove_lora(atspeed_llama* m, int32_t slot) {
   hipFree(m->slots[slot].mem);
   m->slots[slot] = atspeed_llama::LoraSlot{};
   m->n_slots--;
+  m->slot_gen[slot]++;
   return ATSPEED_OK;
 }
 
@@ -1231,6 +1238,9 @@ struct atspeed_decoder {
   // the target's resident adapter this user runs under (atspeed_decoder_set_adapter; a session puts its user's there): 0 = none.  It rides in
   // the user's segment of every target forward; the draft's segments keep 0
   int adapter = 0;
+  // prompt prefixes (atspeed_decoder_set_prefix; a session puts its user's there): none by default.  A user with one starts its first round at
+  // base = the prefix's length, its arenas' slots below that filled by the scatter launch in front of the first forward
+  const atspeed_prefix *tprefix = nullptr, *dprefix = nullptr;
   // the automaton as this user's kernels take it by value: the shared arrays and the user's own blocked-node bits
   FsmDev fsm_dev(const atspeed_fsm* fsm) const { FsmDev f = fsm->dev; f.blocked = ats_mask_bits(masks, mask_user); return f; }
   struct Run {
@@ -1501,6 +1511,186 @@ int ats_seg_finish(SegTable& t, int qtile_rows) {
   return ATSPEED_OK;
 }
 
+// ---- prompt prefixes (include/atspeed_hip.h "prompt prefixes"): the K / V rows of a shared prompt opening, kept compact per model
+struct atspeed_prefix {
+  atspeed_llama* m = nullptr;
+  int len = 0, slot = 0;                       // tokens; the resident adapter slot the rows were made under (0 = none)
+  void *k = nullptr, *v = nullptr;             // [layers][len][hidden] in the model's type
+  int32_t* ids = nullptr;                      // [len]
+  bool fp8 = false, fp4 = false; long lora_gen = 0, slot_gen = 0;     // the arithmetic that produced the rows (prefix_stale)
+  mutable int64_t users_served = 0;
+  size_t bytes = 0;
+};
+static bool prefix_stale(const atspeed_prefix* p) {
+  const atspeed_llama* m = p->m;
+  return p->fp8 != !m->fp8.empty() || p->fp4 != !m->fp4.empty() || p->lora_gen != m->lora_gen || (p->slot && p->slot_gen != m->slot_gen[p->slot]);
+}
+
+extern "C" void atspeed_prefix_destroy(atspeed_prefix* p) {
+  if (!p) return;
+  hipFree(p->k); hipFree(p->v); hipFree(p->ids);
+  delete p;
+}
+
+static int kv_rows_launch(void* store_k, void* store_v, const std::vector<KvRowsUser>& users, int len, const atspeed_llama* m, int to_store, hipStream_t st) {
+  const KvRowsUser* du = nullptr;
+  ATS_TRY(stage_args(users, &du, st));
+  return ats_bf16::ats_kv_rows_copy(store_k, store_v, du, (int)users.size(), len, m->cfg.n_layers, m->cfg.hidden * m->esz, m->cfg.max_slots, to_store, st);
+}
+
+extern "C" int atspeed_prefix_create(atspeed_llama* m, const int32_t* ids, int32_t len, int32_t adapter_slot, void* stream, atspeed_prefix** out) {
+  ATS_REQUIRE(m && ids && out, ATSPEED_ERR_INVALID, "prefix_create: null argument");
+  ATS_REQUIRE(len >= 1 && len < m->cfg.max_slots, ATSPEED_ERR_INVALID, "prefix_create: %d tokens (1 .. max_slots - 1 = %d)", len, m->cfg.max_slots - 1);
+  ATS_REQUIRE(adapter_slot >= 0 && m->slot_ok(adapter_slot), ATSPEED_ERR_INVALID, "prefix_create: adapter slot %d is not occupied", adapter_slot);
+  hipStream_t st = (hipStream_t)stream;
+  Building<atspeed_prefix> p(new atspeed_prefix(), atspeed_prefix_destroy);
+  p->m = m; p->len = len; p->slot = adapter_slot;
+  p->fp8 = !m->fp8.empty(); p->fp4 = !m->fp4.empty(); p->lora_gen = m->lora_gen; p->slot_gen = m->slot_gen[adapter_slot];
+  const size_t store = (size_t)m->cfg.n_layers * len * m->cfg.hidden * m->esz;
+  ATS_HIP(hipMalloc(&p->k, store));
+  ATS_HIP(hipMalloc(&p->v, store));
+  ATS_HIP(hipMalloc((void**)&p->ids, (size_t)len * sizeof(int32_t)));
+  p->bytes = 2 * store + (size_t)len * sizeof(int32_t);
+  // scratch of this call: an arena in the engine's layout for the forward to write, the forward's token rows, and what prompt init writes besides
+  KvCache kv;
+  char* scr = nullptr;
+  const int W = m->vis_words;
+  const size_t tb_bytes = 3 * align_up((size_t)len * 4, 256) + align_up((size_t)len * W * 8, 256);
+  auto run = [&]() -> int {
+    ATS_TRY(kv_create(m, &kv));
+    ATS_HIP(hipMalloc((void**)&scr, tb_bytes + 6 * 256));
+    char* q = scr;
+    TokBuf tb; carve_tokbuf(q, tb, len, W);
+    BeamSet bs{}; bs.score = (float*)q; bs.node = (int32_t*)(q + 256); bs.parent = (int32_t*)(q + 512); bs.tok = (int32_t*)(q + 768); bs.flat = (int32_t*)(q + 1024);
+    ATS_TRY(ats_init_prompt(tb, ids, len, W, bs, 0, m->cfg.vocab_size, (Mailbox*)(q + 1280), st));
+    ATS_TRY(ensure_act(m, len, 1));
+    SegTable t{};
+    t.seg[t.n++] = make_seg(tb, len, len, 1, kv, adapter_slot);
+    ATS_TRY(ats_seg_finish(t));
+    ATS_TRY(llama_forward_segs(m, t, nullptr, st));
+    ATS_TRY(kv_rows_launch(p->k, p->v, std::vector<KvRowsUser>{KvRowsUser{kv.k, kv.v}}, len, m, 1, st));
+    ATS_HIP(hipMemcpyAsync(p->ids, ids, (size_t)len * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    return ATSPEED_OK;
+  };
+  const int rc = run();
+  const hipError_t e = hipStreamSynchronize(st);       // on failure too: what was launched writes the scratch
+  ats_stage_reset();
+  kv_free(&kv); hipFree(scr);
+  ATS_TRY(rc);
+  ATS_HIP(e);
+  *out = p.release();
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_prefix_info(const atspeed_prefix* p, int32_t* len, int64_t* users_served, int64_t* bytes) {
+  ATS_REQUIRE(p, ATSPEED_ERR_INVALID, "prefix_info: null prefix");
+  if (len) *len = p->len;
+  if (users_served) *users_served = p->users_served;
+  if (bytes) *bytes = (int64_t)p->bytes;
+  return prefix_stale(p) ? 1 : 0;
+}
+
+extern "C" int atspeed_prefix_read(const atspeed_prefix* p, void* k_dst, void* v_dst, int32_t* ids_dst, void* stream) {
+  ATS_REQUIRE(p, ATSPEED_ERR_INVALID, "prefix_read: null prefix");
+  const size_t store = (p->bytes - (size_t)p->len * sizeof(int32_t)) / 2;
+  if (k_dst) ATS_HIP(hipMemcpyAsync(k_dst, p->k, store, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (v_dst) ATS_HIP(hipMemcpyAsync(v_dst, p->v, store, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (ids_dst) ATS_HIP(hipMemcpyAsync(ids_dst, p->ids, (size_t)p->len * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return ATSPEED_OK;
+}
+
+// the copy kernel alone (tests): the caller's arenas, staged as the engine stages its users'
+static int kv_rows_abi(const char* who, void* store_k, void* store_v, void* const* k_arenas, void* const* v_arenas, int n, int len, int layers, int row_bytes,
+                       int max_slots, int to_store, hipStream_t st) {
+  ATS_REQUIRE(store_k && store_v && k_arenas && v_arenas, ATSPEED_ERR_INVALID, "%s: null argument", who);
+  ATS_REQUIRE(n >= 1 && n <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "%s: %d arenas per call (max %d)", who, n, ATS_MAX_SEGS);
+  std::vector<KvRowsUser> users(n);
+  for (int i = 0; i < n; ++i) {
+    ATS_REQUIRE(k_arenas[i] && v_arenas[i] && (((uintptr_t)k_arenas[i] | (uintptr_t)v_arenas[i]) & 15) == 0, ATSPEED_ERR_INVALID,
+                "%s: arena %d is null or not 16-byte aligned", who, i);
+    users[i] = KvRowsUser{k_arenas[i], v_arenas[i]};
+  }
+  const KvRowsUser* du = nullptr;
+  ATS_TRY(stage_args(users, &du, st));
+  return ats_bf16::ats_kv_rows_copy(store_k, store_v, du, n, len, layers, row_bytes, max_slots, to_store, st);
+}
+extern "C" int atspeed_kv_rows_scatter(const void* store_k, const void* store_v, void* const* k_arenas, void* const* v_arenas, int32_t n, int32_t len,
+                                       int32_t layers, int32_t row_bytes, int32_t max_slots, void* stream) {
+  return kv_rows_abi("kv_rows_scatter", (void*)store_k, (void*)store_v, k_arenas, v_arenas, n, len, layers, row_bytes, max_slots, 0, (hipStream_t)stream);
+}
+extern "C" int atspeed_kv_rows_gather(void* store_k, void* store_v, const void* k_arena, const void* v_arena, int32_t len, int32_t layers,
+                                      int32_t row_bytes, int32_t max_slots, void* stream) {
+  void* ka = (void*)k_arena; void* va = (void*)v_arena;
+  return kv_rows_abi("kv_rows_gather", store_k, store_v, &ka, &va, 1, len, layers, row_bytes, max_slots, 1, (hipStream_t)stream);
+}
+
+extern "C" int atspeed_prefix_to_batch_arenas(const atspeed_prefix* p, int32_t first, int32_t n, void* stream) {
+  ATS_REQUIRE(p, ATSPEED_ERR_INVALID, "prefix_to_batch_arenas: null prefix");
+  ATS_REQUIRE(first >= 0 && n >= 1 && first + n <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "prefix_to_batch_arenas: arenas [%d, %d) of at most %d", first, first + n, ATS_MAX_SEGS);
+  ATS_REQUIRE(!prefix_stale(p), ATSPEED_ERR_INVALID, "prefix_to_batch_arenas: the prompt prefix is stale: its model's quantisation or adapter changed after it was built");
+  atspeed_llama* m = p->m;
+  while ((int)m->kv_pool.size() < first + n) {
+    KvCache kv;
+    ATS_TRY(kv_create(m, &kv));
+    m->kv_pool.push_back(kv);
+  }
+  std::vector<KvRowsUser> users;
+  for (int i = first; i < first + n; ++i) users.push_back(KvRowsUser{m->kv_pool[i].k, m->kv_pool[i].v});
+  ATS_TRY(kv_rows_launch(p->k, p->v, users, p->len, m, 0, (hipStream_t)stream));
+  p->users_served += n;
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_decoder_set_prefix(atspeed_decoder* d, const atspeed_prefix* tp, const atspeed_prefix* dp) {
+  ATS_REQUIRE(d, ATSPEED_ERR_INVALID, "set_prefix: null decoder");
+  ATS_REQUIRE(!tp || tp->m == d->target, ATSPEED_ERR_INVALID, "set_prefix: the target prefix was built on another model");
+  ATS_REQUIRE(!dp || (d->draft && dp->m == d->draft), ATSPEED_ERR_INVALID, "set_prefix: the draft prefix was built on another model");
+  d->tprefix = tp; d->dprefix = dp;
+  return ATSPEED_OK;
+}
+
+// what a generate call asks of a user's prefixes before it launches anything; bssd: a beam-SD call or a session (draft and target share one
+// token buffer, so both models start at the same offset), else target_generate (the target's prefix alone counts)
+static int prefix_check(const char* who, const atspeed_llama* T, const atspeed_llama* D, int adapter, const atspeed_prefix* tp, const atspeed_prefix* dp,
+                        int P, bool bssd) {
+  if (!bssd) dp = nullptr;
+  if (!tp && !dp) return ATSPEED_OK;
+  ATS_REQUIRE(!bssd || (tp && dp), ATSPEED_ERR_INVALID, "%s: a beam-SD user needs the prefix of both models or of neither (the %s one is missing)", who,
+              tp ? "draft's" : "target's");
+  ATS_REQUIRE(tp, ATSPEED_ERR_INVALID, "%s: no target prefix", who);
+  ATS_REQUIRE(tp->m == T && (!dp || dp->m == D), ATSPEED_ERR_INVALID, "%s: the prompt prefix was built on another model", who);
+  ATS_REQUIRE(!prefix_stale(tp) && (!dp || !prefix_stale(dp)), ATSPEED_ERR_INVALID,
+              "%s: the prompt prefix is stale: its model's quantisation or adapter changed after it was built (build a new one)", who);
+  ATS_REQUIRE(tp->slot == adapter, ATSPEED_ERR_INVALID, "%s: the prompt prefix was built under adapter slot %d, the user runs under slot %d", who, tp->slot, adapter);
+  ATS_REQUIRE(!dp || dp->slot == 0, ATSPEED_ERR_INVALID, "%s: the draft is never adapted, its prefix names slot %d", who, dp ? dp->slot : 0);
+  ATS_REQUIRE(!dp || dp->len == tp->len, ATSPEED_ERR_INVALID, "%s: target and draft prefixes hold %d and %d tokens", who, tp->len, dp ? dp->len : 0);
+  ATS_REQUIRE(tp->len <= P - 1, ATSPEED_ERR_INVALID, "%s: a prefix of %d tokens needs a prompt of at least %d (one suffix row gives the first logit row), got %d",
+              who, tp->len, tp->len + 1, P);
+  return ATSPEED_OK;
+}
+static int prefix_len(const atspeed_decoder* d) { return d->tprefix ? d->tprefix->len : 0; }
+
+// the users' prefix rows into their arenas, in front of their first forward: per model one launch for all users that name the same prefix
+// (draft: the draft model's side too).  No user with a prefix: nothing is staged or launched
+static int prefixes_scatter(atspeed_decoder* const* decs, int n, bool draft_too, hipStream_t st) {
+  for (int side = 0; side < (draft_too ? 2 : 1); ++side) {
+    std::map<const atspeed_prefix*, std::vector<KvRowsUser>> by;
+    for (int u = 0; u < n; ++u) {
+      const atspeed_prefix* p = side ? decs[u]->dprefix : decs[u]->tprefix;
+      if (p && decs[u]->tprefix) by[p].push_back(side ? KvRowsUser{decs[u]->dkv.k, decs[u]->dkv.v} : KvRowsUser{decs[u]->tkv.k, decs[u]->tkv.v});
+    }
+    for (auto& e : by) {
+      ATS_TRY(kv_rows_launch(e.first->k, e.first->v, e.second, e.first->len, e.first->m, 0, st));
+      e.first->users_served += (int64_t)e.second.size();
+    }
+  }
+  return ATSPEED_OK;
+}
+static int prefix_mismatch_error(const atspeed_decoder* d) {
+  atspeed_set_error("generate: the prompt does not open with the %d tokens of its prompt prefix", prefix_len(d));
+  return ATSPEED_ERR_INVALID;
+}
+
 // ---- one decode step: forward, then every user's beam step on its rows of the result
 // where a segment's logit rows, their normalisers and their candidate lists start in the model's buffers
 struct RowViews { const float* logits; const float* lse; const int32_t* row_cand; };
@@ -1583,7 +1773,8 @@ static int init_prompts_multi(atspeed_decoder** decs, int n, const int32_t* cons
   int max_p = 1;
   for (int u = 0; u < n; ++u) {
     atspeed_decoder* d = decs[u];
-    ia[u] = InitPromptArgs{d->tin[0], prompts[u], prompt_lens[u], start_nodes[u], d->round_beams[0], d->mail_dev};
+    ia[u] = InitPromptArgs{d->tin[0], prompts[u], prompt_lens[u], start_nodes[u], d->round_beams[0], d->mail_dev, prefix_len(d),
+                           d->tprefix ? d->tprefix->ids : nullptr};
     max_p = std::max(max_p, (int)prompt_lens[u]);
   }
   const InitPromptArgs* dev = nullptr;
@@ -1598,15 +1789,21 @@ static int bssd_begin(atspeed_decoder* d, const int32_t* prompt, int P, const at
   ATS_REQUIRE(d->draft, ATSPEED_ERR_INVALID, "bssd: decoder was created without a draft model");
   ATS_REQUIRE(dk >= k && dk <= MAXB, ATSPEED_ERR_CAPACITY, "bssd: draft beam size %d must be in [k=%d, %d]", dk, k, MAXB);
   ATS_REQUIRE(gamma >= 1 && gamma <= ATSPEED_MAX_GAMMA, ATSPEED_ERR_CAPACITY, "bssd: gamma %d out of [1,%d]", gamma, ATSPEED_MAX_GAMMA);
+  ATS_TRY(prefix_check("bssd", d->target, d->draft, d->adapter, d->tprefix, d->dprefix, P, true));
+  const int lp = prefix_len(d);                    // the first round starts behind the prefix: what every later round looks like
   atspeed_decoder::Run& r = d->run;
   r.fsm = fsm; r.gamma = gamma; r.max_new = max_new; r.k = k; r.dk = dk;
   r.out_tokens = out_tokens; r.out_scores = out_scores; r.stats_out = stats;
   memset(&r.s, 0, sizeof(r.s));
-  r.cur = 0; r.gen = 0; r.base = 0; r.n0 = P; r.nb = 1; r.dl = 0;
+  r.cur = 0; r.gen = 0; r.base = lp; r.n0 = P - lp; r.nb = 1; r.dl = 0;
   r.reingest = false; r.final_step = false; r.export_only = false; r.done = false;
   d->trace.clear();
   d->decisions.clear();
-  if (init_prompt) ATS_TRY(ats_init_prompt(d->tin[0], prompt, P, d->W, d->round_beams[0], start_node, d->target->cfg.vocab_size, d->mail_dev, st));
+  if (init_prompt) {
+    ATS_TRY(ats_init_prompt(d->tin[0], prompt, P, d->W, d->round_beams[0], start_node, d->target->cfg.vocab_size, d->mail_dev, st, lp,
+                            lp ? d->tprefix->ids : nullptr));
+    ATS_TRY(prefixes_scatter(&d, 1, true, st));
+  }
   return ATSPEED_OK;
 }
 
@@ -1874,6 +2071,16 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
     atspeed_decoder* d = decs[u];
     atspeed_decoder::Run& r = d->run;
     if (r.done) continue;
+    if (d->mail_host->pad) {
+      // the prompt does not open with the user's prefix (found by prompt init): the user ends here, alone, as a filtered one does
+      if (!ctl.keep_filtered) return prefix_mismatch_error(d);
+      r.s.n_valid = 0; r.s.status = ATSPEED_ERR_INVALID;
+      ATS_TRY(blank_outputs(r.out_tokens, r.out_scores, r.k, r.max_new, st));
+      r.s.total_ms = r.s.draft_ms + r.s.target_ms + r.s.verify_ms;
+      if (r.stats_out) *r.stats_out = r.s;
+      r.done = true;
+      continue;
+    }
     if (ctl.keep_filtered && d->mail_host->status == ATSPEED_ERR_FILTERED) {
       // a lock-step batch does not die with one user: this user lost every beam of a step to the id filter (beamSD.py:80-86; the
       // reference dies on a shape mismatch there) and ends with no valid beam, the others go on (the one-user call returns the error)
@@ -1956,6 +2163,7 @@ extern "C" int atspeed_bssd_generate_batch(atspeed_decoder** decs, int32_t n, co
                        stats ? &stats[i] : nullptr, st, false));
   }
   ATS_TRY(init_prompts_multi(decs, n, prompts, prompt_lens, start_nodes, st));
+  ATS_TRY(prefixes_scatter(decs, n, true, st));
   return bssd_group_run(decs, n, st, true);
 }
 
@@ -1974,6 +2182,7 @@ struct SessionJob {          // a submitted user, as it waits in the queue and t
   int32_t* out_tokens = nullptr; float* out_scores = nullptr; atspeed_gen_stats* stats = nullptr;
   const atspeed_node_masks* masks = nullptr; int mask_user = 0;     // the user's item filter (atspeed_session_submit_masked)
   int adapter = 0;                                                   // the user's resident adapter slot (atspeed_session_submit_ex)
+  const atspeed_prefix *tprefix = nullptr, *dprefix = nullptr;       // the user's prompt prefixes (atspeed_session_submit_ex)
 };
 }  // namespace
 struct atspeed_session {
@@ -2068,12 +2277,14 @@ extern "C" int atspeed_session_submit_ex(atspeed_session* s, const atspeed_sessi
   ATS_REQUIRE(!masks || masks->fsm == s->fsm, ATSPEED_ERR_INVALID, "session_submit: the item filter was built on another automaton");
   ATS_REQUIRE(!masks || (user >= 0 && user < masks->n_users), ATSPEED_ERR_INVALID, "session_submit: filter user %d out of [0, %d)", user, masks ? masks->n_users : 0);
   ATS_TRY(check_common(s->lanes[0], prompt, P, s->fsm, start_node, s->max_new, s->k, out_tokens, out_scores));
+  ATS_TRY(prefix_check("session_submit", s->lanes[0]->target, s->lanes[0]->draft, uu.adapter, uu.target_prefix, uu.draft_prefix, P, true));
   ATS_REQUIRE(P <= s->max_prompt, ATSPEED_ERR_CAPACITY, "session_submit: prompt length %d exceeds the session's max_prompt %d", P, s->max_prompt);
   // a user's rounds need up to P + (max_new - 1) * dk KV slots (every draft block of the call kept): refused here, where it costs nobody else
   // a round, rather than inside one
   const int slots = P + (s->max_new - 1) * s->dk, max_slots = s->lanes[0]->target->cfg.max_slots;
   ATS_REQUIRE(slots <= max_slots, ATSPEED_ERR_CAPACITY, "session_submit: prompt of %d tokens can need %d KV slots (%d available)", P, slots, max_slots);
-  *ticket_out = s->q.submit(SessionJob{prompt, P, start_node, seed, out_tokens, out_scores, stats, masks, masks ? user : 0, uu.adapter});
+  *ticket_out = s->q.submit(SessionJob{prompt, P, start_node, seed, out_tokens, out_scores, stats, masks, masks ? user : 0, uu.adapter, uu.target_prefix,
+                                     uu.draft_prefix});
   return ATSPEED_OK;
 }
 
@@ -2093,11 +2304,15 @@ static int session_round(atspeed_session* s) {
     d->seed = j.seed;                                   // draws follow the user, not the lane
     d->masks = j.masks; d->mask_user = j.mask_user;     // and so does its item filter: on at admission, off at retirement
     d->adapter = j.adapter;                             // and its resident adapter
+    d->tprefix = j.tprefix; d->dprefix = j.dprefix;     // and its prompt prefixes
     ATS_TRY(bssd_begin(d, j.prompt, j.P, s->fsm, j.start_node, s->gamma, s->max_new, s->k, s->dk, j.out_tokens, j.out_scores, j.stats, s->st, false));
     fresh.push_back(d); prompts.push_back(j.prompt); lens.push_back(j.P); starts.push_back(j.start_node);
     return (int)ATSPEED_OK;
   }));
-  if (!fresh.empty()) ATS_TRY(init_prompts_multi(fresh.data(), (int)fresh.size(), prompts.data(), lens.data(), starts.data(), s->st));
+  if (!fresh.empty()) {
+    ATS_TRY(init_prompts_multi(fresh.data(), (int)fresh.size(), prompts.data(), lens.data(), starts.data(), s->st));
+    ATS_TRY(prefixes_scatter(fresh.data(), (int)fresh.size(), true, s->st));
+  }
   std::vector<atspeed_decoder*> decs; std::vector<int> lane_of;
   for (int l = 0; l < s->q.n_lanes(); ++l) if (s->q.lane_busy(l)) { decs.push_back(s->lanes[l]); lane_of.push_back(l); }
   if (decs.empty()) return ATSPEED_OK;
@@ -2107,7 +2322,10 @@ static int session_round(atspeed_session* s) {
   ATS_TRY(bssd_round(decs.data(), (int)decs.size(), s->st, g_ev, ctl));
   s->target_forwards += ctl.target_forwards; s->draft_forwards += ctl.draft_forwards; s->target_passes += ctl.target_passes;
   for (size_t i = 0; i < decs.size(); ++i)
-    if (decs[i]->run.done) { decs[i]->masks = nullptr; decs[i]->mask_user = 0; decs[i]->adapter = 0; s->q.retire(lane_of[i], decs[i]->run.s.status); }
+    if (decs[i]->run.done) {
+      decs[i]->masks = nullptr; decs[i]->mask_user = 0; decs[i]->adapter = 0; decs[i]->tprefix = decs[i]->dprefix = nullptr;
+      s->q.retire(lane_of[i], decs[i]->run.s.status);
+    }
   return ATSPEED_OK;
 }
 
@@ -2126,7 +2344,7 @@ static int session_round_guarded(atspeed_session* s) {
         atspeed_decoder::Run& r = s->lanes[l]->run;
         r.done = true; r.s.status = rc; r.s.n_valid = 0;
         if (r.stats_out) *r.stats_out = r.s;
-        s->lanes[l]->masks = nullptr; s->lanes[l]->mask_user = 0; s->lanes[l]->adapter = 0;
+        s->lanes[l]->masks = nullptr; s->lanes[l]->mask_user = 0; s->lanes[l]->adapter = 0; s->lanes[l]->tprefix = s->lanes[l]->dprefix = nullptr;
         s->q.retire(l, rc);
       }
     g_last_error = why;
@@ -2179,6 +2397,7 @@ static int target_check(atspeed_decoder* d, const int32_t* prompt, int P, const 
   ATS_TRY(check_common(d, prompt, P, fsm, start_node, max_new, k, out_tokens, out_scores));
   ATS_REQUIRE(P + max_new * k <= d->target->cfg.max_slots, ATSPEED_ERR_CAPACITY, "target_generate: KV slots exhausted");
   ATS_REQUIRE(P + max_new * k <= d->tok_cap, ATSPEED_ERR_CAPACITY, "target_generate: token buffer too small");
+  ATS_TRY(prefix_check("target_generate", d->target, d->draft, d->adapter, d->tprefix, d->dprefix, P, false));
   return ATSPEED_OK;
 }
 
@@ -2196,14 +2415,16 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
   ATS_TRY(stage_events(&g_ev));
   if (n == 1) {
     atspeed_decoder* d = decs[0];
-    ATS_TRY(ats_init_prompt(d->tin[0], prompts[0], prompt_lens[0], W, d->round_beams[0], start_nodes[0], T->cfg.vocab_size, d->mail_dev, st));
+    ATS_TRY(ats_init_prompt(d->tin[0], prompts[0], prompt_lens[0], W, d->round_beams[0], start_nodes[0], T->cfg.vocab_size, d->mail_dev, st, prefix_len(d),
+                            d->tprefix ? d->tprefix->ids : nullptr));
   } else {
     ATS_TRY(init_prompts_multi(decs, n, prompts, prompt_lens, start_nodes, st));
   }
+  ATS_TRY(prefixes_scatter(decs, n, false, st));
   hipEventRecord(g_ev[0], st);
   struct St { int row0, n_in, nb, base, cur; };
   std::vector<St> s(n);
-  for (int u = 0; u < n; ++u) s[u] = St{0, prompt_lens[u], 1, 0, 0};
+  for (int u = 0; u < n; ++u) s[u] = St{0, prompt_lens[u] - prefix_len(decs[u]), 1, prefix_len(decs[u]), 0};   // behind the user's prefix, if it has one
   std::vector<BeamStepArgs> args(n);
   std::vector<WarpCutArgs> wargs;
   for (int g = 0; g < max_new; ++g) {                                                // beamSD.py:579-588
@@ -2240,18 +2461,25 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
   hipEventElapsedTime(&ms, g_ev[0], g_ev[1]);
   // a lock-step batch does not die with a user that lost every beam of a step to the id filter: that user ends with a blanked result block
   // and its status, the others go on (as in the beam-SD batch loop); the one-user call returns the error
+  // so does a user whose prompt does not open with its prompt prefix (Mailbox::pad), with ATSPEED_ERR_INVALID
+  auto ends_alone = [&](int u) -> int {
+    if (decs[u]->mail_host->pad) return ATSPEED_ERR_INVALID;
+    return decs[u]->mail_host->status == ATSPEED_ERR_FILTERED ? ATSPEED_ERR_FILTERED : ATSPEED_OK;
+  };
+  if (n == 1 && decs[0]->mail_host->pad) return prefix_mismatch_error(decs[0]);
   bool any_filtered = false;
   for (int u = 0; u < n; ++u)
-    if (n > 1 && decs[u]->mail_host->status == ATSPEED_ERR_FILTERED) { ATS_TRY(blank_outputs(out_tokens[u], out_scores[u], k, max_new, st)); any_filtered = true; }
+    if (n > 1 && ends_alone(u) != ATSPEED_OK) { ATS_TRY(blank_outputs(out_tokens[u], out_scores[u], k, max_new, st)); any_filtered = true; }
   if (any_filtered) ATS_HIP(hipStreamSynchronize(st));
   for (int u = 0; u < n; ++u) {
-    const bool filtered = n > 1 && decs[u]->mail_host->status == ATSPEED_ERR_FILTERED;
+    const int alone = n > 1 ? ends_alone(u) : ATSPEED_OK;
+    const bool filtered = alone != ATSPEED_OK;
     if (!filtered) ATS_TRY(mailbox_status(decs[u]));
     if (stats) {
       atspeed_gen_stats gs;
       memset(&gs, 0, sizeof(gs));
       gs.n_target_forwards = gs.n_target_passes = max_new; gs.n_valid = filtered ? 0 : decs[u]->mail_host->n_valid;
-      gs.status = filtered ? ATSPEED_ERR_FILTERED : ATSPEED_OK;
+      gs.status = alone;
       gs.total_ms = gs.target_ms = ms / n;                      // the group's time shared equally by its users
       stats[u] = gs;
     }

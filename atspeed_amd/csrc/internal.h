@@ -82,6 +82,8 @@ enum { ATS_SW_GEMM_SK = 0,        // "gemm_sk"       ATSPEED_GEMM_SK (1): ring k
        ATS_N_SW };
 int ats_switch(int id);
 
+struct KvRowsUser { void* k; void* v; };     // one user's K / V arenas, layer-0 bases (ats_kv_rows_copy: a DEVICE array of these)
+
 enum { EPI_STORE = 0, EPI_F32 = 1, EPI_RESID = 2, EPI_SWIGLU = 3, EPI_F32_LSE = 4 /* ring kernel only: fp32 store + per-tile (max, sum exp) */,
        EPI_QKV_ROPE = 5 /* ring kernel only: qkv projection with RoPE + KV-cache scatter in the epilogue (ats_gemm_qkv_rope) */ };
 // the kernel translation units' functions, once per flavour (declarations: kernels_decl.inc)
@@ -149,7 +151,7 @@ struct Mailbox {      // device -> host, one per round
   int32_t n_matches;
   int32_t status;     // 0 ok, ATSPEED_ERR_*
   int32_t n_valid;
-  int32_t pad;
+  int32_t pad;        // 1: the user's prompt does not open with its prompt prefix (written by prompt init alone)
 };
 
 int ats_lse_rows(const float* logits, int n_rows, int vocab, int ld, float* lse, hipStream_t st);
@@ -222,12 +224,15 @@ int ats_row_warp_cutoff(const WarpCutArgs& a, hipStream_t st);
 int ats_row_warp_cutoff_multi(const WarpCutArgs* dev_args, int n, int max_rows, hipStream_t st);
 extern std::atomic<long long> g_ats_warp_launches;             // scan.hip: launches of the cutoff kernel (atspeed_warp_cutoff_launches)
 
+// lp > 0: the prompt's first lp tokens are a prefix whose K / V the arenas already hold (atspeed_prefix): row i of tb is prompt token lp + i
+// (pos = slot = lp + i, sees slots [0, lp + i]), prompt_len - lp rows in all, and prompt[0 .. lp) is compared with prefix_ids -- a difference
+// puts ATSPEED_ERR_INVALID into the mailbox's status and 1 into its pad word
 int ats_init_prompt(TokBuf tb, const int32_t* prompt, int prompt_len, int vis_words, BeamSet beams, int start_node,
-                    int vocab, Mailbox* mail, hipStream_t st);
+                    int vocab, Mailbox* mail, hipStream_t st, int lp = 0, const int32_t* prefix_ids = nullptr);
 // out_tokens[k][max_new] / out_scores[k] from a beam set
 int ats_export_beams(BeamSet b, int k, int max_new, int32_t* out_tokens, float* out_scores, hipStream_t st, bool sort_desc = false);
 // the same for every user of a lock-step batch in one launch each; `dev_args` = DEVICE arrays of n argument blocks (ats_stage)
-struct InitPromptArgs { TokBuf tb; const int32_t* prompt; int prompt_len; int start_node; BeamSet beams; Mailbox* mail; };
+struct InitPromptArgs { TokBuf tb; const int32_t* prompt; int prompt_len; int start_node; BeamSet beams; Mailbox* mail; int lp; const int32_t* prefix_ids; };
 struct ExportBeamsArgs { BeamSet b; int32_t* out_tokens; float* out_scores; int sort_desc; };
 int ats_init_prompt_multi(const InitPromptArgs* dev_args, int n, int max_prompt_len, int vis_words, int vocab, hipStream_t st);
 int ats_export_beams_multi(const ExportBeamsArgs* dev_args, int n, int k, int max_new, hipStream_t st);

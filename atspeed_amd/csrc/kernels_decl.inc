@@ -19,6 +19,10 @@ int ats_gather_tail_rows(const void* h, const void* att, const SegTable& t, cons
 int ats_rmsnorm(const void* x, const void* w, void* y, int rows, int hidden, float eps, int dtype, hipStream_t st, int pk = 0);   // pk: y in the packed operand layout
 // row-major [rows][row_bytes] -> packed operand layout (common.h ats_pk_byte) or back; out of place, row_bytes % 64 == 0
 int ats_pack_rows(const void* src, void* dst, int rows, int row_bytes, int to_packed, hipStream_t st);
+// rows [0, len) of every layer between a compact store [layers][len][row_bytes] (K and V) and arenas [layers][max_slots][row_bytes]: to_store = 0
+// scatters the store to the arenas of n_users (dev_users: DEVICE array) in one launch, 1 gathers it from dev_users[0]'s.  Bytes only: no flavour
+int ats_kv_rows_copy(void* store_k, void* store_v, const KvRowsUser* dev_users, int n_users, int len, int layers, int row_bytes, int max_slots,
+                     int to_store, hipStream_t st);
 
 // ---- lora.hip -------------------------------------------------------------------------
 // u [rows][r3] = round(A_cat . xn^T) per row, xn = the RMSNorm of h's row under norm_w (recomputed: independent of what the forward left in xn / xq);

@@ -1031,24 +1031,39 @@ __device__ void verify_walk_body(const VerifyArgs& a) {
 }
 
 // ---------------------------------------------------------------------------- prompt init / export / accept
-__device__ __forceinline__ void init_prompt_row(const TokBuf& tb, const int32_t* __restrict__ prompt, int t, int W, int vocab) {
+// row i of the token buffer = prompt token t = lp + i (lp = the length of a prompt prefix whose K / V are already in the user's arenas, 0 = none)
+__device__ __forceinline__ void init_prompt_row(const TokBuf& tb, const int32_t* __restrict__ prompt, int i, int lp, int W, int vocab) {
+  const int t = lp + i;
   int id = prompt[t];
-  tb.ids[t] = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-  tb.pos[t] = t;
-  tb.slot[t] = t;
+  tb.ids[i] = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  tb.pos[i] = t;
+  tb.slot[i] = t;
   for (int w = 0; w < W; ++w) {                         // causal prefix: bits [0, t]
     int lo = w * 64;
     uint64_t bits = (t >= lo + 63) ? ~0ull : (t < lo ? 0ull : ((~0ull) >> (63 - (t - lo))));
-    tb.vis[(size_t)t * W + w] = bits;
+    tb.vis[(size_t)i * W + w] = bits;
   }
 }
+// does prompt[0 .. lp) differ from the prefix's own ids?  Workgroup 0 alone asks (its thread 0 writes the mailbox); lp == 0: no
+__device__ __forceinline__ int prompt_prefix_differs(const int32_t* __restrict__ prompt, const int32_t* __restrict__ prefix_ids, int lp) {
+  if (lp <= 0 || blockIdx.x != 0) return 0;
+  int bad = 0;
+  for (int i = threadIdx.x; i < lp; i += blockDim.x) bad |= prompt[i] != prefix_ids[i] ? 1 : 0;
+  return __syncthreads_or(bad);
+}
+// a user whose prompt does not open with its prefix ends with ATSPEED_ERR_INVALID at the first read-back: `pad` keeps the finding whatever a
+// later step writes into status
+__device__ __forceinline__ void init_mailbox(Mailbox* mail, int differs) {
+  mail->n_matches = 0; mail->status = differs ? ATSPEED_ERR_INVALID : 0; mail->n_valid = 1; mail->pad = differs;
+}
 __global__ void init_prompt_kernel(TokBuf tb, const int32_t* __restrict__ prompt, int P, int W, BeamSet beams,
-                                   int start_node, int vocab, Mailbox* mail) {
+                                   int start_node, int vocab, Mailbox* mail, int lp, const int32_t* __restrict__ prefix_ids) {
   int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < P) init_prompt_row(tb, prompt, t, W, vocab);
+  if (t < P - lp) init_prompt_row(tb, prompt, t, lp, W, vocab);
+  const int differs = prompt_prefix_differs(prompt, prefix_ids, lp);
   if (t == 0) {
     beams.score[0] = 0.f; beams.node[0] = start_node; beams.parent[0] = 0; beams.tok[0] = 0; beams.flat[0] = 0;
-    mail->n_matches = 0; mail->status = 0; mail->n_valid = 1; mail->pad = 0;
+    init_mailbox(mail, differs);
   }
 }
 
@@ -1056,10 +1071,11 @@ __global__ void init_prompt_kernel(TokBuf tb, const int32_t* __restrict__ prompt
 __global__ void init_prompt_multi_kernel(const InitPromptArgs* __restrict__ args, int W, int vocab) {
   const InitPromptArgs a = args[blockIdx.y];
   int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < a.prompt_len) init_prompt_row(a.tb, a.prompt, t, W, vocab);
+  if (t < a.prompt_len - a.lp) init_prompt_row(a.tb, a.prompt, t, a.lp, W, vocab);
+  const int differs = prompt_prefix_differs(a.prompt, a.prefix_ids, a.lp);
   if (t == 0) {
     a.beams.score[0] = 0.f; a.beams.node[0] = a.start_node; a.beams.parent[0] = 0; a.beams.tok[0] = 0; a.beams.flat[0] = 0;
-    a.mail->n_matches = 0; a.mail->status = 0; a.mail->n_valid = 1; a.mail->pad = 0;
+    init_mailbox(a.mail, differs);
   }
 }
 
@@ -1392,8 +1408,8 @@ int ats_verify_walk_multi(const VerifyArgs* dev_args, int n, hipStream_t st) {
 }
 
 int ats_init_prompt(TokBuf tb, const int32_t* prompt, int prompt_len, int vis_words, BeamSet beams, int start_node,
-                    int vocab, Mailbox* mail, hipStream_t st) {
-  init_prompt_kernel<<<(prompt_len + 255) / 256, 256, 0, st>>>(tb, prompt, prompt_len, vis_words, beams, start_node, vocab, mail);
+                    int vocab, Mailbox* mail, hipStream_t st, int lp, const int32_t* prefix_ids) {
+  init_prompt_kernel<<<(prompt_len + 255) / 256, 256, 0, st>>>(tb, prompt, prompt_len, vis_words, beams, start_node, vocab, mail, lp, prefix_ids);
   ATS_LAUNCH_CHECK();
   return ATSPEED_OK;
 }

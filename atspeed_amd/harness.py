@@ -231,6 +231,8 @@ class InferenceResult:
     labels: List[List[int]] = field(default_factory=list)
     rows: List[Dict[str, float]] = field(default_factory=list)      # per-user timing / acceptance columns (inference.py:152-156,181-187)
     wall_s: float = 0.0
+    prefixes_built: int = 0          # share_prefix: PromptPrefix objects the run built (one per distinct shared opening)
+    prefix_users: int = 0            # ... and the users decoded behind one
 
     def metrics(self, index: ItemIndex, topN: Sequence[int] = (1, 5, 10, 20)) -> Dict[str, List[float]]:
         # items that share a code tuple are one item to the generator: compare by code tuple
@@ -278,9 +280,41 @@ def longest_prompt(data: "SeqRecTestData", L: int = 0, R: Optional[int] = None, 
     return max((len(encode_prompt(data, u, tokenizer, enc)) for u in data.users[L:stop_r]), default=1)
 
 
+MIN_SHARED_PREFIX = 8
+
+
+def common_prefix(prompts: Sequence[Sequence[int]], floor: int = MIN_SHARED_PREFIX) -> tuple:
+    """The shared opening of a batch's prompts (token id lists of any lengths) as `run_inference(share_prefix=True)` uses it: their longest
+    common prefix, capped at min(P) - 1 tokens -- every user keeps at least one token to prefill, the row its first logits come from -- and
+    () when fewer than `floor` tokens are left: below that a prefix saves less than its copy and its bookkeeping cost.  No prompts, or an
+    empty prompt, is a ValueError."""
+    if len(prompts) == 0:
+        raise ValueError("common_prefix: no prompts")
+    if any(len(p) == 0 for p in prompts):
+        raise ValueError("common_prefix: an empty prompt")
+    first = prompts[0]
+    n = min(len(p) for p in prompts) - 1
+    for p in prompts[1:]:
+        i = 0
+        while i < n and p[i] == first[i]:
+            i += 1
+        n = i
+    return tuple(int(t) for t in first[:n]) if n >= floor else ()
+
+
+def cached_prefix_for(ids: Sequence[int], built: Iterable[tuple]) -> tuple:
+    """Which prefix serves a batch whose shared opening is `ids` (`common_prefix`), given the token tuples of the prefixes built so far: the
+    longest of those that `ids` opens with -- the batch's prompts open with it too -- else `ids` itself, to be built.  A short last batch,
+    whose prompts share more than the template's header, so reuses the split's prefix instead of building one of its own."""
+    ids = tuple(ids)
+    best = max((k for k in built if len(k) <= len(ids) and ids[:len(k)] == k), key=len, default=())
+    return best if best else ids
+
+
 def run_inference(target, draft, data: SeqRecTestData, gamma: int = 4, max_new_tokens: int = 4, L: int = 0, R: Optional[int] = None,
                   users_per_batch: int = 128, prefix_allowed_tokens_fn=None, tokenizer=None, baseline: bool = False,
-                  device=None, decoder: str = "bssd", stream_lanes: Optional[int] = None, exclude_history: bool = False) -> InferenceResult:
+                  device=None, decoder: str = "bssd", stream_lanes: Optional[int] = None, exclude_history: bool = False,
+                  share_prefix: bool = False) -> InferenceResult:
     """Users [L, R) of the test set through beam-SD (inference.py:123-124,162-187), `users_per_batch` at a time in lock step.
     `baseline=True` also runs `target_generate` per user and records its time and the speed-up columns.
     `decoder="beam"`: the same users through the plain constrained beam search of the target (`target_generate_batch`, beamSD.py:544-595) --
@@ -289,9 +323,13 @@ def run_inference(target, draft, data: SeqRecTestData, gamma: int = 4, max_new_t
     `stream_lanes=N` (beam-SD only): all users through ONE session of N lanes (`BSSD_batch(..., lanes=N)`): a user that finishes hands its lane to
     the next one at the round boundary, `users_per_batch` is not used.  Same predictions.
     `exclude_history=True`: no user is recommended an item of its own train + valid history (all of it, not the `max_his_len` cut the
-    prompt shows): each user's items go to the decoder as `exclude_items`.  Needs the strict item trie (`data.strict_trie_fn()`)."""
+    prompt shows): each user's items go to the decoder as `exclude_items`.  Needs the strict item trie (`data.strict_trie_fn()`).
+    `share_prefix=True`: the tokens every prompt of a batch opens with (`common_prefix`: the template's header) are prefilled once, as a
+    `PromptPrefix`, and copied into the users' KV arenas; each user prefills the rest of its prompt only.  Prefixes are kept by their tokens
+    across the batches of the call and a batch reuses the longest built one its prompts open with, so a whole split builds one.  Same predictions; `prefixes_built` / `prefix_users` of the result count."""
     import torch
     from .beamSD import BSSD_batch, target_generate, target_generate_batch
+    from .model import PromptPrefix
     if decoder not in ("bssd", "beam"):
         raise ValueError(f"decoder must be 'bssd' or 'beam', not {decoder!r}")
     if stream_lanes is not None and (decoder != "bssd" or int(stream_lanes) < 1):
@@ -303,7 +341,22 @@ def run_inference(target, draft, data: SeqRecTestData, gamma: int = 4, max_new_t
     stop_r = min(len(data), R) if R is not None else len(data)
     sel = data.users[L:stop_r]
     res = InferenceResult()
-    prompts = [{"input_ids": torch.from_numpy(encode_prompt(data, u, tokenizer, enc))[None].to(dev)} for u in sel]
+    host_ids = [encode_prompt(data, u, tokenizer, enc) for u in sel]
+    prompts = [{"input_ids": torch.from_numpy(ids)[None].to(dev)} for ids in host_ids]
+    prefix_cache: Dict[tuple, PromptPrefix] = {}
+
+    def shared(lo: int, hi: int):
+        """the PromptPrefix of users [lo, hi), or None"""
+        ids = common_prefix([p.tolist() for p in host_ids[lo:hi]]) if share_prefix and hi > lo else ()
+        if not ids:
+            return None
+        ids = cached_prefix_for(ids, prefix_cache)
+        if ids not in prefix_cache:
+            prefix_cache[ids] = PromptPrefix(target, draft if decoder == "bssd" else None, ids)
+            res.prefixes_built += 1
+        res.prefix_users += hi - lo
+        return prefix_cache[ids]
+
     # the history items' code tokens; items that share a code tuple are one item to the generator, so listing each tuple once is enough
     excl = [[list(c) for c in sorted({data.index.item_codes[i] for i in u.full_history if i in data.index.item_codes})] for u in sel] \
         if exclude_history else None
@@ -312,15 +365,16 @@ def run_inference(target, draft, data: SeqRecTestData, gamma: int = 4, max_new_t
     if stream_lanes is not None:
         users_per_batch = max(len(sel), 1)                      # one call: the session is the batching
     for lo in range(0, len(sel), users_per_batch):
+        pre = shared(lo, min(lo + users_per_batch, len(sel)))
         if decoder == "beam":
             outs = target_generate_batch(target, prompts[lo:lo + users_per_batch], max_new_tokens, prefix_allowed_tokens_fn=fn,
-                                         exclude_items=excl[lo:lo + users_per_batch] if excl is not None else None)
+                                         exclude_items=excl[lo:lo + users_per_batch] if excl is not None else None, prefix=pre)
             for o in outs:                                  # the CSV columns of the beam-SD path (inference.py:152-156): no draft, no verification
                 o.update(draft_time_cost=0.0, target_time_cost=o["device_time_cost"], verify_time_cost=0.0, n_run=0, total_accept_steps=0,
                          total_accept_tokens=0, ave_accept_tokens=0.0)
         else:
             outs = BSSD_batch(target, draft, prompts[lo:lo + users_per_batch], gamma, max_new_tokens, prefix_allowed_tokens_fn=fn,
-                              lanes=stream_lanes, exclude_items=excl[lo:lo + users_per_batch] if excl is not None else None)
+                              lanes=stream_lanes, exclude_items=excl[lo:lo + users_per_batch] if excl is not None else None, prefix=pre)
         for u, pr, o in zip(sel[lo:lo + users_per_batch], prompts[lo:lo + users_per_batch], outs):
             P = pr["input_ids"].shape[1]
             # a user the library ended without a valid beam (status != 0: every beam of a step lost to the id filter, beamSD.py:80-86, where the

@@ -45,6 +45,9 @@ def parse(argv=None):
     ap.add_argument("--exclude_history", action="store_true",
                     help="never recommend a user an item of its own train + valid history (all of it, not the --max_his_len cut): a per-user item "
                          "filter on the device, users stay in lock step; needs --strict_trie")
+    ap.add_argument("--share_prefix", action="store_true",
+                    help="prefill the tokens every prompt of a batch opens with (the template's header) once and copy their K / V into each "
+                         "user's cache (PromptPrefix); users prefill the rest of their prompt only.  Same items")
     ap.add_argument("--decoder", choices=("bssd", "beam"), default="bssd",
                     help="bssd = beam speculative decoding (the reference's method); beam = plain constrained beam search of the target in lock "
                          "step: identical items, and on MI355X the faster of the two once a batch of users makes the target forward MFMA-bound "
@@ -159,7 +162,7 @@ def main(argv=None):
     for beam in ast.literal_eval(args.run_beam_sizes):          # the reference eval()s this flag (inference.py:151); a literal list is all it needs
         tgt, drf = load_models(args, data.index.vocab_size, beam, dev, max_prompt)
         res = run_inference(tgt, drf, data, args.gamma, 4, args.L + lo, args.L + hi, args.users_per_batch, fn, tok, args.baseline, dev, args.decoder,
-                            stream_lanes=args.stream_lanes, exclude_history=args.exclude_history)
+                            stream_lanes=args.stream_lanes, exclude_history=args.exclude_history, share_prefix=args.share_prefix)
         c = res.counters()
         per_rank = all_gather_counters(Counters(len(res.rows), int(sum(r["n_run"] for r in res.rows)),
                                                 int(sum(r["total_accept_steps"] for r in res.rows)), int(res.wall_s * 1e9)), dev)

@@ -503,6 +503,87 @@ class HipLlama:
         return [out[int(r0[i]): int(r0[i + 1])] for i in range(n)]
 
 
+class PromptPrefix:
+    """The K / V rows of a prompt opening that many users share (`include/atspeed_hip.h` "prompt prefixes"), made once by the models' own
+    forwards over `ids` and kept on the device: a user that names the prefix (`prefix=` / `prefixes=` of BSSD, BSSD_batch, target_generate(_batch)
+    and BSSDSession.submit) gets the rows copied into its KV arenas and prefills only the rest of its prompt.
+
+    `target`, `draft`: the HipLlama models the calls will be made with; `draft=None` builds the target's half alone, which serves
+    target_generate(_batch) -- the beam-SD calls need both.  `adapter`: the name of the resident adapter (`target.add_lora`) the users run
+    under, None = none (a model-wide `load_lora` adapter is part of the model's arithmetic and needs no name); the draft is never adapted.
+    The object holds strong references to its models and owns one library handle per model.
+
+    `stale`: the arithmetic of a model changed after the prefix was built (`enable_fp8` / `enable_fp4`, `load_lora` / `unload_lora`, or
+    `remove_lora` / `add_lora` of the prefix's own slot): every call refuses it (ValueError) and a new one has to be built.  Memory per
+    prefix and model: 2 x layers x length x hidden elements (`info()["bytes"]`)."""
+
+    def __init__(self, target: "HipLlama", draft: Optional["HipLlama"], ids, adapter: Optional[str] = None):
+        for m in (target,) + ((draft,) if draft is not None else ()):
+            if not isinstance(m, HipLlama):
+                raise TypeError("PromptPrefix: models must be atspeed_amd.HipLlama")
+        if torch.is_tensor(ids):
+            ids = ids.reshape(-1).tolist()
+        self.ids = tuple(int(t) for t in ids)
+        self.length = len(self.ids)
+        if self.length < 1:
+            raise ValueError("PromptPrefix: a prefix holds at least one token")
+        self.target, self.draft, self.adapter = target, draft, adapter
+        self.slot = target.adapter_slot(adapter)
+        lib = _lib.load()
+        self._owners = []
+        for m, slot in ((target, self.slot), (draft, 0)):
+            if m is None:
+                self._owners.append(None)
+                continue
+            with torch.cuda.device(m.device):
+                t = torch.tensor(self.ids, dtype=torch.int32, device=m.device)
+                self._owners.append(_lib.Handle.create("atspeed_prefix_destroy", lib.atspeed_prefix_create, m._handle, t.data_ptr(), self.length,
+                                                       slot, _lib.stream_ptr(m.device)))
+
+    def handle(self, draft: bool = False):
+        """the library object of the target's (draft's) half, None when that half was not built"""
+        o = self._owners[1 if draft else 0]
+        return o.ptr if o is not None else None
+
+    def info(self, draft: bool = False) -> Dict[str, int]:
+        """{length, users_served, bytes, stale} of one half (atspeed_prefix_info)"""
+        n, served, nbytes = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        st = _lib.load().atspeed_prefix_info(self.handle(draft), C.byref(n), C.byref(served), C.byref(nbytes))
+        if st < 0:
+            _lib.check(st)
+        return {"length": int(n.value), "users_served": int(served.value), "bytes": int(nbytes.value), "stale": bool(st)}
+
+    @property
+    def stale(self) -> bool:
+        return any(self.info(bool(i))["stale"] for i, o in enumerate(self._owners) if o is not None)
+
+    @property
+    def users_served(self) -> int:
+        return self.info()["users_served"]
+
+    def read(self, draft: bool = False):
+        """(K, V, ids) of one half as tensors: K and V [layers, length, hidden] in the model's type (atspeed_prefix_read; tests)"""
+        m = self.draft if draft else self.target
+        with torch.cuda.device(m.device):
+            k = torch.empty(m.dims.n_layers, self.length, m.dims.hidden, dtype=m._dtype, device=m.device)
+            v = torch.empty_like(k)
+            ids = torch.empty(self.length, dtype=torch.int32, device=m.device)
+            _lib.check(_lib.load().atspeed_prefix_read(self.handle(draft), k.data_ptr(), v.data_ptr(), ids.data_ptr(), _lib.stream_ptr(m.device)))
+        return k, v, ids
+
+    def to_batch_arenas(self, n: int, first: int = 0, draft: bool = False) -> None:
+        """Copy the rows into arenas [first, first + n) of the pool `forward_raw_batch` gives its sequences (atspeed_prefix_to_batch_arenas):
+        a following forward whose sequences start at position / slot `length` then sees the prefix as if it had prefilled it."""
+        m = self.draft if draft else self.target
+        with torch.cuda.device(m.device):
+            _lib.check(_lib.load().atspeed_prefix_to_batch_arenas(self.handle(draft), int(first), int(n), _lib.stream_ptr(m.device)))
+
+    def close(self) -> None:
+        for o in self._owners:
+            if o is not None:
+                o.close()
+
+
 def pack_vis_bits(vis: np.ndarray, max_slots: int) -> np.ndarray:
     """bool [T, S] -> int64 [T, max_slots/64]: bit s % 64 of word s // 64 = slot s visible (slots >= S are not); little-endian hosts."""
     T, S = vis.shape

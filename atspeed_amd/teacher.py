@@ -54,9 +54,10 @@ def _check_capacity(model: HipLlama, T: int) -> None:
 
 
 @torch.no_grad()
-def score_branches(model: HipLlama, prompt: np.ndarray, branches: Sequence[Sequence[int]]) -> List[torch.Tensor]:
-    """fp32 logits [len(branch), vocab] for each branch (row j predicts branch[j]) from ONE forward."""
-    return score_branches_batch(model, [prompt], [branches])[0]
+def score_branches(model: HipLlama, prompt: np.ndarray, branches: Sequence[Sequence[int]], prefix=None) -> List[torch.Tensor]:
+    """fp32 logits [len(branch), vocab] for each branch (row j predicts branch[j]) from ONE forward.  `prefix`: not served here
+    (NotImplementedError): the packed prompt + branches forward prefills every prompt whole."""
+    return score_branches_batch(model, [prompt], [branches], prefix=prefix)[0]
 
 
 def _score_rows(model: HipLlama, prompts, branches):
@@ -74,9 +75,13 @@ def _score_rows(model: HipLlama, prompts, branches):
 
 
 @torch.no_grad()
-def score_branches_batch(model: HipLlama, prompts: Sequence[np.ndarray], branches: Sequence[Sequence[Sequence[int]]]) -> List[List[torch.Tensor]]:
+def score_branches_batch(model: HipLlama, prompts: Sequence[np.ndarray], branches: Sequence[Sequence[Sequence[int]]],
+                         prefix=None) -> List[List[torch.Tensor]]:
     """`score_branches` for many samples in ONE forward (`HipLlama.forward_raw_batch`: every sample is a segment with a KV arena of
     its own)."""
+    if prefix is not None:
+        raise NotImplementedError("score_branches: prompt prefixes (PromptPrefix) serve the generate calls only; the branch-scoring forward "
+                                  "prefills every prompt whole")
     logits, index = _score_rows(model, prompts, branches)
     dev = model.device
     return [[logits[torch.tensor(r, device=dev)] for r in rows] for rows in index]

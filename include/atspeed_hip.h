@@ -522,12 +522,15 @@ int atspeed_session_submit_masked(atspeed_session* s, const int32_t* prompt_ids_
  *   a shorter struct of an older caller leaves the members it does not have at 0); atspeed_session_submit and _submit_masked forward to it with
  *   adapter 0.  The adapter follows the user to whichever lane admits it, as the seed and the filter do, and is validated here. */
 int atspeed_decoder_set_adapter(atspeed_decoder* d, int32_t slot);
+typedef struct atspeed_prefix atspeed_prefix;          /* "prompt prefixes" below */
 typedef struct atspeed_session_user {
   size_t struct_size;              /* sizeof(atspeed_session_user) of the caller's build                                */
   const int32_t* prompt_ids_dev; int32_t prompt_len; int32_t start_node; uint32_t seed;
   int32_t* out_tokens_dev; float* out_scores_dev; atspeed_gen_stats* stats_host;
   const atspeed_node_masks* masks; int32_t mask_user;   /* item filter, NULL = none (atspeed_session_submit_masked)     */
   int32_t adapter;                 /* resident slot of the session's target, 0 = none                                    */
+  const struct atspeed_prefix* target_prefix;   /* prompt prefix of the session's target and of its draft ("prompt prefixes" below): both or  */
+  const struct atspeed_prefix* draft_prefix;    /* neither; NULL = the whole prompt is prefilled                                              */
 } atspeed_session_user;
 int atspeed_session_submit_ex(atspeed_session* s, const atspeed_session_user* u, int64_t* ticket_out);
 /* The step and the cutoff kernel alone under a filter (tests): their unmasked twins' arguments plus (masks, user); masks = NULL: the twin. */
@@ -581,6 +584,53 @@ int64_t atspeed_decoder_decisions(atspeed_decoder* d, int32_t* out, int64_t cap_
  * and reads back which slots a call wrote (a round verified in stages leaves the slots of blocks it never forwarded untouched). */
 int64_t atspeed_decoder_kv_bytes(const atspeed_decoder* d, int32_t draft);
 int atspeed_decoder_kv_copy(atspeed_decoder* d, int32_t draft, int32_t to_cache, void* k_dev, void* v_dev, void* stream);
+
+/* ------------------------------------------------------------------ prompt prefixes: K / V of a shared prompt opening kept resident
+ * Prompts built from one template open with the same tokens.  An atspeed_prefix holds the K and V rows those tokens produce in ONE model, in
+ * every layer, as a compact store [layers][len][hidden] each in the model's type, plus the token ids.  A user that names a prefix gets the rows
+ * copied into slots [0, len) of its private arenas by one scatter launch (all users of a batch call / all users a session round admits that
+ * name the same prefix share the launch) and prefills only prompt tokens len .. P - 1: its first round is (base = len, n0 = P - len), which is
+ * what every later round looks like.  The attention kernels and every forward are untouched.  No reference counterpart: the reference
+ * prefills every prompt whole (beamSD.py:52,221).
+ *
+ * atspeed_prefix_create: runs m's own forward over the len tokens of ids_dev (one causal segment, positions and slots 0 .. len - 1, in the
+ *   mode the model is in: 16-bit / fp32 / W8A8 / W4A8, under its model-wide adapter or the resident slot adapter_slot, 0 = none) into a
+ *   scratch arena, gathers rows [0, len) of every layer into the store and keeps the ids.  Every allocation is made here (the scratch is freed
+ *   again); the call synchronises `stream`.  1 <= len < max_slots, else ATSPEED_ERR_INVALID.  The model must outlive the prefix.
+ * Staleness: the prefix remembers the arithmetic that produced it -- W8A8 on / off, W4A8 on / off, the model-wide adapter's generation, and
+ *   its slot with that slot's generation.  A later atspeed_llama_enable_fp8 / _enable_fp4 / _set_lora / _clear_lora that changes the model, or
+ *   an atspeed_llama_remove_lora / _add_lora of THAT slot, makes it stale (atspeed_prefix_info returns 1); other slots coming and going do not.
+ * Refused with ATSPEED_ERR_INVALID before anything is launched: a stale prefix, a prefix of another model, a target prefix whose slot differs
+ *   from the user's adapter, len > P - 1 (one suffix row is needed for the first logit row), target and draft prefixes of different length,
+ *   and -- for the beam-SD calls and sessions, whose two models share one token buffer -- a target prefix without a draft prefix or the reverse.
+ *   atspeed_target_generate(_batch) look at the target prefix alone.
+ * A prompt that does not open with the prefix's ids is found on the device by the prompt-init launch (no extra synchronisation): at the first
+ *   read-back that user ends with ATSPEED_ERR_INVALID -- in the batch calls and sessions alone, with stats.status set and a blanked result
+ *   block (scores -inf, tokens 0) as an ATSPEED_ERR_FILTERED user does, while the others go on; the one-user calls return the error.
+ * atspeed_prefix_info: *len, *users_served (users whose arenas received the rows so far), *bytes (device bytes the object owns); each may be
+ *   NULL.  Returns 1 for a stale prefix, 0 for a usable one, negative on error.
+ * atspeed_prefix_read: the store and the ids to the caller's device buffers ([layers][len][hidden] elements each, [len] int32), stream
+ *   ordered (tests); any of the three may be NULL.
+ * atspeed_decoder_set_prefix: the prefixes the generate calls made with this decoder use, like atspeed_decoder_set_adapter; either may be NULL,
+ *   both NULL clears.  A prefix must belong to the decoder's model of that role and stay alive while set (and, in a session, until the user's
+ *   ticket has come back). */
+int atspeed_prefix_create(atspeed_llama* m, const int32_t* ids_dev, int32_t len, int32_t adapter_slot, void* stream, atspeed_prefix** out);
+void atspeed_prefix_destroy(atspeed_prefix* p);
+int atspeed_prefix_info(const atspeed_prefix* p, int32_t* len, int64_t* users_served, int64_t* bytes);
+int atspeed_prefix_read(const atspeed_prefix* p, void* k_dst_dev, void* v_dst_dev, int32_t* ids_dst_dev, void* stream);
+int atspeed_decoder_set_prefix(atspeed_decoder* d, const atspeed_prefix* target_prefix, const atspeed_prefix* draft_prefix);
+/* The rows into arenas [first, first + n) of the pool atspeed_llama_forward_batch(_adapters) gives the sequences of the prefix's model (grown
+ * on demand, as that call grows it), one launch: a following forward whose sequences carry positions and slots from len on, and see slots
+ * [0, len + row], continues the prefix.  A stale prefix is refused; first + n <= 256.  Counts n users served. */
+int atspeed_prefix_to_batch_arenas(const atspeed_prefix* p, int32_t first, int32_t n, void* stream);
+/* The copy kernel alone.  store_k / store_v: [layers][len][row_bytes] device bytes, 16-byte aligned, row_bytes % 16 == 0; arenas: HOST arrays
+ * of n (1 .. 256) 16-byte aligned device pointers to [layers][max_slots][row_bytes] each.  atspeed_kv_rows_scatter writes rows [0, len) of every
+ * layer of every arena (each 16-byte piece of the store is loaded once and stored n times) and nothing else; atspeed_kv_rows_gather fills the
+ * store from ONE arena pair.  1 <= len <= max_slots.  tests/test_prefix_gpu.py::test_copy_kernel_guard_bands */
+int atspeed_kv_rows_scatter(const void* store_k_dev, const void* store_v_dev, void* const* k_arenas_dev, void* const* v_arenas_dev, int32_t n,
+                            int32_t len, int32_t layers, int32_t row_bytes, int32_t max_slots, void* stream);
+int atspeed_kv_rows_gather(void* store_k_dev, void* store_v_dev, const void* k_arena_dev, const void* v_arena_dev, int32_t len, int32_t layers,
+                           int32_t row_bytes, int32_t max_slots, void* stream);
 
 /* ------------------------------------------------------------------ low-level ops (tests, benches)
  * C[M,N] = A[M,K] * W[N,K]^T on MFMA; epilogue: 0 store (dtype), 1 fp32 store, 2 residual add into
