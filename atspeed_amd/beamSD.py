@@ -29,24 +29,27 @@ counter-based streams (hostmask.py): a callable wrapping a compilable constraint
 runs a list through one.
 
 The four entry points (BSSD, BSSD_batch, target_generate, target_generate_batch) share their scaffolding: `_mode` (models checked, sampling
-mode and warpers), `_setup` (prompts on the device, compiled constraints, the shared `_DeviceFSM`, one `_Decoder` per user, sampling and trace set),
+mode and warpers), `_user_opts` (the users' own options, below), `_prepare` / `_setup` (prompts on the device, compiled constraints, the shared
+`_DeviceFSM`, filter bitsets; one `_Decoder` per user, sampling and trace set),
 `_host_call` (dispatch to hostmask.py and result conversion), `_chunked` (lists above MAX_USERS_PER_CALL) and `_one_user_call` /
 `_batch_call` (buffers, argument marshalling and the library call: the one-user entry points keep their by-value launches, the batch ones
 take one pointer array entry per user).  `_DeviceFSM` and `_Decoder` cache device objects per constraint and per (model pair, lane) and
 hold what they were built from weakly; the objects themselves are owned by `_lib.Handle`.
 
-Item filters (`exclude_items=` / `allow_items=`, include/atspeed_hip.h "item filters"): per user a list of token sequences -- what a beam
-generates after the prompt, e.g. an item's code tokens -- that the user must not be recommended, or the only ones it may be.  They become
-per-user node bitsets over the shared automaton (`_item_filters`, built on the device), so filtered users keep their place in lock-step
-batches and sessions; draft and target see the same bits, so BSSD under a filter is plain beam search under that filter.
-
-Resident adapters (`adapter=` / `adapters=`, include/atspeed_hip.h "several RESIDENT adapters on one model"): per user the name of one of the
-LoRA adapters `HipLlama.add_lora` keeps on the target, or None.  It becomes the slot in the user's segment of every target forward
-(`_adapter_slots`, `_set_adapters`; sessions carry it in the submit record), so users of different fine-tunes share a batch or a session.
-
-Prompt prefixes (`prefix=` / `prefixes=`, include/atspeed_hip.h "prompt prefixes"): a `PromptPrefix` holds the K / V rows of a prompt opening
-that many users share; a user that names one gets the rows copied into its KV arenas and prefills only the rest of its prompt
-(`_prefix_list`, `_set_prefixes`; sessions carry it in the submit record).  Results are those of the full-prompt call.
+Per-user options: what a user names for itself travels as ONE record, `_UserOpts(filter, slot, prefix)`, built from the public keyword
+arguments by `_user_opts` (the validators `_filter_specs`, `_adapter_slots`, `_prefix_list`; None when nobody names anything) and handed on
+whole: `_apply_opts` puts a record on the user's decoder inside the `try` whose `finally` takes everything off again (`_clear_opts`), a
+session carries it in the submit record and the library clears the lane when the user leaves.  So between calls a cached decoder holds no
+filter, slot 0 and no prefix, whatever the call did and however it ended.  A further option is a field of the record and a line in each of
+`_user_opts`, `_apply_opts` and `_submit`.  The fields (include/atspeed_hip.h "item filters", "several RESIDENT adapters on one model",
+"prompt prefixes"):
+  filter (`exclude_items=` / `allow_items=`): token sequences -- what a beam generates after the prompt, e.g. an item's code tokens -- that
+    the user must not be recommended, or the only ones it may be; they become the user's node bitset over the shared automaton
+    (`_item_filters`, built on the device).  Draft and target see the same bits: BSSD under a filter is plain beam search under that filter.
+  slot (`adapter=` / `adapters=`): the name of a LoRA adapter `HipLlama.add_lora` keeps on the target -> the slot in the user's segment of
+    every target forward, so users of different fine-tunes share a batch or a session.
+  prefix (`prefix=` / `prefixes=`): a `PromptPrefix` holds the K / V rows of a prompt opening that many users share; its rows are copied into
+    the user's KV arenas and only the rest of the prompt is prefilled.  Results are those of the full-prompt call.
 """
 from __future__ import annotations
 
@@ -54,7 +57,7 @@ import ctypes as C
 import time
 import weakref
 from types import SimpleNamespace
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -281,44 +284,99 @@ def _set_decoders(decs, mode, num_beams: int, seeds, trace=None) -> None:
             d.trace_on = bool(trace)
 
 
-def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allowed_tokens_fn, mode, who: str, trace=None,
-           filters=None, first_user: int = 0, adapters=None, prefix=None, prefixes=None) -> SimpleNamespace:
-    """The device path's call setup, for one user or a lock-step batch: prompts on the device, each user's compiled constraint (the mask
+def _prepare(target: HipLlama, inputs_list, prefix_allowed_tokens_fn, opts, who: str, first_user: int = 0) -> SimpleNamespace:
+    """What a call's users are made of, before any decoder is touched: prompts on the device, each user's compiled constraint (the mask
     functions look at the prompt -- position of "Response:", data.py:97-102 -- with one D2H copy per call, where the reference does one per beam
-    per step, generation_trie.py:94, data.py:98), the ONE automaton they share (they may differ in their start node only), one decoder per
-    user (lane), set to the call's sampling mode (user u draws from stream seed + u) and, for BSSD (`trace` not None), its decision trace.
-    `filters` (`_filter_specs`): the users' item filters are built and set on their decoders; the caller clears them (`_clear_filters`)
-    when its library call has returned.  `adapters` (`_adapter_slots`): the users' resident adapter slots, None = nobody names one; set on
-    every call.  `prefix` / `prefixes`: the users' prompt prefixes (`_prefix_list`), set on their decoders here and cleared by the caller
-    (`_clear_call`) like the filters."""
+    per step, generation_trie.py:94, data.py:98), the ONE automaton they share (they may differ in their start node only) and the users'
+    records `opts` (`_user_opts`), where a user with a filter now has its node bitset in `mask` (which keeps the library object alive as long
+    as the record lives).  The lock-step calls (`_setup`), `BSSD_batch(lanes=N)` and `BSSDSession.submit` all start here."""
     dev = target.device
-    if filters is not None:
-        _check_filter_constraint(prefix_allowed_tokens_fn, who)
     prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
-    plist = _prefix_list(prefix, prefixes, len(prompts), target, draft, adapters, [int(p.numel()) for p in prompts], who)
     fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
     for f in fsms[1:]:
         if f.row_ptr is not fsms[0].row_ptr:
             raise ValueError(f"{who} needs one shared constraint automaton (only the start node may differ per user)")
     dfsm = _DeviceFSM.get(fsms[0], target.dims.vocab_size)
-    decs = [_Decoder.get(target, draft, int(p.numel()), lane=i) for i, p in enumerate(prompts)]
-    _set_decoders(decs, mode, target.generation_config.num_beams, [mode[2] + u for u in range(len(decs))], trace)
-    _set_adapters(decs, adapters)
-    owners = []
-    if filters is not None:
-        owners, per_user = _item_filters(dfsm, [f.start for f in fsms], filters, dev, who, first_user)
-        _set_filters(decs, per_user)
-    if plist is not None:
-        _set_prefixes(decs, plist, draft is not None)
-    return SimpleNamespace(dev=dev, prompts=prompts, fsms=fsms, dfsm=dfsm, decs=decs, filter_owners=owners, prefixes=plist)
+    if opts is not None and any(o.filter is not None for o in opts):
+        owners, masks = _item_filters(dfsm, [f.start for f in fsms], [o.filter for o in opts], dev, who, first_user)
+        opts = [o if m is None else o._replace(mask=(next(ow for ow in owners if ow.ptr is m[0]), m[1])) for o, m in zip(opts, masks)]
+    return SimpleNamespace(dev=dev, prompts=prompts, fsms=fsms, dfsm=dfsm, opts=opts)
 
 
-def _clear_call(c: SimpleNamespace) -> None:
-    """what a call put on its (cached) decoders for its own duration: item filters and prompt prefixes"""
-    if c.filter_owners:
-        _clear_filters(c.decs)
-    if c.prefixes is not None:
-        _clear_prefixes(c.decs)
+def _setup(target: HipLlama, draft: Optional[HipLlama], inputs_list, prefix_allowed_tokens_fn, mode, who: str, opts, trace=None,
+           first_user: int = 0) -> SimpleNamespace:
+    """The device path's call setup, for one user or a lock-step batch: `_prepare`, then one decoder per user (lane), set to the call's
+    sampling mode (user u draws from stream seed + u) and, for BSSD (`trace` not None), its decision trace.  The users' records `opts` go
+    onto the decoders around the library call itself (`_apply_opts` / `_clear_opts` in `_one_user_call` and `_batch_call`)."""
+    c = _prepare(target, inputs_list, prefix_allowed_tokens_fn, opts, who, first_user)
+    c.bssd = draft is not None
+    c.decs = [_Decoder.get(target, draft, int(p.numel()), lane=i) for i, p in enumerate(c.prompts)]
+    _set_decoders(c.decs, mode, target.generation_config.num_beams, [mode[2] + u for u in range(len(c.decs))], trace)
+    return c
+
+
+# ---------------------------------------------------------------- per-user options: one record, one builder, one refusal, one apply, one clear
+class _UserOpts(NamedTuple):
+    """what one user of a call names for itself (module docstring, "Per-user options")"""
+    filter: Optional[tuple] = None            # (mode, [token sequence, ...]) as `_filter_specs` makes it, None = unfiltered
+    slot: int = 0                             # the target's resident adapter slot (`_adapter_slots`), 0 = none
+    prefix: Optional[PromptPrefix] = None     # checked by `_prefix_list`
+    mask: Optional[tuple] = None              # (owner of the call's node bitsets, the user's index in them): `_prepare` makes it of `filter`
+
+    def mask_args(self):
+        """(masks, user) as atspeed_decoder_set_node_mask and the session's submit record take them"""
+        return (self.mask[0].ptr, self.mask[1]) if self.mask else (None, 0)
+
+
+def _user_opts(who: str, target, draft, inputs_list, prefix_allowed_tokens_fn, per_user: bool, host: bool, exclude_items=None, allow_items=None,
+               adapters=None, prefix=None, prefixes=None):
+    """The public keyword arguments of an entry point -> one `_UserOpts` per user, or None when no user names anything.  `per_user`: the batch
+    calls (one list entry or None per user; `prefix` = one for all), else a one-user call (`adapters` = its `adapter=`).  `host`: the call
+    takes the host path, where naming any option is refused.  Every check a call makes on its options before it touches the device, in the
+    order the entry points have always made them (the batch calls look at their adapters first, the one-user calls at their filter)."""
+    n = len(inputs_list)
+    slots = _adapter_slots(target, adapters, n, True, who) if per_user else None
+    specs = _filter_specs(n, exclude_items, allow_items, per_user, who)
+    if not per_user:
+        slots = _adapter_slots(target, adapters, n, False, who)
+    if host:
+        named = [name for name, v in (("exclude_items / allow_items", specs), ("adapter", slots), ("prefix", prefix)) if v is not None]
+        if named:
+            raise NotImplementedError(f"{who}: {', '.join(named)} run on the device path only (a mask that can compile() itself, no extra "
+                                      "logits_processor); on the host path put a filter into the mask callable and give the model its one "
+                                      "adapter with load_lora")
+        return None
+    if specs is not None:
+        _check_filter_constraint(prefix_allowed_tokens_fn, who)
+    plist = _prefix_list(prefix, prefixes, n, target, draft, slots, [int(_prompt_row(inp).numel()) for inp in inputs_list], who)
+    if specs is None and slots is None and plist is None:
+        return None
+    return [_UserOpts(specs[u] if specs else None, slots[u] if slots else 0, plist[u] if plist else None) for u in range(n)]
+
+
+def _apply_opts(c: SimpleNamespace) -> None:
+    """The users' records onto their decoders, every field of every user: called inside the `try` whose `finally` is `_clear_opts`.  A call
+    that names nothing sets nothing: the decoders hold nothing between calls."""
+    if c.opts is None:
+        return
+    lib = _lib.load()
+    for d, o in zip(c.decs, c.opts):
+        _lib.check(lib.atspeed_decoder_set_node_mask(d.handle, *o.mask_args()))
+        _lib.check(lib.atspeed_decoder_set_adapter(d.handle, o.slot))
+        _lib.check(lib.atspeed_decoder_set_prefix(d.handle, o.prefix.handle() if o.prefix else None,
+                                                  o.prefix.handle(True) if o.prefix and c.bssd else None))
+
+
+def _clear_opts(c: SimpleNamespace) -> None:
+    """A cached decoder keeps nothing of a call, however the call ended: a later call that names nothing is unfiltered, runs without adapter
+    and prefills its whole prompt (and the call's bitsets and prefixes may die).  Host-only calls that cannot fail."""
+    if c.opts is None:
+        return
+    lib = _lib.load()
+    for d in c.decs:
+        lib.atspeed_decoder_set_node_mask(d.handle, None, 0)
+        lib.atspeed_decoder_set_adapter(d.handle, 0)
+        lib.atspeed_decoder_set_prefix(d.handle, None, None)
 
 
 # ---------------------------------------------------------------- item filters
@@ -357,12 +415,6 @@ def _check_filter_constraint(prefix_allowed_tokens_fn, who: str) -> None:
                          f"{' with a chained trie' if hasattr(fn, 'trie') else ''} are not items)")
 
 
-def _refuse_host_filters(specs, who: str) -> None:
-    if specs is not None:
-        raise NotImplementedError(f"{who}: exclude_items / allow_items run on the device path only (a mask that can compile() itself, no "
-                                  "extra logits_processor); on the host path put the filter into the mask callable")
-
-
 def _item_filters(dfsm: _DeviceFSM, starts, specs, dev, who: str, first_user: int = 0):
     """The node bitsets of a call's filtered users -> (owners, per user None or (masks pointer, index)).  The users of one mode are built by
     ONE create call (a call whose users are all excluded-from or all allowed-to makes exactly one); `owners` keeps the library objects
@@ -397,19 +449,6 @@ def _item_filters(dfsm: _DeviceFSM, starts, specs, dev, who: str, first_user: in
     return owners, per_user
 
 
-def _set_filters(decs, per_user) -> None:
-    lib = _lib.load()
-    for d, pu in zip(decs, per_user):
-        _lib.check(lib.atspeed_decoder_set_node_mask(d.handle, pu[0] if pu else None, pu[1] if pu else 0))
-
-
-def _clear_filters(decs) -> None:
-    """A cached decoder must not keep a call's filter: a later unfiltered call on it is unfiltered (and the masks die with the call)."""
-    lib = _lib.load()
-    for d in decs:
-        lib.atspeed_decoder_set_node_mask(d.handle, None, 0)
-
-
 # ---------------------------------------------------------------- resident adapters (HipLlama.add_lora), one per user
 def _adapter_slots(target, adapters, n: int, per_user: bool, who: str):
     """The call's `adapter=` (one name or None) / `adapters=` (a list with one name or None per user) -> None when no user names an
@@ -428,23 +467,6 @@ def _adapter_slots(target, adapters, n: int, per_user: bool, who: str):
         if a is not None and a not in known:
             raise KeyError(f"{who}: no resident adapter named {a!r} on the target model (HipLlama.add_lora); resident: {sorted(known)}")
     return [0 if a is None else int(known[a]) for a in adapters]
-
-
-def _refuse_host_adapters(slots, who: str) -> None:
-    if slots is not None:
-        raise NotImplementedError(f"{who}: adapter= / adapters= run on the device path only (a mask that can compile() itself, no extra "
-                                  "logits_processor); on the host path give the model one adapter with load_lora")
-
-
-def _set_adapters(decs, slots) -> None:
-    """Every call sets its decoders' adapter, to 0 when it names none: a cached decoder must not keep an earlier call's.  The library is told
-    only when the slot changes (`adapter_slot`: what the decoder holds; None after a session used it, which sets its lanes' itself)."""
-    lib = _lib.load()
-    for i, d in enumerate(decs):
-        slot = slots[i] if slots is not None else 0
-        if getattr(d, "adapter_slot", 0) != slot:
-            _lib.check(lib.atspeed_decoder_set_adapter(d.handle, slot))
-            d.adapter_slot = slot
 
 
 # ---------------------------------------------------------------- prompt prefixes (PromptPrefix), one per user
@@ -486,25 +508,6 @@ def _prefix_list(prefix, prefixes, n: int, target, draft, slots, prompt_lens, wh
     return list(prefixes)
 
 
-def _refuse_host_prefixes(prefix, who: str) -> None:
-    if prefix is not None:
-        raise NotImplementedError(f"{who}: prefix= / prefixes= run on the device path only (a mask that can compile() itself, no extra "
-                                  "logits_processor)")
-
-
-def _set_prefixes(decs, prefixes, bssd: bool) -> None:
-    lib = _lib.load()
-    for d, p in zip(decs, prefixes):
-        _lib.check(lib.atspeed_decoder_set_prefix(d.handle, p.handle() if p else None, p.handle(True) if p and bssd else None))
-
-
-def _clear_prefixes(decs) -> None:
-    """A cached decoder must not keep a call's prefix: a later call without one prefills its whole prompt (and the prefix may die)."""
-    lib = _lib.load()
-    for d in decs:
-        lib.atspeed_decoder_set_prefix(d.handle, None, None)
-
-
 def _host_call(host_fn, models, inputs: Dict, args, logits_processor, prefix_allowed_tokens_fn, mode) -> Dict:
     """Arbitrary Python callables (a mask closure, extra logits processors) are served like the reference does, one host call per beam per
     step: `host_fn(*models, prompt, *args, fn, processors, sample)` of hostmask.py, its arrays back on the device.  With do_sample the draws happen
@@ -530,10 +533,11 @@ def _one_user_call(entry, c: SimpleNamespace, k: int, max_new_tokens: int, *midd
         scores = torch.empty(k, dtype=torch.float32, device=dev)
         stats = _lib.GenStats()
         try:
+            _apply_opts(c)
             _lib.check(entry(c.decs[0].handle, ids32.data_ptr(), int(prompt.numel()), c.dfsm.handle, c.fsms[0].start, *middle,
                              toks.data_ptr(), scores.data_ptr(), C.byref(stats), _lib.stream_ptr(dev)))
         finally:
-            _clear_call(c)
+            _clear_opts(c)
     seq = torch.cat((prompt.to(torch.int64)[None, :].repeat(k, 1), toks.to(torch.int64)), dim=1)
     return {"beam_sequence": seq, "beam_scores": scores}, stats
 
@@ -579,28 +583,27 @@ def _batch_call(entry, c: SimpleNamespace, k: int, max_new_tokens: int, *middle)
         ids32, toks, scores, keep = _batch_buffers(c.prompts, k, max_new_tokens, c.dev)
         stats = (_lib.GenStats * n)()
         try:
+            _apply_opts(c)
             _lib.check(entry(ptrs(*[d.handle for d in c.decs]), n, ptrs(*[t.data_ptr() for t in ids32]),
                              ints(*[int(p.numel()) for p in c.prompts]), c.dfsm.handle, ints(*[f.start for f in c.fsms]), *middle,
                              ptrs(*[t.data_ptr() for t in toks]), ptrs(*[t.data_ptr() for t in scores]), stats, _lib.stream_ptr(c.dev)))
         finally:
-            _clear_call(c)
+            _clear_opts(c)
     return (keep, toks, scores, k), stats
 
 
 MAX_USERS_PER_CALL = 256
 
 
-def _chunk_of(lists, i: int, n: int):
-    """users [i, i + n) of a per-user argument that may be None"""
-    return None if lists is None else lists[i:i + n]
-
-
-def _chunked(call, inputs_list, mode):
-    """The library batches up to MAX_USERS_PER_CALL users per forward; a longer list goes chunk by chunk through `call(chunk, seed)`, user u
-    of the list still drawing from stream seed + u."""
+def _chunked(call, inputs_list, mode, per_user: Dict, **shared):
+    """The library batches up to MAX_USERS_PER_CALL users per forward; a longer list goes chunk by chunk through the entry point itself,
+    `call(chunk, seed=, _first_user=, ...)`: user u of the list still draws from stream seed + u and is still user u in a message.
+    `per_user`: the call's per-user keyword arguments (a list or None each), sliced like the inputs; `shared` goes to every chunk as it is."""
     outs = []
     for i in range(0, len(inputs_list), MAX_USERS_PER_CALL):
-        outs += call(inputs_list[i:i + MAX_USERS_PER_CALL], (mode[2] + i) if mode[0] else None, i)
+        part = slice(i, i + MAX_USERS_PER_CALL)
+        outs += call(inputs_list[part], seed=(mode[2] + i) if mode[0] else None, _first_user=i,
+                     **{name: None if v is None else v[part] for name, v in per_user.items()}, **shared)
     return outs
 
 
@@ -632,18 +635,15 @@ def BSSD(target_model, draft_model, inputs: Dict, gamma: int, max_new_tokens: in
          logits_processor=None, prefix_allowed_tokens_fn=None, seed=None, trace_decisions: bool = False,
          exclude_items=None, allow_items=None, adapter=None, prefix=None) -> Dict:
     mode = _mode(seed, target_model, draft_model)
-    filters = _filter_specs(1, exclude_items, allow_items, False, "BSSD")
-    slots = _adapter_slots(target_model, adapter, 1, False, "BSSD")
-    if _host_path(logits_processor, prefix_allowed_tokens_fn):
-        _refuse_host_filters(filters, "BSSD")
-        _refuse_host_adapters(slots, "BSSD")
-        _refuse_host_prefixes(prefix, "BSSD")
+    host = _host_path(logits_processor, prefix_allowed_tokens_fn)
+    opts = _user_opts("BSSD", target_model, draft_model, [inputs], prefix_allowed_tokens_fn, False, host, exclude_items, allow_items, adapter, prefix)
+    if host:
         from .hostmask import bssd_host_mask
         return _host_call(bssd_host_mask, (target_model, draft_model), inputs, (int(gamma), int(max_new_tokens)), logits_processor,
                           prefix_allowed_tokens_fn, mode)
     k = int(target_model.generation_config.num_beams)                 # beamSD.py:482
     dk = int(draft_model.generation_config.num_beams)                 # beamSD.py:483
-    c = _setup(target_model, draft_model, [inputs], prefix_allowed_tokens_fn, mode, "BSSD", trace_decisions, filters, adapters=slots, prefix=prefix)
+    c = _setup(target_model, draft_model, [inputs], prefix_allowed_tokens_fn, mode, "BSSD", opts, trace_decisions)
     out, stats = _one_user_call(_lib.load().atspeed_bssd_generate, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     out.update(_bssd_stats(stats, k))
     return out
@@ -700,19 +700,15 @@ class BSSDSession:
             self._decs = [_Decoder.get(self.target, self.draft, self.max_prompt, lane=i) for i in range(self.n_lanes)]
         else:
             self._decs = [_Decoder(self.target, self.draft, self.max_prompt) for _ in range(self.n_lanes)]
-        _set_decoders(self._decs, self.mode, self.k, [self.mode[2]] * self.n_lanes, trace=False)    # the user's own seed comes with its admission
-        for d in self._decs:               # ... and so does its adapter: a lane starts without one (a cached decoder may hold an earlier call's),
-            _lib.check(lib.atspeed_decoder_set_adapter(d.handle, 0))     # the library sets and clears it per user, a later call sets it anew
-            d.adapter_slot = None
-        with torch.cuda.device(self.dev):
+        _set_decoders(self._decs, self.mode, self.k, [self.mode[2]] * self.n_lanes, trace=False)    # the user's own seed comes with its admission,
+        with torch.cuda.device(self.dev):                                                          # and so do its options (the library clears them when it leaves)
             self._owner = _lib.Handle.create("atspeed_session_destroy", lib.atspeed_session_create,
                                              (C.c_void_p * self.n_lanes)(*[d.handle for d in self._decs]), self.n_lanes, self._dfsm.handle,
                                              self.gamma, self.max_new_tokens, self.k, self.dk, self.max_prompt, _lib.stream_ptr(self.dev))
 
     def _submit(self, prompt: torch.Tensor, fsm: ConstraintFSM, ids32: torch.Tensor, toks: torch.Tensor, scores: torch.Tensor, seed=None,
-                mask=None, mask_owners=(), adapter: int = 0, prefix=None) -> int:
-        """`mask`: None or (masks pointer, user index) of the user's item filter; `mask_owners` stay alive until its ticket has come back;
-        `adapter`: the user's resident adapter slot on the target (0 = none); `prefix`: its checked PromptPrefix or None, kept alive likewise"""
+                opts: _UserOpts = _UserOpts()) -> int:
+        """`opts`: the user's record as `_prepare` returns it; it stays alive, its node bitset and prefix with it, until the ticket has come back"""
         if self._closed:
             raise RuntimeError("BSSDSession is closed")
         if self._fsm0 is None:
@@ -721,16 +717,15 @@ class BSSDSession:
             raise ValueError("BSSDSession needs one shared constraint automaton (only the start node may differ per user)")
         if seed is None:
             seed = self.mode[2] + self._submitted
-        user = SimpleNamespace(prompt=prompt, ids32=ids32, toks=toks, scores=scores, stats=_lib.GenStats(), t0=time.time(), mask_owners=mask_owners,
-                               prefix=prefix)
+        user = SimpleNamespace(prompt=prompt, ids32=ids32, toks=toks, scores=scores, stats=_lib.GenStats(), t0=time.time(), opts=opts)
         ticket = C.c_int64(0)
         # host only: the library queues the user and launches nothing, so no device guard (one per user would be the call's largest cost)
         fields = (ids32.data_ptr(), int(prompt.numel()), fsm.start, int(seed) & 0xFFFFFFFF, toks.data_ptr(), scores.data_ptr(), C.pointer(user.stats),
-                  mask[0] if mask else None, mask[1] if mask else 0, int(adapter))
-        if prefix is None:                 # the record without the prefix pair: the library reads the pair as NULL
+                  *opts.mask_args(), opts.slot)
+        if opts.prefix is None:            # the record without the prefix pair: the library reads the pair as NULL
             rec = _lib.SessionUser(C.sizeof(_lib.SessionUser), *fields)
         else:
-            rec = _lib.SessionUserPrefix(C.sizeof(_lib.SessionUserPrefix), *fields, prefix.handle(), prefix.handle(True))
+            rec = _lib.SessionUserPrefix(C.sizeof(_lib.SessionUserPrefix), *fields, opts.prefix.handle(), opts.prefix.handle(True))
         _lib.check(_lib.load().atspeed_session_submit_ex(self._owner.ptr, C.byref(rec), C.byref(ticket)))
         self._submitted += 1
         self._users[ticket.value] = user
@@ -743,28 +738,14 @@ class BSSDSession:
         resident adapter (`HipLlama.add_lora` on the target) the user runs under, None = none; it follows the user likewise, and must stay
         resident until the user's ticket has come back.  `prefix`: the `PromptPrefix` the user's prompt opens with; the session keeps it
         alive until the ticket has come back."""
-        filters = _filter_specs(1, exclude_items, allow_items, False, "BSSDSession.submit")
-        slots = _adapter_slots(self.target, adapter, 1, False, "BSSDSession.submit")
-        prompt = _prompt_row(inputs).to(self.dev)
-        plist = _prefix_list(prefix, None, 1, self.target, self.draft, slots, [int(prompt.numel())], "BSSDSession.submit")
-        fsm = _compile_constraint(self.fn, prompt.tolist())
+        opts = _user_opts("BSSDSession.submit", self.target, self.draft, [inputs], self.fn, False, False, exclude_items, allow_items, adapter, prefix)
+        c = _prepare(self.target, [inputs], self.fn, opts, "BSSDSession.submit", self._submitted)
+        prompt = c.prompts[0]
         with torch.cuda.device(self.dev):
             ids32 = prompt.to(torch.int32).contiguous()
             toks = torch.empty(self.k, self.max_new_tokens, dtype=torch.int32, device=self.dev)
             scores = torch.empty(self.k, dtype=torch.float32, device=self.dev)
-        mask, owners = None, ()
-        if filters is not None:
-            _check_filter_constraint(self.fn, "BSSDSession.submit")
-            if self._closed:
-                raise RuntimeError("BSSDSession is closed")
-            if self._fsm0 is None:
-                self._create(fsm)
-            elif fsm.row_ptr is not self._fsm0.row_ptr:
-                raise ValueError("BSSDSession needs one shared constraint automaton (only the start node may differ per user)")
-            owners, per_user = _item_filters(self._dfsm, [fsm.start], filters, self.dev, "BSSDSession.submit", self._submitted)
-            mask = per_user[0]
-        return self._submit(prompt, fsm, ids32, toks, scores, seed, mask, tuple(owners), slots[0] if slots is not None else 0,
-                            plist[0] if plist is not None else None)
+        return self._submit(prompt, c.fsms[0], ids32, toks, scores, seed, c.opts[0] if c.opts else _UserOpts())
 
     def _finished(self, buf, n: int, assemble: bool):
         out, now = [], time.time()
@@ -824,33 +805,24 @@ class BSSDSession:
         return False
 
 
-def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes: int, filters=None, adapters=None,
-                      prefix=None, prefixes=None):
+def _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes: int, opts=None):
     """`BSSD_batch(..., lanes=N)`: the whole list through one session of N lanes, results in list order.  The prompts, token blocks and
-    scores are the batch call's buffers (one allocation each) and the result tensors come from its one assemble launch."""
+    scores are the batch call's buffers (one allocation each) and the result tensors come from its one assemble launch; the whole list's
+    filter bitsets are built up front (`_prepare`) and live in the users' records until the drain is over."""
     if not inputs_list:
         return []
     t0 = time.time()
-    dev = target_model.device
-    prompts = [_prompt_row(inp).to(dev) for inp in inputs_list]
-    fsms = [_compile_constraint(prefix_allowed_tokens_fn, ids) for ids in _prompt_lists(prompts)]
-    plist = _prefix_list(prefix, prefixes, len(prompts), target_model, draft_model, adapters, [int(p.numel()) for p in prompts], "BSSD_batch")
+    c = _prepare(target_model, inputs_list, prefix_allowed_tokens_fn, opts, "BSSD_batch")
+    dev, prompts = c.dev, c.prompts
     n_lanes = max(1, min(int(lanes), len(prompts), MAX_USERS_PER_CALL))
     with BSSDSession(target_model, draft_model, n_lanes, gamma, max_new_tokens, prefix_allowed_tokens_fn,
                      max_prompt=max(int(p.numel()) for p in prompts), seed=seed, _cached_decoders=True) as ses:
         k = ses.k
         with torch.cuda.device(dev):
             ids32, toks, scores, keep = _batch_buffers(prompts, k, int(max_new_tokens), dev)
-        per_user, owners = [None] * len(prompts), []
-        if filters is not None:            # the whole list's bitsets up front; they outlive the drain
-            _check_filter_constraint(prefix_allowed_tokens_fn, "BSSD_batch")
-            ses._create(fsms[0])
-            owners, per_user = _item_filters(ses._dfsm, [f.start for f in fsms], filters, dev, "BSSD_batch")
-        tickets = [ses._submit(p, f, i32, toks[u], scores[u], mask=per_user[u], adapter=adapters[u] if adapters is not None else 0,
-                               prefix=plist[u] if plist is not None else None)
-                   for u, (p, f, i32) in enumerate(zip(prompts, fsms, ids32))]
+        tickets = [ses._submit(p, f, i32, toks[u], scores[u], opts=c.opts[u] if c.opts else _UserOpts())
+                   for u, (p, f, i32) in enumerate(zip(prompts, c.fsms, ids32))]
         done = dict(ses.drain(_assemble=False))
-        del owners
         wall = time.time() - t0
         outs = _batch_results(keep, toks, scores, k)
         for out, t in zip(outs, tickets):
@@ -883,24 +855,21 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
     under its own adapter, the draft is never adapted.
     `prefix` (one `PromptPrefix` for every user) / `prefixes` (one or None per user), on either path: the users' shared prompt openings,
     whose K / V are copied into the users' arenas instead of being prefilled."""
-    slots = _adapter_slots(target_model, adapters, len(inputs_list), True, "BSSD_batch")
+    opts = _user_opts("BSSD_batch", target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, True, False, exclude_items, allow_items,
+                      adapters, prefix, prefixes)
     if lanes is not None:
         if trace_decisions:
             raise ValueError("BSSD_batch(lanes=N) keeps no decision trace")
-        return _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes,
-                                 _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch"), slots, prefix, prefixes)
+        return _bssd_batch_lanes(target_model, draft_model, inputs_list, gamma, max_new_tokens, prefix_allowed_tokens_fn, seed, lanes, opts)
     mode = _mode(seed, target_model, draft_model)
-    if len(inputs_list) > MAX_USERS_PER_CALL:
-        return _chunked(lambda chunk, s, i: BSSD_batch(target_model, draft_model, chunk, gamma, max_new_tokens, prefix_allowed_tokens_fn,
-                                                       seed=s, trace_decisions=trace_decisions, exclude_items=_chunk_of(exclude_items, i, len(chunk)),
-                                                       allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i,
-                                                       adapters=_chunk_of(adapters, i, len(chunk)), prefix=prefix,
-                                                       prefixes=_chunk_of(prefixes, i, len(chunk))), inputs_list, mode)
-    filters = _filter_specs(len(inputs_list), exclude_items, allow_items, True, "BSSD_batch")
+    if len(inputs_list) > MAX_USERS_PER_CALL:          # the whole list's options are checked by now; every chunk builds the records of its own users
+        return _chunked(lambda chunk, **kw: BSSD_batch(target_model, draft_model, chunk, gamma, max_new_tokens, prefix_allowed_tokens_fn,
+                                                       trace_decisions=trace_decisions, **kw), inputs_list, mode,
+                        dict(exclude_items=exclude_items, allow_items=allow_items, adapters=adapters, prefixes=prefixes), prefix=prefix)
     k = int(target_model.generation_config.num_beams)
     dk = int(draft_model.generation_config.num_beams)
     t0 = time.time()
-    c = _setup(target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, mode, "BSSD_batch", trace_decisions, filters, _first_user, slots, prefix, prefixes)
+    c = _setup(target_model, draft_model, inputs_list, prefix_allowed_tokens_fn, mode, "BSSD_batch", opts, trace_decisions, _first_user)
     raw, stats = _batch_call(_lib.load().atspeed_bssd_generate_batch, c, k, max_new_tokens, int(gamma), int(max_new_tokens), k, dk)
     wall = time.time() - t0
     outs = _batch_results(*raw)
@@ -915,17 +884,14 @@ def BSSD_batch(target_model, draft_model, inputs_list, gamma: int, max_new_token
 def target_generate(model, inputs: Dict, max_new_tokens: int, logits_processor=None,
                     prefix_allowed_tokens_fn=None, seed=None, exclude_items=None, allow_items=None, adapter=None, prefix=None) -> Dict:
     mode = _mode(seed, model)
-    filters = _filter_specs(1, exclude_items, allow_items, False, "target_generate")
-    slots = _adapter_slots(model, adapter, 1, False, "target_generate")
-    if _host_path(logits_processor, prefix_allowed_tokens_fn):
-        _refuse_host_filters(filters, "target_generate")
-        _refuse_host_adapters(slots, "target_generate")
-        _refuse_host_prefixes(prefix, "target_generate")
+    host = _host_path(logits_processor, prefix_allowed_tokens_fn)
+    opts = _user_opts("target_generate", model, None, [inputs], prefix_allowed_tokens_fn, False, host, exclude_items, allow_items, adapter, prefix)
+    if host:
         from .hostmask import target_generate_host_mask
         return _host_call(target_generate_host_mask, (model,), inputs, (int(max_new_tokens),), logits_processor, prefix_allowed_tokens_fn,
                           mode)
     k = int(model.generation_config.num_beams)                        # beamSD.py:553
-    c = _setup(model, None, [inputs], prefix_allowed_tokens_fn, mode, "target_generate", filters=filters, adapters=slots, prefix=prefix)
+    c = _setup(model, None, [inputs], prefix_allowed_tokens_fn, mode, "target_generate", opts)
     out, stats = _one_user_call(_lib.load().atspeed_target_generate, c, k, max_new_tokens, int(max_new_tokens), k)
     out.update({"n_valid": int(stats.n_valid), "device_time_cost": stats.total_ms * 1e-3})
     return out
@@ -939,19 +905,14 @@ def target_generate_batch(model, inputs_list, max_new_tokens: int, prefix_allowe
     token sequences (or None = unfiltered) per user.  `adapters`: one resident adapter's name (`HipLlama.add_lora`) or None per user.
     `prefix` (one `PromptPrefix` for every user) / `prefixes` (one or None per user): the users' shared prompt openings."""
     mode = _mode(seed, model)
-    slots = _adapter_slots(model, adapters, len(inputs_list), True, "target_generate_batch")
+    opts = _user_opts("target_generate_batch", model, None, inputs_list, prefix_allowed_tokens_fn, True, False, exclude_items, allow_items,
+                      adapters, prefix, prefixes)
     if len(inputs_list) > MAX_USERS_PER_CALL:
-        return _chunked(lambda chunk, s, i: target_generate_batch(model, chunk, max_new_tokens, prefix_allowed_tokens_fn, seed=s,
-                                                                  exclude_items=_chunk_of(exclude_items, i, len(chunk)),
-                                                                  allow_items=_chunk_of(allow_items, i, len(chunk)), _first_user=i,
-                                                                  adapters=_chunk_of(adapters, i, len(chunk)), prefix=prefix,
-                                                                  prefixes=_chunk_of(prefixes, i, len(chunk))),
-                        inputs_list, mode)
-    filters = _filter_specs(len(inputs_list), exclude_items, allow_items, True, "target_generate_batch")
+        return _chunked(lambda chunk, **kw: target_generate_batch(model, chunk, max_new_tokens, prefix_allowed_tokens_fn, **kw), inputs_list, mode,
+                        dict(exclude_items=exclude_items, allow_items=allow_items, adapters=adapters, prefixes=prefixes), prefix=prefix)
     k = int(model.generation_config.num_beams)
     t0 = time.time()
-    c = _setup(model, None, inputs_list, prefix_allowed_tokens_fn, mode, "target_generate_batch", filters=filters, first_user=_first_user, adapters=slots,
-               prefix=prefix, prefixes=prefixes)
+    c = _setup(model, None, inputs_list, prefix_allowed_tokens_fn, mode, "target_generate_batch", opts, first_user=_first_user)
     raw, stats = _batch_call(_lib.load().atspeed_target_generate_batch, c, k, max_new_tokens, int(max_new_tokens), k)
     wall = time.time() - t0
     outs = _batch_results(*raw)

@@ -1202,6 +1202,14 @@ namespace {
 constexpr int MAXB = ATSPEED_MAX_BEAMS;
 constexpr int LMAX = ATSPEED_MAX_NEW_TOKENS;
 constexpr int NBLK = ATSPEED_MAX_GAMMA + 1;
+
+// What a user brings to the decoder it runs on: written by atspeed_decoder_set_node_mask / _set_adapter / _set_prefix, or handed over whole
+// when a session admits the user (SessionJob::opts); UserOpts{} = nothing named, which is what a decoder holds once its user has left.
+struct UserOpts {
+  const atspeed_node_masks* masks = nullptr; int mask_user = 0;   // item filter: the user's blocked-node bits over the call's automaton
+  int adapter = 0;        // the target's resident adapter slot, 0 = none: it rides in the user's segment of every target forward (the draft's keep 0)
+  const atspeed_prefix *tprefix = nullptr, *dprefix = nullptr;    // prompt prefixes: the user's first round starts at base = their length, the arenas'
+};                                                                // slots below that filled by the scatter launch in front of the first forward
 }  // namespace
 
 // One user: private KV caches for target and draft, device-side beam state, pinned mailbox and argument staging,
@@ -1233,16 +1241,9 @@ struct atspeed_decoder {
   int top_k = 0; float top_p = 1.f; int min_keep = 1;
   float* cutoff = nullptr;      // [MAXB + ATSPEED_MAX_GAMMA * MAXB] (allocated on first use)
   bool warps() const { return sample && (top_k > 0 || top_p < 1.f); }
-  // item filter (atspeed_decoder_set_node_mask; a session puts its user's there): none by default
-  const atspeed_node_masks* masks = nullptr; int mask_user = 0;
-  // the target's resident adapter this user runs under (atspeed_decoder_set_adapter; a session puts its user's there): 0 = none.  It rides in
-  // the user's segment of every target forward; the draft's segments keep 0
-  int adapter = 0;
-  // prompt prefixes (atspeed_decoder_set_prefix; a session puts its user's there): none by default.  A user with one starts its first round at
-  // base = the prefix's length, its arenas' slots below that filled by the scatter launch in front of the first forward
-  const atspeed_prefix *tprefix = nullptr, *dprefix = nullptr;
+  UserOpts opts;                // item filter, resident adapter and prompt prefixes of the user on this decoder
   // the automaton as this user's kernels take it by value: the shared arrays and the user's own blocked-node bits
-  FsmDev fsm_dev(const atspeed_fsm* fsm) const { FsmDev f = fsm->dev; f.blocked = ats_mask_bits(masks, mask_user); return f; }
+  FsmDev fsm_dev(const atspeed_fsm* fsm) const { FsmDev f = fsm->dev; f.blocked = ats_mask_bits(opts.masks, opts.mask_user); return f; }
   struct Run {
     const atspeed_fsm* fsm; int gamma, max_new, k, dk;
     int32_t* out_tokens; float* out_scores; atspeed_gen_stats* stats_out;
@@ -1349,14 +1350,14 @@ extern "C" int atspeed_decoder_set_warpers(atspeed_decoder* d, int32_t top_k, fl
 extern "C" int atspeed_decoder_set_node_mask(atspeed_decoder* d, const atspeed_node_masks* masks, int32_t user) {
   ATS_REQUIRE(d, ATSPEED_ERR_INVALID, "set_node_mask: null decoder");
   ATS_REQUIRE(!masks || (user >= 0 && user < masks->n_users), ATSPEED_ERR_INVALID, "set_node_mask: user %d out of [0, %d)", user, masks ? masks->n_users : 0);
-  d->masks = masks; d->mask_user = masks ? user : 0;
+  d->opts.masks = masks; d->opts.mask_user = masks ? user : 0;
   return ATSPEED_OK;
 }
 
 extern "C" int atspeed_decoder_set_adapter(atspeed_decoder* d, int32_t slot) {
   ATS_REQUIRE(d, ATSPEED_ERR_INVALID, "set_adapter: null decoder");
   ATS_REQUIRE(slot >= 0 && slot <= ATSPEED_LORA_MAX_ADAPTERS, ATSPEED_ERR_INVALID, "set_adapter: slot %d out of [0, %d]", slot, ATSPEED_LORA_MAX_ADAPTERS);
-  d->adapter = slot;                               // whether the target holds it is looked up when a generate call starts
+  d->opts.adapter = slot;                          // whether the target holds it is looked up when a generate call starts
   return ATSPEED_OK;
 }
 
@@ -1425,10 +1426,7 @@ static int check_common(atspeed_decoder* d, const int32_t* prompt, int P, const 
               fsm->dev.vocab, d->target->cfg.vocab_size);
   ATS_REQUIRE(start_node >= 0 && start_node < std::max(fsm->dev.n_nodes, 1), ATSPEED_ERR_INVALID, "generate: start node out of range");
   ATS_REQUIRE(!(d->sample && fsm->dev.n_nodes == 0), ATSPEED_ERR_INVALID, "generate: sampling needs a constraint automaton (mask-free search is greedy only)");
-  ATS_REQUIRE(!d->masks || d->masks->fsm == fsm, ATSPEED_ERR_INVALID, "generate: the decoder's item filter was built on another automaton");
-  ATS_REQUIRE(d->target->slot_ok(d->adapter), ATSPEED_ERR_INVALID, "generate: the decoder names adapter slot %d, which its target does not hold "
-              "(atspeed_llama_add_lora / atspeed_decoder_set_adapter)", d->adapter);
-  return ATSPEED_OK;
+  return ATSPEED_OK;             // the user's own options: user_opts_check, which every caller runs next
 }
 
 // a user that ends with NO valid beam (per-user ERR_FILTERED inside a lock-step batch): its result block must not keep whatever the caller's
@@ -1645,15 +1643,17 @@ extern "C" int atspeed_decoder_set_prefix(atspeed_decoder* d, const atspeed_pref
   ATS_REQUIRE(d, ATSPEED_ERR_INVALID, "set_prefix: null decoder");
   ATS_REQUIRE(!tp || tp->m == d->target, ATSPEED_ERR_INVALID, "set_prefix: the target prefix was built on another model");
   ATS_REQUIRE(!dp || (d->draft && dp->m == d->draft), ATSPEED_ERR_INVALID, "set_prefix: the draft prefix was built on another model");
-  d->tprefix = tp; d->dprefix = dp;
+  d->opts.tprefix = tp; d->opts.dprefix = dp;
   return ATSPEED_OK;
 }
 
-// what a generate call asks of a user's prefixes before it launches anything; bssd: a beam-SD call or a session (draft and target share one
-// token buffer, so both models start at the same offset), else target_generate (the target's prefix alone counts)
-static int prefix_check(const char* who, const atspeed_llama* T, const atspeed_llama* D, int adapter, const atspeed_prefix* tp, const atspeed_prefix* dp,
-                        int P, bool bssd) {
-  if (!bssd) dp = nullptr;
+// what a generate call or a session's submit asks of a user's options before anything is launched or queued: the filter lives on the call's
+// automaton, the target holds the adapter slot, and the prefixes fit models, adapter and prompt.  bssd: a beam-SD call or a session (draft
+// and target share one token buffer, so both models start at the same offset), else target_generate (the target's prefix alone counts)
+static int user_opts_check(const char* who, const atspeed_llama* T, const atspeed_llama* D, const atspeed_fsm* fsm, const UserOpts& o, int P, bool bssd) {
+  ATS_REQUIRE(!o.masks || o.masks->fsm == fsm, ATSPEED_ERR_INVALID, "%s: the user's item filter was built on another automaton", who);
+  ATS_REQUIRE(T->slot_ok(o.adapter), ATSPEED_ERR_INVALID, "%s: the user names adapter slot %d, which the target does not hold", who, o.adapter);
+  const atspeed_prefix *tp = o.tprefix, *dp = bssd ? o.dprefix : nullptr;
   if (!tp && !dp) return ATSPEED_OK;
   ATS_REQUIRE(!bssd || (tp && dp), ATSPEED_ERR_INVALID, "%s: a beam-SD user needs the prefix of both models or of neither (the %s one is missing)", who,
               tp ? "draft's" : "target's");
@@ -1661,14 +1661,14 @@ static int prefix_check(const char* who, const atspeed_llama* T, const atspeed_l
   ATS_REQUIRE(tp->m == T && (!dp || dp->m == D), ATSPEED_ERR_INVALID, "%s: the prompt prefix was built on another model", who);
   ATS_REQUIRE(!prefix_stale(tp) && (!dp || !prefix_stale(dp)), ATSPEED_ERR_INVALID,
               "%s: the prompt prefix is stale: its model's quantisation or adapter changed after it was built (build a new one)", who);
-  ATS_REQUIRE(tp->slot == adapter, ATSPEED_ERR_INVALID, "%s: the prompt prefix was built under adapter slot %d, the user runs under slot %d", who, tp->slot, adapter);
+  ATS_REQUIRE(tp->slot == o.adapter, ATSPEED_ERR_INVALID, "%s: the prompt prefix was built under adapter slot %d, the user runs under slot %d", who, tp->slot, o.adapter);
   ATS_REQUIRE(!dp || dp->slot == 0, ATSPEED_ERR_INVALID, "%s: the draft is never adapted, its prefix names slot %d", who, dp ? dp->slot : 0);
   ATS_REQUIRE(!dp || dp->len == tp->len, ATSPEED_ERR_INVALID, "%s: target and draft prefixes hold %d and %d tokens", who, tp->len, dp ? dp->len : 0);
   ATS_REQUIRE(tp->len <= P - 1, ATSPEED_ERR_INVALID, "%s: a prefix of %d tokens needs a prompt of at least %d (one suffix row gives the first logit row), got %d",
               who, tp->len, tp->len + 1, P);
   return ATSPEED_OK;
 }
-static int prefix_len(const atspeed_decoder* d) { return d->tprefix ? d->tprefix->len : 0; }
+static int prefix_len(const atspeed_decoder* d) { return d->opts.tprefix ? d->opts.tprefix->len : 0; }
 
 // the users' prefix rows into their arenas, in front of their first forward: per model one launch for all users that name the same prefix
 // (draft: the draft model's side too).  No user with a prefix: nothing is staged or launched
@@ -1676,8 +1676,8 @@ static int prefixes_scatter(atspeed_decoder* const* decs, int n, bool draft_too,
   for (int side = 0; side < (draft_too ? 2 : 1); ++side) {
     std::map<const atspeed_prefix*, std::vector<KvRowsUser>> by;
     for (int u = 0; u < n; ++u) {
-      const atspeed_prefix* p = side ? decs[u]->dprefix : decs[u]->tprefix;
-      if (p && decs[u]->tprefix) by[p].push_back(side ? KvRowsUser{decs[u]->dkv.k, decs[u]->dkv.v} : KvRowsUser{decs[u]->tkv.k, decs[u]->tkv.v});
+      const atspeed_prefix* p = side ? decs[u]->opts.dprefix : decs[u]->opts.tprefix;
+      if (p && decs[u]->opts.tprefix) by[p].push_back(side ? KvRowsUser{decs[u]->dkv.k, decs[u]->dkv.v} : KvRowsUser{decs[u]->tkv.k, decs[u]->tkv.v});
     }
     for (auto& e : by) {
       ATS_TRY(kv_rows_launch(e.first->k, e.first->v, e.second, e.first->len, e.first->m, 0, st));
@@ -1774,7 +1774,7 @@ static int init_prompts_multi(atspeed_decoder** decs, int n, const int32_t* cons
   for (int u = 0; u < n; ++u) {
     atspeed_decoder* d = decs[u];
     ia[u] = InitPromptArgs{d->tin[0], prompts[u], prompt_lens[u], start_nodes[u], d->round_beams[0], d->mail_dev, prefix_len(d),
-                           d->tprefix ? d->tprefix->ids : nullptr};
+                           d->opts.tprefix ? d->opts.tprefix->ids : nullptr};
     max_p = std::max(max_p, (int)prompt_lens[u]);
   }
   const InitPromptArgs* dev = nullptr;
@@ -1789,7 +1789,7 @@ static int bssd_begin(atspeed_decoder* d, const int32_t* prompt, int P, const at
   ATS_REQUIRE(d->draft, ATSPEED_ERR_INVALID, "bssd: decoder was created without a draft model");
   ATS_REQUIRE(dk >= k && dk <= MAXB, ATSPEED_ERR_CAPACITY, "bssd: draft beam size %d must be in [k=%d, %d]", dk, k, MAXB);
   ATS_REQUIRE(gamma >= 1 && gamma <= ATSPEED_MAX_GAMMA, ATSPEED_ERR_CAPACITY, "bssd: gamma %d out of [1,%d]", gamma, ATSPEED_MAX_GAMMA);
-  ATS_TRY(prefix_check("bssd", d->target, d->draft, d->adapter, d->tprefix, d->dprefix, P, true));
+  ATS_TRY(user_opts_check("bssd", d->target, d->draft, fsm, d->opts, P, true));
   const int lp = prefix_len(d);                    // the first round starts behind the prefix: what every later round looks like
   atspeed_decoder::Run& r = d->run;
   r.fsm = fsm; r.gamma = gamma; r.max_new = max_new; r.k = k; r.dk = dk;
@@ -1801,7 +1801,7 @@ static int bssd_begin(atspeed_decoder* d, const int32_t* prompt, int P, const at
   d->decisions.clear();
   if (init_prompt) {
     ATS_TRY(ats_init_prompt(d->tin[0], prompt, P, d->W, d->round_beams[0], start_node, d->target->cfg.vocab_size, d->mail_dev, st, lp,
-                            lp ? d->tprefix->ids : nullptr));
+                            lp ? d->opts.tprefix->ids : nullptr));
     ATS_TRY(prefixes_scatter(&d, 1, true, st));
   }
   return ATSPEED_OK;
@@ -1870,7 +1870,7 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
     atspeed_decoder::Run& r = d->run;
     if (r.done) continue;
     // (a slot removed under a user that is in a lane: the caller's error, found here before the round launches anything)
-    ATS_REQUIRE(T->slot_ok(d->adapter), ATSPEED_ERR_INVALID, "bssd: a user names adapter slot %d, which the target no longer holds", d->adapter);
+    ATS_REQUIRE(T->slot_ok(d->opts.adapter), ATSPEED_ERR_INVALID, "bssd: a user names adapter slot %d, which the target no longer holds", d->opts.adapter);
     r.final_step = r.export_only = false;
     if (r.gen >= r.max_new) { r.final_step = r.export_only = true; continue; }
     r.dl = std::min(r.gamma, r.max_new - r.gen - 1);                               // beamSD.py:504
@@ -1938,15 +1938,15 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
         atspeed_decoder* d = ver[j];
         atspeed_decoder::Run& r = d->run;
         const int Tn = r.n0 + r.dl * r.dk;
-        if (!staged)     t.seg[t.n++] = make_seg(d->tin[r.cur], Tn, r.base + Tn, r.nb + r.dl * r.dk, d->tkv, d->adapter);
-        else if (p == 0) t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv, d->adapter);
-        else             t.seg[t.n++] = make_seg(tb_offset(d->tin[r.cur], r.n0 + (p - 1) * r.dk, W), r.dk, r.base + r.n0 + p * r.dk, r.dk, d->tkv, d->adapter);
+        if (!staged)     t.seg[t.n++] = make_seg(d->tin[r.cur], Tn, r.base + Tn, r.nb + r.dl * r.dk, d->tkv, d->opts.adapter);
+        else if (p == 0) t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv, d->opts.adapter);
+        else             t.seg[t.n++] = make_seg(tb_offset(d->tin[r.cur], r.n0 + (p - 1) * r.dk, W), r.dk, r.base + r.n0 + p * r.dk, r.dk, d->tkv, d->opts.adapter);
         if (p == 0) r.s.n_target_forwards++;
         r.s.n_target_passes++;
       }
       if (p == 0) for (atspeed_decoder* d : fin) {
         atspeed_decoder::Run& r = d->run;
-        t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv, d->adapter);
+        t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv, d->opts.adapter);
         r.s.n_target_forwards++; r.s.n_target_passes++;
       }
       ATS_TRY(ats_seg_finish(t));
@@ -2180,9 +2180,7 @@ namespace {
 struct SessionJob {          // a submitted user, as it waits in the queue and then sits in its lane
   const int32_t* prompt = nullptr; int P = 0, start_node = 0; uint32_t seed = 0;
   int32_t* out_tokens = nullptr; float* out_scores = nullptr; atspeed_gen_stats* stats = nullptr;
-  const atspeed_node_masks* masks = nullptr; int mask_user = 0;     // the user's item filter (atspeed_session_submit_masked)
-  int adapter = 0;                                                   // the user's resident adapter slot (atspeed_session_submit_ex)
-  const atspeed_prefix *tprefix = nullptr, *dprefix = nullptr;       // the user's prompt prefixes (atspeed_session_submit_ex)
+  UserOpts opts;             // its item filter, adapter slot and prompt prefixes (atspeed_session_submit_ex): its lane's decoder holds them while it decodes
 };
 }  // namespace
 struct atspeed_session {
@@ -2251,14 +2249,20 @@ extern "C" int atspeed_session_create(atspeed_decoder* const* lanes, int32_t n_l
   return ATSPEED_OK;
 }
 
-extern "C" void atspeed_session_destroy(atspeed_session* s) { delete s; }
+// a decoder whose user has gone (finished, failed with its round, or left in its lane by a session that is closed) holds nobody's options:
+// the filter and the prefixes may be freed, and the decoder's next caller starts from nothing
+static void user_leaves(atspeed_decoder* d) { d->opts = UserOpts{}; }
+
+extern "C" void atspeed_session_destroy(atspeed_session* s) {
+  for (int l = 0; s && l < s->q.n_lanes(); ++l) if (s->q.lane_busy(l)) user_leaves(s->lanes[l]);    // the lanes' decoders outlive the session
+  delete s;
+}
 
 extern "C" int atspeed_session_submit_masked(atspeed_session* s, const int32_t* prompt, int32_t P, int32_t start_node, uint32_t seed,
                                              int32_t* out_tokens, float* out_scores, atspeed_gen_stats* stats, const atspeed_node_masks* masks,
                                              int32_t user, int64_t* ticket_out) {
   atspeed_session_user u{};
-  u.struct_size = sizeof(u);
-  u.prompt_ids_dev = prompt; u.prompt_len = P; u.start_node = start_node; u.seed = seed;
+  u.struct_size = sizeof(u); u.prompt_ids_dev = prompt; u.prompt_len = P; u.start_node = start_node; u.seed = seed;
   u.out_tokens_dev = out_tokens; u.out_scores_dev = out_scores; u.stats_host = stats; u.masks = masks; u.mask_user = user;
   return atspeed_session_submit_ex(s, &u, ticket_out);
 }
@@ -2270,21 +2274,18 @@ extern "C" int atspeed_session_submit_ex(atspeed_session* s, const atspeed_sessi
               user_in->struct_size);
   atspeed_session_user uu{};
   memcpy(&uu, user_in, std::min(user_in->struct_size, sizeof(uu)));
-  const int32_t* prompt = uu.prompt_ids_dev; const int32_t P = uu.prompt_len, start_node = uu.start_node, user = uu.mask_user; const uint32_t seed = uu.seed;
-  int32_t* out_tokens = uu.out_tokens_dev; float* out_scores = uu.out_scores_dev; atspeed_gen_stats* stats = uu.stats_host;
-  const atspeed_node_masks* masks = uu.masks;
-  ATS_REQUIRE(s->lanes[0]->target->slot_ok(uu.adapter), ATSPEED_ERR_INVALID, "session_submit: adapter slot %d is not occupied on the session's target", uu.adapter);
-  ATS_REQUIRE(!masks || masks->fsm == s->fsm, ATSPEED_ERR_INVALID, "session_submit: the item filter was built on another automaton");
-  ATS_REQUIRE(!masks || (user >= 0 && user < masks->n_users), ATSPEED_ERR_INVALID, "session_submit: filter user %d out of [0, %d)", user, masks ? masks->n_users : 0);
-  ATS_TRY(check_common(s->lanes[0], prompt, P, s->fsm, start_node, s->max_new, s->k, out_tokens, out_scores));
-  ATS_TRY(prefix_check("session_submit", s->lanes[0]->target, s->lanes[0]->draft, uu.adapter, uu.target_prefix, uu.draft_prefix, P, true));
+  const int32_t P = uu.prompt_len;
+  const UserOpts opts{uu.masks, uu.masks ? uu.mask_user : 0, uu.adapter, uu.target_prefix, uu.draft_prefix};
+  ATS_REQUIRE(!opts.masks || (opts.mask_user >= 0 && opts.mask_user < opts.masks->n_users), ATSPEED_ERR_INVALID, "session_submit: filter user %d out of [0, %d)",
+              opts.mask_user, opts.masks ? opts.masks->n_users : 0);
+  ATS_TRY(check_common(s->lanes[0], uu.prompt_ids_dev, P, s->fsm, uu.start_node, s->max_new, s->k, uu.out_tokens_dev, uu.out_scores_dev));
+  ATS_TRY(user_opts_check("session_submit", s->lanes[0]->target, s->lanes[0]->draft, s->fsm, opts, P, true));
   ATS_REQUIRE(P <= s->max_prompt, ATSPEED_ERR_CAPACITY, "session_submit: prompt length %d exceeds the session's max_prompt %d", P, s->max_prompt);
   // a user's rounds need up to P + (max_new - 1) * dk KV slots (every draft block of the call kept): refused here, where it costs nobody else
   // a round, rather than inside one
   const int slots = P + (s->max_new - 1) * s->dk, max_slots = s->lanes[0]->target->cfg.max_slots;
   ATS_REQUIRE(slots <= max_slots, ATSPEED_ERR_CAPACITY, "session_submit: prompt of %d tokens can need %d KV slots (%d available)", P, slots, max_slots);
-  *ticket_out = s->q.submit(SessionJob{prompt, P, start_node, seed, out_tokens, out_scores, stats, masks, masks ? user : 0, uu.adapter, uu.target_prefix,
-                                     uu.draft_prefix});
+  *ticket_out = s->q.submit(SessionJob{uu.prompt_ids_dev, P, uu.start_node, uu.seed, uu.out_tokens_dev, uu.out_scores_dev, uu.stats_host, opts});
   return ATSPEED_OK;
 }
 
@@ -2302,9 +2303,7 @@ static int session_round(atspeed_session* s) {
   ATS_TRY(s->q.admit([&](int lane, int64_t, SessionJob& j) {
     atspeed_decoder* d = s->lanes[lane];
     d->seed = j.seed;                                   // draws follow the user, not the lane
-    d->masks = j.masks; d->mask_user = j.mask_user;     // and so does its item filter: on at admission, off at retirement
-    d->adapter = j.adapter;                             // and its resident adapter
-    d->tprefix = j.tprefix; d->dprefix = j.dprefix;     // and its prompt prefixes
+    d->opts = j.opts;                                   // and so do its options: on at admission, off at retirement (user_leaves)
     ATS_TRY(bssd_begin(d, j.prompt, j.P, s->fsm, j.start_node, s->gamma, s->max_new, s->k, s->dk, j.out_tokens, j.out_scores, j.stats, s->st, false));
     fresh.push_back(d); prompts.push_back(j.prompt); lens.push_back(j.P); starts.push_back(j.start_node);
     return (int)ATSPEED_OK;
@@ -2323,7 +2322,7 @@ static int session_round(atspeed_session* s) {
   s->target_forwards += ctl.target_forwards; s->draft_forwards += ctl.draft_forwards; s->target_passes += ctl.target_passes;
   for (size_t i = 0; i < decs.size(); ++i)
     if (decs[i]->run.done) {
-      decs[i]->masks = nullptr; decs[i]->mask_user = 0; decs[i]->adapter = 0; decs[i]->tprefix = decs[i]->dprefix = nullptr;
+      user_leaves(decs[i]);
       s->q.retire(lane_of[i], decs[i]->run.s.status);
     }
   return ATSPEED_OK;
@@ -2344,7 +2343,7 @@ static int session_round_guarded(atspeed_session* s) {
         atspeed_decoder::Run& r = s->lanes[l]->run;
         r.done = true; r.s.status = rc; r.s.n_valid = 0;
         if (r.stats_out) *r.stats_out = r.s;
-        s->lanes[l]->masks = nullptr; s->lanes[l]->mask_user = 0; s->lanes[l]->adapter = 0; s->lanes[l]->tprefix = s->lanes[l]->dprefix = nullptr;
+        user_leaves(s->lanes[l]);
         s->q.retire(l, rc);
       }
     g_last_error = why;
@@ -2397,7 +2396,7 @@ static int target_check(atspeed_decoder* d, const int32_t* prompt, int P, const 
   ATS_TRY(check_common(d, prompt, P, fsm, start_node, max_new, k, out_tokens, out_scores));
   ATS_REQUIRE(P + max_new * k <= d->target->cfg.max_slots, ATSPEED_ERR_CAPACITY, "target_generate: KV slots exhausted");
   ATS_REQUIRE(P + max_new * k <= d->tok_cap, ATSPEED_ERR_CAPACITY, "target_generate: token buffer too small");
-  ATS_TRY(prefix_check("target_generate", d->target, d->draft, d->adapter, d->tprefix, d->dprefix, P, false));
+  ATS_TRY(user_opts_check("target_generate", d->target, d->draft, fsm, d->opts, P, false));
   return ATSPEED_OK;
 }
 
@@ -2416,7 +2415,7 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
   if (n == 1) {
     atspeed_decoder* d = decs[0];
     ATS_TRY(ats_init_prompt(d->tin[0], prompts[0], prompt_lens[0], W, d->round_beams[0], start_nodes[0], T->cfg.vocab_size, d->mail_dev, st, prefix_len(d),
-                            d->tprefix ? d->tprefix->ids : nullptr));
+                            d->opts.tprefix ? d->opts.tprefix->ids : nullptr));
   } else {
     ATS_TRY(init_prompts_multi(decs, n, prompts, prompt_lens, start_nodes, st));
   }
@@ -2430,7 +2429,7 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
   for (int g = 0; g < max_new; ++g) {                                                // beamSD.py:579-588
     SegTable t{};
     for (int u = 0; u < n; ++u)
-      t.seg[t.n++] = make_seg(tb_offset(decs[u]->tin[0], s[u].row0, W), s[u].n_in, s[u].base + s[u].n_in, s[u].nb, decs[u]->tkv, decs[u]->adapter);
+      t.seg[t.n++] = make_seg(tb_offset(decs[u]->tin[0], s[u].row0, W), s[u].n_in, s[u].base + s[u].n_in, s[u].nb, decs[u]->tkv, decs[u]->opts.adapter);
     ATS_TRY(ats_seg_finish(t));
     ATS_TRY(decode_forward(T, t, fsm, k, st));
     for (int u = 0; u < n; ++u) {
