@@ -285,7 +285,7 @@ struct ActCtx {
   // 20-140 tokens and launch-bound); the segment table lives at a fixed device address so that it is data, not a kernel argument
   SegTable* segtab_dev = nullptr;
   hipStream_t cap_stream = nullptr;
-  // tokens, logit rows, segments, query tiles, tile rows, weight scheme (0 16-bit, 1 fp8, 2 fp4), last layer's tail row-pruned (forward_prunes_tail)
+  // tokens, logit rows, segments, query tiles, tile rows, weight scheme (Scheme), last layer's tail row-pruned (forward_prunes_tail)
   typedef std::tuple<int, int, int, int, int, int, int> GraphKey;
   std::map<GraphKey, hipGraphExec_t> graphs;
   std::map<GraphKey, int> graph_seen;
@@ -295,12 +295,28 @@ struct ActCtx {
   std::vector<int> prof_kind, prof_m;            // kind / M per bracket of the pending forward
 };
 
-// library-owned quantised copies of one layer's four projections: weights and their scales (S = float: one per output row; void: packed bytes)
-template <typename S>
-struct QuantLayer { void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr; S *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr; };
-template <typename S>
-static void quant_layers_free(std::vector<QuantLayer<S>>& v) {
-  for (auto& f : v) { hipFree(f.wqkv); hipFree(f.wo); hipFree(f.wgu); hipFree(f.wd); hipFree(f.sqkv); hipFree(f.so); hipFree(f.sgu); hipFree(f.sd); }
+// The arithmetic of a layer projection: the model's 16-bit (fp32) weights, or library-owned quantised copies of them -- W8A8 (e4m3 rows, one
+// float scale per output row: atspeed_llama_enable_fp8) or W4A8 (MXFP4: e2m1 nibbles [rows][K / 2] + E8M0 scale bytes [rows][K / 32], gemm.hip
+// "W4A8": atspeed_llama_enable_fp4).  A model holds ONE scheme; a forward of a W8A8 model runs 16-bit the projections whose shape the W8A8
+// kernels do not take at its token count (engine_forward.inc).
+enum Scheme { SCHEME_16 = 0, SCHEME_W8A8 = 1, SCHEME_W4A8 = 2, N_SCHEMES = 3 };
+// The four projections of a layer, in the order of the profile brackets and the counters, and their GEMM shapes: out[M][ldc] = epi(x[M][K] W[N][K]^T)
+enum Proj { P_QKV = 0, P_O = 1, P_GU = 2, P_DOWN = 3, N_PROJ = 4 };
+struct ProjShape { int n, k, ldc, epi; };
+static ProjShape proj_shape(const atspeed_llama_config& c, int p) {
+  const int H = c.hidden, F = c.ffn;
+  switch (p) {
+    case P_QKV: return {3 * H, H, 3 * H, EPI_STORE};
+    case P_O: return {H, H, H, EPI_RESID};
+    case P_GU: return {2 * F, H, F, EPI_SWIGLU};
+    default: return {H, F, H, EPI_RESID};
+  }
+}
+static const void* proj_weight(const atspeed_llama_layer_weights& w, int p) { return p == P_QKV ? w.wqkv : p == P_O ? w.wo : p == P_GU ? w.wgu : w.wd; }
+// the quantised copies of one layer's projections: weights and scales (float per row or packed bytes by the scheme, cast where each family is called)
+namespace { struct QuantLayer { void* w[N_PROJ] = {}; void* s[N_PROJ] = {}; }; }
+static void quant_layers_free(std::vector<QuantLayer>& v) {
+  for (auto& f : v) for (int p = 0; p < N_PROJ; ++p) { hipFree(f.w[p]); hipFree(f.s[p]); }
   v.clear();
 }
 
@@ -312,12 +328,9 @@ struct atspeed_llama {
   int pk;                                        // 1: weights and GEMM-operand activations in the packed operand layout (common.h), bf16 only
   size_t layer_kv_bytes;
   float *cos_tab, *sin_tab;                      // [max_slots][head_dim/2]
-  // optional fp8 (e4m3, per-output-row scales) copies of the layer projections (atspeed_llama_enable_fp8)
-  using Fp8Layer = QuantLayer<float>;
-  std::vector<Fp8Layer> fp8;
-  // optional MXFP4 copies (e2m1 nibbles [rows][K / 2] + E8M0 scale bytes [rows][K / 32], gemm.hip "W4A8") (atspeed_llama_enable_fp4); exclusive with fp8
-  using Fp4Layer = QuantLayer<void>;
-  std::vector<Fp4Layer> fp4;
+  int scheme = SCHEME_16;                        // Scheme; quant holds the copies of every layer unless it is SCHEME_16
+  std::vector<QuantLayer> quant;
+  bool plain16() const { return scheme == SCHEME_16 && !has_lora(); }   // a 16-bit (fp32) target without adapter: row-pruned tail, staged verification
   // optional LoRA adapter kept beside the base (atspeed_llama_set_lora): library-owned zero-padded copies in ONE device block, per layer the
   // stacked A_cat [3 R16][hidden] (q, k, v; an absent module's rows are zero) and B_m [hidden][R16] (NULL = module not adapted)
   struct LoraLayer { const void* a_cat = nullptr; const void* b[3] = {nullptr, nullptr, nullptr}; };
@@ -349,9 +362,8 @@ struct atspeed_llama {
   double prof_big_ms[5] = {0, 0, 0, 0, 0};
   long prof_big_cnt[5] = {0, 0, 0, 0, 0};
   long prof_big_rows[5] = {0, 0, 0, 0, 0};
-  // how often each layer projection (0 qkv, 1 o_proj, 2 gate_up, 3 down) ran as an fp8 / as a bf16 (fp32) GEMM (atspeed_llama_fp8_counters)
-  long fp8_cnt[4] = {0, 0, 0, 0}, other_cnt[4] = {0, 0, 0, 0};
-  long fp4_cnt[4] = {0, 0, 0, 0};                // the same for the W4A8 projections (atspeed_llama_fp4_counters; `other` is shared)
+  // how often each layer projection ran in each scheme (atspeed_llama_fp8_counters, atspeed_llama_fp4_counters: both report SCHEME_16 as `other`)
+  long proj_cnt[N_SCHEMES][N_PROJ] = {};
   long rope_fused_cnt = 0;                       // qkv projections that carried RoPE + the KV scatter in their epilogue (atspeed_llama_rope_fused_launches)
   // staged verification's memory (bssd_round_staged): over the recent greedy verify walks on this target, decayed per round, how often a
   // draft block j was drafted and how often the walk needed its rows (n_matches >= j)
@@ -392,21 +404,15 @@ struct ProfBracket {
 static size_t gemm_ws_for(const atspeed_llama_config& c, int max_tok, int max_rows) {
   size_t best = 0;
   for (int m = 1; m <= max_tok; ++m) {          // the split-K plan depends on the exact M: take the true maximum
-    best = std::max(best, ATS_KD(c.dtype, ats_gemm_workspace_bytes(m, 3 * c.hidden, c.hidden, c.dtype)));
-    best = std::max(best, ATS_KD(c.dtype, ats_gemm_workspace_bytes(m, c.hidden, c.hidden, c.dtype)));
-    best = std::max(best, ATS_KD(c.dtype, ats_gemm_workspace_bytes(m, 2 * c.ffn, c.hidden, c.dtype)));
-    best = std::max(best, ATS_KD(c.dtype, ats_gemm_workspace_bytes(m, c.hidden, c.ffn, c.dtype)));
-    if (m <= max_rows) best = std::max(best, ATS_KD(c.dtype, ats_gemm_workspace_bytes(m, c.vocab_size, c.hidden, c.dtype)));
-    if (c.dtype != ATSPEED_F32) {                  // the W8A8 copies (atspeed_llama_enable_fp8): the split plans of one user's projections and of thin ring grids
-      best = std::max(best, ATS_KD(c.dtype, ats_gemm_fp8_workspace_bytes(m, 3 * c.hidden, c.hidden)));
-      best = std::max(best, ATS_KD(c.dtype, ats_gemm_fp8_workspace_bytes(m, c.hidden, c.hidden)));
-      best = std::max(best, ATS_KD(c.dtype, ats_gemm_fp8_workspace_bytes(m, c.hidden, c.ffn)));
-      // the W4A8 copies (atspeed_llama_enable_fp4): split plans of thin grids (qkv, o_proj, gate_up, down)
-      best = std::max(best, ATS_KD(c.dtype, ats_gemm_w4a8_workspace_bytes(m, 3 * c.hidden, c.hidden)));
-      best = std::max(best, ATS_KD(c.dtype, ats_gemm_w4a8_workspace_bytes(m, c.hidden, c.hidden)));
-      best = std::max(best, ATS_KD(c.dtype, ats_gemm_w4a8_workspace_bytes(m, 2 * c.ffn, c.hidden)));
-      best = std::max(best, ATS_KD(c.dtype, ats_gemm_w4a8_workspace_bytes(m, c.hidden, c.ffn)));
+    for (int p = 0; p < N_PROJ; ++p) {
+      const ProjShape s = proj_shape(c, p);
+      best = std::max(best, ATS_KD(c.dtype, ats_gemm_workspace_bytes(m, s.n, s.k, c.dtype)));
+      if (c.dtype == ATSPEED_F32) continue;        // a 16-bit model may get quantised copies later (enable_fp8 / enable_fp4): their split plans too
+      // (gate_up's W8A8 slabs have never been counted in: whether they fit decides its plan, so counting them in is a change of its own)
+      if (p != P_GU) best = std::max(best, ATS_KD(c.dtype, ats_gemm_fp8_workspace_bytes(m, s.n, s.k)));
+      best = std::max(best, ATS_KD(c.dtype, ats_gemm_w4a8_workspace_bytes(m, s.n, s.k)));
     }
+    if (m <= max_rows) best = std::max(best, ATS_KD(c.dtype, ats_gemm_workspace_bytes(m, c.vocab_size, c.hidden, c.dtype)));
   }
   return best + (1 << 20);
 }
@@ -555,8 +561,7 @@ extern "C" void atspeed_llama_destroy(atspeed_llama* m) {
   kv_free(&m->kv0);
   for (KvCache& kv : m->kv_pool) kv_free(&kv);
   act_free(m->act);
-  quant_layers_free(m->fp8);
-  quant_layers_free(m->fp4);
+  quant_layers_free(m->quant);
   hipFree(m->lora_mem);
   for (auto& sl : m->slots) hipFree(sl.mem);
   hipFree(m->slot_tab);
@@ -611,21 +616,21 @@ extern "C" int atspeed_lmhead_lse(const void* x, const void* w, float* logits, f
   return rc;
 }
 
-// how often each layer projection ran in the quantised format (`cnt`: fp8_cnt or fp4_cnt) and how often as a 16-bit (fp32) GEMM
-static int quant_counters(atspeed_llama* m, const char* who, long* cnt, int64_t* quant_out, int64_t* other_out, int32_t reset) {
+// how often each layer projection ran in the quantised `scheme` and how often as a 16-bit (fp32) GEMM
+static int quant_counters(atspeed_llama* m, const char* who, int scheme, int64_t* quant_out, int64_t* other_out, int32_t reset) {
   ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "%s: null model", who);
-  for (int i = 0; i < 4; ++i) {
-    if (quant_out) quant_out[i] = cnt[i];
-    if (other_out) other_out[i] = m->other_cnt[i];
-    if (reset) { cnt[i] = 0; m->other_cnt[i] = 0; }
+  for (int i = 0; i < N_PROJ; ++i) {
+    if (quant_out) quant_out[i] = m->proj_cnt[scheme][i];
+    if (other_out) other_out[i] = m->proj_cnt[SCHEME_16][i];
+    if (reset) { m->proj_cnt[scheme][i] = 0; m->proj_cnt[SCHEME_16][i] = 0; }
   }
   return ATSPEED_OK;
 }
 extern "C" int atspeed_llama_fp8_counters(atspeed_llama* m, int64_t* fp8_out, int64_t* other_out, int32_t reset) {
-  return quant_counters(m, "fp8_counters", m ? m->fp8_cnt : nullptr, fp8_out, other_out, reset);
+  return quant_counters(m, "fp8_counters", SCHEME_W8A8, fp8_out, other_out, reset);
 }
 extern "C" int atspeed_llama_fp4_counters(atspeed_llama* m, int64_t* fp4_out, int64_t* other_out, int32_t reset) {
-  return quant_counters(m, "fp4_counters", m ? m->fp4_cnt : nullptr, fp4_out, other_out, reset);
+  return quant_counters(m, "fp4_counters", SCHEME_W4A8, fp4_out, other_out, reset);
 }
 
 extern "C" int64_t atspeed_llama_rope_fused_launches(atspeed_llama* m, int32_t reset) {
@@ -653,56 +658,49 @@ extern "C" int atspeed_llama_read(atspeed_llama* m, int32_t what, int32_t index,
   return ATSPEED_OK;
 }
 
-// The quantised copies of every layer, made by `quant` (allocates one projection's copy and scales, launches its quantiser on st).  They are
-// built aside and reach *dst only after the last quantiser has run: on any failure the copies made so far are freed and the model is as before.
-template <typename S, typename Quant>
-static int quant_layers_build(atspeed_llama* m, std::vector<QuantLayer<S>>* dst, hipStream_t st, Quant quant) {
-  const int H = m->cfg.hidden, F = m->cfg.ffn;
-  std::vector<QuantLayer<S>> q(m->cfg.n_layers);
+// The quantised copies of every layer for `scheme`, made by `quant` (allocates one projection's copy and scales, launches its quantiser on st)
+// from the model's own 16-bit values with the kernel of its flavour (round 6: the reference loads fp16 checkpoints and runs the target 8-bit,
+// code/inference.py:75-91); the activations between the quantised projections stay in that type.  The copies are built aside and reach the
+// model only after the last quantiser has run: on any failure the copies made so far are freed and the model is as before.
+template <typename Quant>
+static int quant_layers_build(atspeed_llama* m, const char* who, int scheme, hipStream_t st, Quant quant) {
+  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "%s: null model", who);
+  ATS_REQUIRE(m->cfg.dtype == ATSPEED_BF16 || m->cfg.dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "%s: the model must hold bf16 or fp16 weights", who);
+  ATS_REQUIRE(m->cfg.hidden % 256 == 0 && m->cfg.ffn % 256 == 0, ATSPEED_ERR_INVALID, "%s: hidden and ffn must be multiples of 256", who);
+  const int other_bits = scheme == SCHEME_W8A8 ? 4 : 8;
+  ATS_REQUIRE(m->scheme == SCHEME_16 || m->scheme == scheme, ATSPEED_ERR_INVALID, "%s: the model already runs the %d-bit target (atspeed_llama_enable_fp%d)",
+              who, other_bits, other_bits);
+  if (m->scheme == scheme) return ATSPEED_OK;
+  std::vector<QuantLayer> q(m->cfg.n_layers);
   int rc = ATSPEED_OK;
-  for (int l = 0; rc == ATSPEED_OK && l < m->cfg.n_layers; ++l) {
-    const atspeed_llama_layer_weights& w = m->layers[l];
-    QuantLayer<S>& f = q[l];
-    rc = quant(w.wqkv, 3 * H, H, &f.wqkv, &f.sqkv);
-    if (rc == ATSPEED_OK) rc = quant(w.wo, H, H, &f.wo, &f.so);
-    if (rc == ATSPEED_OK) rc = quant(w.wgu, 2 * F, H, &f.wgu, &f.sgu);
-    if (rc == ATSPEED_OK) rc = quant(w.wd, H, F, &f.wd, &f.sd);
-  }
+  for (int l = 0; rc == ATSPEED_OK && l < m->cfg.n_layers; ++l)
+    for (int p = 0; rc == ATSPEED_OK && p < N_PROJ; ++p) {
+      const ProjShape s = proj_shape(m->cfg, p);
+      rc = quant(proj_weight(m->layers[l], p), s.n, s.k, &q[l].w[p], &q[l].s[p]);
+    }
   const hipError_t e = hipStreamSynchronize(st);      // on failure too: the quantisers already launched write the copies
   if (rc != ATSPEED_OK || e != hipSuccess) {
     quant_layers_free(q);
     ATS_TRY(rc);
     ATS_HIP(e);
   }
-  *dst = std::move(q);
+  m->quant = std::move(q);
+  m->scheme = scheme;
   return ATSPEED_OK;
 }
 
 extern "C" int atspeed_llama_enable_fp8(atspeed_llama* m, void* stream) {
-  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "enable_fp8: null model");
-  // bf16 or fp16 weights (round 6: the reference loads fp16 checkpoints and runs the target 8-bit, code/inference.py:75-91): the e4m3 copies are
-  // made from the model's own 16-bit values by the quantisation kernel of its flavour, the activations between the W8A8 projections stay in that type
-  ATS_REQUIRE(m->cfg.dtype == ATSPEED_BF16 || m->cfg.dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "enable_fp8: the model must hold bf16 or fp16 weights");
-  ATS_REQUIRE(m->cfg.hidden % 256 == 0 && m->cfg.ffn % 256 == 0, ATSPEED_ERR_INVALID, "enable_fp8: hidden and ffn must be multiples of 256");
-  ATS_REQUIRE(m->fp4.empty(), ATSPEED_ERR_INVALID, "enable_fp8: the model already runs the 4-bit target (atspeed_llama_enable_fp4)");
-  if (!m->fp8.empty()) return ATSPEED_OK;
   hipStream_t st = (hipStream_t)stream;
-  return quant_layers_build(m, &m->fp8, st, [&](const void* w, int rows, int cols, void** q, float** sc) -> int {     // packed 16-bit rows -> packed e4m3 rows (or row-major both)
+  return quant_layers_build(m, "enable_fp8", SCHEME_W8A8, st, [&](const void* w, int rows, int cols, void** q, void** sc) -> int {     // packed 16-bit rows -> packed e4m3 rows (or row-major both)
     ATS_HIP(hipMalloc(q, (size_t)((rows + 1) & ~1) * cols));
-    ATS_HIP(hipMalloc((void**)sc, (size_t)rows * sizeof(float)));
-    return ATS_KD(m->cfg.dtype, ats_quant_rows_fp8(w, rows, cols, cols, *q, *sc, st, m->pk));
+    ATS_HIP(hipMalloc(sc, (size_t)rows * sizeof(float)));
+    return ATS_KD(m->cfg.dtype, ats_quant_rows_fp8(w, rows, cols, cols, *q, (float*)*sc, st, m->pk));
   });
 }
 
 extern "C" int atspeed_llama_enable_fp4(atspeed_llama* m, void* stream) {
-  ATS_REQUIRE(m, ATSPEED_ERR_INVALID, "enable_fp4: null model");
-  // the MXFP4 copies are made from the model's own 16-bit values by the quantiser of its flavour (gemm.hip quant_mxfp4_kernel)
-  ATS_REQUIRE(m->cfg.dtype == ATSPEED_BF16 || m->cfg.dtype == ATSPEED_F16, ATSPEED_ERR_INVALID, "enable_fp4: the model must hold bf16 or fp16 weights");
-  ATS_REQUIRE(m->cfg.hidden % 256 == 0 && m->cfg.ffn % 256 == 0, ATSPEED_ERR_INVALID, "enable_fp4: hidden and ffn must be multiples of 256");
-  ATS_REQUIRE(m->fp8.empty(), ATSPEED_ERR_INVALID, "enable_fp4: the model already runs the 8-bit target (atspeed_llama_enable_fp8)");
-  if (!m->fp4.empty()) return ATSPEED_OK;
   hipStream_t st = (hipStream_t)stream;
-  return quant_layers_build(m, &m->fp4, st, [&](const void* w, int rows, int cols, void** q, void** sc) -> int {     // 16-bit rows (packed or row-major) -> nibbles + scale bytes
+  return quant_layers_build(m, "enable_fp4", SCHEME_W4A8, st, [&](const void* w, int rows, int cols, void** q, void** sc) -> int {     // 16-bit rows (packed or row-major) -> nibbles + scale bytes (gemm.hip quant_mxfp4_kernel)
     if (hipMalloc(q, (size_t)rows * cols / 2) != hipSuccess || hipMalloc(sc, (size_t)rows * cols / 32) != hipSuccess) {
       atspeed_set_error("enable_fp4: out of device memory for the MXFP4 copies");
       (void)hipGetLastError();
@@ -873,10 +871,10 @@ extern "C" int64_t atspeed_llama_lora_launches(atspeed_llama* m, int32_t reset) 
 // (gathered from act->att / act->h into act->att_tail / act->gath); qkv, RoPE, the KV scatter and the attention run over all T rows as in
 // every layer, so the caches are bit for bit what the full forward leaves.  Only the last layer: row r's K/V in layer l needs row r's whole
 // output of layer l - 1.  The rule: a 16-bit or fp32 target without adapter and without W8A8 / W4A8 copies (their kernels are chosen by the
-// forward's token count and their layer bodies carry xq_ready state: left on the full path, as staged verification leaves them), at most half
+// forward's token count and that case has not been measured: left on the full path, as staged verification leaves them), at most half
 // of the rows get logits, and the forward holds more than "tail_rows_tokens" tokens (below, a projection is bound by its weight stream).
 static bool forward_prunes_tail(const atspeed_llama* m, const SegTable& t) {
-  return m->fp8.empty() && m->fp4.empty() && !m->has_lora() && 2 * t.total_logit <= t.total_tok && t.total_tok > ats_switch(ATS_SW_TAIL_ROWS_TOKENS);
+  return m->plain16() && 2 * t.total_logit <= t.total_tok && t.total_tok > ats_switch(ATS_SW_TAIL_ROWS_TOKENS);
 }
 static int llama_forward_body(atspeed_llama* m, const SegTable& t, const SegTable* dtab, float* logits_out, hipStream_t st,
                               const unsigned char* tile_store, int logit_row_off);
@@ -912,8 +910,7 @@ static int llama_forward_segs(atspeed_llama* m, const SegTable& t, float* logits
   const int use_graphs = ats_switch(ATS_SW_GRAPHS);                // (atspeed_set_switch("graphs", 1): the tests compare both modes in one process)
   constexpr int graph_max_tok = 512;
   if (use_graphs && !m->prof_on && logits_out == nullptr && logit_row_off == 0 && T <= graph_max_tok) {
-    const ActCtx::GraphKey key(T, t.total_logit, t.n, t.n_qtiles, t.qtile_rows, !m->fp4.empty() ? 2 : m->fp8.empty() ? 0 : 1,
-                               forward_prunes_tail(m, t) ? 1 : 0);
+    const ActCtx::GraphKey key(T, t.total_logit, t.n, t.n_qtiles, t.qtile_rows, m->scheme, forward_prunes_tail(m, t) ? 1 : 0);
     auto it = cx->graphs.find(key);
     if (it == cx->graphs.end() && cx->graphs.size() < 64 && ++cx->graph_seen[key] >= 2) {   // a shape seen twice recurs (K + dl*DK tokens)
       g_ats_lazy_allocs++;                             // the capture stream (first time) and this shape's graph
@@ -1515,13 +1512,13 @@ struct atspeed_prefix {
   int len = 0, slot = 0;                       // tokens; the resident adapter slot the rows were made under (0 = none)
   void *k = nullptr, *v = nullptr;             // [layers][len][hidden] in the model's type
   int32_t* ids = nullptr;                      // [len]
-  bool fp8 = false, fp4 = false; long lora_gen = 0, slot_gen = 0;     // the arithmetic that produced the rows (prefix_stale)
+  int scheme = SCHEME_16; long lora_gen = 0, slot_gen = 0;     // the arithmetic that produced the rows (prefix_stale)
   mutable int64_t users_served = 0;
   size_t bytes = 0;
 };
 static bool prefix_stale(const atspeed_prefix* p) {
   const atspeed_llama* m = p->m;
-  return p->fp8 != !m->fp8.empty() || p->fp4 != !m->fp4.empty() || p->lora_gen != m->lora_gen || (p->slot && p->slot_gen != m->slot_gen[p->slot]);
+  return p->scheme != m->scheme || p->lora_gen != m->lora_gen || (p->slot && p->slot_gen != m->slot_gen[p->slot]);
 }
 
 extern "C" void atspeed_prefix_destroy(atspeed_prefix* p) {
@@ -1543,7 +1540,7 @@ extern "C" int atspeed_prefix_create(atspeed_llama* m, const int32_t* ids, int32
   hipStream_t st = (hipStream_t)stream;
   Building<atspeed_prefix> p(new atspeed_prefix(), atspeed_prefix_destroy);
   p->m = m; p->len = len; p->slot = adapter_slot;
-  p->fp8 = !m->fp8.empty(); p->fp4 = !m->fp4.empty(); p->lora_gen = m->lora_gen; p->slot_gen = m->slot_gen[adapter_slot];
+  p->scheme = m->scheme; p->lora_gen = m->lora_gen; p->slot_gen = m->slot_gen[adapter_slot];
   const size_t store = (size_t)m->cfg.n_layers * len * m->cfg.hidden * m->esz;
   ATS_HIP(hipMalloc(&p->k, store));
   ATS_HIP(hipMalloc(&p->v, store));
@@ -1836,7 +1833,7 @@ static bool bssd_round_staged(const std::vector<atspeed_decoder*>& ver, const st
   const int mode = ats_switch(ATS_SW_VERIFY_STAGED);
   if (mode <= 0 || ver.empty()) return false;
   const atspeed_llama* T = ver[0]->target;
-  if (!T->fp8.empty() || !T->fp4.empty() || T->has_lora()) return false;
+  if (!T->plain16()) return false;
   long long tok = 0;
   for (const atspeed_decoder* d : ver) { if (d->sample) return false; tok += d->run.n0 + d->run.dl * d->run.dk; }
   for (const atspeed_decoder* d : fin) { if (d->sample) return false; tok += d->run.n0; }

@@ -216,6 +216,39 @@ def test_fp4_forward_logits_match_the_w4a8_oracle(width, dtype):
             _judge(outs[i].float().cpu(), ref4, ref32, host[i], 6, f"batched 300 tokens, user {i}")
 
 
+def test_fp4_forward_past_the_fused_norm_width_matches_the_w4a8_oracle():
+    """hidden 8448 = 33 x 256 > 8192, where no fused norm + e4m3 quantisation exists: the first norm and both residual projections leave 16-bit
+    rows and qkv / gate_up quantise them themselves.  Two layers ("down feeds the next layer's norm" and the last layer's down), ffn 512.  One
+    40-token sequence alone and beside two fillers in a 300-token forward: all four projections W4A8 in both layers, its logit rows against
+    the W4A8 oracle with this file's bar."""
+    from tests.mxfp4_ref import RefLlamaW4A8
+    dims = synth.LlamaDims(synth.TINY.vocab_size, 8448, 2, 66, 512)
+    m = _model(dims, 43, torch.bfloat16)
+    sd = m.export_state_dict()
+    ref4, ref32 = RefLlamaW4A8(dims, sd, max_slots=512), RefLlama(dims, sd, max_slots=512)
+    m.enable_fp4()
+    g = torch.Generator().manual_seed(10)
+    seqs, host = [], []
+    for T in (40, 130, 130):
+        ids, pos, vis = _seq(g, dims.vocab_size, T)
+        seqs.append((ids, pos, pos.clone(), vis_bits_from_bool(vis, 512), T, 6))
+        host.append((ids, pos, pos, vis))
+    want4 = ref4.forward(*host[0], n_logit_rows=6)
+    want32 = ref32.forward(*host[0], n_logit_rows=6)
+    scale, qn = float(want4.abs().max()), (want4 - want32).abs()
+    for label, batch in (("40 tokens", seqs[:1]), ("300 tokens", seqs)):
+        m.fp4_counters(reset=True)
+        got = m.forward_raw_batch(batch)[0].float().cpu()
+        torch.cuda.synchronize()
+        cnt = m.fp4_counters()
+        assert all(c["fp4"] == dims.n_layers and c["other"] == 0 for c in cnt.values()), (label, cnt)
+        e4, e32 = (got - want4).abs(), (got - want32).abs()
+        print(f"hidden 8448, {label}: W4A8 engine vs W4A8 oracle max {float(e4.max()) / scale:.4f} mean {float(e4.mean()) / scale:.4f}; vs fp32 oracle "
+              f"mean {float(e32.mean()) / scale:.4f}; scheme noise mean {float(qn.mean()) / scale:.4f} max {float(qn.max()) / scale:.4f}")
+        assert float(e4.mean()) < FP8_VS_NOISE * float(qn.mean()) and float(e4.max()) < float(qn.max()), label
+        assert float(e4.mean()) < float(e32.mean()), label
+
+
 def test_fp4_one_user_bssd_peaked_matches_the_w4a8_oracle():
     """the fp8 tests' `peaked` recipe (residual branches scaled by 3e-4, head rows 3 x wider) at the Llama-7B width, one user"""
     from tests.mxfp4_ref import RefLlamaW4A8

@@ -42,8 +42,14 @@ PROJ_SHAPES = ((3 * H, H), (H, H), (2 * F, H), (H, F))
 H7, F7, HEADS7 = 4096, 11008, 32
 
 
+# past hidden 8192 there is no fused norm + e4m3 quantisation: every quantised consumer of a norm gets 16-bit rows and quantises them itself.
+# 8448 = 33 x 256 is the first such width enable_fp8 takes; two layers reach both "down feeds the next layer's norm" and the last layer's down;
+# ffn 512 is the smallest with which all four projections are W8A8 shapes at one-user sizes (the weight-streaming form wants K >= 512)
+WIDE = synth.LlamaDims(synth.TINY.vocab_size, 8448, 2, 66, 512)
+
+
 def _target(dtype=torch.bfloat16, V=synth.BEAUTY.vocab_size, width="small", layers=LAYERS, **kw):
-    dims = synth.LlamaDims(V, H, layers, HEADS, F) if width == "small" else synth.LlamaDims(V, H7, layers, HEADS7, F7)
+    dims = {"small": synth.LlamaDims(V, H, layers, HEADS, F), "llama7b": synth.LlamaDims(V, H7, layers, HEADS7, F7), "wide": WIDE}[width]
     return dims, HipLlama.from_synthetic(dims, 31, std=0.03 if width == "small" else 0.02, head_std=0.2 if width == "small" else 0.05, dtype=dtype,
                                          max_slots=512, max_tokens=512, max_logit_rows=448, **kw)
 
@@ -92,6 +98,40 @@ def test_fp8_forward_logits_match_the_w8a8_oracle(width, layers, dtype):
     for e8_max, e8_mean, e32_mean, qn_mean, qn_max in worst:
         assert e8_mean < FP8_VS_NOISE * qn_mean and e8_max < qn_max
         assert e8_mean < e32_mean, "the W8A8 oracle must explain the fp8 engine better than the unquantised one"
+
+
+def test_fp8_forward_past_the_fused_norm_width_matches_the_w8a8_oracle():
+    """hidden 8448 > 8192: the first norm and both residual projections leave 16-bit rows and qkv / gate_up quantise them themselves (every
+    other model of the suite takes its e4m3 rows from the fused norm).  One 40-token sequence alone (the one-user kernels) and beside two
+    fillers in a 300-token forward (257-511 tokens: the ring kernel for every K % 256 == 0): all four projections W8A8 in both layers, its
+    logit rows against the W8A8 oracle with this file's bar."""
+    dims, m = _target(width="wide")
+    sd = m.export_state_dict()
+    ref8, ref32 = RefLlama(dims, sd, max_slots=512, w8a8=True), RefLlama(dims, sd, max_slots=512)
+    m.enable_fp8()
+    g = torch.Generator().manual_seed(8)
+    seqs, host = [], []
+    for T in (40, 130, 130):
+        ids = torch.randint(3, dims.vocab_size, (T,), generator=g).to(torch.int32)
+        vis = torch.tril(torch.ones(T, T, dtype=torch.bool))
+        vis[20:, 7] = False                                       # a hidden slot: tree mask, not plain causal
+        pos = torch.arange(T, dtype=torch.int32)
+        seqs.append((ids, pos, pos.clone(), vis_bits_from_bool(vis, 512), T, 6))
+        host.append((ids, pos, pos, vis))
+    want8 = ref8.forward(*host[0], n_logit_rows=6)
+    want32 = ref32.forward(*host[0], n_logit_rows=6)
+    scale, qn = float(want8.abs().max()), (want8 - want32).abs()
+    for label, batch in (("40 tokens", seqs[:1]), ("300 tokens", seqs)):
+        m.fp8_counters(reset=True)
+        got = m.forward_raw_batch(batch)[0].float().cpu()
+        torch.cuda.synchronize()
+        cnt = m.fp8_counters()
+        assert all(c["fp8"] == dims.n_layers and c["other"] == 0 for c in cnt.values()), (label, cnt)
+        e8, e32 = (got - want8).abs(), (got - want32).abs()
+        print(f"hidden 8448, {label}: fp8 engine vs W8A8 oracle max {float(e8.max()) / scale:.4f} mean {float(e8.mean()) / scale:.4f}; vs fp32 oracle "
+              f"mean {float(e32.mean()) / scale:.4f}; scheme noise mean {float(qn.mean()) / scale:.4f} max {float(qn.max()) / scale:.4f}")
+        assert float(e8.mean()) < FP8_VS_NOISE * float(qn.mean()) and float(e8.max()) < float(qn.max()), label
+        assert float(e8.mean()) < float(e32.mean()), label
 
 
 def test_fp8_bssd_runs_every_projection_in_fp8_in_every_round_and_matches_the_w8a8_oracle():
