@@ -108,10 +108,10 @@ def test_embed_gather_row_info(lib, seg_name, dtype, hidden):
 
 
 # ------------------------------------------------------------------ b. RoPE + KV scatter
-def _caches(sg, H, td, values=None):
-    """per segment [LAYERS][MAX_SLOTS][H]: poison, or the given fp64 values"""
+def _caches(sg, H, td, values=None, max_slots=SC.MAX_SLOTS):
+    """per segment [LAYERS][max_slots][H]: poison, or the given values (numpy arrays that hold values of the format)"""
     if values is None:
-        return [_poisoned((SC.LAYERS, SC.MAX_SLOTS, H), td) for _ in range(sg["n"])]
+        return [_poisoned((SC.LAYERS, max_slots, H), td) for _ in range(sg["n"])]
     return [torch.from_numpy(v).to(td).cuda() for v in values]
 
 
@@ -206,59 +206,72 @@ ATTN_C = {"rows32": 2.86, "rows16": 2.26, "staged16": 2.39, "scalar16": 1.64, "s
 EPS = {"bf16": 2.0 ** -8, "fp16": 2.0 ** -11, "fp32": 2.0 ** -24}
 
 
-def _form16(n_qtiles, n_heads, qtile):
-    """which 16-rows-per-wave kernel a launch takes (attn.hip, ats_tree_attention_segs): the LDS-DMA ring up to 256 workgroups and 128-row tiles,
-    else the register-staged form.  Bit-identity between the lock-step launch and the per-segment launches is asserted only where both take the same."""
-    return "ring" if qtile <= 128 and n_qtiles * n_heads <= 256 else "staged"
+def _form16(n_qtiles, n_heads, qtile, head_dim=64, vis_words=SC.VIS_WORDS):
+    """which 16-rows-per-wave kernel a launch takes (attn.hip, ats_tree_attention_segs): the LDS-DMA ring up to 256 workgroups and 128-row tiles
+    while its four K / V tiles and the tile's visibility words fit the kernel's dynamic LDS (AttnTile<DH>::lds_ring <= kAttnLdsCap: head_dim 128
+    at 128-row tiles up to 23 words), else the register-staged form.  Bit-identity between the lock-step launch and the per-segment launches is
+    asserted only where both take the same."""
+    tile = 64 * head_dim * 2 + 64 * (head_dim * 2 + 32)             # AttnTile<DH>::TILE: a K tile and a V tile of padded rows
+    ring_lds = 4 * tile + qtile * vis_words * 8
+    return "ring" if qtile <= 128 and n_qtiles * n_heads <= 256 and ring_lds <= 160 * 1024 - 64 else "staged"
 
 
-def _attention(lib, S, q, H, n_heads, head_dim, td, layer, qtile, rpw, packed, rows_extra=3):
+def _attention(lib, S, q, H, n_heads, head_dim, td, layer, qtile, rpw, packed, rows_extra=3, max_slots=SC.MAX_SLOTS, vis_words=SC.VIS_WORDS):
     sg = S.sg
     T = sg["total_tok"]
     Tp = (T + 1) // 2 * 2
     out = _poisoned((Tp + rows_extra, H), td)
-    loff = layer * SC.MAX_SLOTS * H * q.element_size()
-    _lib.check(lib.atspeed_segs_tree_attention(q.data_ptr(), 3 * H, loff, SC.VIS_WORDS, out.data_ptr(), H, n_heads, head_dim, _lib.dtype_code(td), qtile, rpw,
+    loff = layer * max_slots * H * q.element_size()
+    _lib.check(lib.atspeed_segs_tree_attention(q.data_ptr(), 3 * H, loff, vis_words, out.data_ptr(), H, n_heads, head_dim, _lib.dtype_code(td), qtile, rpw,
                                                packed, *S.args(), _st()))
     torch.cuda.synchronize()
     return out
 
 
-def _check_attention(lib, seg_name, n_heads, head_dim, dtype, layer, qtile, rpw, packed, form):
-    S = Segs(seg_name)
+def _check_attention(lib, seg_name, n_heads, head_dim, dtype, layer, qtile, rpw, packed, form, max_slots=SC.MAX_SLOTS, vis_words=SC.VIS_WORDS, case=None):
+    """case (tests/test_attn_long_gpu.py): a dict in place of the fixture of tests/segs_cases.py -- S (the device side of its table), q, kc, vc
+    (numpy, values of the format), ref, mag, victim, blind (bool per row: the rows that see nothing, which must be exact zeros and stay out of
+    the ratio) and, where the bound on the ratio is not ATTN_C[form], c.  Returns the worst ratio and the output."""
+    S = Segs(seg_name) if case is None else case["S"]
     sg, td, H, T = S.sg, TD[dtype], n_heads * head_dim, S.sg["total_tok"]
-    q64, kc64, vc64 = SC.attn_inputs(seg_name, n_heads, head_dim, dtype)
+    if case is None:
+        q64, kc64, vc64 = SC.attn_inputs(seg_name, n_heads, head_dim, dtype)
+        ref, mag = SC.attn_ref64(seg_name, n_heads, head_dim, dtype, layer)
+        blind, bound, victim = np.zeros(T, dtype=bool), ATTN_C[form], 2 if seg_name == "ragged5" else 11
+    else:
+        q64, kc64, vc64, ref, mag, blind, victim = (case[k] for k in ("q", "kc", "vc", "ref", "mag", "blind", "victim"))
+        bound = case.get("c", ATTN_C[form])
     q = torch.from_numpy(q64).to(td).cuda()
     S.kc, S.vc = _caches(sg, H, td, kc64), _caches(sg, H, td, vc64)
-    ref, mag = SC.attn_ref64(seg_name, n_heads, head_dim, dtype, layer)
-    out = _attention(lib, S, q, H, n_heads, head_dim, td, layer, qtile, rpw, 0)
+    out = _attention(lib, S, q, H, n_heads, head_dim, td, layer, qtile, rpw, 0, max_slots=max_slots, vis_words=vis_words)
     got = out[:T].double().cpu().numpy()
     err = np.abs(got - ref)
-    ratio = float((err / (EPS[dtype] * mag)).max())
+    assert (got[blind] == 0).all(), "a row that sees nothing returns zeros"
+    ratio = float((err[~blind] / (EPS[dtype] * mag[~blind])).max())
     print(f"segs attention {seg_name} heads={n_heads} dh={head_dim} {dtype} layer={layer} qtile={qtile} rows_per_wave={rpw} form={form}: "
           f"max|err|={err.max():.3e} worst |err| / (eps sum p|v|) = {ratio:.3f}")
     # 1. the project's tolerance for this operation on unit-normal inputs; 2. the scale-aware bound
     assert err.max() <= (2e-5 if dtype == "fp32" else 3e-2)
-    assert ratio <= ATTN_C[form], (ratio, ATTN_C[form])
+    assert ratio <= bound, (ratio, bound)
     # 5. rows past total_tok keep their poison
     assert_same("rows past total_tok", out[T:].cpu(), _poisoned((out.shape[0] - T, H), td).cpu())
     # 3. the lock-step launch equals one launch per segment with the same tiling (the same kernel on the same tiles)
     if dtype == "bf16" and qtile:
         esz = 2
-        same_form = rpw == 32 or all(_form16(sum((t + qtile - 1) // qtile for t in sg["n_tok"]), n_heads, qtile) == _form16((t + qtile - 1) // qtile, n_heads, qtile)
-                                     for t in sg["n_tok"])
+        same_form = rpw == 32 or all(_form16(sum((t + qtile - 1) // qtile for t in sg["n_tok"]), n_heads, qtile, head_dim, vis_words) ==
+                                     _form16((t + qtile - 1) // qtile, n_heads, qtile, head_dim, vis_words) for t in sg["n_tok"])
         if same_form:
             one = torch.zeros(T, H, dtype=td, device="cuda")
             for i in range(sg["n"]):
                 r0, t = int(sg["row0"][i]), sg["n_tok"][i]
                 _lib.check(lib.atspeed_tree_attention_tiled(q.data_ptr() + r0 * 3 * H * esz, 3 * H, S.kc[i][layer].data_ptr(), S.vc[i][layer].data_ptr(),
-                                                            S.vis[i].data_ptr(), SC.VIS_WORDS, one.data_ptr() + r0 * H * esz, t, sg["n_slots"][i], n_heads, head_dim,
+                                                            S.vis[i].data_ptr(), vis_words, one.data_ptr() + r0 * H * esz, t, sg["n_slots"][i], n_heads, head_dim,
                                                             _lib.ATSPEED_BF16, qtile, rpw, _st()))
             torch.cuda.synchronize()
             assert_same("lock-step vs one launch per segment", out[:T].cpu(), one.cpu())
     # 4. packed output = atspeed_pack_rows of the row-major output; the pad row of an odd total_tok is not written
     if packed:
-        pk = _attention(lib, S, q, H, n_heads, head_dim, td, layer, qtile, rpw, 1, rows_extra=2)
+        pk = _attention(lib, S, q, H, n_heads, head_dim, td, layer, qtile, rpw, 1, rows_extra=2, max_slots=max_slots, vis_words=vis_words)
         Tp = (T + 1) // 2 * 2
         want = torch.empty(Tp, H, dtype=td, device="cuda")
         _lib.check(lib.atspeed_pack_rows(out[:T].contiguous().data_ptr(), want.data_ptr(), T, H * 2, _st()))
@@ -272,13 +285,13 @@ def _check_attention(lib, seg_name, n_heads, head_dim, dtype, layer, qtile, rpw,
         assert (_bits(pk[Tp:]) == POISON16).all()
     # 5. another segment's cache filled with large finite values changes no bit of the other segments' rows
     big = 3.0e38 if dtype != "fp16" else 60000.0
-    victim = 2 if seg_name == "ragged5" else 11
     S.kc[victim], S.vc[victim] = torch.full_like(S.kc[victim], big), torch.full_like(S.vc[victim], -big)
-    out2 = _attention(lib, S, q, H, n_heads, head_dim, td, layer, qtile, rpw, 0)
+    out2 = _attention(lib, S, q, H, n_heads, head_dim, td, layer, qtile, rpw, 0, max_slots=max_slots, vis_words=vis_words)
     keep = np.ones(T, dtype=bool)
     keep[sg["row0"][victim]: sg["row0"][victim + 1]] = False
     keep = torch.from_numpy(keep).cuda()
     assert_same("rows of the other segments", out2[:T][keep].cpu(), out[:T][keep].cpu())
+    return ratio, out
 
 
 @pytest.mark.parametrize("packed", [0, 1])
