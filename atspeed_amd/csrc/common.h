@@ -404,6 +404,7 @@ template <bool F32, bool RESID> __device__ __forceinline__ void store4_epi(void*
 
 // Sum / maximum over a workgroup of NW waves through its __shared__ red[NW].  The per-wave partials are combined left to right, ((r0 + r1) + r2) + ...:
 // the RMSNorm statistics depend on that order.  block_put + barrier + red_*: for a kernel that reduces two values behind one barrier.
+// None of them opens with a barrier: a caller that reuses red[] while lanes may still read the previous result puts one in front.
 template <int NW> __device__ __forceinline__ void block_put(float wave_value, float (&red)[NW]) { if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wave_value; }
 template <int NW> __device__ __forceinline__ float red_sum(const float (&red)[NW]) {
   float t = red[0];
@@ -428,6 +429,27 @@ template <int NW> __device__ __forceinline__ float block_max(float v, float (&re
   block_put(v, red);
   __syncthreads();
   return red_max(red);
+}
+// the same two for uint32_t (counts, ford keys): exact, so no order to keep
+template <int NW> __device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t (&red)[NW]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint32_t t = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) t += red[w];
+  return t;
+}
+template <int NW> __device__ __forceinline__ uint32_t block_max(uint32_t v, uint32_t (&red)[NW]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)v, o, 64); v = u > v ? u : v; }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint32_t t = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) t = red[w] > t ? red[w] : t;
+  return t;
 }
 
 // V consecutive floats of every split-K slab, summed in slab order.  The loads of four slabs are issued before their adds: with a runtime

@@ -184,8 +184,9 @@ struct VerifyArgs {
   BeamSet blk[ATSPEED_MAX_GAMMA + 1];         // blk[0] round beams, blk[i] draft step i
   int nb, dl, k, dk, gen_len0;
   const float* logits;  int ld;  const float* lse;   // rows: block 0 (nb), then dl blocks of dk
-  // greedy walk only: block i's first row of logits / lse / row_cand (packed: 0, nb, nb + dk, ...; a staged round: where that phase's forward
-  // put them), and how many blocks have rows yet.  A walk that needs block i >= blocks_ready writes n_matches = ATS_WALK_PENDING and nothing else
+  // block i's first row of logits / lse / row_cand / cutoff (packed, sampled walks always: 0, nb, nb + dk, ...; a staged round: where that
+  // phase's forward put them), and -- greedy walk only -- how many blocks have rows yet.  A walk that needs block i >= blocks_ready writes
+  // n_matches = ATS_WALK_PENDING and nothing else
   int blk_row0[ATSPEED_MAX_GAMMA + 1];  int blocks_ready;
   FsmDev fsm;
   TokBuf cur;  int n0;                        // packed target inputs of this round

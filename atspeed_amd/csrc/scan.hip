@@ -3,9 +3,9 @@
 // on-device bookkeeping (visibility bitsets, positions, KV slots, beam suffixes) that the
 // reference does with host round trips (beamSD.py:58-91, :278-380, :383-416).
 //
-// Candidate keys are 64-bit: (monotone(score) << 32) | ~flat_id, so an unsigned max gives
-// "highest score first, lowest flat id on ties" — the tie-break this build defines
-// (torch.topk leaves it unspecified).  Key 0 = no candidate.
+// Each piece the kernels share is written once, where its section comment stands: candidate keys (below), block top-k, the candidate
+// enumeration of an expand (cand_rows / cand_at) with the blocked-edge test and the tempered score, the argument-block loader of the
+// multi kernels, the step rows and the output tail of the two verify walks.  Block sums and maxima are common.h's (block_sum / block_max).
 #include "internal.h"
 #include <cstdlib>
 #include <memory>
@@ -18,7 +18,22 @@ constexpr int kCPT = 16;                               // candidate slots per th
 constexpr int kMaxCand = kScanThreads * kCPT;          // 16384 >= 64 beams * 256 children
 constexpr int MAXB = ATSPEED_MAX_BEAMS;
 constexpr int LMAX = ATSPEED_MAX_NEW_TOKENS;
-constexpr uint32_t kOrdNegInf = 0x007fffffu;           // ford(-inf)
+
+// Candidate keys are 64-bit: (monotone(score) << 32) | ~flat_id, so an unsigned max gives "highest score first, lowest flat id on ties" --
+// the tie-break this build defines (torch.topk leaves it unspecified).  Key 0 = no candidate.  A -0.0 score takes +0.0's key (ford_key),
+// so the two zeros tie by flat id.  A score of -inf is no candidate and a NaN is one: the callers that can meet either say so themselves.
+__device__ __forceinline__ unsigned long long cand_key(float score, uint32_t flat) {
+  return ((unsigned long long)ford_key(score) << 32) | (unsigned long long)(~flat);
+}
+__device__ __forceinline__ int flat_of_key(unsigned long long key) { return key ? (int)(~(uint32_t)(key & 0xffffffffull)) : -1; }
+
+// one multi-kernel workgroup's argument block, from the device array into its __shared__ copy
+template <typename A>
+__device__ __forceinline__ void load_args(A& a, const A* __restrict__ src) {
+  static_assert(sizeof(A) % 4 == 0, "argument blocks are copied word by word");
+  for (int i = threadIdx.x; i < (int)(sizeof(A) / 4); i += blockDim.x) reinterpret_cast<uint32_t*>(&a)[i] = reinterpret_cast<const uint32_t*>(src)[i];
+  __syncthreads();
+}
 
 // ---------------------------------------------------------------------------- LSE
 // one workgroup per row, 16-byte non-temporal streaming reads (the row is read once and never again), online (max, sum) per lane.
@@ -173,6 +188,15 @@ __device__ __forceinline__ int find_edge(const FsmDev& f, int node, int tok) {
 // item filter: is `node` blocked for the user this automaton copy belongs to?  Callers test f.blocked first (uniform: NULL = no filter)
 __device__ __forceinline__ bool node_blocked(const uint32_t* __restrict__ blocked, int node) { return (blocked[node >> 5] >> (node & 31)) & 1u; }
 
+// item filter: an edge into a blocked node is no candidate
+__device__ __forceinline__ bool edge_blocked(const FsmDev& f, int e) { return f.blocked && node_blocked(f.blocked, f.nxt[e]); }
+
+// sampling: the log-softmax of a token at the user's temperature.  The cutoff kernel, the expand and the picks must form it bit for bit alike.
+__device__ __forceinline__ float tempered(float logit, float lse, float temperature) { return (logit - lse) / temperature; }
+
+// ---------------------------------------------------------------------------- candidate enumeration
+// The candidates of an expand are the children of every live row's automaton node, rows in order, children ascending: candidate c is
+// child c - off[r] of the last row r with off[r] <= c, and slot i of thread t holds candidate c = t + i * kScanThreads.
 struct ExpandShared {
   TopkShared topk;
   int off[MAXB + 1];
@@ -189,17 +213,19 @@ struct ExpandShared {
   float red_out;
 };
 
-// Expand n_rows parent rows (sh.node/brow/lrow/bscore filled by the caller, first n_rows entries)
-// through the FSM and leave the k best candidates in sh.topk.sel.  beamSD.py:58-78.
-__device__ void expand_and_select(ExpandShared& sh, int n_rows, const float* __restrict__ logits, int ld,
-                                  const float* __restrict__ lse, const FsmDev& fsm, int k,
-                                  const int32_t* __restrict__ row_cand = nullptr, int n_row_cand = 0) {
+// Row set-up of an expand over the n_rows parent rows the caller put into sh.node/brow/lrow/bscore: fills sh.lse/rp/deg (SAMPLED: and sh.cut,
+// with no cutoff array -inf), then sh.off by a serial prefix over the live rows, and returns the number of candidates.  Greedy expands
+// alone know free mode (no mask, prefix_allowed_tokens_fn = None): a row's candidates are then the n_row_cand entries of its row_cand list.
+template <bool SAMPLED>
+__device__ __forceinline__ int cand_rows(ExpandShared& sh, int n_rows, const float* __restrict__ lse, const FsmDev& fsm,
+                                         const float* __restrict__ cutoff, int n_row_cand) {
   const int tid = threadIdx.x;
-  const bool free_mode = fsm.n_nodes == 0;            // no mask (prefix_allowed_tokens_fn = None): a row's candidates = its row_cand list
+  const bool free_mode = !SAMPLED && fsm.n_nodes == 0;
   if (tid < n_rows) {
     // every row fetches its own edge range (one thread walking 40 rows paid 40 dependent global round trips: 35 of the 87 us a step of ONE
-    // user took); the range's start stays in LDS for the candidates below
+    // user took); the range's start stays in LDS for cand_at
     sh.lse[tid] = lse[sh.lrow[tid]];
+    if constexpr (SAMPLED) sh.cut[tid] = cutoff ? cutoff[sh.lrow[tid]] : -INFINITY;
     const int nd = sh.node[tid];
     const int e0 = free_mode ? 0 : fsm.row_ptr[nd];
     sh.rp[tid] = e0;
@@ -219,26 +245,42 @@ __device__ void expand_and_select(ExpandShared& sh, int n_rows, const float* __r
     if (tot > kMaxCand) sh.status = ATSPEED_ERR_CAPACITY;
   }
   __syncthreads();
-  const int total = min(sh.off[n_rows], kMaxCand);
+  return min(sh.off[n_rows], kMaxCand);
+}
+
+// candidate c of the expand cand_rows set up: its row, its child index in the row, its edge (free mode has no edges: e is not to be used)
+struct Cand { int r, j, e; };
+__device__ __forceinline__ Cand cand_at(const ExpandShared& sh, int n_rows, int c) {
+  int lo = 0, hi = n_rows;                            // last r with off[r] <= c
+  while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (sh.off[mid] <= c) lo = mid; else hi = mid; }
+  const int j = c - sh.off[lo];
+  return Cand{lo, j, sh.rp[lo] + j};
+}
+
+// Greedy expand: leave the k best candidates in sh.topk.sel, scored log-softmax + beam score; a blocked edge or a negative token (a padded
+// row_cand entry) is dropped before it is scored.  beamSD.py:58-78.
+__device__ void expand_and_select(ExpandShared& sh, int n_rows, const float* __restrict__ logits, int ld,
+                                  const float* __restrict__ lse, const FsmDev& fsm, int k,
+                                  const int32_t* __restrict__ row_cand = nullptr, int n_row_cand = 0) {
+  const int tid = threadIdx.x;
+  const bool free_mode = fsm.n_nodes == 0;
+  const int total = cand_rows<false>(sh, n_rows, lse, fsm, nullptr, n_row_cand);
   unsigned long long keys[kCPT];
 #pragma unroll
   for (int i = 0; i < kCPT; ++i) {
     int c = tid + i * kScanThreads;
     unsigned long long key = 0;
     if (c < total) {
-      int lo = 0, hi = n_rows;                        // last r with off[r] <= c
-      while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (sh.off[mid] <= c) lo = mid; else hi = mid; }
-      int r = lo;
-      const int e = sh.rp[r] + (c - sh.off[r]);
-      int tok = free_mode ? row_cand[(size_t)sh.lrow[r] * MAXB + (c - sh.off[r])] : fsm.tok[e];
-      if (fsm.blocked && node_blocked(fsm.blocked, fsm.nxt[e])) tok = -1;       // item filter: an edge into a blocked node is no candidate
+      const Cand cd = cand_at(sh, n_rows, c);
+      const int r = cd.r;
+      int tok = free_mode ? row_cand[(size_t)sh.lrow[r] * MAXB + cd.j] : fsm.tok[cd.e];
+      if (edge_blocked(fsm, cd.e)) tok = -1;
       if (tok >= 0) {
         float sc = (logits[(size_t)sh.lrow[r] * ld + tok] - sh.lse[r]) + sh.bscore[r];
         // -0.0 reaches here only as (-0.0 - +0.0) + -0.0 (x - y of unequal values is never zero and x - x is +0.0), e.g. a processor-rewritten
         // row with lse = 0: it ties with +0.0 by flat id, and comes out as +0.0
-        uint32_t o = ford_key(sc);
         uint32_t flat = (uint32_t)sh.brow[r] * (uint32_t)fsm.vocab + (uint32_t)tok;
-        if (o > kOrdNegInf || sc != sc) key = ((unsigned long long)o << 32) | (unsigned long long)(~flat);
+        if (sc > -INFINITY || sc != sc) key = cand_key(sc, flat);
       }
     }
     keys[i] = key;
@@ -264,8 +306,7 @@ __global__ __launch_bounds__(kScanThreads) void row_topk_kernel(const float* __r
       unsigned long long key = 0;
       if (col < vocab) {
         const float v = row[col];
-        const uint32_t o = ford_key(v);                // equal values, the two zeros included, rank by column
-        if (o > kOrdNegInf || v != v) key = ((unsigned long long)o << 32) | (unsigned long long)(~(uint32_t)col);
+        if (v > -INFINITY || v != v) key = cand_key(v, (uint32_t)col);   // equal values, the two zeros included, rank by column
       }
       keys[i] = key;
     }
@@ -274,16 +315,17 @@ __global__ __launch_bounds__(kScanThreads) void row_topk_kernel(const float* __r
     if (tid < kk) best[tid] = sh.sel[tid];
     __syncthreads();
   }
-  if (tid < MAXB) out[(size_t)blockIdx.x * MAXB + tid] = (tid < kk && best[tid]) ? (int32_t)(~(uint32_t)(best[tid] & 0xffffffffull)) : -1;
+  if (tid < MAXB) out[(size_t)blockIdx.x * MAXB + tid] = tid < kk ? flat_of_key(best[tid]) : -1;
 }
 
 struct Pick { float score; int parent; int tok; int node; int flat; };
+__device__ __forceinline__ Pick no_pick() { return Pick{-INFINITY, 0, 0, 0, -1}; }
 
 __device__ __forceinline__ Pick decode_pick(unsigned long long key, const FsmDev& fsm, const int* rows_brow,
                                             const int* rows_node, int n_rows) {
+  if (key == 0) return no_pick();
   Pick p;
-  if (key == 0) { p.score = -INFINITY; p.parent = 0; p.tok = 0; p.node = 0; p.flat = -1; return p; }
-  uint32_t flat = ~(uint32_t)(key & 0xffffffffull);
+  const uint32_t flat = (uint32_t)flat_of_key(key);
   p.flat = (int)flat;
   p.parent = (int)(flat / (uint32_t)fsm.vocab);
   p.tok = (int)(flat % (uint32_t)fsm.vocab);
@@ -297,55 +339,35 @@ __device__ __forceinline__ Pick decode_pick(unsigned long long key, const FsmDev
 }
 
 // ---------------------------------------------------------------------------- sampling helpers (do_sample)
-// Candidates of an expand kept in registers: slot i of thread t is candidate c = t + i * kScanThreads in expand order
-// (rows in order, children of a row's automaton node ascending).  sc = log-softmax / temperature + beam score.
+// Candidates of an expand kept in registers, slot i of thread t = candidate t + i * kScanThreads.  sc = log-softmax / temperature + beam score.
 struct CandRegs { int flat[kCPT]; float sc[kCPT]; };
 
-__device__ void expand_candidates(ExpandShared& sh, int n_rows, const float* __restrict__ logits, int ld,
+// Sampled expand: every candidate keeps its flat id; one below its row's cutoff or behind a blocked edge is absent by a score of -inf
+// (probability 0 in every distribution formed from the table).  Returns the number of candidates.
+__device__ int expand_candidates(ExpandShared& sh, int n_rows, const float* __restrict__ logits, int ld,
                                   const float* __restrict__ lse, const FsmDev& fsm, float temperature, const float* __restrict__ cutoff,
                                   CandRegs& cr) {
   const int tid = threadIdx.x;
-  if (tid < n_rows) {                                 // as in expand_and_select: every row fetches its own edge range
-    sh.lse[tid] = lse[sh.lrow[tid]];
-    sh.cut[tid] = cutoff ? cutoff[sh.lrow[tid]] : -INFINITY;
-    const int nd = sh.node[tid], e0 = fsm.row_ptr[nd];
-    sh.rp[tid] = e0;
-    sh.deg[tid] = fsm.row_ptr[nd + 1] - e0;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int tot = 0;
-    for (int r = 0; r < n_rows; ++r) {
-      sh.off[r] = tot;
-      const int deg = sh.deg[r];
-      bool live = sh.bscore[r] > -INFINITY;
-      if (live && deg == 0) sh.status = ATSPEED_ERR_CONSTRAINT;
-      tot += live ? deg : 0;
-    }
-    sh.off[n_rows] = tot;
-    if (tot > kMaxCand) sh.status = ATSPEED_ERR_CAPACITY;
-  }
-  __syncthreads();
-  const int total = min(sh.off[n_rows], kMaxCand);
+  const int total = cand_rows<true>(sh, n_rows, lse, fsm, cutoff, 0);
 #pragma unroll
   for (int i = 0; i < kCPT; ++i) {
     int c = tid + i * kScanThreads;
     cr.flat[i] = -1; cr.sc[i] = -INFINITY;
     if (c < total) {
-      int lo = 0, hi = n_rows;
-      while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (sh.off[mid] <= c) lo = mid; else hi = mid; }
-      int r = lo;
-      const int e = sh.rp[r] + (c - sh.off[r]);
-      int tok = fsm.tok[e];
-      const float s = (logits[(size_t)sh.lrow[r] * ld + tok] - sh.lse[r]) / temperature;
-      cr.sc[i] = s < sh.cut[r] ? -INFINITY : s + sh.bscore[r];         // below the row's cutoff: absent
-      if (fsm.blocked && node_blocked(fsm.blocked, fsm.nxt[e])) cr.sc[i] = -INFINITY;       // item filter: absent in the same way
+      const Cand cd = cand_at(sh, n_rows, c);
+      const int r = cd.r;
+      int tok = fsm.tok[cd.e];
+      const float s = tempered(logits[(size_t)sh.lrow[r] * ld + tok], sh.lse[r], temperature);
+      cr.sc[i] = s < sh.cut[r] ? -INFINITY : s + sh.bscore[r];
+      if (edge_blocked(fsm, cd.e)) cr.sc[i] = -INFINITY;
       cr.flat[i] = sh.brow[r] * fsm.vocab + tok;
     }
   }
+  return total;
 }
 
-// log sum exp over every thread's kCPT values (block-wide); -inf entries contribute nothing
+// log sum exp over every thread's kCPT values (block-wide); -inf entries contribute nothing.  The leading barrier: red_m / red_s / red_out
+// may still be read from the previous reduction.
 __device__ float block_lse(ExpandShared& sh, const float (&v)[kCPT]) {
   float m = -INFINITY;
 #pragma unroll
@@ -360,25 +382,15 @@ __device__ float block_lse(ExpandShared& sh, const float (&v)[kCPT]) {
   s = wave_sum_f32(s);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   __syncthreads();
+  // block_put (common.h) twice, written out: profiles/scan_refactor_isa_and_speed.txt, item 6
   if (lane == 0) { sh.red_m[wave] = wm; sh.red_s[wave] = s; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float gm = -INFINITY;
-    for (int w = 0; w < kScanWaves; ++w) gm = fmaxf(gm, sh.red_m[w]);
+    const float gm = red_max(sh.red_m);                 // never NaN: fmaxf keeps the lanes' maxima free of them
     float gs = 0.f;
     for (int w = 0; w < kScanWaves; ++w) gs += (sh.red_m[w] > -INFINITY) ? sh.red_s[w] * expf(sh.red_m[w] - gm) : 0.f;
     sh.red_out = gm > -INFINITY ? gm + logf(gs) : -INFINITY;
   }
-  __syncthreads();
-  return sh.red_out;
-}
-__device__ float block_sum(ExpandShared& sh, float v) {
-  v = wave_sum_f32(v);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) sh.red_s[wave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) { float t = 0.f; for (int w = 0; w < kScanWaves; ++w) t += sh.red_s[w]; sh.red_out = t; }
   __syncthreads();
   return sh.red_out;
 }
@@ -393,7 +405,7 @@ __device__ void sample_topn(ExpandShared& sh, const CandRegs& cr, const float (&
     if (cr.flat[i] >= 0 && logw[i] > -INFINITY) {
       float kf = logw[i] + ats_gumbel(ats_hash_u32((uint32_t)cr.flat[i], sub));
       // the CPU restatement compares the noisy keys as values: a -0.0 ties with a +0.0
-      key = ((unsigned long long)ford_key(kf) << 32) | (unsigned long long)(~(uint32_t)cr.flat[i]);
+      key = cand_key(kf, (uint32_t)cr.flat[i]);
     }
     keys[i] = key;
   }
@@ -403,26 +415,26 @@ __device__ void sample_topn(ExpandShared& sh, const CandRegs& cr, const float (&
 // a pick by flat id with the TRUE tempered score (sampling keys carry noise); rows describe the expand that produced it
 __device__ Pick pick_of_flat(int flat, const FsmDev& fsm, const ExpandShared& sh, int n_rows, const float* __restrict__ logits,
                              int ld, float temperature) {
+  if (flat < 0) return no_pick();                     // -1 is the only negative flat id there is
   Pick p;
   p.flat = flat;
-  if (flat < 0) { p.score = -INFINITY; p.parent = 0; p.tok = 0; p.node = 0; return p; }
   p.parent = flat / fsm.vocab;
   p.tok = flat % fsm.vocab;
   int r = -1;
   for (int q = 0; q < n_rows; ++q) if (sh.brow[q] == p.parent) { r = q; break; }
   if (r < 0) { p.score = -INFINITY; p.node = 0; return p; }
-  const float s = (logits[(size_t)sh.lrow[r] * ld + p.tok] - sh.lse[r]) / temperature;
+  const float s = tempered(logits[(size_t)sh.lrow[r] * ld + p.tok], sh.lse[r], temperature);
   p.score = s + sh.bscore[r];
   int e = find_edge(fsm, sh.node[r], p.tok);
   p.node = e >= 0 ? fsm.nxt[e] : 0;
   if (e < 0 || s < sh.cut[r]) p.score = -INFINITY;
-  if (fsm.blocked && e >= 0 && node_blocked(fsm.blocked, p.node)) p.score = -INFINITY;      // item filter
+  if (e >= 0 && edge_blocked(fsm, e)) p.score = -INFINITY;
   return p;
 }
 
 // write a block of k new beams + (optionally) the forward inputs that feed them next
 __device__ void emit_block(const Pick& pk, int j, int k, const BeamSet& src, int gen_len, const BeamSet& dst, bool emit,
-                           const TokBuf& in, int in_row0, const TokBuf& out, int out_row0, int out_slot0, int W) {
+                           const TokBuf& in, int in_row0, const TokBuf& out, int out_row0, int out_slot0) {
   if (j < k) {
     dst.score[j] = pk.score; dst.parent[j] = pk.parent; dst.tok[j] = pk.tok; dst.flat[j] = pk.flat;
     if (dst.node) dst.node[j] = pk.node;
@@ -450,7 +462,7 @@ __device__ void emit_vis(const int* parents /*LDS*/, int k, const TokBuf& in, in
 
 // ---------------------------------------------------------------------------- sampling-mode warpers (top-k, top-p)
 // One cutoff per score row (internal.h WarpCutArgs).  The row's entries are the children of its automaton node, scored
-// s = (logit - lse) / temperature exactly as expand_candidates forms them; -inf and NaN entries are no candidates.
+// s = tempered(logit, lse, temperature), the expand's own function; -inf and NaN entries are no candidates.
 //   top-k: k' = max(top_k, min_keep); with at least k' finite entries the k'-th largest is the threshold (ties with it survive), with
 //          fewer nothing is cut (transformers' `scores < topk(scores, k')[0][..., -1]` on the full row: its k'-th largest is -inf then).
 //   top-p: over what top-k left, p = softmax(s); in DESCENDING score order an entry is kept while the probability mass strictly above it
@@ -466,53 +478,19 @@ __device__ void emit_vis(const int* parents /*LDS*/, int k, const TokBuf& in, in
 struct WarpShared {
   uint32_t key[kScanThreads];     // a descending run of keys (0 = none)
   int hist[256];
-  float redf[kScanWaves];
-  int redi[kScanWaves];
+  float redf[kScanWaves];         // block_sum / block_max (common.h) of floats, and the nucleus ladder's wave sums
+  uint32_t redu[kScanWaves];      // ... of counts and keys.  A barrier stands before a reduction whose array an earlier one may still be read from
   int cnt;                        // compaction cursor / first entry the nucleus drops
   int pick, above;                // radix select: the bin that holds the rank, keys above that bin
 };
 struct WarpRow {
-  const float* logits; const int32_t* tok; int deg; float lse, temperature;
-  const int32_t* nxt; const uint32_t* blocked;                    // item filter (NULL = none): child j leads to node nxt[j]
+  const float* logits; const FsmDev& fsm; int e0, deg; float lse, temperature;     // child j of the row's node is edge e0 + j
   __device__ __forceinline__ uint32_t key(int j) const {          // 0 = not a candidate
-    if (blocked && node_blocked(blocked, nxt[j])) return 0u;      // the cutoffs are taken over the unblocked children only
-    const float s = (logits[tok[j]] - lse) / temperature;
+    if (edge_blocked(fsm, e0 + j)) return 0u;                     // the cutoffs are taken over the unblocked children only
+    const float s = tempered(logits[fsm.tok[e0 + j]], lse, temperature);
     return s > -INFINITY ? ford_key(s) : 0u;         // a -0.0 (logit -0.0, lse +0.0) is tied with +0.0, as in expand_candidates' `s < cut`
   }
 };
-
-__device__ float warp_block_sum(WarpShared& sh, float v) {
-  v = wave_sum_f32(v);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) sh.redf[wave] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int w = 0; w < kScanWaves; ++w) t += sh.redf[w];
-  return t;
-}
-__device__ int warp_block_sum_i(WarpShared& sh, int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) sh.redi[wave] = v;
-  __syncthreads();
-  int t = 0;
-  for (int w = 0; w < kScanWaves; ++w) t += sh.redi[w];
-  return t;
-}
-__device__ uint32_t warp_block_max_u32(WarpShared& sh, uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)v, o, 64); v = u > v ? u : v; }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) sh.redi[wave] = (int)v;
-  __syncthreads();
-  uint32_t t = 0;
-  for (int w = 0; w < kScanWaves; ++w) t = (uint32_t)sh.redi[w] > t ? (uint32_t)sh.redi[w] : t;
-  return t;
-}
 
 // sh.key[0 .. n2) descending, n2 a power of two <= kScanThreads (bitonic network, one entry per thread)
 __device__ void warp_sort_desc(WarpShared& sh, int n2) {
@@ -587,16 +565,16 @@ __device__ void row_warp_cutoff_body(const WarpCutArgs& a, int r) {
   while (sg < a.n_seg - 1 && r0 >= a.seg[sg].n) { r0 -= a.seg[sg].n; ++sg; }
   const int node = a.seg[sg].node ? a.seg[sg].node[r0] : 0;
   const int e0 = a.fsm.row_ptr[node];
-  const WarpRow row{a.logits + (size_t)r * a.ld, a.fsm.tok + e0, a.fsm.row_ptr[node + 1] - e0, a.lse[r], a.temperature,
-                    a.fsm.nxt + e0, a.fsm.blocked};
+  const WarpRow row{a.logits + (size_t)r * a.ld, a.fsm, e0, a.fsm.row_ptr[node + 1] - e0, a.lse[r], a.temperature};
   const bool use_p = a.top_p < 1.f;
   const int kk = a.top_k > 0 ? max(a.top_k, a.min_keep) : 0;     // 0 = top-k off
   // finite entries and the largest key
   int nf = 0;
   uint32_t kmax = 0;
   for (int j = tid; j < row.deg; j += kScanThreads) { const uint32_t o = row.key(j); nf += o ? 1 : 0; kmax = o > kmax ? o : kmax; }
-  nf = warp_block_sum_i(sh, nf);
-  kmax = warp_block_max_u32(sh, kmax);
+  nf = (int)block_sum((uint32_t)nf, sh.redu);
+  __syncthreads();
+  kmax = block_max(kmax, sh.redu);
   float cut = -INFINITY;
   const bool cut_k = kk > 0 && kk <= nf;
   if (nf > 0 && (cut_k || use_p)) {
@@ -613,7 +591,7 @@ __device__ void row_warp_cutoff_body(const WarpCutArgs& a, int r) {
         cut = ford_inv(tk);
       }
       if (use_p) {
-        const float Z = warp_block_sum(sh, tid < n_surv ? expf(ford_inv(sh.key[tid]) - m) : 0.f);
+        const float Z = block_sum(tid < n_surv ? expf(ford_inv(sh.key[tid]) - m) : 0.f, sh.redf);
         float mass;
         const int n_keep = warp_nucleus_run(sh, n_surv, m, Z, 0.f, 0, a.top_p, a.min_keep, &mass);
         cut = ford_inv(sh.key[max(n_keep, 1) - 1]);
@@ -625,7 +603,7 @@ __device__ void row_warp_cutoff_body(const WarpCutArgs& a, int r) {
       if (use_p) {
         float z = 0.f;
         for (int j = tid; j < row.deg; j += kScanThreads) { const uint32_t o = row.key(j); z += o >= tk ? expf(ford_inv(o) - m) : 0.f; }
-        const float Z = warp_block_sum(sh, z);
+        const float Z = block_sum(z, sh.redf);
         unsigned long long upper = 1ull << 32;         // survivors not yet walked: keys in [tk, upper)
         float head = 0.f;
         int rank = 0;
@@ -633,7 +611,8 @@ __device__ void row_warp_cutoff_body(const WarpCutArgs& a, int r) {
         for (;;) {
           int rem = 0;
           for (int j = tid; j < row.deg; j += kScanThreads) { const uint32_t o = row.key(j); rem += (o >= tk && o < upper) ? 1 : 0; }
-          rem = warp_block_sum_i(sh, rem);
+          __syncthreads();
+          rem = (int)block_sum((uint32_t)rem, sh.redu);
           if (rem == 0) break;                         // every survivor of top-k is kept
           // the next run: the keys in (lo, upper), fewer than 1024, and then the group of keys equal to lo; a last run takes [tk, upper)
           const bool more = rem > kScanThreads;
@@ -649,7 +628,8 @@ __device__ void row_warp_cutoff_body(const WarpCutArgs& a, int r) {
             n_eq += (more && o == lo) ? 1 : 0;
             if (o < upper && (more ? o > lo : o >= lo)) { const int at = atomicAdd(&sh.cnt, 1); if (at < kScanThreads) sh.key[at] = o; }
           }
-          n_eq = warp_block_sum_i(sh, n_eq);
+          __syncthreads();
+          n_eq = (int)block_sum((uint32_t)n_eq, sh.redu);
           const int n = min(sh.cnt, kScanThreads);
           int n2 = 1;
           while (n2 < n) n2 <<= 1;
@@ -675,29 +655,14 @@ __device__ void row_warp_cutoff_body(const WarpCutArgs& a, int r) {
 
 __global__ __launch_bounds__(kScanThreads) void row_warp_cutoff_kernel(WarpCutArgs a) { row_warp_cutoff_body(a, blockIdx.x); }
 __global__ __launch_bounds__(kScanThreads) void row_warp_cutoff_multi_kernel(const WarpCutArgs* __restrict__ args) {
-  __shared__ WarpCutArgs a;                        // grid column = job: copy its argument block first
-  const int words = sizeof(WarpCutArgs) / 4;
-  for (int i = threadIdx.x; i < words; i += blockDim.x)
-    reinterpret_cast<uint32_t*>(&a)[i] = reinterpret_cast<const uint32_t*>(args + blockIdx.y)[i];
-  __syncthreads();
+  __shared__ WarpCutArgs a;                        // grid column = job
+  load_args(a, args + blockIdx.y);
   int rows = 0;
   for (int s2 = 0; s2 < a.n_seg; ++s2) rows += a.seg[s2].n;
   if ((int)blockIdx.x < rows) row_warp_cutoff_body(a, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------- beam step
-__device__ void beam_step_body(const BeamStepArgs& a);
-
-__global__ __launch_bounds__(kScanThreads) void beam_step_kernel(BeamStepArgs a) { beam_step_body(a); }
-__global__ __launch_bounds__(kScanThreads) void beam_step_multi_kernel(const BeamStepArgs* __restrict__ args) {
-  __shared__ BeamStepArgs a;                       // one workgroup per user: copy its argument block first
-  const int words = sizeof(BeamStepArgs) / 4;
-  for (int i = threadIdx.x; i < words; i += blockDim.x)
-    reinterpret_cast<uint32_t*>(&a)[i] = reinterpret_cast<const uint32_t*>(args + blockIdx.x)[i];
-  __syncthreads();
-  beam_step_body(a);
-}
-
 __device__ void beam_step_body(const BeamStepArgs& a) {
   __shared__ ExpandShared sh;
   __shared__ int parents[MAXB];
@@ -713,10 +678,9 @@ __device__ void beam_step_body(const BeamStepArgs& a) {
   Pick pk;
   if (a.sample) {                                                        // beamSD.py:65-75
     CandRegs cr;
-    expand_candidates(sh, a.n_src, a.logits, a.ld, a.lse, a.fsm, a.temperature, a.cutoff, cr);
+    const int total = expand_candidates(sh, a.n_src, a.logits, a.ld, a.lse, a.fsm, a.temperature, a.cutoff, cr);
     if (a.tab_score) {                                                   // the draft's whole distribution, for verify
       const float L = block_lse(sh, cr.sc);
-      const int total = min(sh.off[a.n_src], kMaxCand);
 #pragma unroll
       for (int i = 0; i < kCPT; ++i) { int c = tid + i * kScanThreads; if (c < total) a.tab_score[c] = cr.sc[i]; }
       if (tid <= a.n_src) a.tab_off[tid] = sh.off[tid];
@@ -724,8 +688,7 @@ __device__ void beam_step_body(const BeamStepArgs& a) {
     }
     sample_topn(sh, cr, cr.sc, a.k, a.rng_sub);
     if (tid < a.k) {
-      unsigned long long key = sh.topk.sel[tid];
-      pk = pick_of_flat(key ? (int)(~(uint32_t)(key & 0xffffffffull)) : -1, a.fsm, sh, a.n_src, a.logits, a.ld, a.temperature);
+      pk = pick_of_flat(flat_of_key(sh.topk.sel[tid]), a.fsm, sh, a.n_src, a.logits, a.ld, a.temperature);
       parents[tid] = pk.parent;
     }
   } else {
@@ -756,13 +719,13 @@ __device__ void beam_step_body(const BeamStepArgs& a) {
       int before = 0, total = 0;
       for (int j = 0; j < a.k; ++j) { total += keep[j]; before += (j < tid) ? keep[j] : 0; }
       slot = ok ? before : total + (tid - before);
-      if (!ok) { pk.score = -INFINITY; pk.parent = 0; pk.tok = 0; pk.node = 0; pk.flat = -1; }
+      if (!ok) pk = no_pick();
     }
     __syncthreads();
     if (tid < a.k) parents[slot] = pk.parent;
     __syncthreads();
   }
-  emit_block(pk, slot, a.k, a.src, a.gen_len, a.dst, a.emit != 0, a.in, a.in_row0, a.out, a.out_row0, a.out_slot0, a.vis_words);
+  emit_block(pk, slot, a.k, a.src, a.gen_len, a.dst, a.emit != 0, a.in, a.in_row0, a.out, a.out_row0, a.out_slot0);
   if (a.emit) emit_vis(parents, a.k, a.in, a.in_row0, a.out, a.out_row0, a.out_slot0, a.vis_words);
   if (a.mail) {
     int valid = __syncthreads_count(tid < a.k && pk.flat >= 0);
@@ -773,17 +736,59 @@ __device__ void beam_step_body(const BeamStepArgs& a) {
   }
 }
 
-// ---------------------------------------------------------------------------- verify
-__device__ void verify_walk_body(const VerifyArgs& a);
+__global__ __launch_bounds__(kScanThreads) void beam_step_kernel(BeamStepArgs a) { beam_step_body(a); }
+__global__ __launch_bounds__(kScanThreads) void beam_step_multi_kernel(const BeamStepArgs* __restrict__ args) {
+  __shared__ BeamStepArgs a;                       // one workgroup per user
+  load_args(a, args + blockIdx.x);
+  beam_step_body(a);
+}
 
-__device__ void verify_sample_body(const VerifyArgs& a);
-__global__ __launch_bounds__(kScanThreads) void verify_walk_multi_kernel(const VerifyArgs* __restrict__ args) {
-  __shared__ VerifyArgs a;
-  const int words = sizeof(VerifyArgs) / 4;
-  for (int i = threadIdx.x; i < words; i += blockDim.x)
-    reinterpret_cast<uint32_t*>(&a)[i] = reinterpret_cast<const uint32_t*>(args + blockIdx.x)[i];
+// ---------------------------------------------------------------------------- verify
+// What the two walks share.  Step i of a walk expands the round beams (i == 0, rows 0 .. nb of the logits) or the k beams that matched the
+// draft's block i: hit[] = a beam's position in that block, sbh[] = its score, and its logits row is blk_row0[i] + hit (a packed walk,
+// sampled ones always: blk_row0 = 0, nb, nb + dk, ...).
+__device__ __forceinline__ void verify_step_rows(ExpandShared& sh, const VerifyArgs& a, int i, int n_rows, const int* hit, const float* sbh) {
+  const int tid = threadIdx.x;
   __syncthreads();
-  if (a.sample) verify_sample_body(a); else verify_walk_body(a);
+  if (tid < n_rows) {                                                    // beamSD.py:279-296
+    int br = i == 0 ? tid : hit[tid];
+    sh.brow[tid] = br;
+    sh.node[tid] = a.blk[i].node[br];
+    sh.lrow[tid] = a.blk_row0[i] + br;
+    sh.bscore[tid] = i == 0 ? a.blk[0].score[tid] : sbh[tid];
+  }
+  __syncthreads();
+}
+
+// Outputs of a walk that accepted nm draft blocks: thread j < k holds pick j of the new round beams (parents, in the row space of block nm,
+// in t_parent).  Writes the beams, the next round's target inputs, the draft's re-ingest inputs and the mailbox (beamSD.py:383-416).
+__device__ __forceinline__ void verify_outputs(const VerifyArgs& a, const ExpandShared& sh, const Pick& pk, const int* t_parent, int nm) {
+  const int tid = threadIdx.x;
+  const int k = a.k, dk = a.dk;
+  __syncthreads();
+  const int cnt = nm == 0 ? a.nb : dk;
+  const int rowbase = nm == 0 ? a.n0 - a.nb : a.n0 + (nm - 1) * dk;
+  const int base_next = a.cur.slot[rowbase] + cnt;
+  const int W = a.vis_words;
+  emit_block(pk, tid, k, a.blk[nm], a.gen_len0 + nm, a.res, true, a.cur, rowbase, a.next, 0, base_next);
+  emit_vis(t_parent, k, a.cur, rowbase, a.next, 0, base_next, W);
+  if (nm == a.dl && a.dl > 0) {
+    // the draft has not seen its own last block: next draft input = that block ++ the new beams (:402-416)
+    for (int j = tid; j < dk; j += blockDim.x) {
+      a.dnext.ids[j] = a.cur.ids[rowbase + j];
+      a.dnext.pos[j] = a.cur.pos[rowbase + j];
+      a.dnext.slot[j] = a.cur.slot[rowbase + j];
+    }
+    for (int idx = tid; idx < dk * W; idx += blockDim.x) a.dnext.vis[idx] = a.cur.vis[(size_t)rowbase * W + idx];
+    emit_block(pk, tid, k, a.blk[nm], a.gen_len0 + nm, a.res, true, a.cur, rowbase, a.dnext, dk, base_next);
+    emit_vis(t_parent, k, a.cur, rowbase, a.dnext, dk, base_next, W);
+  }
+  int valid = __syncthreads_count(tid < k && pk.flat >= 0);
+  if (tid == 0) {
+    a.mail->n_matches = nm;
+    a.mail->n_valid = valid;
+    if (sh.status != 0) a.mail->status = sh.status;
+  }
 }
 
 // Sampling verification (beamSD.py:293-321 distributions, :332-369 accept / resample, :303-309 bonus draw), one launch for
@@ -801,28 +806,16 @@ __device__ void verify_sample_body(const VerifyArgs& a) {
   const int k = a.k, dk = a.dk;
   if (tid == 0) sh.status = 0;
   int nm = 0, n_rows_last = a.nb;
-  Pick pk;
-  pk.flat = -1; pk.score = -INFINITY; pk.parent = 0; pk.tok = 0; pk.node = 0;
+  Pick pk = no_pick();
   for (int i = 0; i <= a.dl; ++i) {
     const int n_rows = i == 0 ? a.nb : k;
     n_rows_last = n_rows;
-    __syncthreads();
-    if (tid < n_rows) {
-      int br = i == 0 ? tid : hit[tid];
-      sh.brow[tid] = br;
-      sh.node[tid] = a.blk[i].node[br];
-      sh.lrow[tid] = i == 0 ? tid : a.nb + (i - 1) * dk + br;
-      sh.bscore[tid] = i == 0 ? a.blk[0].score[tid] : sbh[tid];
-    }
-    __syncthreads();
+    verify_step_rows(sh, a, i, n_rows, hit, sbh);
     CandRegs cr;
     expand_candidates(sh, n_rows, a.logits, a.ld, a.lse, a.fsm, a.temperature, a.cutoff, cr);
     if (i == a.dl) {                                                     // bonus draw from the target (:303-309)
       sample_topn(sh, cr, cr.sc, k, ats_rng_sub(a.seed, ATS_RNG_BONUS, a.round, i, 0));
-      if (tid < k) {
-        unsigned long long key = sh.topk.sel[tid];
-        fin_flat[tid] = key ? (int)(~(uint32_t)(key & 0xffffffffull)) : -1;
-      }
+      if (tid < k) fin_flat[tid] = flat_of_key(sh.topk.sel[tid]);
       __syncthreads();
       break;
     }
@@ -878,10 +871,8 @@ __device__ void verify_sample_body(const VerifyArgs& a) {
       logw[s2] = -INFINITY; pr[s2] = 0.f;
       const int fl = cr.flat[s2];
       if (fl >= 0 && cr.sc[s2] > -INFINITY) {
-        const int c = tid + s2 * kScanThreads;
-        int lo = 0, hi = n_rows;
-        while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (sh.off[mid] <= c) lo = mid; else hi = mid; }
-        const float q = expf(dts[dto[sh.brow[lo]] + (c - sh.off[lo])] - Ld);   // same node -> same children order in the draft's table
+        const Cand cd = cand_at(sh, n_rows, tid + s2 * kScanThreads);
+        const float q = expf(dts[dto[sh.brow[cd.r]] + cd.j] - Ld);             // same node -> same children order in the draft's table
         const float p = expf(cr.sc[s2] - Lt);
         bool taken = false;
         for (int j = 0; j < dk; ++j) taken |= (d_acc[j] && d_flat[j] == fl);
@@ -892,7 +883,7 @@ __device__ void verify_sample_body(const VerifyArgs& a) {
         }
       }
     }
-    const float tot = block_sum(sh, part);
+    const float tot = block_sum(part, sh.red_s);                         // red_s is free: block_lse ends in a barrier behind its last read
     if (tot == 0.f) {
 #pragma unroll
       for (int s2 = 0; s2 < kCPT; ++s2) logw[s2] = pr[s2] > 0.f ? logf(pr[s2]) : -INFINITY;
@@ -905,8 +896,8 @@ __device__ void verify_sample_body(const VerifyArgs& a) {
       hit[r0] = d_flat[tid];                                           // scratch: unsorted flats
     }
     if (tid < k - n_acc) {
-      unsigned long long key = sh.topk.sel[tid];
-      hit[n_acc + tid] = key ? (int)(~(uint32_t)(key & 0xffffffffull)) : 0x7fffffff;
+      const int fl = flat_of_key(sh.topk.sel[tid]);
+      hit[n_acc + tid] = fl < 0 ? 0x7fffffff : fl;                     // "none" sorts last
     }
     __syncthreads();
     if (tid < k) {
@@ -923,31 +914,10 @@ __device__ void verify_sample_body(const VerifyArgs& a) {
     pk = pick_of_flat(fin_flat[tid], a.fsm, sh, n_rows_last, a.logits, a.ld, a.temperature);
     t_parent[tid] = pk.parent;
   }
-  __syncthreads();
-  const int cnt = nm == 0 ? a.nb : dk;
-  const int rowbase = nm == 0 ? a.n0 - a.nb : a.n0 + (nm - 1) * dk;
-  const int base_next = a.cur.slot[rowbase] + cnt;
-  const int W = a.vis_words;
-  emit_block(pk, tid, k, a.blk[nm], a.gen_len0 + nm, a.res, true, a.cur, rowbase, a.next, 0, base_next, W);
-  emit_vis(t_parent, k, a.cur, rowbase, a.next, 0, base_next, W);
-  if (nm == a.dl && a.dl > 0) {
-    for (int j = tid; j < dk; j += blockDim.x) {
-      a.dnext.ids[j] = a.cur.ids[rowbase + j];
-      a.dnext.pos[j] = a.cur.pos[rowbase + j];
-      a.dnext.slot[j] = a.cur.slot[rowbase + j];
-    }
-    for (int idx = tid; idx < dk * W; idx += blockDim.x) a.dnext.vis[idx] = a.cur.vis[(size_t)rowbase * W + idx];
-    emit_block(pk, tid, k, a.blk[nm], a.gen_len0 + nm, a.res, true, a.cur, rowbase, a.dnext, dk, base_next, W);
-    emit_vis(t_parent, k, a.cur, rowbase, a.dnext, dk, base_next, W);
-  }
-  int valid = __syncthreads_count(tid < k && pk.flat >= 0);
-  if (tid == 0) {
-    a.mail->n_matches = nm;
-    a.mail->n_valid = valid;
-    if (sh.status != 0) a.mail->status = sh.status;
-  }
+  verify_outputs(a, sh, pk, t_parent, nm);
 }
 
+// Greedy verification: the target's k best of every step must all be among the draft's dk of the next block (beamSD.py:279-298, :323-330, :371-380)
 __device__ void verify_walk_body(const VerifyArgs& a) {
   __shared__ ExpandShared sh;
   __shared__ int t_parent[MAXB], t_pos[MAXB], hit[MAXB];
@@ -957,8 +927,7 @@ __device__ void verify_walk_body(const VerifyArgs& a) {
   const int k = a.k, dk = a.dk;
   if (tid == 0) { sh.status = 0; reject = 0; }
   int nm = 0;
-  Pick pk;
-  pk.flat = -1; pk.score = -INFINITY; pk.parent = 0; pk.tok = 0; pk.node = 0;
+  Pick pk = no_pick();
   for (int i = 0; i <= a.dl; ++i) {
     // staged verification: block i's rows come with a later forward.  Nothing has been written yet (the trace's picks are rewritten by the
     // walk that finishes, which starts from step 0 again and so takes every decision exactly as the one-forward round does)
@@ -967,15 +936,7 @@ __device__ void verify_walk_body(const VerifyArgs& a) {
       return;
     }
     const int n_rows = i == 0 ? a.nb : k;
-    __syncthreads();
-    if (tid < n_rows) {                                                  // beamSD.py:279-296
-      int br = i == 0 ? tid : hit[tid];
-      sh.brow[tid] = br;
-      sh.node[tid] = a.blk[i].node[br];
-      sh.lrow[tid] = a.blk_row0[i] + br;
-      sh.bscore[tid] = i == 0 ? a.blk[0].score[tid] : sbh[tid];
-    }
-    __syncthreads();
+    verify_step_rows(sh, a, i, n_rows, hit, sbh);
     expand_and_select(sh, n_rows, a.logits, a.ld, a.lse, a.fsm, k, a.row_cand, a.n_row_cand);     // :297-298,323-328
     if (tid < k) {
       pk = decode_pick(sh.topk.sel[tid], a.fsm, sh.brow, sh.node, n_rows);
@@ -1003,31 +964,13 @@ __device__ void verify_walk_body(const VerifyArgs& a) {
     }
     nm += 1;
   }
-  __syncthreads();
-  // ---- outputs: new round beams, next-round inputs (:383-416)
-  const int cnt = nm == 0 ? a.nb : dk;
-  const int rowbase = nm == 0 ? a.n0 - a.nb : a.n0 + (nm - 1) * dk;
-  const int base_next = a.cur.slot[rowbase] + cnt;
-  const int W = a.vis_words;
-  emit_block(pk, tid, k, a.blk[nm], a.gen_len0 + nm, a.res, true, a.cur, rowbase, a.next, 0, base_next, W);
-  emit_vis(t_parent, k, a.cur, rowbase, a.next, 0, base_next, W);
-  if (nm == a.dl && a.dl > 0) {
-    // the draft has not seen its own last block: next draft input = that block ++ the new beams (:402-416)
-    for (int j = tid; j < dk; j += blockDim.x) {
-      a.dnext.ids[j] = a.cur.ids[rowbase + j];
-      a.dnext.pos[j] = a.cur.pos[rowbase + j];
-      a.dnext.slot[j] = a.cur.slot[rowbase + j];
-    }
-    for (int idx = tid; idx < dk * W; idx += blockDim.x) a.dnext.vis[idx] = a.cur.vis[(size_t)rowbase * W + idx];
-    emit_block(pk, tid, k, a.blk[nm], a.gen_len0 + nm, a.res, true, a.cur, rowbase, a.dnext, dk, base_next, W);
-    emit_vis(t_parent, k, a.cur, rowbase, a.dnext, dk, base_next, W);
-  }
-  int valid = __syncthreads_count(tid < k && pk.flat >= 0);
-  if (tid == 0) {
-    a.mail->n_matches = nm;
-    a.mail->n_valid = valid;
-    if (sh.status != 0) a.mail->status = sh.status;
-  }
+  verify_outputs(a, sh, pk, t_parent, nm);
+}
+
+__global__ __launch_bounds__(kScanThreads) void verify_walk_multi_kernel(const VerifyArgs* __restrict__ args) {
+  __shared__ VerifyArgs a;
+  load_args(a, args + blockIdx.x);
+  if (a.sample) verify_sample_body(a); else verify_walk_body(a);
 }
 
 // ---------------------------------------------------------------------------- prompt init / export / accept

@@ -581,6 +581,38 @@ def test_sampling_bssd_makes_the_oracles_decisions(name, temperature):
     assert torch.equal(a["beam_sequence"], b["beam_sequence"])
 
 
+def test_sampled_walk_that_accepts_every_block_feeds_the_draft_its_last_block():
+    """do_sample with draft == target at K 6, DK 12, gamma 2, 7 new tokens: for each of these seeds a round before the last accepts both draft
+    blocks, so the sampled walk writes the draft's re-ingest inputs (its own last block ++ the new beams, beamSD.py:402-416) and the next
+    round's draft steps run on them.  Same beams, rounds and accepted steps as oracle/beamsd_sample_ref.py, under the rule of the test above."""
+    from oracle import beamsd_sample_ref as S
+    temperature = 1.0
+    case = dict(next(c for c in CASES if c["name"] == "k6_dk12_new7_gamma2_s5"), sigma=0.0)
+    ci = build_case_inputs(case)
+    tgt, drf = _models(ci, case)
+    for m in (tgt, drf):
+        m.generation_config.do_sample = True
+        m.generation_config.temperature = temperature
+    rt, rd = RefLlama(ci["target_dims"], ci["target_sd"]), RefLlama(ci["draft_dims"], ci["draft_sd"])
+    P = len(ci["prompt"])
+    inputs = {"input_ids": torch.from_numpy(ci["prompt"])[None].cuda()}
+    checked = 0
+    for seed in range(40, 44):
+        rng = S.HashRng(seed)
+        ref = S.BSSD_sample(rt, rd, ci["prompt"], case["gamma"], case["max_new_tokens"], case["K"], case["DK"], ci["fn"], temperature, rng)
+        out = BSSD(tgt, drf, inputs, case["gamma"], case["max_new_tokens"], prefix_allowed_tokens_fn=ci["fn"], seed=seed)
+        nv = out["n_valid"]
+        same = nv == ref["beam_sequence"].shape[0] and out["beam_sequence"][:nv, P:].cpu().tolist() == ref["beam_sequence"][:, P:].tolist()
+        if rng.min_margin < 1e-4 and not same:
+            continue                                   # a draw decided by less than fp32 rounding: not comparable
+        checked += 1
+        assert same, (seed, rng.min_margin)
+        assert out["accept_steps"] == [r["n_matches"] for r in ref["rounds"]] and out["n_run"] == ref["n_run"]
+        assert case["gamma"] in out["accept_steps"][:-1]                          # a walk that accepted every block, and a round after it
+        np.testing.assert_allclose(out["beam_scores"][:nv].cpu().numpy(), ref["beam_scores"].numpy(), atol=SCORE_TOL, rtol=0)
+    assert checked >= 3
+
+
 @pytest.mark.parametrize("name,temperature", [("k10_dk40_sigma01", 1.3), ("k20_dk40_sigma0", 0.7), ("k5_dk10_indep", 1.0)])
 def test_sampling_with_a_host_side_mask_or_processor_samples_what_the_device_path_samples(name, temperature):
     """do_sample with an arbitrary Python mask callable or extra logits processors (legal in the reference: beamSD.py:293-369 with any
