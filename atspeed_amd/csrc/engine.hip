@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "round_plan.h"
 #include "session_queue.h"
 
 // ---------------------------------------------------------------------------- errors / misc
@@ -1241,12 +1242,12 @@ struct atspeed_decoder {
   UserOpts opts;                // item filter, resident adapter and prompt prefixes of the user on this decoder
   // the automaton as this user's kernels take it by value: the shared arrays and the user's own blocked-node bits
   FsmDev fsm_dev(const atspeed_fsm* fsm) const { FsmDev f = fsm->dev; f.blocked = ats_mask_bits(opts.masks, opts.mask_user); return f; }
-  struct Run {
-    const atspeed_fsm* fsm; int gamma, max_new, k, dk;
+  struct Run : ats_round::User {                // n0, nb, base, k, dk, gen, reingest: the part round_plan.h's rules read and move on
+    const atspeed_fsm* fsm; int gamma, max_new;
     int32_t* out_tokens; float* out_scores; atspeed_gen_stats* stats_out;
     atspeed_gen_stats s;
-    int cur, gen, base, n0, nb, dl;
-    bool reingest, final_step, export_only, done;
+    int cur, dl;
+    bool final_step, export_only, done;
   } run;
 };
 
@@ -1413,12 +1414,30 @@ static TokBuf tb_offset(const TokBuf& t, int row, int W) {
   return o;
 }
 
+// the ranges of a call's sizes, under the name of the entry point that was given them: every generate call's (draft = false), and those a
+// beam-SD call or a session adds
+static int check_ranges(const char* who, int max_new, int k, bool draft = false, int dk = 0, int gamma = 0) {
+  ATS_REQUIRE(max_new >= 1 && max_new <= LMAX, ATSPEED_ERR_CAPACITY, "%s: max_new_tokens %d out of [1,%d]", who, max_new, LMAX);
+  ATS_REQUIRE(k >= 1 && k <= MAXB, ATSPEED_ERR_CAPACITY, "%s: beam size %d out of [1,%d]", who, k, MAXB);
+  if (!draft) return ATSPEED_OK;
+  ATS_REQUIRE(dk >= k && dk <= MAXB, ATSPEED_ERR_CAPACITY, "%s: draft beam size %d must be in [k=%d, %d]", who, dk, k, MAXB);
+  ATS_REQUIRE(gamma >= 1 && gamma <= ATSPEED_MAX_GAMMA, ATSPEED_ERR_CAPACITY, "%s: gamma %d out of [1,%d]", who, gamma, ATSPEED_MAX_GAMMA);
+  return ATSPEED_OK;
+}
+// decoder i of a call's list: it is there, runs the models of decoder 0 and stands in the list once.  draft: 0 = the target alone counts,
+// 1 = the draft must be the same too, 2 = and there must be one
+static int same_pair_once(const char* who, const char* rule, atspeed_decoder* const* decs, int i, int draft) {
+  const atspeed_decoder *d = decs[i], *d0 = decs[0];
+  ATS_REQUIRE(d && (draft < 2 || d->draft) && d->target == d0->target && (draft < 1 || d->draft == d0->draft), ATSPEED_ERR_INVALID, "%s: %s", who, rule);
+  for (int j = 0; j < i; ++j) ATS_REQUIRE(decs[i] != decs[j], ATSPEED_ERR_INVALID, "%s: decoder %d used twice", who, i);
+  return ATSPEED_OK;
+}
+
 static int check_common(atspeed_decoder* d, const int32_t* prompt, int P, const atspeed_fsm* fsm, int start_node,
                         int max_new, int k, const int32_t* out_tokens, const float* out_scores) {
   ATS_REQUIRE(d && prompt && fsm && out_tokens && out_scores, ATSPEED_ERR_INVALID, "generate: null argument");
   ATS_REQUIRE(P >= 1 && P <= d->max_prompt, ATSPEED_ERR_CAPACITY, "generate: prompt length %d exceeds max_prompt %d", P, d->max_prompt);
-  ATS_REQUIRE(max_new >= 1 && max_new <= LMAX, ATSPEED_ERR_CAPACITY, "generate: max_new_tokens %d out of [1,%d]", max_new, LMAX);
-  ATS_REQUIRE(k >= 1 && k <= MAXB, ATSPEED_ERR_CAPACITY, "generate: beam size %d out of [1,%d]", k, MAXB);
+  ATS_TRY(check_ranges("generate", max_new, k));
   ATS_REQUIRE(fsm->dev.vocab == d->target->cfg.vocab_size, ATSPEED_ERR_INVALID, "generate: constraint vocab %d != model vocab %d",
               fsm->dev.vocab, d->target->cfg.vocab_size);
   ATS_REQUIRE(start_node >= 0 && start_node < std::max(fsm->dev.n_nodes, 1), ATSPEED_ERR_INVALID, "generate: start node out of range");
@@ -1451,6 +1470,23 @@ static int mailbox_status(atspeed_decoder* d) {
   }
   return ATSPEED_OK;
 }
+// a user of a lock-step call that ends alone while the others go on, by what its mailbox holds: its prompt does not open with its prompt
+// prefix (Mailbox::pad, found by prompt init) or it lost every beam of a step to the id filter (beamSD.py:80-86; the reference dies on a
+// shape mismatch there).  ATSPEED_OK: neither.  The one-user calls return these as errors instead
+static int ends_alone_status(const atspeed_decoder* d) {
+  if (d->mail_host->pad) return ATSPEED_ERR_INVALID;
+  return d->mail_host->status == ATSPEED_ERR_FILTERED ? ATSPEED_ERR_FILTERED : ATSPEED_OK;
+}
+// "this user ends here": its status and count of valid beams, its time, its stats record; blank: it leaves no beam (blank_outputs)
+static int finish_user(atspeed_decoder* d, int status, int n_valid, bool blank, hipStream_t st) {
+  atspeed_decoder::Run& r = d->run;
+  r.s.n_valid = n_valid; r.s.status = status;
+  if (blank) ATS_TRY(blank_outputs(r.out_tokens, r.out_scores, r.k, r.max_new, st));
+  r.s.total_ms = r.s.draft_ms + r.s.target_ms + r.s.verify_ms;
+  if (r.stats_out) *r.stats_out = r.s;
+  r.done = true;
+  return ATSPEED_OK;
+}
 
 // ---- a group of users decoded in lock step ----------------------------------------------------------------------
 struct StageEvents { hipEvent_t ev[8]; bool init = false; };
@@ -1464,12 +1500,13 @@ static int stage_events(hipEvent_t** out) {
   return ATSPEED_OK;
 }
 
-template <typename A>
-static int stage_args(const std::vector<A>& v, const A** dev_out, hipStream_t st) {
-  const void* p = nullptr;
-  ATS_TRY(ats_stage(v.data(), v.size() * sizeof(A), &p, st));
-  *dev_out = (const A*)p;
-  return ATSPEED_OK;
+// several users' argument blocks through one launch of a multi kernel (one workgroup or grid column per block): the vector goes to the
+// device through the staging ring, then launch(device array, count, stream)
+template <typename A, typename F>
+static int launch_staged(const std::vector<A>& args, F launch, hipStream_t st) {
+  const void* dev = nullptr;
+  ATS_TRY(ats_stage(args.data(), args.size() * sizeof(A), &dev, st));
+  return launch((const A*)dev, (int)args.size(), st);
 }
 
 static Seg make_seg(const TokBuf& tb, int n_tok, int n_slots, int n_logit, const KvCache& kv, int adapter = 0) {
@@ -1477,6 +1514,10 @@ static Seg make_seg(const TokBuf& tb, int n_tok, int n_slots, int n_logit, const
   s.ids = tb.ids; s.pos = tb.pos; s.slot = tb.slot; s.vis = tb.vis; s.kc = kv.k; s.vc = kv.v;
   s.n_tok = n_tok; s.n_slots = n_slots; s.n_logit = n_logit; s.adapter = adapter;
   return s;
+}
+// a span of a user's round (round_plan.h) as a segment: its rows of the user's token buffer tb
+static Seg span_seg(const TokBuf& tb, int W, const ats_round::Span& sp, const KvCache& kv, int adapter = 0) {
+  return make_seg(tb_offset(tb, sp.row0, W), sp.n_tok, sp.n_slots, sp.n_logit, kv, adapter);
 }
 int ats_seg_finish(SegTable& t, int qtile_rows) {
   t.total_tok = t.total_logit = t.n_qtiles = 0;
@@ -1528,9 +1569,8 @@ extern "C" void atspeed_prefix_destroy(atspeed_prefix* p) {
 }
 
 static int kv_rows_launch(void* store_k, void* store_v, const std::vector<KvRowsUser>& users, int len, const atspeed_llama* m, int to_store, hipStream_t st) {
-  const KvRowsUser* du = nullptr;
-  ATS_TRY(stage_args(users, &du, st));
-  return ats_bf16::ats_kv_rows_copy(store_k, store_v, du, (int)users.size(), len, m->cfg.n_layers, m->cfg.hidden * m->esz, m->cfg.max_slots, to_store, st);
+  return launch_staged(users, [&](const KvRowsUser* du, int n, hipStream_t s) {
+    return ats_bf16::ats_kv_rows_copy(store_k, store_v, du, n, len, m->cfg.n_layers, m->cfg.hidden * m->esz, m->cfg.max_slots, to_store, s); }, st);
 }
 
 extern "C" int atspeed_prefix_create(atspeed_llama* m, const int32_t* ids, int32_t len, int32_t adapter_slot, void* stream, atspeed_prefix** out) {
@@ -1605,9 +1645,8 @@ static int kv_rows_abi(const char* who, void* store_k, void* store_v, void* cons
                 "%s: arena %d is null or not 16-byte aligned", who, i);
     users[i] = KvRowsUser{k_arenas[i], v_arenas[i]};
   }
-  const KvRowsUser* du = nullptr;
-  ATS_TRY(stage_args(users, &du, st));
-  return ats_bf16::ats_kv_rows_copy(store_k, store_v, du, n, len, layers, row_bytes, max_slots, to_store, st);
+  return launch_staged(users, [&](const KvRowsUser* du, int m, hipStream_t s) {
+    return ats_bf16::ats_kv_rows_copy(store_k, store_v, du, m, len, layers, row_bytes, max_slots, to_store, s); }, st);
 }
 extern "C" int atspeed_kv_rows_scatter(const void* store_k, const void* store_v, void* const* k_arenas, void* const* v_arenas, int32_t n, int32_t len,
                                        int32_t layers, int32_t row_bytes, int32_t max_slots, void* stream) {
@@ -1691,9 +1730,9 @@ static int prefix_mismatch_error(const atspeed_decoder* d) {
 // ---- one decode step: forward, then every user's beam step on its rows of the result
 // where a segment's logit rows, their normalisers and their candidate lists start in the model's buffers
 struct RowViews { const float* logits; const float* lse; const int32_t* row_cand; };
-static RowViews seg_rows(const atspeed_llama* m, const Seg& sg, int row_off = 0) {
+static RowViews seg_rows(const atspeed_llama* m, const Seg& sg) {
   const ActCtx* cx = m->act;
-  const size_t r0 = (size_t)row_off + sg.logit_row0;
+  const size_t r0 = (size_t)sg.logit_row0;
   return RowViews{cx->logits + r0 * m->logits_ld, cx->lse + r0, cx->row_cand + r0 * MAXB};
 }
 
@@ -1722,6 +1761,28 @@ static BeamStepArgs beam_step_args(const atspeed_decoder* d, const atspeed_llama
   if (d->warps()) a.cutoff = d->cutoff;
   return a;
 }
+// the per-round part of user d's verify walk on target T: beams, sizes, token buffers, outputs, sampling tables.  The round's phases add
+// where the rows are (logits / lse / row_cand, blk_row0) and how many blocks have rows (blocks_ready)
+static VerifyArgs verify_args(const atspeed_decoder* d, const atspeed_llama* T) {
+  const atspeed_decoder::Run& r = d->run;
+  VerifyArgs va{};
+  va.blk[0] = d->round_beams[r.cur];
+  for (int b = 1; b <= r.dl; ++b) va.blk[b] = d->blk[b];
+  va.nb = r.nb; va.dl = r.dl; va.k = r.k; va.dk = r.dk; va.gen_len0 = r.gen;
+  va.ld = T->logits_ld; va.fsm = d->fsm_dev(r.fsm); va.n_row_cand = r.k;
+  va.cur = d->tin[r.cur]; va.n0 = r.n0; va.next = d->tin[r.cur ^ 1]; va.dnext = d->dround; va.vis_words = d->W;
+  va.res = d->round_beams[r.cur ^ 1]; va.mail = d->mail_dev;
+  va.vtrace = (d->trace_level >= 1 && !d->sample) ? d->vtrace_dev : nullptr;
+  if (d->sample) {
+    va.sample = 1; va.temperature = d->temperature; va.seed = d->seed; va.round = r.s.n_run;
+    for (int b = 0; b < r.dl; ++b) {
+      va.dtab_score[b] = d->tab_score + (size_t)b * ATS_MAX_CAND; va.dtab_off[b] = d->tab_off + (size_t)b * (MAXB + 1);
+      va.dtab_lse[b] = d->tab_lse + b;
+    }
+  }
+  if (d->warps()) va.cutoff = d->cutoff;
+  return va;
+}
 // sampling-mode warpers: the cutoff job in front of a sampled beam step (one segment: the step's source beams) ...
 static WarpCutArgs warp_cut_args(const atspeed_decoder* d, const BeamStepArgs& s) {
   WarpCutArgs w{};
@@ -1746,9 +1807,7 @@ static int warp_cutoffs(const std::vector<WarpCutArgs>& w, hipStream_t st) {
   if (w.size() == 1) return ats_row_warp_cutoff(w[0], st);
   int max_rows = 0;
   for (const WarpCutArgs& a : w) { int rows = 0; for (int s = 0; s < a.n_seg; ++s) rows += a.seg[s].n; max_rows = std::max(max_rows, rows); }
-  const WarpCutArgs* dw = nullptr;
-  ATS_TRY(stage_args(w, &dw, st));
-  return ats_row_warp_cutoff_multi(dw, (int)w.size(), max_rows, st);
+  return launch_staged(w, [&](const WarpCutArgs* dw, int n, hipStream_t s) { return ats_row_warp_cutoff_multi(dw, n, max_rows, s); }, st);
 }
 // the step also writes the next forward's inputs: the parents' rows start at in_row0 of tb, the k new rows go to out_row0 (KV slots from out_slot0)
 static void beam_step_emit(BeamStepArgs& a, const TokBuf& tb, int in_row0, int out_row0, int out_slot0) {
@@ -1758,14 +1817,19 @@ static void beam_step_emit(BeamStepArgs& a, const TokBuf& tb, int in_row0, int o
 // out_tokens / out_scores of the users that finish: one user by value, several through one staged launch
 static int export_beams(const std::vector<ExportBeamsArgs>& ex, int k, int max_new, hipStream_t st) {
   if (ex.size() == 1) return ats_export_beams(ex[0].b, k, max_new, ex[0].out_tokens, ex[0].out_scores, st, ex[0].sort_desc != 0);
-  const ExportBeamsArgs* de = nullptr;
-  ATS_TRY(stage_args(ex, &de, st));
-  return ats_export_beams_multi(de, (int)ex.size(), k, max_new, st);
+  return launch_staged(ex, [&](const ExportBeamsArgs* de, int n, hipStream_t s) { return ats_export_beams_multi(de, n, k, max_new, s); }, st);
 }
 
-// prompts of every user of a batch -> token buffers, start beams and mailboxes, one launch
-static int init_prompts_multi(atspeed_decoder** decs, int n, const int32_t* const* prompts, const int32_t* prompt_lens, const int32_t* start_nodes,
-                              hipStream_t st) {
+// what stands in front of a user's first forward.  One user: the prompt -> token buffer, start beams and mailbox, by value; then the rows of
+// its prompt prefixes into its arenas (draft_too: the draft's as well)
+static int start_user(atspeed_decoder* d, const int32_t* prompt, int P, int start_node, bool draft_too, hipStream_t st) {
+  ATS_TRY(ats_init_prompt(d->tin[0], prompt, P, d->W, d->round_beams[0], start_node, d->target->cfg.vocab_size, d->mail_dev, st, prefix_len(d),
+                          d->opts.tprefix ? d->opts.tprefix->ids : nullptr));
+  return prefixes_scatter(&d, 1, draft_too, st);
+}
+// ... and every user of a batch, or every user a session admits in a round: one prompt launch for all of them, then the prefixes
+static int start_users(atspeed_decoder** decs, int n, const int32_t* const* prompts, const int32_t* prompt_lens, const int32_t* start_nodes,
+                       bool draft_too, hipStream_t st) {
   std::vector<InitPromptArgs> ia(n);
   int max_p = 1;
   for (int u = 0; u < n; ++u) {
@@ -1774,9 +1838,9 @@ static int init_prompts_multi(atspeed_decoder** decs, int n, const int32_t* cons
                            d->opts.tprefix ? d->opts.tprefix->ids : nullptr};
     max_p = std::max(max_p, (int)prompt_lens[u]);
   }
-  const InitPromptArgs* dev = nullptr;
-  ATS_TRY(stage_args(ia, &dev, st));
-  return ats_init_prompt_multi(dev, n, max_p, decs[0]->W, decs[0]->target->cfg.vocab_size, st);
+  ATS_TRY(launch_staged(ia, [&](const InitPromptArgs* dev, int m, hipStream_t s) {
+    return ats_init_prompt_multi(dev, m, max_p, decs[0]->W, decs[0]->target->cfg.vocab_size, s); }, st));
+  return prefixes_scatter(decs, n, draft_too, st);
 }
 
 static int bssd_begin(atspeed_decoder* d, const int32_t* prompt, int P, const atspeed_fsm* fsm, int start_node, int gamma,
@@ -1784,8 +1848,7 @@ static int bssd_begin(atspeed_decoder* d, const int32_t* prompt, int P, const at
                       hipStream_t st, bool init_prompt = true) {
   ATS_TRY(check_common(d, prompt, P, fsm, start_node, max_new, k, out_tokens, out_scores));
   ATS_REQUIRE(d->draft, ATSPEED_ERR_INVALID, "bssd: decoder was created without a draft model");
-  ATS_REQUIRE(dk >= k && dk <= MAXB, ATSPEED_ERR_CAPACITY, "bssd: draft beam size %d must be in [k=%d, %d]", dk, k, MAXB);
-  ATS_REQUIRE(gamma >= 1 && gamma <= ATSPEED_MAX_GAMMA, ATSPEED_ERR_CAPACITY, "bssd: gamma %d out of [1,%d]", gamma, ATSPEED_MAX_GAMMA);
+  ATS_TRY(check_ranges("bssd", max_new, k, true, dk, gamma));           // (max_new and k have passed check_common)
   ATS_TRY(user_opts_check("bssd", d->target, d->draft, fsm, d->opts, P, true));
   const int lp = prefix_len(d);                    // the first round starts behind the prefix: what every later round looks like
   atspeed_decoder::Run& r = d->run;
@@ -1796,19 +1859,15 @@ static int bssd_begin(atspeed_decoder* d, const int32_t* prompt, int P, const at
   r.reingest = false; r.final_step = false; r.export_only = false; r.done = false;
   d->trace.clear();
   d->decisions.clear();
-  if (init_prompt) {
-    ATS_TRY(ats_init_prompt(d->tin[0], prompt, P, d->W, d->round_beams[0], start_node, d->target->cfg.vocab_size, d->mail_dev, st, lp,
-                            lp ? d->opts.tprefix->ids : nullptr));
-    ATS_TRY(prefixes_scatter(&d, 1, true, st));
-  }
+  if (init_prompt) ATS_TRY(start_user(d, prompt, P, start_node, true, st));
   return ATSPEED_OK;
 }
 
-// activation capacity of both models for the largest possible batched forward of a group of n users whose prompts hold up to n0 tokens
-static int bssd_ensure_capacity(atspeed_llama* T, atspeed_llama* D, int n, int n0, int gamma, int k, int dk) {
-  ATS_TRY(ensure_act(T, n * (std::max(n0, k) + gamma * dk), n * (MAXB + gamma * dk)));
-  ATS_TRY(ensure_act(D, n * std::max(std::max(n0, dk + k), dk), n * MAXB));
-  return ATSPEED_OK;
+// activation capacity of both models for the worst round of these users (round_plan.h; n0: each user's longest round inputs)
+static int bssd_ensure_capacity(atspeed_llama* T, atspeed_llama* D, const std::vector<int>& n0, int gamma, int k, int dk) {
+  const ats_round::Capacity c = ats_round::worst_round(n0.data(), (int)n0.size(), gamma, k, dk, MAXB);
+  ATS_TRY(ensure_act(T, c.t_tok, c.t_rows));
+  return ensure_act(D, c.d_tok, c.d_rows);
 }
 
 // what differs between the callers of a round, and what a round reports back
@@ -1868,13 +1927,14 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
     if (r.done) continue;
     // (a slot removed under a user that is in a lane: the caller's error, found here before the round launches anything)
     ATS_REQUIRE(T->slot_ok(d->opts.adapter), ATSPEED_ERR_INVALID, "bssd: a user names adapter slot %d, which the target no longer holds", d->opts.adapter);
-    r.final_step = r.export_only = false;
-    if (r.gen >= r.max_new) { r.final_step = r.export_only = true; continue; }
-    r.dl = std::min(r.gamma, r.max_new - r.gen - 1);                               // beamSD.py:504
-    if (r.dl == 0) { r.final_step = true; fin.push_back(d); continue; }            // :505-509
-    ATS_REQUIRE(r.n0 + r.dl * r.dk <= d->tok_cap, ATSPEED_ERR_CAPACITY, "bssd: packed target input too long");
-    ATS_REQUIRE(r.base + r.n0 + r.dl * r.dk <= T->cfg.max_slots, ATSPEED_ERR_CAPACITY,
-                "bssd: KV slots exhausted (%d needed, %d available)", r.base + r.n0 + r.dl * r.dk, T->cfg.max_slots);
+    const ats_round::Start start = ats_round::classify(r.gen, r.max_new, r.gamma);  // beamSD.py:504-509
+    r.final_step = start.kind != ats_round::VERIFY; r.export_only = start.kind == ats_round::EXPORT_ONLY;
+    if (r.export_only) continue;
+    r.dl = start.dl;
+    if (r.final_step) { fin.push_back(d); continue; }
+    const ats_round::Span all = ats_round::span(r, 0, r.dl);                        // the round's reach, whether it is forwarded at once or in phases
+    ATS_REQUIRE(all.n_tok <= d->tok_cap, ATSPEED_ERR_CAPACITY, "bssd: packed target input too long");
+    ATS_REQUIRE(all.n_slots <= T->cfg.max_slots, ATSPEED_ERR_CAPACITY, "bssd: KV slots exhausted (%d needed, %d available)", all.n_slots, T->cfg.max_slots);
     ver.push_back(d);
     max_dl = std::max(max_dl, r.dl);
   }
@@ -1888,12 +1948,8 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
     for (atspeed_decoder* d : ver) if (d->run.dl > i) us.push_back(d);
     for (atspeed_decoder* d : us) {
       atspeed_decoder::Run& r = d->run;
-      TokBuf& tin = d->tin[r.cur];
-      Seg sg;
-      if (i == 0) sg = r.reingest ? make_seg(d->dround, r.dk + r.k, r.base + r.n0, r.nb, d->dkv)
-                                  : make_seg(tin, r.n0, r.base + r.n0, r.nb, d->dkv);
-      else        sg = make_seg(tb_offset(tin, r.n0 + (i - 1) * r.dk, W), r.dk, r.base + r.n0 + i * r.dk, r.dk, d->dkv);
-      t.seg[t.n++] = sg;
+      const ats_round::Span sp = ats_round::span(r, i, i);     // step 0 reads the round inputs, step i the block step i - 1 wrote
+      t.seg[t.n++] = (i == 0 && r.reingest) ? span_seg(d->dround, W, ats_round::reingest_span(r), d->dkv) : span_seg(d->tin[r.cur], W, sp, d->dkv);
       r.s.n_draft_forwards++;
     }
     ATS_TRY(ats_seg_finish(t));
@@ -1903,7 +1959,7 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
       atspeed_decoder* d = us[j];
       atspeed_decoder::Run& r = d->run;
       BeamStepArgs a = beam_step_args(d, D, t.seg[j], r.fsm, i == 0 ? d->round_beams[r.cur] : d->blk[i], d->blk[i + 1], r.gen + i, r.dk);
-      beam_step_emit(a, d->tin[r.cur], i == 0 ? r.n0 - r.nb : r.n0 + (i - 1) * r.dk, r.n0 + i * r.dk, r.base + r.n0 + i * r.dk);
+      beam_step_emit(a, d->tin[r.cur], ats_round::beam_row0(r, i), ats_round::span(r, i + 1, i + 1).row0, ats_round::span(r, i, i).n_slots);
       if (a.sample) {
         a.rng_sub = ats_rng_sub(d->seed, ATS_RNG_STEP, r.s.n_run, i, 1);
         a.tab_score = d->tab_score + (size_t)i * ATS_MAX_CAND; a.tab_off = d->tab_off + (size_t)i * (MAXB + 1); a.tab_lse = d->tab_lse + i;
@@ -1912,20 +1968,19 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
       args.push_back(a);
     }
     ATS_TRY(warp_cutoffs(wargs, st));
-    const BeamStepArgs* dev_args = nullptr;
-    ATS_TRY(stage_args(args, &dev_args, st));
-    ATS_TRY(ats_beam_step_multi(dev_args, (int)args.size(), st));
+    ATS_TRY(launch_staged(args, ats_beam_step_multi, st));
   }
   hipEventRecord(g_ev[1], st);
   hipEventRecord(g_ev[5], st);                     // the draft's end (g_ev[1] moves on to the start of a staged round's last phase)
-  // ---- 2. target forward and 3. verify (:190-232, :242-456, :505-509).  Packed: ONE forward over (round inputs ++ draft blocks) of every
-  //         verifying user and the inputs of every user on its final step, then every walk.  Staged (bssd_round_staged): phase 0 forwards the
-  //         round inputs only, phase p >= 1 draft block p of the users whose walk is still pending; each phase ends with the walks of its users
-  //         over the blocks that have rows so far and -- but for the last -- one mailbox read-back
+  // ---- 2. target forward and 3. verify (:190-232, :242-456, :505-509), in phases.  A phase forwards blocks b0 .. b1 (round_plan.h) of every
+  //         verifying user whose walk is still pending -- phase 0 also the inputs of every user on its final step -- and ends with those users'
+  //         walks over the blocks that have rows so far.  Packed: one phase that holds every block.  Staged (bssd_round_staged): phase p holds
+  //         block p, and every phase but the last ends with one mailbox read-back
   float ms_t = 0.f, ms_v = 0.f;                    // target / verify time of the phases already read back
   if (!ver.empty() || !fin.empty()) {
     const bool staged = ctl.lock_step && bssd_round_staged(ver, fin);
     std::vector<VerifyArgs> vall(ver.size());      // every verifying user's walk, built in phase 0; a later phase adds its block's rows
+    std::vector<int> row_first(ver.size());        // ... whose rows are counted from the user's first logit row of the round
     std::vector<size_t> pend(ver.size());          // indices into ver: the users of the phase
     for (size_t j = 0; j < ver.size(); ++j) pend[j] = j;
     int row_off = 0;                               // logit rows the earlier phases of the round hold
@@ -1934,16 +1989,14 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
       for (size_t j : pend) {
         atspeed_decoder* d = ver[j];
         atspeed_decoder::Run& r = d->run;
-        const int Tn = r.n0 + r.dl * r.dk;
-        if (!staged)     t.seg[t.n++] = make_seg(d->tin[r.cur], Tn, r.base + Tn, r.nb + r.dl * r.dk, d->tkv, d->opts.adapter);
-        else if (p == 0) t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv, d->opts.adapter);
-        else             t.seg[t.n++] = make_seg(tb_offset(d->tin[r.cur], r.n0 + (p - 1) * r.dk, W), r.dk, r.base + r.n0 + p * r.dk, r.dk, d->tkv, d->opts.adapter);
+        const ats_round::Blocks ph = ats_round::phase_blocks(staged, p, r.dl);
+        t.seg[t.n++] = span_seg(d->tin[r.cur], W, ats_round::span(r, ph.b0, ph.b1), d->tkv, d->opts.adapter);
         if (p == 0) r.s.n_target_forwards++;
         r.s.n_target_passes++;
       }
       if (p == 0) for (atspeed_decoder* d : fin) {
         atspeed_decoder::Run& r = d->run;
-        t.seg[t.n++] = make_seg(d->tin[r.cur], r.n0, r.base + r.n0, r.nb, d->tkv, d->opts.adapter);
+        t.seg[t.n++] = span_seg(d->tin[r.cur], W, ats_round::span(r, 0, 0), d->tkv, d->opts.adapter);
         r.s.n_target_forwards++; r.s.n_target_passes++;
       }
       ATS_TRY(ats_seg_finish(t));
@@ -1954,38 +2007,24 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
       // ---- 3. verify for the phase's users, one workgroup each
       std::vector<VerifyArgs> vargs;
       std::vector<WarpCutArgs> wargs;                  // sampling-mode warpers: the cutoffs of this round's verify walks and final steps
-      const ActCtx* cx = T->act;
+      bool more = false;                               // a walk can be pending only where the user has a block without rows left
       for (size_t i = 0; i < pend.size(); ++i) {
         atspeed_decoder* d = ver[pend[i]];
         atspeed_decoder::Run& r = d->run;
         VerifyArgs& va = vall[pend[i]];
-        if (p == 0) {
-          va.blk[0] = d->round_beams[r.cur];
-          for (int b = 1; b <= r.dl; ++b) va.blk[b] = d->blk[b];
-          va.nb = r.nb; va.dl = r.dl; va.k = r.k; va.dk = r.dk; va.gen_len0 = r.gen;
-          va.ld = T->logits_ld; va.fsm = d->fsm_dev(r.fsm); va.n_row_cand = r.k;
-          va.cur = d->tin[r.cur]; va.n0 = r.n0; va.next = d->tin[r.cur ^ 1]; va.dnext = d->dround; va.vis_words = W;
-          va.res = d->round_beams[r.cur ^ 1]; va.mail = d->mail_dev;
-          va.vtrace = (d->trace_level >= 1 && !d->sample) ? d->vtrace_dev : nullptr;
-          if (d->sample) {
-            va.sample = 1; va.temperature = d->temperature; va.seed = d->seed; va.round = r.s.n_run;
-            for (int b = 0; b < r.dl; ++b) {
-              va.dtab_score[b] = d->tab_score + (size_t)b * ATS_MAX_CAND; va.dtab_off[b] = d->tab_off + (size_t)b * (MAXB + 1);
-              va.dtab_lse[b] = d->tab_lse + b;
-            }
-          }
-        }
-        if (!staged) {                                 // the walk's rows start at the user's first row; block b's follow block b - 1's
+        if (p == 0) {                                  // the walk's rows start at the user's first row of the round ...
+          va = verify_args(d, T);
           const RowViews rv = seg_rows(T, t.seg[i]);
           va.logits = rv.logits; va.lse = rv.lse; va.row_cand = rv.row_cand;
-          for (int b = 1; b <= r.dl; ++b) va.blk_row0[b] = r.nb + (b - 1) * r.dk;
-          va.blocks_ready = r.dl + 1;
-        } else {                                       // rows counted from the buffers' start: block p's are where this phase's forward puts them
-          va.logits = cx->logits; va.lse = cx->lse; va.row_cand = cx->row_cand;
-          va.blk_row0[p] = row_off + t.seg[i].logit_row0;
-          va.blocks_ready = p + 1;
+          row_first[pend[i]] = t.seg[i].logit_row0;
         }
-        if (d->warps()) { va.cutoff = d->cutoff; wargs.push_back(warp_cut_args(d, va)); }
+        // ... and block b's are where the phase that forwarded it put them: behind the span's earlier blocks
+        const ats_round::Blocks ph = ats_round::phase_blocks(staged, p, r.dl);
+        const int span_row0 = row_off + t.seg[i].logit_row0 - row_first[pend[i]];
+        for (int b = ph.b0; b <= ph.b1; ++b) va.blk_row0[b] = span_row0 + ats_round::logit_row(r, ph.b0, b);
+        va.blocks_ready = ph.b1 + 1;
+        more = more || ph.b1 < r.dl;
+        if (va.cutoff) wargs.push_back(warp_cut_args(d, va));
         vargs.push_back(va);
       }
       std::vector<BeamStepArgs> fargs;
@@ -1998,20 +2037,9 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
         fargs.push_back(a);
       }
       ATS_TRY(warp_cutoffs(wargs, st));
-      if (!vargs.empty()) {
-        const VerifyArgs* dv = nullptr;
-        ATS_TRY(stage_args(vargs, &dv, st));
-        ATS_TRY(ats_verify_walk_multi(dv, (int)vargs.size(), st));
-      }
-      if (!fargs.empty()) {
-        const BeamStepArgs* df = nullptr;
-        ATS_TRY(stage_args(fargs, &df, st));
-        ATS_TRY(ats_beam_step_multi(df, (int)fargs.size(), st));
-      }
+      if (!vargs.empty()) ATS_TRY(launch_staged(vargs, ats_verify_walk_multi, st));
+      if (!fargs.empty()) ATS_TRY(launch_staged(fargs, ats_beam_step_multi, st));
       if (p == 0) for (atspeed_decoder* d : fin) { d->run.cur ^= 1; d->run.gen += 1; }
-      // a walk can be pending only where the user has a block without rows left
-      bool more = false;
-      for (size_t j : pend) more = more || (staged && ver[j]->run.dl > p);
       if (!more) break;
       // ---- hand-over: the phase's mailbox read-back; the next phase is built for the users still pending
       hipEventRecord(g_ev[3], st);
@@ -2045,8 +2073,7 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
     atspeed_decoder* d = decs[u];
     atspeed_decoder::Run& r = d->run;
     if (r.done) continue;
-    if (r.final_step) {}
-    else if (ctl.flat_trace)              // trace of the draft's flat ids (parity tests drive one user at a time; batches skip the copies)
+    if (!r.final_step && ctl.flat_trace)  // trace of the draft's flat ids (parity tests drive one user at a time; batches skip the copies)
       for (int i = 1; i <= r.dl; ++i)
         ATS_HIP(hipMemcpyAsync(d->trace_host + (i - 1) * MAXB, d->blk[i].flat, sizeof(int32_t) * r.dk, hipMemcpyDeviceToHost, st));
     if (d->trace_level >= 1 && !r.export_only)
@@ -2068,36 +2095,16 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
     atspeed_decoder* d = decs[u];
     atspeed_decoder::Run& r = d->run;
     if (r.done) continue;
-    if (d->mail_host->pad) {
-      // the prompt does not open with the user's prefix (found by prompt init): the user ends here, alone, as a filtered one does
-      if (!ctl.keep_filtered) return prefix_mismatch_error(d);
-      r.s.n_valid = 0; r.s.status = ATSPEED_ERR_INVALID;
-      ATS_TRY(blank_outputs(r.out_tokens, r.out_scores, r.k, r.max_new, st));
-      r.s.total_ms = r.s.draft_ms + r.s.target_ms + r.s.verify_ms;
-      if (r.stats_out) *r.stats_out = r.s;
-      r.done = true;
-      continue;
-    }
-    if (ctl.keep_filtered && d->mail_host->status == ATSPEED_ERR_FILTERED) {
-      // a lock-step batch does not die with one user: this user lost every beam of a step to the id filter (beamSD.py:80-86; the
-      // reference dies on a shape mismatch there) and ends with no valid beam, the others go on (the one-user call returns the error)
-      r.s.n_valid = 0; r.s.status = ATSPEED_ERR_FILTERED;
-      ATS_TRY(blank_outputs(r.out_tokens, r.out_scores, r.k, r.max_new, st));
-      r.s.total_ms = r.s.draft_ms + r.s.target_ms + r.s.verify_ms;
-      if (r.stats_out) *r.stats_out = r.s;
-      r.done = true;
-      continue;
-    }
+    // a lock-step batch does not die with one user: a prefix mismatch or a filtered user ends here with no valid beam, the others go on
+    if (d->mail_host->pad && !ctl.keep_filtered) return prefix_mismatch_error(d);
+    if (ctl.keep_filtered && ends_alone_status(d) != ATSPEED_OK) { ATS_TRY(finish_user(d, ends_alone_status(d), 0, true, st)); continue; }
     ATS_TRY(mailbox_status(d));
     // stage times: the group's stage time shared equally by the users that were active in the round
     r.s.draft_ms += ms_d / n_act; r.s.target_ms += ms_t / n_act; r.s.verify_ms += ms_v / n_act;
     if (r.final_step) {
       // `cur` was flipped when the step was launched: the parents are round_beams[cur ^ 1], the result round_beams[cur]
       if (d->trace_level >= 1 && !r.export_only) decisions_append(d, 1, r.nb, 0, 0, r.gen - 1, r.k, r.dk, {r.cur ^ 1, r.cur});
-      r.s.n_valid = d->mail_host->n_valid;
-      r.s.total_ms = r.s.draft_ms + r.s.target_ms + r.s.verify_ms;
-      if (r.stats_out) *r.stats_out = r.s;
-      r.done = true;
+      ATS_TRY(finish_user(d, ATSPEED_OK, d->mail_host->n_valid, false, st));
       continue;
     }
     const int nm = d->mail_host->n_matches, dl = r.dl, dk = r.dk;
@@ -2114,12 +2121,8 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
       decisions_append(d, 0, r.nb, dl, nm, r.gen, r.k, dk, blocks);
     }
     if (r.s.n_run < ATSPEED_MAX_NEW_TOKENS) r.s.accept_steps[r.s.n_run] = nm;
-    r.s.n_run++;
-    r.s.total_accept_steps += nm;
-    r.base += r.n0 + nm * dk;             // compact: keep up to the end of block nm
-    r.n0 = r.k; r.nb = r.k;
-    r.gen += nm + 1;                      // :522
-    r.reingest = (nm == dl);
+    r.s.n_run++; r.s.total_accept_steps += nm;
+    ats_round::advance(r, nm, dl);        // :522: compact (keep up to the end of block nm), the k new beams are the next inputs
     r.cur ^= 1;
     ctl.any = true;
   }
@@ -2131,15 +2134,10 @@ static int bssd_round(atspeed_decoder** decs, int n, hipStream_t st, hipEvent_t*
 static int bssd_group_run(atspeed_decoder** decs, int n, hipStream_t st, bool lock_step) {
   hipEvent_t* g_ev = nullptr;
   ATS_TRY(stage_events(&g_ev));
-  int cap_t = 0, cap_r = 0, cap_d = 0;
-  for (int u = 0; u < n; ++u) {
-    const atspeed_decoder::Run& r = decs[u]->run;
-    cap_t += std::max(r.n0, r.k) + r.gamma * r.dk;
-    cap_r += MAXB + r.gamma * r.dk;
-    cap_d += std::max(std::max(r.n0, r.dk + r.k), r.dk);
-  }
-  ATS_TRY(ensure_act(decs[0]->target, cap_t, cap_r));
-  ATS_TRY(ensure_act(decs[0]->draft, cap_d, n * MAXB));
+  std::vector<int> n0(n);
+  for (int u = 0; u < n; ++u) n0[u] = decs[u]->run.n0;
+  const atspeed_decoder::Run& r0 = decs[0]->run;     // one gamma, k and dk for the whole call
+  ATS_TRY(bssd_ensure_capacity(decs[0]->target, decs[0]->draft, n0, r0.gamma, r0.k, r0.dk));
   RoundCtl ctl{n <= 4, n > 1, lock_step};
   do ATS_TRY(bssd_round(decs, n, st, g_ev, ctl)); while (ctl.any);
   return ATSPEED_OK;
@@ -2153,14 +2151,11 @@ extern "C" int atspeed_bssd_generate_batch(atspeed_decoder** decs, int32_t n, co
   ATS_REQUIRE(n >= 1 && n <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "bssd_batch: %d users per call (max %d)", n, ATS_MAX_SEGS);
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n; ++i) {
-    ATS_REQUIRE(decs[i] && decs[i]->target == decs[0]->target && decs[i]->draft == decs[0]->draft, ATSPEED_ERR_INVALID,
-                "bssd_batch: decoders must share one target/draft pair");
-    for (int j = 0; j < i; ++j) ATS_REQUIRE(decs[i] != decs[j], ATSPEED_ERR_INVALID, "bssd_batch: decoder %d used twice", i);
+    ATS_TRY(same_pair_once("bssd_batch", "decoders must share one target/draft pair", decs, i, 1));
     ATS_TRY(bssd_begin(decs[i], prompts[i], prompt_lens[i], fsm, start_nodes[i], gamma, max_new, k, dk, out_tokens[i], out_scores[i],
                        stats ? &stats[i] : nullptr, st, false));
   }
-  ATS_TRY(init_prompts_multi(decs, n, prompts, prompt_lens, start_nodes, st));
-  ATS_TRY(prefixes_scatter(decs, n, true, st));
+  ATS_TRY(start_users(decs, n, prompts, prompt_lens, start_nodes, true, st));
   return bssd_group_run(decs, n, st, true);
 }
 
@@ -2204,15 +2199,10 @@ extern "C" int atspeed_session_create(atspeed_decoder* const* lanes, int32_t n_l
   ATS_REQUIRE(lanes && fsm && out, ATSPEED_ERR_INVALID, "session_create: null argument");
   ATS_REQUIRE(n_lanes >= 1 && n_lanes <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "session_create: %d lanes (1 .. %d)", n_lanes, ATS_MAX_SEGS);
   ATS_REQUIRE(max_prompt >= 1, ATSPEED_ERR_INVALID, "session_create: max_prompt %d must be positive", max_prompt);
-  ATS_REQUIRE(max_new >= 1 && max_new <= LMAX, ATSPEED_ERR_CAPACITY, "session_create: max_new_tokens %d out of [1,%d]", max_new, LMAX);
-  ATS_REQUIRE(k >= 1 && k <= MAXB, ATSPEED_ERR_CAPACITY, "session_create: beam size %d out of [1,%d]", k, MAXB);
-  ATS_REQUIRE(dk >= k && dk <= MAXB, ATSPEED_ERR_CAPACITY, "session_create: draft beam size %d must be in [k=%d, %d]", dk, k, MAXB);
-  ATS_REQUIRE(gamma >= 1 && gamma <= ATSPEED_MAX_GAMMA, ATSPEED_ERR_CAPACITY, "session_create: gamma %d out of [1,%d]", gamma, ATSPEED_MAX_GAMMA);
+  ATS_TRY(check_ranges("session_create", max_new, k, true, dk, gamma));
   for (int i = 0; i < n_lanes; ++i) {
+    ATS_TRY(same_pair_once("session_create", "lanes must be decoders of one target/draft pair", lanes, i, 2));
     const atspeed_decoder *d = lanes[i], *d0 = lanes[0];
-    ATS_REQUIRE(d && d->draft && d->target == d0->target && d->draft == d0->draft, ATSPEED_ERR_INVALID,
-                "session_create: lanes must be decoders of one target/draft pair");
-    for (int j = 0; j < i; ++j) ATS_REQUIRE(lanes[i] != lanes[j], ATSPEED_ERR_INVALID, "session_create: decoder %d used twice", i);
     ATS_REQUIRE(d->max_prompt >= max_prompt, ATSPEED_ERR_CAPACITY, "session_create: lane %d holds prompts of %d tokens, the session asks for %d",
                 i, d->max_prompt, max_prompt);
     ATS_REQUIRE(d->sample == d0->sample && d->temperature == d0->temperature && d->top_k == d0->top_k && d->top_p == d0->top_p &&
@@ -2227,13 +2217,15 @@ extern "C" int atspeed_session_create(atspeed_decoder* const* lanes, int32_t n_l
   s->lanes.assign(lanes, lanes + n_lanes);
   s->fsm = fsm; s->gamma = gamma; s->max_new = max_new; s->k = k; s->dk = dk; s->max_prompt = max_prompt; s->st = (hipStream_t)stream;
   // everything a round allocates on demand, now: activations for the worst round, stage events, the staging ring, the split-K arenas
-  ATS_TRY(bssd_ensure_capacity(T, D, n_lanes, max_prompt, gamma, k, dk));
+  const std::vector<int> n0(n_lanes, max_prompt);          // any lane may hold the longest prompt
+  ATS_TRY(bssd_ensure_capacity(T, D, n0, gamma, k, dk));
   hipEvent_t* ev = nullptr;
   ATS_TRY(stage_events(&ev));
   const int32_t zero = 0; const void* staged = nullptr;
   ATS_TRY(ats_stage(&zero, sizeof(zero), &staged, s->st));
-  const bool got_t = session_reserve_arena(T, n_lanes * (std::max(max_prompt, k) + gamma * dk), s->st);
-  const bool got_d = session_reserve_arena(D, n_lanes * std::max(max_prompt, dk + k), s->st);
+  const ats_round::Capacity worst = ats_round::worst_round(n0.data(), n_lanes, gamma, k, dk, MAXB);
+  const bool got_t = session_reserve_arena(T, worst.t_tok, s->st);
+  const bool got_d = session_reserve_arena(D, worst.d_tok, s->st);
   ATS_HIP(hipStreamSynchronize(s->st));
   ats_stage_reset();
   g_last_error.clear();
@@ -2280,7 +2272,7 @@ extern "C" int atspeed_session_submit_ex(atspeed_session* s, const atspeed_sessi
   ATS_REQUIRE(P <= s->max_prompt, ATSPEED_ERR_CAPACITY, "session_submit: prompt length %d exceeds the session's max_prompt %d", P, s->max_prompt);
   // a user's rounds need up to P + (max_new - 1) * dk KV slots (every draft block of the call kept): refused here, where it costs nobody else
   // a round, rather than inside one
-  const int slots = P + (s->max_new - 1) * s->dk, max_slots = s->lanes[0]->target->cfg.max_slots;
+  const int slots = ats_round::call_slots(P, s->max_new, s->dk), max_slots = s->lanes[0]->target->cfg.max_slots;
   ATS_REQUIRE(slots <= max_slots, ATSPEED_ERR_CAPACITY, "session_submit: prompt of %d tokens can need %d KV slots (%d available)", P, slots, max_slots);
   *ticket_out = s->q.submit(SessionJob{uu.prompt_ids_dev, P, uu.start_node, uu.seed, uu.out_tokens_dev, uu.out_scores_dev, uu.stats_host, opts});
   return ATSPEED_OK;
@@ -2305,14 +2297,11 @@ static int session_round(atspeed_session* s) {
     fresh.push_back(d); prompts.push_back(j.prompt); lens.push_back(j.P); starts.push_back(j.start_node);
     return (int)ATSPEED_OK;
   }));
-  if (!fresh.empty()) {
-    ATS_TRY(init_prompts_multi(fresh.data(), (int)fresh.size(), prompts.data(), lens.data(), starts.data(), s->st));
-    ATS_TRY(prefixes_scatter(fresh.data(), (int)fresh.size(), true, s->st));
-  }
+  if (!fresh.empty()) ATS_TRY(start_users(fresh.data(), (int)fresh.size(), prompts.data(), lens.data(), starts.data(), true, s->st));
   std::vector<atspeed_decoder*> decs; std::vector<int> lane_of;
   for (int l = 0; l < s->q.n_lanes(); ++l) if (s->q.lane_busy(l)) { decs.push_back(s->lanes[l]); lane_of.push_back(l); }
   if (decs.empty()) return ATSPEED_OK;
-  ATS_TRY(bssd_ensure_capacity(decs[0]->target, decs[0]->draft, s->q.n_lanes(), s->max_prompt, s->gamma, s->k, s->dk));   // create made it: a no-op
+  ATS_TRY(bssd_ensure_capacity(decs[0]->target, decs[0]->draft, std::vector<int>(s->q.n_lanes(), s->max_prompt), s->gamma, s->k, s->dk));   // create made it: a no-op
   s->q.begin_round();
   RoundCtl ctl{false, true, true};
   ATS_TRY(bssd_round(decs.data(), (int)decs.size(), s->st, g_ev, ctl));
@@ -2337,9 +2326,7 @@ static int session_round_guarded(atspeed_session* s) {
     ats_stage_reset();
     for (int l = 0; l < s->q.n_lanes(); ++l)
       if (s->q.lane_busy(l)) {
-        atspeed_decoder::Run& r = s->lanes[l]->run;
-        r.done = true; r.s.status = rc; r.s.n_valid = 0;
-        if (r.stats_out) *r.stats_out = r.s;
+        (void)finish_user(s->lanes[l], rc, 0, false, s->st);
         user_leaves(s->lanes[l]);
         s->q.retire(l, rc);
       }
@@ -2404,19 +2391,12 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
                             atspeed_gen_stats* stats, hipStream_t st) {
   atspeed_llama* T = decs[0]->target;
   const int W = decs[0]->W;
-  int cap_t = 0;
-  for (int u = 0; u < n; ++u) cap_t += std::max(prompt_lens[u], k);
-  ATS_TRY(ensure_act(T, cap_t, n * MAXB));
+  const ats_round::Capacity cap = ats_round::worst_round(prompt_lens, n, 0, k, k, MAXB);     // no draft blocks: the target's steps alone
+  ATS_TRY(ensure_act(T, cap.t_tok, cap.t_rows));
   hipEvent_t* g_ev = nullptr;
   ATS_TRY(stage_events(&g_ev));
-  if (n == 1) {
-    atspeed_decoder* d = decs[0];
-    ATS_TRY(ats_init_prompt(d->tin[0], prompts[0], prompt_lens[0], W, d->round_beams[0], start_nodes[0], T->cfg.vocab_size, d->mail_dev, st, prefix_len(d),
-                            d->opts.tprefix ? d->opts.tprefix->ids : nullptr));
-  } else {
-    ATS_TRY(init_prompts_multi(decs, n, prompts, prompt_lens, start_nodes, st));
-  }
-  ATS_TRY(prefixes_scatter(decs, n, false, st));
+  if (n == 1) ATS_TRY(start_user(decs[0], prompts[0], prompt_lens[0], start_nodes[0], false, st));
+  else        ATS_TRY(start_users(decs, n, prompts, prompt_lens, start_nodes, false, st));
   hipEventRecord(g_ev[0], st);
   struct St { int row0, n_in, nb, base, cur; };
   std::vector<St> s(n);
@@ -2441,11 +2421,7 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
     ATS_TRY(warp_cutoffs(wargs, st));
     wargs.clear();
     if (n == 1) ATS_TRY(ats_beam_step(args[0], st));
-    else {
-      const BeamStepArgs* dev_args = nullptr;
-      ATS_TRY(stage_args(args, &dev_args, st));
-      ATS_TRY(ats_beam_step_multi(dev_args, n, st));
-    }
+    else        ATS_TRY(launch_staged(args, ats_beam_step_multi, st));
   }
   std::vector<ExportBeamsArgs> ex;
   for (int u = 0; u < n; ++u) ex.push_back(ExportBeamsArgs{decs[u]->round_beams[s[u].cur], out_tokens[u], out_scores[u], decs[u]->sample ? 1 : 0});
@@ -2457,18 +2433,14 @@ static int target_group_run(atspeed_decoder** decs, int n, const int32_t* const*
   hipEventElapsedTime(&ms, g_ev[0], g_ev[1]);
   // a lock-step batch does not die with a user that lost every beam of a step to the id filter: that user ends with a blanked result block
   // and its status, the others go on (as in the beam-SD batch loop); the one-user call returns the error
-  // so does a user whose prompt does not open with its prompt prefix (Mailbox::pad), with ATSPEED_ERR_INVALID
-  auto ends_alone = [&](int u) -> int {
-    if (decs[u]->mail_host->pad) return ATSPEED_ERR_INVALID;
-    return decs[u]->mail_host->status == ATSPEED_ERR_FILTERED ? ATSPEED_ERR_FILTERED : ATSPEED_OK;
-  };
+  // so does a user whose prompt does not open with its prompt prefix, with ATSPEED_ERR_INVALID (ends_alone_status)
   if (n == 1 && decs[0]->mail_host->pad) return prefix_mismatch_error(decs[0]);
   bool any_filtered = false;
   for (int u = 0; u < n; ++u)
-    if (n > 1 && ends_alone(u) != ATSPEED_OK) { ATS_TRY(blank_outputs(out_tokens[u], out_scores[u], k, max_new, st)); any_filtered = true; }
+    if (n > 1 && ends_alone_status(decs[u]) != ATSPEED_OK) { ATS_TRY(blank_outputs(out_tokens[u], out_scores[u], k, max_new, st)); any_filtered = true; }
   if (any_filtered) ATS_HIP(hipStreamSynchronize(st));
   for (int u = 0; u < n; ++u) {
-    const int alone = n > 1 ? ends_alone(u) : ATSPEED_OK;
+    const int alone = n > 1 ? ends_alone_status(decs[u]) : ATSPEED_OK;
     const bool filtered = alone != ATSPEED_OK;
     if (!filtered) ATS_TRY(mailbox_status(decs[u]));
     if (stats) {
@@ -2490,8 +2462,7 @@ extern "C" int atspeed_target_generate_batch(atspeed_decoder** decs, int32_t n, 
   ATS_REQUIRE(decs && prompts && prompt_lens && start_nodes && out_tokens && out_scores, ATSPEED_ERR_INVALID, "target_generate_batch: null argument");
   ATS_REQUIRE(n >= 1 && n <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "target_generate_batch: %d users per call (max %d)", n, ATS_MAX_SEGS);
   for (int u = 0; u < n; ++u) {
-    ATS_REQUIRE(decs[u] && decs[u]->target == decs[0]->target, ATSPEED_ERR_INVALID, "target_generate_batch: decoders must share one target model");
-    for (int j = 0; j < u; ++j) ATS_REQUIRE(decs[u] != decs[j], ATSPEED_ERR_INVALID, "target_generate_batch: decoder %d used twice", u);
+    ATS_TRY(same_pair_once("target_generate_batch", "decoders must share one target model", decs, u, 0));
     ATS_TRY(target_check(decs[u], prompts[u], prompt_lens[u], fsm, start_nodes[u], max_new, k, out_tokens[u], out_scores[u]));
   }
   return target_group_run(decs, n, prompts, prompt_lens, fsm, start_nodes, max_new, k, out_tokens, out_scores, stats, (hipStream_t)stream);

@@ -183,10 +183,11 @@ int ats_beam_step_multi(const BeamStepArgs* dev_args, int n, hipStream_t st);
 struct VerifyArgs {
   BeamSet blk[ATSPEED_MAX_GAMMA + 1];         // blk[0] round beams, blk[i] draft step i
   int nb, dl, k, dk, gen_len0;
-  const float* logits;  int ld;  const float* lse;   // rows: block 0 (nb), then dl blocks of dk
-  // block i's first row of logits / lse / row_cand / cutoff (packed, sampled walks always: 0, nb, nb + dk, ...; a staged round: where that
-  // phase's forward put them), and -- greedy walk only -- how many blocks have rows yet.  A walk that needs block i >= blocks_ready writes
-  // n_matches = ATS_WALK_PENDING and nothing else
+  const float* logits;  int ld;  const float* lse;   // the user's first logit row of the round: block 0's nb rows start here
+  // One rule for every walk: block i's first row of logits / lse / row_cand / cutoff, counted from that first row, is where the phase that
+  // forwarded block i put it (round_plan.h).  A packed round, and so every sampled one, has one phase: 0, nb, nb + dk, ...; a staged round's
+  // block i lies behind the rows of phases 0 .. i - 1.  blocks_ready -- greedy walk only -- is how many blocks have rows yet: a walk that
+  // needs block i >= blocks_ready writes n_matches = ATS_WALK_PENDING and nothing else
   int blk_row0[ATSPEED_MAX_GAMMA + 1];  int blocks_ready;
   FsmDev fsm;
   TokBuf cur;  int n0;                        // packed target inputs of this round

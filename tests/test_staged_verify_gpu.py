@@ -14,6 +14,7 @@ from atspeed_amd import _lib, synth
 from atspeed_amd.beamSD import BSSD, BSSD_batch, BSSDSession, release_decoders
 from atspeed_amd.model import HipLlama
 from tests.golden.cases import CASES, build_case_inputs
+from tests.round_ref import expected_draft_log, expected_log
 
 KW = dict(max_slots=512, max_tokens=512, max_logit_rows=448)
 SCORE_TOL = 1e-3
@@ -61,55 +62,6 @@ def assert_same_user(a, b, what=""):
         assert a[key] == b[key], (what, key, a[key], b[key])
 
 
-def expected_log(prompt_lens, accept_steps, gamma, new, k, dk, staged, t_star=None):
-    """The target forwards of a lock-step call over users with these accepted steps per round, from the round rule alone (beamSD.py:504-522):
-    -> ([(tokens, logit rows)], segments per forward, passes per user, draft-block counts gamma' per user and round).  With t_star a round
-    is staged only when its packed forward would exceed that many tokens (the switch at 1)."""
-    n = len(prompt_lens)
-    st = [dict(gen=0, n0=prompt_lens[u], nb=1, r=0, done=False) for u in range(n)]
-    log, segs, passes, dls = [], [], [0] * n, [[] for _ in range(n)]
-    while not all(s["done"] for s in st):
-        ver, fin = [], []
-        for u, s in enumerate(st):
-            if s["done"]:
-                continue
-            if s["gen"] >= new:
-                s["done"] = True                      # its last verification produced the last token: export only
-                continue
-            dl = min(gamma, new - s["gen"] - 1)
-            dls[u].append(dl)
-            (ver if dl > 0 else fin).append((u, dl))
-        if not ver and not fin:
-            continue
-        packed_tokens = sum(st[u]["n0"] + dl * dk for u, dl in ver) + sum(st[u]["n0"] for u, _ in fin)
-        if not staged or not ver or (t_star is not None and packed_tokens <= t_star):
-            log.append((packed_tokens, sum(st[u]["nb"] + dl * dk for u, dl in ver) + sum(st[u]["nb"] for u, _ in fin)))
-            segs.append(len(ver) + len(fin))
-            for u, _ in ver + fin:
-                passes[u] += 1
-        else:
-            log.append((sum(st[u]["n0"] for u, _ in ver + fin), sum(st[u]["nb"] for u, _ in ver + fin)))
-            segs.append(len(ver) + len(fin))
-            for u, _ in ver + fin:
-                passes[u] += 1
-            for p in range(1, gamma + 1):             # block p: the users whose walk accepted steps 0 .. p - 1 and that drafted a block p
-                alive = [u for u, dl in ver if dl >= p and accept_steps[u][st[u]["r"]] >= p]
-                if not alive:
-                    break
-                log.append((len(alive) * dk, len(alive) * dk))
-                segs.append(len(alive))
-                for u in alive:
-                    passes[u] += 1
-        for u, _ in fin:
-            st[u]["done"] = True
-        for u, _ in ver:
-            s = st[u]
-            s["gen"] += accept_steps[u][s["r"]] + 1
-            s["r"] += 1
-            s["n0"] = s["nb"] = k
-    return log, segs, passes, dls
-
-
 @pytest.fixture(scope="module")
 def mix():
     """The mixed batch's models and six users, their packed run (switch 0) and their staged run (switch 2), each once."""
@@ -120,9 +72,13 @@ def mix():
     inputs = _inputs(prompts)
     args = (case["gamma"], case["max_new_tokens"])
     six = [inputs[u] for u in MIX_USERS]
+    drf.forward_log(1)
     packed, plog = _logged(tgt, drf, six, *args, ci["fn"], 0)
+    pdlog = [tuple(int(x) for x in e) for e in drf.forward_log(1)]         # the draft's forwards of the packed call; the log starts again
     staged, slog = _logged(tgt, drf, six, *args, ci["fn"], 2)
-    yield dict(case=case, ci=ci, tgt=tgt, drf=drf, prompts=prompts, inputs=inputs, args=args, packed=packed, plog=plog, staged=staged, slog=slog)
+    sdlog = [tuple(int(x) for x in e) for e in drf.forward_log(0)]
+    yield dict(case=case, ci=ci, tgt=tgt, drf=drf, prompts=prompts, inputs=inputs, args=args, packed=packed, plog=plog, staged=staged, slog=slog,
+               pdlog=pdlog, sdlog=sdlog)
     release_decoders(tgt, drf)
 
 
@@ -168,6 +124,21 @@ def test_mixed_batch_forwards_exactly_the_pending_users_blocks(mix):
     assert r["slog"] == want_s                                            # per phase exactly the still-pending users' block rows
     assert [o["n_target_passes"] for o in r["staged"]] == passes_s and sum(passes_s) == sum(segs_s)
     assert sum(t for t, _ in r["slog"]) < sum(t for t, _ in r["plog"])    # rejected blocks were never forwarded
+
+
+def test_mixed_batch_forward_logs_are_the_round_rules(mix):
+    """Every forward of the six users' call, both models, packed and forced staged, against the restatement of the round rule
+    (tests/round_ref.py): the draft's steps are the same forwards in both runs (step 0: the round inputs, or dk + k rows after a round that
+    accepted every block; step i: dk rows per user that drafts more than i blocks), and the packed target log holds, per round, every
+    user's round inputs and draft blocks."""
+    r = mix
+    k, dk, (gamma, new) = r["case"]["K"], r["case"]["DK"], r["args"]
+    lens = [len(r["prompts"][u]) for u in MIX_USERS]
+    want_d, _ = expected_draft_log(lens, MIX_ORACLE, gamma, new, k, dk)
+    want_p, _, _, _ = expected_log(lens, MIX_ORACLE, gamma, new, k, dk, False)
+    print("draft log, packed call", r["pdlog"], "\ndraft log, staged call", r["sdlog"], "\nwant", want_d)
+    assert r["pdlog"] == want_d and r["sdlog"] == want_d
+    assert r["plog"] == want_p
 
 
 @pytest.mark.parametrize("name,gamma,new,want_dl", [("k5_dk10_indep", 3, 4, [3, 2, 1, 0]), ("k20_dk40_new7_gamma2", 2, 7, [2, 2, 0])])
