@@ -153,6 +153,9 @@ SIGNATURES = {
     "atspeed_session_submit_masked": (C.c_int, [_P, _P, _I, _I, _U32, _P, _P, C.POINTER(GenStats), _P, _I, C.POINTER(C.c_int64)]),
     "atspeed_beam_expand_prune_masked": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "atspeed_warp_cutoffs_masked": (C.c_int, [_P, _I, _P, _I, _P, _P, _F, _I, _F, _I, _P, _P, _I, _P]),
+    "atspeed_score_items": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "atspeed_score_tree_build": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "atspeed_path_scores": (C.c_int, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
     "atspeed_target_generate": (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, C.POINTER(GenStats), _P]),
     "atspeed_target_generate_batch": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "atspeed_assemble_sequences": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),

@@ -25,6 +25,10 @@ inference.py:175-176) are torch callables and are served by the host path: each 
 library's forward and its expand + top-K.  Sampling with a host-side mask or processors draws on the host from the device's
 counter-based streams (hostmask.py): a callable wrapping a compilable constraint samples exactly what the device path samples for that seed.
 
+`score_items` / `score_items_batch` score a given list of items instead of searching: the target's exact log-prob of each, the number a
+constrained beam search would report for it (the rule of beamSD.py:58-64), from one forward in which a user's items share the rows of their
+common prefixes (`atspeed_score_items`).  No reference counterpart.
+
 `BSSDSession` is the queue form of BSSD_batch (lanes refilled at round boundaries, users submitted at any time); `BSSD_batch(..., lanes=N)`
 runs a list through one.
 
@@ -920,6 +924,139 @@ def target_generate_batch(model, inputs_list, max_new_tokens: int, prefix_allowe
         out.update({"n_valid": int(st.n_valid), "status": int(st.status), "device_time_cost": st.total_ms * 1e-3,
                     "time_cost": wall / len(outs)})
     return outs
+
+
+# ---------------------------------------------------------------- scoring candidates
+def _tree_rows_added(prev, seq) -> int:
+    """Tree rows sequence `seq` adds behind `prev` (None: first of its chunk) in the packed layout of include/atspeed_hip.h "scoring
+    candidates": e = min(lcp, len(prev) - 1) leading depths are shared, its last token needs no row."""
+    e = 0
+    if prev is not None:
+        lim = min(len(prev), len(seq))
+        while e < lim and prev[e] == seq[e]:
+            e += 1
+        e = max(0, min(e, len(prev) - 1))
+    return max(0, len(seq) - 1 - e)
+
+
+def _score_chunks(seqs, P: int, model: HipLlama, who: str, user: int):
+    """A user's sorted item list cut into runs that each fit the model with the prompt repeated in front: prompt + tree rows within
+    max_tokens and max_slots, the rows from the prompt's last on within max_logit_rows.  A single item that does not fit raises."""
+    cap = min(model.max_tokens, model.max_slots, model.max_logit_rows + P - 1)
+    chunks, cur, rows = [], [], P
+    for q in seqs:
+        add = _tree_rows_added(cur[-1] if cur else None, q)
+        if cur and rows + add > cap:
+            chunks.append(cur)
+            cur, rows = [], P
+            add = _tree_rows_added(None, q)
+        if rows + add > cap:
+            raise ValueError(f"{who}: user {user}: a prompt of {P} tokens and one item of {len(q)} need {rows + add} rows, the model holds "
+                             f"{cap} (max_tokens {model.max_tokens}, max_slots {model.max_slots}, max_logit_rows {model.max_logit_rows})")
+        cur.append(q)
+        rows += add
+    chunks.append(cur)
+    return chunks
+
+
+@torch.no_grad()
+def score_items_batch(model, inputs_list, items_list, prefix_allowed_tokens_fn, adapters=None, prefix=None, errors: str = "raise",
+                      return_unknown: bool = False):
+    """The target's exact log-prob of every listed item, per user: one fp32 tensor [len(items)] per user, in the caller's order.  An item's
+    score is what a constrained beam search reports for it (the sum over its tokens of logit - LSE over the full vocabulary, in token order),
+    from ONE forward over all users in which a user's items share the rows of their common prefixes.
+
+    `items_list`: per user a list of token sequences in the form `allow_items=` takes, in any order, repeats allowed.  Items the
+    constraint does not know score -inf.  `adapters`: one resident adapter's name (`HipLlama.add_lora`) or None per user.  A list that does
+    not fit the model's capacity in one segment is scored in several, each repeating the prompt.
+    `errors="return"`: a user that cannot be scored (a single item that does not fit behind its prompt) gets its ValueError in place of its
+    tensor and the others are scored; "raise" (default) raises it.  `return_unknown`: also return the unknown items counted per user."""
+    who = "score_items_batch"
+    if prefix is not None:
+        raise NotImplementedError(f"{who}: prompt prefixes (PromptPrefix) serve the generate calls only; the branch-scoring forward "
+                                  "prefills every prompt whole")
+    if errors not in ("raise", "return"):
+        raise ValueError(f"{who}: errors must be 'raise' or 'return', not {errors!r}")
+    _mode(None, model)
+    n = len(inputs_list)
+    if len(items_list) != n:
+        raise ValueError(f"{who}: items_list needs one list per user: {len(items_list)} for {n} users")
+    if prefix_allowed_tokens_fn is None or _host_path(None, prefix_allowed_tokens_fn):
+        raise NotImplementedError(f"{who}: items are scored on the device path only (a mask that can compile() itself); "
+                                  f"{type(prefix_allowed_tokens_fn).__name__ if prefix_allowed_tokens_fn is not None else 'a mask-free search'} "
+                                  "has no automaton to walk them through")
+    slots = _adapter_slots(model, adapters, n, True, who)
+    lists = []
+    for u, items in enumerate(items_list):
+        seqs = [tuple(int(t) for t in q) for q in items]
+        if not seqs:
+            raise ValueError(f"{who}: user {u}: the item list is empty")
+        for q in seqs:
+            if not 1 <= len(q) <= _lib.MAX_NEW_TOKENS:
+                raise ValueError(f"{who}: user {u}: an item holds 1 .. {_lib.MAX_NEW_TOKENS} tokens, not {len(q)}")
+        lists.append(seqs)
+    c = _prepare(model, inputs_list, prefix_allowed_tokens_fn, None, who)
+    if c.fsms[0].free:
+        raise NotImplementedError(f"{who}: a mask-free search has no automaton to walk the items through")
+    dev, lib = c.dev, _lib.load()
+    # per user: sorted, de-duplicated, cut into segments; a segment is one "user" of the library call
+    segs, failed, uniq = [], {}, []
+    for u, seqs in enumerate(lists):
+        order = sorted(set(seqs))
+        uniq.append(order)
+        try:
+            chunks = _score_chunks(order, int(c.prompts[u].numel()), model, who, u)
+        except ValueError as e:
+            if errors == "raise":
+                raise
+            failed[u] = e
+            continue
+        segs += [(u, ch) for ch in chunks]
+    scores = {u: [] for u in range(n)}
+    unknown = [0] * n
+    with torch.cuda.device(dev):
+        flat = torch.cat([p.reshape(-1) for p in c.prompts]).to(torch.int32)
+        starts = np.concatenate([[0], np.cumsum([int(p.numel()) for p in c.prompts])])
+        for g0 in range(0, len(segs), MAX_USERS_PER_CALL):
+            part = segs[g0: g0 + MAX_USERS_PER_CALL]
+            m = len(part)
+            toks = np.asarray([t for _, ch in part for q in ch for t in q], np.int32)
+            seq_off = np.concatenate([[0], np.cumsum([len(q) for _, ch in part for q in ch])]).astype(np.int32)
+            user_off = np.concatenate([[0], np.cumsum([len(ch) for _, ch in part])]).astype(np.int32)
+            a_prompt = (C.c_void_p * m)(*[flat.data_ptr() + 4 * int(starts[u]) for u, _ in part])
+            a_len = np.asarray([int(c.prompts[u].numel()) for u, _ in part], np.int32)
+            a_start = np.asarray([c.fsms[u].start for u, _ in part], np.int32)
+            a_slot = np.asarray([slots[u] if slots else 0 for u, _ in part], np.int32)
+            out = torch.empty(int(user_off[-1]), dtype=torch.float32, device=dev)
+            unk, status = np.zeros(m, np.int32), np.zeros(m, np.int32)
+            _lib.check(lib.atspeed_score_items(model._handle, c.dfsm.handle, m, a_prompt, a_len.ctypes.data, a_start.ctypes.data, toks.ctypes.data,
+                                               seq_off.ctypes.data, user_off.ctypes.data, a_slot.ctypes.data if slots else None, out.data_ptr(),
+                                               unk.ctypes.data, status.ctypes.data, _lib.stream_ptr(dev)))
+            for i, (u, _) in enumerate(part):
+                if status[i] != 0:           # the front end sorts and sizes the lists itself: the library disagreeing is a bug, not a user error
+                    raise _lib.AtSpeedError(int(status[i]), f"{who}: user {u}: the library refused a segment the front end built")
+                scores[u].append(out[int(user_off[i]): int(user_off[i + 1])])
+                unknown[u] += int(unk[i])
+    res = []
+    for u in range(n):
+        if u in failed:
+            res.append(failed[u])
+            continue
+        s = torch.cat(scores[u]) if len(scores[u]) > 1 else scores[u][0]
+        where = {q: i for i, q in enumerate(uniq[u])}
+        res.append(s[torch.tensor([where[q] for q in lists[u]], device=dev)])      # the caller's order, repeats included
+    return (res, unknown) if return_unknown else res
+
+
+@torch.no_grad()
+def score_items(model, inputs: Dict, items, prefix_allowed_tokens_fn, adapter=None, prefix=None, return_unknown: bool = False):
+    """`score_items_batch` for one user: fp32 [len(items)], the target's log-prob of each item in the caller's order."""
+    if prefix is not None:
+        raise NotImplementedError("score_items: prompt prefixes (PromptPrefix) serve the generate calls only; the branch-scoring forward "
+                                  "prefills every prompt whole")
+    out = score_items_batch(model, [inputs], [items], prefix_allowed_tokens_fn, adapters=None if adapter is None else [adapter],
+                            return_unknown=return_unknown)
+    return (out[0][0], out[1][0]) if return_unknown else out[0]
 
 
 def last_trace(target_model, draft_model):

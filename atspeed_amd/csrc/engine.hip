@@ -355,6 +355,7 @@ struct atspeed_llama {
   KvCache kv0;                                   // cache of the plain atspeed_llama_forward API
   std::vector<KvCache> kv_pool;                  // one more cache per segment of atspeed_llama_forward_batch (grown on demand)
   ActCtx* act;                                   // grown on demand (ensure_act)
+  void* score_mem = nullptr; size_t score_bytes = 0;   // atspeed_score_items' lists, tree rows and per-sequence tables: one block, grown on demand like the pool
   bool prof_on = false;
   double prof_ms[5] = {0, 0, 0, 0, 0};
   long prof_cnt[5] = {0, 0, 0, 0, 0};
@@ -562,6 +563,7 @@ extern "C" void atspeed_llama_destroy(atspeed_llama* m) {
   kv_free(&m->kv0);
   for (KvCache& kv : m->kv_pool) kv_free(&kv);
   act_free(m->act);
+  hipFree(m->score_mem);
   quant_layers_free(m->quant);
   hipFree(m->lora_mem);
   for (auto& sl : m->slots) hipFree(sl.mem);
@@ -1009,6 +1011,157 @@ extern "C" int atspeed_llama_forward_batch_adapters(atspeed_llama* m, int32_t n,
   ATS_TRY(ats_seg_finish(t));
   ATS_TRY(ensure_act(m, tot, rows));
   return llama_forward_segs(m, t, logits_out, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------- scoring candidates
+// The exact target log-prob of every item of a list per user from ONE segmented forward (include/atspeed_hip.h "scoring candidates"): the
+// lists are staged into the model's score block, the tree builder packs each user's prompt + prefix-sharing tree, the forward runs the
+// decoder's lm_head form (full-vocabulary normaliser from the epilogue, only the automaton's logit tiles stored) and the path-score kernel
+// adds each item's terms as a beam search would (beamSD.py:58-64).
+// rows a user's list packs to, prompt included, by the builder's own rule: e(s) = min(lcp(s), len(s - 1) - 1), len(s) - 1 - e(s) new rows
+static int64_t score_tree_rows(const int32_t* tok, const int32_t* off, int s0, int s1, int P) {
+  int64_t rows = P;
+  for (int s = s0; s < s1; ++s) {
+    const int L = off[s + 1] - off[s];
+    int e = 0;
+    if (s > s0) {
+      const int Lp = off[s] - off[s - 1];
+      int lcp = 0;
+      while (lcp < L && lcp < Lp && tok[off[s - 1] + lcp] == tok[off[s] + lcp]) ++lcp;
+      e = std::max(0, std::min(lcp, Lp - 1));
+    }
+    rows += std::max(0, L - 1 - e);
+  }
+  return rows;
+}
+
+extern "C" int atspeed_score_items(atspeed_llama* m, const atspeed_fsm* fsm, int32_t n_users, const int32_t* const* prompt_ids,
+                                   const int32_t* prompt_len, const int32_t* start_nodes, const int32_t* seq_tokens, const int32_t* seq_offsets,
+                                   const int32_t* user_seq_offsets, const int32_t* adapter_slots, float* scores_out, int32_t* unknown_out,
+                                   int32_t* status_out, void* stream) {
+  ATS_REQUIRE(m && fsm && prompt_ids && prompt_len && start_nodes && seq_tokens && seq_offsets && user_seq_offsets && scores_out && status_out,
+              ATSPEED_ERR_INVALID, "score_items: null argument");
+  ATS_REQUIRE(fsm->dev.n_nodes > 0 && fsm->dev.vocab == m->cfg.vocab_size, ATSPEED_ERR_INVALID,
+              "score_items: needs a constraint automaton over the model's vocabulary (a mask-free search knows no items)");
+  ATS_REQUIRE(n_users >= 1 && n_users <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "score_items: %d users per call (1 .. %d)", n_users, ATS_MAX_SEGS);
+  ATS_REQUIRE(user_seq_offsets[0] == 0 && seq_offsets[0] == 0, ATSPEED_ERR_INVALID, "score_items: offsets must start at 0");
+  const atspeed_llama_config& c = m->cfg;
+  for (int u = 0; u < n_users; ++u) {
+    ATS_REQUIRE(user_seq_offsets[u + 1] > user_seq_offsets[u], ATSPEED_ERR_INVALID, "score_items: user %d has no sequence", u);
+    ATS_REQUIRE(prompt_ids[u] && prompt_len[u] >= 1, ATSPEED_ERR_INVALID, "score_items: user %d has no prompt", u);
+    ATS_REQUIRE(start_nodes[u] >= 0 && start_nodes[u] < fsm->dev.n_nodes, ATSPEED_ERR_INVALID, "score_items: start node of user %d out of range", u);
+    ATS_REQUIRE(!adapter_slots || m->slot_ok(adapter_slots[u]), ATSPEED_ERR_INVALID, "score_items: user %d names adapter slot %d, which is not occupied", u,
+                adapter_slots ? adapter_slots[u] : 0);
+  }
+  const int n_seq = user_seq_offsets[n_users];
+  for (int s = 0; s < n_seq; ++s) {
+    const int64_t len = (int64_t)seq_offsets[s + 1] - seq_offsets[s];
+    ATS_REQUIRE(len >= 1 && len <= ATSPEED_MAX_NEW_TOKENS, ATSPEED_ERR_INVALID, "score_items: sequence %d holds %lld tokens (1 .. %d)", s, (long long)len,
+                ATSPEED_MAX_NEW_TOKENS);
+  }
+  const int n_tok = seq_offsets[n_seq];
+  hipStream_t st = (hipStream_t)stream;
+  // per user: rows by the lcp rule, and whether they fit the model (found here, before anything is launched; the others are still scored)
+  std::vector<int> rows((size_t)n_users), status((size_t)n_users, ATSPEED_OK);
+  std::vector<size_t> row0((size_t)n_users + 1, 0);
+  for (int u = 0; u < n_users; ++u) {
+    const int64_t r = score_tree_rows(seq_tokens, seq_offsets, user_seq_offsets[u], user_seq_offsets[u + 1], prompt_len[u]);
+    const bool fits = r <= c.max_tokens && r <= c.max_slots && r - (prompt_len[u] - 1) <= c.max_logit_rows;
+    rows[u] = fits ? (int)r : 0;
+    if (!fits) status[u] = ATSPEED_ERR_CAPACITY;
+    row0[u + 1] = row0[u] + (size_t)rows[u];
+  }
+  // the model's score block: lists, per-user records and results, per-sequence tables, then the packed rows of every user
+  const int W = m->vis_words;
+  const size_t total_rows = row0[n_users];
+  auto up = [](size_t x) { return (x + 15) / 16 * 16; };
+  size_t o = 0;
+  const size_t o_users = o;  o += up(sizeof(ScoreTreeUser) * n_users);
+  const size_t o_vis = o;    o += up(sizeof(uint64_t) * std::max<size_t>(total_rows, 1) * W);
+  const size_t o_tok = o;    o += up(4 * (size_t)n_tok);
+  const size_t o_off = o;    o += up(4 * ((size_t)n_seq + 1));
+  const size_t o_pred = o;   o += up(4 * (size_t)n_seq * ATSPEED_MAX_NEW_TOKENS);
+  const size_t o_known = o;  o += up(4 * (size_t)n_seq);
+  const size_t o_base = o;   o += up(4 * (size_t)n_seq);
+  const size_t o_res = o;    o += up(4 * 3 * (size_t)n_users);
+  const size_t o_rows = o;   o += up(4 * 3 * std::max<size_t>(total_rows, 1));
+  if (o > m->score_bytes) {
+    ATS_HIP(hipStreamSynchronize(st));                                  // an earlier call's launches may still read the old block
+    hipFree(m->score_mem); m->score_mem = nullptr; m->score_bytes = 0;
+    g_ats_lazy_allocs++;
+    const size_t want = o + o / 4;
+    ATS_HIP(hipMalloc(&m->score_mem, want));
+    m->score_bytes = want;
+  }
+  char* blk = (char*)m->score_mem;
+  int32_t* d_tok = (int32_t*)(blk + o_tok);
+  int32_t* d_off = (int32_t*)(blk + o_off);
+  int32_t* d_pred = (int32_t*)(blk + o_pred);
+  int32_t* d_known = (int32_t*)(blk + o_known);
+  int32_t* d_base = (int32_t*)(blk + o_base);
+  int32_t* d_res = (int32_t*)(blk + o_res);                             // n_rows | unknown | status, [n_users] each
+  int32_t* d_rows = (int32_t*)(blk + o_rows);                           // ids | pos | slot, [total_rows] each
+  uint64_t* d_vis = (uint64_t*)(blk + o_vis);
+  std::vector<ScoreTreeUser> users((size_t)n_users);
+  for (int u = 0; u < n_users; ++u) {
+    ScoreTreeUser& su = users[u];
+    su.prompt = prompt_ids[u]; su.P = prompt_len[u]; su.start = start_nodes[u]; su.s0 = user_seq_offsets[u]; su.s1 = user_seq_offsets[u + 1];
+    su.cap = rows[u]; su.pad = 0;                                       // a user that does not fit writes no row at all
+    su.ids = d_rows + row0[u]; su.pos = d_rows + total_rows + row0[u]; su.slot = d_rows + 2 * total_rows + row0[u];
+    su.vis = d_vis + row0[u] * W;
+  }
+  ATS_HIP(hipMemcpyAsync(blk + o_users, users.data(), sizeof(ScoreTreeUser) * n_users, hipMemcpyHostToDevice, st));
+  ATS_HIP(hipMemcpyAsync(d_tok, seq_tokens, 4 * (size_t)n_tok, hipMemcpyHostToDevice, st));
+  ATS_HIP(hipMemcpyAsync(d_off, seq_offsets, 4 * ((size_t)n_seq + 1), hipMemcpyHostToDevice, st));
+  ScoreTreeBuild b{};
+  b.fsm = fsm->dev; b.users = (const ScoreTreeUser*)(blk + o_users); b.seq_tok = d_tok; b.seq_off = d_off; b.n_tok = n_tok;
+  b.pred_row = d_pred; b.known = d_known; b.n_rows = d_res; b.unknown = d_res + n_users; b.status = d_res + 2 * n_users; b.vis_words = W;
+  ATS_TRY(ats_score_tree_build(b, n_users, st));
+  // what the builder found: its row count must be the host's, and an unsorted list is refused -- before such a user's rows reach a forward
+  std::vector<int32_t> res(3 * (size_t)n_users);
+  ATS_HIP(hipMemcpyAsync(res.data(), d_res, 4 * res.size(), hipMemcpyDeviceToHost, st));
+  ATS_HIP(hipStreamSynchronize(st));
+  ats_stage_reset();
+  for (int u = 0; u < n_users; ++u) {
+    if (unknown_out) unknown_out[u] = res[n_users + u];
+    if (status[u] != ATSPEED_OK) continue;
+    if (res[2 * n_users + u] != ATSPEED_OK || res[u] != rows[u]) status[u] = ATSPEED_ERR_INVALID;
+  }
+  // one segment (and KV arena of the pool) per user that is left
+  SegTable t{};
+  std::vector<int32_t> base((size_t)n_seq, -(1 << 30));                 // a refused user's sequences name no row: -inf
+  int tot = 0, lrows = 0;
+  for (int u = 0; u < n_users; ++u) {
+    if (status[u] != ATSPEED_OK) continue;
+    while ((int)m->kv_pool.size() <= t.n) {
+      KvCache kv;
+      ATS_TRY(kv_create(m, &kv));
+      m->kv_pool.push_back(kv);
+    }
+    Seg& sg = t.seg[t.n];
+    sg.ids = users[u].ids; sg.pos = users[u].pos; sg.slot = users[u].slot; sg.vis = users[u].vis;
+    sg.kc = m->kv_pool[t.n].k; sg.vc = m->kv_pool[t.n].v;
+    sg.n_tok = rows[u]; sg.n_slots = rows[u]; sg.n_logit = rows[u] - (prompt_len[u] - 1);
+    sg.adapter = adapter_slots ? adapter_slots[u] : 0;
+    // segment row r's logits are row lrows + r - (P - 1) of the model's buffer: the prompt's last row is the segment's first logit row
+    for (int s = user_seq_offsets[u]; s < user_seq_offsets[u + 1]; ++s) base[s] = lrows - (prompt_len[u] - 1);
+    tot += sg.n_tok; lrows += sg.n_logit;
+    t.n++;
+  }
+  for (int u = 0; u < n_users; ++u) status_out[u] = status[u];
+  ATS_HIP(hipMemcpyAsync(d_base, base.data(), 4 * (size_t)n_seq, hipMemcpyHostToDevice, st));
+  if (t.n > 0) {
+    ATS_TRY(ats_seg_finish(t));
+    ATS_TRY(ensure_act(m, tot, lrows));
+    ATS_TRY(llama_forward_segs(m, t, nullptr, st, fsm->d_tile_store));
+  }
+  // with no user left there is no forward and no row: every score is -inf (n_rows = 1 keeps the kernel's range test meaningful)
+  const float* lg = t.n > 0 ? m->act->logits : (const float*)d_base;
+  const float* ls = t.n > 0 ? m->act->lse : (const float*)d_base;
+  ATS_TRY(ats_path_scores(lg, m->logits_ld, ls, std::max(lrows, 1), c.vocab_size, d_tok, d_off, d_pred, d_base, d_known, n_seq, scores_out, st));
+  ATS_HIP(hipStreamSynchronize(st));                                    // the host vectors staged above die with this call
+  ats_stage_reset();
+  return ATSPEED_OK;
 }
 
 // ---------------------------------------------------------------------------- segment-table kernels, one at a time (tests)

@@ -133,6 +133,28 @@ struct NodeMaskBuild {
 int ats_node_masks_build(const NodeMaskBuild& b, int n_users, hipStream_t st);
 inline const uint32_t* ats_mask_bits(const atspeed_node_masks* m, int user) { return m ? m->bits + (size_t)user * m->words : nullptr; }
 
+// Scoring candidates (include/atspeed_hip.h "scoring candidates"): the packed prompt + prefix-sharing tree of each user's item list, built on
+// the device by ats_score_tree_build, one workgroup per user.  A user's rows are rows [0, cap) of its own arrays; every write is bounded by cap.
+struct ScoreTreeUser {
+  const int32_t* prompt;  int32_t P, start, s0, s1;      // prompt tokens, start node, the user's sequences [s0, s1)
+  int32_t cap, pad;                                      // rows the arrays below hold (<= 64 * vis_words)
+  int32_t* ids;  int32_t* pos;  int32_t* slot;  uint64_t* vis;   // [cap], [cap][vis_words]
+};
+struct ScoreTreeBuild {
+  FsmDev fsm;
+  const ScoreTreeUser* users;                            // DEVICE array [n_users]
+  const int32_t* seq_tok;  const int32_t* seq_off;  int32_t n_tok;   // flat tokens, offsets [sequences + 1]; offsets outside [0, n_tok] are refused per user
+  int32_t* pred_row;                                     // [sequences][ATSPEED_MAX_NEW_TOKENS] row of the user's segment that predicts token d, -1 past the end
+  int32_t* known;                                        // [sequences] 1 = the automaton knows the sequence
+  int32_t* n_rows;  int32_t* unknown;  int32_t* status;  // [n_users]: prompt + tree rows, unknown sequences, ATSPEED_OK / _ERR_INVALID / _ERR_CAPACITY
+  int vis_words;
+};
+int ats_score_tree_build(const ScoreTreeBuild& b, int n_users, hipStream_t st);
+// scores[s] = sum over d of (logits[row][tok_d] - lse[row]), row = seq_base[s] + pred_row[s][d] (seq_base NULL: 0), fp32, d ascending; -inf for a
+// sequence that is not known or that names a row outside [0, n_rows) or a token outside [0, vocab)
+int ats_path_scores(const float* logits, int ld, const float* lse, int n_rows, int vocab, const int32_t* seq_tok, const int32_t* seq_off,
+                    const int32_t* pred_row, const int32_t* seq_base, const int32_t* known, int n_seq, float* scores, hipStream_t st);
+
 struct TokBuf {       // inputs of a forward: one row per token
   int32_t* ids;
   int32_t* pos;

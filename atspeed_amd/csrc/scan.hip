@@ -1163,6 +1163,164 @@ __global__ __launch_bounds__(kMaskThreads) void node_masks_kernel(NodeMaskBuild 
   }
 }
 
+// ---------------------------------------------------------------------------- scoring candidates: prompt + prefix-sharing tree of an item list
+// One workgroup per user (semantics: include/atspeed_hip.h "scoring candidates"; the scoring rule is beamSD.py:58-64).  The user's sequences
+// are strictly ascending, so the sequences that share a prefix are neighbours and a prefix's row belongs to the first of them that goes on
+// beyond it.  With lcp(s) = the tokens sequence s shares with its predecessor and e(s) = min(lcp(s), len(s - 1) - 1) -- the predecessor owns
+// no row for its LAST token, so a sequence that continues its predecessor owns that depth itself --, token d of s gets a row iff
+// e(s) <= d < len(s) - 1, rows are numbered P, P + 1, ... in (sequence, depth) order, and the row of prefix depth d < e(s) is that of the nearest
+// s' < s with e(s') <= d.  The sequences are taken in passes of kTreeThreads; `carry` hands the owner of every depth to the next pass.  Rows are
+// shared by PREFIX, never by automaton node: two prefixes that reach one node (a position-set automaton has one node per depth) see
+// different tokens.  Every row's arrays are written whole by the thread that owns it, every write is bounded by the user's `cap`.
+constexpr int kTreeThreads = 256;
+__device__ __forceinline__ uint64_t low_bits_word(int n, int w) {          // word w of the bitset [0, n)
+  const int k = n - 64 * w;
+  return k >= 64 ? ~0ull : k <= 0 ? 0ull : (1ull << k) - 1ull;
+}
+__global__ __launch_bounds__(kTreeThreads) void score_tree_kernel(ScoreTreeBuild b) {
+  __shared__ int sh_e[kTreeThreads], sh_base[kTreeThreads], sh_len[kTreeThreads], sh_scan[kTreeThreads];
+  __shared__ int carry[LMAX];
+  __shared__ int total, n_unknown, bad;
+  const ScoreTreeUser u = b.users[blockIdx.x];
+  const int tid = threadIdx.x, P = u.P, W = b.vis_words, cap = u.cap;
+  if (tid == 0) { total = P; n_unknown = 0; bad = 0; }
+  if (tid < LMAX) carry[tid] = -1;
+  for (int r = tid; r < P && r < cap; r += kTreeThreads) {             // the prompt: causal
+    u.ids[r] = u.prompt[r]; u.pos[r] = r; u.slot[r] = r;
+    uint64_t* v = u.vis + (size_t)r * W;
+    for (int w = 0; w < W; ++w) v[w] = low_bits_word(r + 1, w);
+  }
+  __syncthreads();
+  auto seq_span = [&](int s, int* t0) {                                  // a sequence's tokens; 0 = offsets the token array does not hold
+    const int a = b.seq_off[s], z = b.seq_off[s + 1];
+    *t0 = a;
+    return (a >= 0 && z > a && z - a <= LMAX && z <= b.n_tok) ? z - a : 0;
+  };
+  for (int c0 = u.s0; c0 < u.s1; c0 += kTreeThreads) {
+    const int s = c0 + tid;
+    const bool active = s < u.s1;
+    int tk[LMAX], row[LMAX];
+    int L = 0, e = 0, t0 = 0;
+    if (active) {
+      L = seq_span(s, &t0);
+      if (L == 0) atomicOr(&bad, 1);
+#pragma unroll
+      for (int d = 0; d < LMAX; ++d) tk[d] = d < L ? b.seq_tok[t0 + d] : -1;
+      if (s > u.s0 && L > 0) {
+        int p0 = 0;
+        const int Lp = seq_span(s - 1, &p0);
+        int lcp = 0;
+#pragma unroll
+        for (int d = 0; d < LMAX; ++d) if (lcp == d && d < L && d < Lp && b.seq_tok[p0 + d] == tk[d]) lcp = d + 1;
+        // strictly ascending: the predecessor is a proper prefix, or the first token that differs is larger here
+        bool ok = Lp > 0 && (lcp == Lp ? L > Lp : lcp < L);
+        if (ok && lcp < Lp) {
+          int cur = 0;
+#pragma unroll
+          for (int d = 0; d < LMAX; ++d) if (d == lcp) cur = tk[d];
+          ok = b.seq_tok[p0 + lcp] < cur;
+        }
+        if (!ok) atomicOr(&bad, 1);
+        e = max(0, min(lcp, Lp - 1));
+      }
+      int node = u.start, d = 0;
+      for (; d < L; ++d) {
+        int cur = 0;
+#pragma unroll
+        for (int i = 0; i < LMAX; ++i) if (i == d) cur = tk[i];
+        const int ed = find_edge(b.fsm, node, cur);
+        if (ed < 0 || edge_blocked(b.fsm, ed)) break;
+        node = b.fsm.nxt[ed];
+      }
+      const bool known = L > 0 && d == L;
+      b.known[s] = known ? 1 : 0;
+      if (!known) atomicAdd(&n_unknown, 1);
+    }
+    const int cnt = active ? max(0, L - 1 - e) : 0;
+    sh_e[tid] = e; sh_len[tid] = L; sh_scan[tid] = cnt;
+    __syncthreads();
+    for (int off = 1; off < kTreeThreads; off <<= 1) {                  // inclusive prefix sum of the passes' new rows
+      const int v = tid >= off ? sh_scan[tid - off] : 0;
+      __syncthreads();
+      sh_scan[tid] += v;
+      __syncthreads();
+    }
+    const int base = total + sh_scan[tid] - cnt;
+    sh_base[tid] = base;
+    __syncthreads();
+    if (active) {
+      // the row of every prefix depth: own rows from e on, below it the nearest earlier sequence that is new at the depth
+      int m = min(e, L - 1);
+#pragma unroll
+      for (int d = 0; d < LMAX; ++d) row[d] = (d >= e && d < L - 1) ? base + d - e : -1;
+      for (int j = tid - 1; m > 0 && j >= 0; --j) {
+        const int ej = sh_e[j];
+        if (ej < m) {
+#pragma unroll
+          for (int d = 0; d < LMAX; ++d) if (d >= ej && d < m) row[d] = sh_base[j] + d - ej;
+          m = ej;
+        }
+      }
+#pragma unroll
+      for (int d = 0; d < LMAX; ++d) if (d < m) row[d] = carry[d];
+#pragma unroll
+      for (int d = 0; d < LMAX; ++d) {
+        const int r = row[d];
+        if (d >= e && d < L - 1 && r >= 0 && r < cap) {
+          u.ids[r] = tk[d]; u.pos[r] = P + d; u.slot[r] = r;
+          uint64_t* v = u.vis + (size_t)r * W;
+          for (int w = 0; w < W; ++w) {
+            uint64_t word = low_bits_word(P, w);
+#pragma unroll
+            for (int a = 0; a < LMAX; ++a) {
+              const int ra = row[a];
+              if (a <= d && ra >= 0 && ra < cap && (ra >> 6) == w) word |= 1ull << (ra & 63);
+            }
+            v[w] = word;
+          }
+        }
+      }
+      int32_t* pr = b.pred_row + (size_t)s * LMAX;
+#pragma unroll
+      for (int d = 0; d < LMAX; ++d) pr[d] = d >= L ? -1 : d == 0 ? P - 1 : row[d - 1];
+    }
+    __syncthreads();
+    // hand over: the owner of each depth as the next pass's first sequence sees it, and the rows so far
+    const int n_act = min(kTreeThreads, u.s1 - c0);
+    if (tid < LMAX) {
+      for (int j = n_act - 1; j >= 0; --j)
+        if (sh_e[j] <= tid) { carry[tid] = tid < sh_len[j] - 1 ? sh_base[j] + tid - sh_e[j] : -1; break; }
+    }
+    if (tid == n_act - 1) total = base + cnt;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    b.n_rows[blockIdx.x] = total;
+    b.unknown[blockIdx.x] = n_unknown;
+    b.status[blockIdx.x] = bad ? ATSPEED_ERR_INVALID : total > cap ? ATSPEED_ERR_CAPACITY : ATSPEED_OK;
+  }
+}
+
+// One thread per candidate: the sum of its tokens' log-probs in token order, each term formed by the beam expand's own rule (`tempered`,
+// temperature 1) and added onto the running sum in fp32 as expand_candidates adds a beam's score.
+__global__ void path_scores_kernel(const float* __restrict__ logits, int ld, const float* __restrict__ lse, int n_rows, int vocab,
+                                   const int32_t* __restrict__ seq_tok, const int32_t* __restrict__ seq_off, const int32_t* __restrict__ pred_row,
+                                   const int32_t* __restrict__ seq_base, const int32_t* __restrict__ known, int n_seq, float* __restrict__ scores) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_seq) return;
+  const int t0 = seq_off[s], L = seq_off[s + 1] - t0;
+  bool ok = known[s] != 0 && L >= 1 && L <= LMAX;
+  const long long base = seq_base ? seq_base[s] : 0;
+  float sum = 0.f;
+  for (int d = 0; ok && d < L; ++d) {
+    const long long r = base + pred_row[(size_t)s * LMAX + d];
+    const int tok = seq_tok[t0 + d];
+    if (r < 0 || r >= n_rows || tok < 0 || tok >= vocab) { ok = false; break; }
+    sum = sum + tempered(logits[(size_t)r * ld + tok], lse[r], 1.0f);
+  }
+  scores[s] = ok ? sum : -INFINITY;
+}
+
 }  // namespace
 
 int ats_lse_rows(const float* logits, int n_rows, int vocab, int ld, float* lse, hipStream_t st) {
@@ -1267,6 +1425,64 @@ extern "C" int atspeed_node_masks_read(const atspeed_node_masks* m, int32_t user
   ATS_REQUIRE(n_words == m->words, ATSPEED_ERR_INVALID, "node_masks_read: a user's bitset holds %d words, not %d", m->words, n_words);
   ATS_HIP(hipMemcpy(words_out, ats_mask_bits(m, user), sizeof(uint32_t) * m->words, hipMemcpyDeviceToHost));
   return ATSPEED_OK;
+}
+
+// ---- scoring candidates (include/atspeed_hip.h): the tree builder and the path-score kernel
+int ats_score_tree_build(const ScoreTreeBuild& b, int n_users, hipStream_t st) {
+  if (n_users <= 0) return ATSPEED_OK;
+  score_tree_kernel<<<n_users, kTreeThreads, 0, st>>>(b);
+  ATS_LAUNCH_CHECK();
+  return ATSPEED_OK;
+}
+
+int ats_path_scores(const float* logits, int ld, const float* lse, int n_rows, int vocab, const int32_t* seq_tok, const int32_t* seq_off,
+                    const int32_t* pred_row, const int32_t* seq_base, const int32_t* known, int n_seq, float* scores, hipStream_t st) {
+  if (n_seq <= 0) return ATSPEED_OK;
+  path_scores_kernel<<<(n_seq + 255) / 256, 256, 0, st>>>(logits, ld, lse, n_rows, vocab, seq_tok, seq_off, pred_row, seq_base, known, n_seq, scores);
+  ATS_LAUNCH_CHECK();
+  return ATSPEED_OK;
+}
+
+extern "C" int atspeed_score_tree_build(const atspeed_fsm* fsm, int32_t n_users, const int32_t* const* prompt_ids, const int32_t* prompt_len,
+                                        const int32_t* start_nodes, const int32_t* seq_tokens, int32_t n_seq_tokens, const int32_t* seq_offsets,
+                                        const int32_t* user_seq_offsets, int32_t max_slots, const int32_t* row_offsets, int32_t* ids, int32_t* pos,
+                                        int32_t* slots, uint64_t* vis, int32_t* pred_row, int32_t* known, int32_t* n_rows, int32_t* unknown,
+                                        int32_t* status, void* stream) {
+  ATS_REQUIRE(fsm && prompt_ids && prompt_len && start_nodes && seq_tokens && seq_offsets && user_seq_offsets && row_offsets && ids && pos && slots &&
+              vis && pred_row && known && n_rows && unknown && status, ATSPEED_ERR_INVALID, "score_tree_build: null argument");
+  ATS_REQUIRE(fsm->dev.n_nodes > 0, ATSPEED_ERR_INVALID, "score_tree_build: a mask-free automaton knows no items");
+  ATS_REQUIRE(n_users >= 1 && n_users <= ATS_MAX_SEGS, ATSPEED_ERR_CAPACITY, "score_tree_build: %d users per call (1 .. %d)", n_users, ATS_MAX_SEGS);
+  ATS_REQUIRE(max_slots >= 64 && max_slots % 64 == 0 && n_seq_tokens >= 1, ATSPEED_ERR_INVALID, "score_tree_build: max_slots %d must be a positive multiple of 64, and there must be tokens", max_slots);
+  ATS_REQUIRE(user_seq_offsets[0] == 0 && row_offsets[0] == 0, ATSPEED_ERR_INVALID, "score_tree_build: offsets must start at 0");
+  std::vector<ScoreTreeUser> users((size_t)n_users);
+  const int W = max_slots / 64;
+  for (int u = 0; u < n_users; ++u) {
+    ATS_REQUIRE(user_seq_offsets[u + 1] > user_seq_offsets[u], ATSPEED_ERR_INVALID, "score_tree_build: user %d has no sequence", u);
+    ATS_REQUIRE(row_offsets[u + 1] >= row_offsets[u], ATSPEED_ERR_INVALID, "score_tree_build: row offsets not monotone at user %d", u);
+    ATS_REQUIRE(prompt_ids[u] && prompt_len[u] >= 1, ATSPEED_ERR_INVALID, "score_tree_build: user %d has no prompt", u);
+    ATS_REQUIRE(start_nodes[u] >= 0 && start_nodes[u] < fsm->dev.n_nodes, ATSPEED_ERR_INVALID, "score_tree_build: start node of user %d out of range", u);
+    ScoreTreeUser& su = users[u];
+    const size_t r0 = (size_t)row_offsets[u];
+    su.prompt = prompt_ids[u]; su.P = prompt_len[u]; su.start = start_nodes[u]; su.s0 = user_seq_offsets[u]; su.s1 = user_seq_offsets[u + 1];
+    su.cap = std::min(row_offsets[u + 1] - row_offsets[u], max_slots); su.pad = 0;       // a row past max_slots has no visibility bit
+    su.ids = ids + r0; su.pos = pos + r0; su.slot = slots + r0; su.vis = vis + r0 * W;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ScoreTreeBuild b{};
+  const void* d_users = nullptr;
+  ATS_TRY(ats_stage(users.data(), users.size() * sizeof(ScoreTreeUser), &d_users, st));
+  b.fsm = fsm->dev; b.users = (const ScoreTreeUser*)d_users; b.seq_tok = seq_tokens; b.seq_off = seq_offsets; b.n_tok = n_seq_tokens;
+  b.pred_row = pred_row; b.known = known; b.n_rows = n_rows; b.unknown = unknown; b.status = status; b.vis_words = W;
+  return ats_score_tree_build(b, n_users, st);
+}
+
+extern "C" int atspeed_path_scores(const float* logits, int32_t ld, const float* lse, int32_t n_rows, int32_t vocab, const int32_t* seq_tokens,
+                                   const int32_t* seq_offsets, const int32_t* pred_row, const int32_t* seq_base, const int32_t* known, int32_t n_seqs,
+                                   float* scores_out, void* stream) {
+  ATS_REQUIRE(logits && lse && seq_tokens && seq_offsets && pred_row && known && scores_out, ATSPEED_ERR_INVALID, "path_scores: null argument");
+  ATS_REQUIRE(n_rows >= 1 && vocab >= 1 && ld >= vocab && n_seqs >= 0, ATSPEED_ERR_INVALID, "path_scores: bad shape (rows %d, vocab %d, ld %d, sequences %d)",
+              n_rows, vocab, ld, n_seqs);
+  return ats_path_scores(logits, ld, lse, n_rows, vocab, seq_tokens, seq_offsets, pred_row, seq_base, known, n_seqs, scores_out, (hipStream_t)stream);
 }
 
 // the filter of `user` on a by-value copy of the automaton, for the bare kernel entries

@@ -233,6 +233,7 @@ class InferenceResult:
     wall_s: float = 0.0
     prefixes_built: int = 0          # share_prefix: PromptPrefix objects the run built (one per distinct shared opening)
     prefix_users: int = 0            # ... and the users decoded behind one
+    label_scores: List[float] = field(default_factory=list)         # score_labels: the target's log-prob of each user's label item (nan: no label in the index)
 
     def metrics(self, index: ItemIndex, topN: Sequence[int] = (1, 5, 10, 20)) -> Dict[str, List[float]]:
         # items that share a code tuple are one item to the generator: compare by code tuple
@@ -314,7 +315,7 @@ def cached_prefix_for(ids: Sequence[int], built: Iterable[tuple]) -> tuple:
 def run_inference(target, draft, data: SeqRecTestData, gamma: int = 4, max_new_tokens: int = 4, L: int = 0, R: Optional[int] = None,
                   users_per_batch: int = 128, prefix_allowed_tokens_fn=None, tokenizer=None, baseline: bool = False,
                   device=None, decoder: str = "bssd", stream_lanes: Optional[int] = None, exclude_history: bool = False,
-                  share_prefix: bool = False) -> InferenceResult:
+                  share_prefix: bool = False, score_labels: bool = False) -> InferenceResult:
     """Users [L, R) of the test set through beam-SD (inference.py:123-124,162-187), `users_per_batch` at a time in lock step.
     `baseline=True` also runs `target_generate` per user and records its time and the speed-up columns.
     `decoder="beam"`: the same users through the plain constrained beam search of the target (`target_generate_batch`, beamSD.py:544-595) --
@@ -326,9 +327,12 @@ def run_inference(target, draft, data: SeqRecTestData, gamma: int = 4, max_new_t
     prompt shows): each user's items go to the decoder as `exclude_items`.  Needs the strict item trie (`data.strict_trie_fn()`).
     `share_prefix=True`: the tokens every prompt of a batch opens with (`common_prefix`: the template's header) are prefilled once, as a
     `PromptPrefix`, and copied into the users' KV arenas; each user prefills the rest of its prompt only.  Prefixes are kept by their tokens
-    across the batches of the call and a batch reuses the longest built one its prompts open with, so a whole split builds one.  Same predictions; `prefixes_built` / `prefix_users` of the result count."""
+    across the batches of the call and a batch reuses the longest built one its prompts open with, so a whole split builds one.  Same predictions; `prefixes_built` / `prefix_users` of the result count.
+    `score_labels=True`: the target's exact log-prob of every user's label item (its first label's code tokens) under the call's mask, one
+    `score_items_batch` forward per batch after the decode and outside its clock, in `label_scores` (-inf: the mask does not know the item; nan: the user has no
+    label the index knows).  With it a label's rank beyond K can be evaluated."""
     import torch
-    from .beamSD import BSSD_batch, target_generate, target_generate_batch
+    from .beamSD import BSSD_batch, score_items_batch, target_generate, target_generate_batch
     from .model import PromptPrefix
     if decoder not in ("bssd", "beam"):
         raise ValueError(f"decoder must be 'bssd' or 'beam', not {decoder!r}")
@@ -391,6 +395,15 @@ def run_inference(target, draft, data: SeqRecTestData, gamma: int = 4, max_new_t
                              "ave_accept_tokens": o["ave_accept_tokens"]})
     torch.cuda.synchronize(dev)
     res.wall_s = time.perf_counter() - t0
+    if score_labels:
+        codes = [next((list(data.index.item_codes[i]) for i in u.labels if i in data.index.item_codes), None) for u in sel]
+        res.label_scores = [float("nan")] * len(sel)
+        have = [i for i, c in enumerate(codes) if c is not None]
+        for lo in range(0, len(have), users_per_batch):
+            part = have[lo:lo + users_per_batch]
+            got = score_items_batch(target, [prompts[i] for i in part], [[codes[i]] for i in part], fn)
+            for i, s in zip(part, got):
+                res.label_scores[i] = float(s[0])
     if baseline:
         for row, pr in zip(res.rows, prompts):
             tg = target_generate(target, pr, max_new_tokens, prefix_allowed_tokens_fn=fn)

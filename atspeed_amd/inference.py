@@ -48,6 +48,9 @@ def parse(argv=None):
     ap.add_argument("--share_prefix", action="store_true",
                     help="prefill the tokens every prompt of a batch opens with (the template's header) once and copy their K / V into each "
                          "user's cache (PromptPrefix); users prefill the rest of their prompt only.  Same items")
+    ap.add_argument("--score_labels", action="store_true",
+                    help="also score every user's label item with the target (score_items_batch: its exact log-prob under the mask, whether or not "
+                         "the decode found it) and write uid, label and log-prob per user to label_scores_*.csv")
     ap.add_argument("--decoder", choices=("bssd", "beam"), default="bssd",
                     help="bssd = beam speculative decoding (the reference's method); beam = plain constrained beam search of the target in lock "
                          "step: identical items, and on MI355X the faster of the two once a batch of users makes the target forward MFMA-bound "
@@ -162,7 +165,8 @@ def main(argv=None):
     for beam in ast.literal_eval(args.run_beam_sizes):          # the reference eval()s this flag (inference.py:151); a literal list is all it needs
         tgt, drf = load_models(args, data.index.vocab_size, beam, dev, max_prompt)
         res = run_inference(tgt, drf, data, args.gamma, 4, args.L + lo, args.L + hi, args.users_per_batch, fn, tok, args.baseline, dev, args.decoder,
-                            stream_lanes=args.stream_lanes, exclude_history=args.exclude_history, share_prefix=args.share_prefix)
+                            stream_lanes=args.stream_lanes, exclude_history=args.exclude_history, share_prefix=args.share_prefix,
+                            score_labels=args.score_labels)
         c = res.counters()
         per_rank = all_gather_counters(Counters(len(res.rows), int(sum(r["n_run"] for r in res.rows)),
                                                 int(sum(r["total_accept_steps"] for r in res.rows)), int(res.wall_s * 1e9)), dev)
@@ -177,6 +181,12 @@ def main(argv=None):
             name = f"timing_mean_B{beam}-{args.draft_beam_size}_{args.L}-{stop_r}_seed{args.seed}.json"
             with open(os.path.join(args.output_dir, args.dataset, name), "w") as f:
                 json.dump(row, f, indent=1)
+            if args.score_labels:             # rank 0's users, like timing_mean_rank0 (the file name carries the shard's own L-R)
+                name = f"label_scores_B{beam}-{args.draft_beam_size}_{args.L + lo}-{args.L + hi}_seed{args.seed}.csv"
+                with open(os.path.join(args.output_dir, args.dataset, name), "w") as f:
+                    f.write("uid,label,label_logprob\n")
+                    for uid, lab, s in zip(res.uids, res.labels, res.label_scores):
+                        f.write(f"{uid},{lab[0] if lab else ''},{s!r}\n")
             print(json.dumps(row))
         release_decoders(tgt, drf)        # per-lane KV arenas of this beam size (the cache only holds weak references to the models)
         del tgt, drf, res

@@ -632,6 +632,59 @@ int atspeed_kv_rows_scatter(const void* store_k_dev, const void* store_v_dev, vo
 int atspeed_kv_rows_gather(void* store_k_dev, void* store_v_dev, const void* k_arena_dev, const void* v_arena_dev, int32_t len, int32_t layers,
                            int32_t row_bytes, int32_t max_slots, void* stream);
 
+/* ------------------------------------------------------------------ scoring candidates: exact target log-probs of item lists
+ * "What does the target give each of these N items?" -- the second stage of retrieve-then-rank, and a label's rank beyond K.  The score of an
+ * item is exactly what a constrained beam search reports for it (beamSD.py:58-64: log_softmax over the FULL vocabulary, then the mask, then
+ * the beam's running score): the sum over its tokens of logit - LSE(full vocabulary) at the row that predicts the token, added in token
+ * order in fp32.  No reference counterpart: the reference scores sequences by repeating the prompt per sequence
+ * (generate_teacher_data.py:225-232).
+ *
+ * Lists use atspeed_node_masks_create's format: user u owns sequences [user_seq_offsets[u], user_seq_offsets[u + 1]), sequence s is
+ * seq_tokens[seq_offsets[s] .. seq_offsets[s + 1]), 1 .. ATSPEED_MAX_NEW_TOKENS tokens, lengths may differ.  A user's sequences must be
+ * STRICTLY ASCENDING lexicographically (sorted, no duplicates; a proper prefix sorts before its extensions): the builder checks the order.
+ *
+ * Row layout of a user with a prompt of P tokens (one segment of a batched forward, slots private to the user): rows 0 .. P - 1 are the
+ * prompt, causal (pos = slot = row, row r sees slots [0, r]).  Then the tree: with lcp(s) = the tokens s shares with its predecessor and
+ * e(s) = min(lcp(s), len(s - 1) - 1) (0 for the first sequence), token d of sequence s gets a row of its own iff e(s) <= d < len(s) - 1 -- an
+ * item's last token needs none, nothing is predicted from it, which is also why a sequence that continues its predecessor owns the
+ * predecessor's last depth itself.  Rows are numbered P, P + 1, ... in (sequence, depth) order; a tree row has ids = the token, pos = P + d,
+ * slot = row and sees slots [0, P), the rows of its prefix and itself.  The row that PREDICTS token d is the prompt's last row for d = 0, else
+ * the row of prefix depth d - 1: the sequence's own, or that of the nearest earlier sequence that is new at that depth.  Rows are shared by
+ * prefix, never by automaton node.  Each sequence is walked through the automaton from the user's start node; one with a token that has no
+ * edge is UNKNOWN: it keeps its rows (the layout is a function of the token lists alone), is flagged and counted per user, and scores -inf.
+ *
+ * atspeed_score_items: all arrays are HOST pointers except prompt_ids_dev[u] (device, [prompt_len[u]]) and scores_out_dev (device,
+ *   [sequences] fp32, in list order).  Stages the lists, runs the builder, ONE segmented forward over all users (user = one segment and one KV
+ *   arena of the pool atspeed_llama_forward_batch uses; adapter_slots[u] = the user's resident adapter, NULL = none; the decoder's lm_head
+ *   form: normaliser from the epilogue, only the automaton's logit tiles stored) and the path-score kernel.  status_out[u]: ATSPEED_OK;
+ *   ATSPEED_ERR_CAPACITY when prompt + tree exceed max_tokens or max_slots, or the rows from the prompt's last on exceed max_logit_rows (found
+ *   on the host before anything is launched); ATSPEED_ERR_INVALID for a list that is not strictly ascending or whose row count the builder
+ *   and the host disagree on.  A refused user takes no part in the forward and its scores are -inf; the other users are scored.
+ *   unknown_out[u] (may be NULL) counts its unknown sequences.  The model keeps one scratch block for the lists and rows, grown on demand as
+ *   the arena pool is; the call synchronises `stream` (once after the builder, once at its end).
+ * atspeed_score_tree_build: the builder alone on caller-owned DEVICE buffers (prompt_ids, prompt_len, start_nodes, user_seq_offsets and
+ *   row_offsets are HOST arrays; prompt_ids[u] is a device pointer).  User u's rows are rows [row_offsets[u], row_offsets[u + 1]) of ids / pos /
+ *   slots (int32) and vis_bits ([row][max_slots / 64] uint64); no row at or past a user's range, nor past max_slots, is written.
+ *   pred_row_dev [sequences][ATSPEED_MAX_NEW_TOKENS]: the user's row that predicts token d, -1 past the sequence's end; known_dev [sequences]
+ *   1 / 0; n_rows_dev / unknown_dev / status_dev [n_users]: prompt + tree rows (whether they fit or not), unknown sequences, and ATSPEED_OK,
+ *   ATSPEED_ERR_INVALID (order violated, or offsets outside [0, n_seq_tokens] / a length outside 1 .. ATSPEED_MAX_NEW_TOKENS) or
+ *   ATSPEED_ERR_CAPACITY (more rows than the user's range or max_slots hold; the rows that fit are written).
+ * atspeed_path_scores: scores_out[s] = sum over d of (logits[r][tok_d] - lse[r]), r = seq_base[s] + pred_row[s][d] (seq_base NULL = 0), on
+ *   caller-owned device buffers; logits rows are ld floats apart.  -inf for a sequence whose known flag is 0, or that names a row outside
+ *   [0, n_rows) or a token outside [0, vocab). */
+int atspeed_score_items(atspeed_llama* model, const atspeed_fsm* fsm, int32_t n_users, const int32_t* const* prompt_ids_dev,
+                        const int32_t* prompt_len, const int32_t* start_nodes, const int32_t* seq_tokens, const int32_t* seq_offsets,
+                        const int32_t* user_seq_offsets, const int32_t* adapter_slots /* may be NULL */, float* scores_out_dev,
+                        int32_t* unknown_out /* [n_users], may be NULL */, int32_t* status_out /* [n_users] */, void* stream);
+int atspeed_score_tree_build(const atspeed_fsm* fsm, int32_t n_users, const int32_t* const* prompt_ids_dev, const int32_t* prompt_len,
+                             const int32_t* start_nodes, const int32_t* seq_tokens_dev, int32_t n_seq_tokens, const int32_t* seq_offsets_dev,
+                             const int32_t* user_seq_offsets, int32_t max_slots, const int32_t* row_offsets, int32_t* ids_dev, int32_t* pos_dev,
+                             int32_t* slots_dev, uint64_t* vis_bits_dev, int32_t* pred_row_dev, int32_t* known_dev, int32_t* n_rows_dev,
+                             int32_t* unknown_dev, int32_t* status_dev, void* stream);
+int atspeed_path_scores(const float* logits_dev, int32_t ld, const float* lse_dev, int32_t n_rows, int32_t vocab, const int32_t* seq_tokens_dev,
+                        const int32_t* seq_offsets_dev, const int32_t* pred_row_dev, const int32_t* seq_base_dev /* may be NULL */,
+                        const int32_t* known_dev, int32_t n_seqs, float* scores_out_dev, void* stream);
+
 /* ------------------------------------------------------------------ low-level ops (tests, benches)
  * C[M,N] = A[M,K] * W[N,K]^T on MFMA; epilogue: 0 store (dtype), 1 fp32 store, 2 residual add into
  * C (dtype), 3 SwiGLU over interleaved gate/up column groups (C is [M, N/2]).
