@@ -77,6 +77,25 @@ class SessionUserPrefix(C.Structure):
 
 # every symbol include/atspeed_hip.h declares: (restype, argtypes)
 _P, _I, _F, _SZ, _U32, _U64 = C.c_void_p, C.c_int32, C.c_float, C.c_size_t, C.c_uint32, C.c_uint64
+
+
+class WalkArgs(C.Structure):
+    """atspeed_walk_args: one verify walk as device pointers and ints (atspeed_verify_walk)"""
+    _fields_ = [("struct_size", _SZ),
+                ("blk_score", _P * (MAX_GAMMA + 1)), ("blk_node", _P * (MAX_GAMMA + 1)), ("blk_flat", _P * (MAX_GAMMA + 1)),
+                ("blk_seq", _P * (MAX_GAMMA + 1)),
+                ("nb", _I), ("dl", _I), ("k", _I), ("dk", _I), ("gen_len0", _I), ("ld", _I), ("logits", _P), ("lse", _P),
+                ("blk_row0", _I * (MAX_GAMMA + 1)), ("blocks_ready", _I), ("fsm", _P), ("masks", _P), ("user", _I),
+                ("vocab", _I), ("n_row_cand", _I), ("n0", _I), ("row_cand", _P),
+                ("cur_ids", _P), ("cur_pos", _P), ("cur_slot", _P), ("cur_vis", _P),
+                ("next_ids", _P), ("next_pos", _P), ("next_slot", _P), ("next_vis", _P),
+                ("dnext_ids", _P), ("dnext_pos", _P), ("dnext_slot", _P), ("dnext_vis", _P),
+                ("res_score", _P), ("res_node", _P), ("res_seq", _P), ("res_parent", _P), ("res_tok", _P), ("res_flat", _P),
+                ("mailbox", _P), ("vis_words", _I), ("sample", _I), ("temperature", _F), ("seed", _U32), ("round", _I), ("pad", _I),
+                ("dtab_score", _P * MAX_GAMMA), ("dtab_off", _P * MAX_GAMMA), ("dtab_lse", _P * MAX_GAMMA),
+                ("cutoff", _P), ("vtrace", _P)]
+
+
 # ATSPEED_SEGMENTS of the header: n, six host arrays of per-segment device pointers, three host arrays of counts
 _SEGS = [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P]
 SIGNATURES = {
@@ -153,6 +172,8 @@ SIGNATURES = {
     "atspeed_session_submit_masked": (C.c_int, [_P, _P, _I, _I, _U32, _P, _P, C.POINTER(GenStats), _P, _I, C.POINTER(C.c_int64)]),
     "atspeed_beam_expand_prune_masked": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "atspeed_warp_cutoffs_masked": (C.c_int, [_P, _I, _P, _I, _P, _P, _F, _I, _F, _I, _P, _P, _I, _P]),
+    "atspeed_beam_sample_step": (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _F, _U32, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "atspeed_verify_walk": (C.c_int, [C.POINTER(WalkArgs), _P]),
     "atspeed_score_items": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "atspeed_score_tree_build": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "atspeed_path_scores": (C.c_int, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),

@@ -1665,6 +1665,92 @@ extern "C" int atspeed_beam_expand_prune(const float* logits, int32_t ld, const 
                                           nullptr, 0, stream);
 }
 
+// ---- the sampled step and the verify walks alone (tests): the argument blocks a round builds, from plain pointers.  Host code only
+extern "C" int atspeed_beam_sample_step(const float* logits, int32_t ld, const float* lse, const float* beam_score, const int32_t* beam_node,
+                                        int32_t n_rows, const atspeed_fsm* fsm, const atspeed_node_masks* masks, int32_t user, int32_t k,
+                                        float temperature, uint32_t rng_sub, const float* cutoffs, int32_t filter_ids, float* out_score,
+                                        int32_t* out_parent, int32_t* out_token, int32_t* out_node, int32_t* out_flat, float* tab_score,
+                                        int32_t* tab_off, float* tab_lse, int32_t* mailbox, void* stream) {
+  ATS_REQUIRE(logits && lse && beam_score && beam_node && fsm && out_score && out_parent && out_token && out_node && out_flat,
+              ATSPEED_ERR_INVALID, "beam_sample_step: null argument");
+  ATS_REQUIRE((tab_score && tab_off && tab_lse) || (!tab_score && !tab_off && !tab_lse), ATSPEED_ERR_INVALID,
+              "beam_sample_step: the table is tab_score, tab_off and tab_lse together, or none of them");
+  ATS_REQUIRE(ld > 0 && temperature > 0.f, ATSPEED_ERR_INVALID, "beam_sample_step: ld %d / temperature %g out of range", ld, (double)temperature);
+  ATS_REQUIRE(fsm->dev.n_nodes > 0, ATSPEED_ERR_INVALID, "beam_sample_step: a sampled step needs an automaton with nodes");
+  ATS_REQUIRE(k >= 1 && k <= MAXB && n_rows >= 1 && n_rows <= MAXB, ATSPEED_ERR_CAPACITY, "beam_sample_step: k=%d / rows=%d out of [1,%d]", k, n_rows, MAXB);
+  BeamStepArgs a{};
+  a.src.score = const_cast<float*>(beam_score);
+  a.src.node = const_cast<int32_t*>(beam_node);
+  a.n_src = n_rows; a.gen_len = 0;
+  a.logits = logits; a.ld = ld; a.lse = lse;
+  ATS_TRY(masked_fsm(fsm, masks, user, "beam_sample_step", &a.fsm));
+  a.k = k;
+  a.dst.score = out_score; a.dst.parent = out_parent; a.dst.tok = out_token; a.dst.node = out_node; a.dst.flat = out_flat;
+  a.emit = 0; a.filter_ids = filter_ids ? 1 : 0; a.vis_words = 0;
+  a.mail = reinterpret_cast<Mailbox*>(mailbox);
+  a.sample = 1; a.temperature = temperature; a.rng_sub = rng_sub;
+  a.tab_score = tab_score; a.tab_off = tab_off; a.tab_lse = tab_lse;
+  a.cutoff = cutoffs;
+  return ats_beam_step(a, (hipStream_t)stream);
+}
+
+static_assert(sizeof(Mailbox) == 4 * sizeof(int32_t), "atspeed_walk_args::mailbox is the four words of a Mailbox");
+
+extern "C" int atspeed_verify_walk(const atspeed_walk_args* w, void* stream) {
+  ATS_REQUIRE(w && w->struct_size == sizeof(atspeed_walk_args), ATSPEED_ERR_INVALID, "verify_walk: null argument block, or one of another size");
+  ATS_REQUIRE(w->k >= 1 && w->k <= MAXB && w->dk >= 1 && w->dk <= MAXB && w->nb >= 1 && w->nb <= MAXB, ATSPEED_ERR_CAPACITY,
+              "verify_walk: k=%d / dk=%d / nb=%d out of [1,%d]", w->k, w->dk, w->nb, MAXB);
+  ATS_REQUIRE(w->dl >= 0 && w->dl <= ATSPEED_MAX_GAMMA, ATSPEED_ERR_CAPACITY, "verify_walk: %d draft blocks (0 .. %d)", w->dl, ATSPEED_MAX_GAMMA);
+  ATS_REQUIRE(w->gen_len0 >= 0 && w->n0 >= w->nb && w->ld > 0 && w->vis_words >= 1 && w->blocks_ready >= 0 && w->blocks_ready <= w->dl + 1,
+              ATSPEED_ERR_INVALID, "verify_walk: gen_len0 %d / n0 %d / ld %d / vis_words %d / blocks_ready %d out of range", w->gen_len0, w->n0, w->ld,
+              w->vis_words, w->blocks_ready);
+  ATS_REQUIRE(w->gen_len0 + w->dl <= LMAX, ATSPEED_ERR_CAPACITY, "verify_walk: %d tokens + %d blocks exceed the %d a suffix holds", w->gen_len0, w->dl, LMAX);
+  ATS_REQUIRE(w->logits && w->lse && w->cur_ids && w->cur_pos && w->cur_slot && w->cur_vis && w->next_ids && w->next_pos && w->next_slot &&
+              w->next_vis && w->dnext_ids && w->dnext_pos && w->dnext_slot && w->dnext_vis && w->res_score && w->res_parent && w->res_tok &&
+              w->res_flat && w->mailbox, ATSPEED_ERR_INVALID, "verify_walk: null argument");
+  for (int i = 0; i <= w->dl; ++i) {
+    ATS_REQUIRE(w->blk_score[i] && w->blk_node[i] && (i == 0 || w->blk_flat[i]), ATSPEED_ERR_INVALID, "verify_walk: block %d lacks score, node or flat", i);
+    ATS_REQUIRE(w->blk_row0[i] >= 0, ATSPEED_ERR_INVALID, "verify_walk: block %d starts at row %d", i, w->blk_row0[i]);
+  }
+  VerifyArgs a{};
+  if (w->fsm) {
+    ATS_TRY(masked_fsm(w->fsm, w->masks, w->user, "verify_walk", &a.fsm));
+  } else {
+    ATS_REQUIRE(!w->masks && w->vocab > 0 && (int64_t)MAXB * w->vocab < (int64_t)0x7fffffff, ATSPEED_ERR_INVALID, "verify_walk: no automaton and no usable vocabulary");
+    a.fsm = FsmDev{nullptr, nullptr, nullptr, 0, 0, w->vocab, 0, -1, nullptr};
+  }
+  if (a.fsm.n_nodes == 0)
+    ATS_REQUIRE(!w->sample && w->row_cand && w->n_row_cand >= 1 && w->n_row_cand <= MAXB, ATSPEED_ERR_INVALID,
+                "verify_walk: the mask-free search is greedy and needs row_cand with 1 .. %d entries per row", MAXB);
+  if (w->sample) {
+    ATS_REQUIRE(w->temperature > 0.f, ATSPEED_ERR_INVALID, "verify_walk: temperature %g", (double)w->temperature);
+    for (int i = 0; i < w->dl; ++i)
+      ATS_REQUIRE(w->dtab_score[i] && w->dtab_off[i] && w->dtab_lse[i], ATSPEED_ERR_INVALID, "verify_walk: draft step %d has no table", i);
+  }
+  for (int i = 0; i <= w->dl; ++i) {
+    a.blk[i].score = const_cast<float*>(w->blk_score[i]); a.blk[i].node = const_cast<int32_t*>(w->blk_node[i]);
+    a.blk[i].flat = const_cast<int32_t*>(w->blk_flat[i]); a.blk[i].seq = const_cast<int32_t*>(w->blk_seq[i]);
+    a.blk_row0[i] = w->blk_row0[i];
+  }
+  a.nb = w->nb; a.dl = w->dl; a.k = w->k; a.dk = w->dk; a.gen_len0 = w->gen_len0;
+  a.logits = w->logits; a.ld = w->ld; a.lse = w->lse; a.blocks_ready = w->blocks_ready;
+  a.cur = TokBuf{const_cast<int32_t*>(w->cur_ids), const_cast<int32_t*>(w->cur_pos), const_cast<int32_t*>(w->cur_slot), const_cast<uint64_t*>(w->cur_vis)};
+  a.n0 = w->n0;
+  a.next = TokBuf{w->next_ids, w->next_pos, w->next_slot, w->next_vis};
+  a.dnext = TokBuf{w->dnext_ids, w->dnext_pos, w->dnext_slot, w->dnext_vis};
+  a.vis_words = w->vis_words;
+  a.res.score = w->res_score; a.res.node = w->res_node; a.res.seq = w->res_seq; a.res.parent = w->res_parent; a.res.tok = w->res_tok; a.res.flat = w->res_flat;
+  a.mail = reinterpret_cast<Mailbox*>(w->mailbox);
+  a.row_cand = w->row_cand; a.n_row_cand = w->n_row_cand;
+  a.sample = w->sample ? 1 : 0; a.temperature = w->temperature; a.seed = w->seed; a.round = w->round;
+  for (int i = 0; i < w->dl; ++i) { a.dtab_score[i] = w->dtab_score[i]; a.dtab_off[i] = w->dtab_off[i]; a.dtab_lse[i] = w->dtab_lse[i]; }
+  a.cutoff = w->cutoff; a.vtrace = w->vtrace;
+  hipStream_t st = (hipStream_t)stream;
+  const void* dev = nullptr;
+  ATS_TRY(ats_stage(&a, sizeof(a), &dev, st));
+  return ats_verify_walk_multi((const VerifyArgs*)dev, 1, st);
+}
+
 extern "C" int atspeed_row_topk(const float* scores, int32_t n_rows, int32_t vocab, int32_t ld, int32_t k, int32_t* out_tokens, void* stream) {
   ATS_REQUIRE(scores && out_tokens && vocab > 0 && ld >= vocab && n_rows >= 0, ATSPEED_ERR_INVALID, "row_topk: bad arguments");
   return ats_row_topk(scores, n_rows, vocab, ld, k, out_tokens, (hipStream_t)stream);

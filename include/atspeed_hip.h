@@ -543,6 +543,74 @@ int atspeed_warp_cutoffs_masked(const float* logits_dev, int32_t ld, const float
                                 const int32_t* nodes_dev, float temperature, int32_t top_k, float top_p, int32_t min_tokens_to_keep,
                                 float* cutoffs_out_dev, const atspeed_node_masks* masks, int32_t user, void* stream);
 
+/* The sampled beam step alone (tests): one do_sample expand of n_rows beams, i.e. the step kernel with the sampling branch that
+ * atspeed_beam_expand_prune never takes.  k picks are drawn without replacement with probability proportional to
+ * exp((logit - lse) / temperature + beam score) over the children of every live beam's node (a child under its row's cutoff or behind a
+ * blocked edge has probability 0), by the counter-based generator: rng_sub is what ats_rng_sub gives for (seed, purpose, round, step,
+ * model).  filter_ids != 0 applies the automaton's post-top-k id filter (atspeed_fsm_set_id_filter): dropped picks leave the block, the
+ * survivors keep their order and "no beam" (flat -1, score -inf) fills the end.  Outputs hold k entries each.  Optional, all NULL or none:
+ * tab_score_dev [candidates in expand order], tab_off_dev [n_rows + 1], tab_lse_dev [1] -- the whole distribution as the verify walk reads
+ * it.  Optional cutoffs_dev [n_rows] (atspeed_warp_cutoffs), optional mailbox_dev [4] int32 {n_matches, status, n_valid, pad}: n_valid is
+ * written, status only when the step has one to report.  Refused before any launch: a NULL required pointer, ld <= 0, temperature <= 0, a
+ * mask-free automaton (ATSPEED_ERR_INVALID); k or n_rows outside [1, ATSPEED_MAX_BEAMS] (ATSPEED_ERR_CAPACITY). */
+int atspeed_beam_sample_step(const float* logits_dev, int32_t ld, const float* lse_dev, const float* beam_score_dev,
+                             const int32_t* beam_node_dev, int32_t n_rows, const atspeed_fsm* fsm, const atspeed_node_masks* masks,
+                             int32_t user, int32_t k, float temperature, uint32_t rng_sub, const float* cutoffs_dev, int32_t filter_ids,
+                             float* out_score_dev, int32_t* out_parent_dev, int32_t* out_token_dev, int32_t* out_node_dev,
+                             int32_t* out_flat_dev, float* tab_score_dev, int32_t* tab_off_dev, float* tab_lse_dev, int32_t* mailbox_dev,
+                             void* stream);
+
+/* One verify walk alone (tests), greedy or sampled: what a round hands its walk kernel, as device pointers and ints.
+ *   Blocks: block 0 = the nb round beams, block i = the dk beams of draft step i, i <= dl.  score / node of blocks 0 .. dl and flat of
+ *   blocks 1 .. dl are required; seq (block i: [rows][ATSPEED_MAX_NEW_TOKENS]) may be NULL (the suffixes then count as zeros).
+ *   Logits: block i's first row of logits / lse / row_cand / cutoff is blk_row0[i] (a packed round: 0, nb, nb + dk, ...); blocks_ready =
+ *   how many blocks have rows (greedy walk only: a walk that needs block i >= blocks_ready writes mailbox[0] = -1 and, if it has one,
+ *   a status, and nothing else but the trace of the steps it took).
+ *   Automaton: fsm (+ optional masks, user), or fsm = NULL for the mask-free search over `vocab` tokens (greedy only), whose candidates are
+ *   the n_row_cand first entries of row_cand_dev [logit row][ATSPEED_MAX_BEAMS].
+ *   cur_*: the packed target inputs of the round, n0 rows of round input then dk rows per draft block; next_* (k rows), dnext_* (dk + k
+ *   rows, written only when every block was accepted and dl > 0), res_* (k entries; node / seq may be NULL), vis rows of vis_words words.
+ *   mailbox_dev [4] int32 {n_matches, status, n_valid, pad}.  sample != 0: temperature, seed, round and the draft's tables dtab_*[i],
+ *   i < dl, as atspeed_beam_sample_step writes them.  vtrace_dev (greedy, optional): [dl + 1][3][ATSPEED_MAX_BEAMS] words.
+ * Refused before any launch: struct_size other than sizeof(atspeed_walk_args), a NULL required pointer, ld <= 0, vis_words < 1, n0 < nb,
+ * gen_len0 < 0, blocks_ready outside [0, dl + 1], a sampled walk without automaton, tables or a positive temperature (ATSPEED_ERR_INVALID);
+ * k, dk, nb outside [1, ATSPEED_MAX_BEAMS], dl outside [0, ATSPEED_MAX_GAMMA], gen_len0 + dl > ATSPEED_MAX_NEW_TOKENS (ATSPEED_ERR_CAPACITY). */
+typedef struct atspeed_walk_args {
+  size_t struct_size;
+  const float* blk_score[ATSPEED_MAX_GAMMA + 1];
+  const int32_t* blk_node[ATSPEED_MAX_GAMMA + 1];
+  const int32_t* blk_flat[ATSPEED_MAX_GAMMA + 1];
+  const int32_t* blk_seq[ATSPEED_MAX_GAMMA + 1];
+  int32_t nb, dl, k, dk, gen_len0;
+  int32_t ld;
+  const float* logits;
+  const float* lse;
+  int32_t blk_row0[ATSPEED_MAX_GAMMA + 1];
+  int32_t blocks_ready;
+  const atspeed_fsm* fsm;
+  const atspeed_node_masks* masks;
+  int32_t user;
+  int32_t vocab, n_row_cand, n0;
+  const int32_t* row_cand;
+  const int32_t* cur_ids; const int32_t* cur_pos; const int32_t* cur_slot; const uint64_t* cur_vis;
+  int32_t* next_ids; int32_t* next_pos; int32_t* next_slot; uint64_t* next_vis;
+  int32_t* dnext_ids; int32_t* dnext_pos; int32_t* dnext_slot; uint64_t* dnext_vis;
+  float* res_score; int32_t* res_node; int32_t* res_seq; int32_t* res_parent; int32_t* res_tok; int32_t* res_flat;
+  int32_t* mailbox;
+  int32_t vis_words;
+  int32_t sample;
+  float temperature;
+  uint32_t seed;
+  int32_t round;
+  int32_t pad;
+  const float* dtab_score[ATSPEED_MAX_GAMMA];
+  const int32_t* dtab_off[ATSPEED_MAX_GAMMA];
+  const float* dtab_lse[ATSPEED_MAX_GAMMA];
+  const float* cutoff;
+  int32_t* vtrace;
+} atspeed_walk_args;
+int atspeed_verify_walk(const atspeed_walk_args* args, void* stream);
+
 int atspeed_target_generate(atspeed_decoder* d, const int32_t* prompt_ids_dev, int32_t prompt_len,
                             const atspeed_fsm* fsm, int32_t start_node, int32_t max_new_tokens, int32_t k,
                             int32_t* out_tokens_dev, float* out_scores_dev, atspeed_gen_stats* stats_host,
